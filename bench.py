@@ -1,8 +1,12 @@
 """bench.py — utterances/sec of a full train step (forward + loss + backward + gradient all-reduce + clip +
-Adam) of the seq2seq ASR hot path on N MI355X GPUs, plus the dominant kernel's roofline fraction, the per-layer
-encoder gate-GEMM fractions and a CPU baseline (the oracle port) timed on the host cores of the same box.
+Adam) of the seq2seq ASR hot path on N MI355X GPUs.  A plain run sets up, warms up, times --steps steps and prints
+the result line; with --full it also measures the other arithmetics and workloads, the dominant kernel's roofline
+fraction, the per-layer encoder gate-GEMM fractions and a CPU baseline (the oracle port) on the host cores of the same box.
 
     python bench.py --gpus 1 --steps 10 --warmup 3                                  # cfg-2, the headline line
+    python bench.py --full                                                           # ... and everything else
+    python bench.py --dump-outputs DIR                                               # + loss, weights, gradients of the last step,
+                                                                                     #   which starts from the set-up state
     python bench.py --config cfg5            |  --config cfg1  |  --frames 400       # the other BASELINE.json shapes
     python bench.py --scaling strong --global-batch 256                              # fixed total work over N GPUs
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -501,6 +505,63 @@ def make_solver(model_cfg, batch_per_gpu, frames, workdir, **overrides):
     return solver
 
 
+DUMP_SAMPLE = 1 << 18                          # elements kept of a larger tensor by --dump-outputs
+
+
+class StepStart(object):
+    """--dump-outputs: the state a train step computes from besides the batch - weights, gradient buffer, Adam moments and
+    counters, the torch / numpy random streams (dropout seeds, teacher-forcing draws) - taken after set-up and put back in
+    front of the LAST timed step.  Every step before it moves the weights, and the product's sums meet in fp32 atomics, so
+    after a few steps two runs would hand the last step weights that differ by more than rounding; put back, the last step
+    starts from the same inputs in every run, and its outputs differ by the rounding of that one step at most.  restore()
+    enqueues device copies on the current stream (behind the step before, no host wait): ~0.4 GB of copies inside the timed
+    region, once."""
+
+    def __init__(self, opt):
+        self.opt = opt
+        self.saved = [t.clone() for t in self._tensors()]
+        self.counters = (opt.t, opt._applies, opt._norm_taken)
+        self.rng = (torch.get_rng_state(), np.random.get_state())
+
+    def _tensors(self):
+        o = self.opt
+        return [o.buf.flat_p, o.buf.flat_g, o.m, o.v, o.gnorm_pair] + ([o.vmax] if o.vmax is not None else [])
+
+    def restore(self):
+        for dst, src in zip(self._tensors(), self.saved):
+            dst.copy_(src, non_blocking=True)
+        self.opt.t, self.opt._applies, self.opt._norm_taken = self.counters
+        torch.set_rng_state(self.rng[0])
+        np.random.set_state(self.rng[1])
+
+
+def dump_outputs(outdir, model, loss):
+    """--dump-outputs: what a caller of the timed Solver.sup_train_one_iteration holds after the last timed step (which starts
+    from the set-up state, StepStart) - its loss (float64), every parameter after the update (param.<name>.npy) and the
+    gradient it was taken from (grad.<name>.npy), as float32.  A tensor of more than DUMP_SAMPLE elements is kept as a fixed
+    sample of DUMP_SAMPLE of its flat elements (ascending indices drawn from a RandomState seeded by the tensor's name), so
+    cfg-2 writes ~40 MB instead of 137."""
+    import zlib
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "loss.npy"), np.array([loss], dtype=np.float64))
+    total = 8
+    for name, p in model.named_parameters():
+        n = p.numel()
+        idx = None
+        if n > DUMP_SAMPLE:
+            rs = np.random.RandomState(zlib.crc32(name.encode()))
+            idx = torch.from_numpy(np.sort(rs.choice(n, DUMP_SAMPLE, replace=False))).to(p.device)
+        for kind, t in (("param", p.detach()), ("grad", p.grad)):
+            if t is None:
+                continue
+            flat = t.reshape(-1) if idx is None else t.reshape(-1)[idx]
+            arr = flat.float().cpu().numpy()
+            np.save(os.path.join(outdir, "%s.%s.npy" % (kind, name)), arr if idx is not None else arr.reshape(tuple(t.shape)))
+            total += arr.nbytes
+    assert total <= 64 << 20, "--dump-outputs wrote %d bytes" % total
+    note("outputs of the last timed step: %.1f MB in %s" % (total / 2.0 ** 20, outdir))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -520,7 +581,15 @@ def main():
     ap.add_argument("--no-also", action="store_true", help="skip the extra timings under the other arithmetics")
     ap.add_argument("--epoch-only", type=int, default=0, metavar="STEPS",
                     help="only the epoch workload (Solver.sup_train_one_epoch through the input pipeline), for profiling")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline: the other arithmetics (also_*), the other workloads, the dominant "
+                         "kernel's roofline, the encoder gate GEMMs, the CPU baseline and, N > 1, the all-reduce alone and the "
+                         "overlapped exchange (the --no-* options leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss, parameters and gradients of the last timed step to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and args.epoch_only:
+        ap.error("--dump-outputs writes the outputs of the timed train step; --epoch-only has none")
     # stdout carries ONE line, the JSON record.  Libraries write there too - RCCL prints a five-line version banner from C when a
     # communicator comes up, on every rank - so file descriptor 1 is pointed at stderr for the whole run and the record goes
     # out through a private duplicate of the original descriptor at the end.
@@ -552,6 +621,7 @@ def main():
     else:
         n_global = (args.batch_per_gpu or spec["batch"]) * world
     torch.manual_seed(1000 + rank)                     # per-rank dropout streams; weights below are shared
+    np.random.seed(1000 + rank)                        # (the teacher-forcing draws: identical runs for --dump-outputs)
     tmp = tempfile.mkdtemp(prefix="asr_bench_r%d_" % rank)
     if args.epoch_only:
         assert world == 1
@@ -581,12 +651,14 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed(n, fn=None):
+    def timed(n, fn=None, before_last=None):
         """n steps bracketed by barrier + synchronize on both sides; wall seconds, max over ranks."""
         fn = fn or step
         fence()
         t0 = time.perf_counter()
-        for _ in range(n):
+        for i in range(n):
+            if before_last is not None and i == n - 1:
+                before_last()
             fn()
         solver.flush()                                # the host record (loss + abort latch) of the last step too
         fence()
@@ -621,6 +693,8 @@ def main():
     # repeat under data parallelism): ASR_BENCH_INJECT_ABORT=warmup|timed sets the sticky latch from the host once, as an
     # aborting persistent kernel would (on the last rank only).
     inject = os.environ.get("ASR_BENCH_INJECT_ABORT", "")
+    start = StepStart(solver.gen_opt) if args.dump_outputs else None      # the last timed step starts from here
+    restore = start.restore if start is not None else None
     for i in range(args.warmup):
         if inject == "warmup" and i == 0 and rank == world - 1:
             hb.persist_scratch(dev)
@@ -636,7 +710,7 @@ def main():
         hb.persist_scratch(dev)
         hb.persist_abort_flag(dev).fill_(1)
     with contextlib.redirect_stdout(sys.stderr):
-        el = timed(args.steps)
+        el = timed(args.steps, before_last=restore)
     retimed = False
     if persist_before and not hb.USE_PERSIST:
         # a persistent kernel aborted inside the timed steps and the Solver repeated that step on the per-step kernels
@@ -644,9 +718,11 @@ def main():
         note("persistent kernels were left during the timed steps (abort handled by the Solver): timing again on the per-step kernels")
         hb.LAUNCHES.clear()
         with contextlib.redirect_stdout(sys.stderr):
-            el = timed(args.steps)
+            el = timed(args.steps, before_last=restore)
         retimed = True
     final_loss = float(last["loss"])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, solver.model, final_loss)
     paths = {k: v // max(1, args.steps) for k, v in sorted(hb.LAUNCHES.items())}
     # which stage of the fallback ladder this rank is on after the timed steps
     stage = ("persistent kernels" if hb.USE_PERSIST else
@@ -668,7 +744,7 @@ def main():
     # the gradient all-reduce alone (68.7 MB at cfg-2), outside the timed region
     allreduce_ms = None
     opt = solver.gen_opt
-    if world > 1:
+    if world > 1 and args.full:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         dist.all_reduce(opt.buf.flat_g)
         fence()
@@ -686,7 +762,7 @@ def main():
         note("rank %d: all-reduce of the flat gradient buffer alone %.3f ms" % (rank, allreduce_ms))
     # the same steps under the other arithmetics (labelled sub-objects; never the headline)
     also = {}
-    if not args.no_also:
+    if args.full and not args.no_also:
         for other in ("bf16x3", "f32"):
             if other == args.arith:
                 continue
@@ -698,7 +774,7 @@ def main():
     # N > 1: the bucketed exchange issued from inside the backward pass (opt-in in the product: config key dp_overlap /
     # ASR_DP_OVERLAP=1), as a labelled sub-object next to the default (one collective)
     also_overlapped = None
-    if world > 1 and not args.no_also:
+    if world > 1 and args.full and not args.no_also:
         opt.buf.enable_overlap()
         with contextlib.redirect_stdout(sys.stderr):
             step()
@@ -725,7 +801,7 @@ def main():
             "dtype": {"bf16x6": "f32 (fp32-equivalent bf16x6 products)", "f32": "f32", "bf16x3": "f32 (bf16x3 products: 16-bit significands)"}[args.arith],
             "data": "synthetic", "arithmetic": ARITH_TEXT[args.arith],
             "config": {"workload": "%s: batch %d per GPU, 80x%d synthetic fbank, RAGGED lengths U[0.6T, T] (mean %.0f frames per "
-                                   "utterance, longest %d; the fixed-length reading is workloads.cfg2_fixed_T), V=%d, L+1=%d, "
+                                   "utterance, longest %d; the fixed-length reading is --full's workloads.cfg2_fixed_T), V=%d, L+1=%d, "
                                    "dropout %.2f, Adam(amsgrad)+clip 5; %s"
                                    % (args.config, b_local, t_frames, float(np.mean(lens)), int(max(lens)), cfg["output_dim"],
                                       info["olength"], cfg["dropout_rate"], spec["name"]),
@@ -757,10 +833,10 @@ def main():
         if "f32" in also:
             out["also_f32_mfma"] = also["f32"]
         note("%.1f utt/s, %.2f ms/step" % (value, ms))
-    # ---- the other workloads of BASELINE.json through the same Solver methods (N = 1 only; ~2 s each)
+    # ---- --full: the other workloads of BASELINE.json through the same Solver methods (N = 1 only; ~2 s each)
     del solver, opt
     torch.cuda.empty_cache()
-    if world == 1 and not args.no_workloads and rank == 0:
+    if world == 1 and args.full and not args.no_workloads and rank == 0:
         out["workloads"] = other_workloads(dev, tmp, args.config, t_frames)
         if args.config == "cfg2" and t_frames == spec["frames"] and args.scaling == "weak" and not args.batch_per_gpu:
             note("workload epoch")
@@ -768,14 +844,15 @@ def main():
             ep["vs_resident_batch"] = ep["ms_per_step"] / out["ms_per_step"]
             out["workloads"]["epoch"] = ep
     if rank == 0:
-        note("measuring dominant kernel")
-        lens_local = [lens[i] for i in parallel.shard_indices(n_global, rank, world)]
-        out["roofline"] = kernel_roofline(dev, cfg, b_local, t_frames, info["olength"], lens_local)
-        if not args.no_layer_gemms:
-            out["encoder_gate_gemm"] = encoder_gate_gemms(dev, cfg, b_local, t_frames, lens_local)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(cfg, xs, lens, ys, args.config + " T=%d" % t_frames,
-                                               3 if args.config == "cfg1" else 1)
+        if args.full:
+            note("measuring dominant kernel")
+            lens_local = [lens[i] for i in parallel.shard_indices(n_global, rank, world)]
+            out["roofline"] = kernel_roofline(dev, cfg, b_local, t_frames, info["olength"], lens_local)
+            if not args.no_layer_gemms:
+                out["encoder_gate_gemm"] = encoder_gate_gemms(dev, cfg, b_local, t_frames, lens_local)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(cfg, xs, lens, ys, args.config + " T=%d" % t_frames,
+                                                   3 if args.config == "cfg1" else 1)
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if world > 1:
         dist.barrier()
