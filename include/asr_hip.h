@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define ASR_ABI_VERSION 5
+#define ASR_ABI_VERSION 6
 
 #define ASR_E_ARG    (-1)  /* null pointer / non-positive size */
 #define ASR_E_SHAPE  (-2)  /* size not supported by the kernel (see each function) */
@@ -589,6 +589,59 @@ int asr_dec_feedback_fwd(int B, int V, int E, int DO, const float* x, int64_t ld
                          float* xd_emb_next, const float* mask, int64_t ldm, asr_stream_t stream);
 int asr_dec_feedback_bwd(int B, int V, int E, int DO, const float* demb, float* gtop, int64_t ldg, const float* probs,
                          const float* emb, const float* w_out, float scaling, float* dlog, asr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Beam search between two decoder steps (Decoder.recognize_beams, model.py:369-406 - a stub in the reference that this
+ * library completes; the semantics are DESIGN 4.8's).  Per step the caller runs asr_dec_step_fwd and
+ * asr_gemm_skinny_f32 on the B*K beam rows (row b*K + k), then asr_beam_select_f32 and asr_beam_reorder_f32; after the
+ * last step asr_beam_backtrack.  Every buffer is caller-owned device memory; K > ASR_BEAM_KMAX, V < 2 or an eos outside
+ * [0, V) returns ASR_E_SHAPE.
+ *   asr_beam_select_f32   step t (0 <= t < L), one workgroup per utterance that is not done: logp = log_softmax(logits)
+ *                         of each live beam (score > -inf); candidates score[k] + logp[v] ranked by score, then by the
+ *                         lower flat index k*V + v; of the first 2K, an <EOS> at rank < K is finished (step t, source
+ *                         beam k, length t+1), other <EOS> are skipped, the rest fill the live slots j in rank order
+ *                         (tok_hist[t][b][j], bp_hist[t][b][j] = k, scores[b][j]); empty slots get <EOS>, 0, -inf.  At
+ *                         t = L-1 the live beams are finished as they stand unless K are finished already.  An utterance
+ *                         with K finished hypotheses (or at t = L-1, or with no live beam left) sets done[b] and adds 1
+ *                         to *ndone; done utterances are not touched again.
+ *   asr_beam_reorder_f32  step t (`logits` is not read): for every beam row of an utterance that is not done, row
+ *                         b*K+j of the destination slot gathers row b*K + bp_hist[t][b][j] of the source slot - x[:, 0:D+O] (z, ctx), the cell
+ *                         state and the attention weights - and x[:, D+O:] = emb[tok_hist[t][b][j]].  A gather: source
+ *                         and destination are different buffers (ASR_E_ARG otherwise).
+ *   asr_beam_backtrack    ranks each utterance's finished hypotheses by score / length^length_penalty (ties: the one
+ *                         finished first) and writes the first K as tokens [B][K][L] (padded with <EOS>), scores [B][K]
+ *                         (the ranking key; -inf for a rank without a hypothesis) and lengths [B][K] (counting <EOS>).
+ * ------------------------------------------------------------------------------------- */
+#define ASR_BEAM_KMAX 16
+#define ASR_BEAM_FCAP 48    /* finished entries per utterance the caller provides (at most 2K - 1 are ever written) */
+typedef struct {
+  int B, K, V, L;         /* utterances, beam width (1..16), vocabulary, max_dec_timesteps */
+  int eos;
+  const float* logits;    /* [B*K][V] this step's output-layer logits */
+  float* scores;          /* [B][K] running scores: 0 for beam 0 and -inf for the others at the start */
+  int32_t* tok_hist;      /* [L][B][K] token of live slot j after step t */
+  int32_t* bp_hist;       /* [L][B][K] its predecessor slot at step t-1 */
+  int32_t* fin;           /* [B][ASR_BEAM_FCAP][4] finished hypotheses: (step, slot, length, ends with <EOS>) */
+  float* fin_score;       /* [B][ASR_BEAM_FCAP] their scores (sum of log-probabilities) */
+  int32_t* nfin;          /* [B] number of finished hypotheses, 0 at the start */
+  int32_t* done;          /* [B] 0 at the start */
+  int32_t* ndone;         /* one word: number of done utterances, 0 at the start (the host polls it) */
+} asr_beam_t;
+typedef struct {
+  int D, O, E, Tp;
+  int64_t ldx;            /* row stride of x_src / x_dst (>= D + O + E) */
+  const float* x_src;     /* [B*K][ldx] step output slot: z, ctx */
+  float* x_dst;           /* [B*K][ldx] next step's input slot */
+  const float* c_src;     /* [B*K][D] cell state */
+  float* c_dst;
+  const float* w_src;     /* [B*K][Tp] attention weights */
+  float* w_dst;
+  const float* emb;       /* [V][E] embedding */
+} asr_beam_state_t;
+int asr_beam_select_f32(const asr_beam_t* p, int t, asr_stream_t stream);
+int asr_beam_reorder_f32(const asr_beam_t* p, int t, const asr_beam_state_t* s, asr_stream_t stream);
+int asr_beam_backtrack(const asr_beam_t* p, float length_penalty, int32_t* tokens, float* scores, int32_t* lengths,
+                       asr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Optimiser on a flat fp32 buffer (solver.py:152-153,384-385: clip_grad_norm_ + Adam(amsgrad,

@@ -1,0 +1,279 @@
+// beam.hip — beam-search decoding between two decoder steps (Decoder.recognize_beams, model.py:369-406; the reference
+// leaves the method unfinished, the semantics are DESIGN 4.8's).  Per step the host runs asr_dec_step_fwd and the skinny
+// output GEMM on B*K rows, then:
+//   beam_select   one workgroup per utterance: log-softmax of each live beam's logits, the top 2K of the K*V candidates
+//                 (score desc, flat index k*V+v asc on ties), the fairseq walk over them (<EOS> at rank < K finishes a
+//                 hypothesis, other <EOS> are skipped, non-<EOS> fill the live slots in rank order);
+//   beam_reorder  one workgroup per beam row: the next step's input slot gathers its predecessor's z, ctx, cell state
+//                 and attention weights (out of place: source and destination are different step slots) and the
+//                 embedding of its new token;
+// and once at the end
+//   beam_backtrack  one workgroup per utterance: rank the finished hypotheses, follow the backpointers into token rows.
+#include <float.h>
+#include <limits.h>
+#include "common.h"
+
+namespace {
+
+constexpr int BEAM_NT = 256;               // threads of the select / reorder / backtrack workgroups
+constexpr int BEAM_WAVES = BEAM_NT / 64;
+constexpr int BEAM_KMAX = ASR_BEAM_KMAX;
+constexpr int BEAM_FCAP = ASR_BEAM_FCAP;   // finished entries per utterance (< 2K can be held: include/asr_hip.h)
+
+// candidate order: higher score first, lower flat index on ties
+__device__ __forceinline__ bool beam_better(float av, int ai, float bv, int bi) {
+  return av > bv || (av == bv && ai < bi);
+}
+
+__device__ __forceinline__ float beam_wave_max(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+  return v;
+}
+
+// M: the per-thread candidate list length, a power of two >= 2K
+template <int M>
+__global__ __launch_bounds__(BEAM_NT) void beam_select_kernel(asr_beam_t p, int t) {
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int K = p.K, V = p.V, B = p.B;
+  if (p.done[b]) return;                                   // finished utterances are left untouched
+  __shared__ float s_score[BEAM_KMAX], s_max[BEAM_KMAX], s_lsum[BEAM_KMAX];
+  __shared__ float red_v[2][BEAM_WAVES];
+  __shared__ int red_i[2][BEAM_WAVES];
+  __shared__ float top_v[2 * BEAM_KMAX];
+  __shared__ int top_i[2 * BEAM_KMAX];
+  __shared__ int s_ntop;
+  if (tid < K) s_score[tid] = p.scores[(int64_t)b * K + tid];
+  __syncthreads();
+
+  // log-softmax statistics of every live beam's row: max and log(sum exp(x - max)), one wave per row
+  const float* lg = p.logits + (int64_t)b * K * V;
+  for (int k = wave; k < K; k += BEAM_WAVES) {
+    if (s_score[k] == -INFINITY) continue;                 // wave-uniform
+    const float* row = lg + (int64_t)k * V;
+    float m = -INFINITY;
+    for (int v = lane; v < V; v += 64) m = fmaxf(m, row[v]);
+    m = beam_wave_max(m);
+    float s = 0.f;
+    for (int v = lane; v < V; v += 64) s += expf(row[v] - m);
+    s = wave_sum(s);
+    if (lane == 0) { s_max[k] = m; s_lsum[k] = logf(s); }
+  }
+  __syncthreads();
+
+  // every thread keeps its best M candidates, sorted, in registers (fully unrolled: no scratch); it visits flat indices
+  // in increasing order, so an equal score never displaces an entry
+  float lv[M];
+  int li[M];
+#pragma unroll
+  for (int j = 0; j < M; ++j) { lv[j] = -INFINITY; li[j] = INT_MAX; }
+  for (int k = 0; k < K; ++k) {
+    const float sc = s_score[k];
+    if (sc == -INFINITY) continue;
+    const float m = s_max[k], ls = s_lsum[k];
+    const float* row = lg + (int64_t)k * V;
+    for (int v = tid; v < V; v += BEAM_NT) {
+      float c = sc + ((row[v] - m) - ls);
+      if (c > lv[M - 1]) {                                 // -inf and NaN never enter
+        int ci = k * V + v;
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+          const bool sw = beam_better(c, ci, lv[j], li[j]);
+          const float tv = lv[j];
+          const int ti = li[j];
+          lv[j] = sw ? c : tv;
+          li[j] = sw ? ci : ti;
+          c = sw ? tv : c;
+          ci = sw ? ti : ci;
+        }
+      }
+    }
+  }
+
+  // merge: 2K rounds of a workgroup arg-best over the list heads; the owner of the winner pops its head
+  const int want = 2 * K;
+  int ntop = 0;
+  for (int r = 0; r < want; ++r) {
+    float v = lv[0];
+    int i = li[0];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const float ov = __shfl_xor(v, off, 64);
+      const int oi = __shfl_xor(i, off, 64);
+      if (beam_better(ov, oi, v, i)) { v = ov; i = oi; }
+    }
+    const int buf = r & 1;                                  // double-buffered: one barrier per round
+    if (lane == 0) { red_v[buf][wave] = v; red_i[buf][wave] = i; }
+    __syncthreads();
+    v = red_v[buf][0];
+    i = red_i[buf][0];
+#pragma unroll
+    for (int w = 1; w < BEAM_WAVES; ++w)
+      if (beam_better(red_v[buf][w], red_i[buf][w], v, i)) { v = red_v[buf][w]; i = red_i[buf][w]; }
+    if (v == -INFINITY) break;                              // fewer than 2K finite candidates (uniform)
+    if (li[0] == i) {
+#pragma unroll
+      for (int j = 0; j < M - 1; ++j) { lv[j] = lv[j + 1]; li[j] = li[j + 1]; }
+      lv[M - 1] = -INFINITY;
+      li[M - 1] = INT_MAX;
+    }
+    if (tid == 0) { top_v[r] = v; top_i[r] = i; }
+    ntop = r + 1;
+  }
+  if (tid == 0) s_ntop = ntop;
+  __syncthreads();
+  if (tid != 0) return;
+
+  // the fairseq walk over the ranked candidates (a handful of entries: one thread)
+  ntop = s_ntop;
+  const int64_t hb = ((int64_t)t * B + b) * K;
+  int nf = p.nfin[b], nlive = 0;
+  for (int r = 0; r < ntop; ++r) {
+    const int idx = top_i[r];
+    const int k = idx / V, v = idx - k * V;
+    if (v == p.eos) {
+      if (r < K) {
+        int4* f = reinterpret_cast<int4*>(p.fin) + (int64_t)b * BEAM_FCAP + nf;
+        *f = make_int4(t, k, t + 1, 1);
+        p.fin_score[(int64_t)b * BEAM_FCAP + nf] = top_v[r];
+        ++nf;
+      }
+    } else if (nlive < K) {
+      p.tok_hist[hb + nlive] = v;
+      p.bp_hist[hb + nlive] = k;
+      p.scores[(int64_t)b * K + nlive] = top_v[r];
+      ++nlive;
+    }
+  }
+  for (int j = nlive; j < K; ++j) {                         // dead slots: a valid token and predecessor, score -inf
+    p.tok_hist[hb + j] = p.eos;
+    p.bp_hist[hb + j] = 0;
+    p.scores[(int64_t)b * K + j] = -INFINITY;
+  }
+  if (t == p.L - 1 && nf < K) {                             // max_dec_timesteps: the live beams finish as they stand
+    for (int j = 0; j < nlive; ++j) {
+      int4* f = reinterpret_cast<int4*>(p.fin) + (int64_t)b * BEAM_FCAP + nf;
+      *f = make_int4(t, j, t + 1, 0);
+      p.fin_score[(int64_t)b * BEAM_FCAP + nf] = p.scores[(int64_t)b * K + j];
+      ++nf;
+    }
+  }
+  p.nfin[b] = nf;
+  if (nf >= K || t == p.L - 1 || nlive == 0) {
+    p.done[b] = 1;
+    atomicAdd(p.ndone, 1);
+  }
+}
+
+__global__ __launch_bounds__(BEAM_NT) void beam_reorder_kernel(asr_beam_t p, int t, asr_beam_state_t s) {
+  const int row = blockIdx.x, b = row / p.K, j = row - b * p.K;
+  if (p.done[b]) return;
+  const int64_t h = ((int64_t)t * p.B + b) * p.K + j;
+  const int src = b * p.K + p.bp_hist[h];
+  const int tok = p.tok_hist[h];
+  const int DO = s.D + s.O;
+  const float* xs = s.x_src + (int64_t)src * s.ldx;
+  float* xd = s.x_dst + (int64_t)row * s.ldx;
+  for (int i = threadIdx.x; i < DO; i += BEAM_NT) xd[i] = xs[i];
+  const float* e = s.emb + (int64_t)tok * s.E;
+  for (int i = threadIdx.x; i < s.E; i += BEAM_NT) xd[DO + i] = e[i];
+  for (int i = threadIdx.x; i < s.D; i += BEAM_NT) s.c_dst[(int64_t)row * s.D + i] = s.c_src[(int64_t)src * s.D + i];
+  for (int i = threadIdx.x; i < s.Tp; i += BEAM_NT) s.w_dst[(int64_t)row * s.Tp + i] = s.w_src[(int64_t)src * s.Tp + i];
+}
+
+__global__ __launch_bounds__(BEAM_NT) void beam_backtrack_kernel(asr_beam_t p, float alpha, int32_t* out_tok,
+                                                                 float* out_score, int32_t* out_len) {
+  const int b = blockIdx.x, tid = threadIdx.x, K = p.K, L = p.L;
+  __shared__ int order[BEAM_FCAP];
+  __shared__ float key[BEAM_FCAP];
+  __shared__ int s_nf;
+  const int4* fin = reinterpret_cast<const int4*>(p.fin) + (int64_t)b * BEAM_FCAP;
+  if (tid == 0) {
+    int nf = p.nfin[b];
+    nf = nf < 0 ? 0 : (nf > BEAM_FCAP ? BEAM_FCAP : nf);
+    // insertion sort by score / len^alpha, descending; stable, so ties keep the order of finishing
+    for (int i = 0; i < nf; ++i) {
+      const float sc = p.fin_score[(int64_t)b * BEAM_FCAP + i];
+      const float kv = alpha == 0.f ? sc : sc / powf((float)fin[i].z, alpha);
+      int j = i;
+      while (j > 0 && kv > key[j - 1]) { key[j] = key[j - 1]; order[j] = order[j - 1]; --j; }
+      key[j] = kv;
+      order[j] = i;
+    }
+    s_nf = nf;
+  }
+  __syncthreads();
+  const int nf = s_nf;
+  for (int r = tid; r < K; r += BEAM_NT) {
+    int32_t* row = out_tok + ((int64_t)b * K + r) * L;
+    for (int s = 0; s < L; ++s) row[s] = p.eos;
+    if (r >= nf) {
+      out_score[(int64_t)b * K + r] = -INFINITY;
+      out_len[(int64_t)b * K + r] = 0;
+      continue;
+    }
+    const int4 f = fin[order[r]];                          // (step, slot, length, ends with <EOS>)
+    int s = f.x, j = f.y;
+    if (f.w) {
+      --s;                                                  // row[f.x] is the <EOS>; slot j is the beam at step f.x - 1
+    }
+    for (; s >= 0; --s) {
+      const int64_t h = ((int64_t)s * p.B + b) * K + j;
+      row[s] = p.tok_hist[h];
+      j = p.bp_hist[h];
+    }
+    out_score[(int64_t)b * K + r] = key[r];
+    out_len[(int64_t)b * K + r] = f.z;
+  }
+}
+
+int check_beam(const asr_beam_t* p, bool need_logits) {
+  if (!p || (need_logits && !p->logits) || !p->scores || !p->tok_hist || !p->bp_hist || !p->fin || !p->fin_score || !p->nfin || !p->done ||
+      !p->ndone)
+    return ASR_E_ARG;
+  if (p->B <= 0 || p->K <= 0 || p->V <= 0 || p->L <= 0) return ASR_E_ARG;
+  if (p->K > BEAM_KMAX || p->V < 2 || (int64_t)p->K * p->V > INT_MAX / 2 || p->eos < 0 || p->eos >= p->V) return ASR_E_SHAPE;
+  if (!asr_aligned16(p->fin)) return ASR_E_ALIGN;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int asr_beam_select_f32(const asr_beam_t* p, int t, asr_stream_t stream_) {
+  int rc = check_beam(p, true);
+  if (rc) return rc;
+  if (t < 0 || t >= p->L) return ASR_E_ARG;
+  hipStream_t stream = (hipStream_t)stream_;
+  const dim3 grid(p->B), block(BEAM_NT);
+  const int m = 2 * p->K;
+  if (m <= 2) hipLaunchKernelGGL(beam_select_kernel<2>, grid, block, 0, stream, *p, t);
+  else if (m <= 4) hipLaunchKernelGGL(beam_select_kernel<4>, grid, block, 0, stream, *p, t);
+  else if (m <= 8) hipLaunchKernelGGL(beam_select_kernel<8>, grid, block, 0, stream, *p, t);
+  else if (m <= 16) hipLaunchKernelGGL(beam_select_kernel<16>, grid, block, 0, stream, *p, t);
+  else hipLaunchKernelGGL(beam_select_kernel<32>, grid, block, 0, stream, *p, t);
+  ASR_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int asr_beam_reorder_f32(const asr_beam_t* p, int t, const asr_beam_state_t* s, asr_stream_t stream_) {
+  int rc = check_beam(p, false);
+  if (rc) return rc;
+  if (!s || !s->x_src || !s->x_dst || !s->c_src || !s->c_dst || !s->w_src || !s->w_dst || !s->emb) return ASR_E_ARG;
+  if (t < 0 || t >= p->L || s->D <= 0 || s->O < 0 || s->E <= 0 || s->Tp <= 0 || s->ldx < s->D + s->O + s->E)
+    return ASR_E_ARG;
+  if (s->x_src == s->x_dst || s->c_src == s->c_dst || s->w_src == s->w_dst) return ASR_E_ARG;   // a gather: out of place
+  hipLaunchKernelGGL(beam_reorder_kernel, dim3(p->B * p->K), dim3(BEAM_NT), 0, (hipStream_t)stream_, *p, t, *s);
+  ASR_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int asr_beam_backtrack(const asr_beam_t* p, float length_penalty, int32_t* tokens, float* scores,
+                                  int32_t* lengths, asr_stream_t stream_) {
+  int rc = check_beam(p, false);
+  if (rc) return rc;
+  if (!tokens || !scores || !lengths) return ASR_E_ARG;
+  hipLaunchKernelGGL(beam_backtrack_kernel, dim3(p->B), dim3(BEAM_NT), 0, (hipStream_t)stream_, *p, length_penalty,
+                     tokens, scores, lengths);
+  ASR_CHECK_LAUNCH();
+  return 0;
+}

@@ -11,7 +11,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libasr_hip.so")
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 EXPORTS = (
     "asr_abi_version", "asr_persist_scratch_bytes", "asr_gemm_f32", "asr_gemm_skinny_f32", "asr_colsum_f32",
@@ -23,6 +23,7 @@ EXPORTS = (
     "asr_lstm_pack_multi_f32", "asr_lstm_unpack_multi_f32", "asr_dec_pack_f32", "asr_colsum_parts_f32", "asr_gemm_drop_f32", "asr_gemm_side_f32", "asr_embedding_grad_f32",
     "asr_label_logprob_fwd", "asr_label_logprob_bwd", "asr_dec_feedback_fwd", "asr_dec_feedback_bwd",
     "asr_adam_clip_f32", "asr_sumsq_f32", "asr_gather_sumsq_f32", "asr_graphs_create", "asr_graphs_destroy", "asr_graphs_stats",
+    "asr_beam_select_f32", "asr_beam_reorder_f32", "asr_beam_backtrack",
 )
 
 _lib = None
@@ -61,6 +62,21 @@ class DecFwd(ctypes.Structure):
     _fields_ = [(n, c_i) for n in ("B", "nb", "Tp", "A", "D", "O", "E", "C", "K", "L")] + [("scaling", c_f)] + \
                [(n, c_p) for n in ("P", "Q", "bo", "wcat", "bcat", "wdec", "convw", "watt", "wattT", "gvec", "w0", "xmask",
                                    "X", "Xd", "gates", "cstate", "Dproj", "fconv", "S", "energy", "ws")]
+
+
+class Beam(ctypes.Structure):
+    """asr_beam_t"""
+    _fields_ = [(n, c_i) for n in ("B", "K", "V", "L", "eos")] + \
+               [(n, c_p) for n in ("logits", "scores", "tok_hist", "bp_hist", "fin", "fin_score", "nfin", "done", "ndone")]
+
+
+class BeamState(ctypes.Structure):
+    """asr_beam_state_t"""
+    _fields_ = [(n, c_i) for n in ("D", "O", "E", "Tp")] + [("ldx", ctypes.c_int64)] + \
+               [(n, c_p) for n in ("x_src", "x_dst", "c_src", "c_dst", "w_src", "w_dst", "emb")]
+
+
+BEAM_KMAX, BEAM_FCAP = 16, 48          # ASR_BEAM_KMAX, ASR_BEAM_FCAP
 
 
 class DecBwd(ctypes.Structure):
@@ -112,6 +128,9 @@ def load():
     lib.asr_relu_dropout_bwd_f32.argtypes = [c_i64, c_p, c_p, c_u64, c_f, c_p, c_p]
     lib.asr_dropout_mask_f32.argtypes = [c_i64, c_p, c_u64, c_f, c_p]
     lib.asr_dec_step_fwd.argtypes = [ctypes.POINTER(DecFwd), c_i, c_p]
+    lib.asr_beam_select_f32.argtypes = [ctypes.POINTER(Beam), c_i, c_p]
+    lib.asr_beam_reorder_f32.argtypes = [ctypes.POINTER(Beam), c_i, ctypes.POINTER(BeamState), c_p]
+    lib.asr_beam_backtrack.argtypes = [ctypes.POINTER(Beam), c_f, c_p, c_p, c_p, c_p]
     lib.asr_att_step_fwd.argtypes = [ctypes.POINTER(DecFwd), c_i, c_p]
     lib.asr_dec_seq_fwd.argtypes = [ctypes.POINTER(DecFwd), c_i, c_i, c_p, c_p]
     lib.asr_dec_seq_fwd_persist.argtypes = [ctypes.POINTER(DecFwd), c_p, c_p, c_p]
@@ -320,6 +339,56 @@ def gemm_skinny(A, Bt, bias=None, out=None, accumulate=False):
     check(load().asr_gemm_skinny_f32(M, N, K, ptr(A), lda, ptr(Bt), ldb, ptr(out), ldc, ptr(bias), int(accumulate),
                                      None, 0, 0, stream()), "asr_gemm_skinny_f32")
     return out
+
+
+class BeamSearch:
+    """The device state of one beam search (asr_beam_t): B utterances, beam width K, vocabulary V, at most L steps.
+    select / reorder / backtrack enqueue the three beam kernels (csrc/beam.hip) on the current stream; `ndone` is the
+    device word the host polls."""
+
+    def __init__(self, B, K, V, L, eos, device):
+        if not 1 <= K <= BEAM_KMAX:
+            raise ValueError("beam width %d outside 1..%d" % (K, BEAM_KMAX))
+        i32 = dict(dtype=torch.int32, device=device)
+        self.B, self.K, self.V, self.L, self.eos = B, K, V, L, eos
+        self.scores = torch.full((B, K), float("-inf"), dtype=torch.float32, device=device)
+        self.scores[:, 0] = 0.0
+        self.tok_hist = torch.empty(L, B, K, **i32)
+        self.bp_hist = torch.empty(L, B, K, **i32)
+        self.fin = torch.empty(B, BEAM_FCAP, 4, **i32)
+        self.fin_score = torch.empty(B, BEAM_FCAP, dtype=torch.float32, device=device)
+        counters = torch.zeros(2 * B + 1, **i32)                 # nfin | done | ndone: one fill
+        self.nfin, self.done, self.ndone = counters[:B], counters[B:2 * B], counters[2 * B:]
+        self._counters = counters
+        self.struct = Beam(B=B, K=K, V=V, L=L, eos=eos, logits=None, scores=ptr(self.scores),
+                           tok_hist=ptr(self.tok_hist), bp_hist=ptr(self.bp_hist), fin=ptr(self.fin),
+                           fin_score=ptr(self.fin_score), nfin=ptr(self.nfin), done=ptr(self.done), ndone=ptr(self.ndone))
+
+    def select(self, logits, t):
+        """logits [B*K, V] (contiguous) of step t -> tokens, backpointers, scores, finished list, done flags."""
+        assert logits.is_contiguous() and tuple(logits.shape) == (self.B * self.K, self.V)
+        self.struct.logits = ptr(logits)
+        check(load().asr_beam_select_f32(ctypes.byref(self.struct), int(t), stream()), "asr_beam_select_f32")
+
+    def reorder(self, t, x_src, x_dst, c_src, c_dst, w_src, w_dst, emb, D, O):
+        """Gather the step-t state of every live beam's predecessor: x rows [B*K, ldx] (z | ctx | embedding columns),
+        cell state [B*K, D], attention weights [B*K, Tp]; the new tokens' embedding rows into x_dst[:, D+O:]."""
+        E = emb.shape[1]
+        st = BeamState(D=D, O=O, E=E, Tp=w_src.shape[1], ldx=x_src.stride(0), x_src=ptr(x_src), x_dst=ptr(x_dst),
+                       c_src=ptr(c_src), c_dst=ptr(c_dst), w_src=ptr(w_src), w_dst=ptr(w_dst), emb=ptr(emb))
+        assert x_dst.stride(0) == x_src.stride(0) and emb.is_contiguous()
+        check(load().asr_beam_reorder_f32(ctypes.byref(self.struct), int(t), ctypes.byref(st), stream()),
+              "asr_beam_reorder_f32")
+
+    def backtrack(self, length_penalty=0.0):
+        """-> tokens [B, K, L] int32 (ranked, <EOS>-padded), scores [B, K] (score / len**length_penalty), lengths [B, K]."""
+        dev = self.scores.device
+        tokens = torch.empty(self.B, self.K, self.L, dtype=torch.int32, device=dev)
+        scores = torch.empty(self.B, self.K, dtype=torch.float32, device=dev)
+        lengths = torch.empty(self.B, self.K, dtype=torch.int32, device=dev)
+        check(load().asr_beam_backtrack(ctypes.byref(self.struct), float(length_penalty), ptr(tokens), ptr(scores),
+                                        ptr(lengths), stream()), "asr_beam_backtrack")
+        return tokens, scores, lengths
 
 
 FEED_PREDICTED, FEED_SMOOTH, FEED_TEACHER, FEED_NONE = 0, 1, 2, 3

@@ -1106,3 +1106,76 @@ def attention_step(enc_pad, P, Q, wdec, convw, watt, gvec, bo, dec_z, att_prev, 
         fs = _dec_fwd_struct(d, 0, B)
         hb.check(hb.load().asr_att_step_fwd(ctypes.byref(fs), 0, hb.stream()), "asr_att_step_fwd")
         return ws["X"][1, :, D:D + O].clone(), ws["ws"][0].clone()
+
+
+BEAM_POLL_STEPS = 8          # the host reads the all-done word of a beam search every this many steps
+
+
+def beam_search(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo, w_out, b_out, w0, beam, L, bos, eos,
+                length_penalty=0.0, scaling=2.0):
+    """Beam search over the decoder (Decoder.recognize_beams, model.py:369-406; semantics in DESIGN 4.8), eval arithmetic.
+
+    Inputs as decoder_sequence's for B utterances; the search runs B*beam rows (row b*beam + k).  Every step is
+    asr_dec_step_fwd at s = 1 -> output-layer GEMM -> beam select -> beam reorder (7 launches, no host sync).  The step
+    reads its input slot (X[1], cstate[0], ws[0]) and writes its output slot (X[2], cstate[1], ws[1]); the reorder gathers
+    the output slot back into the input slot, so two step slots serve any L.  Step 0 runs at s = 1 as well, from an input
+    slot primed with what s = 0 would read (zero z, ctx and cell state, <BOS>, w0).
+    Returns tokens [B, beam, L] int32 (ranked, <EOS>-padded), scores [B, beam], lengths [B, beam]."""
+    dev = P.device
+    B, Tp, A = P.shape
+    O = Q.shape[2]
+    D = w_hh.shape[1]
+    E = emb_w.shape[1]
+    V = w_out.shape[0]
+    C = convw.shape[0]
+    Kc = (convw.shape[-1] - 1) // 2
+    KX = D + O + E
+    R = B * beam
+    f32 = dict(device=dev, dtype=torch.float32)
+    with torch.no_grad():
+        search = hb.BeamSearch(B, beam, V, L, eos, dev)
+        ws = dict(P=P.repeat_interleave(beam, 0).contiguous(), Q=Q.repeat_interleave(beam, 0).contiguous(),
+                  w0=w0.repeat_interleave(beam, 0).contiguous(), wcat=torch.empty(4 * D, KX, **f32),
+                  bcat=torch.empty(4 * D, **f32), wattT=torch.empty(C, A, **f32),
+                  convw=convw.reshape(C, 2 * Kc + 1).contiguous(), gvec=gvec.reshape(A).contiguous(), xmask=None, Xd=None,
+                  X=torch.zeros(3, R, KX, **f32), gates=torch.empty(2, R, 4 * D, **f32), cstate=torch.zeros(2, R, D, **f32),
+                  Dproj=torch.empty(2, R, A, **f32), fconv=torch.empty(2, R, C, Tp, **f32),
+                  S=torch.empty(2, R, Tp, A, **f32), energy=torch.empty(2, R, Tp, **f32), ws=torch.empty(2, R, Tp, **f32))
+        hb.dec_pack(w_ih, w_hh, b_ih, b_hh, wdec, watt, D, O, E, A, C, ws["wcat"], ws["bcat"], None, None, ws["wattT"])
+        d = dict(B=R, Tp=Tp, A=A, D=D, O=O, E=E, C=C, K=Kc, L=2, KX=KX, scaling=float(scaling), bo=bo.contiguous(),
+                 wdec=wdec.contiguous(), watt=watt.contiguous())
+        d.update({k: ws[k] for k in ("P", "Q", "wcat", "bcat", "convw", "gvec", "wattT", "w0", "xmask", "X", "Xd", "gates",
+                                     "cstate", "Dproj", "fconv", "S", "energy", "ws")})
+        fs = _dec_fwd_struct(d, 0, R)
+        X, cst, wts = ws["X"], ws["cstate"], ws["ws"]
+        emb_c, w_out_c = emb_w.contiguous(), w_out.contiguous()
+        X[1, :, D + O:] = emb_c[bos]
+        wts[0].copy_(ws["w0"])
+        logits = torch.empty(R, V, **f32)
+        lib = hb.load()
+        landing = torch.zeros(1, dtype=torch.int32).pin_memory()
+        polled = None
+        steps = launches = 0
+        for t in range(L):
+            hb.check(lib.asr_dec_step_fwd(ctypes.byref(fs), 1, hb.stream()), "asr_dec_step_fwd")
+            hb.gemm_skinny(X[2][:, :D + O], w_out_c, bias=b_out, out=logits)
+            search.select(logits, t)
+            steps += 1
+            launches += 6                                  # 4 decoder-step kernels, the GEMM, the select
+            if t == L - 1:
+                break
+            search.reorder(t, X[2], X[1], cst[1], cst[0], wts[1], wts[0], emb_c, D, O)
+            launches += 1
+            if (t + 1) % BEAM_POLL_STEPS == 0:
+                # the word copied BEAM_POLL_STEPS steps ago: the host waits for that step at most, never for this one
+                if polled is not None:
+                    polled.synchronize()
+                    if int(landing[0]) == B:
+                        break
+                landing.copy_(search.ndone, non_blocking=True)
+                polled = torch.cuda.Event()
+                polled.record()
+        hb.LAUNCHES["beam_step"] += steps
+        hb.LAUNCHES["beam_launch"] += launches
+        out = search.backtrack(length_penalty)
+    return out

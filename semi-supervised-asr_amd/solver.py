@@ -252,6 +252,23 @@ class Solver(object):
             out = run()
         return out
 
+    def _beam(self, xs, ilens, beam_size):
+        """Best beam-search hypothesis ids for one batch (E2E.recognize_beams).  The encoder still runs on the persistent
+        LSTM kernels: the abort word is checked after the decode and the batch repeated on the per-step kernels, as in
+        _greedy."""
+        def run():
+            prediction, _ = self.model.recognize_beams(
+                xs, ilens, self.config["max_dec_timesteps"], beam_size,
+                length_penalty=float(self.config.get("beam_length_penalty", 0.0)))
+            return prediction.cpu().numpy().tolist()
+        out = run()
+        if self._abort_seen(xs.device):
+            print("persistent kernels aborted during beam decoding (this rank's code %d): repeating the batch on the "
+                  "per-step kernels" % hb.persist_abort_code(xs.device))
+            hb.disable_persistent(xs.device)
+            out = run()
+        return out
+
     def validation(self):
         """Teacher-forced dev loss + greedy CER (solver.py:212-242); greedy pass runs without autograd."""
         self.flush()
@@ -303,10 +320,11 @@ class Solver(object):
         loader = get_data_loader(self._dataset(test_set, None, sort=False), batch_size=1, shuffle=False,
                                  drop_last=False)
         self.model.eval()
+        beam_size = int(self.config.get("beam_size", 1) or 1)    # not reference keys: beam_size, beam_length_penalty
         preds, refs = [], []
         for batch in self._feed(loader, sharded=False):
             xs, ilens, _ = batch
-            preds += self._greedy(xs, ilens)
+            preds += self._beam(xs, ilens, beam_size) if beam_size > 1 else self._greedy(xs, ilens)
             refs += batch.ys_host
         self.model.train()
         cer, hyp_sents, _ = self.ind2sent(preds, refs)
