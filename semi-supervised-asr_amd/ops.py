@@ -20,6 +20,7 @@ GPU only; see hip_backend for the no-fallback rule.
 """
 import ctypes
 import os
+import weakref
 
 import numpy as np
 import torch
@@ -166,12 +167,13 @@ class _SideStream(object):
       join_now()         flush + the wait at once (a node that consumes side results inside the pass: _LstmPack.backward).
     Outputs are zeroed on the main stream BEFORE defer() (the side products add into them with atomics).  Off: ASR_SIDE_GEMM=0, the
     fp32-input MFMA arithmetic (no such kernel), gradients exchanged from inside the backward pass (dp_overlap: its hooks
-    read a gradient as soon as autograd has it)."""
+    read a gradient as soon as autograd has it).
+      count_use(ctx, w) / may_defer(ctx, w)   a weight gradient handed back before its product exists (_Linear): see there."""
 
     def __init__(self):
         self.enabled = os.environ.get("ASR_SIDE_GEMM", "1") != "0"
         self.streams, self.active, self.mask_hint = {}, None, 0
-        self.uses = {}                     # weight data_ptr -> forward passes since the last join (see _Linear)
+        self.uses = {}                     # weight data_ptr -> live autograd nodes that use it (count_use)
         self.deferred = []                 # (launch closure, temporaries) waiting for the next recurrence
         self.task = -1                     # the autograd graph task (backward pass) `active` belongs to
         self.launches = 0
@@ -181,6 +183,29 @@ class _SideStream(object):
 
     def usable(self, mask):
         return bool(mask) and self.enabled and (hb.current_arith() & 0xff) != hb.ARITH_F32
+
+    def count_use(self, ctx, weight):
+        """A forward use of `weight` that may send it a gradient: counted for as long as its node `ctx` lives - a graph whose
+        backward never runs (dropped, or a forward under no_grad) takes its count with it, whichever step comes next."""
+        key = weight.data_ptr()
+        self.uses[key] = self.uses.get(key, 0) + 1
+        weakref.finalize(ctx, self._drop_use, key)
+
+    def _drop_use(self, key):
+        n = self.uses.get(key, 0) - 1
+        if n > 0:
+            self.uses[key] = n
+        else:
+            self.uses.pop(key, None)
+
+    def may_defer(self, ctx, weight):
+        """May the backward of node `ctx` return a zeroed dW of `weight` whose product lands in it after the pass?  Only if
+        autograd hands that tensor on unread as the new .grad: a leaf with no .grad yet, no hook that reads its gradient on
+        the way, and no other live node using it - any second gradient of the pass (the other model pass of the
+        semi-supervised step, whatever its rows or XCD mask) would be ADDED to it on the main stream while it is zeros."""
+        return (ctx.side_mask and ctx.needs_input_grad[0] and weight.is_leaf and weight.grad is None
+                and not weight._backward_hooks and not getattr(weight, "_post_accumulate_grad_hooks", None)
+                and self.uses.get(weight.data_ptr(), 0) == 1 and self.usable(ctx.side_mask))
 
     def defer(self, dev, launch, keep):
         """Inside a backward function, once the operands are final on the current stream: queue `launch` (a closure that
@@ -202,7 +227,6 @@ class _SideStream(object):
             self.active[0].wait_stream(self.active[1])
             del self.deferred[:]
             self.active = None
-            self.uses.clear()
         if self.active is None:
             self.active, self.task = (main, st), task
             torch.autograd.Variable._execution_engine.queue_callback(self.join)
@@ -234,7 +258,6 @@ class _SideStream(object):
     def join(self):
         self.join_now()
         self.active = None
-        self.uses.clear()
 
 
 _SIDE = _SideStream()
@@ -288,9 +311,9 @@ class _Linear(torch.autograd.Function):
                     out_zeroed=out is not None)
         ctx.save_for_backward(x2, weight, y if relu else None)
         ctx.side_mask = 0
-        if _SIDE.mask_hint and x2.shape[0] >= 512 and ctx.needs_input_grad[1]:      # (grad mode is off inside forward: ask the node)
-            ctx.side_mask = _SIDE.mask_hint
-            _SIDE.uses[weight.data_ptr()] = _SIDE.uses.get(weight.data_ptr(), 0) + 1
+        if ctx.needs_input_grad[1]:                  # (grad mode is off inside forward: ask the node)
+            _SIDE.count_use(ctx, weight)             # EVERY use, whatever its rows or mask (_SideStream.may_defer)
+            ctx.side_mask = _SIDE.mask_hint if x2.shape[0] >= 512 else 0
         ctx.relu = relu
         ctx.drop = (drop.seed, drop.p) if seeded else None
         ctx.has_bias = bias is not None
@@ -313,10 +336,11 @@ class _Linear(torch.autograd.Function):
         elif ctx.relu:
             dy2 = dy2 * (y > 0).to(dy2.dtype)
         dx = hb.gemm(dy2, weight).view(ctx.in_shape) if ctx.needs_input_grad[0] else None
-        # the weight gradient beside the recurrence of the layer below (a small batch; _SideStream) - unless this weight has
-        # a second gradient on its way (the two model passes of the semi-supervised step: autograd would ADD the two on the
-        # main stream while the side stream still writes them) or nothing follows this node in the pass
-        if ctx.side_mask and ctx.needs_input_grad[0] and _SIDE.uses.get(weight.data_ptr(), 0) == 1 and _SIDE.usable(ctx.side_mask):
+        # the weight gradient beside the recurrence of the layer below (a small batch, >= 512 rows; _SideStream) - unless
+        # nothing follows this node in the pass, or autograd would not take dW over unread as the new .grad: a weight with
+        # another live use (the other model pass of the semi-supervised step, whatever its rows or mask: autograd would ADD
+        # the two on the main stream while this one is still zeros), a .grad to add into, a hook (_SideStream.may_defer)
+        if _SIDE.may_defer(ctx, weight):
             dw = zeros_acc((dy2.shape[1], x2.shape[1]), dy2.device)
             queue = zeros_acc((1,), dy2.device)
             # (the closure writes through an ALIAS of dw - a tensor object of its own over the same memory: AccumulateGrad

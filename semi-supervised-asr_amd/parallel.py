@@ -315,6 +315,8 @@ class FlatBuffers(object):
 
     NAUX = 4
     BUCKET_FLOATS = 4 << 20          # 16 MB of gradients per overlapped all-reduce
+    _overlapping = 0                 # buffers with enable_overlap on, process-wide (the side stream is off while any is)
+    _side_before = True              # ops._SIDE.enabled when the first of them began to overlap
 
     def __init__(self, params):
         self.params = []
@@ -378,14 +380,22 @@ class FlatBuffers(object):
             return
         self.overlap, self._group = True, group
         import ops
-        ops._SIDE.enabled = False          # the hooks below read a gradient the moment autograd has it: no products in flight
+        # the hooks below read a gradient the moment autograd has it: no products in flight while ANY buffer overlaps
+        if FlatBuffers._overlapping == 0:
+            FlatBuffers._side_before = ops._SIDE.enabled
+        FlatBuffers._overlapping += 1
+        ops._SIDE.enabled = False
         for i, p in enumerate(self.params):
             self._hooks.append(p.register_post_accumulate_grad_hook(lambda q, i=i: self._on_grad(i)))
 
     def disable_overlap(self):
         """Back to ONE collective after the backward pass (removes the hooks; outstanding collectives are awaited, and a
-        step abandoned between two buckets issues the rest of the fixed sequence first, as zero_grad does)."""
-        if self.overlap and self._started and self._issued < len(self.buckets):
+        step abandoned between two buckets issues the rest of the fixed sequence first, as zero_grad does).  The side
+        stream comes back on with the last overlapping buffer (the generator's and the judge's both overlap under
+        dp_overlap)."""
+        if not self.overlap:
+            return
+        if self._started and self._issued < len(self.buckets):
             self._issue_ready(force=True)
         for w in self._works:
             w.wait()
@@ -393,8 +403,10 @@ class FlatBuffers(object):
             h.remove()
         self._hooks, self.overlap = [], False
         self._reset_overlap_state()
-        import ops
-        ops._SIDE.enabled = os.environ.get("ASR_SIDE_GEMM", "1") != "0"
+        FlatBuffers._overlapping -= 1
+        if FlatBuffers._overlapping == 0:
+            import ops
+            ops._SIDE.enabled = FlatBuffers._side_before
 
     def _on_grad(self, i):
         b = self.bucket_of[i]

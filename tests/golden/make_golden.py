@@ -309,7 +309,7 @@ def gen_big(name, shape):
     print("%s: loss %.6f" % (name, float(loss)))
 
 
-def _store_grads(out, m):
+def _store_grads(out, m, n_sample=4096):
     """Per parameter: gradient norm, first / last 16 elements and a seeded sample of 4 096 elements (synth.grad_sample_index:
     an error confined to the interior of a large gradient moves neither the norm nor the ends)."""
     for i, (n, p) in enumerate(m.named_parameters()):
@@ -317,7 +317,7 @@ def _store_grads(out, m):
         out["gnorm/" + n] = np.float64(np.sqrt((g.astype(np.float64) ** 2).sum()))
         out["ghead/" + n] = g[:16].copy()
         out["gtail/" + n] = g[-16:].copy()
-        out["gsample/" + n] = g[synth.grad_sample_index(i, g.size)].copy()
+        out["gsample/" + n] = g[synth.grad_sample_index(i, g.size, n_sample)].copy()
         out["gmax/" + n] = np.float32(np.abs(g).max())
 
 
@@ -360,6 +360,45 @@ def gen_big_ssl():
     np.savez_compressed(os.path.join(HERE, "big_ssl.npz"), **out)
     print("big_ssl: sup %.6f unsup %.6f, %d hypothesis tokens, smallest top-2 logit margin %.3e"
           % (float(sup), float(unsup), int(mask.sum()), margin))
+
+
+def gen_ssl_straddle():
+    """gen_big_ssl's step with the two passes on different batch shapes (synth.SSL_STRADDLE_SHAPES): a weight the labeled
+    and the unlabeled pass both use sees >= 512 rows in one and fewer (or a batch of 12) in the other.  One file per case,
+    ssl_straddle_<case>.npz, with what big_ssl.npz stores (gradient samples of n_sample elements)."""
+    import time
+    cfg = synth.CFG2
+    for case, sh in sorted(synth.SSL_STRADDLE_SHAPES.items()):
+        m, _ = build_e2e(cfg, sh["wseed"], sh["ldseed"])
+        lm, _ = build_lm(synth.CFG_JUDGE, sh["jseed"], sh["jldseed"])
+        xs_np, ilens, ys_np = synth.ragged_batch(sh["n_lab"], sh["t_lab"], cfg["input_dim"], cfg["output_dim"], sh["bseed"])
+        uxs_np, uilens, _ = synth.ragged_batch(sh["n_unlab"], sh["t_unlab"], cfg["input_dim"], cfg["output_dim"],
+                                               sh["ubseed"])
+        xs, ys = to_t(xs_np, ys_np)
+        uxs = torch.from_numpy(uxs_np)
+        t0 = time.time()
+        u_logits, u_lp, u_pred, _ = m(uxs, uilens, ys=None, sample=False, label_smoothing=False,
+                                      max_dec_timesteps=int(uxs.size(1) * sh["proportion"]), smooth=True,
+                                      scaling=sh["scaling"])
+        _, lm_p, _ = lm(ys=u_pred, discrete_input=False)
+        mask = (u_pred != 2).float()
+        unsup = -torch.sum(lm_p * u_lp * mask) / torch.sum(mask)
+        np.random.seed(9)
+        _, l_lp, _, _ = m(xs, ilens, ys=ys, tf_rate=1.0, sample=False)
+        sup = -torch.mean(l_lp)
+        loss = sup + sh["unsup_weight"] * unsup
+        m.zero_grad()
+        lm.zero_grad()
+        loss.backward()
+        top2 = torch.topk(u_logits, 2, dim=2).values
+        margin = float((top2[..., 0] - top2[..., 1]).min())
+        out = dict(unsup=npy(unsup), sup=npy(sup), loss=npy(loss), u_pred=npy(u_pred), u_lp=npy(u_lp), lm_p=npy(lm_p),
+                   n_hyp_tokens=np.float32(mask.sum()), min_top2_margin=np.float32(margin),
+                   ilens=np.asarray(ilens), uilens=np.asarray(uilens))
+        _store_grads(out, m, sh["n_sample"])
+        np.savez_compressed(os.path.join(HERE, "ssl_straddle_%s.npz" % case), **out)
+        print("ssl_straddle_%s: reference step %.1f s, sup %.6f unsup %.6f, %d hypothesis tokens, smallest top-2 logit "
+              "margin %.3e" % (case, time.time() - t0, float(sup), float(unsup), int(mask.sum()), margin))
 
 
 def gen_tiny_opt():
@@ -732,7 +771,7 @@ if __name__ == "__main__":
     torch.set_num_threads(int(os.environ.get("GOLDEN_THREADS", "4")))
     jobs = dict(tiny_e2e=gen_tiny_e2e, tiny_lm=gen_tiny_lm, tiny_ssl=gen_tiny_ssl, cfg1=gen_cfg1, text=gen_text,
                 tiny_opt=gen_tiny_opt, cfg2=lambda: gen_big("cfg2", synth.CFG2_SHAPE),
-                cfg5=lambda: gen_big("cfg5", synth.CFG5_SHAPE), big_ssl=gen_big_ssl,
+                cfg5=lambda: gen_big("cfg5", synth.CFG5_SHAPE), big_ssl=gen_big_ssl, ssl_straddle=gen_ssl_straddle,
                 solver_run=gen_solver_run, solver_loops=gen_solver_loops,
                 solver_run_extend=gen_solver_run_extend)
     for name in (sys.argv[1:] or [j for j in jobs if j != "solver_run_extend"]):          # no arguments: everything (cfg2 / cfg5 take minutes)

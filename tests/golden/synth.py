@@ -31,6 +31,17 @@ CFG5_SHAPE = dict(n_utt=8, t_max=1600, wseed=99, bseed=1235, ldseed=5)
 CFG_JUDGE = dict(output_dim=34, embedding_dim=256, hidden_dim=640, dropout_rate=0.0, n_layers=2, ls_weight=0.05)
 BIG_SSL_SHAPE = dict(n_lab=8, n_unlab=8, t_max=400, wseed=99, jseed=77, bseed=2234, ubseed=2235, ldseed=5, jldseed=6,
                      proportion=0.125, unsup_weight=0.5, scaling=3.0)
+# the same step where the two passes put a weight on opposite sides of the side-stream rule of ops._Linear (>= 512 rows
+# under a non-zero XCD mask, which only batches of <= 8 utterances get; make_golden.py gen_ssl_straddle):
+#   a: 8 labeled of T = 400 (attention projections: 8 x 50 rows) + 8 unlabeled of T = 800 (8 x 100 rows)
+#   b: the other way round
+#   c: 12 labeled (no side stream: mask 0) + 8 unlabeled, both T = 400
+# Gradients are stored as norm, ends and a seeded sample of `n_sample` elements (grad_sample_index).
+_STRADDLE = dict(wseed=99, jseed=77, bseed=2234, ubseed=2235, ldseed=5, jldseed=6, proportion=0.125, unsup_weight=0.5,
+                 scaling=3.0, n_sample=1024)
+SSL_STRADDLE_SHAPES = dict(a=dict(_STRADDLE, n_lab=8, t_lab=400, n_unlab=8, t_unlab=800),
+                           b=dict(_STRADDLE, n_lab=8, t_lab=800, n_unlab=8, t_unlab=400),
+                           c=dict(_STRADDLE, n_lab=12, t_lab=400, n_unlab=8, t_unlab=400))
 
 
 def grad_sample_index(i, numel, n=4096):
