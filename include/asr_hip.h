@@ -644,6 +644,53 @@ int asr_beam_backtrack(const asr_beam_t* p, float length_penalty, int32_t* token
                        asr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Shallow fusion: the beam search rescored by the judge LM on the device.  Three entries added to ABI
+ * version 6 WITHOUT a version change: they are additive - no existing entry, structure or constant changes, and a
+ * caller that does not use them sees the library it saw before.
+ * Every beam row carries the LM's state: per layer l an input row [x_l | h_l] of In_l + H floats (x_0: the LM embedding
+ * of the consumed token, x_l: layer l-1's new h) and a cell state of H floats, each in two step slots.  Per step the
+ * caller runs asr_lm_step_f32 once per layer (input slot -> output slot), asr_gemm_skinny_f32 for the LM's output layer,
+ * asr_beam_select_lm_f32 in place of asr_beam_select_f32 and asr_beam_reorder_lm_f32 in place of asr_beam_reorder_f32.
+ *   asr_lm_step_f32         one LSTM layer step for R rows (1 .. ASR_LM_MAX_ROWS), one launch, no gates in memory:
+ *                           gates = xin[r][0 : In+H] W_cat^T + b with W_cat [4H][In+H] = [W_ih | W_hh] and b = b_ih + b_hh,
+ *                           both gate-interleaved (row = unit*4 + gate, gates (i,f,g,o)); c_out = f c_prev + i g;
+ *                           h = o tanh(c_out) goes to h_out[r*ldh + unit] and, if h_out2 != NULL, to h_out2[r*ldh2 +
+ *                           unit] (the x part of the next layer's input row).  fp32-input MFMA: exact fp32 products.
+ *                           H, In multiples of 16 up to ASR_LM_MAX_WIDTH, R <= ASR_LM_MAX_ROWS: ASR_E_SHAPE otherwise.
+ *                           xin (row stride ldx >= In + H, a multiple of 4), W_cat and b 16-byte aligned.  A step reads
+ *                           one slot and writes another: c_out == c_prev or an output equal to xin is ASR_E_ARG.
+ *   asr_beam_select_lm_f32  asr_beam_select_f32 on the fused candidate score
+ *                           (score[k] + log_softmax(logits_k)[v]) + lm_weight * log_softmax(lm_logits_k)[v] - fp32, each
+ *                           operation rounded on its own, in this order; lm_logits [B*K][V] like p->logits.  Everything
+ *                           else (ranking, ties, <EOS>, finishing, done) as asr_beam_select_f32; with lm_weight = 0 and
+ *                           finite lm_logits every output word equals that entry's.
+ *   asr_beam_reorder_lm_f32 the gather of asr_beam_reorder_f32 (s; NULL: skipped) and, in the same launch, for every LM
+ *                           layer l and every beam row b*K+j of an utterance that is not done: the h part
+ *                           x_dst[l][row][In_l : In_l+H] and c_dst[l][row] from row b*K + bp_hist[t][b][j] of x_src[l] /
+ *                           c_src[l], and x_dst[0][row][0 : In_0] = emb[tok_hist[t][b][j]] (emb [V][In_0]: the LM's own
+ *                           table).  The x parts of layers l > 0 are not touched (the next step writes them).  Source
+ *                           and destination of a layer must differ (ASR_E_ARG); 1 .. ASR_LM_MAX_LAYERS layers.
+ * ------------------------------------------------------------------------------------- */
+#define ASR_LM_MAX_LAYERS 4
+#define ASR_LM_MAX_ROWS 512
+#define ASR_LM_MAX_WIDTH 1024
+typedef struct {
+  int n_layers, H;
+  int in_dim[ASR_LM_MAX_LAYERS];          /* In_l: E of the LM for layer 0, H above */
+  const float* x_src[ASR_LM_MAX_LAYERS];  /* [B*K][In_l + H] the step's output slot (only the h part is read) */
+  float* x_dst[ASR_LM_MAX_LAYERS];        /* [B*K][In_l + H] the next step's input slot */
+  const float* c_src[ASR_LM_MAX_LAYERS];  /* [B*K][H] */
+  float* c_dst[ASR_LM_MAX_LAYERS];
+  const float* emb;                       /* [V][In_0] */
+} asr_beam_lm_state_t;
+int asr_lm_step_f32(int R, int H, int In, const float* xin, int64_t ldx, const float* wcat, const float* bcat,
+                    const float* c_prev, float* c_out, float* h_out, int64_t ldh, float* h_out2, int64_t ldh2,
+                    asr_stream_t stream);
+int asr_beam_select_lm_f32(const asr_beam_t* p, const float* lm_logits, float lm_weight, int t, asr_stream_t stream);
+int asr_beam_reorder_lm_f32(const asr_beam_t* p, int t, const asr_beam_state_t* s, const asr_beam_lm_state_t* lm,
+                            asr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Optimiser on a flat fp32 buffer (solver.py:152-153,384-385: clip_grad_norm_ + Adam(amsgrad,
  * weight_decay).step).  asr_sumsq_f32 adds sum(g^2) into the device scalar out[0] (caller zeroes
  * it); asr_adam_clip_f32 scales g by min(1, max_norm/(sqrt(*gnorm_sq)+1e-6)) (skipped when

@@ -7,7 +7,9 @@
 //   beam_reorder  one workgroup per beam row: the next step's input slot gathers its predecessor's z, ctx, cell state
 //                 and attention weights (out of place: source and destination are different step slots) and the
 //                 embedding of its new token;
-// and once at the end
+// With a language model (shallow fusion) the select kernel's LM variant adds lm_weight * log_softmax(lm_logits)
+// to every candidate, and beam_reorder_lm gathers the LM's h / c of every layer (and the decoder's state) in one launch.
+// And once at the end
 //   beam_backtrack  one workgroup per utterance: rank the finished hypotheses, follow the backpointers into token rows.
 #include <float.h>
 #include <limits.h>
@@ -31,13 +33,16 @@ __device__ __forceinline__ float beam_wave_max(float v) {
   return v;
 }
 
-// M: the per-thread candidate list length, a power of two >= 2K
-template <int M>
-__global__ __launch_bounds__(BEAM_NT) void beam_select_kernel(asr_beam_t p, int t) {
+// M: the per-thread candidate list length, a power of two >= 2K.  LM: candidates are score + logp + lmw * logp_lm (each
+// operation rounded on its own, in this order); without it lm_logits / lmw are not read and the code is the plain select's.
+template <int M, bool LM>
+__global__ __launch_bounds__(BEAM_NT) void beam_select_kernel(asr_beam_t p, int t, const float* __restrict__ lm_logits,
+                                                              float lmw) {
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = p.K, V = p.V, B = p.B;
   if (p.done[b]) return;                                   // finished utterances are left untouched
   __shared__ float s_score[BEAM_KMAX], s_max[BEAM_KMAX], s_lsum[BEAM_KMAX];
+  __shared__ float s_lmmax[LM ? BEAM_KMAX : 1], s_lmlsum[LM ? BEAM_KMAX : 1];
   __shared__ float red_v[2][BEAM_WAVES];
   __shared__ int red_i[2][BEAM_WAVES];
   __shared__ float top_v[2 * BEAM_KMAX];
@@ -58,6 +63,16 @@ __global__ __launch_bounds__(BEAM_NT) void beam_select_kernel(asr_beam_t p, int 
     for (int v = lane; v < V; v += 64) s += expf(row[v] - m);
     s = wave_sum(s);
     if (lane == 0) { s_max[k] = m; s_lsum[k] = logf(s); }
+    if (LM) {
+      const float* lrow = lm_logits + ((int64_t)b * K + k) * V;
+      float lm = -INFINITY;
+      for (int v = lane; v < V; v += 64) lm = fmaxf(lm, lrow[v]);
+      lm = beam_wave_max(lm);
+      float lsum = 0.f;
+      for (int v = lane; v < V; v += 64) lsum += expf(lrow[v] - lm);
+      lsum = wave_sum(lsum);
+      if (lane == 0) { s_lmmax[k] = lm; s_lmlsum[k] = logf(lsum); }
+    }
   }
   __syncthreads();
 
@@ -72,8 +87,11 @@ __global__ __launch_bounds__(BEAM_NT) void beam_select_kernel(asr_beam_t p, int 
     if (sc == -INFINITY) continue;
     const float m = s_max[k], ls = s_lsum[k];
     const float* row = lg + (int64_t)k * V;
+    const float* lrow = LM ? lm_logits + ((int64_t)b * K + k) * V : nullptr;
+    const float lmm = LM ? s_lmmax[k] : 0.f, lml = LM ? s_lmlsum[k] : 0.f;
     for (int v = tid; v < V; v += BEAM_NT) {
       float c = sc + ((row[v] - m) - ls);
+      if (LM) c = __fadd_rn(c, __fmul_rn(lmw, (lrow[v] - lmm) - lml));   // no fused multiply-add: the order is the contract
       if (c > lv[M - 1]) {                                 // -inf and NaN never enter
         int ci = k * V + v;
 #pragma unroll
@@ -165,12 +183,8 @@ __global__ __launch_bounds__(BEAM_NT) void beam_select_kernel(asr_beam_t p, int 
   }
 }
 
-__global__ __launch_bounds__(BEAM_NT) void beam_reorder_kernel(asr_beam_t p, int t, asr_beam_state_t s) {
-  const int row = blockIdx.x, b = row / p.K, j = row - b * p.K;
-  if (p.done[b]) return;
-  const int64_t h = ((int64_t)t * p.B + b) * p.K + j;
-  const int src = b * p.K + p.bp_hist[h];
-  const int tok = p.tok_hist[h];
+// the decoder state of beam row `row` (not done): gathered from row `src`, with the embedding of token `tok`
+__device__ __forceinline__ void beam_reorder_row(const asr_beam_state_t& s, int row, int src, int tok) {
   const int DO = s.D + s.O;
   const float* xs = s.x_src + (int64_t)src * s.ldx;
   float* xd = s.x_dst + (int64_t)row * s.ldx;
@@ -179,6 +193,40 @@ __global__ __launch_bounds__(BEAM_NT) void beam_reorder_kernel(asr_beam_t p, int
   for (int i = threadIdx.x; i < s.E; i += BEAM_NT) xd[DO + i] = e[i];
   for (int i = threadIdx.x; i < s.D; i += BEAM_NT) s.c_dst[(int64_t)row * s.D + i] = s.c_src[(int64_t)src * s.D + i];
   for (int i = threadIdx.x; i < s.Tp; i += BEAM_NT) s.w_dst[(int64_t)row * s.Tp + i] = s.w_src[(int64_t)src * s.Tp + i];
+}
+
+__global__ __launch_bounds__(BEAM_NT) void beam_reorder_kernel(asr_beam_t p, int t, asr_beam_state_t s) {
+  const int row = blockIdx.x, b = row / p.K, j = row - b * p.K;
+  if (p.done[b]) return;
+  const int64_t h = ((int64_t)t * p.B + b) * p.K + j;
+  beam_reorder_row(s, row, b * p.K + p.bp_hist[h], p.tok_hist[h]);
+}
+
+// blockIdx.y = 0: the decoder state (if has_dec); 1 + l: LM layer l - the h part of its input row and its cell state
+// gathered by the backpointer, and for layer 0 the new token's LM embedding into the x part
+__global__ __launch_bounds__(BEAM_NT) void beam_reorder_lm_kernel(asr_beam_t p, int t, asr_beam_state_t s, int has_dec,
+                                                                 asr_beam_lm_state_t m) {
+  const int row = blockIdx.x, b = row / p.K, j = row - b * p.K;
+  if (p.done[b]) return;
+  const int64_t h = ((int64_t)t * p.B + b) * p.K + j;
+  const int src = b * p.K + p.bp_hist[h];
+  const int tok = p.tok_hist[h];
+  if (blockIdx.y == 0) {
+    if (has_dec) beam_reorder_row(s, row, src, tok);
+    return;
+  }
+  const int l = blockIdx.y - 1, H = m.H, In = m.in_dim[l];
+  const int64_t ld = In + H;
+  const float* hs = m.x_src[l] + (int64_t)src * ld + In;
+  float* xd = m.x_dst[l] + (int64_t)row * ld;
+  for (int i = threadIdx.x; i < H; i += BEAM_NT) xd[In + i] = hs[i];
+  const float* cs = m.c_src[l] + (int64_t)src * H;
+  float* cd = m.c_dst[l] + (int64_t)row * H;
+  for (int i = threadIdx.x; i < H; i += BEAM_NT) cd[i] = cs[i];
+  if (l == 0) {
+    const float* e = m.emb + (int64_t)tok * In;
+    for (int i = threadIdx.x; i < In; i += BEAM_NT) xd[i] = e[i];
+  }
 }
 
 __global__ __launch_bounds__(BEAM_NT) void beam_backtrack_kernel(asr_beam_t p, float alpha, int32_t* out_tok,
@@ -237,32 +285,66 @@ int check_beam(const asr_beam_t* p, bool need_logits) {
   return 0;
 }
 
-}  // namespace
-
-extern "C" int asr_beam_select_f32(const asr_beam_t* p, int t, asr_stream_t stream_) {
+template <bool LM>
+int beam_select_launch(const asr_beam_t* p, const float* lm_logits, float lmw, int t, hipStream_t stream) {
   int rc = check_beam(p, true);
   if (rc) return rc;
   if (t < 0 || t >= p->L) return ASR_E_ARG;
-  hipStream_t stream = (hipStream_t)stream_;
   const dim3 grid(p->B), block(BEAM_NT);
   const int m = 2 * p->K;
-  if (m <= 2) hipLaunchKernelGGL(beam_select_kernel<2>, grid, block, 0, stream, *p, t);
-  else if (m <= 4) hipLaunchKernelGGL(beam_select_kernel<4>, grid, block, 0, stream, *p, t);
-  else if (m <= 8) hipLaunchKernelGGL(beam_select_kernel<8>, grid, block, 0, stream, *p, t);
-  else if (m <= 16) hipLaunchKernelGGL(beam_select_kernel<16>, grid, block, 0, stream, *p, t);
-  else hipLaunchKernelGGL(beam_select_kernel<32>, grid, block, 0, stream, *p, t);
+  if (m <= 2) hipLaunchKernelGGL((beam_select_kernel<2, LM>), grid, block, 0, stream, *p, t, lm_logits, lmw);
+  else if (m <= 4) hipLaunchKernelGGL((beam_select_kernel<4, LM>), grid, block, 0, stream, *p, t, lm_logits, lmw);
+  else if (m <= 8) hipLaunchKernelGGL((beam_select_kernel<8, LM>), grid, block, 0, stream, *p, t, lm_logits, lmw);
+  else if (m <= 16) hipLaunchKernelGGL((beam_select_kernel<16, LM>), grid, block, 0, stream, *p, t, lm_logits, lmw);
+  else hipLaunchKernelGGL((beam_select_kernel<32, LM>), grid, block, 0, stream, *p, t, lm_logits, lmw);
   ASR_CHECK_LAUNCH();
   return 0;
+}
+
+int check_beam_state(const asr_beam_t* p, int t, const asr_beam_state_t* s) {
+  if (!s || !s->x_src || !s->x_dst || !s->c_src || !s->c_dst || !s->w_src || !s->w_dst || !s->emb) return ASR_E_ARG;
+  if (t < 0 || t >= p->L || s->D <= 0 || s->O < 0 || s->E <= 0 || s->Tp <= 0 || s->ldx < s->D + s->O + s->E)
+    return ASR_E_ARG;
+  if (s->x_src == s->x_dst || s->c_src == s->c_dst || s->w_src == s->w_dst) return ASR_E_ARG;   // a gather: out of place
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int asr_beam_select_f32(const asr_beam_t* p, int t, asr_stream_t stream_) {
+  return beam_select_launch<false>(p, nullptr, 0.f, t, (hipStream_t)stream_);
+}
+
+extern "C" int asr_beam_select_lm_f32(const asr_beam_t* p, const float* lm_logits, float lm_weight, int t,
+                                      asr_stream_t stream_) {
+  if (!lm_logits) return ASR_E_ARG;
+  return beam_select_launch<true>(p, lm_logits, lm_weight, t, (hipStream_t)stream_);
 }
 
 extern "C" int asr_beam_reorder_f32(const asr_beam_t* p, int t, const asr_beam_state_t* s, asr_stream_t stream_) {
   int rc = check_beam(p, false);
   if (rc) return rc;
-  if (!s || !s->x_src || !s->x_dst || !s->c_src || !s->c_dst || !s->w_src || !s->w_dst || !s->emb) return ASR_E_ARG;
-  if (t < 0 || t >= p->L || s->D <= 0 || s->O < 0 || s->E <= 0 || s->Tp <= 0 || s->ldx < s->D + s->O + s->E)
-    return ASR_E_ARG;
-  if (s->x_src == s->x_dst || s->c_src == s->c_dst || s->w_src == s->w_dst) return ASR_E_ARG;   // a gather: out of place
+  rc = check_beam_state(p, t, s);
+  if (rc) return rc;
   hipLaunchKernelGGL(beam_reorder_kernel, dim3(p->B * p->K), dim3(BEAM_NT), 0, (hipStream_t)stream_, *p, t, *s);
+  ASR_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int asr_beam_reorder_lm_f32(const asr_beam_t* p, int t, const asr_beam_state_t* s, const asr_beam_lm_state_t* m,
+                                       asr_stream_t stream_) {
+  int rc = check_beam(p, false);
+  if (rc) return rc;
+  if (!m || !m->emb || t < 0 || t >= p->L) return ASR_E_ARG;
+  if (s && (rc = check_beam_state(p, t, s))) return rc;
+  if (m->n_layers < 1 || m->n_layers > ASR_LM_MAX_LAYERS || m->H <= 0) return ASR_E_SHAPE;
+  for (int l = 0; l < m->n_layers; ++l) {
+    if (!m->x_src[l] || !m->x_dst[l] || !m->c_src[l] || !m->c_dst[l] || m->in_dim[l] <= 0) return ASR_E_ARG;
+    if (m->x_src[l] == m->x_dst[l] || m->c_src[l] == m->c_dst[l]) return ASR_E_ARG;            // a gather: out of place
+  }
+  asr_beam_state_t none = {};
+  hipLaunchKernelGGL(beam_reorder_lm_kernel, dim3(p->B * p->K, 1 + m->n_layers), dim3(BEAM_NT), 0, (hipStream_t)stream_, *p,
+                     t, s ? *s : none, s ? 1 : 0, *m);
   ASR_CHECK_LAUNCH();
   return 0;
 }

@@ -24,6 +24,7 @@ EXPORTS = (
     "asr_label_logprob_fwd", "asr_label_logprob_bwd", "asr_dec_feedback_fwd", "asr_dec_feedback_bwd",
     "asr_adam_clip_f32", "asr_sumsq_f32", "asr_gather_sumsq_f32", "asr_graphs_create", "asr_graphs_destroy", "asr_graphs_stats",
     "asr_beam_select_f32", "asr_beam_reorder_f32", "asr_beam_backtrack",
+    "asr_lm_step_f32", "asr_beam_select_lm_f32", "asr_beam_reorder_lm_f32",
 )
 
 _lib = None
@@ -77,6 +78,13 @@ class BeamState(ctypes.Structure):
 
 
 BEAM_KMAX, BEAM_FCAP = 16, 48          # ASR_BEAM_KMAX, ASR_BEAM_FCAP
+LM_MAX_LAYERS, LM_MAX_ROWS, LM_MAX_WIDTH = 4, 512, 1024      # ASR_LM_MAX_LAYERS, ASR_LM_MAX_ROWS, ASR_LM_MAX_WIDTH
+
+
+class BeamLmState(ctypes.Structure):
+    """asr_beam_lm_state_t"""
+    _fields_ = [("n_layers", c_i), ("H", c_i), ("in_dim", c_i * LM_MAX_LAYERS)] + \
+               [(n, c_p * LM_MAX_LAYERS) for n in ("x_src", "x_dst", "c_src", "c_dst")] + [("emb", c_p)]
 
 
 class DecBwd(ctypes.Structure):
@@ -131,6 +139,10 @@ def load():
     lib.asr_beam_select_f32.argtypes = [ctypes.POINTER(Beam), c_i, c_p]
     lib.asr_beam_reorder_f32.argtypes = [ctypes.POINTER(Beam), c_i, ctypes.POINTER(BeamState), c_p]
     lib.asr_beam_backtrack.argtypes = [ctypes.POINTER(Beam), c_f, c_p, c_p, c_p, c_p]
+    lib.asr_lm_step_f32.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p]
+    lib.asr_beam_select_lm_f32.argtypes = [ctypes.POINTER(Beam), c_p, c_f, c_i, c_p]
+    lib.asr_beam_reorder_lm_f32.argtypes = [ctypes.POINTER(Beam), c_i, ctypes.POINTER(BeamState),
+                                            ctypes.POINTER(BeamLmState), c_p]
     lib.asr_att_step_fwd.argtypes = [ctypes.POINTER(DecFwd), c_i, c_p]
     lib.asr_dec_seq_fwd.argtypes = [ctypes.POINTER(DecFwd), c_i, c_i, c_p, c_p]
     lib.asr_dec_seq_fwd_persist.argtypes = [ctypes.POINTER(DecFwd), c_p, c_p, c_p]
@@ -370,15 +382,36 @@ class BeamSearch:
         self.struct.logits = ptr(logits)
         check(load().asr_beam_select_f32(ctypes.byref(self.struct), int(t), stream()), "asr_beam_select_f32")
 
+    def select_lm(self, logits, lm_logits, lm_weight, t):
+        """select() on score + log_softmax(logits) + lm_weight * log_softmax(lm_logits) (shallow fusion, DESIGN 4.9);
+        lm_logits [B*K, V] like logits."""
+        assert logits.is_contiguous() and tuple(logits.shape) == (self.B * self.K, self.V)
+        assert lm_logits.is_contiguous() and lm_logits.shape == logits.shape
+        self.struct.logits = ptr(logits)
+        check(load().asr_beam_select_lm_f32(ctypes.byref(self.struct), ptr(lm_logits), float(lm_weight), int(t), stream()),
+              "asr_beam_select_lm_f32")
+
+    @staticmethod
+    def _state(x_src, x_dst, c_src, c_dst, w_src, w_dst, emb, D, O):
+        assert x_dst.stride(0) == x_src.stride(0) and emb.is_contiguous()
+        return BeamState(D=D, O=O, E=emb.shape[1], Tp=w_src.shape[1], ldx=x_src.stride(0), x_src=ptr(x_src),
+                         x_dst=ptr(x_dst), c_src=ptr(c_src), c_dst=ptr(c_dst), w_src=ptr(w_src), w_dst=ptr(w_dst),
+                         emb=ptr(emb))
+
     def reorder(self, t, x_src, x_dst, c_src, c_dst, w_src, w_dst, emb, D, O):
         """Gather the step-t state of every live beam's predecessor: x rows [B*K, ldx] (z | ctx | embedding columns),
         cell state [B*K, D], attention weights [B*K, Tp]; the new tokens' embedding rows into x_dst[:, D+O:]."""
-        E = emb.shape[1]
-        st = BeamState(D=D, O=O, E=E, Tp=w_src.shape[1], ldx=x_src.stride(0), x_src=ptr(x_src), x_dst=ptr(x_dst),
-                       c_src=ptr(c_src), c_dst=ptr(c_dst), w_src=ptr(w_src), w_dst=ptr(w_dst), emb=ptr(emb))
-        assert x_dst.stride(0) == x_src.stride(0) and emb.is_contiguous()
+        st = self._state(x_src, x_dst, c_src, c_dst, w_src, w_dst, emb, D, O)
         check(load().asr_beam_reorder_f32(ctypes.byref(self.struct), int(t), ctypes.byref(st), stream()),
               "asr_beam_reorder_f32")
+
+    def reorder_lm(self, t, lm_state, dec=None):
+        """The LM state of every live beam's predecessor (lm_state: LmStepState - every layer's h and c from the output
+        slot into the input slot, the new tokens' LM embedding into layer 0's x part) and, in the same launch, the
+        decoder's gather (dec: the arguments of reorder() after t; None: the LM state alone)."""
+        st = self._state(*dec) if dec is not None else None
+        check(load().asr_beam_reorder_lm_f32(ctypes.byref(self.struct), int(t), ctypes.byref(st) if st is not None else None,
+                                             ctypes.byref(lm_state.reorder_struct()), stream()), "asr_beam_reorder_lm_f32")
 
     def backtrack(self, length_penalty=0.0):
         """-> tokens [B, K, L] int32 (ranked, <EOS>-padded), scores [B, K] (score / len**length_penalty), lengths [B, K]."""
@@ -389,6 +422,75 @@ class BeamSearch:
         check(load().asr_beam_backtrack(ctypes.byref(self.struct), float(length_penalty), ptr(tokens), ptr(scores),
                                         ptr(lengths), stream()), "asr_beam_backtrack")
         return tokens, scores, lengths
+
+
+def lm_step(R, H, In, xin, wcat, bcat, c_prev, c_out, h_out, h_out2=None):
+    """asr_lm_step_f32: one LSTM layer step for R rows.  xin [R, >= In+H] rows [x | h_prev]; wcat [4H, In+H], bcat [4H]
+    gate-interleaved; c_prev, c_out [R, H]; h_out (and h_out2) 2-D views with unit column stride that take h_new.
+    Raises for widths the kernel does not serve (code -2): there is no other path."""
+    check(load().asr_lm_step_f32(int(R), int(H), int(In), ptr(xin), xin.stride(0), ptr(wcat), ptr(bcat), ptr(c_prev),
+                                 ptr(c_out), ptr(h_out), h_out.stride(0), ptr(h_out2),
+                                 0 if h_out2 is None else h_out2.stride(0), stream()), "asr_lm_step_f32")
+
+
+class LmStepState:
+    """The judge LM's state for R rows of a beam search, two step slots per layer: xin[l] [2, R, In_l + H]
+    input rows [x | h] and cell[l] [2, R, H]; slot 0 is what a step reads, slot 1 what it writes (the reorder gathers slot
+    1 back into slot 0), so memory does not depend on the number of steps.  Weights are packed once here:
+    wcat[l] [4H, In_l + H] = [W_ih | W_hh] and bcat[l] = b_ih + b_hh, rows gate-interleaved (unit * 4 + gate).
+    `layers`: [(w_ih, w_hh, b_ih, b_hh)] per layer (LM.LSTM.direction_params), `emb` the LM's embedding table."""
+
+    def __init__(self, R, emb, layers, device=None):
+        device = emb.device if device is None else device
+        n = len(layers)
+        if not 1 <= n <= LM_MAX_LAYERS:
+            raise ValueError("%d LM layers outside 1..%d" % (n, LM_MAX_LAYERS))
+        if not 1 <= R <= LM_MAX_ROWS:
+            raise ValueError("%d beam rows outside 1..%d: the LM step kernel does not serve them" % (R, LM_MAX_ROWS))
+        f32 = dict(device=device, dtype=torch.float32)
+        self.R, self.n, self.H = R, n, layers[0][1].shape[1]
+        self.emb = emb.detach().contiguous()
+        self.in_dim, self.xin, self.cell, self.wcat, self.bcat = [], [], [], [], []
+        with torch.no_grad():
+            for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(layers):
+                H, In = self.H, w_ih.shape[1]
+                want = self.emb.shape[1] if l == 0 else H
+                if tuple(w_hh.shape) != (4 * H, H) or w_ih.shape[0] != 4 * H or In != want:
+                    raise ValueError("LM layer %d: weights %s / %s do not stack on input width %d, hidden width %d"
+                                     % (l, tuple(w_ih.shape), tuple(w_hh.shape), want, H))
+                self.in_dim.append(In)
+                self.xin.append(torch.zeros(2, R, In + H, **f32))
+                self.cell.append(torch.zeros(2, R, H, **f32))
+                w = torch.cat([w_ih.detach(), w_hh.detach()], dim=1).view(4, H, In + H)
+                self.wcat.append(w.transpose(0, 1).reshape(4 * H, In + H).contiguous())
+                self.bcat.append((b_ih.detach() + b_hh.detach()).view(4, H).t().contiguous().view(-1))
+        self._reorder = None
+
+    def prime(self, token):
+        """Step 0's input: zero state (as allocated), `token` (<BOS>) in every row."""
+        self.xin[0][0, :, :self.in_dim[0]] = self.emb[token]
+
+    def step(self):
+        """All layers, slot 0 -> slot 1: one launch per layer.  Layer l also writes its h into layer l+1's x part."""
+        for l in range(self.n):
+            In = self.in_dim[l]
+            nxt = self.xin[l + 1][0][:, :self.H] if l + 1 < self.n else None
+            lm_step(self.R, self.H, In, self.xin[l][0], self.wcat[l], self.bcat[l], self.cell[l][0], self.cell[l][1],
+                    self.xin[l][1][:, In:], nxt)
+
+    def top(self):
+        """[R, H] view (row stride In + H) of the last layer's new h: the operand of the LM's output layer."""
+        return self.xin[-1][1][:, self.in_dim[-1]:]
+
+    def reorder_struct(self):
+        if self._reorder is None:
+            st = BeamLmState(n_layers=self.n, H=self.H, emb=ptr(self.emb))
+            for l in range(self.n):
+                st.in_dim[l] = self.in_dim[l]
+                st.x_src[l], st.x_dst[l] = self.xin[l][1].data_ptr(), self.xin[l][0].data_ptr()
+                st.c_src[l], st.c_dst[l] = self.cell[l][1].data_ptr(), self.cell[l][0].data_ptr()
+            self._reorder = st
+        return self._reorder
 
 
 FEED_PREDICTED, FEED_SMOOTH, FEED_TEACHER, FEED_NONE = 0, 1, 2, 3

@@ -390,12 +390,25 @@ class Decoder(torch.nn.Module):
             ys_log_probs.fused_sum = total
         return logits.transpose(0, 1), ys_log_probs, prediction, ws
 
-    def recognize_beams(self, enc_pad, enc_len, max_dec_timesteps, topk, length_penalty=0.0, nbest=False):
+    def recognize_beams(self, enc_pad, enc_len, max_dec_timesteps, topk, length_penalty=0.0, nbest=False, *, lm=None,
+                        lm_weight=0.0):
         """Beam search with beam width topk (1..16) - model.py:369-406, which the reference left unfinished; the semantics
         are DESIGN 4.8's.  Eval arithmetic (no dropout, attention temperature 2.0), per utterance; hypotheses are ranked by
         score / len**length_penalty (score: the sum of the tokens' log-probabilities, <EOS> included).
+        lm (an LM module) with lm_weight != 0: shallow fusion - every candidate token's score is
+        log p_asr + lm_weight * log p_lm, the LM stepped on the device beside the decoder, eval arithmetic.
         -> (prediction [B, L] int64, scores [B]): the best hypothesis, <EOS>-padded to L = max_dec_timesteps; with
         nbest=True all topk hypotheses, ranked: ([B, topk, L], [B, topk]).  topk = 1 is greedy decoding."""
+        lm_t = None
+        if lm is not None:
+            V = self.output_layer.weight.shape[0]
+            if lm.output_dim != V:
+                raise ValueError("the LM predicts %d tokens, the decoder %d" % (lm.output_dim, V))
+            if (lm.bos, lm.eos) != (self.bos, self.eos):
+                raise ValueError("the LM's <BOS>/<EOS> (%d, %d) are not the decoder's (%d, %d)"
+                                 % (lm.bos, lm.eos, self.bos, self.eos))
+            lm_t = dict(emb=lm.embedding.weight, layers=[lm.LSTM.direction_params(l) for l in range(lm.n_layers)],
+                        w_out=lm.output_layer.weight, b_out=lm.output_layer.bias)
         att = self.attention
         att.reset()
         with torch.no_grad():
@@ -407,7 +420,7 @@ class Decoder(torch.nn.Module):
                 P, Q, self.embedding.weight, cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh,
                 att.mlp_dec.weight, att.loc_conv.weight, att.mlp_att.weight, att.gvec.weight, att.mlp_o.bias,
                 self.output_layer.weight, self.output_layer.bias, w0, int(topk), int(max_dec_timesteps), self.bos,
-                self.eos, length_penalty=float(length_penalty))
+                self.eos, length_penalty=float(length_penalty), lm=lm_t, lm_weight=float(lm_weight))
             tokens = tokens.long()
         if nbest:
             return tokens, scores
@@ -441,14 +454,15 @@ class E2E(torch.nn.Module):
                             smooth=smooth, scaling=scaling, label_smoothing=label_smoothing, olength=olength,
                             loss_norm=loss_norm)
 
-    def recognize_beams(self, data, ilens, max_dec_timesteps, topk, length_penalty=0.0, nbest=False):
+    def recognize_beams(self, data, ilens, max_dec_timesteps, topk, length_penalty=0.0, nbest=False, *, lm=None,
+                        lm_weight=0.0):
         """Encoder, then Decoder.recognize_beams (not a reference method)."""
         if data.is_cuda:
             hb.upload_side_stream_for(data.shape[0] * data.shape[1])
         with torch.no_grad():
             enc_h, enc_lens = self.encoder(data, ilens)
             return self.decoder.recognize_beams(enc_h, enc_lens, max_dec_timesteps, topk, length_penalty=length_penalty,
-                                                nbest=nbest)
+                                                nbest=nbest, lm=lm, lm_weight=lm_weight)
 
     def mask_and_cal_loss(self, log_probs, ys, mask=None):
         if mask is None:

@@ -1136,7 +1136,7 @@ BEAM_POLL_STEPS = 8          # the host reads the all-done word of a beam search
 
 
 def beam_search(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo, w_out, b_out, w0, beam, L, bos, eos,
-                length_penalty=0.0, scaling=2.0):
+                length_penalty=0.0, scaling=2.0, lm=None, lm_weight=0.0):
     """Beam search over the decoder (Decoder.recognize_beams, model.py:369-406; semantics in DESIGN 4.8), eval arithmetic.
 
     Inputs as decoder_sequence's for B utterances; the search runs B*beam rows (row b*beam + k).  Every step is
@@ -1144,6 +1144,11 @@ def beam_search(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo
     reads its input slot (X[1], cstate[0], ws[0]) and writes its output slot (X[2], cstate[1], ws[1]); the reorder gathers
     the output slot back into the input slot, so two step slots serve any L.  Step 0 runs at s = 1 as well, from an input
     slot primed with what s = 0 would read (zero z, ctx and cell state, <BOS>, w0).
+    lm (with lm_weight != 0): shallow fusion with a language model - dict(emb [V, E'], layers
+    [(w_ih, w_hh, b_ih, b_hh)] of the stacked LSTM, w_out [V, H], b_out [V]).  Every beam row carries the LM's state; per
+    step the LM consumes the decoder's input token (asr_lm_step_f32 per layer, the output GEMM) and the select ranks
+    score + logp + lm_weight * logp_lm; the reorder gathers both states in one launch: 8 + n_layers launches.  Without it
+    (or with lm_weight == 0) the search is the plain one, launch for launch.
     Returns tokens [B, beam, L] int32 (ranked, <EOS>-padded), scores [B, beam], lengths [B, beam]."""
     dev = P.device
     B, Tp, A = P.shape
@@ -1156,8 +1161,17 @@ def beam_search(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo
     KX = D + O + E
     R = B * beam
     f32 = dict(device=dev, dtype=torch.float32)
+    fused = lm is not None and float(lm_weight) != 0.0
+    if fused and (tuple(lm["w_out"].shape) != (V, lm["layers"][-1][1].shape[1]) or lm["emb"].shape[0] != V):
+        raise ValueError("the LM's vocabulary (%d outputs, %d embeddings) is not the decoder's (%d)"
+                         % (lm["w_out"].shape[0], lm["emb"].shape[0], V))
     with torch.no_grad():
         search = hb.BeamSearch(B, beam, V, L, eos, dev)
+        if fused:
+            lms = hb.LmStepState(R, lm["emb"], lm["layers"], dev)
+            lms.prime(bos)
+            lm_w_out, lm_b_out = lm["w_out"].detach().contiguous(), lm["b_out"].detach().contiguous()
+            lm_logits = torch.empty(R, V, **f32)
         ws = dict(P=P.repeat_interleave(beam, 0).contiguous(), Q=Q.repeat_interleave(beam, 0).contiguous(),
                   w0=w0.repeat_interleave(beam, 0).contiguous(), wcat=torch.empty(4 * D, KX, **f32),
                   bcat=torch.empty(4 * D, **f32), wattT=torch.empty(C, A, **f32),
@@ -1183,12 +1197,21 @@ def beam_search(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo
         for t in range(L):
             hb.check(lib.asr_dec_step_fwd(ctypes.byref(fs), 1, hb.stream()), "asr_dec_step_fwd")
             hb.gemm_skinny(X[2][:, :D + O], w_out_c, bias=b_out, out=logits)
-            search.select(logits, t)
+            if fused:
+                lms.step()
+                hb.gemm_skinny(lms.top(), lm_w_out, bias=lm_b_out, out=lm_logits)
+                search.select_lm(logits, lm_logits, lm_weight, t)
+                launches += lms.n + 1                      # the LM's layers and its output GEMM
+            else:
+                search.select(logits, t)
             steps += 1
             launches += 6                                  # 4 decoder-step kernels, the GEMM, the select
             if t == L - 1:
                 break
-            search.reorder(t, X[2], X[1], cst[1], cst[0], wts[1], wts[0], emb_c, D, O)
+            if fused:
+                search.reorder_lm(t, lms, (X[2], X[1], cst[1], cst[0], wts[1], wts[0], emb_c, D, O))
+            else:
+                search.reorder(t, X[2], X[1], cst[1], cst[0], wts[1], wts[0], emb_c, D, O)
             launches += 1
             if (t + 1) % BEAM_POLL_STEPS == 0:
                 # the word copied BEAM_POLL_STEPS steps ago: the host waits for that step at most, never for this one
@@ -1199,7 +1222,7 @@ def beam_search(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo
                 landing.copy_(search.ndone, non_blocking=True)
                 polled = torch.cuda.Event()
                 polled.record()
-        hb.LAUNCHES["beam_step"] += steps
-        hb.LAUNCHES["beam_launch"] += launches
+        hb.LAUNCHES["beam_lm_step" if fused else "beam_step"] += steps
+        hb.LAUNCHES["beam_lm_launch" if fused else "beam_launch"] += launches
         out = search.backtrack(length_penalty)
     return out

@@ -252,14 +252,15 @@ class Solver(object):
             out = run()
         return out
 
-    def _beam(self, xs, ilens, beam_size):
-        """Best beam-search hypothesis ids for one batch (E2E.recognize_beams).  The encoder still runs on the persistent
-        LSTM kernels: the abort word is checked after the decode and the batch repeated on the per-step kernels, as in
-        _greedy."""
+    def _beam(self, xs, ilens, beam_size, lm_weight=0.0):
+        """Best beam-search hypothesis ids for one batch (E2E.recognize_beams; lm_weight > 0: rescored by the judge, shallow
+        fusion).  The encoder still runs on the persistent LSTM kernels: the abort word is checked after the decode and
+        the batch repeated on the per-step kernels, as in _greedy."""
         def run():
             prediction, _ = self.model.recognize_beams(
                 xs, ilens, self.config["max_dec_timesteps"], beam_size,
-                length_penalty=float(self.config.get("beam_length_penalty", 0.0)))
+                length_penalty=float(self.config.get("beam_length_penalty", 0.0)),
+                lm=self.judge if lm_weight > 0 else None, lm_weight=lm_weight)
             return prediction.cpu().numpy().tolist()
         out = run()
         if self._abort_seen(xs.device):
@@ -311,11 +312,21 @@ class Solver(object):
         self.judge.train()
         return total / len(self.dev_loader), sents
 
-    def test(self, state_dict=None):
+    def test(self, state_dict=None, judge_state_dict=None):
         if state_dict:
             self.model.load_state_dict(state_dict)
         else:
             self.load_model(self.config["load_model_path"], self.config["load_optimizer"])
+        # `lm_weight` (not a reference key, like beam_size): > 0 decodes with the judge's log-probabilities added to the
+        # recogniser's, weighted (shallow fusion), also at beam_size 1; the judge is the one saved beside the recogniser
+        lm_weight = float(self.config.get("lm_weight", 0.0) or 0.0)
+        if lm_weight > 0:
+            if judge_state_dict:
+                self.judge.load_state_dict(judge_state_dict)
+            else:
+                self.load_judge(self.config["load_judge_path"], False)
+            judge_was_training = self.judge.training
+            self.judge.eval()
         test_set = self.config["test_set"]
         loader = get_data_loader(self._dataset(test_set, None, sort=False), batch_size=1, shuffle=False,
                                  drop_last=False)
@@ -324,9 +335,14 @@ class Solver(object):
         preds, refs = [], []
         for batch in self._feed(loader, sharded=False):
             xs, ilens, _ = batch
-            preds += self._beam(xs, ilens, beam_size) if beam_size > 1 else self._greedy(xs, ilens)
+            if lm_weight > 0:
+                preds += self._beam(xs, ilens, beam_size, lm_weight)
+            else:
+                preds += self._beam(xs, ilens, beam_size) if beam_size > 1 else self._greedy(xs, ilens)
             refs += batch.ys_host
         self.model.train()
+        if lm_weight > 0:
+            self.judge.train(judge_was_training)
         cer, hyp_sents, _ = self.ind2sent(preds, refs)
         with open(f"{test_set}.txt", "w") as f:
             f.writelines(f"{p}\n" for p in hyp_sents)
