@@ -58,11 +58,16 @@ class DecFeedbackBwd(ctypes.Structure):
     _fields_ = [("V", c_i), ("scaling", c_f), ("w_out", c_p), ("emb", c_p), ("probs", c_p), ("dlfb", c_p)]
 
 
+_DEC_DIMS = ("B", "nb", "Tp", "A", "D", "O", "E", "C", "K", "L")
+_DEC_FWD_PTRS = ("P", "Q", "bo", "wcat", "bcat", "wdec", "convw", "watt", "wattT", "gvec", "w0", "xmask",
+                 "X", "Xd", "gates", "cstate", "Dproj", "fconv", "S", "energy", "ws")
+_DEC_BWD_PTRS = ("wcatT", "wdecT", "dws", "G", "dwext", "dwraw", "dfpart", "dP", "dgates", "dD",
+                 "dcell", "dgvec_part", "dwatt_part", "dconv_part")
+
+
 class DecFwd(ctypes.Structure):
     """asr_dec_fwd_t"""
-    _fields_ = [(n, c_i) for n in ("B", "nb", "Tp", "A", "D", "O", "E", "C", "K", "L")] + [("scaling", c_f)] + \
-               [(n, c_p) for n in ("P", "Q", "bo", "wcat", "bcat", "wdec", "convw", "watt", "wattT", "gvec", "w0", "xmask",
-                                   "X", "Xd", "gates", "cstate", "Dproj", "fconv", "S", "energy", "ws")]
+    _fields_ = [(n, c_i) for n in _DEC_DIMS] + [("scaling", c_f)] + [(n, c_p) for n in _DEC_FWD_PTRS]
 
 
 class Beam(ctypes.Structure):
@@ -89,9 +94,96 @@ class BeamLmState(ctypes.Structure):
 
 class DecBwd(ctypes.Structure):
     """asr_dec_bwd_t"""
-    _fields_ = [("f", DecFwd)] + \
-               [(n, c_p) for n in ("wcatT", "wdecT", "dws", "G", "dwext", "dwraw", "dfpart", "dP", "dgates", "dD",
-                                   "dcell", "dgvec_part", "dwatt_part", "dconv_part")]
+    _fields_ = [("f", DecFwd)] + [(n, c_p) for n in _DEC_BWD_PTRS]
+
+
+def _fptr(t, off=0):
+    """device pointer of float tensor t advanced by `off` elements (None stays NULL)."""
+    return None if t is None else c_p(t.data_ptr() + 4 * int(off))
+
+
+class DecBuffers(object):
+    """Every buffer the decoder kernels read or write for B utterances and L step slots (X / Xd / G hold L + 1: slot s + 1
+    is step s's output), and the two C structs over them (DecFwd / DecBwd).  Attributes carry the struct's field names.
+      the constructor allocates what the kernels own: the packed weights (wcat, bcat, wattT; wcatT, wdecT), the per-step state,
+            staging tensors for the inputs, and - with_bwd - the backward's scratch and its accumulators `acc` (a dict: G,
+            dwext, dP, dcell, dgvec_part, dwatt_part, dconv_part), cut from ONE buffer `zbuf` that one fill zeroes;
+      bind()    the per-call inputs used as they are (no staging copies), kept alive here until the next bind();
+      fwd_struct / bwd_struct   the structs for batch rows [b0, b0 + nb): every per-row pointer advanced by b0 rows;
+      accumulators(base)   `acc` laid out over another zeroed buffer (the step arena's slice) instead of zbuf."""
+
+    _ACC = ("G", "dwext", "dP", "dcell", "dgvec_part", "dwatt_part", "dconv_part")
+
+    def __init__(self, B, Tp, A, D, O, E, C, K, L, drop, dev, with_bwd):
+        f32 = dict(device=dev, dtype=torch.float32)
+        KX = D + O + E
+        self.dims = dict(B=B, Tp=Tp, A=A, D=D, O=O, E=E, C=C, K=K, L=L)
+        self.B, self.L, self.KX, self.scaling = B, L, KX, 2.0
+        self.bo = self.wdec = self.watt = None
+        self.P, self.Q, self.w0 = torch.empty(B, Tp, A, **f32), torch.empty(B, Tp, O, **f32), torch.empty(B, Tp, **f32)
+        self.wcat, self.bcat, self.wattT = torch.empty(4 * D, KX, **f32), torch.empty(4 * D, **f32), torch.empty(C, A, **f32)
+        self.convw, self.gvec = torch.empty(C, 2 * K + 1, **f32), torch.empty(A, **f32)
+        self.X = torch.empty(L + 1, B, KX, **f32)
+        self.Xd = torch.empty(L + 1, B, KX, **f32) if drop else None
+        self.xmask = torch.empty(L, B, O + E, **f32) if drop else None
+        self.gates, self.cstate = torch.empty(L, B, 4 * D, **f32), torch.empty(L, B, D, **f32)
+        self.Dproj, self.fconv = torch.empty(L, B, A, **f32), torch.empty(L, B, C, Tp, **f32)
+        self.S, self.energy, self.ws = torch.empty(L, B, Tp, A, **f32), torch.empty(L, B, Tp, **f32), torch.empty(L, B, Tp, **f32)
+        # floats per batch row of every field a row group advances (the fields not named here are shared by all rows)
+        self._row = dict(P=Tp * A, Q=Tp * O, w0=Tp, xmask=O + E, X=KX, Xd=KX, gates=4 * D, cstate=D, Dproj=A, fconv=C * Tp,
+                         S=Tp * A, energy=Tp, ws=Tp, dws=Tp, G=KX, dwext=Tp, dwraw=Tp, dfpart=C * Tp, dP=Tp * A, dgates=4 * D,
+                         dD=A, dcell=D, dgvec_part=A, dwatt_part=A * C, dconv_part=C * (2 * K + 1))
+        self.zbuf = self.acc = None
+        if with_bwd:
+            ntile = (A + 63) // 64
+            # everything the backward accumulates into lives in ONE buffer (16-byte aligned slices): one fill per step
+            shapes = dict(G=(L + 1, B, KX), dwext=(C, B, Tp), dP=(B, Tp, A), dcell=(B, D), dgvec_part=(B, A),
+                          dwatt_part=(B, A, C), dconv_part=(B, C, 2 * K + 1))
+            self._acc_layout, off = [], 0
+            for name in self._ACC:
+                strides = torch.empty(shapes[name], device="meta").stride()
+                self._acc_layout.append((name, shapes[name], strides, off))
+                off += (strides[0] * shapes[name][0] + 3) // 4 * 4
+            self.zbuf = torch.empty(off, **f32)
+            self.acc = self.accumulators(self.zbuf)
+            self.wcatT, self.wdecT = torch.empty(KX, 4 * D, **f32), torch.empty(D, A, **f32)
+            self.dwraw, self.dfpart = torch.empty(B, Tp, **f32), torch.empty(ntile, B, C, Tp, **f32)
+            self.dgates, self.dD = torch.empty(L, B, 4 * D, **f32), torch.empty(L, B, A, **f32)
+            self.dws, self.Mf = torch.empty(L, B, Tp, **f32), torch.empty(L, B, C, Tp, **f32)
+        else:
+            self.wcatT = self.wdecT = None
+
+    def bind(self, P=None, Q=None, w0=None, convw=None, gvec=None, bo=None, wdec=None, watt=None, xmask=None, scaling=None):
+        """The inputs of a call (those given; the others stay as they are), made contiguous and kept alive here."""
+        given = dict(P=P, Q=Q, w0=w0, bo=bo, wdec=wdec, watt=watt, xmask=xmask,
+                     convw=None if convw is None else convw.reshape(self.convw.shape),
+                     gvec=None if gvec is None else gvec.reshape(self.gvec.shape))
+        for name, t in given.items():
+            if t is not None:
+                setattr(self, name, t.contiguous())
+        if scaling is not None:
+            self.scaling = float(scaling)
+
+    def accumulators(self, base):
+        """The backward's accumulators as views of `base`, a flat buffer of zbuf's size (one as_strided each: a slice + a
+        view per accumulator cost the host 20 us more per backward, and the small configurations are host-bound)."""
+        first = base.storage_offset()
+        return {name: base.as_strided(shape, strides, first + off) for name, shape, strides, off in self._acc_layout}
+
+    def fwd_struct(self, b0=0, nb=None):
+        """asr_dec_fwd_t for rows [b0, b0 + nb) (pointers pre-offset, B = stride)."""
+        row = self._row
+        return DecFwd(nb=self.B if nb is None else nb, scaling=self.scaling,
+                      **{n: _fptr(getattr(self, n), b0 * row.get(n, 0)) for n in _DEC_FWD_PTRS}, **self.dims)
+
+    def bwd_struct(self, b0=0, nb=None, acc=None, with_dws=True):
+        """asr_dec_bwd_t for rows [b0, b0 + nb).  acc: the accumulators to use (accumulators(); None: those in zbuf);
+        with_dws False: no gradient arrives through the attention weights (dws = NULL)."""
+        acc, own, row = self.acc if acc is None else acc, self.__dict__, self._row
+        ptrs = {n: _fptr(acc[n] if n in acc else own[n], b0 * row.get(n, 0)) for n in _DEC_BWD_PTRS}
+        if not with_dws:
+            ptrs["dws"] = None
+        return DecBwd(f=self.fwd_struct(b0, nb), **ptrs)
 
 
 def load():
@@ -871,6 +963,24 @@ def count_path(op, persistent, why=""):
         raise RuntimeError("%s fell back to the per-step kernels (%s) while the persistent path was required" % (op, why))
 
 
+ASR_E_SHAPE = -2             # include/asr_hip.h: a launcher's answer for sizes / a device its kernel does not cover
+
+
+def persistent_ran(rc, what):
+    """The return code of a persistent entry point -> True: it ran; False: it declined (ASR_E_SHAPE - the caller takes the
+    per-step kernels); anything else is an error."""
+    if rc == 0:
+        return True
+    if rc != ASR_E_SHAPE:
+        check(rc, what)
+    return False
+
+
+def _scratch_ptrs(device):
+    xch, ctrl = persist_scratch(device)
+    return c_p(xch.data_ptr()), c_p(ctrl.data_ptr())
+
+
 class require_persistent(object):
     """Context manager: any sequence operator that does not run on its persistent kernel raises."""
 
@@ -1090,15 +1200,11 @@ def lstm_seq_fwd(gates, w_hh, lens, y, c, use_graphs=True, rows=None):
     if rows is not None:
         assert B == 1 and T == rows.R
         T, B = rows.T, rows.B
-    if USE_PERSIST:
-        xch, ctrl = persist_scratch(gates.device)
-        rc = lib.asr_lstm_seq_fwd_persist(T, B, B, H, ndir, ptr(gates), ptr(w_hh), ptr(lens), rb, re, rh, ptr(y), ptr(c),
-                                          c_p(xch.data_ptr()), c_p(ctrl.data_ptr()), ARITH[0], stream())
-        if rc == 0:
-            count_path("lstm_fwd", True)
-            return
-        if rc != -2:                      # anything but ASR_E_SHAPE is an error
-            check(rc, "asr_lstm_seq_fwd_persist")
+    if USE_PERSIST and persistent_ran(
+            lib.asr_lstm_seq_fwd_persist(T, B, B, H, ndir, ptr(gates), ptr(w_hh), ptr(lens), rb, re, rh, ptr(y), ptr(c),
+                                         *_scratch_ptrs(gates.device), ARITH[0], stream()), "asr_lstm_seq_fwd_persist"):
+        count_path("lstm_fwd", True)
+        return
     count_path("lstm_fwd", False, "H=%d B=%d ndir=%d persist=%s" % (H, B, ndir, USE_PERSIST))
     groups = row_groups(B)
     gh = [graphs_for(i) if use_graphs else None for i in range(len(groups))]     # created on the calling thread
@@ -1132,26 +1238,18 @@ def lstm_seq_bwd(gates, w_hhT, lens, dy, c, dcarry, y=None, dw_hh=None, db=None,
         T, B = rows.T, rows.B
     fuses = USE_PERSIST and rows is None and lib.asr_lstm_bwd_persist_fuses_dw(H, ar) == 1 and y is not None and dw_hh is not None
     yk, dwk = (y, dw_hh) if fuses else (None, None)
-    if USE_PERSIST and w_hh is not None:
-        xch, ctrl = persist_scratch(gates.device)
-        rc = lib.asr_lstm_seq_bwd_persist_w(T, B, B, H, ndir, ptr(gates), ptr(w_hh), ptr(lens), rb, re, rh, ptr(dy), ptr(c),
-                                            ptr(yk), ptr(dwk), ptr(db), c_p(xch.data_ptr()), c_p(ctrl.data_ptr()), ar, stream())
-        if rc == 0:
-            count_path("lstm_bwd", True)
-            return fuses, db is not None
-        if rc != -2:
-            check(rc, "asr_lstm_seq_bwd_persist_w")
+    def persistent(entry, what, w):
+        return persistent_ran(entry(T, B, B, H, ndir, ptr(gates), ptr(w), ptr(lens), rb, re, rh, ptr(dy), ptr(c), ptr(yk),
+                                    ptr(dwk), ptr(db), *_scratch_ptrs(gates.device), ar, stream()), what)
+
+    if USE_PERSIST and w_hh is not None and persistent(lib.asr_lstm_seq_bwd_persist_w, "asr_lstm_seq_bwd_persist_w", w_hh):
+        count_path("lstm_bwd", True)
+        return fuses, db is not None
     if callable(w_hhT):
         w_hhT = w_hhT()
-    if USE_PERSIST:
-        xch, ctrl = persist_scratch(gates.device)
-        rc = lib.asr_lstm_seq_bwd_persist(T, B, B, H, ndir, ptr(gates), ptr(w_hhT), ptr(lens), rb, re, rh, ptr(dy), ptr(c),
-                                          ptr(yk), ptr(dwk), ptr(db), c_p(xch.data_ptr()), c_p(ctrl.data_ptr()), ar, stream())
-        if rc == 0:
-            count_path("lstm_bwd", True)
-            return fuses, db is not None
-        if rc != -2:
-            check(rc, "asr_lstm_seq_bwd_persist")
+    if USE_PERSIST and persistent(lib.asr_lstm_seq_bwd_persist, "asr_lstm_seq_bwd_persist", w_hhT):
+        count_path("lstm_bwd", True)
+        return fuses, db is not None
     count_path("lstm_bwd", False, "H=%d B=%d ndir=%d persist=%s" % (H, B, ndir, USE_PERSIST))
     groups = row_groups(B)
     gh = [graphs_for(i) for i in range(len(groups))]
@@ -1169,6 +1267,163 @@ def lstm_seq_bwd(gates, w_hhT, lens, dy, c, dcarry, y=None, dw_hh=None, db=None,
 
     run_grouped(groups, one)
     return False, False
+
+
+# ---------------------------------------------------------------------------------------------------
+# The decoder's sequence operators on a DecBuffers: as for the LSTM, the persistent kernel first, the per-step kernels when it is
+# switched off or declines.
+def dec_step_fwd(fs, s):
+    """Decoder step s on the per-step kernels (fs: DecBuffers.fwd_struct())."""
+    check(load().asr_dec_step_fwd(ctypes.byref(fs), s, stream()), "asr_dec_step_fwd")
+
+
+def att_step_fwd(fs, s):
+    """The attention half of step s alone: X[s + 1][:, :D] (the decoder state) and ws[s - 1] / w0 -> X[s + 1][:, D:D+O], ws[s]."""
+    check(load().asr_att_step_fwd(ctypes.byref(fs), s, stream()), "asr_att_step_fwd")
+
+
+def dec_step_bwd(bs, s):
+    check(load().asr_dec_step_bwd(ctypes.byref(bs), s, stream()), "asr_dec_step_bwd")
+
+
+def dec_shape(buf):
+    return "D=%(D)d A=%(A)d O=%(O)d E=%(E)d Tp=%(Tp)d B=%(B)d" % buf.dims
+
+
+def dec_seq_fwd(buf, use_graphs=True):
+    """All L steps over inputs that are complete in X / Xd before the first one (teacher forcing)."""
+    lib, L = load(), buf.L
+    groups = row_groups(buf.B)
+    done = False
+    if USE_PERSIST_DEC and len(groups) == 1:          # one launch for the whole sequence
+        entry = lib.asr_dec_seq_fwd_persist_fault if DEC_FAULT[0] else lib.asr_dec_seq_fwd_persist
+        done = persistent_ran(entry(ctypes.byref(buf.fwd_struct()), *_scratch_ptrs(buf.X.device), stream()),
+                              "asr_dec_seq_fwd_persist")
+    count_path("dec_fwd", done, dec_shape(buf))
+    if not done:
+        gh = [graphs_for(i) if use_graphs else None for i in range(len(groups))]
+
+        def run(gi, grp, st):
+            check(lib.asr_dec_seq_fwd(ctypes.byref(buf.fwd_struct(*grp)), 0, L, gh[gi], st), "asr_dec_seq_fwd")
+
+        run_grouped(groups, run)
+
+
+def dec_free_fwd(buf, w_out, b_out, emb, logits, pred, fed, probs, tokens=None, tf_flags=None, smooth=False, smooth_scaling=1.0,
+                 eos=-1):
+    """Free-running steps: per step the decoder chain, then ONE kernel for logits + argmax + the next step's embedding input
+    (teacher / predicted token, or the smooth embedding softmax(k*logit) @ E).  Step 0's input is in X[0] / Xd[0] already.
+    w_out [V, D+O] (V <= 128), emb [V, E], tokens [B, L] long (scheduled sampling: tf_flags[s] picks teacher or prediction) -
+    all contiguous; logits [L, B, V], pred / fed [L, B] long, probs [L-1, B, V] (smooth) are written.
+    -> True when the persistent kernel ran the sequence."""
+    B, L, DO, V = buf.B, buf.L, buf.dims["D"] + buf.dims["O"], w_out.shape[0]
+    X, Xd, xmask, dev = buf.X, buf.Xd, buf.xmask, buf.X.device
+    drop = Xd is not None
+    fs = buf.fwd_struct()
+    done = False
+    if USE_PERSIST_DEC and (tokens is None or not smooth) and V <= 64 and len(row_groups(B)) == 1:
+        # the whole sequence in one launch, the feedback computed in the kernel: no teacher tokens at all, or
+        # scheduled sampling (the host's per-step draws go along as a byte per step)
+        # decoding without autograd: a group of 4 utterances stops once all of them have emitted <EOS>; the
+        # outputs of the steps that are not run read <EOS> / zero logits / zero attention weights
+        stop = DECODE_EARLY_STOP and eos >= 0 and not torch.is_grad_enabled() and tokens is None
+        if stop:
+            pred.fill_(eos)
+            logits.zero_()
+            buf.ws.zero_()
+        tf_dev = None
+        if tokens is not None:
+            tf_dev = torch.tensor([1 if (tf_flags is None or tf_flags[i]) else 0 for i in range(L)],
+                                  dtype=torch.uint8).to(dev, non_blocking=True)
+        fb = DecFeedback(
+            tokens=_lptr(tokens), ld_tokens=int(tokens.stride(0)) if tokens is not None else 0, teacher=_lptr(tf_dev),
+            mode=2 if smooth else 1, V=V, eos=eos if stop else -1, scaling=float(smooth_scaling), w_out=_fptr(w_out),
+            b_out=_fptr(b_out.contiguous()), emb=_fptr(emb), logits=_fptr(logits), probs=_fptr(probs) if smooth else None,
+            pred=_lptr(pred), fed=_lptr(fed))
+        done = persistent_ran(load().asr_dec_seq_fwd_persist_free(ctypes.byref(fs), ctypes.byref(fb), *_scratch_ptrs(dev),
+                                                                  stream()), "asr_dec_seq_fwd_persist_free")
+        if done and stop and L > 1:
+            # the last step's logits come from X[L], which a stopped group never wrote: rows that had
+            # already emitted <EOS> keep the pre-filled outputs
+            lg_last = torch.empty(B, V, device=dev, dtype=torch.float32)
+            pr_last = torch.empty(B, dtype=torch.long, device=dev)
+            dec_feedback_fwd(X[L][:, :DO], w_out, b_out, emb, lg_last, pr_last, FEED_NONE)
+            live = pred[:L - 1].ne(eos).all(0)
+            pred[L - 1] = torch.where(live, pr_last, pred[L - 1])
+            logits[L - 1] = torch.where(live.unsqueeze(1), lg_last, logits[L - 1])
+        elif done:
+            dec_feedback_fwd(X[L][:, :DO], w_out, b_out, emb, logits[L - 1], pred[L - 1], FEED_NONE)
+    count_path("dec_free", done, "%s V=%d teacher=%s" % (dec_shape(buf), V, tokens is not None))
+    if done:
+        return True
+    for s in range(L):
+        dec_step_fwd(fs, s)
+        last = s == L - 1
+        if last:
+            mode = FEED_NONE
+        elif tokens is not None:
+            mode = FEED_TEACHER if (tf_flags is None or tf_flags[s + 1]) else FEED_PREDICTED
+        else:
+            mode = FEED_SMOOTH if smooth else FEED_PREDICTED
+        dec_feedback_fwd(
+            X[s + 1][:, :DO], w_out, b_out, emb, logits[s], pred[s], mode, smooth_scaling,
+            tok=tokens[:, s + 1] if mode == FEED_TEACHER else None, fed=None if last else fed[s + 1],
+            probs=probs[s] if mode == FEED_SMOOTH else None,
+            x_emb_next=None if last else X[s + 1][:, DO:],
+            xd_emb_next=Xd[s + 1][:, DO:] if (drop and not last) else None,
+            mask=xmask[s + 1][:, buf.dims["O"]:] if (drop and not last) else None)
+    return False
+
+
+def dec_seq_bwd(buf, acc, with_dws, persistent, teacher):
+    """The backward of all L steps; the gradient of every step's [z, ctx] is in acc["G"][1:] already.  persistent: the forward's
+    inputs were all tokens (teacher forcing, or scheduled sampling inside the persistent forward: no gradient flows through an
+    argmax), so the persistent kernel may run it."""
+    lib, L = load(), buf.L
+    groups = row_groups(buf.B)
+    done = False
+    if USE_PERSIST_DEC_BWD and persistent and len(groups) == 1:
+        done = persistent_ran(lib.asr_dec_seq_bwd_persist(ctypes.byref(buf.bwd_struct(0, None, acc, with_dws)), _fptr(buf.Mf),
+                                                          *_scratch_ptrs(buf.X.device), stream()), "asr_dec_seq_bwd_persist")
+    count_path("dec_bwd", done, "%s teacher=%s" % (dec_shape(buf), teacher))
+    if not done:
+        gh = [graphs_for(i) for i in range(len(groups))]
+
+        def run(gi, grp, st):
+            bg = buf.bwd_struct(grp[0], grp[1], acc, with_dws)
+            check(lib.asr_dec_seq_bwd(ctypes.byref(bg), 0, L, gh[gi], st), "asr_dec_seq_bwd")
+
+        run_grouped(groups, run)
+
+
+def dec_smooth_bwd(buf, acc, with_dws, w_out, emb, probs, scaling, dlog):
+    """The backward of a free-running sequence with smooth-embedding feedback (model.py:341): emb_s = softmax(logit_{s-1}*k) @ E
+    couples step s to the logits of step s-1.  probs [L-1, B, V]: the forward's softmax outputs; dlog [L*B, V]: the gradient
+    of the logits from outside.  -> dtot [L, B, V] = dlog + what reaches the logits through the feedback (the weight gradients
+    that depend on it are the caller's: one product each over the whole sequence)."""
+    B, L, DO, V = buf.B, buf.L, buf.dims["D"] + buf.dims["O"], w_out.shape[0]
+    bs = buf.bwd_struct(0, None, acc, with_dws)
+    done = False
+    if USE_PERSIST_DEC_BWD and L > 1 and len(row_groups(B)) == 1:
+        # the whole free-running sequence in one launch: the feedback path (d(emb_s) -> logit_{s-1} -> [z, ctx]_{s-1})
+        # is carried inside the persistent kernel (dec_persist.hip, template FB)
+        dlfb = torch.zeros(L, B, V, device=dlog.device, dtype=torch.float32)
+        fbs = DecFeedbackBwd(V=V, scaling=float(scaling), w_out=_fptr(w_out), emb=_fptr(emb), probs=_fptr(probs),
+                             dlfb=_fptr(dlfb))
+        done = persistent_ran(load().asr_dec_seq_bwd_persist_free(ctypes.byref(bs), ctypes.byref(fbs), _fptr(buf.Mf),
+                                                                  *_scratch_ptrs(dlog.device), stream()),
+                              "asr_dec_seq_bwd_persist_free")
+    count_path("dec_bwd", done, "free-running smooth: %s V=%d L=%d fused-feedback=True" % (dec_shape(buf), V, L))
+    if done:
+        return dlog.view(L, B, V) + dlfb
+    # one kernel per step carries the embedding gradient back into logit_{s-1} and [z_{s-1}, c_{s-1}]
+    G = acc["G"]
+    dtot = dlog.clone().view(L, B, V)
+    for s in range(L - 1, -1, -1):
+        dec_step_bwd(bs, s)
+        if s >= 1:
+            dec_feedback_bwd(G[s][:, DO:], G[s][:, :DO], probs[s - 1], emb, w_out, scaling, dtot[s - 1])
+    return dtot
 
 
 # dropout masks regenerated inside the consuming kernels from a seed (off: materialised fp32 masks, as injected by tests)

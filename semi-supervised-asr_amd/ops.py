@@ -8,6 +8,10 @@ recurrence, decoder loop) never bounce through Python/autograd per time step:
     pyramid_concat    pair-concat (+dropout mask)                 -> asr_pyramid_concat_*
     decoder_sequence  all decoder steps incl. attention           -> asr_dec_* (+ GEMMs)
 
+The Functions here are autograd bookkeeping: which buffers, which gradients, in which order.  The ctypes calls, the choice
+"persistent kernel, else the per-step chain", the row groups and the path counters are hip_backend's (lstm_seq_fwd / _bwd;
+dec_seq_fwd, dec_free_fwd, dec_seq_bwd, dec_smooth_bwd on a hip_backend.DecBuffers).
+
 Workspaces.  The per-time-step launch chains are replayed as HIP graphs whose kernel arguments are baked
 (see csrc/graphs.h), so the chain buffers must keep their addresses from step to step.  Each chain op
 therefore leases a preallocated, shape-keyed workspace from a pool for the span forward -> end of backward
@@ -22,7 +26,6 @@ import ctypes
 import os
 import weakref
 
-import numpy as np
 import torch
 
 import hip_backend as hb
@@ -39,7 +42,8 @@ def gate_unperm(H, device):
 
 # -------------------------------------------------------------------------------------- workspace pool
 class _Lease(object):
-    """Exclusive use of one workspace (a dict of tensors) until release() / garbage collection."""
+    """Exclusive use of one workspace (the LSTM's dict of tensors, the decoder's hb.DecBuffers) until release() / garbage
+    collection."""
 
     def __init__(self, free_list, ws):
         self._free, self.ws = free_list, ws
@@ -497,58 +501,51 @@ class _LstmLayer(torch.autograd.Function):
                                              ws["c"], ws["dcarry"], y=y, dw_hh=ws["dw_hh"], db=ws["db"],
                                              w_hh=w_hh, rows=ctx.rows)                    # gates <- dG in place
         dG = gates.view(T * B, ndir * 4 * H)
+        # dW_hh[d] = sum_t dG_t[d]^T h_prev(t), h_prev = y[t-1] (d = 0) or y[t+1] (reverse direction) - unless the persistent
+        # kernel has summed it: ONE batched GEMM over the directions, K = (T-1)*B, accumulated into a zeroed output (no zero
+        # pass of its own).
+        #   d = 0: A = dG[B:, 0:4H],        B = y[:(T-1)B, 0:H]
+        #   d = 1: A = dG[:(T-1)B, 4H:8H],  B = y[B:, H:2H]          -> batch strides relative to d = 0 (may be negative)
+        # packed rows: K = R instead of R - 1 (a multiple of 4: the GEMM's fast kernels want that).  The one extra pair
+        # is (row R of dG, the last row of y) resp. (the last row of dG, row R of y): the last row of the matrix is a
+        # padding row - zero in both - and row R exists in the workspace and holds finite numbers (_lstm_workspace)
+        with_hh = not fused_dw and T > 1
+        ldg, ldy = ndir * 4 * H, ndir * H
+        kk = T * B if ctx.rows is not None else (T - 1) * B
+        hh_shape = (True, False, 4 * H, H, kk, ldg, ldy, H, ndir, 4 * H - B * ldg, B * ldy + H, 4 * H * H)
         # a small batch: this layer's weight gradients go beside the recurrence of the layer BELOW (_SideStream) - not those of
         # the bottom layer (no input gradient: nothing follows it in the pass, and the main stream's kernels have the whole chip)
-        side, side_dw_hh = False, False
-        if ctx.side_mask and ctx.needs_input_grad[0] and _SIDE.usable(ctx.side_mask):
-            side = True
+        side = bool(ctx.side_mask and ctx.needs_input_grad[0] and _SIDE.usable(ctx.side_mask))
+        if side:
             dw_ih = zeros_acc((ndir * 4 * H, I), dev)
             queue = zeros_acc((2,), dev)
             # (without a step arena the accumulators live in the leased workspace and are copied out below, on the main
             # stream: the side product then needs a tensor of its own)
             dw_hh_side = ws["dw_hh"] if zb is not None else torch.zeros_like(ws["dw_hh"])
-            if ctx.rows is not None and not fused_dw and T > 1 and ws.get("rows_written", 0) > T * B:
-                ws["gates_buf"][T * B].zero_()             # (row R of a workspace a longer batch has used: see below)
-                ws["y_buf"][T * B].zero_()
+        if with_hh and ctx.rows is not None and ws.get("rows_written", 0) > T * B:
+            # the workspace is shared by capacity: a LONGER batch left its own values in row R - finite ones normally,
+            # but NaN when that batch's launch aborted (the kernels poison their outputs), and 0 * NaN is NaN
+            ws["gates_buf"][T * B].zero_()
+            ws["y_buf"][T * B].zero_()
         dx = hb.gemm(dG, w_ih).view(T, B, I) if ctx.needs_input_grad[0] else None
         if side:
-            mask, with_hh, code = ctx.side_mask, (not fused_dw and T > 1), hb.current_arith()
-            kk = T * B if ctx.rows is not None else (T - 1) * B
+            mask, code = ctx.side_mask, hb.current_arith()
 
             def launch():
                 # (dG and y live in the layer's pooled workspace: no forward pass leases it again before the pass has ended)
                 hb.gemm_side(dG, x2, dw_ih, queue[0:1], mask, trans_a=True, arith=code)
                 if with_hh:
-                    ldg, ldy = ndir * 4 * H, ndir * H
-                    hb.gemm_side_batched(dG, y, dw_hh_side, queue[1:2], mask, True, False, 4 * H, H, kk, ldg, ldy, H, ndir,
-                                         4 * H - B * ldg, B * ldy + H, 4 * H * H, arith=code, a_off=B * ldg, b_off=0)
+                    hb.gemm_side_batched(dG, y, dw_hh_side, queue[1:2], mask, *hh_shape, arith=code, a_off=B * ldg)
             _SIDE.defer(dev, launch, (x2, queue))
-            side_dw_hh = with_hh
-            fused_dw = True                                # (done: skip the main-stream product below)
         else:
             dw_ih = _gemm_acc(dG, x2, trans_a=True, shape=(ndir * 4 * H, I))      # [ndir*4H, I]
         db = ws["db"] if fused_db else _colsum_acc(dG)     # the persistent kernels sum the bias gradient themselves
-        if not fused_dw and T > 1:
-            # dW_hh[d] = sum_t dG_t[d]^T h_prev(t), h_prev = y[t-1] (d = 0) or y[t+1] (reverse direction): ONE batched GEMM
-            # over the directions, K = (T-1)*B, accumulated into the zeroed dw_hh (no zero pass of its own).
-            #   d = 0: A = dG[B:, 0:4H],        B = y[:(T-1)B, 0:H]
-            #   d = 1: A = dG[:(T-1)B, 4H:8H],  B = y[B:, H:2H]          -> batch strides relative to d = 0 (may be negative)
-            ldg, ldy = ndir * 4 * H, ndir * H
-            # packed rows: K = R instead of R - 1 (a multiple of 4: the GEMM's fast kernels want that).  The one extra pair
-            # is (row R of dG, the last row of y) resp. (the last row of dG, row R of y): the last row of the matrix is a
-            # padding row - zero in both - and row R exists in the workspace and holds finite numbers (_lstm_workspace)
-            kk = T * B if ctx.rows is not None else (T - 1) * B
-            if ctx.rows is not None and ws.get("rows_written", 0) > T * B:
-                # the workspace is shared by capacity: a LONGER batch left its own values in row R - finite ones normally,
-                # but NaN when that batch's launch aborted (the kernels poison their outputs), and 0 * NaN is NaN
-                ws["gates_buf"][T * B].zero_()
-                ws["y_buf"][T * B].zero_()
-            hb.gemm_batched(dG, y, ws["dw_hh"], True, False, 4 * H, H, kk, ldg, ldy, H, ndir,
-                            4 * H - B * ldg, B * ldy + H, 4 * H * H, accumulate=True, a_off=B * ldg, b_off=0)
+        if with_hh and not side:
+            hb.gemm_batched(dG, y, ws["dw_hh"], *hh_shape, accumulate=True, a_off=B * ldg)
         # the gradients stay gate-interleaved (_LstmPack.backward converts every layer's in one launch); what lives in the
         # leased workspace is copied out of it, slices of the step's arena outlive the lease
         dw_hh, db = (ws["dw_hh"], db) if zb is not None else (ws["dw_hh"].clone(), db.clone() if fused_db else db)
-        if side_dw_hh:
+        if side and with_hh:
             dw_hh = dw_hh_side
         lease.release()
         return dx, None, None, None, None, dw_ih, dw_hh, db
@@ -629,65 +626,108 @@ def rows_unpack(packed, rows, T, fill=None, mask=None, fill_relu=False):
 
 
 # --------------------------------------------------------------------------------------
-def _p(t, off=0):
-    """device pointer of tensor t advanced by `off` float elements (None stays NULL)."""
-    return None if t is None else ctypes.c_void_p(t.data_ptr() + 4 * int(off))
+def _dec_clear(buf):
+    """Zeroed step inputs for a sequence whose inputs are filled in step by step -> fed [L, B] (zeros)."""
+    fed = torch.zeros(buf.L, buf.B, dtype=torch.long, device=buf.X.device)   # token whose embedding fed step s (-1: smooth)
+    buf.X.zero_()
+    if buf.Xd is not None:
+        buf.Xd.zero_()
+    return fed
 
 
-def _dec_fwd_struct(d, b0, nb):
-    """asr_dec_fwd_t for rows [b0, b0+nb) of the decoder buffers in dict d (pointers pre-offset, B = stride)."""
-    Tp, A, D, O, E, C, KX = d["Tp"], d["A"], d["D"], d["O"], d["E"], d["C"], d["KX"]
-    return hb.DecFwd(
-        B=d["B"], nb=nb, Tp=Tp, A=A, D=D, O=O, E=E, C=C, K=d["K"], L=d["L"], scaling=d["scaling"],
-        P=_p(d["P"], b0 * Tp * A), Q=_p(d["Q"], b0 * Tp * O), bo=_p(d["bo"]), wcat=_p(d["wcat"]), bcat=_p(d["bcat"]),
-        wdec=_p(d["wdec"]), convw=_p(d["convw"]), watt=_p(d["watt"]), wattT=_p(d["wattT"]), gvec=_p(d["gvec"]), w0=_p(d["w0"], b0 * Tp),
-        xmask=_p(d["xmask"], b0 * (O + E)), X=_p(d["X"], b0 * KX), Xd=_p(d["Xd"], b0 * KX),
-        gates=_p(d["gates"], b0 * 4 * D), cstate=_p(d["cstate"], b0 * D), Dproj=_p(d["Dproj"], b0 * A),
-        fconv=_p(d["fconv"], b0 * C * Tp), S=_p(d["S"], b0 * Tp * A), energy=_p(d["energy"], b0 * Tp),
-        ws=_p(d["ws"], b0 * Tp))
+def _dec_teacher_forced(buf, emb_w, tokens, w_out, b_out, use_graphs, skip_pred):
+    """Every step is fed its teacher token: the inputs are complete before the first step.  -> fed, logits, pred"""
+    B, L, D, O, E = (buf.dims[k] for k in "BLDOE")
+    X, Xd, xmask = buf.X, buf.Xd, buf.xmask
+    if (D + O) % 4 == 0 and E % 4 == 0 and (O + E) % 4 == 0 and tokens.stride(1) == 1:
+        # zero fills, embedding gather, input dropout, fed: one launch
+        fed = torch.empty(L, B, dtype=torch.long, device=X.device)
+        hb.dec_prepare(tokens, emb_w.contiguous(), xmask, X, Xd, fed, L, B, D, O, E)
+    else:
+        fed = _dec_clear(buf)
+        fed.copy_(tokens.t())
+        X[:L, :, D + O:] = emb_w[fed]
+        if Xd is not None:
+            Xd[:L, :, D + O:] = X[:L, :, D + O:] * xmask[:, :, O:]
+    hb.dec_seq_fwd(buf, use_graphs)
+    logits = hb.gemm(X[1:].view(L * B, buf.KX)[:, :D + O], w_out, trans_b=True, bias=b_out).view(L, B, w_out.shape[0])
+    # (skip_pred: the caller takes the argmax from the loss kernel that reads the logits anyway - label_logprob)
+    return fed, logits, (None if skip_pred else logits.argmax(-1))
 
 
-def _dec_bwd_struct(d, w, b0, nb):
-    Tp, A, D, C, KX = d["Tp"], d["A"], d["D"], d["C"], d["KX"]
-    taps = 2 * d["K"] + 1
-    return hb.DecBwd(
-        f=_dec_fwd_struct(d, b0, nb), wcatT=_p(w["wcatT"]), wdecT=_p(w["wdecT"]), dws=_p(w["dws"], b0 * Tp),
-        G=_p(w["G"], b0 * KX), dwext=_p(w["dwext"], b0 * Tp), dwraw=_p(w["dwraw"], b0 * Tp),
-        dfpart=_p(w["dfpart"], b0 * C * Tp), dP=_p(w["dP"], b0 * Tp * A), dgates=_p(w["dgates"], b0 * 4 * D),
-        dD=_p(w["dD"], b0 * A), dcell=_p(w["dcell"], b0 * D), dgvec_part=_p(w["dgvec_part"], b0 * A),
-        dwatt_part=_p(w["dwatt_part"], b0 * A * C), dconv_part=_p(w["dconv_part"], b0 * C * taps))
+def _dec_free_kernels(buf, emb_w, tokens, tf_flags, smooth, opts, w_out, b_out):
+    """Free-running steps on the feedback kernels (hb.dec_free_fwd: persistent, else per step); no sampling, V <= 128.
+    -> fed, logits, pred, probs_saved (smooth feedback: a tensor [L-1, B, V]), whether the persistent kernel ran"""
+    B, L, D, O = (buf.dims[k] for k in "BLDO")
+    X, Xd, dev, V = buf.X, buf.Xd, buf.X.device, w_out.shape[0]
+    fed = _dec_clear(buf)
+    logits = torch.empty(L, B, V, device=dev, dtype=torch.float32)
+    pred = torch.empty(L, B, dtype=torch.long, device=dev)
+    emb_c = emb_w.contiguous()
+    probs_saved = torch.empty(max(L - 1, 1), B, V, device=dev, dtype=torch.float32) if smooth and tokens is None else []
+    tok_c = tokens.contiguous() if tokens is not None else None
+    fed[0] = tok_c[:, 0] if tok_c is not None else opts["bos"]
+    X[0, :, D + O:] = emb_c[fed[0]]
+    if Xd is not None:
+        Xd[0, :, D + O:] = X[0, :, D + O:] * buf.xmask[0, :, O:]
+    done = hb.dec_free_fwd(buf, w_out, b_out, emb_c, logits, pred, fed, probs_saved, tok_c, tf_flags, smooth,
+                           float(opts.get("smooth_scaling", 1.0)), int(opts.get("eos", -1)))
+    return fed, logits, pred, probs_saved, done
 
 
-def _dec_workspace(B, Tp, A, D, O, E, C, K, L, drop, dev, with_bwd):
-    f32 = dict(device=dev, dtype=torch.float32)
-    KX = D + O + E
-    ws = dict(
-        P=torch.empty(B, Tp, A, **f32), Q=torch.empty(B, Tp, O, **f32), wcat=torch.empty(4 * D, KX, **f32),
-        bcat=torch.empty(4 * D, **f32), convw=torch.empty(C, 2 * K + 1, **f32), gvec=torch.empty(A, **f32),
-        wattT=torch.empty(C, A, **f32),
-        w0=torch.empty(B, Tp, **f32), X=torch.empty(L + 1, B, KX, **f32),
-        Xd=torch.empty(L + 1, B, KX, **f32) if drop else None,
-        xmask=torch.empty(L, B, O + E, **f32) if drop else None,
-        gates=torch.empty(L, B, 4 * D, **f32), cstate=torch.empty(L, B, D, **f32), Dproj=torch.empty(L, B, A, **f32),
-        fconv=torch.empty(L, B, C, Tp, **f32), S=torch.empty(L, B, Tp, A, **f32), energy=torch.empty(L, B, Tp, **f32),
-        ws=torch.empty(L, B, Tp, **f32))
-    if with_bwd:
-        ntile = (A + 63) // 64
-        # everything the backward accumulates into lives in ONE buffer (16-byte aligned slices): one fill per step
-        shapes = dict(G=(L + 1, B, KX), dwext=(C, B, Tp), dP=(B, Tp, A), dcell=(B, D), dgvec_part=(B, A),
-                      dwatt_part=(B, A, C), dconv_part=(B, C, 2 * K + 1))
-        sizes = {k: (int(np.prod(v)) + 3) // 4 * 4 for k, v in shapes.items()}
-        zbuf = torch.empty(sum(sizes.values()), **f32)
-        off = 0
-        for k, shp in shapes.items():
-            ws[k] = zbuf[off:off + int(np.prod(shp))].view(*shp)
-            off += sizes[k]
-        ws.update(
-            zbuf=zbuf, wcatT=torch.empty(KX, 4 * D, **f32), wdecT=torch.empty(D, A, **f32),
-            dwraw=torch.empty(B, Tp, **f32), dfpart=torch.empty(ntile, B, C, Tp, **f32),
-            dgates=torch.empty(L, B, 4 * D, **f32), dD=torch.empty(L, B, A, **f32),
-            dws=torch.empty(L, B, Tp, **f32), Mf=torch.empty(L, B, C, Tp, **f32))
-    return ws
+def _dec_free_torch(buf, emb_w, tokens, tf_flags, smooth, sample, opts, w_out, b_out):
+    """Free-running steps with the feedback in torch between the per-step kernels: sampling, V > 128, or the feedback kernels
+    switched off.  -> fed, logits, pred, probs_saved (smooth feedback: a list of L-1 tensors [B, V])"""
+    B, L, D, O = (buf.dims[k] for k in "BLDO")
+    X, Xd, dev, V = buf.X, buf.Xd, buf.X.device, w_out.shape[0]
+    fed = _dec_clear(buf)
+    fs = buf.fwd_struct()
+    logits = torch.empty(L, B, V, device=dev, dtype=torch.float32)
+    pred = torch.empty(L, B, dtype=torch.long, device=dev)
+    probs_saved = []
+    for s in range(L):
+        if s == 0:
+            tok = tokens[:, 0] if tokens is not None else torch.full((B,), opts["bos"], dtype=torch.long, device=dev)
+            fed[0] = tok
+            X[0, :, D + O:] = emb_w[tok]
+        elif tokens is not None:
+            tok = tokens[:, s] if tf_flags[s] else pred[s - 1]
+            fed[s] = tok
+            X[s, :, D + O:] = emb_w[tok]
+        elif not smooth:
+            fed[s] = pred[s - 1]
+            X[s, :, D + O:] = emb_w[pred[s - 1]]
+        else:
+            pr = torch.softmax(logits[s - 1] * opts["smooth_scaling"], dim=-1)
+            probs_saved.append(pr)
+            fed[s] = -1
+            hb.gemm(pr, emb_w, out=X[s][:, D + O:])
+        if Xd is not None:
+            Xd[s, :, D + O:] = X[s, :, D + O:] * buf.xmask[s, :, O:]
+        hb.dec_step_fwd(fs, s)
+        hb.gemm_skinny(X[s + 1][:, :D + O], w_out, bias=b_out, out=logits[s])
+        pred[s] = torch.distributions.Categorical(logits=logits[s]).sample() if sample else logits[s].argmax(-1)
+    return fed, logits, pred, probs_saved
+
+
+def _dec_smooth_bwd_torch(buf, acc, with_dws, w_out, emb_w, probs_saved, k, dw_out, db_out, demb_w):
+    """The smooth-feedback backward (hb.dec_smooth_bwd) of a forward that ran on torch glue: the extra gradient is injected
+    between the per-step kernels, and the weight gradients that depend on it are added step by step."""
+    D, O = buf.dims["D"], buf.dims["O"]
+    hb.count_path("dec_bwd", False, "free-running smooth: %s L=%d fused-feedback=False" % (hb.dec_shape(buf), buf.L))
+    bs = buf.bwd_struct(0, None, acc, with_dws)
+    G, X = acc["G"], buf.X
+    for s in range(buf.L - 1, -1, -1):
+        hb.dec_step_bwd(bs, s)
+        if s >= 1:
+            demb = G[s][:, D + O:]
+            pr = probs_saved[s - 1]
+            hb.gemm(pr, demb, trans_a=True, out=demb_w, accumulate=True, split_k=1)
+            dp = hb.gemm(demb, emb_w, trans_b=True)
+            dl = (k * pr * (dp - (pr * dp).sum(-1, keepdim=True))).contiguous()
+            hb.gemm(dl, w_out, out=G[s][:, :D + O], accumulate=True, split_k=1)
+            hb.gemm(dl, X[s][:, :D + O], trans_a=True, out=dw_out, accumulate=True, split_k=1)
+            hb.colsum(dl, out=db_out, accumulate=True)
 
 
 class _DecoderSeq(torch.autograd.Function):
@@ -699,6 +739,11 @@ class _DecoderSeq(torch.autograd.Function):
     opts   : dict(L, tokens [B,L] long or None, tf_flags list[bool] or None, smooth, smooth_scaling,
                   sample, scaling (attention temperature), xmask [L,B,O+E] or None, pooled)
     returns: logits [L,B,V], ws [L,B,Tp], prediction [L,B] (long)
+
+    The buffers are one hb.DecBuffers (leased from the pool when a backward follows); the launches are hip_backend's.
+    forward: teacher-forced (_dec_teacher_forced) | free-running on the feedback kernels (_dec_free_kernels) | free-running on
+    torch glue (_dec_free_torch).  backward: the chain backward (hb.dec_seq_bwd) | smooth feedback on the kernels
+    (hb.dec_smooth_bwd: persistent, else per step) | smooth feedback on torch glue (_dec_smooth_bwd_torch).
     """
 
     @staticmethod
@@ -714,319 +759,103 @@ class _DecoderSeq(torch.autograd.Function):
         K = (convw.shape[-1] - 1) // 2
         L = int(opts["L"])
         KX = D + O + E
-        f32 = dict(device=dev, dtype=torch.float32)
         xmask_in = opts.get("xmask")
         drop = xmask_in is not None
         pooled = bool(opts.get("pooled", False))
         if pooled:
             lease = _POOL.acquire(("dec", dev.index, B, Tp, A, D, O, E, C, K, L, drop),
-                                  lambda: _dec_workspace(B, Tp, A, D, O, E, C, K, L, drop, dev, True))
-            ws = lease.ws
+                                  lambda: hb.DecBuffers(B, Tp, A, D, O, E, C, K, L, drop, dev, True))
+            buf = lease.ws
         else:
-            lease, ws = None, _dec_workspace(B, Tp, A, D, O, E, C, K, L, drop, dev, False)
+            lease, buf = None, hb.DecBuffers(B, Tp, A, D, O, E, C, K, L, drop, dev, False)
         # [4D, KX] gate-interleaved rows + the transposed images the per-step forward (wattT) and the backward (wcatT, wdecT)
         # read, one launch
-        hb.dec_pack(w_ih, w_hh, b_ih, b_hh, wdec, watt, D, O, E, A, C, ws["wcat"], ws["bcat"], ws.get("wcatT"),
-                    ws.get("wdecT"), ws["wattT"])
-        # inputs used as they are (no staging copies); the dict keeps them alive until the backward has run
-        ws["convw"] = convw.reshape(C, 2 * K + 1).contiguous()
-        ws["gvec"] = gvec.reshape(A).contiguous()
-        ws["P"], ws["Q"], ws["w0"] = P.contiguous(), Q.contiguous(), w0.contiguous()
-        if drop:
-            ws["xmask"] = xmask_in.contiguous()
-        X, Xd, xmask = ws["X"], ws["Xd"], ws["xmask"]
-        wdec_c, watt_c, bo_c, w_out_c = wdec.contiguous(), watt.contiguous(), bo.contiguous(), w_out.contiguous()
-        d = dict(B=B, Tp=Tp, A=A, D=D, O=O, E=E, C=C, K=K, L=L, KX=KX, scaling=float(opts.get("scaling", 2.0)),
-                 bo=bo_c, wdec=wdec_c, watt=watt_c)
-        d.update({k: ws[k] for k in ("P", "Q", "wcat", "bcat", "convw", "gvec", "wattT", "w0", "xmask", "X", "Xd", "gates",
-                                     "cstate", "Dproj", "fconv", "S", "energy", "ws")})
-        lib = hb.load()
+        hb.dec_pack(w_ih, w_hh, b_ih, b_hh, wdec, watt, D, O, E, A, C, buf.wcat, buf.bcat, buf.wcatT, buf.wdecT, buf.wattT)
+        # inputs used as they are (no staging copies); the buffer object keeps them alive until the backward has run
+        buf.bind(P, Q, w0, convw, gvec, bo, wdec, watt, xmask_in, opts.get("scaling", 2.0))
+        w_out_c = w_out.contiguous()
         tokens = opts.get("tokens")
         tf_flags = opts.get("tf_flags")
         smooth = bool(opts.get("smooth", False))
         sample = bool(opts.get("sample", False))
         all_teacher = tokens is not None and (tf_flags is None or all(tf_flags)) and not sample
-        fused_prep = (all_teacher and (D + O) % 4 == 0 and E % 4 == 0 and (O + E) % 4 == 0 and X.shape[0] == L + 1 and
-                      X.is_contiguous() and tokens.stride(1) == 1)
-        probs_saved = []
-        if fused_prep:                           # zero fills, embedding gather, input dropout, fed: one launch
-            fed = torch.empty(L, B, dtype=torch.long, device=dev)
-            hb.dec_prepare(tokens, emb_w.contiguous(), xmask if drop else None, X, Xd if drop else None, fed, L, B, D, O, E)
-        else:
-            fed = torch.zeros(L, B, dtype=torch.long, device=dev)   # token whose embedding fed step s (-1: smooth)
-            X.zero_()
-            if drop:
-                Xd.zero_()
+        probs_saved, done = [], False
         if all_teacher:
-            if not fused_prep:
-                fed.copy_(tokens.t())
-                X[:L, :, D + O:] = emb_w[fed]
-                if drop:
-                    Xd[:L, :, D + O:] = X[:L, :, D + O:] * xmask[:, :, O:]
-            groups = hb.row_groups(B)
-            done = False
-            if hb.USE_PERSIST_DEC and len(groups) == 1:          # one launch for the whole sequence
-                fg = _dec_fwd_struct(d, 0, B)
-                xch, ctrl = hb.persist_scratch(dev)
-                entry = lib.asr_dec_seq_fwd_persist_fault if hb.DEC_FAULT[0] else lib.asr_dec_seq_fwd_persist
-                rc = entry(ctypes.byref(fg), ctypes.c_void_p(xch.data_ptr()), ctypes.c_void_p(ctrl.data_ptr()), hb.stream())
-                if rc == 0:
-                    done = True
-                elif rc != -2:                                  # -2: shape/device not covered by the fast path
-                    hb.check(rc, "asr_dec_seq_fwd_persist")
-            hb.count_path("dec_fwd", done, "D=%d A=%d O=%d E=%d Tp=%d B=%d" % (D, A, O, E, Tp, B))
-            if not done:
-                gh = [hb.graphs_for(i) if pooled else None for i in range(len(groups))]
-
-                def run(gi, grp, st):
-                    fg = _dec_fwd_struct(d, grp[0], grp[1])
-                    hb.check(lib.asr_dec_seq_fwd(ctypes.byref(fg), 0, L, gh[gi], st), "asr_dec_seq_fwd")
-
-                hb.run_grouped(groups, run)
-            logits = hb.gemm(X[1:].view(L * B, KX)[:, :D + O], w_out_c, trans_b=True, bias=b_out).view(L, B, V)
-            # (skip_pred: the caller takes the argmax from the loss kernel that reads the logits anyway - label_logprob)
-            pred = None if opts.get("skip_pred") else logits.argmax(-1)
+            fed, logits, pred = _dec_teacher_forced(buf, emb_w, tokens, w_out_c, b_out, pooled, opts.get("skip_pred"))
+        elif hb.USE_FEEDBACK_KERNEL and not sample and V <= 128:
+            fed, logits, pred, probs_saved, done = _dec_free_kernels(buf, emb_w, tokens, tf_flags, smooth, opts, w_out_c, b_out)
         else:
-            fs = _dec_fwd_struct(d, 0, B)
-            logits = torch.empty(L, B, V, **f32)
-            pred = torch.empty(L, B, dtype=torch.long, device=dev)
-            done = False
-            if hb.USE_FEEDBACK_KERNEL and not sample and V <= 128:
-                # free-running steps: per step the decoder chain, then ONE kernel for logits + argmax + the next
-                # step's embedding input (teacher / predicted token, or the smooth embedding softmax(k*logit) @ E)
-                emb_c = emb_w.contiguous()
-                if smooth and tokens is None:
-                    probs_saved = torch.empty(max(L - 1, 1), B, V, **f32)
-                tok_c = tokens.contiguous() if tokens is not None else None
-                fed[0] = tok_c[:, 0] if tok_c is not None else opts["bos"]
-                X[0, :, D + O:] = emb_c[fed[0]]
-                if drop:
-                    Xd[0, :, D + O:] = X[0, :, D + O:] * xmask[0, :, O:]
-                if hb.USE_PERSIST_DEC and (tok_c is None or not smooth) and V <= 64 and len(hb.row_groups(B)) == 1:
-                    # the whole sequence in one launch, the feedback computed in the kernel: no teacher tokens at all, or
-                    # scheduled sampling (the host's per-step draws go along as a byte per step)
-                    # decoding without autograd: a group of 4 utterances stops once all of them have emitted <EOS>; the
-                    # outputs of the steps that are not run read <EOS> / zero logits / zero attention weights
-                    eos = int(opts.get("eos", -1))
-                    stop = hb.DECODE_EARLY_STOP and eos >= 0 and not torch.is_grad_enabled() and tok_c is None
-                    if stop:
-                        pred.fill_(eos)
-                        logits.zero_()
-                        ws["ws"].zero_()
-                    tf_dev = None
-                    if tok_c is not None:
-                        tf_dev = torch.tensor([1 if (tf_flags is None or tf_flags[i]) else 0 for i in range(L)],
-                                              dtype=torch.uint8).to(dev, non_blocking=True)
-                    fb = hb.DecFeedback(
-                        tokens=ctypes.c_void_p(tok_c.data_ptr()) if tok_c is not None else None,
-                        ld_tokens=int(tok_c.stride(0)) if tok_c is not None else 0,
-                        teacher=ctypes.c_void_p(tf_dev.data_ptr()) if tf_dev is not None else None,
-                        mode=2 if smooth else 1, V=V, eos=eos if stop else -1,
-                        scaling=float(opts.get("smooth_scaling", 1.0)), w_out=_p(w_out_c),
-                        b_out=_p(b_out.contiguous()), emb=_p(emb_c), logits=_p(logits),
-                        probs=_p(probs_saved) if smooth else None, pred=ctypes.c_void_p(pred.data_ptr()),
-                        fed=ctypes.c_void_p(fed.data_ptr()))
-                    xch, ctrl = hb.persist_scratch(dev)
-                    rc = lib.asr_dec_seq_fwd_persist_free(ctypes.byref(fs), ctypes.byref(fb), ctypes.c_void_p(xch.data_ptr()),
-                                                          ctypes.c_void_p(ctrl.data_ptr()), hb.stream())
-                    if rc == 0:
-                        done = True
-                        if stop and L > 1:
-                            # the last step's logits come from X[L], which a stopped group never wrote: rows that had
-                            # already emitted <EOS> keep the pre-filled outputs
-                            lg_last, pr_last = torch.empty(B, V, **f32), torch.empty(B, dtype=torch.long, device=dev)
-                            hb.dec_feedback_fwd(X[L][:, :D + O], w_out_c, b_out, emb_c, lg_last, pr_last, hb.FEED_NONE)
-                            live = pred[:L - 1].ne(eos).all(0)
-                            pred[L - 1] = torch.where(live, pr_last, pred[L - 1])
-                            logits[L - 1] = torch.where(live.unsqueeze(1), lg_last, logits[L - 1])
-                        else:
-                            hb.dec_feedback_fwd(X[L][:, :D + O], w_out_c, b_out, emb_c, logits[L - 1], pred[L - 1],
-                                                hb.FEED_NONE)
-                    elif rc != -2:
-                        hb.check(rc, "asr_dec_seq_fwd_persist_free")
-                hb.count_path("dec_free", done, "D=%d A=%d O=%d E=%d Tp=%d B=%d V=%d teacher=%s" % (
-                    D, A, O, E, Tp, B, V, tok_c is not None))
-                for s in (range(L) if not done else ()):
-                    hb.check(lib.asr_dec_step_fwd(ctypes.byref(fs), s, hb.stream()), "asr_dec_step_fwd")
-                    last = s == L - 1
-                    if last:
-                        mode = hb.FEED_NONE
-                    elif tok_c is not None:
-                        mode = hb.FEED_TEACHER if (tf_flags is None or tf_flags[s + 1]) else hb.FEED_PREDICTED
-                    else:
-                        mode = hb.FEED_SMOOTH if smooth else hb.FEED_PREDICTED
-                    hb.dec_feedback_fwd(
-                        X[s + 1][:, :D + O], w_out_c, b_out, emb_c, logits[s], pred[s], mode, opts["smooth_scaling"],
-                        tok=tok_c[:, s + 1] if mode == hb.FEED_TEACHER else None, fed=None if last else fed[s + 1],
-                        probs=probs_saved[s] if mode == hb.FEED_SMOOTH else None,
-                        x_emb_next=None if last else X[s + 1][:, D + O:],
-                        xd_emb_next=Xd[s + 1][:, D + O:] if (drop and not last) else None,
-                        mask=xmask[s + 1][:, O:] if (drop and not last) else None)
-            elif not done:
-                for s in range(L):
-                    if s == 0:
-                        tok = tokens[:, 0] if tokens is not None else torch.full((B,), opts["bos"], dtype=torch.long,
-                                                                                 device=dev)
-                        fed[0] = tok
-                        X[0, :, D + O:] = emb_w[tok]
-                    elif tokens is not None:
-                        tok = tokens[:, s] if tf_flags[s] else pred[s - 1]
-                        fed[s] = tok
-                        X[s, :, D + O:] = emb_w[tok]
-                    elif not smooth:
-                        fed[s] = pred[s - 1]
-                        X[s, :, D + O:] = emb_w[pred[s - 1]]
-                    else:
-                        pr = torch.softmax(logits[s - 1] * opts["smooth_scaling"], dim=-1)
-                        probs_saved.append(pr)
-                        fed[s] = -1
-                        hb.gemm(pr, emb_w, out=X[s][:, D + O:])
-                    if drop:
-                        Xd[s, :, D + O:] = X[s, :, D + O:] * xmask[s, :, O:]
-                    hb.check(lib.asr_dec_step_fwd(ctypes.byref(fs), s, hb.stream()), "asr_dec_step_fwd")
-                    hb.gemm_skinny(X[s + 1][:, :D + O], w_out_c, bias=b_out, out=logits[s])
-                    pred[s] = torch.distributions.Categorical(logits=logits[s]).sample() if sample \
-                        else logits[s].argmax(-1)
-        ctx.d = d
+            fed, logits, pred, probs_saved = _dec_free_torch(buf, emb_w, tokens, tf_flags, smooth, sample, opts, w_out_c, b_out)
         ctx.lease = lease
-        ctx.keep = (wdec_c, watt_c, bo_c, fed, probs_saved, w_out_c, emb_w)
+        ctx.keep = (fed, probs_saved, w_out_c, emb_w)
         ctx.dims = (B, Tp, A, O, D, E, V, C, K, L, KX)
         ctx.smooth = smooth and tokens is None
         ctx.all_teacher = all_teacher
         # a scheduled-sampling sequence that ran in the persistent kernel takes the persistent backward as well: no gradient
         # flows through an argmax, the backward only needs what the forward saved (X, fed)
-        ctx.free_persist = (not all_teacher) and bool(done) and not (smooth and tokens is None)
+        ctx.free_persist = (not all_teacher) and done and not ctx.smooth
         ctx.smooth_scaling = float(opts.get("smooth_scaling", 1.0))
         if pred is not None:
             ctx.mark_non_differentiable(pred)
         ctx.set_materialize_grads(False)       # an unused `ws` output arrives as None instead of a zero tensor + copy
         # the attention weights: in a training step a view of the leased workspace (valid until the next forward of the same
         # shape; nothing on the training path keeps them), a copy otherwise
-        return logits, (ws["ws"].detach() if pooled else ws["ws"].clone()), pred
+        return logits, (buf.ws.detach() if pooled else buf.ws.clone()), pred
 
     @staticmethod
     @_with_saved_arith
     def backward(ctx, dlogits, dws, _dpred):
-        wdec, watt, bo, fed, probs_saved, w_out, emb_w = ctx.keep
+        fed, probs_saved, w_out, emb_w = ctx.keep
         B, Tp, A, O, D, E, V, C, K, L, KX = ctx.dims
-        lease, d = ctx.lease, ctx.d
+        lease = ctx.lease
         assert lease is not None and lease.ws is not None, "decoder_sequence backward needs the leased workspace"
-        wk = lease.ws
-        X, Xd = wk["X"], wk["Xd"]
+        buf = lease.ws
+        X, Xd = buf.X, buf.Xd
         dev = X.device
-        lib = hb.load()
         if dlogits is None:
             dlogits = torch.zeros(L, B, V, device=dev, dtype=torch.float32)
         dlog2 = dlogits.contiguous().view(L * B, V)
-        zb = _ARENA.take((wk["zbuf"].numel(),), dev)
+        zb = _ARENA.take((buf.zbuf.numel(),), dev)
         if zb is None:
-            wk["zbuf"].zero_()                 # G, dwext, dP, dcell, dgvec_part, dwatt_part, dconv_part
+            buf.zbuf.zero_()                   # G, dwext, dP, dcell, dgvec_part, dwatt_part, dconv_part
+            acc = buf.acc
         else:                                  # ... or their places in the step's arena (zeroed with everything else)
-            wk = dict(wk)
-            for k_ in ("G", "dwext", "dP", "dcell", "dgvec_part", "dwatt_part", "dconv_part"):
-                o_ = (wk[k_].data_ptr() - wk["zbuf"].data_ptr()) // 4
-                wk[k_] = zb[o_:o_ + wk[k_].numel()].view_as(wk[k_])
-        G = wk["G"]                            # (wcatT, wdecT: written by the forward's dec_pack)
+            acc = buf.accumulators(zb)
+        G = acc["G"]                           # (wcatT, wdecT: written by the forward's dec_pack)
         XO = X[1:].view(L * B, KX)[:, :D + O]
         hb.gemm(dlog2, w_out, out=G[1:].view(L * B, KX)[:, :D + O])
         dw_out = _gemm_acc(dlog2, XO, trans_a=True, shape=(V, D + O))
         db_out = _colsum_acc(dlog2)
-        w = dict(wk)
         if dws is not None:
-            wk["dws"].copy_(dws)
-        else:
-            w["dws"] = None
+            buf.dws.copy_(dws)
         demb_w = zeros_acc(tuple(emb_w.shape), dev)
         if not ctx.smooth:
-            groups = hb.row_groups(B)
-            done = False
-            if hb.USE_PERSIST_DEC_BWD and (ctx.all_teacher or ctx.free_persist) and len(groups) == 1:
-                bg = _dec_bwd_struct(d, w, 0, B)
-                xch, ctrl = hb.persist_scratch(dev)
-                rc = lib.asr_dec_seq_bwd_persist(ctypes.byref(bg), _p(wk["Mf"]), ctypes.c_void_p(xch.data_ptr()),
-                                                 ctypes.c_void_p(ctrl.data_ptr()), hb.stream())
-                if rc == 0:
-                    done = True
-                elif rc != -2:
-                    hb.check(rc, "asr_dec_seq_bwd_persist")
-            hb.count_path("dec_bwd", done, "D=%d A=%d O=%d E=%d Tp=%d B=%d teacher=%s" % (D, A, O, E, Tp, B, ctx.all_teacher))
-            if not done:
-                gh = [hb.graphs_for(i) for i in range(len(groups))]
-
-                def run(gi, grp, st):
-                    bg = _dec_bwd_struct(d, w, grp[0], grp[1])
-                    hb.check(lib.asr_dec_seq_bwd(ctypes.byref(bg), 0, L, gh[gi], st), "asr_dec_seq_bwd")
-
-                hb.run_grouped(groups, run)
+            hb.dec_seq_bwd(buf, acc, dws is not None, ctx.all_teacher or ctx.free_persist, ctx.all_teacher)
+        elif torch.is_tensor(probs_saved):
+            # the feedback's gradient reaches the logits inside the kernels; the weight gradients that depend on it are taken
+            # once over the whole sequence afterwards
+            dtot = hb.dec_smooth_bwd(buf, acc, dws is not None, w_out.contiguous(), emb_w.contiguous(), probs_saved,
+                                     ctx.smooth_scaling, dlog2)
+            dw_out = hb.gemm(dtot.view(L * B, V), XO, trans_a=True)
+            db_out = hb.colsum(dtot.view(L * B, V))
+            if L > 1:
+                hb.gemm(probs_saved[:L - 1].view((L - 1) * B, V), G[1:L].view((L - 1) * B, KX)[:, D + O:], trans_a=True,
+                        out=demb_w, accumulate=True, split_k=1)
         else:
-            # smooth-embedding feedback (model.py:341): emb_s = softmax(logit_{s-1}*k) @ E couples step s to
-            # the logits of step s-1, so the extra gradient is injected between the per-step kernels.
-            bs = _dec_bwd_struct(d, w, 0, B)
-            k = ctx.smooth_scaling
-            fused = torch.is_tensor(probs_saved)
-            done = False
-            if fused and hb.USE_PERSIST_DEC_BWD and L > 1 and len(hb.row_groups(B)) == 1:
-                # the whole free-running sequence in one launch: the feedback path (d(emb_s) -> logit_{s-1} -> [z, ctx]_{s-1})
-                # is carried inside the persistent kernel (dec_persist.hip, template FB)
-                emb_c, w_out_c = emb_w.contiguous(), w_out.contiguous()
-                dlfb = torch.zeros(L, B, V, device=dev, dtype=torch.float32)
-                fbs = hb.DecFeedbackBwd(V=V, scaling=float(k), w_out=_p(w_out_c), emb=_p(emb_c), probs=_p(probs_saved),
-                                        dlfb=_p(dlfb))
-                xch, ctrl = hb.persist_scratch(dev)
-                rc = lib.asr_dec_seq_bwd_persist_free(ctypes.byref(bs), ctypes.byref(fbs), _p(wk["Mf"]),
-                                                      ctypes.c_void_p(xch.data_ptr()), ctypes.c_void_p(ctrl.data_ptr()),
-                                                      hb.stream())
-                if rc == 0:
-                    done = True
-                    dtot = dlog2.view(L, B, V) + dlfb
-                    dw_out = hb.gemm(dtot.view(L * B, V), XO, trans_a=True)
-                    db_out = hb.colsum(dtot.view(L * B, V))
-                    hb.gemm(probs_saved[:L - 1].view((L - 1) * B, V), G[1:L].view((L - 1) * B, KX)[:, D + O:], trans_a=True,
-                            out=demb_w, accumulate=True, split_k=1)
-                elif rc != -2:
-                    hb.check(rc, "asr_dec_seq_bwd_persist_free")
-            hb.count_path("dec_bwd", done, "free-running smooth: D=%d A=%d O=%d E=%d Tp=%d B=%d V=%d L=%d fused-feedback=%s" % (
-                D, A, O, E, Tp, B, V, L, fused))
-            if done:
-                pass
-            elif fused:
-                # one kernel per step carries the embedding gradient back into logit_{s-1} and [z_{s-1}, c_{s-1}];
-                # the weight gradients that depend on it are taken once over the whole sequence afterwards
-                dtot = dlog2.clone().view(L, B, V)
-                emb_c, w_out_c = emb_w.contiguous(), w_out.contiguous()
-                for s in range(L - 1, -1, -1):
-                    hb.check(lib.asr_dec_step_bwd(ctypes.byref(bs), s, hb.stream()), "asr_dec_step_bwd")
-                    if s >= 1:
-                        hb.dec_feedback_bwd(G[s][:, D + O:], G[s][:, :D + O], probs_saved[s - 1], emb_c, w_out_c, k,
-                                            dtot[s - 1])
-                dw_out = hb.gemm(dtot.view(L * B, V), XO, trans_a=True)
-                db_out = hb.colsum(dtot.view(L * B, V))
-                if L > 1:
-                    hb.gemm(probs_saved[:L - 1].view((L - 1) * B, V), G[1:L].view((L - 1) * B, KX)[:, D + O:], trans_a=True,
-                            out=demb_w, accumulate=True, split_k=1)
-            for s in (range(L - 1, -1, -1) if not (fused or done) else ()):
-                hb.check(lib.asr_dec_step_bwd(ctypes.byref(bs), s, hb.stream()), "asr_dec_step_bwd")
-                if s >= 1:
-                    demb = G[s][:, D + O:]
-                    pr = probs_saved[s - 1]
-                    hb.gemm(pr, demb, trans_a=True, out=demb_w, accumulate=True, split_k=1)
-                    dp = hb.gemm(demb, emb_w, trans_b=True)
-                    dl = (k * pr * (dp - (pr * dp).sum(-1, keepdim=True))).contiguous()
-                    hb.gemm(dl, w_out, out=G[s][:, :D + O], accumulate=True, split_k=1)
-                    hb.gemm(dl, X[s][:, :D + O], trans_a=True, out=dw_out, accumulate=True, split_k=1)
-                    hb.colsum(dl, out=db_out, accumulate=True)
+            _dec_smooth_bwd_torch(buf, acc, dws is not None, w_out, emb_w, probs_saved, ctx.smooth_scaling, dw_out, db_out,
+                                  demb_w)
         # deferred weight gradients: one GEMM each over the whole sequence
-        dg2 = wk["dgates"].view(L * B, 4 * D)
+        dg2 = buf.dgates.view(L * B, 4 * D)
         Xin = X[:L] if Xd is None else Xd[:L]
         dwcat = _gemm_acc(dg2, Xin.reshape(L * B, KX), trans_a=True, shape=(4 * D, KX))     # [4D, KX] gate-interleaved rows
         dw_ih, dw_hh, dbias, dbias2 = hb.cell_unpack(dwcat, _colsum_acc(dg2), D, O, E)       # -> torch layout, one launch
-        dwdec = _gemm_acc(wk["dD"].view(L * B, A), X[1:].view(L * B, KX)[:, :D], trans_a=True, shape=(A, D))
-        dgvec, dwatt, dconvw = hb.colsum_parts([wk["dgvec_part"], wk["dwatt_part"], wk["dconv_part"]])   # sums over utterances
+        dwdec = _gemm_acc(buf.dD.view(L * B, A), X[1:].view(L * B, KX)[:, :D], trans_a=True, shape=(A, D))
+        dgvec, dwatt, dconvw = hb.colsum_parts([acc["dgvec_part"], acc["dwatt_part"], acc["dconv_part"]])   # sums over utterances
         dgvec, dconvw = dgvec.view(1, A), dconvw.view(C, 1, 1, 2 * K + 1)
         # dQ[b] = ws[:, b, :]^T dctx[:, b, :]   (batched over utterances)
         dQ = torch.empty(B, Tp, O, device=dev, dtype=torch.float32)
         dctx_base = G[1:]                               # [L, B, KX], ctx grad at columns D:D+O
-        hb.gemm_batched(wk["ws"], dctx_base[:, :, D:], dQ, True, False, Tp, O, L, B * Tp, B * KX, O, B, Tp, KX,
+        hb.gemm_batched(buf.ws, dctx_base[:, :, D:], dQ, True, False, Tp, O, L, B * Tp, B * KX, O, B, Tp, KX,
                         Tp * O)
         dbo = _colsum_acc(dctx_base.view(L * B, KX)[:, D:D + O])
         # embedding gradient for token-fed steps: one launch over the embedding columns of G as they lie (fed = -1: a step
@@ -1041,7 +870,7 @@ class _DecoderSeq(torch.autograd.Function):
             else:
                 tokfed = fed >= 0
                 demb_w.index_add_(0, fed[tokfed], demb_all[tokfed])
-        dP = wk["dP"] if zb is not None else wk["dP"].clone()      # (an arena slice outlives the lease)
+        dP = acc["dP"] if zb is not None else acc["dP"].clone()      # (an arena slice outlives the lease)
         lease.release()
         return (dP, dQ, demb_w, dw_ih, dw_hh, dbias, dbias2, dwdec, dconvw, dwatt, dgvec, dbo, dw_out, db_out,
                 None, None)
@@ -1117,19 +946,15 @@ def attention_step(enc_pad, P, Q, wdec, convw, watt, gvec, bo, dec_z, att_prev, 
     O, D, C = Q.shape[2], wdec.shape[1], convw.shape[0]
     K = (convw.shape[-1] - 1) // 2
     E = 16                                                   # dummy embedding width (unused columns of X)
-    ws = _dec_workspace(B, Tp, A, D, O, E, C, K, 1, False, dev, False)
+    buf = hb.DecBuffers(B, Tp, A, D, O, E, C, K, 1, False, dev, False)
     with torch.no_grad():
-        ws["P"].copy_(P); ws["Q"].copy_(Q); ws["w0"].copy_(att_prev)
-        ws["convw"].copy_(convw.reshape(C, 2 * K + 1)); ws["gvec"].copy_(gvec.reshape(A)); ws["wattT"].copy_(watt.t())
-        ws["wcat"].zero_(); ws["bcat"].zero_(); ws["X"].zero_()
-        ws["X"][1, :, :D] = dec_z
-        d = dict(B=B, Tp=Tp, A=A, D=D, O=O, E=E, C=C, K=K, L=1, KX=D + O + E, scaling=float(scaling),
-                 bo=bo.contiguous(), wdec=wdec.contiguous(), watt=watt.contiguous())
-        d.update({k: ws[k] for k in ("P", "Q", "wcat", "bcat", "convw", "gvec", "wattT", "w0", "xmask", "X", "Xd",
-                                     "gates", "cstate", "Dproj", "fconv", "S", "energy", "ws")})
-        fs = _dec_fwd_struct(d, 0, B)
-        hb.check(hb.load().asr_att_step_fwd(ctypes.byref(fs), 0, hb.stream()), "asr_att_step_fwd")
-        return ws["X"][1, :, D:D + O].clone(), ws["ws"][0].clone()
+        buf.P.copy_(P); buf.Q.copy_(Q); buf.w0.copy_(att_prev)
+        buf.convw.copy_(convw.reshape(C, 2 * K + 1)); buf.gvec.copy_(gvec.reshape(A)); buf.wattT.copy_(watt.t())
+        buf.wcat.zero_(); buf.bcat.zero_(); buf.X.zero_()
+        buf.X[1, :, :D] = dec_z
+        buf.bind(bo=bo, wdec=wdec, watt=watt, scaling=scaling)
+        hb.att_step_fwd(buf.fwd_struct(), 0)
+        return buf.X[1, :, D:D + O].clone(), buf.ws[0].clone()
 
 
 BEAM_POLL_STEPS = 8          # the host reads the all-done word of a beam search every this many steps
@@ -1158,7 +983,6 @@ def beam_search(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo
     V = w_out.shape[0]
     C = convw.shape[0]
     Kc = (convw.shape[-1] - 1) // 2
-    KX = D + O + E
     R = B * beam
     f32 = dict(device=dev, dtype=torch.float32)
     fused = lm is not None and float(lm_weight) != 0.0
@@ -1172,30 +996,21 @@ def beam_search(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo
             lms.prime(bos)
             lm_w_out, lm_b_out = lm["w_out"].detach().contiguous(), lm["b_out"].detach().contiguous()
             lm_logits = torch.empty(R, V, **f32)
-        ws = dict(P=P.repeat_interleave(beam, 0).contiguous(), Q=Q.repeat_interleave(beam, 0).contiguous(),
-                  w0=w0.repeat_interleave(beam, 0).contiguous(), wcat=torch.empty(4 * D, KX, **f32),
-                  bcat=torch.empty(4 * D, **f32), wattT=torch.empty(C, A, **f32),
-                  convw=convw.reshape(C, 2 * Kc + 1).contiguous(), gvec=gvec.reshape(A).contiguous(), xmask=None, Xd=None,
-                  X=torch.zeros(3, R, KX, **f32), gates=torch.empty(2, R, 4 * D, **f32), cstate=torch.zeros(2, R, D, **f32),
-                  Dproj=torch.empty(2, R, A, **f32), fconv=torch.empty(2, R, C, Tp, **f32),
-                  S=torch.empty(2, R, Tp, A, **f32), energy=torch.empty(2, R, Tp, **f32), ws=torch.empty(2, R, Tp, **f32))
-        hb.dec_pack(w_ih, w_hh, b_ih, b_hh, wdec, watt, D, O, E, A, C, ws["wcat"], ws["bcat"], None, None, ws["wattT"])
-        d = dict(B=R, Tp=Tp, A=A, D=D, O=O, E=E, C=C, K=Kc, L=2, KX=KX, scaling=float(scaling), bo=bo.contiguous(),
-                 wdec=wdec.contiguous(), watt=watt.contiguous())
-        d.update({k: ws[k] for k in ("P", "Q", "wcat", "bcat", "convw", "gvec", "wattT", "w0", "xmask", "X", "Xd", "gates",
-                                     "cstate", "Dproj", "fconv", "S", "energy", "ws")})
-        fs = _dec_fwd_struct(d, 0, R)
-        X, cst, wts = ws["X"], ws["cstate"], ws["ws"]
+        buf = hb.DecBuffers(R, Tp, A, D, O, E, C, Kc, 2, False, dev, False)      # two step slots (three of X) serve any L
+        buf.bind(P.repeat_interleave(beam, 0), Q.repeat_interleave(beam, 0), w0.repeat_interleave(beam, 0), convw, gvec, bo,
+                 wdec, watt, None, scaling)
+        X, cst, wts = buf.X.zero_(), buf.cstate.zero_(), buf.ws
+        hb.dec_pack(w_ih, w_hh, b_ih, b_hh, wdec, watt, D, O, E, A, C, buf.wcat, buf.bcat, None, None, buf.wattT)
+        fs = buf.fwd_struct()
         emb_c, w_out_c = emb_w.contiguous(), w_out.contiguous()
         X[1, :, D + O:] = emb_c[bos]
-        wts[0].copy_(ws["w0"])
+        wts[0].copy_(buf.w0)
         logits = torch.empty(R, V, **f32)
-        lib = hb.load()
         landing = torch.zeros(1, dtype=torch.int32).pin_memory()
         polled = None
         steps = launches = 0
         for t in range(L):
-            hb.check(lib.asr_dec_step_fwd(ctypes.byref(fs), 1, hb.stream()), "asr_dec_step_fwd")
+            hb.dec_step_fwd(fs, 1)
             hb.gemm_skinny(X[2][:, :D + O], w_out_c, bias=b_out, out=logits)
             if fused:
                 lms.step()

@@ -2,17 +2,18 @@
 import sys, os, ctypes, glob
 ROOT=os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0]=[ROOT, ROOT+'/semi-supervised-asr_amd']
-import torch, hip_backend as hb, ops
+import torch, hip_backend as hb
 dev=torch.device('cuda')
 B,Tp,A,D,O,E,C,K,L=32,100,512,512,512,128,10,100,101
-ws=ops._dec_workspace(B,Tp,A,D,O,E,C,K,L,False,dev,False)
-for k,v in ws.items():
-    if v is not None: v.normal_(0,0.1)
-ws['w0'].fill_(1.0/Tp)
+def noise(buf):
+    for v in vars(buf).values():
+        if torch.is_tensor(v): v.normal_(0,0.1)
+buf=hb.DecBuffers(B,Tp,A,D,O,E,C,K,L,False,dev,False)
+noise(buf)
+buf.w0.fill_(1.0/Tp)
 bo=torch.zeros(O,device=dev); wdec=torch.randn(A,D,device=dev)*0.04; watt=torch.randn(A,C,device=dev)*0.3
-d=dict(B=B,Tp=Tp,A=A,D=D,O=O,E=E,C=C,K=K,L=L,KX=D+O+E,scaling=2.0,bo=bo,wdec=wdec,watt=watt)
-d.update({k: ws[k] for k in ("P","Q","wcat","bcat","convw","gvec","wattT","w0","xmask","X","Xd","gates","cstate","Dproj","fconv","S","energy","ws")})
-fs=ops._dec_fwd_struct(d,0,B)
+buf.bind(bo=bo,wdec=wdec,watt=watt)
+fs=buf.fwd_struct()
 st=ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 for path in sorted(glob.glob(ROOT+'/scratchlibs/lib_*.so')):
     l=ctypes.CDLL(path); l.asr_dec_seq_fwd.restype=ctypes.c_int
@@ -26,13 +27,11 @@ for path in sorted(glob.glob(ROOT+'/scratchlibs/lib_*.so')):
     print('%-20s %.2f us/launch'%(os.path.basename(path),best),flush=True)
 
 # ---- backward kernels (libs named lib_b*)
-wsb=ops._dec_workspace(B,Tp,A,D,O,E,C,K,L,False,dev,True)
-for k,v in wsb.items():
-    if v is not None: v.normal_(0,0.1)
-wk=dict(wsb); wk['dws']=None
-d2=dict(d); d2.update({k: wsb[k] for k in ("P","Q","wcat","bcat","convw","gvec","wattT","w0","xmask","X","Xd","gates","cstate","Dproj","fconv","S","energy","ws")})
-d2['ws'].copy_(torch.softmax(torch.randn(L,B,Tp,device=dev),-1))
-bs=ops._dec_bwd_struct(d2,wk,0,B)
+bufb=hb.DecBuffers(B,Tp,A,D,O,E,C,K,L,False,dev,True)
+noise(bufb)
+bufb.bind(bo=bo,wdec=wdec,watt=watt)
+bufb.ws.copy_(torch.softmax(torch.randn(L,B,Tp,device=dev),-1))
+bs=bufb.bwd_struct(with_dws=False)
 for path in sorted(glob.glob(ROOT+'/scratchlibs/libb_*.so')):
     l=ctypes.CDLL(path); l.asr_dec_seq_bwd.restype=ctypes.c_int
     l.asr_dec_seq_bwd.argtypes=[ctypes.POINTER(hb.DecBwd),ctypes.c_int,ctypes.c_int,ctypes.c_void_p,ctypes.c_void_p]

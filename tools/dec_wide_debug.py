@@ -101,7 +101,7 @@ if L == 2:
 
 if os.environ.get('DBGLIB'):
     key = [k for k in ops._POOL.free if k[0] == "dec"][0]
-    dbg = ops._POOL.free[key][-1]["dfpart"].reshape(-1)[:3 * B * C * Tp].view(3, B, C, Tp).double().cpu()
+    dbg = ops._POOL.free[key][-1].dfpart.reshape(-1)[:3 * B * C * Tp].view(3, B, C, Tp).double().cpu()
     f64, S64, e64 = ref64.last
     U = base["watt"].double().cpu(); gvv = base["gvec"].double().cpu().view(-1)
     M64 = torch.einsum('ac,a,bta->bct', U, gvv, S64.detach() ** 2)
@@ -117,7 +117,7 @@ if os.environ.get('DBGLIB'):
     print('ratio des', (dbg[2][0, 0, :6] / e64.grad[0, :6]).tolist())
 
 if os.environ.get('DBGLIB'):
-    raw = ops._POOL.free[key][-1]["dfpart"].reshape(-1)
+    raw = ops._POOL.free[key][-1].dfpart.reshape(-1)
     dwx = raw[3 * B * C * Tp: 3 * B * C * Tp + B * Tp].view(B, Tp).double().cpu()
     Fw = base["convw"].double().cpu().view(C, 2 * K + 1)
     dfp = torch.zeros(B, C, Tp + 2 * K, dtype=torch.float64); dfp[:, :, K:K + Tp] = f64.grad
