@@ -691,6 +691,34 @@ int asr_beam_reorder_lm_f32(const asr_beam_t* p, int t, const asr_beam_state_t* 
                             asr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Scoring: batched edit distance on token ids (utils.py:222-228: editdistance.eval per utterance).  One entry
+ * added to ABI version 6 WITHOUT a version change: it is additive, like the beam entries.
+ *   asr_edit_distance_i32   for every pair p < n_pairs: dist[p] = the Levenshtein distance (unit costs) between
+ *                           filter(cut(hypothesis row p)) and filter(reference row r), r = p or ref_of_pair[p] (a valid
+ *                           row of `ref`: K hypotheses may share one reference).
+ *                           hyp: rows of hyp_cols tokens, row stride ldh elements, int32 (hyp_elem_bytes 4: beam tokens)
+ *                           or int64 (8: the greedy prediction; the ids must fit int32); row p runs to hyp_len[p]
+ *                           (clamped to 0 .. hyp_cols; NULL: to hyp_cols).  ref: int32 rows of stride ldr, row r runs to
+ *                           ref_len[r] (clamped to 0 .. ldr).
+ *                           cut: the hypothesis ends before its first `eos` (eos < 0: no cut); references are never cut.
+ *                           filter: a token t with 0 <= t < V and skip[t] != 0 is dropped from BOTH sides (skip NULL or
+ *                           V <= 0: nothing is dropped); ids outside [0, V) are ordinary tokens, the table is never read
+ *                           out of range.  Empty sides are legal: the distance is the other side's filtered length.
+ *                           hyp_n[p], ref_n[p] (each may be NULL): the two filtered lengths.  totals (may be NULL):
+ *                           totals[0] += sum of dist, totals[1] += sum of ref_n, 64-bit integer atomics (the caller zeroes
+ *                           them; integer sums do not depend on the order, so the result is deterministic).
+ *                           Limits: hyp_cols and ldr (the bound of a reference's length) at most ASR_ED_MAX_COLS, which
+ *                           also bounds both filtered lengths: ASR_E_SHAPE beyond.  n_pairs <= 0, a NULL hyp / ref /
+ *                           ref_len / dist, an element size other than 4 or 8, ldh < hyp_cols: ASR_E_ARG.
+ *                           One launch, no host synchronisation, no allocation.
+ * ------------------------------------------------------------------------------------- */
+#define ASR_ED_MAX_COLS 4096
+int asr_edit_distance_i32(int n_pairs, const void* hyp, int hyp_elem_bytes, int64_t ldh, int hyp_cols,
+                          const int32_t* hyp_len, const int32_t* ref, int64_t ldr, const int32_t* ref_len,
+                          const int32_t* ref_of_pair, int eos, const uint8_t* skip, int V, int32_t* dist, int32_t* hyp_n,
+                          int32_t* ref_n, long long* totals, asr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Optimiser on a flat fp32 buffer (solver.py:152-153,384-385: clip_grad_norm_ + Adam(amsgrad,
  * weight_decay).step).  asr_sumsq_f32 adds sum(g^2) into the device scalar out[0] (caller zeroes
  * it); asr_adam_clip_f32 scales g by min(1, max_norm/(sqrt(*gnorm_sq)+1e-6)) (skipped when

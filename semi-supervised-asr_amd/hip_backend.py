@@ -25,6 +25,7 @@ EXPORTS = (
     "asr_adam_clip_f32", "asr_sumsq_f32", "asr_gather_sumsq_f32", "asr_graphs_create", "asr_graphs_destroy", "asr_graphs_stats",
     "asr_beam_select_f32", "asr_beam_reorder_f32", "asr_beam_backtrack",
     "asr_lm_step_f32", "asr_beam_select_lm_f32", "asr_beam_reorder_lm_f32",
+    "asr_edit_distance_i32",
 )
 
 _lib = None
@@ -235,6 +236,8 @@ def load():
     lib.asr_beam_select_lm_f32.argtypes = [ctypes.POINTER(Beam), c_p, c_f, c_i, c_p]
     lib.asr_beam_reorder_lm_f32.argtypes = [ctypes.POINTER(Beam), c_i, ctypes.POINTER(BeamState),
                                             ctypes.POINTER(BeamLmState), c_p]
+    lib.asr_edit_distance_i32.argtypes = [c_i, c_p, c_i, c_i64, c_i, c_p, c_p, c_i64, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p,
+                                          c_p, c_p]
     lib.asr_att_step_fwd.argtypes = [ctypes.POINTER(DecFwd), c_i, c_p]
     lib.asr_dec_seq_fwd.argtypes = [ctypes.POINTER(DecFwd), c_i, c_i, c_p, c_p]
     lib.asr_dec_seq_fwd_persist.argtypes = [ctypes.POINTER(DecFwd), c_p, c_p, c_p]
@@ -514,6 +517,59 @@ class BeamSearch:
         check(load().asr_beam_backtrack(ctypes.byref(self.struct), float(length_penalty), ptr(tokens), ptr(scores),
                                         ptr(lengths), stream()), "asr_beam_backtrack")
         return tokens, scores, lengths
+
+
+ED_MAX_COLS = 4096         # ASR_ED_MAX_COLS
+
+
+class UnsupportedShape(RuntimeError):
+    """A launcher answered ASR_E_SHAPE: its kernel does not cover these sizes (the caller may have another route)."""
+
+
+def _ints(t, name, dtypes, dim):
+    if t is None:
+        return None
+    if not t.is_cuda:
+        raise RuntimeError("%s must live on the GPU: the HIP path has no CPU fallback" % name)
+    if t.dtype not in dtypes:
+        raise RuntimeError("%s must be %s, got %s" % (name, " or ".join(str(d) for d in dtypes), t.dtype))
+    if t.dim() != dim or (t.shape[-1] > 1 and t.stride(-1) != 1):
+        raise RuntimeError("%s must be %d-D with unit stride in its last dimension" % (name, dim))
+    return c_p(t.data_ptr())
+
+
+def edit_distance(hyp, ref, ref_len, *, hyp_len=None, ref_index=None, eos=-1, skip=None, totals=None, out=None):
+    """asr_edit_distance_i32 (csrc/edit_distance.hip): the Levenshtein distance of every hypothesis row to its reference row
+    on token ids, one launch.  hyp [N, cols] int32 or int64 (row p runs to hyp_len[p], int32 [N]; None: to cols; cut before
+    its first `eos` unless eos < 0); ref [R, cols] int32 with ref_len int32 [R]; pair p scores against reference row p, or
+    ref_index[p] (int32 [N]: K hypotheses per reference); skip: uint8 [V], tokens with a non-zero entry are dropped from
+    both sides (utils.cer_token_table); totals: int64 [2], += (sum of distances, sum of reference lengths).
+    -> (dist, hyp_n, ref_n), int32 [N] device tensors: distance and the two filtered lengths - rows of `out` (int32 [3, N])
+    when it is given.  Raises UnsupportedShape beyond ED_MAX_COLS columns: there is no other device path."""
+    N = hyp.shape[0]
+    hp = _ints(hyp, "hyp", (torch.int32, torch.int64), 2)
+    rp, rlp = _ints(ref, "ref", (torch.int32,), 2), _ints(ref_len, "ref_len", (torch.int32,), 1)
+    hlp, rip = _ints(hyp_len, "hyp_len", (torch.int32,), 1), _ints(ref_index, "ref_index", (torch.int32,), 1)
+    sp, tp = _ints(skip, "skip", (torch.uint8,), 1), _ints(totals, "totals", (torch.int64,), 1)
+    if ref_len.shape[0] != ref.shape[0] or (ref_index is None and ref.shape[0] < N):
+        raise RuntimeError("ref has %d rows, ref_len %d, for %d pairs" % (ref.shape[0], ref_len.shape[0], N))
+    for t, n, name in ((hyp_len, N, "hyp_len"), (ref_index, N, "ref_index"), (totals, 2, "totals")):
+        if t is not None and t.shape[0] != n:
+            raise RuntimeError("%s must have %d entries, got %d" % (name, n, t.shape[0]))
+    if out is None:
+        out = torch.empty(3, N, dtype=torch.int32, device=hyp.device)
+    op = _ints(out, "out", (torch.int32,), 2)
+    if tuple(out.shape) != (3, N) or not out.is_contiguous():
+        raise RuntimeError("out must be a contiguous int32 [3, %d]" % N)
+    rc = load().asr_edit_distance_i32(
+        N, hp, hyp.element_size(), hyp.stride(0) if N > 1 else max(hyp.shape[1], 1), hyp.shape[1], hlp, rp,
+        ref.stride(0) if ref.shape[0] > 1 else max(ref.shape[1], 1), rlp, rip, int(eos), sp,
+        0 if skip is None else skip.shape[0], op, c_p(out[1].data_ptr()), c_p(out[2].data_ptr()), tp, stream())
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("asr_edit_distance_i32: more than %d columns (hyp %d, ref %d)"
+                               % (ED_MAX_COLS, hyp.shape[1], ref.shape[1]))
+    check(rc, "asr_edit_distance_i32")
+    return out[0], out[1], out[2]
 
 
 def lm_step(R, H, In, xin, wcat, bcat, c_prev, c_out, h_out, h_out2=None):

@@ -22,7 +22,8 @@ from dataset import PickleDataset
 from feed import DeviceFeed
 from model import E2E, LM
 from parallel import FlatAdam
-from utils import Logger, adjust_learning_rate, calculate_cer, cc, infinite_iter, remove_pad_eos, to_sents
+from utils import (Logger, adjust_learning_rate, calculate_cer, calculate_cer_ids, cc, infinite_iter, remove_pad_eos,
+                   to_sents)
 
 
 class StepScalar(object):
@@ -216,10 +217,23 @@ class Solver(object):
             print(self.judge)
 
     # ------------------------------------------------------------------ text scoring
+    def _cer_device(self):
+        """The device that scores CER when `cer_on_gpu` (not a reference key; default false) is set and the model is on a
+        GPU: one launch of the edit-distance kernel over the whole set (utils.calculate_cer_ids) instead of the host's
+        Levenshtein loop per utterance; None: the host loop."""
+        dev = next(self.model.parameters()).device
+        return dev if self.config.get("cer_on_gpu", False) and dev.type == "cuda" else None
+
+    def _score_ids(self, hyp_ids, ref_ids, ref_index=None):
+        return calculate_cer_ids(hyp_ids, ref_ids, self.vocab, self.non_lang_syms, self.vocab["<EOS>"], self._cer_device(),
+                                 ref_index=ref_index)
+
     def ind2sent(self, all_prediction, all_ys):
         hyp_ids = remove_pad_eos(all_prediction, eos=self.vocab["<EOS>"])
         hyps = to_sents(hyp_ids, self.vocab, self.non_lang_syms)
         refs = to_sents(all_ys, self.vocab, self.non_lang_syms)
+        if self._cer_device() is not None:
+            return self._score_ids(hyp_ids, all_ys)[0], hyps, refs
         return calculate_cer(hyps, refs), hyps, refs
 
     def _abort_seen(self, dev):
@@ -252,14 +266,15 @@ class Solver(object):
             out = run()
         return out
 
-    def _beam(self, xs, ilens, beam_size, lm_weight=0.0):
+    def _beam(self, xs, ilens, beam_size, lm_weight=0.0, nbest=False):
         """Best beam-search hypothesis ids for one batch (E2E.recognize_beams; lm_weight > 0: rescored by the judge, shallow
-        fusion).  The encoder still runs on the persistent LSTM kernels: the abort word is checked after the decode and
-        the batch repeated on the per-step kernels, as in _greedy."""
+        fusion) - with nbest all beam_size of them per utterance, ranked ([B][K][L]).  The encoder still runs on the
+        persistent LSTM kernels: the abort word is checked after the decode and the batch repeated on the per-step kernels,
+        as in _greedy."""
         def run():
             prediction, _ = self.model.recognize_beams(
                 xs, ilens, self.config["max_dec_timesteps"], beam_size,
-                length_penalty=float(self.config.get("beam_length_penalty", 0.0)),
+                length_penalty=float(self.config.get("beam_length_penalty", 0.0)), nbest=nbest,
                 lm=self.judge if lm_weight > 0 else None, lm_weight=lm_weight)
             return prediction.cpu().numpy().tolist()
         out = run()
@@ -332,10 +347,16 @@ class Solver(object):
                                  drop_last=False)
         self.model.eval()
         beam_size = int(self.config.get("beam_size", 1) or 1)    # not reference keys: beam_size, beam_length_penalty
-        preds, refs = [], []
+        # with `cer_on_gpu` a beam search keeps all its K hypotheses per utterance: the best-of-K CER below
+        nbest = beam_size > 1 and self._cer_device() is not None
+        preds, refs, beams = [], [], []
         for batch in self._feed(loader, sharded=False):
             xs, ilens, _ = batch
-            if lm_weight > 0:
+            if nbest:
+                ranked = self._beam(xs, ilens, beam_size, lm_weight, nbest=True)
+                preds += [hyps[0] for hyps in ranked]
+                beams += ranked
+            elif lm_weight > 0:
                 preds += self._beam(xs, ilens, beam_size, lm_weight)
             else:
                 preds += self._beam(xs, ilens, beam_size) if beam_size > 1 else self._greedy(xs, ilens)
@@ -343,10 +364,26 @@ class Solver(object):
         self.model.train()
         if lm_weight > 0:
             self.judge.train(judge_was_training)
-        cer, hyp_sents, _ = self.ind2sent(preds, refs)
+        self.last_test = dict(cer=None, best_of_k_cer=None, dist=None, ref_n=None)
+        if nbest:
+            # every hypothesis of every utterance against the utterance's reference in one launch; a rank the search left
+            # without a hypothesis is a row of <EOS>: an empty hypothesis.  The rank-0 rows give the CER itself.
+            K = beam_size
+            _, dist, ref_n = self._score_ids([h for hyps in beams for h in hyps], refs,
+                                             ref_index=[b for b in range(len(beams)) for _ in range(K)])
+            dist = [dist[b * K:(b + 1) * K] for b in range(len(beams))]
+            ref_n = ref_n[::K]
+            cer = float(sum(d[0] for d in dist)) / float(sum(ref_n))
+            best_of_k = float(sum(min(d) for d in dist)) / float(sum(ref_n))
+            self.last_test.update(best_of_k_cer=best_of_k, dist=dist, ref_n=ref_n)
+            hyp_sents = to_sents(remove_pad_eos(preds, eos=self.vocab["<EOS>"]), self.vocab, self.non_lang_syms)
+        else:
+            cer, hyp_sents, _ = self.ind2sent(preds, refs)
+        self.last_test["cer"] = cer
         with open(f"{test_set}.txt", "w") as f:
             f.writelines(f"{p}\n" for p in hyp_sents)
-        print(f"{test_set}: {len(hyp_sents)} utterances, CER={cer:.4f}")
+        print(f"{test_set}: {len(hyp_sents)} utterances, CER={cer:.4f}"
+              + (f", best of {beam_size} hypotheses: CER={self.last_test['best_of_k_cer']:.4f}" if nbest else ""))
         return cer
 
     # ------------------------------------------------------------------ judge (LM) pre-training
