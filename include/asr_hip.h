@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define ASR_ABI_VERSION 6
+#define ASR_ABI_VERSION 7
 
 #define ASR_E_ARG    (-1)  /* null pointer / non-positive size */
 #define ASR_E_SHAPE  (-2)  /* size not supported by the kernel (see each function) */
@@ -86,18 +86,6 @@ int asr_abi_version(void);
 #define ASR_GEMM_C_ZEROED    0x2000
 #define ASR_LSTM_BWD_GATHER  0x400
 #define ASR_DEBUG_FAULT      0x10000
-
-/* ---------------------------------------------------------------------------------------
- * Graph memo for the per-time-step launch chains (asr_lstm_seq_*, asr_dec_seq_*).  The `graphs`
- * argument of those calls may be NULL (eager launches) or a handle from asr_graphs_create(): the
- * chain is then stream-captured the second time the same argument tuple is seen and replayed
- * with one hipGraphLaunch afterwards (kernel arguments are baked, so a different buffer address
- * is a different key and simply runs eagerly).  One handle per launching host thread; the handle
- * is the only state and is owned by the caller.
- * ------------------------------------------------------------------------------------- */
-void* asr_graphs_create(int max_entries);
-void asr_graphs_destroy(void* graphs);
-int asr_graphs_stats(void* graphs, int64_t* hits, int64_t* captures, int64_t* eager);
 
 /* ---------------------------------------------------------------------------------------
  * Dense fp32 GEMM on the MFMA (product arithmetic: `arith`, see above).
@@ -191,7 +179,7 @@ int asr_colsum_f32(int64_t M, int64_t N, const float* X, int64_t ldx, float* out
  * ------------------------------------------------------------------------------------- */
 int asr_lstm_seq_fwd(int T, int B, int nb, int H, int ndir, float* gates, const float* w_hh,
                      const int32_t* lens, const int32_t* rowbase, const int32_t* rowext, float* y, float* c,
-                     void* graphs, asr_stream_t stream);
+                     asr_stream_t stream);
 
 /* Persistent fast path of asr_lstm_seq_fwd (same arguments and results; csrc/lstm_persist.hip): ONE launch runs
  * all T steps, each XCD owns a (direction, 8- or 4-row) group, W_hh stays in registers, h_t is exchanged inside the
@@ -229,7 +217,7 @@ int asr_lstm_seq_fwd_persist(int T, int B, int nb, int H, int ndir, float* gates
  * (transA=1) over the whole sequence after this call. */
 int asr_lstm_seq_bwd(int T, int B, int nb, int H, int ndir, float* gates, const float* w_hhT,
                      const int32_t* lens, const int32_t* rowbase, const int32_t* rowext, const float* dy, const float* c,
-                     float* dcarry, void* graphs, asr_stream_t stream);
+                     float* dcarry, asr_stream_t stream);
 /* Persistent fast path of asr_lstm_seq_bwd (same conditions / scratch / abort convention as asr_lstm_seq_fwd_persist;
  * H in {128, 256, 320, 512}, and 640 under ASR_ARITH_BF16X6).  With a bf16 arithmetic and H in {128, 256, 512} - and
  * H = 320 (10 units per CU in 12 slots) / H = 640 (20 units per CU, its own kernel) under ASR_ARITH_BF16X6 - the CUs of a
@@ -370,7 +358,7 @@ int asr_dec_step_fwd(const asr_dec_fwd_t* p, int s, asr_stream_t stream);
 /* attention part of step s only (AttLoc.forward model.py:139-173): z is read from X[s+1][:,0:D]; writes
  * mlp_o(context) to X[s+1][:,D:D+O] and the weights to ws[s] */
 int asr_att_step_fwd(const asr_dec_fwd_t* p, int s, asr_stream_t stream);
-int asr_dec_seq_fwd(const asr_dec_fwd_t* p, int s_begin, int s_end, void* graphs, asr_stream_t stream);
+int asr_dec_seq_fwd(const asr_dec_fwd_t* p, int s_begin, int s_end, asr_stream_t stream);
 /* Persistent fast path of asr_dec_seq_fwd(p, 0, L): all L teacher-forced steps in one launch per 32 rows (each XCD
  * owns 4 utterances; W_cat, W_dec and the P slice stay in registers, exchanges stay in the XCD's L2).  Same results
  * except that Dproj is not written.  Returns ASR_E_SHAPE (-2) when it does not apply ((D,A,O,E) other than
@@ -446,7 +434,7 @@ typedef struct {
 } asr_dec_bwd_t;
 
 int asr_dec_step_bwd(const asr_dec_bwd_t* p, int s, asr_stream_t stream);
-int asr_dec_seq_bwd(const asr_dec_bwd_t* p, int s_begin, int s_end, void* graphs, asr_stream_t stream);
+int asr_dec_seq_bwd(const asr_dec_bwd_t* p, int s_begin, int s_end, asr_stream_t stream);
 /* Persistent fast path of asr_dec_seq_bwd(p, 0, L) (same applicability rule and scratch convention as
  * asr_dec_seq_fwd_persist; the sequence must have been teacher-forced).  mbuf: caller-allocated scratch
  * [L][B][C][Tp].  Results as the per-step path in G[:, :, D:], dgates, dD, dP; dgvec_part / dwatt_part / dconv_part

@@ -10,7 +10,6 @@
 // sums are written as partial slabs and added by the consumer kernel of the next launch (no atomics,
 // results are bitwise reproducible run to run).
 #include "common.h"
-#include "graphs.h"
 
 int asr_skinny_launch(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* Bt, int64_t ldb,
                       float* C, int64_t ldc, const float* bias, int accumulate, const float* mask, int64_t ldmask,
@@ -727,20 +726,15 @@ extern "C" int asr_att_step_fwd(const asr_dec_fwd_t* p, int s, asr_stream_t stre
   return 0;
 }
 
-extern "C" int asr_dec_seq_fwd(const asr_dec_fwd_t* p, int s_begin, int s_end, void* graphs, asr_stream_t stream_) {
+extern "C" int asr_dec_seq_fwd(const asr_dec_fwd_t* p, int s_begin, int s_end, asr_stream_t stream_) {
   int rc = check_fwd(p);
   if (rc) return rc;
   if (s_begin < 0 || s_end > p->L || s_begin > s_end) return ASR_E_ARG;
-  struct { int kind, s0, s1; asr_dec_fwd_t f; } key;
-  memset(&key, 0, sizeof(key));
-  key.kind = 3; key.s0 = s_begin; key.s1 = s_end; key.f = *p;
-  return asr_graph_run((AsrGraphCache*)graphs, &key, sizeof(key), (hipStream_t)stream_, [&](hipStream_t stream) -> int {
-    for (int s = s_begin; s < s_end; ++s) {
-      int r = dec_step_fwd_impl(p, s, stream);
-      if (r) return r;
-    }
-    return 0;
-  });
+  for (int s = s_begin; s < s_end; ++s) {
+    rc = dec_step_fwd_impl(p, s, (hipStream_t)stream_);
+    if (rc) return rc;
+  }
+  return 0;
 }
 
 static int check_bwd(const asr_dec_bwd_t* q) {
@@ -807,18 +801,13 @@ extern "C" int asr_dec_step_bwd(const asr_dec_bwd_t* q, int s, asr_stream_t stre
   return dec_step_bwd_impl(q, s, (hipStream_t)stream_);
 }
 
-extern "C" int asr_dec_seq_bwd(const asr_dec_bwd_t* q, int s_begin, int s_end, void* graphs, asr_stream_t stream_) {
+extern "C" int asr_dec_seq_bwd(const asr_dec_bwd_t* q, int s_begin, int s_end, asr_stream_t stream_) {
   int rc = check_bwd(q);
   if (rc) return rc;
   if (s_begin < 0 || s_end > q->f.L || s_begin > s_end) return ASR_E_ARG;
-  struct { int kind, s0, s1; asr_dec_bwd_t b; } key;
-  memset(&key, 0, sizeof(key));
-  key.kind = 4; key.s0 = s_begin; key.s1 = s_end; key.b = *q;
-  return asr_graph_run((AsrGraphCache*)graphs, &key, sizeof(key), (hipStream_t)stream_, [&](hipStream_t stream) -> int {
-    for (int s = s_end - 1; s >= s_begin; --s) {
-      int r = dec_step_bwd_impl(q, s, stream);
-      if (r) return r;
-    }
-    return 0;
-  });
+  for (int s = s_end - 1; s >= s_begin; --s) {
+    rc = dec_step_bwd_impl(q, s, (hipStream_t)stream_);
+    if (rc) return rc;
+  }
+  return 0;
 }

@@ -8,7 +8,6 @@
 // hidden units in the backward; the recurrent product runs on v_mfma_f32_16x16x4_f32 with K split
 // over the 4 waves and reduced through LDS, followed by the pointwise gate math in the same kernel.
 #include "common.h"
-#include "graphs.h"
 
 namespace {
 
@@ -282,26 +281,22 @@ int asr_cell_bwd_launch(int B, int D, int KX, const float* Gnext, const float* g
 
 extern "C" int asr_lstm_seq_fwd(int T, int B, int nb, int H, int ndir, float* gates, const float* w_hh,
                                 const int32_t* lens, const int32_t* rowbase, const int32_t* rowext, float* y, float* c,
-                                void* graphs, asr_stream_t stream_) {
-  hipStream_t stream0 = (hipStream_t)stream_;
+                                asr_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   if (!gates || !w_hh || !lens || !y || !c || T <= 0 || B <= 0 || H <= 0 || nb <= 0 || nb > B) return ASR_E_ARG;
   if ((rowbase == nullptr) != (rowext == nullptr)) return ASR_E_ARG;
   if (H % 16 || (ndir != 1 && ndir != 2)) return ASR_E_SHAPE;
   if (!asr_aligned16(gates) || !asr_aligned16(w_hh) || !asr_aligned16(y)) return ASR_E_ALIGN;
-  struct { int kind, T, B, nb, H, ndir; const void *a, *b, *c, *d, *e, *f, *g; } key = {1, T, B, nb, H, ndir, gates, w_hh,
-                                                                                     lens, y, c, rowbase, rowext};
-  return asr_graph_run((AsrGraphCache*)graphs, &key, sizeof(key), stream0, [&](hipStream_t stream) -> int {
-    for (int s = 0; s < T; ++s) {
-      if (nb <= 16)
-        hipLaunchKernelGGL((enc_step_fwd_kernel<1>), dim3(H / 4, ndir, 1), dim3(256), 0, stream, T, B, nb, H, ndir,
-                           gates, w_hh, lens, y, c, s, rowbase, rowext);
-      else
-        hipLaunchKernelGGL((enc_step_fwd_kernel<2>), dim3(H / 4, ndir, (nb + 31) / 32), dim3(256), 0, stream, T, B, nb,
-                           H, ndir, gates, w_hh, lens, y, c, s, rowbase, rowext);
-    }
-    ASR_CHECK_LAUNCH();
-    return 0;
-  });
+  for (int s = 0; s < T; ++s) {
+    if (nb <= 16)
+      hipLaunchKernelGGL((enc_step_fwd_kernel<1>), dim3(H / 4, ndir, 1), dim3(256), 0, stream, T, B, nb, H, ndir,
+                         gates, w_hh, lens, y, c, s, rowbase, rowext);
+    else
+      hipLaunchKernelGGL((enc_step_fwd_kernel<2>), dim3(H / 4, ndir, (nb + 31) / 32), dim3(256), 0, stream, T, B, nb,
+                         H, ndir, gates, w_hh, lens, y, c, s, rowbase, rowext);
+  }
+  ASR_CHECK_LAUNCH();
+  return 0;
 }
 
 #ifndef ASR_BWD_UNITS
@@ -316,45 +311,18 @@ extern "C" int asr_lstm_seq_fwd(int T, int B, int nb, int H, int ndir, float* ga
 
 extern "C" int asr_lstm_seq_bwd(int T, int B, int nb, int H, int ndir, float* gates, const float* w_hhT,
                                 const int32_t* lens, const int32_t* rowbase, const int32_t* rowext, const float* dy,
-                                const float* c, float* dcarry, void* graphs, asr_stream_t stream_) {
-  hipStream_t stream0 = (hipStream_t)stream_;
+                                const float* c, float* dcarry, asr_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   if (!gates || !w_hhT || !lens || !dy || !c || !dcarry || T <= 0 || B <= 0 || H <= 0 || nb <= 0 || nb > B)
     return ASR_E_ARG;
   if ((rowbase == nullptr) != (rowext == nullptr)) return ASR_E_ARG;
   if (H % 16 || (ndir != 1 && ndir != 2)) return ASR_E_SHAPE;
   if (!asr_aligned16(gates) || !asr_aligned16(w_hhT)) return ASR_E_ALIGN;
   constexpr int U = ASR_BWD_UNITS, MTB = ASR_BWD_MT, NWB = ASR_BWD_NW;
-  struct { int kind, T, B, nb, H, ndir; const void *a, *b, *c, *d, *e, *f, *g, *h; } key = {2, T, B, nb, H, ndir, gates, w_hhT,
-                                                                                         lens, dy, c, dcarry, rowbase, rowext};
-  return asr_graph_run((AsrGraphCache*)graphs, &key, sizeof(key), stream0, [&](hipStream_t stream) -> int {
-    for (int s = 0; s < T; ++s) {
-      hipLaunchKernelGGL((enc_step_bwd_kernel<MTB, U, NWB>), dim3(H / U, ndir, (nb + MTB * 16 - 1) / (MTB * 16)),
-                         dim3(NWB * 64), 0, stream, T, B, nb, H, ndir, gates, w_hhT, lens, dy, c, dcarry, s, rowbase, rowext);
-    }
-    ASR_CHECK_LAUNCH();
-    return 0;
-  });
-}
-
-extern "C" void* asr_graphs_create(int max_entries) {
-  AsrGraphCache* gc = new AsrGraphCache();
-  if (max_entries > 0) gc->max_entries = (size_t)max_entries;
-  return gc;
-}
-
-extern "C" void asr_graphs_destroy(void* graphs) {
-  AsrGraphCache* gc = (AsrGraphCache*)graphs;
-  if (!gc) return;
-  for (auto& e : gc->entries)
-    if (e.exec) (void)hipGraphExecDestroy(e.exec);
-  delete gc;
-}
-
-extern "C" int asr_graphs_stats(void* graphs, int64_t* hits, int64_t* captures, int64_t* eager) {
-  AsrGraphCache* gc = (AsrGraphCache*)graphs;
-  if (!gc) return ASR_E_ARG;
-  if (hits) *hits = (int64_t)gc->hits;
-  if (captures) *captures = (int64_t)gc->captures;
-  if (eager) *eager = (int64_t)gc->eager;
+  for (int s = 0; s < T; ++s) {
+    hipLaunchKernelGGL((enc_step_bwd_kernel<MTB, U, NWB>), dim3(H / U, ndir, (nb + MTB * 16 - 1) / (MTB * 16)),
+                       dim3(NWB * 64), 0, stream, T, B, nb, H, ndir, gates, w_hhT, lens, dy, c, dcarry, s, rowbase, rowext);
+  }
+  ASR_CHECK_LAUNCH();
   return 0;
 }

@@ -11,7 +11,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libasr_hip.so")
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 EXPORTS = (
     "asr_abi_version", "asr_persist_scratch_bytes", "asr_gemm_f32", "asr_gemm_skinny_f32", "asr_colsum_f32",
@@ -22,7 +22,7 @@ EXPORTS = (
     "asr_lstm_pack_f32", "asr_lstm_unpack_f32", "asr_lstm_unpack2_f32", "asr_dec_prepare_f32", "asr_cell_pack_f32", "asr_cell_unpack_f32",
     "asr_lstm_pack_multi_f32", "asr_lstm_unpack_multi_f32", "asr_dec_pack_f32", "asr_colsum_parts_f32", "asr_gemm_drop_f32", "asr_gemm_side_f32", "asr_embedding_grad_f32",
     "asr_label_logprob_fwd", "asr_label_logprob_bwd", "asr_dec_feedback_fwd", "asr_dec_feedback_bwd",
-    "asr_adam_clip_f32", "asr_sumsq_f32", "asr_gather_sumsq_f32", "asr_graphs_create", "asr_graphs_destroy", "asr_graphs_stats",
+    "asr_adam_clip_f32", "asr_sumsq_f32", "asr_gather_sumsq_f32",
     "asr_beam_select_f32", "asr_beam_reorder_f32", "asr_beam_backtrack",
     "asr_lm_step_f32", "asr_beam_select_lm_f32", "asr_beam_reorder_lm_f32",
     "asr_edit_distance_i32",
@@ -110,7 +110,7 @@ class DecBuffers(object):
             staging tensors for the inputs, and - with_bwd - the backward's scratch and its accumulators `acc` (a dict: G,
             dwext, dP, dcell, dgvec_part, dwatt_part, dconv_part), cut from ONE buffer `zbuf` that one fill zeroes;
       bind()    the per-call inputs used as they are (no staging copies), kept alive here until the next bind();
-      fwd_struct / bwd_struct   the structs for batch rows [b0, b0 + nb): every per-row pointer advanced by b0 rows;
+      fwd_struct / bwd_struct   the structs over all B rows (nb = B);
       accumulators(base)   `acc` laid out over another zeroed buffer (the step arena's slice) instead of zbuf."""
 
     _ACC = ("G", "dwext", "dP", "dcell", "dgvec_part", "dwatt_part", "dconv_part")
@@ -130,10 +130,6 @@ class DecBuffers(object):
         self.gates, self.cstate = torch.empty(L, B, 4 * D, **f32), torch.empty(L, B, D, **f32)
         self.Dproj, self.fconv = torch.empty(L, B, A, **f32), torch.empty(L, B, C, Tp, **f32)
         self.S, self.energy, self.ws = torch.empty(L, B, Tp, A, **f32), torch.empty(L, B, Tp, **f32), torch.empty(L, B, Tp, **f32)
-        # floats per batch row of every field a row group advances (the fields not named here are shared by all rows)
-        self._row = dict(P=Tp * A, Q=Tp * O, w0=Tp, xmask=O + E, X=KX, Xd=KX, gates=4 * D, cstate=D, Dproj=A, fconv=C * Tp,
-                         S=Tp * A, energy=Tp, ws=Tp, dws=Tp, G=KX, dwext=Tp, dwraw=Tp, dfpart=C * Tp, dP=Tp * A, dgates=4 * D,
-                         dD=A, dcell=D, dgvec_part=A, dwatt_part=A * C, dconv_part=C * (2 * K + 1))
         self.zbuf = self.acc = None
         if with_bwd:
             ntile = (A + 63) // 64
@@ -171,20 +167,18 @@ class DecBuffers(object):
         first = base.storage_offset()
         return {name: base.as_strided(shape, strides, first + off) for name, shape, strides, off in self._acc_layout}
 
-    def fwd_struct(self, b0=0, nb=None):
-        """asr_dec_fwd_t for rows [b0, b0 + nb) (pointers pre-offset, B = stride)."""
-        row = self._row
-        return DecFwd(nb=self.B if nb is None else nb, scaling=self.scaling,
-                      **{n: _fptr(getattr(self, n), b0 * row.get(n, 0)) for n in _DEC_FWD_PTRS}, **self.dims)
+    def fwd_struct(self):
+        """asr_dec_fwd_t over all B rows."""
+        return DecFwd(nb=self.B, scaling=self.scaling, **{n: _fptr(getattr(self, n)) for n in _DEC_FWD_PTRS}, **self.dims)
 
-    def bwd_struct(self, b0=0, nb=None, acc=None, with_dws=True):
-        """asr_dec_bwd_t for rows [b0, b0 + nb).  acc: the accumulators to use (accumulators(); None: those in zbuf);
+    def bwd_struct(self, acc=None, with_dws=True):
+        """asr_dec_bwd_t over all B rows.  acc: the accumulators to use (accumulators(); None: those in zbuf);
         with_dws False: no gradient arrives through the attention weights (dws = NULL)."""
-        acc, own, row = self.acc if acc is None else acc, self.__dict__, self._row
-        ptrs = {n: _fptr(acc[n] if n in acc else own[n], b0 * row.get(n, 0)) for n in _DEC_BWD_PTRS}
+        acc, own = self.acc if acc is None else acc, self.__dict__
+        ptrs = {n: _fptr(acc[n] if n in acc else own[n]) for n in _DEC_BWD_PTRS}
         if not with_dws:
             ptrs["dws"] = None
-        return DecBwd(f=self.fwd_struct(b0, nb), **ptrs)
+        return DecBwd(f=self.fwd_struct(), **ptrs)
 
 
 def load():
@@ -199,24 +193,19 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name in EXPORTS:
         getattr(lib, name).restype = c_i
-    lib.asr_graphs_create.restype = c_p
-    lib.asr_graphs_create.argtypes = [c_i]
-    lib.asr_graphs_destroy.restype = None
-    lib.asr_graphs_destroy.argtypes = [c_p]
-    lib.asr_graphs_stats.argtypes = [c_p, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]
     lib.asr_persist_scratch_bytes.argtypes = [ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]
     lib.asr_gemm_f32.argtypes = [c_i, c_i, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i, c_i,
                                  c_i, c_i64, c_i64, c_i64, c_i, c_i, c_p]
     lib.asr_gemm_skinny_f32.argtypes = [c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i, c_p,
                                         c_i64, c_i64, c_p]
     lib.asr_colsum_f32.argtypes = [c_i64, c_i64, c_p, c_i64, c_p, c_i, c_p]
-    lib.asr_lstm_seq_fwd.argtypes = [c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]
+    lib.asr_lstm_seq_fwd.argtypes = [c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]
     lib.asr_lstm_seq_fwd_persist.argtypes = [c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p]
     lib.asr_lstm_seq_bwd_persist.argtypes = [c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                              c_i, c_p]
     lib.asr_lstm_seq_bwd_persist_w.argtypes = lib.asr_lstm_seq_bwd_persist.argtypes
     lib.asr_lstm_bwd_persist_fuses_dw.argtypes = [c_i, c_i]
-    lib.asr_lstm_seq_bwd.argtypes = [c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]
+    lib.asr_lstm_seq_bwd.argtypes = [c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]
     lib.asr_rows_pack_f32.argtypes = [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p]
     lib.asr_rows_unpack_fwd_f32.argtypes = [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, ctypes.c_uint64, c_f, c_p, c_p]
     lib.asr_rows_unpack_bwd_f32.argtypes = [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, ctypes.c_uint64, c_f, c_p, c_p, c_p, c_p]
@@ -239,12 +228,12 @@ def load():
     lib.asr_edit_distance_i32.argtypes = [c_i, c_p, c_i, c_i64, c_i, c_p, c_p, c_i64, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p,
                                           c_p, c_p]
     lib.asr_att_step_fwd.argtypes = [ctypes.POINTER(DecFwd), c_i, c_p]
-    lib.asr_dec_seq_fwd.argtypes = [ctypes.POINTER(DecFwd), c_i, c_i, c_p, c_p]
+    lib.asr_dec_seq_fwd.argtypes = [ctypes.POINTER(DecFwd), c_i, c_i, c_p]
     lib.asr_dec_seq_fwd_persist.argtypes = [ctypes.POINTER(DecFwd), c_p, c_p, c_p]
     lib.asr_dec_seq_fwd_persist_fault.argtypes = lib.asr_dec_seq_fwd_persist.argtypes
     lib.asr_dec_seq_fwd_persist_free.argtypes = [ctypes.POINTER(DecFwd), ctypes.POINTER(DecFeedback), c_p, c_p, c_p]
     lib.asr_dec_step_bwd.argtypes = [ctypes.POINTER(DecBwd), c_i, c_p]
-    lib.asr_dec_seq_bwd.argtypes = [ctypes.POINTER(DecBwd), c_i, c_i, c_p, c_p]
+    lib.asr_dec_seq_bwd.argtypes = [ctypes.POINTER(DecBwd), c_i, c_i, c_p]
     lib.asr_dec_seq_bwd_persist.argtypes = [ctypes.POINTER(DecBwd), c_p, c_p, c_p, c_p]
     lib.asr_dec_seq_bwd_persist_free.argtypes = [ctypes.POINTER(DecBwd), ctypes.POINTER(DecFeedbackBwd), c_p, c_p, c_p, c_p]
     lib.asr_adam_clip_f32.argtypes = [c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p, c_p]
@@ -696,85 +685,6 @@ def colsum(X, out=None, accumulate=False):
         out = torch.empty(N, device=X.device, dtype=torch.float32)
     check(load().asr_colsum_f32(M, N, ptr(X), ldx, ptr(out), int(accumulate), stream()), "asr_colsum_f32")
     return out
-
-
-# ---------------------------------------------------------------------------------------------------
-# Utterance-group concurrency: the recurrent chains are latency-bound (one small kernel per time step), and
-# utterances are independent, so disjoint row groups run on separate HIP streams and overlap each other's
-# launch-boundary / memory latency.  Each group's launch loop runs in its own host thread (ctypes drops the
-# GIL inside the C call), so the host enqueue rate scales with the number of groups as well.
-# Measured on MI355X: graph-replayed kernels run ~0.8 us slower each than eager launches and
-# two concurrent row groups disturb each other (per-kernel cache maintenance), so the defaults are one group and
-# eager launches; graphs pay off only when the host cannot keep up (bench.py picks the faster mode in warm-up).
-GROUPS = int(os.environ.get("ASR_ROW_GROUPS", "1"))
-USE_GRAPHS = os.environ.get("ASR_GRAPHS", "0") != "0"
-_side_streams = {}
-_pool = None
-_graph_handles = {}
-
-
-def graphs_for(group_index):
-    """hipGraph memo handle of a row group (one per launching thread; see include/asr_hip.h)."""
-    if not USE_GRAPHS:
-        return None
-    key = (torch.cuda.current_device(), group_index)
-    h = _graph_handles.get(key)
-    if h is None:
-        h = c_p(load().asr_graphs_create(96))
-        _graph_handles[key] = h
-    return h
-
-
-def graph_stats():
-    out = {}
-    for key, h in _graph_handles.items():
-        a, b, c = c_i64(0), c_i64(0), c_i64(0)
-        load().asr_graphs_stats(h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
-        out[key] = dict(hits=a.value, captures=b.value, eager=c.value)
-    return out
-
-
-def row_groups(B):
-    """Split B rows into <= GROUPS contiguous groups whose sizes are multiples of 16 where possible."""
-    g = max(1, min(GROUPS, B // 16))
-    if g <= 1:
-        return [(0, B)]
-    per = ((B + g - 1) // g + 15) // 16 * 16
-    out, b0 = [], 0
-    while b0 < B:
-        out.append((b0, min(per, B - b0)))
-        b0 += per
-    return out
-
-
-def run_grouped(groups, fn):
-    """fn(group_index, (b0, nb), stream_ptr) for every group.  Every group runs on its own non-default HIP stream
-    (stream capture for the graph memo is illegal on the legacy default stream), forked from and joined back
-    into the current stream.  With several groups the launch loops run concurrently on a thread pool."""
-    global _pool
-    if len(groups) == 1 and not USE_GRAPHS:
-        fn(0, groups[0], stream())          # plain in-order launches on the current stream (fastest on the GPU side)
-        return
-    main = torch.cuda.current_stream()
-    dev = main.device
-    side = _side_streams.setdefault(dev, [])
-    while len(side) < len(groups):
-        side.append(torch.cuda.Stream(device=dev))
-    used = side[: len(groups)]
-    for st in used:
-        st.wait_stream(main)
-    if len(groups) == 1:
-        fn(0, groups[0], c_p(used[0].cuda_stream))
-    else:
-        from concurrent.futures import ThreadPoolExecutor
-        if _pool is None:
-            _pool = ThreadPoolExecutor(max_workers=8)
-        futs = [_pool.submit(fn, gi, groups[gi], c_p(used[gi].cuda_stream)) for gi in range(1, len(groups))]
-        fn(0, groups[0], c_p(used[0].cuda_stream))
-        for f in futs:
-            f.result()
-    for st in used:
-        main.wait_stream(st)
 
 
 _pinned_ring = {}
@@ -1247,7 +1157,7 @@ class LayerRows(object):
         return c_p(self.lens_host.ctypes.data)
 
 
-def lstm_seq_fwd(gates, w_hh, lens, y, c, use_graphs=True, rows=None):
+def lstm_seq_fwd(gates, w_hh, lens, y, c, rows=None):
     """rows: a LayerRows - gates / y / c are then row matrices [R, 1, ...] in the packed layout (lens = rows.lens)."""
     T, B, ndir, H4 = gates.shape
     H = H4 // 4
@@ -1262,19 +1172,8 @@ def lstm_seq_fwd(gates, w_hh, lens, y, c, use_graphs=True, rows=None):
         count_path("lstm_fwd", True)
         return
     count_path("lstm_fwd", False, "H=%d B=%d ndir=%d persist=%s" % (H, B, ndir, USE_PERSIST))
-    groups = row_groups(B)
-    gh = [graphs_for(i) if use_graphs else None for i in range(len(groups))]     # created on the calling thread
-
-    def one(gi, grp, st):
-        b0, nb = grp
-        if rows is not None:                               # packed rows: the row maps are absolute, only they advance
-            check(lib.asr_lstm_seq_fwd(T, B, nb, H, ndir, ptr(gates), ptr(w_hh), _off(lens, b0), _off(rows.base, b0),
-                                       _off(rows.ext, b0), ptr(y), ptr(c), gh[gi], st), "asr_lstm_seq_fwd")
-            return
-        check(lib.asr_lstm_seq_fwd(T, B, nb, H, ndir, _off(gates, b0 * ndir * H4), ptr(w_hh), _off(lens, b0), None, None,
-                                   _off(y, b0 * ndir * H), _off(c, b0 * ndir * H), gh[gi], st), "asr_lstm_seq_fwd")
-
-    run_grouped(groups, one)
+    check(lib.asr_lstm_seq_fwd(T, B, B, H, ndir, ptr(gates), ptr(w_hh), ptr(lens), rb, re, ptr(y), ptr(c), stream()),
+          "asr_lstm_seq_fwd")
 
 
 def lstm_seq_bwd(gates, w_hhT, lens, dy, c, dcarry, y=None, dw_hh=None, db=None, w_hh=None, rows=None):
@@ -1307,21 +1206,8 @@ def lstm_seq_bwd(gates, w_hhT, lens, dy, c, dcarry, y=None, dw_hh=None, db=None,
         count_path("lstm_bwd", True)
         return fuses, db is not None
     count_path("lstm_bwd", False, "H=%d B=%d ndir=%d persist=%s" % (H, B, ndir, USE_PERSIST))
-    groups = row_groups(B)
-    gh = [graphs_for(i) for i in range(len(groups))]
-
-    def one(gi, grp, st):
-        b0, nb = grp
-        if rows is not None:
-            check(lib.asr_lstm_seq_bwd(T, B, nb, H, ndir, ptr(gates), ptr(w_hhT), _off(lens, b0), _off(rows.base, b0),
-                                       _off(rows.ext, b0), ptr(dy), ptr(c), _off(dcarry, b0 * ndir * H), gh[gi], st),
-                  "asr_lstm_seq_bwd")
-            return
-        check(lib.asr_lstm_seq_bwd(T, B, nb, H, ndir, _off(gates, b0 * ndir * H4), ptr(w_hhT), _off(lens, b0), None, None,
-                                   _off(dy, b0 * ndir * H), _off(c, b0 * ndir * H), _off(dcarry, b0 * ndir * H), gh[gi],
-                                   st), "asr_lstm_seq_bwd")
-
-    run_grouped(groups, one)
+    check(lib.asr_lstm_seq_bwd(T, B, B, H, ndir, ptr(gates), ptr(w_hhT), ptr(lens), rb, re, ptr(dy), ptr(c), ptr(dcarry),
+                               stream()), "asr_lstm_seq_bwd")
     return False, False
 
 
@@ -1346,23 +1232,17 @@ def dec_shape(buf):
     return "D=%(D)d A=%(A)d O=%(O)d E=%(E)d Tp=%(Tp)d B=%(B)d" % buf.dims
 
 
-def dec_seq_fwd(buf, use_graphs=True):
+def dec_seq_fwd(buf):
     """All L steps over inputs that are complete in X / Xd before the first one (teacher forcing)."""
     lib, L = load(), buf.L
-    groups = row_groups(buf.B)
+    fs = buf.fwd_struct()
     done = False
-    if USE_PERSIST_DEC and len(groups) == 1:          # one launch for the whole sequence
+    if USE_PERSIST_DEC:          # one launch for the whole sequence
         entry = lib.asr_dec_seq_fwd_persist_fault if DEC_FAULT[0] else lib.asr_dec_seq_fwd_persist
-        done = persistent_ran(entry(ctypes.byref(buf.fwd_struct()), *_scratch_ptrs(buf.X.device), stream()),
-                              "asr_dec_seq_fwd_persist")
+        done = persistent_ran(entry(ctypes.byref(fs), *_scratch_ptrs(buf.X.device), stream()), "asr_dec_seq_fwd_persist")
     count_path("dec_fwd", done, dec_shape(buf))
     if not done:
-        gh = [graphs_for(i) if use_graphs else None for i in range(len(groups))]
-
-        def run(gi, grp, st):
-            check(lib.asr_dec_seq_fwd(ctypes.byref(buf.fwd_struct(*grp)), 0, L, gh[gi], st), "asr_dec_seq_fwd")
-
-        run_grouped(groups, run)
+        check(lib.asr_dec_seq_fwd(ctypes.byref(fs), 0, L, stream()), "asr_dec_seq_fwd")
 
 
 def dec_free_fwd(buf, w_out, b_out, emb, logits, pred, fed, probs, tokens=None, tf_flags=None, smooth=False, smooth_scaling=1.0,
@@ -1377,7 +1257,7 @@ def dec_free_fwd(buf, w_out, b_out, emb, logits, pred, fed, probs, tokens=None, 
     drop = Xd is not None
     fs = buf.fwd_struct()
     done = False
-    if USE_PERSIST_DEC and (tokens is None or not smooth) and V <= 64 and len(row_groups(B)) == 1:
+    if USE_PERSIST_DEC and (tokens is None or not smooth) and V <= 64:
         # the whole sequence in one launch, the feedback computed in the kernel: no teacher tokens at all, or
         # scheduled sampling (the host's per-step draws go along as a byte per step)
         # decoding without autograd: a group of 4 utterances stops once all of them have emitted <EOS>; the
@@ -1436,20 +1316,14 @@ def dec_seq_bwd(buf, acc, with_dws, persistent, teacher):
     inputs were all tokens (teacher forcing, or scheduled sampling inside the persistent forward: no gradient flows through an
     argmax), so the persistent kernel may run it."""
     lib, L = load(), buf.L
-    groups = row_groups(buf.B)
+    bs = buf.bwd_struct(acc=acc, with_dws=with_dws)
     done = False
-    if USE_PERSIST_DEC_BWD and persistent and len(groups) == 1:
-        done = persistent_ran(lib.asr_dec_seq_bwd_persist(ctypes.byref(buf.bwd_struct(0, None, acc, with_dws)), _fptr(buf.Mf),
-                                                          *_scratch_ptrs(buf.X.device), stream()), "asr_dec_seq_bwd_persist")
+    if USE_PERSIST_DEC_BWD and persistent:
+        done = persistent_ran(lib.asr_dec_seq_bwd_persist(ctypes.byref(bs), _fptr(buf.Mf), *_scratch_ptrs(buf.X.device), stream()),
+                              "asr_dec_seq_bwd_persist")
     count_path("dec_bwd", done, "%s teacher=%s" % (dec_shape(buf), teacher))
     if not done:
-        gh = [graphs_for(i) for i in range(len(groups))]
-
-        def run(gi, grp, st):
-            bg = buf.bwd_struct(grp[0], grp[1], acc, with_dws)
-            check(lib.asr_dec_seq_bwd(ctypes.byref(bg), 0, L, gh[gi], st), "asr_dec_seq_bwd")
-
-        run_grouped(groups, run)
+        check(lib.asr_dec_seq_bwd(ctypes.byref(bs), 0, L, stream()), "asr_dec_seq_bwd")
 
 
 def dec_smooth_bwd(buf, acc, with_dws, w_out, emb, probs, scaling, dlog):
@@ -1458,9 +1332,9 @@ def dec_smooth_bwd(buf, acc, with_dws, w_out, emb, probs, scaling, dlog):
     of the logits from outside.  -> dtot [L, B, V] = dlog + what reaches the logits through the feedback (the weight gradients
     that depend on it are the caller's: one product each over the whole sequence)."""
     B, L, DO, V = buf.B, buf.L, buf.dims["D"] + buf.dims["O"], w_out.shape[0]
-    bs = buf.bwd_struct(0, None, acc, with_dws)
+    bs = buf.bwd_struct(acc=acc, with_dws=with_dws)
     done = False
-    if USE_PERSIST_DEC_BWD and L > 1 and len(row_groups(B)) == 1:
+    if USE_PERSIST_DEC_BWD and L > 1:
         # the whole free-running sequence in one launch: the feedback path (d(emb_s) -> logit_{s-1} -> [z, ctx]_{s-1})
         # is carried inside the persistent kernel (dec_persist.hip, template FB)
         dlfb = torch.zeros(L, B, V, device=dlog.device, dtype=torch.float32)

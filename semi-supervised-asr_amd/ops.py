@@ -9,12 +9,11 @@ recurrence, decoder loop) never bounce through Python/autograd per time step:
     decoder_sequence  all decoder steps incl. attention           -> asr_dec_* (+ GEMMs)
 
 The Functions here are autograd bookkeeping: which buffers, which gradients, in which order.  The ctypes calls, the choice
-"persistent kernel, else the per-step chain", the row groups and the path counters are hip_backend's (lstm_seq_fwd / _bwd;
+"persistent kernel, else the per-step chain" and the path counters are hip_backend's (lstm_seq_fwd / _bwd;
 dec_seq_fwd, dec_free_fwd, dec_seq_bwd, dec_smooth_bwd on a hip_backend.DecBuffers).
 
-Workspaces.  The per-time-step launch chains are replayed as HIP graphs whose kernel arguments are baked
-(see csrc/graphs.h), so the chain buffers must keep their addresses from step to step.  Each chain op
-therefore leases a preallocated, shape-keyed workspace from a pool for the span forward -> end of backward
+Workspaces.  Each chain op leases a preallocated, shape-keyed workspace from a pool for the span forward ->
+end of backward, so that a train step causes no allocator traffic
 (`_Lease`); a second concurrent user of the same shape (e.g. the two model passes of the SSL step) simply gets
 another instance.  With autograd disabled (validation / greedy decoding) plain fresh tensors are used.
 Outputs that alias a workspace (`y`) are only valid until that op's backward has run — the model consumes
@@ -469,7 +468,7 @@ class _LstmLayer(torch.autograd.Function):
         ctx.side_mask = _SIDE.mask_hint = _SIDE.mask_for(nbatch) if pooled else 0
         ws["lens"] = lens                      # int32 device tensor, kept for the backward (no copy)
         hb.gemm(x2, w_ih, trans_b=True, bias=bias, out=ws["gates"].view(T * B, ndir * 4 * H))
-        hb.lstm_seq_fwd(ws["gates"], w_hh, ws["lens"], ws["y"], ws["c"], use_graphs=pooled, rows=rows)
+        hb.lstm_seq_fwd(ws["gates"], w_hh, ws["lens"], ws["y"], ws["c"], rows=rows)
         ctx.save_for_backward(x2, w_ih, w_hh)
         ctx.lease = lease
         ctx.rows = rows
@@ -635,7 +634,7 @@ def _dec_clear(buf):
     return fed
 
 
-def _dec_teacher_forced(buf, emb_w, tokens, w_out, b_out, use_graphs, skip_pred):
+def _dec_teacher_forced(buf, emb_w, tokens, w_out, b_out, skip_pred):
     """Every step is fed its teacher token: the inputs are complete before the first step.  -> fed, logits, pred"""
     B, L, D, O, E = (buf.dims[k] for k in "BLDOE")
     X, Xd, xmask = buf.X, buf.Xd, buf.xmask
@@ -649,7 +648,7 @@ def _dec_teacher_forced(buf, emb_w, tokens, w_out, b_out, use_graphs, skip_pred)
         X[:L, :, D + O:] = emb_w[fed]
         if Xd is not None:
             Xd[:L, :, D + O:] = X[:L, :, D + O:] * xmask[:, :, O:]
-    hb.dec_seq_fwd(buf, use_graphs)
+    hb.dec_seq_fwd(buf)
     logits = hb.gemm(X[1:].view(L * B, buf.KX)[:, :D + O], w_out, trans_b=True, bias=b_out).view(L, B, w_out.shape[0])
     # (skip_pred: the caller takes the argmax from the loss kernel that reads the logits anyway - label_logprob)
     return fed, logits, (None if skip_pred else logits.argmax(-1))
@@ -715,7 +714,7 @@ def _dec_smooth_bwd_torch(buf, acc, with_dws, w_out, emb_w, probs_saved, k, dw_o
     between the per-step kernels, and the weight gradients that depend on it are added step by step."""
     D, O = buf.dims["D"], buf.dims["O"]
     hb.count_path("dec_bwd", False, "free-running smooth: %s L=%d fused-feedback=False" % (hb.dec_shape(buf), buf.L))
-    bs = buf.bwd_struct(0, None, acc, with_dws)
+    bs = buf.bwd_struct(acc=acc, with_dws=with_dws)
     G, X = acc["G"], buf.X
     for s in range(buf.L - 1, -1, -1):
         hb.dec_step_bwd(bs, s)
@@ -781,7 +780,7 @@ class _DecoderSeq(torch.autograd.Function):
         all_teacher = tokens is not None and (tf_flags is None or all(tf_flags)) and not sample
         probs_saved, done = [], False
         if all_teacher:
-            fed, logits, pred = _dec_teacher_forced(buf, emb_w, tokens, w_out_c, b_out, pooled, opts.get("skip_pred"))
+            fed, logits, pred = _dec_teacher_forced(buf, emb_w, tokens, w_out_c, b_out, opts.get("skip_pred"))
         elif hb.USE_FEEDBACK_KERNEL and not sample and V <= 128:
             fed, logits, pred, probs_saved, done = _dec_free_kernels(buf, emb_w, tokens, tf_flags, smooth, opts, w_out_c, b_out)
         else:

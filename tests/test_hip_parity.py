@@ -1944,7 +1944,7 @@ def test_lstm_kernel_raises_its_own_abort_and_the_next_launch_is_clean():
     def run():
         gts, y, c = gates0.clone(), torch.empty(T, B, ndir * H, device=dev), torch.empty(T, B, ndir * H, device=dev)
         with hb.require_persistent():
-            hb.lstm_seq_fwd(gts, whh, lens, y, c, use_graphs=False)
+            hb.lstm_seq_fwd(gts, whh, lens, y, c)
         return y
     hb.persist_clear_abort(dev)
     want = run()

@@ -17,11 +17,11 @@ fs=buf.fwd_struct()
 st=ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 for path in sorted(glob.glob(ROOT+'/scratchlibs/lib_*.so')):
     l=ctypes.CDLL(path); l.asr_dec_seq_fwd.restype=ctypes.c_int
-    l.asr_dec_seq_fwd.argtypes=[ctypes.POINTER(hb.DecFwd),ctypes.c_int,ctypes.c_int,ctypes.c_void_p,ctypes.c_void_p]
+    l.asr_dec_seq_fwd.argtypes=[ctypes.POINTER(hb.DecFwd),ctypes.c_int,ctypes.c_int,ctypes.c_void_p]
     best=1e9
     for r in range(3):
         torch.cuda.synchronize(); e0=torch.cuda.Event(enable_timing=True); e1=torch.cuda.Event(enable_timing=True)
-        e0.record(); rc=l.asr_dec_seq_fwd(ctypes.byref(fs),0,L,None,st); e1.record(); torch.cuda.synchronize()
+        e0.record(); rc=l.asr_dec_seq_fwd(ctypes.byref(fs),0,L,st); e1.record(); torch.cuda.synchronize()
         assert rc==0, rc
         best=min(best,e0.elapsed_time(e1)*1e3/L)
     print('%-20s %.2f us/launch'%(os.path.basename(path),best),flush=True)
@@ -34,11 +34,11 @@ bufb.ws.copy_(torch.softmax(torch.randn(L,B,Tp,device=dev),-1))
 bs=bufb.bwd_struct(with_dws=False)
 for path in sorted(glob.glob(ROOT+'/scratchlibs/libb_*.so')):
     l=ctypes.CDLL(path); l.asr_dec_seq_bwd.restype=ctypes.c_int
-    l.asr_dec_seq_bwd.argtypes=[ctypes.POINTER(hb.DecBwd),ctypes.c_int,ctypes.c_int,ctypes.c_void_p,ctypes.c_void_p]
+    l.asr_dec_seq_bwd.argtypes=[ctypes.POINTER(hb.DecBwd),ctypes.c_int,ctypes.c_int,ctypes.c_void_p]
     best=1e9
     for r in range(3):
         torch.cuda.synchronize(); e0=torch.cuda.Event(enable_timing=True); e1=torch.cuda.Event(enable_timing=True)
-        e0.record(); rc=l.asr_dec_seq_bwd(ctypes.byref(bs),0,L,None,st); e1.record(); torch.cuda.synchronize()
+        e0.record(); rc=l.asr_dec_seq_bwd(ctypes.byref(bs),0,L,st); e1.record(); torch.cuda.synchronize()
         assert rc==0, rc
         best=min(best,e0.elapsed_time(e1)*1e3/L)
     print('%-20s %.2f us/launch'%(os.path.basename(path),best),flush=True)

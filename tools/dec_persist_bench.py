@@ -37,9 +37,9 @@ for path in libs:
     for f in ("asr_dec_seq_fwd_persist", "asr_dec_seq_fwd"):
         getattr(l, f).restype = ctypes.c_int
     l.asr_dec_seq_fwd_persist.argtypes = [ctypes.POINTER(hb.DecFwd), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    l.asr_dec_seq_fwd.argtypes = [ctypes.POINTER(hb.DecFwd), ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    l.asr_dec_seq_fwd.argtypes = [ctypes.POINTER(hb.DecFwd), ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     if ref is None:
-        te = timeit(lambda: l.asr_dec_seq_fwd(ctypes.byref(fs), 0, L, None, st))
+        te = timeit(lambda: l.asr_dec_seq_fwd(ctypes.byref(fs), 0, L, st))
         ref = buf.ws.clone()
         print('per-step chain: %.2f us/step' % te, flush=True)
     tp = timeit(lambda: l.asr_dec_seq_fwd_persist(ctypes.byref(fs), ctypes.c_void_p(xch.data_ptr()), ctypes.c_void_p(ctrl.data_ptr()), st))

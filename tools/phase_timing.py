@@ -35,4 +35,3 @@ for it in range(3):
     h=time.time(); sync(); t1=time.time()
     log('full step: host enqueue %.1f ms, gpu done %.1f ms'%((h-t0)*1e3,(t1-t0)*1e3))
 import hip_backend as hb
-log('graph stats', hb.graph_stats())
