@@ -361,13 +361,38 @@ int asr_att_step_fwd(const asr_dec_fwd_t* p, int s, asr_stream_t stream);
 int asr_dec_seq_fwd(const asr_dec_fwd_t* p, int s_begin, int s_end, asr_stream_t stream);
 /* Persistent fast path of asr_dec_seq_fwd(p, 0, L): all L teacher-forced steps in one launch per 32 rows (each XCD
  * owns 4 utterances; W_cat, W_dec and the P slice stay in registers, exchanges stay in the XCD's L2).  Same results
- * except that Dproj is not written.  Returns ASR_E_SHAPE (-2) when it does not apply ((D,A,O,E) other than
- * (512,512,512,128) / (320,320,320,128), Tp > 128, C > 16, K > 100, not an 8 x 32-CU device): use asr_dec_seq_fwd.
+ * except that Dproj is not written.  Returns ASR_E_SHAPE (-2) when it does not apply (see the table; not an 8 x 32-CU
+ * device): use asr_dec_seq_fwd.
  * xch and ctrl: the scratch pair of asr_lstm_seq_fwd_persist (sizes: asr_persist_scratch_bytes(); the decoder kernels
- * zero up to 3.6 MB of xch and use all 128 bytes of ctrl); abort convention as asr_lstm_seq_fwd_persist. */
+ * zero up to 3.6 MB of xch and use all 128 bytes of ctrl); abort convention as asr_lstm_seq_fwd_persist.
+ *
+ * ACCEPTED RANGES of the decoder sequence entry points.  C = conv channels, K = conv half width (2K + 1 taps), T' = Tp =
+ * encoder frames, T'p = T' rounded up to a multiple of 4, V = vocabulary; every persistent entry point also wants
+ * (D,A,O,E) = (512,512,512,128) or (320,320,320,128).  Outside its range a persistent entry point returns ASR_E_SHAPE
+ * and the caller takes the per-step one; tests/test_decoder_shapes_gpu.py runs both sides of every limit below.
+ *
+ *   entry point                         C        K        T'                                   V
+ *   asr_dec_step/seq_fwd (per step)     1..16    >= 0     any                                  -
+ *   asr_dec_step/seq_bwd (per step)     1..16    >= 0     any                                  -
+ *   asr_dec_feedback_fwd / _bwd         -        -        -                                    1..128
+ *   asr_dec_seq_fwd_persist             1..12    0..100   4 rows per group (32 per launch): T' <= 128 and C T'p <= 1024;
+ *                                                         else 2 rows per group (16 per launch): T' <= 256 and
+ *                                                         C T'p <= 3072                        -
+ *   asr_dec_seq_fwd_persist_free        as asr_dec_seq_fwd_persist                             1..64
+ *   asr_dec_seq_fwd_persist_fault       as asr_dec_seq_fwd_persist, (512,512,512,128) and the 4-row geometry only
+ *   asr_dec_seq_bwd_persist             1..16    0..100   4 rows per group: T' <= 128 and C T'p <= 1024; else 2 rows per
+ *                                                         group: T' <= 256, C T'p <= 2560 and an LDS plan (a function of
+ *                                                         T', C, K and V) of at most 160 KB    -
+ *   asr_dec_seq_bwd_persist_free        as asr_dec_seq_bwd_persist, E = 128                    1..36
+ *
+ * At 10 channels the 4-row geometry ends at T' = 100 and the 2-row one at T' = 256 in both directions; at 8 or fewer the
+ * 4-row geometry reaches its full T' = 128.  At 12 channels the forward is persistent up to T' = 256 and the backward up
+ * to T' = 212; at 13..16 channels only the backward is persistent (4 rows up to C T'p = 1024, 2 rows up to 2560).  With
+ * V = 37..64 a free-running smooth sequence has a persistent forward and the per-step backward + asr_dec_feedback_bwd. */
 int asr_dec_seq_fwd_persist(const asr_dec_fwd_t* p, void* xch, void* ctrl, asr_stream_t stream);
 /* TESTS ONLY: asr_dec_seq_fwd_persist on the FAULT instantiation of its kernel (see ASR_DEBUG_FAULT): the launch aborts by
- * itself within a millisecond.  cfg-2 widths (512, 512, 512, 128), T' <= 102; ASR_E_SHAPE otherwise. */
+ * itself within a millisecond.  cfg-2 widths (512, 512, 512, 128) in the 4-row geometry (T' <= 128 and C T'p <= 1024:
+ * T' <= 100 at 10 conv channels); ASR_E_SHAPE otherwise. */
 int asr_dec_seq_fwd_persist_fault(const asr_dec_fwd_t* p, void* xch, void* ctrl, asr_stream_t stream);
 /* Free-running variant (greedy / smooth-embedding decode, model.py:334-341; solver.py:230-231,466-470): the embedding
  * input of step s >= 1 is made inside the kernel from the logits of step s-1: mode 1 = emb[argmax], mode 2 =
@@ -450,9 +475,9 @@ int asr_dec_seq_bwd_persist(const asr_dec_bwd_t* p, float* mbuf, void* xch, void
  *   probs [L-1][B][V]  the probabilities the forward saved;  w_out [V][D+O];  emb [V][E]
  *   dlfb  [L][B][V]    out (zero-filled by the caller): gradient reaching logit_s through the feedback; the caller adds
  *                      it to the upstream d(logits) before forming the output-layer weight gradients
- * On return G[s][:, D+O:] holds d(emb_s) (dropout-masked) for every step.  V <= 36, E = 128, the 4-row geometry of
- * asr_dec_seq_bwd_persist (T' <= 100 at 10 conv channels); otherwise ASR_E_SHAPE (per-step kernels +
- * asr_dec_feedback_bwd). */
+ * On return G[s][:, D+O:] holds d(emb_s) (dropout-masked) for every step.  V <= 36, E = 128, both geometries of
+ * asr_dec_seq_bwd_persist (4 rows per group up to T' = 100 at 10 conv channels, 2 rows per group up to T' = 256: the
+ * table at asr_dec_seq_fwd_persist); otherwise ASR_E_SHAPE (per-step kernels + asr_dec_feedback_bwd). */
 typedef struct {
   int V;
   float scaling;

@@ -50,7 +50,8 @@ constexpr int DP_KMAX = 100;        // max conv half width
 constexpr int DP_TAPS4 = 208;       // LDS row length of the filter image (>= 2*KMAX+1 rounded to 4)
 // Geometry of a group (= XCD).  RG utterances per group, each served by PPR = 32 / RG CUs ("parts"): a part owns 16 conv
 // frames, O / PPR context outputs and (like every CU) D/32 cell units and A/32 attention columns of all RG rows.
-//   RG = 4, TPM = 128: a batch of 32 fills the chip (T' <= 102 with 10 conv channels: cfg-2, cfg-1);
+//   RG = 4, TPM = 128: a batch of 32 fills the chip (T' <= 128 and C T'p <= 1024, T'p = T' rounded up to a multiple of 4:
+//                      T' <= 100 with 10 conv channels - cfg-2, cfg-1 - and the full T' <= 128 with 8 or fewer);
 //   RG = 2, TPM = 256: 16 CUs per utterance, so the T'-sized LDS images (P slice, Q slice, conv features) keep their
 //                      size at twice the frames (T' <= 256: cfg-5's T' = 200); 16 utterances per launch.
 // The row axis of the exchange and LDS layouts keeps 4 slots in both geometries (rows >= RG are never published to
@@ -1703,8 +1704,9 @@ int dec_fwd_persist_impl(const asr_dec_fwd_t* p, const asr_dec_feedback_t* f, vo
   if (!cfg1 && !cfg2) return ASR_E_SHAPE;
   const int TpP = (p->Tp + 3) & ~3;
   if (p->Tp <= 0 || p->C <= 0 || p->C > 12 || p->K < 0 || p->K > DP_KMAX) return ASR_E_SHAPE;
-  // geometry: 4 utterances per group while the conv features of 4 rows fit the z / f poll (2 quads per thread: T' <= 102
-  // at 10 channels), else 2 utterances per group on 16 CUs each (T' <= 256), teacher-forced and free-running alike
+  // geometry: 4 utterances per group while the conv features of 4 rows fit the z / f poll (2 quads per thread:
+  // C T'p <= 1024, which is T' <= 100 at 10 channels and T' <= 128 at 8 or fewer), else 2 utterances per group on 16 CUs
+  // each (3 quads per thread: T' <= 256 and C T'p <= 3072), teacher-forced and free-running alike
   using G4 = DecGeo<4, DP_TPM>;
   using G2 = DecGeo<2, 256>;
   const bool geo4 = p->Tp <= G4::TPM && 4 * p->C * (TpP / 4) <= G4::NFQ * DP_NT;
@@ -1763,7 +1765,8 @@ extern "C" int asr_dec_seq_fwd_persist(const asr_dec_fwd_t* p, void* xch, void* 
   return dec_fwd_persist_impl(p, nullptr, xch, ctrl, (hipStream_t)stream_);
 }
 // Test entry: the same launch on the FAULT instantiation of the kernel (csrc/persist.h) - a producer goes silent, the
-// bounded spins expire in a millisecond, the launch aborts by itself.  cfg-2 widths, T' <= 102; ASR_E_SHAPE otherwise.
+// bounded spins expire in a millisecond, the launch aborts by itself.  cfg-2 widths in the 4-row geometry (T' <= 128 and
+// C T'p <= 1024: T' <= 100 at 10 channels); ASR_E_SHAPE otherwise.
 extern "C" int asr_dec_seq_fwd_persist_fault(const asr_dec_fwd_t* p, void* xch, void* ctrl, asr_stream_t stream_) {
   return dec_fwd_persist_impl(p, nullptr, xch, ctrl, (hipStream_t)stream_, true);
 }
@@ -1801,7 +1804,8 @@ static int dec_bwd_persist_impl(const asr_dec_bwd_t* q, const asr_dec_feedback_b
   const int TpP = (p->Tp + 3) & ~3;
   if (p->C <= 0 || p->C > 16 || p->K < 0 || p->K > DP_KMAX) return ASR_E_SHAPE;
   // geometry as in the forward: 4 utterances per group while the per-thread prefetch registers cover the conv features
-  // and M of 4 rows (T' <= 102 at 10 channels), else 2 utterances per group on 16 CUs each (T' <= 256)
+  // and M of 4 rows (C T'p <= 1024: T' <= 100 at 10 channels, T' <= 128 at 8 or fewer), else 2 utterances per group on 16
+  // CUs each (T' <= 256, C T'p <= 2560 and an LDS plan - bwd_lds_plan - of at most 160 KB)
   const bool geo4 = p->Tp <= DP_TPM && p->C * TpP <= 2 * DP_NT && 4 * p->C * TpP <= 8 * DP_NT;
   const bool geo2 = !geo4 && p->Tp <= 256 && p->C * TpP <= 5 * DP_NT && 2 * p->C * TpP <= 10 * DP_NT;
   if (!geo4 && !geo2) return ASR_E_SHAPE;

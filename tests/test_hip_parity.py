@@ -1090,7 +1090,7 @@ def test_decoder_persistent_path(dim, B, Tp, L, drop, K=100):
             hb.USE_PERSIST_DEC, hb.USE_PERSIST_DEC_BWD = old
 
     lr, wr, gr = run(False)
-    # (T' > 102 at 10 conv channels: both persistent kernels run in the 2-utterances-per-group geometry, T' <= 256)
+    # (T' > 100 at 10 conv channels: both persistent kernels run in the 2-utterances-per-group geometry, T' <= 256)
     for mode in ((True, False), (False, True), (True, True)):      # persistent forward / backward / both
         lp, wpp, gp = run(*mode)
         assert not hb.persist_aborted(dev), mode
@@ -1409,7 +1409,7 @@ def test_decoder_feedback_kernels(B, V, E, DO):
                                                   (320, 7, 37, 5, False, "smooth"), (512, 9, 60, 6, True, "mixed"),
                                                   (512, 40, 100, 4, False, "greedy"), (320, 6, 50, 7, True, "smooth"),
                                                   (512, 5, 30, 1, True, "smooth"), (320, 8, 16, 2, False, "greedy"),
-                                                  # T' > 102: the free-running kernel in the 2-rows-per-group geometry
+                                                  # T' > 100: the free-running kernel in the 2-rows-per-group geometry
                                                   (512, 9, 200, 6, False, "greedy"), (512, 12, 130, 5, True, "smooth"),
                                                   (320, 5, 256, 4, False, "smooth"), (512, 19, 200, 3, True, "greedy"),
                                                   (512, 8, 200, 7, True, "smooth"), (512, 21, 200, 4, False, "smooth"),
