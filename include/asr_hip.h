@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define ASR_ABI_VERSION 7
+#define ASR_ABI_VERSION 8
 
 #define ASR_E_ARG    (-1)  /* null pointer / non-positive size */
 #define ASR_E_SHAPE  (-2)  /* size not supported by the kernel (see each function) */
@@ -96,7 +96,7 @@ int asr_abi_version(void);
  * split_k <= 0: the library chooses a K split; split_k == 1: unsplit (no atomics: run-to-run deterministic);
  * split_k > 1 splits K over grid.z and accumulates with fp32 atomics (C is zero-filled on
  * the stream first unless accumulate!=0); with a K split, bias/relu are applied by a second
- * pass over C (not combinable with accumulate).
+ * pass over C (not combinable with accumulate).  batch * split_k is grid.y: ASR_E_SHAPE above 65 535.
  * Replaces torch.nn.Linear / mm / bmm on the path: the LSTM input-gate product inside
  * torch.nn.LSTM (model.py:67-68,80), project_layer (model.py:93-94), mlp_enc
  * (model.py:144), output_layer (model.py:293) and every autograd mm behind them.
@@ -113,6 +113,36 @@ int asr_gemm_drop_f32(int transA, int transB, int64_t M, int64_t N, int64_t K, c
                       const float* B, int64_t ldb, float* C, int64_t ldc, const float* bias, int relu, int split_k,
                       int arith, uint64_t seed, float p, asr_stream_t stream);
 
+/* What asr_gemm_f32 / asr_gemm_drop_f32 decide for a call before they launch anything (csrc/gemm.hip: plan_gemm): the kernel
+ * family and its template choices, the K split as it will run, the grid, and the passes in front of and behind the product.
+ * tests/golden/gemm_plan.json.gz pins it per call. */
+#define ASR_GEMM_FAMILY_F32 0 /* gemm_f32_kernel<AKC, BKC> */
+#define ASR_GEMM_FAMILY_BF3 1 /* gemm_bf3_kernel<AKC, BKC, terms, tile, queue>: 128 x 128 or 64 x 64 tiles */
+#define ASR_GEMM_FAMILY_BFW 2 /* gemm_bf6w_kernel (terms 3) / gemm_bf3w_kernel (terms 2) <AKC, BKC>: 256 x 128, LDS-DMA */
+#define ASR_GEMM_FAMILY_BFS 3 /* gemm_bfs_kernel<AKC, BKC, terms, kt>: 256 x 128, one wave per SIMD */
+#define ASR_GEMM_FAMILY_BFK 4 /* gemm_bfk_kernel<terms, 5, plain>: K = 80, weights stationary */
+#define ASR_GEMM_BEHIND_EPILOGUE 1 /* the pass behind the product applies bias / ReLU (a product split over K) */
+#define ASR_GEMM_BEHIND_DROPOUT  2 /* ... and / or the seeded dropout mask */
+typedef struct {
+  int family;              /* ASR_GEMM_FAMILY_* */
+  int terms;               /* bf16 terms per operand: 3 (ASR_ARITH_BF16X6), 2 (ASR_ARITH_BF16X3), 0 (ASR_ARITH_F32) */
+  int tile;                /* rows of an output tile: 128, 64, or 256 for the 256 x 128 kernels */
+  int akc, bkc;            /* operand layouts: k contiguous (A: !transA, B: transB) */
+  int kt, plain, queue;    /* template choices: masked K tail (BFS), branch-free epilogue (BFK), ticket queue (asr_gemm_side_f32) */
+  int split_k;             /* K slices as they will run */
+  int tiles_m, tiles_n, groups;      /* (groups: workgroups that walk down the M tiles of one column of tiles, BFK) */
+  unsigned grid[3], block;           /* the product's launch, in workgroups / threads */
+  unsigned pass_grid[3];             /* the zero pass and the pass behind (256 threads) */
+  int zero_pass;           /* zero_rows_kernel runs in front of the product */
+  int behind;              /* ASR_GEMM_BEHIND_* carried by bias_act_kernel behind it; 0: no such pass */
+} asr_gemm_plan_t;
+/* Arguments as asr_gemm_f32, without the stream; has_drop: the call is asr_gemm_drop_f32 with p > 0.  Returns what that call
+ * would return before it launches (0, ASR_E_ARG, ASR_E_SHAPE).  The pointers are looked at for NULL and 16-byte alignment
+ * only, never dereferenced: no GPU is needed. */
+int asr_gemm_plan(int transA, int transB, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B,
+                  int64_t ldb, const float* C, int64_t ldc, const float* bias, int relu, int accumulate, int batch,
+                  int64_t sA, int64_t sB, int64_t sC, int split_k, int arith, int has_drop, asr_gemm_plan_t* plan);
+
 /* C[b] += op(A[b]) op(B[b]) on the XCDs of `xcd_mask` only (bit x = XCC id x), by workgroups built to run BESIDE the
  * persistent XCD-local kernels below: a batch of <= 8 utterances keeps the LSTM / decoder recurrences on four of the eight
  * XCDs (group g of a persistent launch = XCC id g; groups without rows leave at once), and the weight-gradient products
@@ -123,7 +153,8 @@ int asr_gemm_drop_f32(int transA, int transB, int64_t M, int64_t N, int64_t K, c
  * K slices are ADDED to C with atomics: C holds zeros for a plain product.  Arguments as asr_gemm_f32 (strides in elements,
  * negative batch strides allowed); arith: ASR_ARITH_BF16X6 / _BF16X3 (ASR_E_SHAPE for ASR_ARITH_F32: the caller runs
  * asr_gemm_f32 instead).  The result does not depend on where the hardware places workgroups (a second, unmasked launch
- * draws whatever tickets the masked one left). */
+ * draws whatever tickets the masked one left).  ASR_E_SHAPE when batch * K slices exceeds 65 535 (grid.y) or the masked
+ * launch would have 2^32 workgroups or more. */
 int asr_gemm_side_f32(int transA, int transB, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
                       const float* B, int64_t ldb, float* C, int64_t ldc, int batch, int64_t sA, int64_t sB, int64_t sC,
                       int arith, unsigned xcd_mask, unsigned* queue, asr_stream_t stream);

@@ -2122,33 +2122,9 @@ static int narrow_split_k(int64_t M, int64_t N, int64_t K, int batch, bool epilo
   return (int)sk;
 }
 
-template <int NT, int TS = 128>
-static void launch_narrow_split(bool akc, bool bkc, dim3 grid, hipStream_t stream, const GemmArgs& g) {
-  const dim3 block(256);
-  if (akc && bkc) hipLaunchKernelGGL((gemm_bf3_kernel<true, true, NT, TS>), grid, block, 0, stream, g);
-  else if (akc && !bkc) hipLaunchKernelGGL((gemm_bf3_kernel<true, false, NT, TS>), grid, block, 0, stream, g);
-  else if (!akc && bkc) hipLaunchKernelGGL((gemm_bf3_kernel<false, true, NT, TS>), grid, block, 0, stream, g);
-  else hipLaunchKernelGGL((gemm_bf3_kernel<false, false, NT, TS>), grid, block, 0, stream, g);
-}
-
-static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
-                     const float* B, int64_t ldb, float* C, int64_t ldc, const float* bias, int relu,
-                     int accumulate, int batch, int64_t sA, int64_t sB, int64_t sC, int split_k, int arith,
-                     DropEpi drop, hipStream_t stream) {
-  if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || batch <= 0) return ASR_E_ARG;
-  if (drop.thresh && (batch != 1 || accumulate)) return ASR_E_ARG;
-  const DropEpi no_drop = {0ull, 0u, 1.f};
-  // the pass behind the product: the late epilogue of a split product and / or the dropout mask
-  auto pass_behind = [&](bool late) {
-    if (!late && !drop.thresh) return;
-    dim3 eg((unsigned)((M * N + 255) / 256 > 2048 ? 2048 : (M * N + 255) / 256), 1, batch);
-    hipLaunchKernelGGL(bias_act_kernel, eg, dim3(256), 0, stream, C, ldc, M, N, sC, late ? bias : nullptr, late ? relu : 0,
-                       drop.thresh ? drop : no_drop);
-  };
-  const int ar = arith & ASR_ARITH_MASK;
-  if (ar != ASR_ARITH_F32 && ar != ASR_ARITH_BF16X6 && ar != ASR_ARITH_BF16X3) return ASR_E_ARG;
-  const bool auto_split = split_k <= 0;           // the kernel chooses; split_k == 1 is honoured as "unsplit" (run-to-run
-                                                  // deterministic: no atomics), split_k > 1 as given on the 128 x 128 kernels
+// The operands of a product as the kernels take them.  Epilogue, K split and tiles are the caller's to fill.
+static GemmArgs make_args(int transA, int transB, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
+                          const float* B, int64_t ldb, float* C, int64_t ldc, int64_t sA, int64_t sB, int64_t sC) {
   GemmArgs g;
   const bool akc = !transA, bkc = transB != 0;
   g.A.p = A; g.A.ld = lda;
@@ -2158,9 +2134,40 @@ static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K, co
   if (bkc) { g.B.R = N; g.B.Cn = K; } else { g.B.R = K; g.B.Cn = N; }
   g.B.vec = (ldb % 4 == 0) && asr_aligned16(B) && (sB % 4 == 0);
   g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
-  g.accumulate = accumulate;
+  g.bias = nullptr; g.relu = 0; g.accumulate = 0; g.split_k = 1; g.tiles_m = g.tiles_n = 0;
   g.sA = sA; g.sB = sB; g.sC = sC;
   g.queue = nullptr; g.xcd_mask = 0xffu;
+  return g;
+}
+
+typedef asr_gemm_plan_t GemmPlan;
+
+// Everything asr_gemm_f32 / asr_gemm_drop_f32 decide, and nothing else: no HIP call, no pointer of `g` dereferenced (its
+// operands, bias / relu / accumulate as the caller gave them).  launch_gemm runs the plan; asr_gemm_plan shows it.
+static int plan_gemm(const GemmArgs& g, bool akc, bool bkc, int batch, int split_k, int arith, bool has_drop, GemmPlan* p) {
+  const int64_t M = g.M, N = g.N, K = g.K, lda = g.A.ld, ldb = g.B.ld, ldc = g.ldc;
+  const float* bias = g.bias;
+  const int relu = g.relu, accumulate = g.accumulate;
+  if (!g.A.p || !g.B.p || !g.C || M <= 0 || N <= 0 || K <= 0 || batch <= 0) return ASR_E_ARG;
+  if (has_drop && (batch != 1 || accumulate)) return ASR_E_ARG;
+  const int ar = arith & ASR_ARITH_MASK;
+  if (ar != ASR_ARITH_F32 && ar != ASR_ARITH_BF16X6 && ar != ASR_ARITH_BF16X3) return ASR_E_ARG;
+  const bool auto_split = split_k <= 0;           // the kernel chooses; split_k == 1 is honoured as "unsplit" (run-to-run
+                                                  // deterministic: no atomics), split_k > 1 as given on the 128 x 128 kernels
+  *p = GemmPlan();
+  p->terms = ar == ASR_ARITH_BF16X6 ? 3 : ar == ASR_ARITH_BF16X3 ? 2 : 0;
+  p->akc = akc; p->bkc = bkc; p->split_k = 1;
+  // what every path ends with: grid (grid.y above 65 535 is refused), zero pass, pass behind (late: bias / ReLU of a split product)
+  auto finish = [&](bool late) {
+    if ((int64_t)batch * p->split_k > 65535) return ASR_E_SHAPE;
+    p->grid[0] = (unsigned)(p->family == ASR_GEMM_FAMILY_BFK ? p->tiles_n * p->groups : p->tiles_m * p->tiles_n);
+    p->grid[1] = (unsigned)(batch * p->split_k); p->grid[2] = 1;
+    p->zero_pass = p->split_k > 1 && !accumulate && !(arith & ASR_GEMM_C_ZEROED);
+    p->behind = (late ? ASR_GEMM_BEHIND_EPILOGUE : 0) | (has_drop ? ASR_GEMM_BEHIND_DROPOUT : 0);
+    p->pass_grid[0] = (unsigned)((M * N + 255) / 256 > 2048 ? 2048 : (M * N + 255) / 256);
+    p->pass_grid[1] = 1; p->pass_grid[2] = (unsigned)batch;
+    return 0;
+  };
   const bool epi = bias || relu;
   // Wide-tile LDS-DMA kernels (gemm_bf3w_kernel / gemm_bf6w_kernel) for conforming shapes: any M, N (edge tiles clamp their
   // DMA rows / columns and guard the stores); K % 32 == 0; row-contiguous operands need a multiple of 4 rows; per-lane
@@ -2182,19 +2189,10 @@ static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K, co
     const int tiles_n = (int)((N + 127) / 128);
     if (tiles_n <= 256) {
       const int groups = 8 * (tiles_n >= 32 ? 1 : 32 / tiles_n);
-      g.bias = bias; g.relu = relu; g.split_k = 1;
-      dim3 grid(tiles_n * groups, batch, 1), b4(512);
       const bool plain = M % 128 == 0 && N % 128 == 0 && !relu && !accumulate && M * ldc < ((int64_t)1 << 29);
-      if (ar == ASR_ARITH_BF16X6) {
-        if (plain) hipLaunchKernelGGL((gemm_bfk_kernel<3, 5, true>), grid, b4, 0, stream, g, groups);
-        else hipLaunchKernelGGL((gemm_bfk_kernel<3, 5, false>), grid, b4, 0, stream, g, groups);
-      } else {
-        if (plain) hipLaunchKernelGGL((gemm_bfk_kernel<2, 5, true>), grid, b4, 0, stream, g, groups);
-        else hipLaunchKernelGGL((gemm_bfk_kernel<2, 5, false>), grid, b4, 0, stream, g, groups);
-      }
-      pass_behind(false);
-      ASR_CHECK_LAUNCH();
-      return 0;
+      p->family = ASR_GEMM_FAMILY_BFK; p->tile = 128; p->block = 512; p->plain = plain;
+      p->tiles_m = (int)((M + 127) / 128); p->tiles_n = tiles_n; p->groups = groups;
+      return finish(false);
     }
   }
   // Products too small to fill the chip with 128 x 128 tiles take 64 x 64 tiles (gemm_bf3_kernel<..., 64>): at most
@@ -2243,70 +2241,98 @@ static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K, co
     static const int forced_sk = [] { const char* f = getenv("ASR_GEMM_WIDE_SK"); return f ? atoi(f) : 0; }();   // measurement
     if (forced_sk >= 1 && forced_sk <= stages && may_split) best = forced_sk;
     const bool late_epi = best > 1 && epi;
-    g.bias = late_epi ? nullptr : bias; g.relu = late_epi ? 0 : relu;
-    g.split_k = best;
-    g.tiles_m = (int)((M + WM - 1) / WM);
-    g.tiles_n = (int)((N + WN - 1) / WN);
-    if (best > 1 && !accumulate && !(arith & ASR_GEMM_C_ZEROED)) {
-      dim3 zg((unsigned)((M * N + 255) / 256 > 2048 ? 2048 : (M * N + 255) / 256), 1, batch);
-      hipLaunchKernelGGL(zero_rows_kernel, zg, dim3(256), 0, stream, C, ldc, M, N, sC);
-    }
-    dim3 grid(g.tiles_m * g.tiles_n, batch * best, 1), block(512);
-    if (use_sp) {
-      const dim3 b4(256);
-#define SP_LAUNCH(nt_, kt_)                                                                                             \
-      do {                                                                                                              \
-        if (akc && bkc) hipLaunchKernelGGL((gemm_bfs_kernel<true, true, nt_, kt_>), grid, b4, 0, stream, g);            \
-        else if (akc && !bkc) hipLaunchKernelGGL((gemm_bfs_kernel<true, false, nt_, kt_>), grid, b4, 0, stream, g);     \
-        else if (!akc && bkc) hipLaunchKernelGGL((gemm_bfs_kernel<false, true, nt_, kt_>), grid, b4, 0, stream, g);     \
-        else hipLaunchKernelGGL((gemm_bfs_kernel<false, false, nt_, kt_>), grid, b4, 0, stream, g);                     \
-      } while (0)
-      if (ar == ASR_ARITH_BF16X6) { if (K % WK) SP_LAUNCH(3, true); else SP_LAUNCH(3, false); }
-      else { if (K % WK) SP_LAUNCH(2, true); else SP_LAUNCH(2, false); }
-#undef SP_LAUNCH
-    } else if (ar == ASR_ARITH_BF16X6) {
-      if (akc && bkc) hipLaunchKernelGGL((gemm_bf6w_kernel<true, true>), grid, block, 0, stream, g);
-      else if (akc && !bkc) hipLaunchKernelGGL((gemm_bf6w_kernel<true, false>), grid, block, 0, stream, g);
-      else if (!akc && bkc) hipLaunchKernelGGL((gemm_bf6w_kernel<false, true>), grid, block, 0, stream, g);
-      else hipLaunchKernelGGL((gemm_bf6w_kernel<false, false>), grid, block, 0, stream, g);
-    } else {
-      if (akc && bkc) hipLaunchKernelGGL((gemm_bf3w_kernel<true, true>), grid, block, 0, stream, g);
-      else if (akc && !bkc) hipLaunchKernelGGL((gemm_bf3w_kernel<true, false>), grid, block, 0, stream, g);
-      else if (!akc && bkc) hipLaunchKernelGGL((gemm_bf3w_kernel<false, true>), grid, block, 0, stream, g);
-      else hipLaunchKernelGGL((gemm_bf3w_kernel<false, false>), grid, block, 0, stream, g);
-    }
-    pass_behind(late_epi);
-    ASR_CHECK_LAUNCH();
-    return 0;
+    p->family = use_sp ? ASR_GEMM_FAMILY_BFS : ASR_GEMM_FAMILY_BFW; p->tile = WM; p->block = use_sp ? 256 : 512;
+    p->kt = use_sp && K % WK != 0;
+    p->split_k = best;
+    p->tiles_m = (int)((M + WM - 1) / WM);
+    p->tiles_n = (int)((N + WN - 1) / WN);
+    return finish(late_epi);
   }
   const int ts = small ? 64 : 128;
   if (auto_split) split_k = (epi && accumulate) ? 1 : narrow_split_k(M, N, K, batch, epi, ts);
   // split-K with an epilogue: the product is formed without it (atomics) and a second pass applies bias / ReLU
   const bool late_epilogue = split_k > 1 && epi;
   if (late_epilogue && accumulate) return ASR_E_SHAPE;
-  g.bias = late_epilogue ? nullptr : bias;
-  g.relu = late_epilogue ? 0 : relu;
-  g.tiles_m = (int)((M + ts - 1) / ts);
-  g.tiles_n = (int)((N + ts - 1) / ts);
+  p->family = ar == ASR_ARITH_F32 ? ASR_GEMM_FAMILY_F32 : ASR_GEMM_FAMILY_BF3; p->tile = ts; p->block = 256;
+  p->tiles_m = (int)((M + ts - 1) / ts);
+  p->tiles_n = (int)((N + ts - 1) / ts);
   const int64_t ktiles = (K + BK - 1) / BK;
   if (split_k > ktiles) split_k = (int)ktiles;
-  g.split_k = split_k;
-  if (split_k > 1 && !accumulate && !(arith & ASR_GEMM_C_ZEROED)) {
-    dim3 zg((unsigned)((M * N + 255) / 256 > 2048 ? 2048 : (M * N + 255) / 256), 1, batch);
-    hipLaunchKernelGGL(zero_rows_kernel, zg, dim3(256), 0, stream, C, ldc, M, N, sC);
+  p->split_k = split_k;
+  return finish(late_epilogue);
+}
+
+// The product kernel a plan names, on `grid` (asr_gemm_side_f32 launches one plan on two grids).  GEMM_LAUNCH is the one
+// place the operand layouts pick a template instance: they are the first two arguments of every kernel but gemm_bfk_kernel.
+static void launch_product(const GemmPlan& p, const GemmArgs& g, dim3 grid, hipStream_t stream) {
+#define GEMM_LAUNCH(kernel_, ...)                                                                                          \
+  do {                                                                                                                     \
+    if (p.akc && p.bkc) hipLaunchKernelGGL((kernel_<true, true, ##__VA_ARGS__>), grid, block, 0, stream, g);               \
+    else if (p.akc && !p.bkc) hipLaunchKernelGGL((kernel_<true, false, ##__VA_ARGS__>), grid, block, 0, stream, g);        \
+    else if (!p.akc && p.bkc) hipLaunchKernelGGL((kernel_<false, true, ##__VA_ARGS__>), grid, block, 0, stream, g);        \
+    else hipLaunchKernelGGL((kernel_<false, false, ##__VA_ARGS__>), grid, block, 0, stream, g);                            \
+  } while (0)
+  const dim3 block(p.block);
+  const bool t3 = p.terms == 3;
+  if (p.family == ASR_GEMM_FAMILY_BFK) {
+    if (t3 && p.plain) hipLaunchKernelGGL((gemm_bfk_kernel<3, 5, true>), grid, block, 0, stream, g, p.groups);
+    else if (t3) hipLaunchKernelGGL((gemm_bfk_kernel<3, 5, false>), grid, block, 0, stream, g, p.groups);
+    else if (p.plain) hipLaunchKernelGGL((gemm_bfk_kernel<2, 5, true>), grid, block, 0, stream, g, p.groups);
+    else hipLaunchKernelGGL((gemm_bfk_kernel<2, 5, false>), grid, block, 0, stream, g, p.groups);
+  } else if (p.family == ASR_GEMM_FAMILY_BFS) {
+    if (t3 && p.kt) GEMM_LAUNCH(gemm_bfs_kernel, 3, true);
+    else if (t3) GEMM_LAUNCH(gemm_bfs_kernel, 3, false);
+    else if (p.kt) GEMM_LAUNCH(gemm_bfs_kernel, 2, true);
+    else GEMM_LAUNCH(gemm_bfs_kernel, 2, false);
+  } else if (p.family == ASR_GEMM_FAMILY_BFW) {
+    if (t3) GEMM_LAUNCH(gemm_bf6w_kernel); else GEMM_LAUNCH(gemm_bf3w_kernel);
+  } else if (p.family == ASR_GEMM_FAMILY_BF3 && !p.queue) {
+    if (t3 && p.tile == 64) GEMM_LAUNCH(gemm_bf3_kernel, 3, 64);
+    else if (p.tile == 64) GEMM_LAUNCH(gemm_bf3_kernel, 2, 64);
+    else if (t3) GEMM_LAUNCH(gemm_bf3_kernel, 3);
+    else GEMM_LAUNCH(gemm_bf3_kernel, 2);
+  } else if (p.family == ASR_GEMM_FAMILY_F32) {
+    GEMM_LAUNCH(gemm_f32_kernel);
+  } else {
+    if (t3) GEMM_LAUNCH(gemm_bf3_kernel, 3, 64, true); else GEMM_LAUNCH(gemm_bf3_kernel, 2, 64, true);
   }
-  dim3 grid(g.tiles_m * g.tiles_n, batch * split_k, 1), block(256);
-  if (ar == ASR_ARITH_BF16X6 && small) launch_narrow_split<3, 64>(akc, bkc, grid, stream, g);
-  else if (ar == ASR_ARITH_BF16X3 && small) launch_narrow_split<2, 64>(akc, bkc, grid, stream, g);
-  else if (ar == ASR_ARITH_BF16X6) launch_narrow_split<3>(akc, bkc, grid, stream, g);
-  else if (ar == ASR_ARITH_BF16X3) launch_narrow_split<2>(akc, bkc, grid, stream, g);
-  else if (akc && bkc) hipLaunchKernelGGL((gemm_f32_kernel<true, true>), grid, block, 0, stream, g);
-  else if (akc && !bkc) hipLaunchKernelGGL((gemm_f32_kernel<true, false>), grid, block, 0, stream, g);
-  else if (!akc && bkc) hipLaunchKernelGGL((gemm_f32_kernel<false, true>), grid, block, 0, stream, g);
-  else hipLaunchKernelGGL((gemm_f32_kernel<false, false>), grid, block, 0, stream, g);
-  pass_behind(late_epilogue);
+#undef GEMM_LAUNCH
+}
+
+// zero pass (a split product that does not accumulate adds its slices to zeros), product, the pass behind it
+static int launch_gemm(const GemmPlan& p, GemmArgs g, const DropEpi& drop, hipStream_t stream) {
+  const bool late = (p.behind & ASR_GEMM_BEHIND_EPILOGUE) != 0;
+  const float* late_bias = late ? g.bias : nullptr;
+  const int late_relu = late ? g.relu : 0;
+  if (late) { g.bias = nullptr; g.relu = 0; }
+  g.split_k = p.split_k; g.tiles_m = p.tiles_m; g.tiles_n = p.tiles_n;
+  const dim3 pass(p.pass_grid[0], p.pass_grid[1], p.pass_grid[2]);
+  if (p.zero_pass) hipLaunchKernelGGL(zero_rows_kernel, pass, dim3(256), 0, stream, g.C, g.ldc, g.M, g.N, g.sC);
+  launch_product(p, g, dim3(p.grid[0], p.grid[1], p.grid[2]), stream);
+  if (p.behind) hipLaunchKernelGGL(bias_act_kernel, pass, dim3(256), 0, stream, g.C, g.ldc, g.M, g.N, g.sC, late_bias, late_relu, drop);
   ASR_CHECK_LAUNCH();
   return 0;
+}
+
+static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
+                     const float* B, int64_t ldb, float* C, int64_t ldc, const float* bias, int relu,
+                     int accumulate, int batch, int64_t sA, int64_t sB, int64_t sC, int split_k, int arith,
+                     DropEpi drop, hipStream_t stream) {
+  GemmArgs g = make_args(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, sA, sB, sC);
+  g.bias = bias; g.relu = relu; g.accumulate = accumulate;
+  GemmPlan p;
+  const int rc = plan_gemm(g, !transA, transB != 0, batch, split_k, arith, drop.thresh != 0, &p);
+  return rc ? rc : launch_gemm(p, g, drop, stream);
+}
+
+extern "C" int asr_gemm_plan(int transA, int transB, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
+                             const float* B, int64_t ldb, const float* C, int64_t ldc, const float* bias, int relu,
+                             int accumulate, int batch, int64_t sA, int64_t sB, int64_t sC, int split_k, int arith,
+                             int has_drop, asr_gemm_plan_t* plan) {
+  if (!plan) return ASR_E_ARG;
+  GemmArgs g = make_args(transA, transB, M, N, K, A, lda, B, ldb, const_cast<float*>(C), ldc, sA, sB, sC);
+  g.bias = bias; g.relu = relu; g.accumulate = accumulate;
+  return plan_gemm(g, !transA, transB != 0, batch, split_k, arith, has_drop != 0, plan);
 }
 
 extern "C" int asr_gemm_f32(int transA, int transB, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
@@ -2338,24 +2364,13 @@ extern "C" int asr_gemm_drop_f32(int transA, int transB, int64_t M, int64_t N, i
 // are left - none, when workgroups are dealt round robin over the XCDs; the result does not depend on that.
 extern "C" int asr_gemm_side_f32(int transA, int transB, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
                                  const float* B, int64_t ldb, float* C, int64_t ldc, int batch, int64_t sA, int64_t sB,
-                                 int64_t sC, int arith, unsigned xcd_mask, unsigned* queue, asr_stream_t stream_) {
+                                 int64_t sC, int arith, unsigned xcd_mask, unsigned* queue, asr_stream_t stream) {
   if (!A || !B || !C || !queue || M <= 0 || N <= 0 || K <= 0 || batch <= 0 || !(xcd_mask & 0xffu)) return ASR_E_ARG;
   const int ar = arith & ASR_ARITH_MASK;
   if (ar != ASR_ARITH_BF16X6 && ar != ASR_ARITH_BF16X3) return ASR_E_SHAPE;      // (the fp32-input MFMA kernel has no such form)
-  hipStream_t stream = (hipStream_t)stream_;
-  GemmArgs g;
-  const bool akc = !transA, bkc = transB != 0;
-  g.A.p = A; g.A.ld = lda;
-  if (akc) { g.A.R = M; g.A.Cn = K; } else { g.A.R = K; g.A.Cn = M; }
-  g.A.vec = (lda % 4 == 0) && asr_aligned16(A) && (sA % 4 == 0);
-  g.B.p = B; g.B.ld = ldb;
-  if (bkc) { g.B.R = N; g.B.Cn = K; } else { g.B.R = K; g.B.Cn = N; }
-  g.B.vec = (ldb % 4 == 0) && asr_aligned16(B) && (sB % 4 == 0);
-  g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
-  g.bias = nullptr; g.relu = 0; g.accumulate = 1;
-  g.sA = sA; g.sB = sB; g.sC = sC;
-  g.tiles_m = (int)((M + 63) / 64);
-  g.tiles_n = (int)((N + 63) / 64);
+  GemmArgs g = make_args(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, sA, sB, sC);
+  g.accumulate = 1;
+  g.tiles_m = (int)((M + 63) / 64); g.tiles_n = (int)((N + 63) / 64);
   g.queue = queue; g.xcd_mask = xcd_mask & 0xffu;
   const int nx = __builtin_popcount(g.xcd_mask);
   // K slices: about four tickets per CU of the allowed XCDs (a workgroup is 1 of up to 4 on its CU), at least 8 K tiles each
@@ -2365,27 +2380,17 @@ extern "C" int asr_gemm_side_f32(int transA, int transB, int64_t M, int64_t N, i
   if (sk < 1) sk = 1;
   if (sk > 64) sk = 64;
   g.split_k = (int)sk;
-  const int64_t tickets = (int64_t)g.tiles_m * g.tiles_n * batch * sk;
-  if (tickets > 0x3fffffff) return ASR_E_SHAPE;
-  const unsigned gy = (unsigned)(batch * sk);
+  const int64_t tickets = tiles * sk, gy = batch * sk;
   const int64_t per_y = (int64_t)g.tiles_m * g.tiles_n;                 // tickets per unit of grid.y
-  const unsigned gx = (unsigned)((per_y * 8 + nx - 1) / nx + 8);      // x extent oversubscribed: 1 in 8 / nx workgroups survives
-  auto launch = [&](dim3 grid) {
-    const dim3 block(256);
-#define SIDE_LAUNCH(nt_)                                                                                                     \
-    do {                                                                                                                     \
-      if (akc && bkc) hipLaunchKernelGGL((gemm_bf3_kernel<true, true, nt_, 64, true>), grid, block, 0, stream, g);           \
-      else if (akc && !bkc) hipLaunchKernelGGL((gemm_bf3_kernel<true, false, nt_, 64, true>), grid, block, 0, stream, g);    \
-      else if (!akc && bkc) hipLaunchKernelGGL((gemm_bf3_kernel<false, true, nt_, 64, true>), grid, block, 0, stream, g);    \
-      else hipLaunchKernelGGL((gemm_bf3_kernel<false, false, nt_, 64, true>), grid, block, 0, stream, g);                    \
-    } while (0)
-    if (ar == ASR_ARITH_BF16X6) SIDE_LAUNCH(3); else SIDE_LAUNCH(2);
-#undef SIDE_LAUNCH
-  };
-  launch(dim3(gx, gy, 1));
+  const int64_t gx = (per_y * 8 + nx - 1) / nx + 8;                     // x extent oversubscribed: 1 in 8 / nx workgroups survives
+  // (grid.y; and the kernel numbers its workgroups x + gridDim.x y in 32 bits)
+  if (tickets > 0x3fffffff || gy > 65535 || gx * gy > 0xffffffffll) return ASR_E_SHAPE;
+  GemmPlan p = GemmPlan();
+  p.family = ASR_GEMM_FAMILY_BF3; p.terms = ar == ASR_ARITH_BF16X6 ? 3 : 2; p.tile = 64; p.queue = 1; p.block = 256; p.akc = !transA; p.bkc = transB != 0;
+  launch_product(p, g, dim3((unsigned)gx, (unsigned)gy, 1), (hipStream_t)stream);
   // the sweep: every XCD, one workgroup per ticket that could be left at most - all of them leave at once in the expected case
   g.xcd_mask = 0xffu;
-  launch(dim3((unsigned)per_y, gy, 1));
+  launch_product(p, g, dim3((unsigned)per_y, (unsigned)gy, 1), (hipStream_t)stream);
   ASR_CHECK_LAUNCH();
   return 0;
 }

@@ -11,10 +11,10 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libasr_hip.so")
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 EXPORTS = (
-    "asr_abi_version", "asr_persist_scratch_bytes", "asr_gemm_f32", "asr_gemm_skinny_f32", "asr_colsum_f32",
+    "asr_abi_version", "asr_persist_scratch_bytes", "asr_gemm_f32", "asr_gemm_plan", "asr_gemm_skinny_f32", "asr_colsum_f32",
     "asr_lstm_seq_fwd", "asr_lstm_seq_fwd_persist", "asr_lstm_seq_bwd", "asr_lstm_seq_bwd_persist", "asr_lstm_seq_bwd_persist_w", "asr_lstm_bwd_persist_fuses_dw", "asr_pyramid_concat_fwd", "asr_pyramid_concat_bwd",
     "asr_pyramid_concat_fwd_seeded", "asr_pyramid_concat_bwd_seeded", "asr_rows_pack_f32", "asr_rows_unpack_fwd_f32", "asr_rows_unpack_bwd_f32", "asr_dropout_seeded_f32", "asr_relu_dropout_bwd_f32",
     "asr_dropout_mask_f32",
@@ -91,6 +91,13 @@ class BeamLmState(ctypes.Structure):
     """asr_beam_lm_state_t"""
     _fields_ = [("n_layers", c_i), ("H", c_i), ("in_dim", c_i * LM_MAX_LAYERS)] + \
                [(n, c_p * LM_MAX_LAYERS) for n in ("x_src", "x_dst", "c_src", "c_dst")] + [("emb", c_p)]
+
+
+class GemmPlan(ctypes.Structure):
+    """asr_gemm_plan_t"""
+    _fields_ = [(n, c_i) for n in ("family", "terms", "tile", "akc", "bkc", "kt", "plain", "queue", "split_k", "tiles_m", "tiles_n",
+                                   "groups")] + \
+               [("grid", ctypes.c_uint * 3), ("block", ctypes.c_uint), ("pass_grid", ctypes.c_uint * 3), ("zero_pass", c_i), ("behind", c_i)]
 
 
 class DecBwd(ctypes.Structure):
@@ -196,6 +203,7 @@ def load():
     lib.asr_persist_scratch_bytes.argtypes = [ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]
     lib.asr_gemm_f32.argtypes = [c_i, c_i, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i, c_i,
                                  c_i, c_i64, c_i64, c_i64, c_i, c_i, c_p]
+    lib.asr_gemm_plan.argtypes = lib.asr_gemm_f32.argtypes[:-1] + [c_i, ctypes.POINTER(GemmPlan)]
     lib.asr_gemm_skinny_f32.argtypes = [c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i, c_p,
                                         c_i64, c_i64, c_p]
     lib.asr_colsum_f32.argtypes = [c_i64, c_i64, c_p, c_i64, c_p, c_i, c_p]
@@ -391,6 +399,38 @@ def gemm_batched(A, B, out, trans_a, trans_b, M, N, K, lda, ldb, ldc, batch, sA,
                               None, 0, int(accumulate), batch, sA, sB, sC, 0 if split_k is None else int(split_k),
                               ARITH[0] if arith is None else _arith_code(arith), stream()), "asr_gemm_f32(batched)")
     return out
+
+
+GEMM_FAMILIES = ("f32", "bf3", "bfw", "bfs", "bfk")          # ASR_GEMM_FAMILY_*
+
+
+def gemm_plan(M, N, K, trans_a=False, trans_b=False, lda=None, ldb=None, ldc=None, batch=1, sA=0, sB=0, sC=0, bias=False,
+              relu=False, accumulate=False, drop=False, split_k=None, arith=None, misaligned=0):
+    """What gemm() / gemm_batched() would launch for these sizes (asr_gemm_plan; plain integers, no tensors, no GPU): the
+    fields of asr_gemm_plan_t, `rc` (the code the call would return before launching; the other fields are missing when
+    it is not 0), `kernel` (the product kernel in the short form of tools/isa_guard.py) and `launches` (every launch in
+    order as (kernel, grid in workgroups, threads per workgroup): zero pass, product, pass behind).
+    Leading dimensions default to dense, pointers to 16-byte aligned (misaligned: bit 0 / 1 / 2 = A / B / C is not)."""
+    lda, ldb, ldc = lda or (M if trans_a else K), ldb or (K if trans_b else N), ldc or N
+    code = ARITH[0] if arith is None else _arith_code(arith)
+    p = GemmPlan()
+    rc = load().asr_gemm_plan(int(trans_a), int(trans_b), M, N, K, 64 + 4 * (misaligned & 1), lda, 64 + 4 * (misaligned >> 1 & 1), ldb,
+                              64 + 4 * (misaligned >> 2 & 1), ldc, 64 if bias else None, int(relu), int(accumulate), batch, sA, sB, sC,
+                              0 if split_k is None else int(split_k), code, int(drop), ctypes.byref(p))
+    if rc != 0:
+        return dict(rc=rc, launches=[])
+    d = {n: (list(v) if hasattr(v, "__len__") else v) for n, v in ((f[0], getattr(p, f[0])) for f in GemmPlan._fields_)}
+    tf = lambda *v: ",".join(("true" if x else "false") if isinstance(x, bool) else str(x) for x in v)
+    lay = (bool(p.akc), bool(p.bkc))
+    d["family"] = fam = GEMM_FAMILIES[p.family]
+    d["kernel"] = {"f32": "gemm_f32_kernel<%s>" % tf(*lay), "bf3": "gemm_bf3_kernel<%s>" % tf(*lay, p.terms, p.tile, bool(p.queue)),
+                   "bfw": "gemm_bf%dw_kernel<%s>" % (6 if p.terms == 3 else 3, tf(*lay)),
+                   "bfs": "gemm_bfs_kernel<%s>" % tf(*lay, p.terms, bool(p.kt)), "bfk": "gemm_bfk_kernel<%s>" % tf(p.terms, 5, bool(p.plain))}[fam]
+    d["behind"] = [s for b, s in ((1, "epilogue"), (2, "dropout")) if p.behind & b]
+    d["launches"] = ([("zero_rows_kernel", d["pass_grid"], 256)] if p.zero_pass else []) + [(d["kernel"], d["grid"], p.block)] + \
+                    ([("bias_act_kernel", d["pass_grid"], 256)] if p.behind else [])
+    d["rc"] = 0
+    return d
 
 
 def gemm_side(A, B, out, queue, xcd_mask, trans_a=False, trans_b=False, arith=None):

@@ -108,6 +108,6 @@ def test_beam_exports_and_abi_version():
     for name in ("asr_beam_select_f32", "asr_beam_reorder_f32", "asr_beam_backtrack"):
         assert re.search(r"^int\s+%s\s*\(" % name, header, flags=re.M), name
         assert name in hb.EXPORTS and hasattr(lib, name), name
-    assert lib.asr_abi_version() == 7 == hb.ABI_VERSION
+    assert lib.asr_abi_version() == 8 == hb.ABI_VERSION
     assert "#define ASR_BEAM_KMAX 16" in header and "#define ASR_BEAM_FCAP 48" in header
     assert (hb.BEAM_KMAX, hb.BEAM_FCAP) == (16, 48)

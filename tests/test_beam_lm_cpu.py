@@ -122,7 +122,7 @@ def test_lm_exports_and_abi_version():
     for name in ("asr_lm_step_f32", "asr_beam_select_lm_f32", "asr_beam_reorder_lm_f32"):
         assert re.search(r"^int\s+%s\s*\(" % name, header, flags=re.M), name
         assert name in hb.EXPORTS and hasattr(lib, name), name
-    assert lib.asr_abi_version() == 7 == hb.ABI_VERSION
+    assert lib.asr_abi_version() == 8 == hb.ABI_VERSION
     assert "additive" in header
     assert "#define ASR_LM_MAX_LAYERS 4" in header and "#define ASR_LM_MAX_ROWS 512" in header
     assert (hb.LM_MAX_LAYERS, hb.LM_MAX_ROWS) == (4, 512)

@@ -1,6 +1,7 @@
-"""Every asr_gemm_f32 call of one cfg-2 train step (shape, layout, epilogue, whether the 256 x 128 LDS-DMA kernel takes
-it), each timed on its own with cold operands, sorted by time: where the GEMM time of the step goes."""
-import os, sys, collections, ctypes
+"""Every asr_gemm_f32 call of one cfg-2 train step (shape, layout, epilogue, the kernel the library plans for it), each
+timed on its own with cold operands, sorted by time: where the GEMM time of the step goes.  GS_RECORD=FILE: write the
+step's calls, in order and with strides, arithmetic and pointer alignment, as JSON and stop (tools/gemm_plan_trace.py)."""
+import os, sys, collections, ctypes, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, ROOT + '/semi-supervised-asr_amd', ROOT + '/tests/golden']
 import numpy as np, torch
@@ -26,15 +27,19 @@ for _ in range(2): step()
 torch.cuda.synchronize()
 lib = hb.load()
 real = lib.asr_gemm_f32
-calls = []
+calls, full = [], []
 class Spy(object):
     def __call__(self, ta, tb, M_, N, K, A, lda, B, ldb, C, ldc, bias, relu, acc, batch, sA, sB, sC, sk, ar, st):
         v = lambda x: int(getattr(x, 'value', x) or 0)
         calls.append((int(ta), int(tb), int(M_), int(N), int(K), int(batch), v(bias) != 0, int(relu), int(acc), int(sk), int(lda), int(ldb), int(ldc)))
+        full.append((int(ta), int(tb), int(M_), int(N), int(K), int(lda), int(ldb), int(ldc), int(batch), int(sA), int(sB), int(sC), int(v(bias) != 0),
+                     int(relu), int(acc), int(sk), int(ar), sum(1 << i for i, p in enumerate((A, B, C)) if v(p) % 16)))
         return real(ta, tb, M_, N, K, A, lda, B, ldb, C, ldc, bias, relu, acc, batch, sA, sB, sC, sk, ar, st)
 lib.asr_gemm_f32 = Spy()
 step(); torch.cuda.synchronize()
 lib.asr_gemm_f32 = real
+if os.environ.get('GS_RECORD'):
+    json.dump(full, open(os.environ['GS_RECORD'], 'w')); sys.exit(0)
 flush = torch.empty(256 * 1024 * 1024, device=dev)
 agg = collections.OrderedDict()
 for c in calls: agg[c] = agg.get(c, 0) + 1
@@ -55,10 +60,10 @@ for (ta, tb, M_, N, K, batch, bias, relu, acc, sk, lda, ldb, ldc), n in agg.item
             e0.record(); hb.gemm(Av, Bv, trans_a=bool(ta), trans_b=bool(tb), bias=bv, relu=bool(relu), out=out[:, :N], accumulate=bool(acc), split_k=sk, arith=mode); e1.record(); torch.cuda.synchronize()
             ts.append(e0.elapsed_time(e1) * 1e3)
         res.append(sorted(ts)[1])
-    wide = M_ % 256 == 0 and N % 128 == 0 and K % 32 == 0
-    rows.append((res[0] * n, '%s%s M%6d N%5d K%6d sk%2d %s%s%s x%d: %6.0f us policy / %6.0f narrow / %6.0f wide / %6.0f sp each  (%5.1f TF)%s' % (
+    plan = hb.gemm_plan(M_, N, K, bool(ta), bool(tb), lda=lda, ldb=ldb, ldc=ldc, bias=bias, relu=bool(relu), accumulate=bool(acc), split_k=sk, arith=base)
+    rows.append((res[0] * n, '%s%s M%6d N%5d K%6d sk%2d %s%s%s x%d: %6.0f us policy / %6.0f narrow / %6.0f wide / %6.0f sp each  (%5.1f TF)  %s' % (
         'T' if ta else 'N', 'T' if tb else 'N', M_, N, K, sk, 'b' if bias else '-', 'r' if relu else '-', 'a' if acc else '-', n, res[0], res[1], res[2], res[3],
-        2.0 * M_ * N * K / res[0] / 1e6, '  [conforms]' if wide else '')))
+        2.0 * M_ * N * K / res[0] / 1e6, plan['kernel'])))
 tot = sum(r[0] for r in rows)
 for t, s in sorted(rows, key=lambda r: -r[0]): print(s)
 print('sum over the step with the wide kernel enabled: %.0f us' % tot)
