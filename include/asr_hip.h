@@ -254,9 +254,10 @@ int asr_lstm_seq_bwd(int T, int B, int nb, int H, int ndir, float* gates, const 
  * H = 320 (10 units per CU in 12 slots) / H = 640 (20 units per CU, its own kernel) under ASR_ARITH_BF16X6 - the CUs of a
  * group exchange partial sums of dh_rec, laid out [8 groups][2][32 dest][32 src]
  * [8 rows][slots per CU] floats in xch (8 MB at H = 512); otherwise (H = 320 with two terms, ASR_ARITH_F32,
- * ASR_LSTM_BWD_GATHER) every CU gathers the step's dG tile.  Exchanged words carry a 1-bit tag in the
+ * ASR_LSTM_BWD_GATHER) every CU gathers the step's dG tile: one kernel, lstm_persist_bwd_kernel, whose product dG W_hh
+ * takes fp32 operands or operands split in two / three bf16 terms.  Exchanged words carry a 1-bit tag in the
  * mantissa LSB; the in-place dG is what the pointwise update produced.  `arith` selects the product arithmetic of
- * dG W_hh and of the fused dW_hh (the gathered-dG kernels always form dW_hh on the fp32 MFMA).
+ * dG W_hh and of the fused dW_hh (the gathered-dG kernel always forms dW_hh on the fp32 MFMA).
  * If y (forward hidden states) and dw_hh ([ndir][4H][H], gate-interleaved, zero-filled or holding a running sum)
  * are given, the recurrent weight gradient sum_t dG_t^T h_{t-1} is accumulated into dw_hh inside the kernel
  * (fp32 atomics across the row groups) and the caller skips that GEMM.  If db ([ndir][4H], gate-interleaved,

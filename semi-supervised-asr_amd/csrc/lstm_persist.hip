@@ -20,6 +20,7 @@
 // placement the kernel raises an abort word, poisons its outputs with NaN and drains — the host falls back to
 // the per-step kernels.  1 workgroup per CU is enforced by the LDS request, so 256 workgroups are co-resident.
 #include <cstdlib>
+#include <type_traits>
 #include "persist.h"
 #ifndef ASR_LP_ABL
 #define ASR_LP_ABL 0
@@ -813,30 +814,51 @@ __global__ __launch_bounds__(PNT) void lstm_persist_fwd_bf3_kernel(PersistArgs a
 }
 
 // --------------------------------------------------------------------------------------------------- backward
-// dh_rec = dG_{t_next} W_hh for this CU's 16 units, then the pointwise LSTM backward at time t (dG_t written in
-// place over the saved gates AND published to the group).  The exchange here is 4x larger than in the forward
-// (8 rows x 4H), so it uses bare fp32 words whose mantissa LSB is the validity tag: a slot is rewritten every
-// second step and the expected bit flips with every rewrite (the buffer starts zeroed = invalid), so a consumer
-// can tell new from stale per word; tearing between words is harmless.  Cost: <= 1 ulp on the exchanged copy
-// (the in-place dG used by the weight-gradient GEMMs is untouched).  Float4 traffic both ways.
-// MFMA blocks: 16 = 4 unit-groups x 4 k-subs; A[blk][i] = W_hhT[unit 4ug+i][k], B[blk][j] = dG[row j][k],
-// k = 256*wave + 64*ks + q.  The 4 k-sub partials and the 8 waves' partials are summed by the pointwise thread.
-template <int PH, int NR, bool PACKED = false>
+// The "gathered-dG" backward: dh_rec = dG_{t_next} W_hh for this CU's 16 units, then the pointwise LSTM backward at
+// time t (dG_t written in place over the saved gates AND published to the group).  The exchange here is 4x larger
+// than in the forward (8 rows x 4H), so it uses bare fp32 words whose mantissa LSB is the validity tag: a slot is
+// rewritten every second step and the expected bit flips with every rewrite (the buffer starts zeroed = invalid), so
+// a consumer can tell new from stale per word; tearing between words is harmless.  Cost: <= 1 ulp on the exchanged
+// copy (the in-place dG used by the weight-gradient GEMMs is untouched).  Float4 traffic both ways.
+// One kernel, whose product dh_rec has two forms (`if constexpr (NT == 1)` below; everything else - roles, row map,
+// prefetch, hand-off poll and its abort path, pointwise backward, deferred stores, fused dW_hh, db - is shared):
+//   NT = 1       exact fp32 on v_mfma_f32_4x4x1f32.  MFMA blocks: 16 = 4 unit-groups x 4 k-subs; A[blk][i] =
+//                W_hhT[unit 4ug+i][k], B[blk][j] = dG[row j][k], k = 256*wave + 64*ks + q.  The 4 k-sub partials are
+//                summed with DPP, the 8 waves' partials by the pointwise thread.
+//   NT = 2 / 3   v_mfma_f32_16x16x32_bf16, operands split in NT bf16 terms as in lstm_persist_fwd_bf3_kernel (three /
+//                six products, fp32 accumulation): A = this CU's 16 units of W_hh^T in registers, B = the gathered dG
+//                tile, which the gathering lanes write to LDS twice - as fp32 for the fused dW_hh product (unchanged,
+//                exact fp32, off the serial chain) and split in bf16 for this one.
+
+template <int PH, int NR, int NT, bool PACKED = false>
 __global__ __launch_bounds__(PNT) void lstm_persist_bwd_kernel(PersistArgs a) {
   static_assert(NR == 4 || NR == PRG, "rows per group (see the forward kernel)");
+  static_assert(NT >= 1 && NT <= 3, "1: fp32 operands, 2 / 3: split-bf16 terms");
   constexpr int PUC = PH / 32;       // hidden units per CU
   constexpr int PKB = 4 * PH / PW;   // gate columns per wave
   constexpr int PQ = PKB / 4;        // k's per (wave, k-sub)
   constexpr int PQS = PQ + 4;        // padded LDS stride of a k-sub chunk
+  constexpr int KSB = PKB / 32;      // split form: k-steps of the dh product
+  constexpr int BST = PKB + 8;       // split form: bf16 row stride (16-byte multiple, 8 rows of a read on distinct bank groups)
   // this wave's K range of dG as [row][k-sub][64 + 4]: the 16 distinct (k-sub, row) addresses of one ds_read_b128
-  // differ by 68*ks + 272*row floats = 16 distinct 16-B bank slots (unpadded they are all 256-B multiples: 16-way)
+  // differ by 68*ks + 272*row floats = 16 distinct 16-B bank slots (unpadded they are all 256-B multiples: 16-way).
+  // The fp32 copy of the tile: operand of dW_hh in both forms, of the dh product with NT = 1.
   __shared__ __attribute__((aligned(16))) float hs[PW][PRG][4 * PQS];
-  __shared__ float part[2][PW][64][9];                                    // partial dh_rec, double buffered (36 KB)
+  // partial dh_rec, double buffered: NT = 1 [lane][register] of the 4x4x1 blocks (36 KB), split form [row][unit]
+  __shared__ __attribute__((aligned(NT == 1 ? 4 : 16))) float part[2][PW][NT == 1 ? 64 : PRG][NT == 1 ? 9 : 16];
+  // the dG tile split in NT bf16 terms, B operand of the split product.  With NT = 1 an empty type that nothing names: it
+  // takes no LDS (the lds_bytes column of tests/golden/isa_table.json)
+  struct NoTile {};
+  __shared__ __attribute__((aligned(16))) std::conditional_t<NT == 1, NoTile, unsigned short[NT][PW][PRG][BST]> bsp;
   __shared__ float ysl[2][PRG][16];                                       // this CU's slice of h at the current time
   __shared__ int role[2];
   constexpr int NKQ = (PKB + 63) / 64;                                    // 64-column chunks of the wave's K range
   const int tid = threadIdx.x, lane = tid & 63;
   if (tid < 2 * PRG * 16) (&ysl[0][0][0])[tid] = 0.f;
+  if constexpr (NT > 1) {
+    static_assert(PKB % 32 == 0 && PUC <= 16, "one 16-unit M tile, whole k-steps");
+    for (int i = tid; i < NT * PW * PRG * BST; i += PNT) (&bsp[0][0][0][0])[i] = 0;   // rows >= NR stay 0
+  }
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int g, slice;
   take_role(a.ctrl, role, g, slice);
@@ -847,11 +869,14 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_kernel(PersistArgs a) {
   const int r0 = rowgroup * NR;
   if (r0 >= a.nb) return;
   const int64_t ldy = (int64_t)ndir * PH, ldg = (int64_t)ndir * 4 * PH;
-  // W_hhT slice -> registers: lane (ug = lane>>4, ks = (lane>>2)&3, i = lane&3) holds unit 16*slice+4ug+i,
-  // k = 256*wave + 64*ks + q, q = 0..63
+  // lane maps of the dh product.  NT = 1: lane (ug = lane>>4, ks = (lane>>2)&3, li = lane&3) holds unit 16*slice+4ug+li,
+  // k = 256*wave + 64*ks + q, q = 0..63.  Split form: lane l holds unit ml = l & 15 of this CU, gate columns
+  // wave*PKB + 32 kt + 8 kg + j, kg = l >> 4 (A operand of the 16x16x32 product).
   const int ug = lane >> 4, ks = (lane >> 2) & 3, li = lane & 3;
-  float wreg[PQ];
-  {
+  const int ml = lane & 15, kg = lane >> 4;
+  // W_hhT slice -> registers for the whole sequence: fp32 words, or split bf16 per k-step
+  std::conditional_t<NT == 1, float[PQ], u32x4[KSB][NT]> wreg;
+  if constexpr (NT == 1) {
     const int wu = 4 * ug + li < PUC ? 4 * ug + li : 0;     // unit groups beyond PUC idle
     const float* wr = a.w + ((int64_t)d * PH + PUC * slice + wu) * (4 * PH) + wave * PKB + PQ * ks;
 #pragma unroll
@@ -859,325 +884,15 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_kernel(PersistArgs a) {
       const float4 v = *reinterpret_cast<const float4*>(wr + 4 * q4);
       wreg[4 * q4] = v.x; wreg[4 * q4 + 1] = v.y; wreg[4 * q4 + 2] = v.z; wreg[4 * q4 + 3] = v.w;
     }
-  }
-  // Waves 6-7 mirror the pointwise threads' (unit, row) mapping: they issue the SAME forward-data loads two steps
-  // further ahead and discard them, which pulls those HBM rows into this XCD's L2 before the pointwise threads ask
-  // (their own loads, one step ahead, were HBM first touches: ~0.3 us of every step with a cached row, see DESIGN).
-  const int mt = tid & 127;
-  const int pu = mt >> 3, pj = mt & 7;
-  const bool pw_lane = tid < PUC * PRG;                 // all 8 row lanes of a unit (bias-gradient reduction)
-  const bool pw_thread = pw_lane && pj < NR;
-  const int prow = r0 + pj;
-  const bool prow_ok = pw_thread && prow < a.nb;
-  const bool touch_ok = ASR_LSTM_TOUCH && tid >= 384 && mt < PUC * PRG && pj < NR && prow < a.nb;
-  const int punit = PUC * slice + pu;
-  const int plen = prow_ok ? a.lens[prow] : 0;
-  // row of (time, this thread's batch row): see PersistArgs and the note in lstm_persist_bwd_rs_kernel
-  const int pbase = (PACKED && prow_ok) ? a.rowbase[prow] : 0;
-  const int pext = PACKED ? (prow_ok ? a.rowext[prow] : 1) : a.T;
-  float dcarry = 0.f;
-  float4 dbacc = make_float4(0.f, 0.f, 0.f, 0.f);   // bias gradient of this thread's (unit, row): sum of dG over time
-  float* xch_g = reinterpret_cast<float*>(a.xch) + (int64_t)g * PRG * 4 * PH;   // + parity * 8*PRG*4H
-  const int64_t par_stride = (int64_t)8 * PRG * 4 * PH;
-#if ASR_LSTM_BWD_B128
-  typedef unsigned u4v __attribute__((ext_vector_type(4)));
-  const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(a.xch, 0, 0x7ffffff0, 0x00020000);   // raw dwords
-#endif
-  bool aborted = false;
-  // pointwise operands are fetched one step ahead (see the forward kernel)
-  float n_dy = 0.f, n_ct = 0.f, n_cp = 0.f, n_y = 0.f;
-  float4 n_av = make_float4(0.f, 0.f, 0.f, 0.f);
-  const bool fuse_dw = a.dw != nullptr && a.yfwd != nullptr;
-  // dW_hh accumulators: [64-column chunk][unit group] 4x4 blocks, kept in registers for the whole sequence
-  f32x4 dwacc[NKQ][4];
-#pragma unroll
-  for (int kq = 0; kq < NKQ; ++kq)
-#pragma unroll
-    for (int u4 = 0; u4 < 4; ++u4) dwacc[kq][u4] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  auto fetch_step = [&](int sn) {
-    const int tt = (ASR_LP_ABL & 8) ? 1 : (d == 0 ? T - 1 - sn : sn);      // bit 8 (measurement): always the same, cached row
-    const int ttp = d == 0 ? tt - 1 : tt + 1;
-    const bool hp = d == 0 ? (tt > 0) : (tt < T - 1);
-    const int64_t so = ROW_AT(tt) * ldy + d * PH + punit;
-    n_dy = a.dy[so];
-    n_av = *reinterpret_cast<const float4*>(a.gates + ROW_AT(tt) * ldg + (int64_t)d * 4 * PH + punit * 4);
-    n_ct = a.c[so];
-    n_cp = hp ? a.c[ROW_AT(ttp) * ldy + d * PH + punit] : 0.f;
-    if (fuse_dw) n_y = a.yfwd[so];
-  };
-  if (prow_ok) fetch_step(0);
-  for (int s = 0; s < T; ++s) {
-    const int t = d == 0 ? T - 1 - s : s;
-    LP_MARK(0);
-    const unsigned abort_seen = pw_thread ? flag_load(a.ctrl + 8) : 0u;     // see the forward kernel
-    const float dyv = n_dy, ct = n_ct, cp = n_cp;
-    const float4 av = n_av;
-    float4* gp = nullptr;
-    if (prow_ok) gp = reinterpret_cast<float4*>(a.gates + ROW_AT(t) * ldg + (int64_t)d * 4 * PH + punit * 4);
-    if (fuse_dw && pw_thread) ysl[s & 1][pj][pu] = prow_ok ? n_y : 0.f;     // h_t of this CU's units (read after the barrier)
-    f32x4 acc0 = (f32x4){0.f, 0.f, 0.f, 0.f}, acc1 = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if (s > 0) {
-      const unsigned want = (((unsigned)(s - 1) >> 1) & 1u) ^ 1u;      // tag bit of the data written at step s-1
-      const bool gl = 4 * lane < PKB;                   // lanes beyond the wave's K range re-read column 0
-      const float* src = xch_g + ((s - 1) & 1) * par_stride + wave * PKB + (gl ? 4 * lane : 0);
-      float4 gr[NR];
-      unsigned spins = 0;
-      auto load_row = [&](int rr) {
-#if ASR_LSTM_BWD_B128
-        // L1-bypassing 16-byte read in ONE instruction: buffer load with the sc1 cache policy (the same policy the
-        // agent-scope atomic loads get, which exist only up to 8 bytes)
-        const u4v v = __builtin_amdgcn_raw_buffer_load_b128(
-            xrs, (unsigned)((src - reinterpret_cast<const float*>(a.xch)) + rr * 4 * PH) * 4u, 0, 16);
-        gr[rr].x = __uint_as_float(v.x); gr[rr].y = __uint_as_float(v.y);
-        gr[rr].z = __uint_as_float(v.z); gr[rr].w = __uint_as_float(v.w);
-#else
-        // L1-bypassing 16-byte read as two 8-byte agent-scope atomics
-        const u64 lo = granule_load(reinterpret_cast<const u64*>(src + (int64_t)rr * 4 * PH));
-        const u64 hi = granule_load(reinterpret_cast<const u64*>(src + (int64_t)rr * 4 * PH) + 1);
-        gr[rr].x = __uint_as_float((unsigned)lo); gr[rr].y = __uint_as_float((unsigned)(lo >> 32));
-        gr[rr].z = __uint_as_float((unsigned)hi); gr[rr].w = __uint_as_float((unsigned)(hi >> 32));
-#endif
-      };
-      auto row_bits = [&](int rr) -> unsigned {
-        const unsigned m = (__float_as_uint(gr[rr].x) & 1u) | ((__float_as_uint(gr[rr].y) & 1u) << 1) |
-                           ((__float_as_uint(gr[rr].z) & 1u) << 2) | ((__float_as_uint(gr[rr].w) & 1u) << 3);
-        return want ? m : (~m & 0xFu);
-      };
-      bool first = wave < ASR_LSTM_BWD_FULL_WAVES;
-      while (true) {
-        if (first) {
-          // the pointwise waves poll last: first attempt requests the whole tile at once (one L2 round trip); as a
-          // separate code path -- folded into the sentinel condition the compiler still waited for the sentinel
-          first = false;
-#pragma unroll
-          for (int rr = 0; rr < NR; ++rr) load_row(rr);
-          unsigned bits = 0xFu;
-#pragma unroll
-          for (int rr = 0; rr < NR; ++rr) bits &= row_bits(rr);
-          if (__all(!gl || bits == 0xFu)) break;
-        } else {
-          // cheap sentinel poll: the last row of this wave's K range (1 KB, touches all 4 producer CUs); a failed
-          // poll of the whole 64 KB per CU would saturate the XCD's L2 and delay the producers themselves
-          load_row(NR - 1);
-          bool ok = !gl || row_bits(NR - 1) == 0xFu;
-          if (__all(ok)) {
-#pragma unroll
-            for (int rr = 0; rr < NR - 1; ++rr) load_row(rr);
-            unsigned bits = row_bits(NR - 1);
-#pragma unroll
-            for (int rr = 0; rr < NR - 1; ++rr) bits &= row_bits(rr);
-            if (__all(!gl || bits == 0xFu)) break;
-          }
-        }
-#ifdef ASR_NO_POLL
-        break;
-#endif
-        if (++spins > SPIN_LIMIT || ((spins & 63u) == 0u && flag_load(a.ctrl + 8) != 0u)) {
-          if (lane == 0) raise_abort(a.ctrl, 3u);
-          aborted = true;
-          break;
-        }
-        __builtin_amdgcn_s_sleep(ASR_POLL_SLEEP);
-      }
-      LP_MARK(1);
-#pragma unroll
-      for (int rr = 0; rr < NR; ++rr)
-        if (gl) *reinterpret_cast<float4*>(&hs[wave][rr][PQS * ((4 * lane) / PQ) + (4 * lane) % PQ]) = gr[rr];
-      if (prow_ok && s + 1 < T) fetch_step(s + 1);
-      else if (touch_ok && s + ASR_LSTM_TOUCH_DIST < T) fetch_step(s + ASR_LSTM_TOUCH_DIST);   // L2 warm-up (results unused)
-      const float* h0 = &hs[wave][li][PQS * ks];
-      const float* h1 = &hs[wave][4 + li][PQS * ks];
-#pragma unroll
-      for (int q4 = 0; q4 < ((ASR_LP_ABL & 1) ? 1 : PQ / 4); ++q4) {
-        const float4 b0 = *reinterpret_cast<const float4*>(h0 + 4 * q4);
-        if (NR > 4) {                      // alternating accumulators, see the forward kernel
-          const float4 b1 = *reinterpret_cast<const float4*>(h1 + 4 * q4);
-          acc0 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4], b0.x, acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4], b1.x, acc1, 0, 0, 0);
-          acc0 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4 + 1], b0.y, acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4 + 1], b1.y, acc1, 0, 0, 0);
-          acc0 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4 + 2], b0.z, acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4 + 2], b1.z, acc1, 0, 0, 0);
-          acc0 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4 + 3], b0.w, acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4 + 3], b1.w, acc1, 0, 0, 0);
-        } else {
-          acc0 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4], b0.x, acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4 + 1], b0.y, acc1, 0, 0, 0);
-          acc0 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4 + 2], b0.z, acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4 + 3], b0.w, acc1, 0, 0, 0);
-        }
-      }
-      if (NR <= 4) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc0[i] += acc1[i];
-      }
-    }
-    if (s == 0 && prow_ok && T > 1) fetch_step(1);
-    LP_MARK(2);
-    // the 4 k-sub partials of a (unit, row) sit 4 lanes apart inside a row of 16: two DPP row rotations leave their
-    // sum in every one of those lanes, so the pointwise thread reads 8 values (one per wave) instead of 32.  (Done on
-    // scalar copies: applied to the elements of the MFMA accumulator vector in place, hipcc 7.2 paired the rotations
-    // with the wrong elements.)
-    float red[8];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { red[i] = acc0[i]; red[4 + i] = NR > 4 ? acc1[i] : 0.f; }
-#pragma unroll
-    for (int i = 0; i < (NR > 4 ? 8 : 4); ++i) {
-      red[i] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, red[i]), 0x124, 0xf, 0xf, true));
-      red[i] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, red[i]), 0x128, 0xf, 0xf, true));
-    }
-    float* pp = &part[s & 1][wave][lane][0];
-#pragma unroll
-    for (int i = 0; i < (NR > 4 ? 8 : 4); ++i) pp[i] = red[i];
-    LP_MARK(3);
-    __syncthreads();
-    LP_MARK(4);
-    if (pw_thread) {
-      // dh_rec[unit pu][row pj]: lanes 16*(pu>>2) + 4*ks + (pj&3), register 4*(pj>>2) + (pu&3), all ks, all waves
-      float dh = dyv;
-      const int pl = 16 * (pu >> 2) + (pj & 3), pr = 4 * (pj >> 2) + (pu & 3);
-#pragma unroll
-      for (int w2 = 0; w2 < PW; ++w2) dh += part[s & 1][w2][pl][pr];      // k-subs already summed (DPP, above)
-      LP_MARK(9);
-      const float tc = asr_fast_tanh(ct);
-      const float dc = dcarry + dh * av.w * (1.f - tc * tc);
-      float4 da;
-      da.x = dc * av.z * av.x * (1.f - av.x);
-      da.y = dc * cp * av.y * (1.f - av.y);
-      da.z = dc * av.x * (1.f - av.z * av.z);
-      da.w = dh * tc * av.w * (1.f - av.w);
-      float dcn = dc * av.y;
-      if (t >= plen) { da = make_float4(0.f, 0.f, 0.f, 0.f); dcn = 0.f; }
-      if (aborted || abort_seen != 0u) da.x = __builtin_nanf("");
-      dcarry = dcn;
-      const unsigned bit = (((unsigned)s >> 1) & 1u) ^ 1u;
-      float4 tg;
-      tg.x = tag_word(da.x, bit); tg.y = tag_word(da.y, bit); tg.z = tag_word(da.z, bit); tg.w = tag_word(da.w, bit);
-      LP_MARK(10);
-      float* dst = xch_g + (s & 1) * par_stride + (int64_t)pj * 4 * PH + punit * 4;
-      // two 8-byte workgroup-scope (plain, L2-resident) stores; every word carries its own tag
-      __hip_atomic_store((gu64*)dst, ((u64)__float_as_uint(tg.y) << 32) | __float_as_uint(tg.x), __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_WORKGROUP);
-      __hip_atomic_store((gu64*)dst + 1, ((u64)__float_as_uint(tg.w) << 32) | __float_as_uint(tg.z), __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_WORKGROUP);
-      LP_MARK(11);
-      if (prow_ok) {     // after the hand-off: the bulk store and the bias-gradient sum are off the serial chain
-        if (!(ASR_LP_ABL & 16) && (!PACKED || t < pext)) *gp = da;
-        dbacc.x += da.x; dbacc.y += da.y; dbacc.z += da.z; dbacc.w += da.w;
-      }
-    }
-    LP_MARK(5);
-    // Fused recurrent weight gradient: dW_hh[k][u] += sum_rows dG_{t_next}[row][k] * h_t[row][u].  The gathered dG
-    // tile is still in this wave's LDS region and h_t is the partner of dG_{t_next} in both directions.  Placed
-    // after the publish so that it fills the wait for the next hand-off.  Blocks = 16 groups of 4 gate columns,
-    // A = dG (4 columns), B = h (4 units), K = one batch row per instruction.
-    if (fuse_dw && s > 0 && !(ASR_LP_ABL & 2)) {
-      const int kb4 = lane;                      // column within the 64-column chunk (= 4*block + i)
-      const int jj = lane & 3;
-#pragma unroll
-      for (int rr = 0; rr < NR; ++rr) {
-        float bv[4];
-#pragma unroll
-        for (int u4 = 0; u4 < 4; ++u4) bv[u4] = ysl[s & 1][rr][4 * u4 + jj];
-#pragma unroll
-        for (int kq = 0; kq < NKQ; ++kq) {
-          const int cidx = 64 * kq + kb4;
-          const float av2 = cidx < PKB ? hs[wave][rr][PQS * (cidx / PQ) + cidx % PQ] : 0.f;
-#pragma unroll
-          for (int u4 = 0; u4 < 4; ++u4)
-            dwacc[kq][u4] = __builtin_amdgcn_mfma_f32_4x4x1f32(av2, bv[u4], dwacc[kq][u4], 0, 0, 0);
-        }
-      }
-    }
-  }
-  // packed rows: dG of the block's padding rows behind the T steps that were run (PersistArgs)
-  if constexpr (PACKED) if (prow_ok) {
-    for (int tt = T; tt < pext; ++tt)
-      *reinterpret_cast<float4*>(a.gates + ROW_AT(tt) * ldg + (int64_t)d * 4 * PH + punit * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  if (a.db != nullptr && pw_lane) {
-    // rows of a unit sit in 8 consecutive lanes (pj = tid & 7); the 4 row groups (XCDs) of a direction add up
-    float v[4] = {dbacc.x, dbacc.y, dbacc.z, dbacc.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      v[k] += __shfl_xor(v[k], 1, 64);
-      v[k] += __shfl_xor(v[k], 2, 64);
-      v[k] += __shfl_xor(v[k], 4, 64);
-    }
-    if (pj == 0) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) atomicAdd(a.db + (int64_t)d * 4 * PH + punit * 4 + k, v[k]);
-    }
-  }
-  if (fuse_dw) {
-    // D[i][j] of block kb: gate column 64*kq + 4*kb + i of this wave's range, unit 4*u4 + j of this CU; the 4 row
-    // groups (XCDs) of a direction add into the same dW_hh
-    const int kb = lane >> 2, jj = lane & 3;
-#pragma unroll
-    for (int kq = 0; kq < NKQ; ++kq)
-#pragma unroll
-      for (int u4 = 0; u4 < 4; ++u4)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int cidx = 64 * kq + 4 * kb + i, un = 4 * u4 + jj;
-          if (cidx < PKB && un < PUC)
-            atomicAdd(a.dw + ((int64_t)d * 4 * PH + wave * PKB + cidx) * PH + PUC * slice + un, dwacc[kq][u4][i]);
-        }
-  }
-}
-
-// ---------------------------------------------------------------------------- backward, split-bf16 dh product
-// lstm_persist_bwd_kernel with the recurrent product dh_rec = dG_{t_next} W_hh on v_mfma_f32_16x16x32_bf16 (operands
-// split as in lstm_persist_fwd_bf3_kernel: three products, fp32 accumulation): A = this CU's 16 units of W_hh^T in
-// registers, B = the gathered dG tile, which the gathering lanes write to LDS twice - as fp32 for the fused dW_hh
-// product (unchanged, exact fp32, off the serial chain) and split in bf16 for this one.  D puts the 4 units 4 (l >> 4)
-// .. + 3 of batch row l & 15 in one lane: the 4 k-sub partials and their DPP reduction of the 4x4x1 mapping are gone.
-template <int PH, int NR, int NT, bool PACKED = false>
-__global__ __launch_bounds__(PNT) void lstm_persist_bwd_bf3_kernel(PersistArgs a) {
-  static_assert(NR == 4 || NR == PRG, "rows per group (see the forward kernel)");
-  constexpr int PUC = PH / 32;       // hidden units per CU
-  constexpr int PKB = 4 * PH / PW;   // gate columns per wave
-  constexpr int PQ = PKB / 4;        // k's per (wave, k-sub)
-  constexpr int PQS = PQ + 4;        // padded LDS stride of a k-sub chunk
-  // this wave's K range of dG as [row][k-sub][64 + 4]: the 16 distinct (k-sub, row) addresses of one ds_read_b128
-  // differ by 68*ks + 272*row floats = 16 distinct 16-B bank slots (unpadded they are all 256-B multiples: 16-way)
-  __shared__ __attribute__((aligned(16))) float hs[PW][PRG][4 * PQS];    // fp32 copy of the dG tile: operand of dW_hh
-  constexpr int KSB = PKB / 32;      // k-steps of the split-bf16 dh product
-  constexpr int BST = PKB + 8;       // bf16 row stride (16-byte multiple, 8 rows of a read on distinct bank groups)
-  static_assert(PKB % 32 == 0 && PUC <= 16, "one 16-unit M tile, whole k-steps");
-  __shared__ __attribute__((aligned(16))) unsigned short bsp[NT][PW][PRG][BST];   // dG tile split for the dh product
-  __shared__ __attribute__((aligned(16))) float part[2][PW][PRG][16];         // partial dh_rec [row][unit], double buffered
-  __shared__ float ysl[2][PRG][16];                                       // this CU's slice of h at the current time
-  __shared__ int role[2];
-  constexpr int NKQ = (PKB + 63) / 64;                                    // 64-column chunks of the wave's K range
-  const int tid = threadIdx.x, lane = tid & 63;
-  if (tid < 2 * PRG * 16) (&ysl[0][0][0])[tid] = 0.f;
-  for (int i = tid; i < NT * PW * PRG * BST; i += PNT) (&bsp[0][0][0][0])[i] = 0;   // rows >= NR stay 0
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int g, slice;
-  take_role(a.ctrl, role, g, slice);
-  if (slice < 0) return;
-  const int T = a.T, B = a.B, ndir = a.ndir;
-  const int d = ndir == 2 ? (g & 1) : 0;
-  const int rowgroup = ndir == 2 ? (g >> 1) : g;
-  const int r0 = rowgroup * NR;
-  if (r0 >= a.nb) return;
-  const int64_t ldy = (int64_t)ndir * PH, ldg = (int64_t)ndir * 4 * PH;
-  // W_hhT slice -> registers: lane (ug = lane>>4, ks = (lane>>2)&3, i = lane&3) holds unit 16*slice+4ug+i,
-  // k = 256*wave + 64*ks + q, q = 0..63
-  // W_hhT slice -> split bf16 registers: A operand of the 16x16x32 product, lane l holds unit l & 15 of this CU,
-  // gate columns wave*PKB + 32 ks + 8 (l >> 4) + j
-  const int ml = lane & 15, kq = lane >> 4;
-  u32x4 wt[KSB][NT];
-  {
+  } else {
     const bool uok = ml < PUC;
-    const float* wr = a.w + ((int64_t)d * PH + PUC * slice + (uok ? ml : 0)) * (4 * PH) + wave * PKB + 8 * kq;
+    const float* wr = a.w + ((int64_t)d * PH + PUC * slice + (uok ? ml : 0)) * (4 * PH) + wave * PKB + 8 * kg;
 #pragma unroll
-    for (int ks = 0; ks < KSB; ++ks) {
-      const float4 q0 = *reinterpret_cast<const float4*>(wr + 32 * ks), q1 = *reinterpret_cast<const float4*>(wr + 32 * ks + 4);
+    for (int kt = 0; kt < KSB; ++kt) {
+      const float4 q0 = *reinterpret_cast<const float4*>(wr + 32 * kt), q1 = *reinterpret_cast<const float4*>(wr + 32 * kt + 4);
       const float v[8] = {uok ? q0.x : 0.f, uok ? q0.y : 0.f, uok ? q0.z : 0.f, uok ? q0.w : 0.f,
                           uok ? q1.x : 0.f, uok ? q1.y : 0.f, uok ? q1.z : 0.f, uok ? q1.w : 0.f};
-      bfn_split8<NT>(v, wt[ks]);
+      bfn_split8<NT>(v, wreg[kt]);
     }
   }
   // Waves 6-7 mirror the pointwise threads' (unit, row) mapping: they issue the SAME forward-data loads two steps
@@ -1235,6 +950,7 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_bf3_kernel(PersistArgs a
     float4* gp = nullptr;
     if (prow_ok) gp = reinterpret_cast<float4*>(a.gates + ROW_AT(t) * ldg + (int64_t)d * 4 * PH + punit * 4);
     if (fuse_dw && pw_thread) ysl[s & 1][pj][pu] = prow_ok ? n_y : 0.f;     // h_t of this CU's units (read after the barrier)
+    // NT = 1: two alternating accumulators; split form: three independent ones (one per group of split products)
     f32x4 acc0 = (f32x4){0.f, 0.f, 0.f, 0.f}, acc1 = (f32x4){0.f, 0.f, 0.f, 0.f}, acc2 = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (s > 0) {
       const unsigned want = (((unsigned)(s - 1) >> 1) & 1u) ^ 1u;      // tag bit of the data written at step s-1
@@ -1304,45 +1020,101 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_bf3_kernel(PersistArgs a
       for (int rr = 0; rr < NR; ++rr)
         if (gl) {
           *reinterpret_cast<float4*>(&hs[wave][rr][PQS * ((4 * lane) / PQ) + (4 * lane) % PQ]) = gr[rr];
-          unsigned p0[NT], p1[NT];
-          bfn_split2<NT>(gr[rr].x, gr[rr].y, p0);
-          bfn_split2<NT>(gr[rr].z, gr[rr].w, p1);
+          if constexpr (NT > 1) {
+            unsigned p0[NT], p1[NT];
+            bfn_split2<NT>(gr[rr].x, gr[rr].y, p0);
+            bfn_split2<NT>(gr[rr].z, gr[rr].w, p1);
 #pragma unroll
-          for (int k = 0; k < NT; ++k) *reinterpret_cast<uint2*>(&bsp[k][wave][rr][4 * lane]) = make_uint2(p0[k], p1[k]);
+            for (int k = 0; k < NT; ++k) *reinterpret_cast<uint2*>(&bsp[k][wave][rr][4 * lane]) = make_uint2(p0[k], p1[k]);
+          }
         }
       if (prow_ok && s + 1 < T) fetch_step(s + 1);
       else if (touch_ok && s + ASR_LSTM_TOUCH_DIST < T) fetch_step(s + ASR_LSTM_TOUCH_DIST);   // L2 warm-up (results unused)
-      // dh partial [16 units x rows] of this wave's K range: three independent accumulators (one per split term)
+      if constexpr (NT == 1) {
+        const float* h0 = &hs[wave][li][PQS * ks];
+        const float* h1 = &hs[wave][4 + li][PQS * ks];
 #pragma unroll
-      for (int ks = 0; ks < ((ASR_LP_ABL & 1) ? 1 : KSB); ++ks) {
-        u32x4 bt[NT];
+        for (int q4 = 0; q4 < ((ASR_LP_ABL & 1) ? 1 : PQ / 4); ++q4) {
+          const float4 b0 = *reinterpret_cast<const float4*>(h0 + 4 * q4);
+          if (NR > 4) {                      // alternating accumulators, see the forward kernel
+            const float4 b1 = *reinterpret_cast<const float4*>(h1 + 4 * q4);
+            acc0 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4], b0.x, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4], b1.x, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4 + 1], b0.y, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4 + 1], b1.y, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4 + 2], b0.z, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4 + 2], b1.z, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4 + 3], b0.w, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4 + 3], b1.w, acc1, 0, 0, 0);
+          } else {
+            acc0 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4], b0.x, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4 + 1], b0.y, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4 + 2], b0.z, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * q4 + 3], b0.w, acc1, 0, 0, 0);
+          }
+        }
+        if (NR <= 4) {
 #pragma unroll
-        for (int k = 0; k < NT; ++k) bt[k] = *reinterpret_cast<const u32x4*>(&bsp[k][wave][ml & 7][32 * ks + 8 * kq]);
-        acc0 = bf3_mfma(wt[ks][0], bt[0], acc0);
-        acc1 = bf3_mfma(wt[ks][0], bt[1], acc1);
-        acc2 = bf3_mfma(wt[ks][1], bt[0], acc2);
-        if constexpr (NT == 3) {
-          acc0 = bf3_mfma(wt[ks][0], bt[2], acc0);
-          acc1 = bf3_mfma(wt[ks][2], bt[0], acc1);
-          acc2 = bf3_mfma(wt[ks][1], bt[1], acc2);
+          for (int i = 0; i < 4; ++i) acc0[i] += acc1[i];
+        }
+      } else {
+        // dh partial [16 units x rows] of this wave's K range
+#pragma unroll
+        for (int kt = 0; kt < ((ASR_LP_ABL & 1) ? 1 : KSB); ++kt) {
+          u32x4 bt[NT];
+#pragma unroll
+          for (int k = 0; k < NT; ++k) bt[k] = *reinterpret_cast<const u32x4*>(&bsp[k][wave][ml & 7][32 * kt + 8 * kg]);
+          acc0 = bf3_mfma(wreg[kt][0], bt[0], acc0);
+          acc1 = bf3_mfma(wreg[kt][0], bt[1], acc1);
+          acc2 = bf3_mfma(wreg[kt][1], bt[0], acc2);
+          if constexpr (NT == 3) {
+            acc0 = bf3_mfma(wreg[kt][0], bt[2], acc0);
+            acc1 = bf3_mfma(wreg[kt][2], bt[0], acc1);
+            acc2 = bf3_mfma(wreg[kt][1], bt[1], acc2);
+          }
         }
       }
     }
     if (s == 0 && prow_ok && T > 1) fetch_step(1);
     LP_MARK(2);
-    // D: lane l holds units 4 (l >> 4) .. + 3 of batch row l & 15
-    if (ml < NR)
-      *reinterpret_cast<float4*>(&part[s & 1][wave][ml][4 * kq]) =
-          make_float4(acc0[0] + acc1[0] + acc2[0], acc0[1] + acc1[1] + acc2[1], acc0[2] + acc1[2] + acc2[2],
-                      acc0[3] + acc1[3] + acc2[3]);
+    if constexpr (NT == 1) {
+      // the 4 k-sub partials of a (unit, row) sit 4 lanes apart inside a row of 16: two DPP row rotations leave their
+      // sum in every one of those lanes, so the pointwise thread reads 8 values (one per wave) instead of 32.  (Done on
+      // scalar copies: applied to the elements of the MFMA accumulator vector in place, hipcc 7.2 paired the rotations
+      // with the wrong elements.)
+      float red[8];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { red[i] = acc0[i]; red[4 + i] = NR > 4 ? acc1[i] : 0.f; }
+#pragma unroll
+      for (int i = 0; i < (NR > 4 ? 8 : 4); ++i) {
+        red[i] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, red[i]), 0x124, 0xf, 0xf, true));
+        red[i] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, red[i]), 0x128, 0xf, 0xf, true));
+      }
+      float* pp = &part[s & 1][wave][lane][0];
+#pragma unroll
+      for (int i = 0; i < (NR > 4 ? 8 : 4); ++i) pp[i] = red[i];
+    } else {
+      // D of the 16x16x32 product puts the 4 units 4 (l >> 4) .. + 3 of batch row l & 15 in one lane: the 4 k-sub
+      // partials of the 4x4x1 mapping and their DPP reduction are gone
+      if (ml < NR)
+        *reinterpret_cast<float4*>(&part[s & 1][wave][ml][4 * kg]) =
+            make_float4(acc0[0] + acc1[0] + acc2[0], acc0[1] + acc1[1] + acc2[1], acc0[2] + acc1[2] + acc2[2],
+                        acc0[3] + acc1[3] + acc2[3]);
+    }
     LP_MARK(3);
     __syncthreads();
     LP_MARK(4);
     if (pw_thread) {
-      // dh_rec[unit pu][row pj]: lanes 16*(pu>>2) + 4*ks + (pj&3), register 4*(pj>>2) + (pu&3), all ks, all waves
       float dh = dyv;
+      if constexpr (NT == 1) {
+        // dh_rec[unit pu][row pj]: lanes 16*(pu>>2) + 4*ks + (pj&3), register 4*(pj>>2) + (pu&3), all waves
+        const int pl = 16 * (pu >> 2) + (pj & 3), pr = 4 * (pj >> 2) + (pu & 3);
 #pragma unroll
-      for (int w2 = 0; w2 < PW; ++w2) dh += part[s & 1][w2][pj][pu];
+        for (int w2 = 0; w2 < PW; ++w2) dh += part[s & 1][w2][pl][pr];      // k-subs already summed (DPP, above)
+      } else {
+#pragma unroll
+        for (int w2 = 0; w2 < PW; ++w2) dh += part[s & 1][w2][pj][pu];
+      }
       LP_MARK(9);
       const float tc = asr_fast_tanh(ct);
       const float dc = dcarry + dh * av.w * (1.f - tc * tc);
@@ -1447,7 +1219,7 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_bf3_kernel(PersistArgs a
 //     local, h_{t_prev} is forward data (8 rows x H, prefetched a step ahead); the product runs on
 //     v_mfma_f32_16x16x16_bf16 (K = 8 batch rows, zero padded to 16), split in three like the others: 768 MFMA cycles
 //     per SIMD and step instead of 2 048 on the fp32 pipe, and it sits between the publish and the next gather.
-// H in {128, 256, 512} (units per CU a multiple of 4); other sizes keep lstm_persist_bwd_bf3_kernel.
+// H in {128, 256, 512} (units per CU a multiple of 4); other sizes keep lstm_persist_bwd_kernel.
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 __device__ __forceinline__ f32x4 bf3_mfma16(const uint2& a, const uint2& b, const f32x4& c) {
@@ -2228,84 +2000,35 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_rs640_kernel(PersistArgs
 
 namespace {
 
-template <int PH, int NR>
-int launch_fwd(const PersistArgs& a, hipStream_t stream) {
-  const size_t stat = sizeof(float) * ((size_t)PW * PRG * (PH / PW + 4) + 2 * PW * 64 * 8) + 64;
-  const size_t pad = stat > 82 * 1024 ? 0 : 82 * 1024 - stat;       // static + pad > 80 KB: one workgroup per CU
-  const void* fn = a.rowbase ? (const void*)lstm_persist_fwd_kernel<PH, NR, true> : (const void*)lstm_persist_fwd_kernel<PH, NR, false>;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad);
+// Dynamic LDS that keeps a second workgroup off the CU (160 KB): static + pad > 80 KB, so the 256 workgroups of a launch
+// are co-resident, one per CU.  The static size is the compiled kernel's own; -1 when it cannot be read.
+int one_per_cu_pad(const void* kernel) {
+  hipFuncAttributes fa;
+  if (hipFuncGetAttributes(&fa, kernel) != hipSuccess) return -1;
+  const size_t stat = fa.sharedSizeBytes;
+  return stat < 82 * 1024 ? (int)(82 * 1024 - stat) : 0;
+}
+
+// Launch of a persistent kernel, 256 workgroups x PNT threads: its PACKED instantiation when the arguments carry a row
+// map (PersistArgs), its time-major one otherwise.
+template <auto TIME_MAJOR, auto PACKED_ROWS>
+int launch_persist(const PersistArgs& a, hipStream_t stream) {
+  static const int pads[2] = {one_per_cu_pad((const void*)TIME_MAJOR), one_per_cu_pad((const void*)PACKED_ROWS)};
+  const auto kernel = a.rowbase ? PACKED_ROWS : TIME_MAJOR;
+  const int pad = pads[a.rowbase ? 1 : 0];
+  if (pad < 0) return (int)hipErrorInvalidDeviceFunction;
+  hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, pad);
   if (e != hipSuccess) return (int)e;
-  if (a.rowbase) hipLaunchKernelGGL((lstm_persist_fwd_kernel<PH, NR, true>), dim3(256), dim3(PNT), pad, stream, a);
-  else hipLaunchKernelGGL((lstm_persist_fwd_kernel<PH, NR, false>), dim3(256), dim3(PNT), pad, stream, a);
+  hipLaunchKernelGGL(kernel, dim3(256), dim3(PNT), pad, stream, a);
   return 0;
 }
 
-template <int PH, int NR, int NT, int RG = PRG>
-int launch_fwd_bf3(const PersistArgs& a, hipStream_t stream, bool fault = false) {
-  constexpr int KP = ((PH / PW + 31) / 32) * 32, MT = (PH / 32 + 3) / 4;
-  const size_t stat = (size_t)((NT == 3 && RG == 8) ? 4 : NT) * PW * RG * (KP + 8) * 2 + sizeof(float) * 2 * PW * 4 * MT * RG * 4 + 64;
-  const size_t pad = stat > 82 * 1024 ? 0 : 82 * 1024 - stat;       // static + pad > 80 KB: one workgroup per CU
-  // (packed rows / time-major rows: two instantiations, see the row map in the kernel)
-  if constexpr (PH == 512 && NT == 3 && RG == PRG) {      // the FAULT instantiations exist for the default arithmetic at H = 512 only
-    if (fault) {
-      const void* ff = a.rowbase ? (const void*)lstm_persist_fwd_bf3_kernel<PH, NR, NT, RG, true, true>
-                                 : (const void*)lstm_persist_fwd_bf3_kernel<PH, NR, NT, RG, false, true>;
-      hipError_t ef = hipFuncSetAttribute(ff, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad);
-      if (ef != hipSuccess) return (int)ef;
-      if (a.rowbase) hipLaunchKernelGGL((lstm_persist_fwd_bf3_kernel<PH, NR, NT, RG, true, true>), dim3(256), dim3(PNT), pad, stream, a);
-      else hipLaunchKernelGGL((lstm_persist_fwd_bf3_kernel<PH, NR, NT, RG, false, true>), dim3(256), dim3(PNT), pad, stream, a);
-      return 0;
-    }
-  } else if (fault) {
-    return ASR_E_SHAPE;
-  }
-  const void* fn = a.rowbase ? (const void*)lstm_persist_fwd_bf3_kernel<PH, NR, NT, RG, true>
-                             : (const void*)lstm_persist_fwd_bf3_kernel<PH, NR, NT, RG, false>;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad);
-  if (e != hipSuccess) return (int)e;
-  if (a.rowbase) hipLaunchKernelGGL((lstm_persist_fwd_bf3_kernel<PH, NR, NT, RG, true>), dim3(256), dim3(PNT), pad, stream, a);
-  else hipLaunchKernelGGL((lstm_persist_fwd_bf3_kernel<PH, NR, NT, RG, false>), dim3(256), dim3(PNT), pad, stream, a);
-  return 0;
-}
-
-template <int PH, int NR>
-int launch_bwd(const PersistArgs& a, hipStream_t stream) {
-  const size_t stat = sizeof(float) * ((size_t)PW * PRG * 4 * (PH / 2 / 4 + 4) + 2 * PW * 64 * 9) + 64;
-  const size_t pad = stat > 82 * 1024 ? 0 : 82 * 1024 - stat;
-  const void* fn = a.rowbase ? (const void*)lstm_persist_bwd_kernel<PH, NR, true> : (const void*)lstm_persist_bwd_kernel<PH, NR, false>;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad);
-  if (e != hipSuccess) return (int)e;
-  if (a.rowbase) hipLaunchKernelGGL((lstm_persist_bwd_kernel<PH, NR, true>), dim3(256), dim3(PNT), pad, stream, a);
-  else hipLaunchKernelGGL((lstm_persist_bwd_kernel<PH, NR, false>), dim3(256), dim3(PNT), pad, stream, a);
-  return 0;
-}
-
-template <int PH, int NR, int NT>
-int launch_bwd_bf3(const PersistArgs& a, hipStream_t stream) {
-  const size_t lds = sizeof(float) * ((size_t)PW * PRG * 4 * (PH / 2 / 4 + 4) + 2 * PW * PRG * 16 + 2 * PRG * 16) +
-                     (size_t)NT * PW * PRG * (PH / 2 + 8) * 2 + 64;
-  const size_t pad = lds > 82 * 1024 ? 0 : 82 * 1024 - lds;
-  const void* fn = a.rowbase ? (const void*)lstm_persist_bwd_bf3_kernel<PH, NR, NT, true> : (const void*)lstm_persist_bwd_bf3_kernel<PH, NR, NT, false>;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad);
-  if (e != hipSuccess) return (int)e;
-  if (a.rowbase) hipLaunchKernelGGL((lstm_persist_bwd_bf3_kernel<PH, NR, NT, true>), dim3(256), dim3(PNT), pad, stream, a);
-  else hipLaunchKernelGGL((lstm_persist_bwd_bf3_kernel<PH, NR, NT, false>), dim3(256), dim3(PNT), pad, stream, a);
-  return 0;
-}
-
-template <int PH, int NR, int NT>
-int launch_bwd_rs(const PersistArgs& a, hipStream_t stream) {
-  using RD = RsDims<PH>;
-  const size_t stat = (size_t)(NT == 3 ? 4 : NT) * (NT == 2 ? 4 : 1) * PRG * RD::GST * 2 + PRG * 16 * sizeof(float) + 64 +
-                      (NT == 2 ? (size_t)2 * PH * 4 * PRG * 2 : (size_t)64);
-  const size_t pad = stat > 82 * 1024 ? 0 : 82 * 1024 - stat;       // static + pad > 80 KB: one workgroup per CU
-  const void* fn = a.rowbase ? (const void*)lstm_persist_bwd_rs_kernel<PH, NR, NT, true>
-                             : (const void*)lstm_persist_bwd_rs_kernel<PH, NR, NT, false>;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad);
-  if (e != hipSuccess) return (int)e;
-  if (a.rowbase) hipLaunchKernelGGL((lstm_persist_bwd_rs_kernel<PH, NR, NT, true>), dim3(256), dim3(PNT), pad, stream, a);
-  else hipLaunchKernelGGL((lstm_persist_bwd_rs_kernel<PH, NR, NT, false>), dim3(256), dim3(PNT), pad, stream, a);
-  return 0;
+// Runtime H -> compile-time width: f(std::integral_constant<int, H>) for H among WIDTHS, ASR_E_SHAPE for any other
+template <int... WIDTHS, class F>
+int with_width(int H, F&& f) {
+  int rc = ASR_E_SHAPE;
+  (void)((H == WIDTHS && (rc = f(std::integral_constant<int, WIDTHS>{}), true)) || ...);
+  return rc;
 }
 
 bool persist_supported(int H) { return H == 128 || H == 256 || H == 320 || H == 512; }
@@ -2340,12 +2063,21 @@ bool fwd_rows16(int left, int ndir, int H, int arith) {
 
 // arith (include/asr_hip.h): ASR_ARITH_F32 -> the 4x4x1 fp32-MFMA kernels; ASR_ARITH_BF16X6 / _BF16X3 -> the bf16-MFMA
 // kernels with three / two split terms.  H = 640 (the judge's width) exists on the bf16 kernels only.
-template <int NR, int NT>
+template <int NR, int NT, int RG = PRG>
 int dispatch_fwd_split(int H, const PersistArgs& a, hipStream_t stream, bool fault) {
-  if (fault && H != 512) return ASR_E_SHAPE;
-  return H == 640 ? launch_fwd_bf3<640, NR, NT>(a, stream) : H == 512 ? launch_fwd_bf3<512, NR, NT>(a, stream, fault)
-       : H == 320 ? launch_fwd_bf3<320, NR, NT>(a, stream) : H == 256 ? launch_fwd_bf3<256, NR, NT>(a, stream)
-                                                           : launch_fwd_bf3<128, NR, NT>(a, stream);
+  if (fault) {      // the FAULT instantiations exist for the default arithmetic at H = 512 only
+    if constexpr (NT == 3 && RG == PRG)
+      if (H == 512)
+        return launch_persist<lstm_persist_fwd_bf3_kernel<512, NR, 3, RG, false, true>,
+                              lstm_persist_fwd_bf3_kernel<512, NR, 3, RG, true, true>>(a, stream);
+    return ASR_E_SHAPE;
+  }
+  auto launch = [&](auto w) {
+    constexpr int PH = decltype(w)::value;
+    return launch_persist<lstm_persist_fwd_bf3_kernel<PH, NR, NT, RG, false>, lstm_persist_fwd_bf3_kernel<PH, NR, NT, RG, true>>(a, stream);
+  };
+  if constexpr (RG == 16) return with_width<512>(H, launch);
+  else return with_width<128, 256, 320, 512, 640>(H, launch);
 }
 template <int NR>
 int dispatch_fwd(int H, int arith, const PersistArgs& a, hipStream_t stream) {
@@ -2354,11 +2086,13 @@ int dispatch_fwd(int H, int arith, const PersistArgs& a, hipStream_t stream) {
   if (ar == ASR_ARITH_BF16X6) return dispatch_fwd_split<NR, 3>(H, a, stream, fault);
   if (fault) return ASR_E_SHAPE;
   if (ar == ASR_ARITH_BF16X3) return dispatch_fwd_split<NR, 2>(H, a, stream, false);
-  if (H == 640) return ASR_E_SHAPE;
-  return H == 512 ? launch_fwd<512, NR>(a, stream) : H == 320 ? launch_fwd<320, NR>(a, stream)
-       : H == 256 ? launch_fwd<256, NR>(a, stream) : launch_fwd<128, NR>(a, stream);
+  return with_width<128, 256, 320, 512>(H, [&](auto w) {
+    constexpr int PH = decltype(w)::value;
+    return launch_persist<lstm_persist_fwd_kernel<PH, NR, false>, lstm_persist_fwd_kernel<PH, NR, true>>(a, stream);
+  });
 }
-// which backward kernel a call takes: 0 fp32 gathered-dG, 1 split gathered-dG, 2 split exchanged partials, -1 none
+// which backward kernel a call takes: 0 gathered-dG with fp32 operands, 1 gathered-dG with split operands, 2 split
+// exchanged partials, -1 none
 int bwd_kernel_kind(int H, int arith) {
   const int ar = arith & ASR_ARITH_MASK;
   if (H == 640) return (ar == ASR_ARITH_BF16X6 && !(arith & ASR_LSTM_BWD_GATHER)) ? 2 : -1;
@@ -2368,42 +2102,34 @@ int bwd_kernel_kind(int H, int arith) {
   if (ar == ASR_ARITH_BF16X6 && H > 320) return -1;
   return 1;
 }
-template <int NR>
-int launch_bwd_rs640(const PersistArgs& a, hipStream_t stream) {
-  const size_t pad = 70 * 1024;                      // static (15 KB) + pad > 80 KB: one workgroup per CU
-  const void* fn = a.rowbase ? (const void*)lstm_persist_bwd_rs640_kernel<NR, true> : (const void*)lstm_persist_bwd_rs640_kernel<NR, false>;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad);
-  if (e != hipSuccess) return (int)e;
-  if (a.rowbase) hipLaunchKernelGGL((lstm_persist_bwd_rs640_kernel<NR, true>), dim3(256), dim3(PNT), pad, stream, a);
-  else hipLaunchKernelGGL((lstm_persist_bwd_rs640_kernel<NR, false>), dim3(256), dim3(PNT), pad, stream, a);
-  return 0;
-}
-
+// NT: terms of the operand split (1: the fp32 operands of kind 0)
 template <int NR, int NT>
-int dispatch_bwd_split(int H, int kind, const PersistArgs& a, hipStream_t stream) {
-  if (kind == 2) {
-    if constexpr (NT == 3) {
-      if (H == 640) return launch_bwd_rs640<NR>(a, stream);
-      if (H == 320) return launch_bwd_rs<320, NR, 3>(a, stream);
-    }
-    return H == 512 ? launch_bwd_rs<512, NR, NT>(a, stream) : H == 256 ? launch_bwd_rs<256, NR, NT>(a, stream)
-                                                            : launch_bwd_rs<128, NR, NT>(a, stream);
+int dispatch_bwd_terms(int H, int kind, const PersistArgs& a, hipStream_t stream) {
+  auto gathered = [&](auto w) {
+    constexpr int PH = decltype(w)::value;
+    return launch_persist<lstm_persist_bwd_kernel<PH, NR, NT, false>, lstm_persist_bwd_kernel<PH, NR, NT, true>>(a, stream);
+  };
+  if constexpr (NT == 1) {
+    return with_width<128, 256, 320, 512>(H, gathered);
+  } else {
+    auto exchanged = [&](auto w) {
+      constexpr int PH = decltype(w)::value;
+      if constexpr (PH == 640)
+        return launch_persist<lstm_persist_bwd_rs640_kernel<NR, false>, lstm_persist_bwd_rs640_kernel<NR, true>>(a, stream);
+      else
+        return launch_persist<lstm_persist_bwd_rs_kernel<PH, NR, NT, false>, lstm_persist_bwd_rs_kernel<PH, NR, NT, true>>(a, stream);
+    };
+    if constexpr (NT == 3) return kind == 2 ? with_width<128, 256, 320, 512, 640>(H, exchanged) : with_width<128, 256, 320>(H, gathered);
+    else return kind == 2 ? with_width<128, 256, 512>(H, exchanged) : with_width<128, 256, 320, 512>(H, gathered);
   }
-  if constexpr (NT == 2) {
-    if (H == 512) return launch_bwd_bf3<512, NR, 2>(a, stream);
-  }
-  return H == 320 ? launch_bwd_bf3<320, NR, NT>(a, stream) : H == 256 ? launch_bwd_bf3<256, NR, NT>(a, stream)
-                                                           : launch_bwd_bf3<128, NR, NT>(a, stream);
 }
 template <int NR>
 int dispatch_bwd(int H, int arith, const PersistArgs& a, hipStream_t stream) {
   const int kind = bwd_kernel_kind(H, arith);
   if (kind < 0) return ASR_E_SHAPE;
-  if (kind == 0)
-    return H == 512 ? launch_bwd<512, NR>(a, stream) : H == 320 ? launch_bwd<320, NR>(a, stream)
-         : H == 256 ? launch_bwd<256, NR>(a, stream) : launch_bwd<128, NR>(a, stream);
-  return (arith & ASR_ARITH_MASK) == ASR_ARITH_BF16X6 ? dispatch_bwd_split<NR, 3>(H, kind, a, stream)
-                                                     : dispatch_bwd_split<NR, 2>(H, kind, a, stream);
+  if (kind == 0) return dispatch_bwd_terms<NR, 1>(H, kind, a, stream);
+  return (arith & ASR_ARITH_MASK) == ASR_ARITH_BF16X6 ? dispatch_bwd_terms<NR, 3>(H, kind, a, stream)
+                                                     : dispatch_bwd_terms<NR, 2>(H, kind, a, stream);
 }
 
 }  // namespace
@@ -2483,7 +2209,8 @@ extern "C" int asr_lstm_seq_fwd_persist(int T, int B, int nb, int H, int ndir, f
     a.dy = nullptr; a.yfwd = nullptr; a.dw = nullptr; a.db = nullptr; a.xch = (u64*)xch; a.ctrl = persist_launch_words(ctrl);
     int rc;
     if (nr == 16)
-      rc = (arith & ASR_ARITH_MASK) == ASR_ARITH_BF16X6 ? launch_fwd_bf3<512, 16, 3, 16>(a, stream) : launch_fwd_bf3<512, 16, 2, 16>(a, stream);
+      rc = (arith & ASR_ARITH_MASK) == ASR_ARITH_BF16X6 ? dispatch_fwd_split<16, 3, 16>(H, a, stream, false)
+                                                        : dispatch_fwd_split<16, 2, 16>(H, a, stream, false);
     else
       rc = nr == 4 ? dispatch_fwd<4>(H, arith, a, stream) : dispatch_fwd<PRG>(H, arith, a, stream);
     if (rc) return rc;

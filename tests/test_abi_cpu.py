@@ -40,6 +40,24 @@ def test_product_does_not_import_oracle():
             assert "oracle" not in src.replace("# oracle", ""), fn
 
 
+def test_every_persistent_lstm_kernel_gets_a_cu_to_itself():
+    """launch_persist (csrc/lstm_persist.hip) pads a kernel's own static LDS with dynamic LDS up to 82 KB: with the static
+    sizes the compiler gives (the lds_bytes column of tests/golden/isa_table.json, held to the build by test_isa_guard_cpu.py)
+    every instantiation asks for more than half of a CU's 160 KB - one workgroup per CU, 256 co-resident - and for no more
+    than a CU has."""
+    import json
+    src = open(os.path.join(ROOT, "semi-supervised-asr_amd", "csrc", "lstm_persist.hip")).read()
+    rule = src[src.index("int one_per_cu_pad("):src.index("int launch_persist(")]
+    assert "fa.sharedSizeBytes" in rule and "stat < 82 * 1024 ? (int)(82 * 1024 - stat) : 0" in rule, rule
+    with open(os.path.join(ROOT, "tests", "golden", "isa_table.json")) as f:
+        kernels = json.load(f)["lstm_persist.hip"]
+    assert len(kernels) > 100 and any(m["lds_bytes"] > 82 * 1024 for m in kernels.values())
+    for name, m in kernels.items():
+        stat = m["lds_bytes"]
+        pad = 82 * 1024 - stat if stat < 82 * 1024 else 0
+        assert 80 * 1024 < stat + pad <= 160 * 1024, (name, stat, pad)
+
+
 def test_persistent_kernels_come_back_after_a_probation(monkeypatch):
     """Host logic of hip_backend.disable_persistent / persistent_step_tick: an abort sends the process to the per-step
     kernels for PERSIST_RETRY_STEPS train steps, twice as long after every further abort; a permanent switch (several

@@ -888,6 +888,21 @@ def test_lstm_layer_packed_rows_persistent_kernels(ndir, B, T, H, sub, lens, ari
         _packed_lstm_case(ndir, B, T, H, sub, lens, persistent=True)
 
 
+@pytest.mark.parametrize("arith", ["bf16x3+gather", "bf16x6+gather"])
+@pytest.mark.parametrize("ndir,B,T,H,sub,lens", [(2, 7, 6, 128, 1, None), (1, 70, 4, 256, 2, None), (2, 48, 5, 320, 2, None),
+                                                  (2, 3, 4, 512, 2, [4, 2, 1])])
+def test_lstm_layer_packed_rows_gathered_split_backward(ndir, B, T, H, sub, lens, arith):
+    """The PACKED instantiations of the gathered-dG backward with split dh products (two and three terms), which only the
+    `+gather` flag reaches on packed rows: 4-row groups with an incomplete last one, 8-row groups in two launches with a
+    short last block, 10 units per CU, ragged lengths."""
+    _gpu()
+    import hip_backend as hb
+    if arith == "bf16x6+gather" and H == 512:
+        pytest.skip("the gathered-dG backward with three terms needs 171 KB of LDS at H = 512: the call declines")
+    with hb.arith(arith):
+        _packed_lstm_case(ndir, B, T, H, sub, lens, persistent=True)
+
+
 @pytest.mark.parametrize("persistent,H", [(False, 16), (True, 512)])
 def test_packed_rows_after_a_longer_batch_left_nan_in_the_shared_workspace(persistent, H):
     """The pooled LSTM workspace is shared by row CAPACITY, and the packed-row dW_hh product reads one row behind the matrix
@@ -923,8 +938,9 @@ def test_lstm_judge_width_packed_rows():
 @pytest.mark.parametrize("ndir,B,T,H", [(2, 32, 9, 512), (2, 7, 6, 128), (1, 40, 5, 256), (2, 12, 7, 320), (2, 64, 5, 512)])
 def test_lstm_persistent_other_arithmetics(ndir, B, T, H, arith):
     """The persistent LSTM kernels that are not the default stay selectable (the `arith` argument of the C ABI) and
-    correct: the exact-fp32 4x4x1 products of round 1, the two-term bf16x3 products of round 2, and the gathered-dG
-    backward with split dh products (the only three-term backward at H = 320; it does not exist at H = 512)."""
+    correct: the exact-fp32 4x4x1 products of round 1, the two-term bf16x3 products of round 2, and - behind `+gather` -
+    the split dh products of the gathered-dG backward.  That backward is one kernel, lstm_persist_bwd_kernel<H, NR, NT>:
+    NT = 1 is the f32 column, NT = 2 / 3 the two / three split terms (three terms do not exist at H = 512)."""
     _gpu()
     import hip_backend as hb
     if arith == "bf16x6+gather" and H == 512:
