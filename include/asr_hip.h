@@ -787,6 +787,84 @@ int asr_adam_clip_f32(int64_t n, float* p, const float* g, float* m, float* v, f
                       float weight_decay, float bias_c1, float bias_c2, const void* skip_if_nonzero, float* zero_word,
                       asr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Deterministic mode (csrc/reduce_det.hip).  Ten entries added to ABI version 8 WITHOUT a version change, like
+ * the beam and scoring entries: they are additive - no existing entry, structure or constant changes, and a caller that does
+ * not use them sees the library it saw before.  Every entry above that adds fp32 partial sums with
+ * atomics - a K split of asr_gemm_f32 / asr_gemm_skinny_f32, asr_colsum_f32, asr_embedding_grad_f32, the dfill of
+ * asr_rows_unpack_bwd_f32, asr_sumsq_f32 / asr_gather_sumsq_f32, the `total` of asr_label_logprob_fwd - gives results
+ * that differ in the last bits from run to run: the order of the adds is the order in which workgroups happen to arrive.
+ * The entries below compute the same quantities as functions of the inputs and the shapes ONLY.  There is no switch
+ * inside the library: a caller that wants reproducible results calls these instead (hip_backend.DETERMINISTIC routes the
+ * host code).  Workspaces are the caller's, like every other buffer; no entry waits for the host or fills memory.
+ * One scheme throughout: partial sums are written by their one owner with plain stores, a second launch adds them in index
+ * order.  No float atomics, in global memory or LDS.
+ *
+ *   asr_colsum_det_f32         replaces asr_colsum_f32.  Rows in chunks of 256 (N, ldx multiples of 4 and X 16-byte
+ *                              aligned: the float4 path) or 512 rows.  Column n of a chunk: row group r sums its rows
+ *                              m0 + r, m0 + r + G, ... in ascending order (G = 16 / 4 row groups), the groups are added
+ *                              (((l_0 + l_1) + l_2) + ...) (G = 16) resp. (l_0 + l_1) + (l_2 + l_3) (G = 4); the chunk sums
+ *                              are added in ascending chunk order; out = that, or out + that with accumulate.
+ *                              ws: ceil(M / 256) * N floats (not touched when M fits one chunk); ASR_E_ARG if smaller.
+ *   asr_gemm_det_f32           replaces asr_gemm_f32 wherever that would split K.  Arguments as asr_gemm_f32 plus the
+ *                              workspace.  K is cut into S ranges: S = split_k when split_k >= 1 (tests, measurements),
+ *                              else the library's rule, a function of M, N and K alone - 1 when K < 1 024 or the
+ *                              ceil(M / 128) ceil(N / 128) output tiles are 256 or more, else min(16, 256 / tiles,
+ *                              K / 512).  A range is ceil(K / S) long, rounded up to a multiple of 32 when that is at
+ *                              least 32; the last range takes what is left, and S becomes the number of ranges that exist.
+ *                              Slab s = op(A)[:, range s] op(B)[range s, :] is an UNSPLIT product (asr_gemm_f32 with
+ *                              split_k = 1, the ranges as its batch: stride = the range's offset in A and B, M N in ws; a
+ *                              shorter last range is a second launch), then one kernel forms
+ *                                C = (((ws[0] + ws[1]) + ...) + ws[S-1]) (+ bias) (+ C if accumulate) (relu)
+ *                              one rounded fp32 add per step, in exactly this order (bias, accumulate, relu: the order of
+ *                              the unsplit asr_gemm_f32 epilogue, so S = 1 and S > 1 are one function).  S = 1: asr_gemm_f32 with
+ *                              split_k = 1 and nothing else (ws may be NULL).  batch > 1 with S > 1: the products run one
+ *                              after the other through the same workspace.  ASR_GEMM_C_ZEROED is ignored.
+ *   asr_gemm_det_ws_bytes      the bytes asr_gemm_det_f32 needs for these arguments (0, or S M N 4), S and the range
+ *                              length; returns what the call would return before it launches (0, ASR_E_ARG, ASR_E_SHAPE -
+ *                              the refusals of asr_gemm_f32).  Pointers are looked at for NULL and alignment only.
+ *   asr_embedding_grad_det_f32 replaces asr_embedding_grad_f32 (same limits).  One owner per (token id v, 4 columns):
+ *                              a = 0; for r = 0 .. rows - 1 in order: a += grad[r] if tokens[r] == v; demb[v] += a.
+ *   asr_rows_fill_grad_det_f32 replaces the dfill half of asr_rows_unpack_bwd_f32 (call that with dfill = NULL, then this).
+ *                              Utterance b: frame lane f of FL = min(8, 512 / (C / 4)) sums dout * mask over the padded
+ *                              frames len + f, len + f + FL, ... in ascending order, the lanes are added
+ *                              ((l_0 + l_1) + ...); dfill[c] += ((p_0 + p_1) + ... + p_{B-1}) in ascending b, only where
+ *                              relu_of[c] > 0 when relu_of is given.  ws: B * C floats.
+ *   asr_sumsq_det_f32          replaces asr_sumsq_f32: out[0] = out[0] + sum(g^2).  min(1 024, ceil(n / 1 024)) workgroups
+ *                              store one partial each (a thread's elements in ascending order; lanes by the xor butterfly
+ *                              32, 16, .. 1; waves (w_0 + w_1) + (w_2 + w_3)); ONE workgroup of a second launch adds the
+ *                              partials the same way (thread t: partials t, t + 256, ...).  Adding to the word keeps the
+ *                              protocol of asr_adam_clip_f32's zero_word: no fill launch.  ws: ASR_SUMSQ_DET_WS_BYTES.
+ *   asr_gather_sumsq_det_f32   replaces asr_gather_sumsq_f32 (same jobs, chunks and copies): a partial per 8 192-element
+ *                              chunk, combined as above after each launch.  ws: sum_j ceil(count[j] / 8 192) floats.
+ *   asr_sum_det_f32            out[0] = out[0] + scale * sum_i x[i], one workgroup, order as the second launch above:
+ *                              the `total` of asr_label_logprob_fwd (call that with total = NULL, then this on its `out`
+ *                              with scale = total_scale).
+ *   asr_dec_step_bwd_det / asr_dec_seq_bwd_det   replace asr_dec_step_bwd / asr_dec_seq_bwd: the same kernels, the two
+ *                              skinny products that add into G without their K split (csrc/gemm.hip: skinny_kernel adds
+ *                              the slices with atomics).  The per-utterance partial sums of these kernels have one owner.
+ * ------------------------------------------------------------------------------------- */
+#define ASR_SUMSQ_DET_WS_BYTES 4096
+int asr_colsum_det_f32(int64_t M, int64_t N, const float* X, int64_t ldx, float* out, int accumulate, float* ws,
+                       int64_t ws_bytes, asr_stream_t stream);
+int asr_gemm_det_f32(int transA, int transB, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B,
+                     int64_t ldb, float* C, int64_t ldc, const float* bias, int relu, int accumulate, int batch, int64_t sA,
+                     int64_t sB, int64_t sC, int split_k, int arith, float* ws, int64_t ws_bytes, asr_stream_t stream);
+int asr_gemm_det_ws_bytes(int transA, int transB, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
+                          const float* B, int64_t ldb, const float* C, int64_t ldc, const float* bias, int relu,
+                          int accumulate, int batch, int64_t sA, int64_t sB, int64_t sC, int split_k, int arith,
+                          int64_t* ws_bytes, int* split, int64_t* k_range);
+int asr_embedding_grad_det_f32(int64_t rows, int E, int V, const long long* tokens, const float* grad, int64_t ldg,
+                               float* demb, asr_stream_t stream);
+int asr_rows_fill_grad_det_f32(int B, int T, int C, const float* dout, const int32_t* lens, const float* mask, uint64_t seed,
+                               float p, float* dfill, const float* relu_of, float* ws, int64_t ws_bytes, asr_stream_t stream);
+int asr_sumsq_det_f32(int64_t n, const float* g, float* out, float* ws, int64_t ws_bytes, asr_stream_t stream);
+int asr_gather_sumsq_det_f32(int njobs, const float* const* src, const int64_t* dst_offset, const int64_t* count, float* flat,
+                             float* sumsq, float* ws, int64_t ws_bytes, asr_stream_t stream);
+int asr_sum_det_f32(int64_t n, const float* x, float scale, float* out, asr_stream_t stream);
+int asr_dec_step_bwd_det(const asr_dec_bwd_t* p, int s, asr_stream_t stream);
+int asr_dec_seq_bwd_det(const asr_dec_bwd_t* p, int s_begin, int s_end, asr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

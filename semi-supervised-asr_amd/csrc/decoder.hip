@@ -14,6 +14,9 @@
 int asr_skinny_launch(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* Bt, int64_t ldb,
                       float* C, int64_t ldc, const float* bias, int accumulate, const float* mask, int64_t ldmask,
                       int64_t mask_from, hipStream_t stream);
+int asr_skinny_launch_ex(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* Bt, int64_t ldb,
+                         float* C, int64_t ldc, const float* bias, int accumulate, const float* mask, int64_t ldmask,
+                         int64_t mask_from, int may_split, hipStream_t stream);
 int asr_cell_fwd_launch(int B, int D, int KX, const float* Xs, const float* wcat, const float* bcat, float* gates,
                         const float* cprev, float* cout, float* zout, float* zout2, hipStream_t stream);
 int asr_cell_bwd_launch(int B, int D, int KX, const float* Gnext, const float* gates, const float* cst,
@@ -747,7 +750,9 @@ static int check_bwd(const asr_dec_bwd_t* q) {
   return 0;
 }
 
-static int dec_step_bwd_impl(const asr_dec_bwd_t* q, int s, hipStream_t stream) {
+// det: the two skinny products add to G without their K split (whose slices meet in atomics); every other sum of the step has
+// one owner (+=, plain stores) either way.
+static int dec_step_bwd_impl(const asr_dec_bwd_t* q, int s, hipStream_t stream, bool det = false) {
   const asr_dec_fwd_t* p = &q->f;
   const int B = p->B, nb = p->nb, Tp = p->Tp, A = p->A, D = p->D, O = p->O, E = p->E, C = p->C, K = p->K;
   const int KX = D + O + E, taps = 2 * K + 1;
@@ -782,7 +787,7 @@ static int dec_step_bwd_impl(const asr_dec_bwd_t* q, int s, hipStream_t stream) 
   // dz_s += dD W_dec
   int rc = 0;
   if (onlyb == 0 || onlyb == 4)
-  rc = asr_skinny_launch(nb, D, A, dDs, A, q->wdecT, A, Gn, KX, nullptr, 1, nullptr, 0, 0, stream);
+  rc = asr_skinny_launch_ex(nb, D, A, dDs, A, q->wdecT, A, Gn, KX, nullptr, 1, nullptr, 0, 0, det ? 0 : 1, stream);
   if (rc) return rc;
   float* dg = q->dgates + (int64_t)s * B * 4 * D;
   if (onlyb == 0 || onlyb == 5)
@@ -791,7 +796,7 @@ static int dec_step_bwd_impl(const asr_dec_bwd_t* q, int s, hipStream_t stream) 
   if (rc) return rc;
   const float* xm = p->xmask ? p->xmask + (int64_t)s * B * (O + E) : nullptr;
   if (!(onlyb == 0 || onlyb == 6)) return 0;
-  return asr_skinny_launch(nb, KX, 4 * D, dg, 4 * D, q->wcatT, 4 * D, Gs, KX, nullptr, 1, xm, O + E, D, stream);
+  return asr_skinny_launch_ex(nb, KX, 4 * D, dg, 4 * D, q->wcatT, 4 * D, Gs, KX, nullptr, 1, xm, O + E, D, det ? 0 : 1, stream);
 }
 
 extern "C" int asr_dec_step_bwd(const asr_dec_bwd_t* q, int s, asr_stream_t stream_) {
@@ -807,6 +812,25 @@ extern "C" int asr_dec_seq_bwd(const asr_dec_bwd_t* q, int s_begin, int s_end, a
   if (s_begin < 0 || s_end > q->f.L || s_begin > s_end) return ASR_E_ARG;
   for (int s = s_end - 1; s >= s_begin; --s) {
     rc = dec_step_bwd_impl(q, s, (hipStream_t)stream_);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+// asr_dec_step_bwd / asr_dec_seq_bwd with no float atomic anywhere (include/asr_hip.h, "Deterministic mode")
+extern "C" int asr_dec_step_bwd_det(const asr_dec_bwd_t* q, int s, asr_stream_t stream_) {
+  int rc = check_bwd(q);
+  if (rc) return rc;
+  if (s < 0 || s >= q->f.L) return ASR_E_ARG;
+  return dec_step_bwd_impl(q, s, (hipStream_t)stream_, true);
+}
+
+extern "C" int asr_dec_seq_bwd_det(const asr_dec_bwd_t* q, int s_begin, int s_end, asr_stream_t stream_) {
+  int rc = check_bwd(q);
+  if (rc) return rc;
+  if (s_begin < 0 || s_end > q->f.L || s_begin > s_end) return ASR_E_ARG;
+  for (int s = s_end - 1; s >= s_begin; --s) {
+    rc = dec_step_bwd_impl(q, s, (hipStream_t)stream_, true);
     if (rc) return rc;
   }
   return 0;

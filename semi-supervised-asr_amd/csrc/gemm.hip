@@ -2395,9 +2395,11 @@ extern "C" int asr_gemm_side_f32(int transA, int transB, int64_t M, int64_t N, i
   return 0;
 }
 
-int asr_skinny_launch(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* Bt, int64_t ldb,
-                      float* C, int64_t ldc, const float* bias, int accumulate, const float* mask, int64_t ldmask,
-                      int64_t mask_from, hipStream_t stream) {
+// may_split == 0 (the deterministic decoder backward, asr_dec_seq_bwd_det): never the K split below - one workgroup owns an
+// output element and adds its product to C with a plain store.
+int asr_skinny_launch_ex(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* Bt, int64_t ldb,
+                         float* C, int64_t ldc, const float* bias, int accumulate, const float* mask, int64_t ldmask,
+                         int64_t mask_from, int may_split, hipStream_t stream) {
   if (!A || !Bt || !C || M <= 0 || N <= 0 || K <= 0) return ASR_E_ARG;
   if (K % 16 || lda % 4 || ldb % 4) return ASR_E_SHAPE;
   if (!asr_aligned16(A) || !asr_aligned16(Bt)) return ASR_E_ALIGN;
@@ -2405,7 +2407,7 @@ int asr_skinny_launch(int64_t M, int64_t N, int64_t K, const float* A, int64_t l
   // long-K accumulate products (the decoder's dX = dgates Wcat, K = 4D) are split over K: the consumer is a later
   // launch, so partial sums can simply be added atomically into C
   int ksplit = 1;
-  if (accumulate && !bias && K >= 1024 && K % 64 == 0) {
+  if (may_split && accumulate && !bias && K >= 1024 && K % 64 == 0) {
     ksplit = (int)(K / 512);
     while ((K / 16) % ksplit) --ksplit;
   }
@@ -2418,6 +2420,12 @@ int asr_skinny_launch(int64_t M, int64_t N, int64_t K, const float* A, int64_t l
   }
   ASR_CHECK_LAUNCH();
   return 0;
+}
+
+int asr_skinny_launch(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* Bt, int64_t ldb,
+                      float* C, int64_t ldc, const float* bias, int accumulate, const float* mask, int64_t ldmask,
+                      int64_t mask_from, hipStream_t stream) {
+  return asr_skinny_launch_ex(M, N, K, A, lda, Bt, ldb, C, ldc, bias, accumulate, mask, ldmask, mask_from, 1, stream);
 }
 
 extern "C" int asr_gemm_skinny_f32(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* Bt,

@@ -26,6 +26,8 @@ EXPORTS = (
     "asr_beam_select_f32", "asr_beam_reorder_f32", "asr_beam_backtrack",
     "asr_lm_step_f32", "asr_beam_select_lm_f32", "asr_beam_reorder_lm_f32",
     "asr_edit_distance_i32",
+    "asr_colsum_det_f32", "asr_gemm_det_f32", "asr_gemm_det_ws_bytes", "asr_embedding_grad_det_f32", "asr_rows_fill_grad_det_f32",
+    "asr_sumsq_det_f32", "asr_gather_sumsq_det_f32", "asr_sum_det_f32", "asr_dec_step_bwd_det", "asr_dec_seq_bwd_det",
 )
 
 _lib = None
@@ -268,6 +270,18 @@ def load():
                                       ctypes.c_uint64, c_f, c_p]
     lib.asr_gemm_side_f32.argtypes = [c_i, c_i, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i, c_i64, c_i64, c_i64,
                                       c_i, ctypes.c_uint, c_p, c_p]
+    lib.asr_colsum_det_f32.argtypes = [c_i64, c_i64, c_p, c_i64, c_p, c_i, c_p, c_i64, c_p]
+    lib.asr_gemm_det_f32.argtypes = lib.asr_gemm_f32.argtypes[:-1] + [c_p, c_i64, c_p]
+    lib.asr_gemm_det_ws_bytes.argtypes = lib.asr_gemm_f32.argtypes[:-1] + [ctypes.POINTER(c_i64), ctypes.POINTER(c_i),
+                                                                            ctypes.POINTER(c_i64)]
+    lib.asr_embedding_grad_det_f32.argtypes = lib.asr_embedding_grad_f32.argtypes
+    lib.asr_rows_fill_grad_det_f32.argtypes = [c_i, c_i, c_i, c_p, c_p, c_p, ctypes.c_uint64, c_f, c_p, c_p, c_p, c_i64, c_p]
+    lib.asr_sumsq_det_f32.argtypes = [c_i64, c_p, c_p, c_p, c_i64, c_p]
+    lib.asr_gather_sumsq_det_f32.argtypes = [c_i, ctypes.POINTER(c_p), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_p, c_p, c_p,
+                                             c_i64, c_p]
+    lib.asr_sum_det_f32.argtypes = [c_i64, c_p, c_f, c_p, c_p]
+    lib.asr_dec_step_bwd_det.argtypes = lib.asr_dec_step_bwd.argtypes
+    lib.asr_dec_seq_bwd_det.argtypes = lib.asr_dec_seq_bwd.argtypes
     if lib.asr_abi_version() != ABI_VERSION:
         raise RuntimeError("libasr_hip.so ABI %d != expected %d" % (lib.asr_abi_version(), ABI_VERSION))
     _lib = lib
@@ -322,6 +336,54 @@ class arith(object):
     def __exit__(self, *exc):
         ARITH[0] = self.old
         return False
+
+
+# Deterministic mode (include/asr_hip.h "Deterministic mode"): with the cell set, every wrapper below whose
+# default entry adds fp32 partial sums with atomics calls the ordered entry of csrc/reduce_det.hip instead, the persistent
+# LSTM backward leaves dW_hh and the bias gradient to the caller's (ordered) product and column sum, the decoder backward
+# runs on the per-step kernels, and the side stream is not used (ops._SideStream.usable).  Off by default; env
+# ASR_DETERMINISTIC=1, config key `deterministic` (solver.py), `with hb.deterministic():`.  The library has no such state:
+# the mode is WHICH entry the host code calls.
+DETERMINISTIC = [os.environ.get("ASR_DETERMINISTIC", "0") == "1"]
+
+
+def is_deterministic():
+    return DETERMINISTIC[0]
+
+
+class deterministic(object):
+    """Context manager: deterministic mode on (or off) for the calls inside."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.old = DETERMINISTIC[0]
+        DETERMINISTIC[0] = self.on
+        return self
+
+    def __exit__(self, *exc):
+        DETERMINISTIC[0] = self.old
+        return False
+
+
+_det_ws_cache = {}
+
+
+def det_workspace(device, nbytes):
+    """Scratch of the ordered reductions: one buffer per (device, stream) - calls on one stream are ordered, so they share it
+    - grown to the largest request so far and kept for the life of the process (tens of MB at cfg-2: the slabs of the widest
+    weight-gradient product).  HOST-SIDE STATE of this module, like the persistent kernels' scratch pair: the library itself
+    stays stateless, the buffer is an argument of every call.  Not the step arena: that is zeroed at every step, and these
+    bytes are written before they are read.  -> (pointer, bytes); (None, 0) for nbytes <= 0."""
+    if nbytes <= 0:
+        return None, 0
+    key = (_scratch_key(device), _raw_stream(_raw_device()) if _raw_stream is not None and _raw_device is not None
+           else torch.cuda.current_stream().cuda_stream)
+    buf = _det_ws_cache.get(key)
+    if buf is None or buf.numel() * 4 < nbytes:
+        buf = _det_ws_cache[key] = torch.empty((int(nbytes) + 3) // 4 + 1024, device=device, dtype=torch.float32)
+    return c_p(buf.data_ptr()), buf.numel() * 4
 
 
 def _dev(t, name="tensor"):
@@ -381,10 +443,15 @@ def gemm(A, B, trans_a=False, trans_b=False, bias=None, relu=False, out=None, ac
     code = (ARITH[0] if arith is None else _arith_code(arith)) | (C_ZEROED if out_zeroed else 0)
     if drop is not None:
         assert not accumulate and ldc == N
+        if DETERMINISTIC[0]:
+            split_k = 1                # (the dropout epilogue sits on forward products, whose K is small: unsplit)
         check(load().asr_gemm_drop_f32(int(trans_a), int(trans_b), M, N, K, ptr(A), lda, ptr(B), ldb, ptr(out), ldc,
                                        ptr(bias), int(relu), 0 if split_k is None else int(split_k), code, drop.seed,
                                        float(drop.p), stream()), "asr_gemm_drop_f32")
         return out
+    if DETERMINISTIC[0] and split_k != 1:
+        return _gemm_det((int(trans_a), int(trans_b), M, N, K, ptr(A), lda, ptr(B), ldb, ptr(out), ldc, ptr(bias), int(relu),
+                          int(accumulate), 1, 0, 0, 0, 0 if split_k is None else int(split_k), code), out)
     check(load().asr_gemm_f32(int(trans_a), int(trans_b), M, N, K, ptr(A), lda, ptr(B), ldb, ptr(out), ldc,
                               ptr(bias), int(relu), int(accumulate), 1, 0, 0, 0, 0 if split_k is None else int(split_k),
                               code, stream()), "asr_gemm_f32")
@@ -395,10 +462,42 @@ def gemm_batched(A, B, out, trans_a, trans_b, M, N, K, lda, ldb, ldc, batch, sA,
                  split_k=None, a_off=0, b_off=0):
     """Raw batched form (pointer + strides in elements; strides may be negative); tensors only provide the base pointers
     (a_off / b_off: element offsets of the first operand elements inside A / B)."""
-    check(load().asr_gemm_f32(int(trans_a), int(trans_b), M, N, K, _off(A, a_off), lda, _off(B, b_off), ldb, ptr(out), ldc,
-                              None, 0, int(accumulate), batch, sA, sB, sC, 0 if split_k is None else int(split_k),
-                              ARITH[0] if arith is None else _arith_code(arith), stream()), "asr_gemm_f32(batched)")
+    args = (int(trans_a), int(trans_b), M, N, K, _off(A, a_off), lda, _off(B, b_off), ldb, ptr(out), ldc,
+            None, 0, int(accumulate), batch, sA, sB, sC, 0 if split_k is None else int(split_k),
+            ARITH[0] if arith is None else _arith_code(arith))
+    if DETERMINISTIC[0] and split_k != 1:
+        return _gemm_det(args, out)
+    check(load().asr_gemm_f32(*args, stream()), "asr_gemm_f32(batched)")
     return out
+
+
+def _gemm_det(args, out):
+    """asr_gemm_det_f32 on the argument tuple of asr_gemm_f32 (without the stream): the K split as ordered slabs."""
+    lib = load()
+    need, S, kr = c_i64(0), c_i(0), c_i64(0)
+    check(lib.asr_gemm_det_ws_bytes(*args, ctypes.byref(need), ctypes.byref(S), ctypes.byref(kr)), "asr_gemm_det_ws_bytes")
+    ws, nbytes = det_workspace(out.device, need.value)
+    check(lib.asr_gemm_det_f32(*args, ws, nbytes, stream()), "asr_gemm_det_f32")
+    return out
+
+
+def gemm_det(A, B, trans_a=False, trans_b=False, bias=None, relu=False, out=None, accumulate=False, split=None, arith=None):
+    """gemm() through asr_gemm_det_f32 whatever the mode; split: the number of K ranges asked for (None: the library's rule)."""
+    with deterministic(True):
+        return gemm(A, B, trans_a, trans_b, bias, relu, out, accumulate, 0 if split is None else int(split), arith)
+
+
+def gemm_det_split(M, N, K, trans_a=False, trans_b=False, split=None, batch=1, arith=None, lda=None, ldb=None, ldc=None,
+                   accumulate=False, bias=False, relu=False):
+    """asr_gemm_det_ws_bytes on plain integers (no tensors, no GPU) -> dict(rc, bytes, split, k_range): the workspace
+    asr_gemm_det_f32 needs, the K ranges it forms and their length; rc != 0: the refusal, the rest missing."""
+    lda, ldb, ldc = lda or (M if trans_a else K), ldb or (K if trans_b else N), ldc or N
+    need, S, kr = c_i64(0), c_i(0), c_i64(0)
+    rc = load().asr_gemm_det_ws_bytes(int(trans_a), int(trans_b), M, N, K, 64, lda, 64, ldb, 64, ldc, 64 if bias else None,
+                                      int(relu), int(accumulate), batch, 0, 0, 0, 0 if split is None else int(split),
+                                      ARITH[0] if arith is None else _arith_code(arith), ctypes.byref(need), ctypes.byref(S),
+                                      ctypes.byref(kr))
+    return dict(rc=rc) if rc != 0 else dict(rc=0, bytes=need.value, split=S.value, k_range=kr.value)
 
 
 GEMM_FAMILIES = ("f32", "bf3", "bfw", "bfs", "bfk")          # ASR_GEMM_FAMILY_*
@@ -723,6 +822,10 @@ def colsum(X, out=None, accumulate=False):
     M, N = X.shape
     if out is None:
         out = torch.empty(N, device=X.device, dtype=torch.float32)
+    if DETERMINISTIC[0]:
+        ws, nbytes = det_workspace(X.device, ((M + 255) // 256) * N * 4 if M > 256 else 0)
+        check(load().asr_colsum_det_f32(M, N, ptr(X), ldx, ptr(out), int(accumulate), ws, nbytes, stream()), "asr_colsum_det_f32")
+        return out
     check(load().asr_colsum_f32(M, N, ptr(X), ldx, ptr(out), int(accumulate), stream()), "asr_colsum_f32")
     return out
 
@@ -901,16 +1004,33 @@ def cell_unpack(dwcat, db_il, D, O, E):
     return dw_ih, dw_hh, db, db2
 
 
+_warned_embedding = []
+
+
+def _embedding_layout_ok(tokens, grad, demb):
+    V, E = demb.shape
+    return not (grad.stride(1) != 1 or grad.shape != (tokens.numel(), E) or not tokens.is_contiguous() or not demb.is_contiguous()
+                or E % 4 or grad.stride(0) % 4 or V * E * 4 > 65536 or E // 4 > 256 or grad.data_ptr() % 16)
+
+
 def embedding_grad(tokens, grad, demb):
     """demb [V, E] += grad[r] for the token of row r (tokens [rows] int64, -1 = none; grad [rows, E] row-strided view).
     False when the layout is outside the kernel's (the caller then uses index_add_)."""
     V, E = demb.shape
     rows = tokens.numel()
+    if DETERMINISTIC[0] and not _embedding_layout_ok(tokens, grad, demb) and not _warned_embedding:
+        # the caller's own path is torch's index_add_, which adds with float atomics: say once that the mode ends here
+        import warnings
+        _warned_embedding.append(True)
+        warnings.warn("deterministic mode: the embedding gradient [%d x %d] is outside asr_embedding_grad_det_f32's layout "
+                      "(E %% 4, V * E * 4 <= 64 KB, 16-byte aligned rows); the caller's index_add_ is not run-to-run "
+                      "reproducible" % (V, E), RuntimeWarning, stacklevel=2)
     if (grad.stride(1) != 1 or grad.shape != (rows, E) or not tokens.is_contiguous() or not demb.is_contiguous()
             or E % 4 or grad.stride(0) % 4 or V * E * 4 > 65536 or E // 4 > 256 or grad.data_ptr() % 16):
         return False
-    check(load().asr_embedding_grad_f32(rows, E, V, c_p(tokens.data_ptr()), ptr(grad), grad.stride(0), ptr(demb), stream()),
-          "asr_embedding_grad_f32")
+    entry = load().asr_embedding_grad_det_f32 if DETERMINISTIC[0] else load().asr_embedding_grad_f32
+    check(entry(rows, E, V, c_p(tokens.data_ptr()), ptr(grad), grad.stride(0), ptr(demb), stream()),
+          "asr_embedding_grad_det_f32" if DETERMINISTIC[0] else "asr_embedding_grad_f32")
     return True
 
 
@@ -918,9 +1038,34 @@ def gather_sumsq(srcs, offsets, flat, sumsq=None):
     """flat[offsets[j] : + srcs[j].numel()] = srcs[j] (contiguous fp32 device tensors) in one launch; sumsq (1-element
     tensor or None) += the sum of their squares."""
     n = len(srcs)
+    if DETERMINISTIC[0]:
+        ws, nbytes = det_workspace(flat.device, 4 * sum((int(t.numel()) + 8191) // 8192 for t in srcs) if sumsq is not None else 0)
+        check(load().asr_gather_sumsq_det_f32(n, _ptr_array(srcs), (c_i64 * n)(*[int(o) for o in offsets]),
+                                              (c_i64 * n)(*[int(t.numel()) for t in srcs]), ptr(flat), ptr(sumsq), ws, nbytes,
+                                              stream()), "asr_gather_sumsq_det_f32")
+        return
     check(load().asr_gather_sumsq_f32(n, _ptr_array(srcs), (c_i64 * n)(*[int(o) for o in offsets]),
                                       (c_i64 * n)(*[int(t.numel()) for t in srcs]), ptr(flat), ptr(sumsq), stream()),
           "asr_gather_sumsq_f32")
+
+
+SUMSQ_DET_WS_BYTES = 4096          # ASR_SUMSQ_DET_WS_BYTES
+
+
+def sumsq(g, out):
+    """out[0] += sum(g^2) over a flat fp32 device tensor (asr_sumsq_f32; asr_sumsq_det_f32 in deterministic mode)."""
+    if DETERMINISTIC[0]:
+        ws, nbytes = det_workspace(g.device, SUMSQ_DET_WS_BYTES)
+        check(load().asr_sumsq_det_f32(g.numel(), ptr(g), ptr(out), ws, nbytes, stream()), "asr_sumsq_det_f32")
+    else:
+        check(load().asr_sumsq_f32(g.numel(), ptr(g), ptr(out), stream()), "asr_sumsq_f32")
+    return out
+
+
+def sum_det(x, out, scale=1.0):
+    """out[0] += scale * sum(x) in a fixed order (asr_sum_det_f32): x a contiguous fp32 device tensor."""
+    check(load().asr_sum_det_f32(x.numel(), ptr(x), float(scale), ptr(out), stream()), "asr_sum_det_f32")
+    return out
 
 
 def colsum_parts(parts):
@@ -958,6 +1103,9 @@ XCH_BYTES = 8 * 2 * 32 * 32 * 8 * 20 * 4      # the largest user: exchanged dh p
 # or the launcher answered ASR_E_SHAPE = -2: unsupported sizes / not an 8 x 32-CU device).  Ops: lstm_fwd, lstm_bwd,
 # dec_fwd, dec_bwd, dec_free (free-running decode forward).  Tests assert on these so that a silent fallback cannot
 # pass for the fast path; `with require_persistent():` turns a fallback into an error.
+# "dec_bwd_det" counts decoder backward sequences of DETERMINISTIC mode (asr_dec_seq_bwd_det, or the per-step loop of the
+# smooth feedback): the per-step kernels by the mode's choice, so neither a "dec_bwd_persist" nor a "dec_bwd_step" record is
+# made and require_persistent() does not raise for them.
 import collections
 LAUNCHES = collections.Counter()
 _REQUIRE_PERSIST = [os.environ.get("ASR_REQUIRE_PERSIST", "0") != "0"]
@@ -1231,7 +1379,10 @@ def lstm_seq_bwd(gates, w_hhT, lens, dy, c, dcarry, y=None, dw_hh=None, db=None,
     if rows is not None:                                   # packed rows (see lstm_seq_fwd): dW_hh is always the caller's
         assert B == 1 and T == rows.R
         T, B = rows.T, rows.B
-    fuses = USE_PERSIST and rows is None and lib.asr_lstm_bwd_persist_fuses_dw(H, ar) == 1 and y is not None and dw_hh is not None
+    if DETERMINISTIC[0]:                                   # the fused dW_hh / db meet in atomics across the row groups: both are
+        db = None                                          # the caller's (ordered) product and column sum instead
+    fuses = (USE_PERSIST and rows is None and not DETERMINISTIC[0] and lib.asr_lstm_bwd_persist_fuses_dw(H, ar) == 1
+             and y is not None and dw_hh is not None)
     yk, dwk = (y, dw_hh) if fuses else (None, None)
     def persistent(entry, what, w):
         return persistent_ran(entry(T, B, B, H, ndir, ptr(gates), ptr(w), ptr(lens), rb, re, rh, ptr(dy), ptr(c), ptr(yk),
@@ -1265,6 +1416,9 @@ def att_step_fwd(fs, s):
 
 
 def dec_step_bwd(bs, s):
+    if DETERMINISTIC[0]:
+        check(load().asr_dec_step_bwd_det(ctypes.byref(bs), s, stream()), "asr_dec_step_bwd_det")
+        return
     check(load().asr_dec_step_bwd(ctypes.byref(bs), s, stream()), "asr_dec_step_bwd")
 
 
@@ -1358,6 +1512,12 @@ def dec_seq_bwd(buf, acc, with_dws, persistent, teacher):
     lib, L = load(), buf.L
     bs = buf.bwd_struct(acc=acc, with_dws=with_dws)
     done = False
+    if DETERMINISTIC[0]:
+        # the persistent backward adds its per-group partial sums of dgvec / dwatt / dconv with atomics: the per-step kernels
+        # (one owner per partial sum), their two skinny products unsplit.  Not a fallback: the mode's choice, counted apart
+        LAUNCHES["dec_bwd_det"] += 1
+        check(lib.asr_dec_seq_bwd_det(ctypes.byref(bs), 0, L, stream()), "asr_dec_seq_bwd_det")
+        return
     if USE_PERSIST_DEC_BWD and persistent:
         done = persistent_ran(lib.asr_dec_seq_bwd_persist(ctypes.byref(bs), _fptr(buf.Mf), *_scratch_ptrs(buf.X.device), stream()),
                               "asr_dec_seq_bwd_persist")
@@ -1374,7 +1534,7 @@ def dec_smooth_bwd(buf, acc, with_dws, w_out, emb, probs, scaling, dlog):
     B, L, DO, V = buf.B, buf.L, buf.dims["D"] + buf.dims["O"], w_out.shape[0]
     bs = buf.bwd_struct(acc=acc, with_dws=with_dws)
     done = False
-    if USE_PERSIST_DEC_BWD and L > 1:
+    if USE_PERSIST_DEC_BWD and L > 1 and not DETERMINISTIC[0]:
         # the whole free-running sequence in one launch: the feedback path (d(emb_s) -> logit_{s-1} -> [z, ctx]_{s-1})
         # is carried inside the persistent kernel (dec_persist.hip, template FB)
         dlfb = torch.zeros(L, B, V, device=dlog.device, dtype=torch.float32)
@@ -1383,7 +1543,10 @@ def dec_smooth_bwd(buf, acc, with_dws, w_out, emb, probs, scaling, dlog):
         done = persistent_ran(load().asr_dec_seq_bwd_persist_free(ctypes.byref(bs), ctypes.byref(fbs), _fptr(buf.Mf),
                                                                   *_scratch_ptrs(dlog.device), stream()),
                               "asr_dec_seq_bwd_persist_free")
-    count_path("dec_bwd", done, "free-running smooth: %s V=%d L=%d fused-feedback=True" % (dec_shape(buf), V, L))
+    if DETERMINISTIC[0]:
+        LAUNCHES["dec_bwd_det"] += 1
+    else:
+        count_path("dec_bwd", done, "free-running smooth: %s V=%d L=%d fused-feedback=True" % (dec_shape(buf), V, L))
     if done:
         return dlog.view(L, B, V) + dlfb
     # one kernel per step carries the embedding gradient back into logit_{s-1} and [z_{s-1}, c_{s-1}]
@@ -1481,8 +1644,13 @@ def rows_unpack_bwd(dout, rows, C, mask, want_fill, relu_of=None, dfill=None):
     elif dfill is None:
         dfill = torch.zeros(C, device=dout.device, dtype=torch.float32)
     seeded = isinstance(mask, SeededMask)
+    margs = (None if (mask is None or seeded) else ptr(mask), mask.seed if seeded else 0, mask.p if seeded else 0.0)
+    det = DETERMINISTIC[0] and dfill is not None
     check(load().asr_rows_unpack_bwd_f32(B, T, C, ptr(dout), ptr(rows.lens), ptr(rows.base), ptr(rows.ext), rows.ext_max,
-                                         None if (mask is None or seeded) else ptr(mask), mask.seed if seeded else 0,
-                                         mask.p if seeded else 0.0, ptr(drows), ptr(dfill), ptr(relu_of), stream()),
+                                         *margs, ptr(drows), None if det else ptr(dfill), ptr(relu_of), stream()),
           "asr_rows_unpack_bwd_f32")
+    if det:
+        ws, nbytes = det_workspace(dout.device, B * C * 4)
+        check(load().asr_rows_fill_grad_det_f32(B, T, C, ptr(dout), ptr(rows.lens), *margs, ptr(dfill), ptr(relu_of), ws, nbytes,
+                                                stream()), "asr_rows_fill_grad_det_f32")
     return drows, dfill

@@ -169,7 +169,7 @@ class _SideStream(object):
       flush()            in front of a recurrence: start what is queued, beside it.
       join_now()         flush + the wait at once (a node that consumes side results inside the pass: _LstmPack.backward).
     Outputs are zeroed on the main stream BEFORE defer() (the side products add into them with atomics).  Off: ASR_SIDE_GEMM=0, the
-    fp32-input MFMA arithmetic (no such kernel), gradients exchanged from inside the backward pass (dp_overlap: its hooks
+    fp32-input MFMA arithmetic (no such kernel), deterministic mode (hb.DETERMINISTIC), gradients exchanged from inside the backward pass (dp_overlap: its hooks
     read a gradient as soon as autograd has it).
       count_use(ctx, w) / may_defer(ctx, w)   a weight gradient handed back before its product exists (_Linear): see there."""
 
@@ -184,8 +184,10 @@ class _SideStream(object):
     def mask_for(self, nbatch):
         return hb.idle_xcd_mask(nbatch) if self.enabled else 0
 
-    def usable(self, mask):
-        return bool(mask) and self.enabled and (hb.current_arith() & 0xff) != hb.ARITH_F32
+    def usable(self, mask=0xff):
+        # (deterministic mode: the side products add their K slices with atomics, and a second stream is one more ordering
+        # freedom - every weight gradient is formed on the main stream)
+        return bool(mask) and self.enabled and not hb.is_deterministic() and (hb.current_arith() & 0xff) != hb.ARITH_F32
 
     def count_use(self, ctx, weight):
         """A forward use of `weight` that may send it a gradient: counted for as long as its node `ctx` lives - a graph whose
@@ -894,10 +896,13 @@ class _LabelLogProb(torch.autograd.Function):
         total = zeros_acc((1,), lg.device).view(()) if with_sum else None
         amax = torch.empty(lg.shape[:-1], device=lg.device, dtype=torch.long) if with_argmax else None
         dist = labeldist.contiguous() if labeldist is not None else None
+        det = total is not None and hb.is_deterministic()       # the kernel's own total is one atomic per block: summed behind it
         hb.check(hb.load().asr_label_logprob_fwd(rows, V, hb.ptr(lg), V, ctypes.c_void_p(idx.data_ptr()), hb.ptr(dist),
-                                                 float(ls_weight), hb.ptr(out), hb.ptr(total), float(sum_scale),
+                                                 float(ls_weight), hb.ptr(out), None if det else hb.ptr(total), float(sum_scale),
                                                  None if amax is None else ctypes.c_void_p(amax.data_ptr()), hb.stream()),
                  "asr_label_logprob_fwd")
+        if det:
+            hb.sum_det(out, total, sum_scale)
         ctx.save_for_backward(lg, idx, dist)
         ctx.ls, ctx.sum_scale = float(ls_weight), float(sum_scale)
         ctx.set_materialize_grads(False)

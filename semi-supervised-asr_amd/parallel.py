@@ -611,8 +611,7 @@ class FlatAdam(object):
         if clip is not None:
             if not self._norm_taken:                 # (else reduce() took the norm with the gather)
                 self._norm_word()
-                hb.check(lib.asr_sumsq_f32(n, hb.ptr(self.buf.flat_g), hb.ptr(self.gnorm_sq), hb.stream()),
-                         "asr_sumsq_f32")
+                hb.sumsq(self.buf.flat_g[:n], self.gnorm_sq)      # (asr_sumsq_det_f32 in deterministic mode)
             self._norm_taken = False
             k = (self._applies - 1) & 1
             nxt = hb.ptr(self.gnorm_pair[1 - k:2 - k])

@@ -198,6 +198,14 @@ class Solver(object):
         # workgroups back until its bounded spins expire (every rank then repeats the step off the persistent kernels).
         # bench.py measures it as a labelled sub-object; turn it on here once a multi-GPU run has shown the latch stays clear.
         overlap = bool(cfg.get("dp_overlap", False))
+        # `deterministic` (not a reference key; default false, env ASR_DETERMINISTIC=1): every train step of this Solver runs
+        # in hip_backend's deterministic mode - ordered reductions in place of the fp32 atomics, no side stream:
+        # two runs from the same state and seeds give the same bits.  One process; with several ranks it covers each rank's
+        # own computation, not the collective.  The bucketed exchange reads gradients from inside the backward pass: refused.
+        self.deterministic = bool(cfg.get("deterministic", hb.DETERMINISTIC[0]))
+        if self.deterministic and overlap:
+            raise ValueError("`deterministic` and `dp_overlap` exclude each other: the bucketed all-reduce is issued from "
+                             "inside the backward pass, in an order of its own")
         # `persist_retry_steps` (not a reference key): train steps on the per-step kernels after an abort of the persistent
         # ones before they are tried again (hip_backend.PERSIST_RETRY_STEPS: 200, doubling per abort; 0: never)
         if "persist_retry_steps" in cfg:
@@ -415,8 +423,8 @@ class Solver(object):
         dev0 = opt.buf.flat_g.device
         if hb.persistent_step_tick() and self.rank == 0:     # the end of a probation after an abort (hb.PERSIST_RETRY_STEPS)
             print("persistent kernels: trying them again after %d abort(s)" % hb.persistent_probation()[0])
-        with ops.step_arena(dev0):       # every zero-initialised accumulator of the step comes out of one buffer, one fill
-            return self._step_inner(make_local, opt, n_scalars)
+        with hb.deterministic(self.deterministic), ops.step_arena(dev0):   # every zero-initialised accumulator of the step
+            return self._step_inner(make_local, opt, n_scalars)           # comes out of one buffer, one fill
 
     def _step_inner(self, make_local, opt, n_scalars):
         depth = min(int(self.config.get("pipeline_steps", self.PIPELINE_STEPS)), self.PINNED_ROWS - 2)   # one landing row each
@@ -569,7 +577,7 @@ class Solver(object):
             # this file - the input noise has a stream of its own, feed.DeviceFeed - but a caller may make some) are not
             # part of a step and must not shift the teacher-forcing draws of the repeats
             np.random.set_state(rec["rng"])
-            with ops.step_arena(dev):
+            with hb.deterministic(self.deterministic), ops.step_arena(dev):
                 loss, scalars = rec["make_local"]()
                 rec["opt"].zero_grad()
                 loss.backward()
