@@ -137,20 +137,12 @@ __device__ __forceinline__ void skinny_fetch(SkinnyRegs<MT>& rg, int i0, int nmi
 #pragma unroll
   for (int u = 0; u < SK_GROUP; ++u) {
     int i = i0 + u < nmine ? i0 + u : nmine - 1;
-#ifndef ASR_NO_ROTATE
     i += cbase;                       // per-workgroup rotation of the K traversal (cbase < nmine):
     i = i < nmine ? i : i - nmine;    // all workgroups share operand A; staggering avoids L2-channel hot spots
-#endif
     const int k0 = ((wave + NW * i) << 4) + (q << 2);
-#ifdef ASR_ABLATE_NOLOAD
-    rg.b[u] = make_float4(k0 * 1e-9f, 1.f, 2.f, 3.f);
-#pragma unroll
-    for (int m = 0; m < MT; ++m) rg.a[u][m] = make_float4(1.f, k0 * 1e-9f, 2.f, 3.f);
-#else
     rg.b[u] = *reinterpret_cast<const float4*>(brow + k0);
 #pragma unroll
     for (int m = 0; m < MT; ++m) rg.a[u][m] = *reinterpret_cast<const float4*>(A + arow[m] * lda + k0);
-#endif
   }
 }
 
@@ -160,11 +152,6 @@ __device__ __forceinline__ void skinny_mma(const SkinnyRegs<MT>& rg, int i0, int
   for (int u = 0; u < SK_GROUP; ++u) {
     float4 b = rg.b[u];
     if (!FULL && i0 + u >= nmine) b = make_float4(0.f, 0.f, 0.f, 0.f);
-#ifdef ASR_ABLATE_NOMMA
-#pragma unroll
-    for (int m = 0; m < MT; ++m) { acc[m][0] += rg.a[u][m].x * b.x + rg.a[u][m].y * b.y + rg.a[u][m].z * b.z + rg.a[u][m].w * b.w; }
-    continue;
-#endif
     // alternate the accumulators so consecutive MFMAs are independent (40-cycle dependent latency)
 #pragma unroll
     for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(rg.a[u][m].x, b.x, acc[m], 0, 0, 0);

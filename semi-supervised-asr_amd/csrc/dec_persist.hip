@@ -34,13 +34,6 @@
 #define DP_MARK(k) do {} while (0)
 #endif
 
-#ifndef ASR_DP_ABL
-#define ASR_DP_ABL 0
-#endif
-#ifndef ASR_DP_FULL
-#define ASR_DP_FULL false
-#endif
-
 namespace {
 
 constexpr int DP_NT = 512;          // 8 waves
@@ -316,7 +309,7 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_fwd_kernel(DecPersistArgs a
             const int row = (2 * id) / OO, o = 2 * id - row * OO;
             p[i] = reinterpret_cast<const u64*>(ux + ((2 * id < RG * OO) ? row * 512 + o : 0));
           }
-          poll_pairs<NC, ASR_DP_FULL>(p, tag_bit_of_step(s - 1), v, a.ctrl, aborted, 16u, spin_limit);
+          poll_pairs<NC>(p, tag_bit_of_step(s - 1), v, a.ctrl, aborted, 16u, spin_limit);
 #pragma unroll
           for (int i = 0; i < NC; ++i) {
             const int id = tid_ + DP_NT * i;
@@ -478,7 +471,7 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_fwd_kernel(DecPersistArgs a
       f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f}, accb = (f32x4){0.f, 0.f, 0.f, 0.f};
       const float* xr = xs + (lane_ & 3) * XS + wave * KXW;
 #pragma unroll
-      for (int k4 = 0; k4 < ((ASR_DP_ABL & 2) ? 1 : KXW / 4); ++k4) {
+      for (int k4 = 0; k4 < KXW / 4; ++k4) {
         const float4 b = *reinterpret_cast<const float4*>(xr + 4 * k4);
         acc = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * k4], b.x, acc, 0, 0, 0);
         accb = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * k4 + 1], b.y, accb, 0, 0, 0);
@@ -507,7 +500,7 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_fwd_kernel(DecPersistArgs a
       float zn = go * asr_fast_tanh(cn);
       if (aborted || abort_seen != 0u) zn = __builtin_nanf("");
       c_prev = cn;
-      if (pb_ok_ && !(ASR_DP_ABL & 32)) {
+      if (pb_ok_) {
         *reinterpret_cast<float4*>(a.gates + ((int64_t)s * B + pb_) * 4 * DD + punit_ * 4) = make_float4(gi, gf, gg, go);
         a.cstate[((int64_t)s * B + pb_) * DD + punit_] = cn;
         a.X[((int64_t)(s + 1) * B + pb_) * KX + punit_] = zn;
@@ -523,7 +516,7 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_fwd_kernel(DecPersistArgs a
       const int r = lane_ & 15, q = lane_ >> 4;
       const float* ap = wp + aq * DP_FPC + r + q;
       const float* bp = Fs + (r < FROWS ? r : FROWS - 1) * DP_TAPS4 + q;      // rows >= C are zero
-      for (int j = 4 * wave; j < ((ASR_DP_ABL & 8) ? 4 : taps4); j += 32) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[j], bp[j], acc, 0, 0, 0);
+      for (int j = 4 * wave; j < taps4; j += 32) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[j], bp[j], acc, 0, 0, 0);
 #pragma unroll
       for (int i = 0; i < 4; ++i) cred[(wave * 16 + 4 * q + i) * 17 + r] = acc[i];
     }
@@ -619,7 +612,7 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_fwd_kernel(DecPersistArgs a
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
         const int tile = wave + 8 * it;
-        if (FPT * tile < TpP && !(ASR_DP_ABL & 4)) {                      // wave-uniform
+        if (FPT * tile < TpP) {                      // wave-uniform
           f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
           const float* fa = fs + ((m % RG) * 16 + sq_) * TPM + FPT * tile + m / RG;
 #pragma unroll
@@ -632,7 +625,7 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_fwd_kernel(DecPersistArgs a
             pe[i] = sc_ok_ ? gv * sv[i] : 0.f;
           }
           // uniform row bases + one 32-bit lane offset per pair (no 64-bit index math per element)
-          if (sc_ok_ && !(ASR_DP_ABL & 16)) {
+          if (sc_ok_) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
               const int ri = (4 * sq_ + i) % RG, ti = FPT * tile + (4 * sq_ + i) / RG;
@@ -662,7 +655,7 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_fwd_kernel(DecPersistArgs a
 #pragma unroll
         for (int i = 0; i < 4; ++i)
           p[i] = reinterpret_cast<const u64*>(ex + (4 * wave + i) * 4 * TPM + (ok ? 2 * t2 : 0));
-        poll_pairs<4, ASR_DP_FULL>(p, bit, v, a.ctrl, aborted, 14u, spin_limit);
+        poll_pairs<4>(p, bit, v, a.ctrl, aborted, 14u, spin_limit);
         float e0 = 0.f, e1 = 0.f;
 #pragma unroll
         for (int i = 0; i < 4; ++i) { e0 += pair_lo(v[i]); e1 += pair_hi(v[i]); }
@@ -801,7 +794,8 @@ struct DecPersistBwdArgs {
   const float *Q, *wcatT, *wdecT, *convw, *watt, *gvec, *w0, *xmask;
   const float *gates, *cstate, *S, *fconv, *ws, *Mf, *dws;
   float *G, *dgates, *dD, *dP, *dgvec_part, *dwatt_part, *dconv_part;
-  float* dbg;          // measurement builds only (ASR_DP_DEBUG): d(conv features) of the last step, [B][C][Tp]
+  float* dbg;          // unused (a former debug dump wrote here); left in place: without it the kernel arguments move and
+                       // hipcc allocates the scalar registers of every dec_persist_bwd_kernel differently (profiles/ablation_strip_isa.txt)
   float* xch;
   unsigned* ctrl;
   // smooth-embedding feedback (kernel template FB): emb_s = softmax(fb_scale * logit_{s-1}) @ emb couples step s to the
@@ -1014,8 +1008,7 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_bwd_kernel(DecPersistBwdArg
   float ct = 0.f, cp = 0.f, gz = 0.f, gc = 0.f, xm = 1.f;
   // forward data of step s (no dependence on the recurrence), issued ~one iteration before use.  Indices are derived
   // from an opaque copy of the thread id (see the forward kernel) and addresses are uniform base + 32-bit lane offset.
-  auto prefetchA = [&](int s_, int zq) {
-    const int s = (ASR_DP_ABL & 64) ? (s_ > 0 ? 1 : 0) : s_;     // bit 64 (measurement): always the same, cached rows
+  auto prefetchA = [&](int s, int zq) {
     const int tidq = tid + zq, laneq = lane + zq;
     const int q4q = laneq >> 4, alq = laneq & 15;
     const int acolq = AU * slice + (alq < AU ? alq : 0);
@@ -1055,8 +1048,7 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_bwd_kernel(DecPersistBwdArg
       dwsreg = a.dws ? a.dws[((int64_t)s * B + abc) * Tp + (tq < Tp ? tq : Tp - 1)] : 0.f;
     }
   };
-  auto prefetchB = [&](int s_, int zq) {
-    const int s = (ASR_DP_ABL & 64) ? (s_ > 0 ? 1 : 0) : s_;
+  auto prefetchB = [&](int s, int zq) {
     const int tidq = tid + zq;
     const int pbq = r0 + (tidq & 3);
     const int pbcq = pbq < nb ? pbq : r0;
@@ -1133,9 +1125,6 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_bwd_kernel(DecPersistBwdArg
       acc += __shfl_xor(acc, 16, 64);
       const int t = 16 * aq + tl;
       if (op == 0 && t < TpP) word_store(xg + BX_W + (slot * 4 + ar) * TPM + t, t < Tp ? acc + dwext[tl] + dwsreg : 0.f, bit);
-#ifdef ASR_DP_DEBUG
-      if (op == 0 && t < Tp && n == 1 && ab_ok) a.dbg[(int64_t)3 * B * C * Tp + (int64_t)ab * Tp + t] = dwext[tl];
-#endif
     }
     DP_MARK(2);
     // ------------------------------------------------------------ (c) dw_raw of the 4 rows -> softmax backward
@@ -1172,7 +1161,7 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_bwd_kernel(DecPersistBwdArg
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
         const int tile = wave + 8 * it;
-        if (FPT * tile < TpP && !(ASR_DP_ABL & 256)) {              // bit 256 (measurement): no score backward
+        if (FPT * tile < TpP) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             // pair 4 q4 + i of the tile: row ri (a compile-time constant: 4 q4 is a multiple of RG), frame t
@@ -1205,7 +1194,7 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_bwd_kernel(DecPersistBwdArg
       for (int w2 = 0; w2 < 8; ++w2) v += dDp[(w2 * 4 + row) * 16 + al];
       const int b = r0 + row;
       if (al < AU) {
-        if (row < RG && b < nb && !(ASR_DP_ABL & 2048)) a.dD[((int64_t)s * B + b) * AA + AU * slice + al] = v;
+        if (row < RG && b < nb) a.dD[((int64_t)s * B + b) * AA + AU * slice + al] = v;
         word_store(xg + BX_D + (slot * 4 + row) * 512 + AU * slice + al, v, bit);
       }
     }
@@ -1219,13 +1208,6 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_bwd_kernel(DecPersistBwdArg
         if (id < C * TpP) {
           const int c = (int)(((float)id + 0.5f) * rtp), t = id - c * TpP;
           if (t < Tp) dfh[c * DFS + K + t] = des[ar * TPM + t] * (ugs[c] - mreg[k]);
-#ifdef ASR_DP_DEBUG
-          if (t < Tp && n == 0 && aq == 0 && ab_ok) {
-            a.dbg[((int64_t)ab * C + c) * Tp + t] = des[ar * TPM + t] * (ugs[c] - mreg[k]);
-            a.dbg[(int64_t)B * C * Tp + ((int64_t)ab * C + c) * Tp + t] = mreg[k];
-            a.dbg[(int64_t)2 * B * C * Tp + ((int64_t)ab * C + c) * Tp + t] = des[ar * TPM + t];
-          }
-#endif
         }
       }
     }
@@ -1246,7 +1228,7 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_bwd_kernel(DecPersistBwdArg
         // round 1).  js = j + 4 >= 0 is the loop variable; taps with j + jj < 0 are masked.
         const float* ap = dfh + cc * DFS + 16 * aq + 4 * li + 2 * K + 4;
         const float* bp = Fs + cc * FSS + li - 4;
-        const int jend = (ASR_DP_ABL & 128) ? 1 : taps + 3 + 4;      // bit 128 (measurement): one trip of each Toeplitz product
+        const int jend = taps + 3 + 4;
         for (int j = wave; j < jend; j += 32) {      // 4 taps per trip: 8 LDS reads in flight, then 4 MFMAs
           float av[4], bv[4];
 #pragma unroll
@@ -1272,7 +1254,7 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_bwd_kernel(DecPersistBwdArg
         const float* bq = dfh + cc * DFS + K - li;
         const float* a0 = wph + 16 * aq + 4 * li;
         const bool two = 16 * (aq + PPR) < taps;
-        const int uend = (ASR_DP_ABL & 128) ? 1 : Tp + 3;
+        const int uend = Tp + 3;
         for (int u = wave; u < uend; u += 32) {
           float bv[4], a0v[4], a1v[4];
 #pragma unroll
@@ -1337,7 +1319,7 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_bwd_kernel(DecPersistBwdArg
       f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f}, accb = (f32x4){0.f, 0.f, 0.f, 0.f};   // even / odd k partials
       const float* dr = dDs + ((lane_ & 3) % RG) * DS + wave * AKW + (lane_ >> 4) * AQ;      // rows >= RG alias (results unused)
 #pragma unroll
-      for (int q = 0; q < ((ASR_DP_ABL & 1024) ? 2 : AQ); q += 2) {      // bit 1024 (measurement): one pair of the dz product
+      for (int q = 0; q < AQ; q += 2) {
         acc = __builtin_amdgcn_mfma_f32_4x4x1f32(wd[q], dr[q], acc, 0, 0, 0);
         if (q + 1 < AQ) accb = __builtin_amdgcn_mfma_f32_4x4x1f32(wd[q + 1], dr[q + 1], accb, 0, 0, 0);
       }
@@ -1365,7 +1347,7 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_bwd_kernel(DecPersistBwdArg
       dcarry = dc * ga.y;
       if (aborted || abort_seen != 0u) da.x = __builtin_nanf("");
       const int un = DU * slice + ul, b = r0 + row;
-      if (row < RG && b < nb && !(ASR_DP_ABL & 2048)) *reinterpret_cast<float4*>(a.dgates + ((int64_t)s * B + b) * GK + un * 4) = da;   // bit 2048: no global stores
+      if (row < RG && b < nb) *reinterpret_cast<float4*>(a.dgates + ((int64_t)s * B + b) * GK + un * 4) = da;
       float* dst = xg + BX_G + (slot * 4 + row) * 2048 + un * 4;
       word_store(dst, da.x, bit); word_store(dst + 1, da.y, bit);
       word_store(dst + 2, da.z, bit); word_store(dst + 3, da.w, bit);
@@ -1423,7 +1405,7 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_bwd_kernel(DecPersistBwdArg
       DP_MARK(8);
       const float* gr = dgs + ((lane_ & 3) % RG) * GS + wave * GKW + ((lane_ >> 2) & 1) * GKS;   // rows >= RG alias
 #pragma unroll
-      for (int q4 = 0; q4 < ((ASR_DP_ABL & 512) ? 1 : GKS / 4); ++q4) {      // bit 512 (measurement): one quad of the dX product
+      for (int q4 = 0; q4 < GKS / 4; ++q4) {
         const float4 b = *reinterpret_cast<const float4*>(gr + 4 * q4);
         acc = __builtin_amdgcn_mfma_f32_4x4x1f32(wx[4 * q4], b.x, acc, 0, 0, 0);
         accb = __builtin_amdgcn_mfma_f32_4x4x1f32(wx[4 * q4 + 1], b.y, accb, 0, 0, 0);

@@ -121,9 +121,7 @@ __device__ __forceinline__ void score_compute(const ScoreRegs& r, const float* _
     }
     float4 sv;
     sv.x = fast_tanh(u.x); sv.y = fast_tanh(u.y); sv.z = fast_tanh(u.z); sv.w = fast_tanh(u.w);
-#if !(defined(ASR_ABL) && (ASR_ABL & 8))
     if (tw + i < Tp) *reinterpret_cast<float4*>(S + ((int64_t)b * Tp + tw + i) * A + a) = sv;
-#endif
     part[i] += r.g.x * sv.x + r.g.y * sv.y + r.g.z * sv.z + r.g.w * sv.w;
   }
 }
@@ -175,9 +173,7 @@ __global__ __launch_bounds__(SC_NT) void att_score_fwd_kernel(int B, int Tp, int
       if (i < 16 * taps4) Fs[i] = (ch < C && j < taps) ? v[k] : 0.f;
     }
   }
-#if !(defined(ASR_ABL) && (ASR_ABL & 1))
   stage_copy<10, SC_NT>(Ut, wattT, A * C);
-#endif
   __syncthreads();
   // location conv f[tl][ch] = sum_j F[ch][j] wp[t0+tl+j] as a Toeplitz product on the f32 MFMA, K (taps) split
   // over the waves: A[row=tl][k=j] = wp[t0+tl+j], B[k=j][col=ch] = F[ch][j]; D: lane holds rows 4*(lane>>4)+i of
@@ -207,12 +203,8 @@ __global__ __launch_bounds__(SC_NT) void att_score_fwd_kernel(int B, int Tp, int
 #pragma unroll
   for (int i = 0; i < SC_FPW; ++i) part[i] = 0.f;
   const float* fs4 = fs + wave * SC_FPW * C;
-#if defined(ASR_ABL) && (ASR_ABL & 4)
-  part[0] = r0.p[0].x + r1.p[3].w + r0.d.x + r1.g.y;
-#else
   score_compute(r0, Ut, fs4, S, b, Tp, A, C, tw, lane * 4, part);
   score_compute(r1, Ut, fs4, S, b, Tp, A, C, tw, 256 + lane * 4, part);
-#endif
   for (int a0 = 512; a0 < A; a0 += 512) {           // attention dims beyond 512: same code, not prefetched
     score_load(r0, P, Dp, gvec, b, Tp, A, tw, a0 + lane * 4);
     score_load(r1, P, Dp, gvec, b, Tp, A, tw, a0 + 256 + lane * 4);
@@ -658,19 +650,11 @@ static int dec_step_fwd_impl(const asr_dec_fwd_t* p, int s, hipStream_t stream) 
   const bool drop = p->xmask != nullptr;
   if (drop && !p->Xd) return ASR_E_ARG;
   float* Xdn = drop ? p->Xd + (int64_t)(s + 1) * B * KX : nullptr;
-  int rc = 0;
-#ifdef ASR_ONLY
-  const int only = ASR_ONLY;
-#else
-  const int only = 0;
-#endif
-  if (only == 0 || only == 1)
-  rc = asr_cell_fwd_launch(nb, D, KX, drop ? p->Xd + (int64_t)s * B * KX : Xs, p->wcat, p->bcat,
+  int rc = asr_cell_fwd_launch(nb, D, KX, drop ? p->Xd + (int64_t)s * B * KX : Xs, p->wcat, p->bcat,
                                p->gates + (int64_t)s * B * 4 * D, s > 0 ? p->cstate + (int64_t)(s - 1) * B * D : nullptr,
                                p->cstate + (int64_t)s * B * D, Xn, Xdn, stream);
   if (rc) return rc;
   float* Dp = p->Dproj + (int64_t)s * B * A;
-  if (only == 0 || only == 2)
   rc = asr_skinny_launch(nb, A, D, Xn, KX, p->wdec, D, Dp, A, nullptr, 0, nullptr, 0, 0, stream);
   if (rc) return rc;
   const float* wprev = s > 0 ? p->ws + (int64_t)(s - 1) * B * Tp : p->w0;
@@ -678,12 +662,10 @@ static int dec_step_fwd_impl(const asr_dec_fwd_t* p, int s, hipStream_t stream) 
   const size_t lds1 = sizeof(float) * ((size_t)(FRAMES_PER_WG * ((Tp + FRAMES_PER_WG - 1) / FRAMES_PER_WG) + 2 * K + 4) +
                                        (size_t)16 * ((taps + 3) & ~3) + FRAMES_PER_WG * C + (size_t)C * A +
                                        (size_t)SC_WAVES * 16 * 17);
-  if (only == 0 || only == 3)
   hipLaunchKernelGGL(att_score_fwd_kernel, dim3((Tp + FRAMES_PER_WG - 1) / FRAMES_PER_WG, nb), dim3(SC_NT), lds1, stream,
                      B, Tp, A, C, K, p->P, Dp, wprev, p->convw, p->wattT, p->gvec, p->S + (int64_t)s * B * Tp * A,
                      p->fconv + (int64_t)s * B * C * Tp, p->energy + (int64_t)s * B * Tp);
   const size_t lds2 = sizeof(float) * ((size_t)((Tp + 3) & ~3) + 4 * 256);
-  if (only == 0 || only == 4)
   hipLaunchKernelGGL(att_softmax_ctx_fwd_kernel, dim3((O + 255) / 256, nb), dim3(256), lds2, stream, B, Tp, O,
                      p->scaling, p->energy + (int64_t)s * B * Tp, p->Q, p->bo, p->ws + (int64_t)s * B * Tp, Xn + D,
                      (int64_t)KX, (drop && s + 1 < p->L) ? Xdn + D : nullptr,
@@ -760,12 +742,6 @@ static int dec_step_bwd_impl(const asr_dec_bwd_t* q, int s, hipStream_t stream, 
   float* Gn = q->G + (int64_t)(s + 1) * B * KX;
   float* Gs = q->G + (int64_t)s * B * KX;
   const int tgrid = (Tp + FRAMES_PER_WG - 1) / FRAMES_PER_WG;
-#ifdef ASR_ONLYB
-  const int onlyb = ASR_ONLYB;
-#else
-  const int onlyb = 0;
-#endif
-  if (onlyb == 0 || onlyb == 1)
   hipLaunchKernelGGL(att_dw_kernel, dim3(tgrid, nb), dim3(256), 0, stream, B, Tp, O, C, p->Q, Gn + D, (int64_t)KX,
                      s + 1 < p->L ? q->dwext : nullptr, q->dws ? q->dws + (int64_t)s * B * Tp : nullptr, q->dwraw);
   const int TpP = (Tp + 3) & ~3;
@@ -773,29 +749,23 @@ static int dec_step_bwd_impl(const asr_dec_bwd_t* q, int s, hipStream_t stream, 
   const size_t lds2 = sizeof(float) * ((size_t)TpP + (size_t)16 * TpP + ATILE * 16 + (size_t)TpM * 65 +
                                        SC_WAVES * 64 * 2 + 2 * 64 * 17);
   float* dDs = q->dD + (int64_t)s * B * A;
-  if (onlyb == 0 || onlyb == 2)
   hipLaunchKernelGGL(att_score_bwd_kernel, dim3(ntile, nb), dim3(SC_NT), lds2, stream, B, Tp, A, C, p->scaling,
                      p->ws + (int64_t)s * B * Tp, q->dwraw, p->S + (int64_t)s * B * Tp * A,
                      p->fconv + (int64_t)s * B * C * Tp, p->watt, p->gvec, q->dP, dDs, q->dgvec_part, q->dwatt_part,
                      q->dfpart);
   const float* wprev = s > 0 ? p->ws + (int64_t)(s - 1) * B * Tp : p->w0;
   const size_t lds3 = sizeof(float) * ((size_t)TpP + (size_t)((Tp + 2 * K + 3) & ~3) + taps);
-  if (onlyb == 0 || onlyb == 3)
   hipLaunchKernelGGL(att_conv_bwd_kernel, dim3(C, nb), dim3(256), lds3, stream, B, Tp, C, K, ntile, q->dfpart, wprev,
                      p->convw, q->dwext, q->dconv_part);
   ASR_CHECK_LAUNCH();
   // dz_s += dD W_dec
-  int rc = 0;
-  if (onlyb == 0 || onlyb == 4)
-  rc = asr_skinny_launch_ex(nb, D, A, dDs, A, q->wdecT, A, Gn, KX, nullptr, 1, nullptr, 0, 0, det ? 0 : 1, stream);
+  int rc = asr_skinny_launch_ex(nb, D, A, dDs, A, q->wdecT, A, Gn, KX, nullptr, 1, nullptr, 0, 0, det ? 0 : 1, stream);
   if (rc) return rc;
   float* dg = q->dgates + (int64_t)s * B * 4 * D;
-  if (onlyb == 0 || onlyb == 5)
   rc = asr_cell_bwd_launch(nb, D, KX, Gn, p->gates + (int64_t)s * B * 4 * D, p->cstate + (int64_t)s * B * D,
                            s > 0 ? p->cstate + (int64_t)(s - 1) * B * D : nullptr, q->dcell, dg, stream);
   if (rc) return rc;
   const float* xm = p->xmask ? p->xmask + (int64_t)s * B * (O + E) : nullptr;
-  if (!(onlyb == 0 || onlyb == 6)) return 0;
   return asr_skinny_launch_ex(nb, KX, 4 * D, dg, 4 * D, q->wcatT, 4 * D, Gs, KX, nullptr, 1, xm, O + E, D, det ? 0 : 1, stream);
 }
 

@@ -5,31 +5,20 @@
 //   asr_colsum_f32      bias gradients.
 // Replaces the torch mm/addmm/bmm calls behind nn.Linear / nn.LSTM input projections on the
 // reference path (model.py:67-68,80,93-94,144,163,293 and their autograd backward).
-#include <cstdlib>
 #include <type_traits>
 #include "common.h"
 
-#ifndef ASR_GEMM_BF3_TOUCH      /* L2 warm-up distance of the split-bf16 kernel in K tiles (2, 4, 6, 10 measured within 5 %: tools/gemm_cold_sweep.py; the kernel is bound by operand traffic at 32 flop/byte per 128x128 tile, not by latency) */
-#define ASR_GEMM_BF3_TOUCH 2
-#endif
-#ifndef ASR_GB_ABL               /* measurement only: 1 no products, 2 no operand loads after the first tile, 4 no LDS staging, 8 no epilogue stores */
-#define ASR_GB_ABL 0
-#endif
-#ifndef ASR_GLDS_CLOBBER_M0
-#define ASR_GLDS_CLOBBER_M0 0
-#endif
-#ifndef ASR_GEMM_SETPRIO
-#define ASR_GEMM_SETPRIO 1
-#endif
 namespace {
 
 constexpr int BM = 128, BN = 128, BK = 32;
-#ifndef ASR_GEMM_SMALL_OCC      /* waves per SIMD the 64 x 64-tile kernel is compiled for (= workgroups per CU) */
-#define ASR_GEMM_SMALL_OCC 1      /* (3: 168 registers with 11-21 spilled, 4: 52-113 spilled; left to itself hipcc takes 195-229 = two workgroups per CU) */
-#endif
-#ifndef ASR_GEMM_TOUCH
-#define ASR_GEMM_TOUCH 2      /* L2 warm-up distance in K tiles (0 = off); 2 measured best of 2,3,5,8 */
-#endif
+constexpr int ASR_GEMM_TOUCH = 2;         // L2 warm-up distance in K tiles (0 = off); 2 measured best of 2,3,5,8
+// L2 warm-up distance of the split-bf16 kernel in K tiles (2, 4, 6, 10 measured within 5 %, DESIGN_HISTORY 6: the kernel is
+// bound by operand traffic at 32 flop/byte per 128x128 tile, not by latency)
+constexpr int ASR_GEMM_BF3_TOUCH = 2;
+constexpr int ASR_GEMM_SETPRIO = 1;       // raise the wave priority over the MFMA block of the transA shapes (gemm_f32_kernel)
+// waves per SIMD the 64 x 64-tile kernel is compiled for (= workgroups per CU); 3: 168 registers with 11-21 spilled,
+// 4: 52-113 spilled; left to itself hipcc takes 195-229 = two workgroups per CU
+constexpr int ASR_GEMM_SMALL_OCC = 1;
 
 // A "stored matrix" view: element (r, c) at p[r*ld + c], valid for r < R, c < Cn.
 struct MatView {
@@ -115,9 +104,7 @@ struct GemmArgs {
 // panels per K tile in the XCD's L2 instead of 33.  The operand fetch of the split-bf16 kernels runs at what ONE CU can
 // pull through its memory path (~11 B / cycle from the Infinity Cache, ~30 from L2; they need 16 - 21 B / cycle), so L2
 // hits are what the main loop's speed is made of.
-#ifndef ASR_GEMM_GM
-#define ASR_GEMM_GM 4
-#endif
+constexpr int ASR_GEMM_GM = 4;
 __device__ __forceinline__ void tile_coords(int tid, int tiles_m, int tiles_n, int gm_, int& tm, int& tn) {
   const int per = gm_ * tiles_n;
   const int grp = tid / per, in = tid - grp * per;
@@ -225,10 +212,10 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
     tile_store<BKC>(Bs, rb);
     __syncthreads();
     if (kt + 1 < kt_end) fetch(kt + 1);
-#if ASR_GEMM_TOUCH
-    asm volatile("" ::"v"(touched));                 // retire the previous touch (issued one tile ago)
-    if (do_touch && kt + ASR_GEMM_TOUCH < kt_end) touch_tile(kt + ASR_GEMM_TOUCH);
-#endif
+    if constexpr (ASR_GEMM_TOUCH != 0) {
+      asm volatile("" ::"v"(touched));               // retire the previous touch (issued one tile ago)
+      if (do_touch && kt + ASR_GEMM_TOUCH < kt_end) touch_tile(kt + ASR_GEMM_TOUCH);
+    }
     const float* ap = As + kh * SA + wm * 64 + l31;
     const float* bp = Bs + kh * SB + wn * 64 + l31;
     // transA (weight-gradient) shapes: raise the wave priority over the MFMA block, so that the co-resident
@@ -540,7 +527,7 @@ __global__ __launch_bounds__(256, QUEUE ? 4 : (TS == 64 ? ASR_GEMM_SMALL_OCC : 1
   const int ao = (wm * (TS / 2) + l31) * BS + 8 * kh, bo = (wn * (TS / 2) + l31) * BS + 8 * kh;
   auto multiply = [&]() {
 #pragma unroll
-    for (int ks = 0; ks < ((ASR_GB_ABL & 1) ? 0 : BK / 16); ++ks) {
+    for (int ks = 0; ks < BK / 16; ++ks) {
       gu32x4 af[NB][NT], bf[NB][NT];
 #pragma unroll
       for (int i = 0; i < NB; ++i)
@@ -616,24 +603,14 @@ __global__ __launch_bounds__(256, QUEUE ? 4 : (TS == 64 ? ASR_GEMM_SMALL_OCC : 1
   } else if (kt_begin < kt_fast_end) {
     fetch_fast(kt_begin);
     for (int64_t kt = kt_begin; kt < kt_fast_end; ++kt) {
-#if ASR_GB_ABL & 4
-      if (kt == kt_begin) {
-        tile_store_bf3<AKC, NT, TS>(Ai, ra);
-        tile_store_bf3<BKC, NT, TS>(Bi, rb);
-      } else {
-#pragma unroll
-        for (int i = 0; i < NP; ++i) asm volatile("" ::"v"(ra[i].x), "v"(ra[i].y), "v"(ra[i].z), "v"(ra[i].w), "v"(rb[i].x), "v"(rb[i].y), "v"(rb[i].z), "v"(rb[i].w));
-      }
-#else
       tile_store_bf3<AKC, NT, TS>(Ai, ra);
       tile_store_bf3<BKC, NT, TS>(Bi, rb);
-#endif
       __syncthreads();
-      if (kt + 1 < kt_fast_end && !(ASR_GB_ABL & 2)) fetch_fast(kt + 1);
-#if ASR_GEMM_TOUCH
-      asm volatile("" ::"v"(touched));
-      if (do_touch && kt + ASR_GEMM_BF3_TOUCH < kt_end) touch_tile(kt + ASR_GEMM_BF3_TOUCH);
-#endif
+      if (kt + 1 < kt_fast_end) fetch_fast(kt + 1);
+      if constexpr (ASR_GEMM_TOUCH != 0) {
+        asm volatile("" ::"v"(touched));
+        if (do_touch && kt + ASR_GEMM_BF3_TOUCH < kt_end) touch_tile(kt + ASR_GEMM_BF3_TOUCH);
+      }
       multiply();
       __syncthreads();
     }
@@ -645,26 +622,15 @@ __global__ __launch_bounds__(256, QUEUE ? 4 : (TS == 64 ? ASR_GEMM_SMALL_OCC : 1
       tile_store_bf3<BKC, NT, TS>(Bi, rb);
       __syncthreads();
       if (kt + 1 < kt_end) fetch_guard(kt + 1);
-#if ASR_GEMM_TOUCH
-      asm volatile("" ::"v"(touched));
-      if (do_touch && kt + ASR_GEMM_BF3_TOUCH < kt_end) touch_tile(kt + ASR_GEMM_BF3_TOUCH);
-#endif
+      if constexpr (ASR_GEMM_TOUCH != 0) {
+        asm volatile("" ::"v"(touched));
+        if (do_touch && kt + ASR_GEMM_BF3_TOUCH < kt_end) touch_tile(kt + ASR_GEMM_BF3_TOUCH);
+      }
       multiply();
       __syncthreads();
     }
   }
 
-#if ASR_GB_ABL & 8   /* measurement: no epilogue stores (one lane keeps the accumulators alive) */
-  if (threadIdx.x + blockIdx.x + blockIdx.y != 0 || g.M != 1) {
-#pragma unroll
-    for (int i = 0; i < NB; ++i)
-#pragma unroll
-      for (int j = 0; j < NB; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) asm volatile("" ::"v"(acc[i][j][e]));
-    return;
-  }
-#endif
   // epilogue (as gemm_f32_kernel: the C/D lane map of the 32x32 MFMAs does not depend on the input type)
   if (m0 + BM <= g.M && n0 + BN <= g.N) {
     const unsigned ldc = (unsigned)g.ldc;
@@ -751,24 +717,12 @@ typedef __attribute__((address_space(3))) void* lds_vptr;
 // itself; no other VMEM load is outstanding while DMAs are.
 __device__ __forceinline__ void glds16(const float* src, float* lds_dst) {
   const unsigned dst = (unsigned)(uintptr_t)(lds_vptr)lds_dst;
-#if ASR_GLDS_CLOBBER_M0     /* measurement: m0 on the clobber list instead (hipcc warns: reserved register) */
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(dst) : "memory", "m0");
-#else
   unsigned keep;                                   // m0 is saved and restored: it may not appear in a clobber list
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-#endif
 }
 
-#ifndef ASR_GW_ABL      /* measurement only: 1 no DMA inside the stage loop, 2 no split arithmetic (raw bits as hi / lo), 4 no fragment reads after the prologue */
-#define ASR_GW_ABL 0
-#endif
 __device__ __forceinline__ void bf3w_split(const float (&v)[8], gu32x4& hi, gu32x4& lo) {
-#if ASR_GW_ABL & 2
-#pragma unroll
-  for (int p = 0; p < 4; ++p) { hi[p] = __float_as_uint(v[p]); lo[p] = __float_as_uint(v[4 + p]); }
-  return;
-#endif
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
     hi[p] = bf3g_hi2(v[2 * p], v[2 * p + 1]);
@@ -955,7 +909,7 @@ __global__ __launch_bounds__(512) void gemm_bf3w_kernel(GemmArgs g) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) BF3W(a0h[a], bh[P][j], acc[a][j]);
 #pragma unroll
-    for (int a = 0; a < 2; ++a) if (!(ASR_GW_ABL & 4) || st == 0) bf3w_frag<AKC, WM>(sa, arow + 32 * (2 + a), kq0s, kq1s, kfirst, a1h[a], a1l[a]);
+    for (int a = 0; a < 2; ++a) bf3w_frag<AKC, WM>(sa, arow + 32 * (2 + a), kq0s, kq1s, kfirst, a1h[a], a1l[a]);
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -976,7 +930,7 @@ __global__ __launch_bounds__(512) void gemm_bf3w_kernel(GemmArgs g) {
     }
     GW_MARK(3);
     // ---- H2
-    const bool dma = (FULL || st + 3 < S) && !(ASR_GW_ABL & 1);
+    const bool dma = FULL || st + 3 < S;
     float* sb = smem + buf * W_STAGE_FLOATS;           // stage st + 3 goes where stage st was
     const float* pa = basea + (st + 3) * stepa;
     const float* pb = baseb + (st + 3) * stepb;
@@ -988,7 +942,7 @@ __global__ __launch_bounds__(512) void gemm_bf3w_kernel(GemmArgs g) {
       glds16(pa + offa[0], sb + (4 * wave + 0) * 256);
       glds16(pa + offa[1], sb + (4 * wave + 1) * 256);
     }
-    if (next && (!(ASR_GW_ABL & 4) || st < 2)) {
+    if (next) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) bf3w_frag<BKC, WN>(sa1 + W_A_FLOATS, brow + 32 * j, kq0s, kq1s, kfirst, bh[1 - P][j], bl[1 - P][j]);
     }
@@ -1000,7 +954,7 @@ __global__ __launch_bounds__(512) void gemm_bf3w_kernel(GemmArgs g) {
       glds16(pa + offa[2], sb + (4 * wave + 2) * 256);
       glds16(pa + offa[3], sb + (4 * wave + 3) * 256);
     }
-    if (next && (!(ASR_GW_ABL & 4) || st < 2)) {
+    if (next) {
 #pragma unroll
       for (int a = 0; a < 2; ++a) bf3w_frag<AKC, WM>(sa1, arow + 32 * a, kq0s, kq1s, kfirst, a0h[a], a0l[a]);
     }
@@ -1333,18 +1287,6 @@ __global__ __launch_bounds__(512) void gemm_bf6w_kernel(GemmArgs g) {
 // stores), row-contiguous operands need a multiple of 4 rows: the wide kernels' conditions.
 constexpr int SM = 256, SN = 128, SK = 32;
 constexpr int SP_A = SM * SK, SP_B = SN * SK;          // bf16 elements of one image
-#ifndef ASR_GS_ABL      /* measurement only: 1 no products, 2 no split arithmetic / image writes after the prologue, 4 no operand loads after the prologue, 8 no epilogue stores */
-#define ASR_GS_ABL 0
-#endif
-#ifndef ASR_GS_PAT      /* filler pattern inside a slot (measurement) */
-#define ASR_GS_PAT 0
-#endif
-#ifndef ASR_GS_NOBAR    /* measurement only (wrong results): no barrier in the K loop */
-#define ASR_GS_NOBAR 0
-#endif
-#ifndef ASR_GS_SCHED    /* 1: pin the MFMA / filler interleave with sched_group_barrier */
-#define ASR_GS_SCHED 3
-#endif
 
 typedef unsigned gu32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) gu32x2* lds_u2ptr;
@@ -1359,18 +1301,8 @@ __device__ __forceinline__ P lds_at(unsigned a) { return (P)(uintptr_t)a; }
 template <int NT>
 __device__ __forceinline__ void bfs_write4(unsigned a, int plane, float x0, float x1, float x2, float x3) {
   unsigned p0[NT], p1[NT];
-#if ASR_GS_ABL & 32      /* measurement: no split arithmetic (raw bits as terms) */
-  p0[0] = __float_as_uint(x0); p0[1] = __float_as_uint(x1); p1[0] = __float_as_uint(x2); p1[1] = __float_as_uint(x3);
-  if constexpr (NT > 2) { p0[2] = p0[0] ^ p1[1]; p1[2] = p0[1] ^ p1[0]; }
-#else
   bfn_split2<NT>(x0, x1, p0);
   bfn_split2<NT>(x2, x3, p1);
-#endif
-#if ASR_GS_ABL & 16      /* measurement: no image writes (the split stays) */
-  asm volatile("" ::"v"(p0[0]), "v"(p0[1]), "v"(p1[0]), "v"(p1[1]));
-  if constexpr (NT > 2) asm volatile("" ::"v"(p0[2]), "v"(p1[2]));
-  return;
-#endif
   *lds_at<lds_u2ptr>(a) = gu32x2{p0[0], p1[0]};
   *lds_at<lds_u2ptr>(a + plane) = gu32x2{p0[1], p1[1]};
   if constexpr (NT > 2) *lds_at<lds_u2ptr>(a + 2 * plane) = gu32x2{p0[2], p1[2]};
@@ -1484,7 +1416,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bfs_kernel(GemmArgs g) {
   // load piece u (0-7: A, 8-11: B) of K tile st into register set Q
   auto load_piece = [&](auto qtag, auto utag, int st) __attribute__((always_inline)) {
     constexpr int Q = decltype(qtag)::value, U = decltype(utag)::value;
-    if (ASR_GS_ABL & 4) return;
     if constexpr (KT) {          // the last K tile reaches behind the operand: offset in the VGPR, where the range check sees it
       if constexpr (U < 8) RA[Q][U] = __builtin_amdgcn_raw_buffer_load_b128(rsA, offa[U] + (unsigned)(st * stepa), 0, 0);
       else RB[Q][U - 8] = __builtin_amdgcn_raw_buffer_load_b128(rsB, offb[U - 8] + (unsigned)(st * stepb), 0, 0);
@@ -1500,7 +1431,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bfs_kernel(GemmArgs g) {
 #define BFS_F(v_, e_) (kok ? __uint_as_float((v_)[e_]) : 0.f)
     constexpr bool isA = (U % 6) < 4;
     constexpr int idx = isA ? (U / 6) * 4 + (U % 6) : (U / 6) * 2 + (U % 6) - 4;      // A piece 0-7 / B piece 0-3
-    if (ASR_GS_ABL & 2) return;
     if constexpr (isA) {
       if constexpr (AKC) {
         const gu32x4 v = RA[Q][idx];
@@ -1565,7 +1495,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bfs_kernel(GemmArgs g) {
   auto products = [&](auto kstag, auto tptag) __attribute__((always_inline)) {
     constexpr int KS = decltype(kstag)::value, TP = decltype(tptag)::value;
     constexpr int o = TP == 0 ? 0 : TP < 3 ? 1 : 2, p = TP == 0 ? 0 : TP < 3 ? TP - 1 : TP - 3;
-    if (ASR_GS_ABL & 1) return;
     if constexpr (o < NT) {
       BFS(FA[KS][0][p], FB[KS][0][o - p], acc[0][0]); BFS(FA[KS][0][p], FB[KS][1][o - p], acc[0][1]);
       BFS(FA[KS][1][p], FB[KS][0][o - p], acc[1][0]); BFS(FA[KS][1][p], FB[KS][1][o - p], acc[1][1]);
@@ -1587,29 +1516,14 @@ __global__ __launch_bounds__(256, 1) void gemm_bfs_kernel(GemmArgs g) {
     if (do_rd) frag_read(KSN(), std::integral_constant<int, q_>(), rdtag);                               \
     if (do_wr) unit(UQT(), std::integral_constant<int, U0 + q_>(), wrtag, stu);                               \
     if (do_ld) reload(UQT(), std::integral_constant<int, U0 + q_>(), ld_st);                             \
-    if (ASR_GS_SCHED & 2) {                                                                              \
-      _Pragma("unroll") for (int m_ = 0; m_ < 8; ++m_) {                                                 \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                               \
-        if (ASR_GS_PAT == 0) {                                                                           \
-          if (m_ < 3) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                 \
-          __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);                                             \
-          if (m_ >= 5) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                                \
-        } else if (ASR_GS_PAT == 1) {                                                                    \
-          if (m_ < 3) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                 \
-          if (m_ < 6) __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);                                 \
-          if (m_ >= 5) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                                \
-        } else if (ASR_GS_PAT == 2) {                                                                    \
-          __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);                                             \
-        } else if (ASR_GS_PAT == 3) {                                                                    \
-          if (m_ == 0) __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);                                \
-          if (m_ < 3) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                 \
-          __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);                                             \
-          if (m_ >= 4 && m_ < 7) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                      \
-        }                                                                                                \
-      }                                                                                                  \
-      if (ASR_GS_PAT != 3) __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);                            \
+    _Pragma("unroll") for (int m_ = 0; m_ < 8; ++m_) {      /* MFMA / filler interleave of the slot, pinned */\
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                 \
+      if (m_ < 3) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                     \
+      __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);                                                 \
+      if (m_ >= 5) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                                    \
     }                                                                                                    \
-    if (ASR_GS_SCHED & 1) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);                                                   \
+    __builtin_amdgcn_sched_barrier(0);
     BFS_SLOT(0) BFS_SLOT(1) BFS_SLOT(2) BFS_SLOT(3) BFS_SLOT(4) BFS_SLOT(5)
 #undef BFS_SLOT
   };
@@ -1653,7 +1567,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bfs_kernel(GemmArgs g) {
     typedef std::integral_constant<int, 1 - P> PN;
     const bool n1 = FULL || st + 1 < S, n2 = FULL || st + 2 < S;
     half(I0(), PN(), I6(), PT(), true, PN(), n1, st + 1, st + 3, FULL || st + 3 < S);
-    if (n1 && !ASR_GS_NOBAR) barrier();
+    if (n1) barrier();
     half(I1(), PT(), I0(), PN(), n1, PT(), n2, st + 2, st + 4, FULL || st + 4 < S);
   };
   typedef std::integral_constant<bool, true> Full;
@@ -1669,17 +1583,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bfs_kernel(GemmArgs g) {
   }
 #undef BFS
 
-#if ASR_GS_ABL & 8
-  if (threadIdx.x + blockIdx.x + blockIdx.y != 0 || g.M != 1) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) asm volatile("" ::"v"(acc[i][j][e]));
-    return;
-  }
-#endif
   // ---- epilogue: lane owns column n, rows (e & 3) + 8 (e >> 2) + 4 kh of each 32 x 32 block
   const int64_t mrow0 = m0 + wm * 128, ncol0 = n0 + wn * 64;
   const unsigned ldc = (unsigned)g.ldc;
@@ -1749,9 +1652,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bfs_kernel(GemmArgs g) {
 // Workgroup w: XCD w % 8 = group of M tiles (tiles g, g + G, ...), w / G = column tile: the 32 column tiles that read one
 // A tile run on one XCD at about the same time (one HBM read per XCD).  Image rows are padded to 2 K + 16 bytes:
 // 11 r mod 16 is a bijection, so a fragment read's 16 lanes hit 16 different bank quads.
-#ifndef ASR_GK_ABL      /* measurement only: 1 no products, 2 no split / image writes in the loop, 8 no output stores */
-#define ASR_GK_ABL 0
-#endif
 template <int KS> struct BfkDims {
   static constexpr int K = 16 * KS, ROWB = 2 * K + 16, PLANE = 128 * ROWB, HP = K / 16;   // HP float4 pieces per thread and tile
 };
@@ -1826,7 +1726,6 @@ __global__ __launch_bounds__(512) void gemm_bfk_kernel(GemmArgs g, int groups) {
 #define BFK(a_, b_, c_) c_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(gbf16x8, a_), __builtin_bit_cast(gbf16x8, b_), c_, 0, 0, 0)
   auto products = [&](auto slottag, auto kstag, auto settag) __attribute__((always_inline)) {
     constexpr int SL = decltype(slottag)::value, KSI = decltype(kstag)::value, P = decltype(settag)::value;
-    if (ASR_GK_ABL & 1) return;
 #pragma unroll
     for (int o = 0; o < NT; ++o)
 #pragma unroll
@@ -1844,10 +1743,7 @@ __global__ __launch_bounds__(512) void gemm_bfk_kernel(GemmArgs g, int groups) {
   // store half HF (accumulator elements 8 HF .. 8 HF + 7) of row block I of accumulator set P = tile mt's rows wm*64 + 32 I ..
   auto store_half = [&](auto settag, auto itag, auto hftag, int mt) __attribute__((always_inline)) {
     constexpr int P = decltype(settag)::value, I = decltype(itag)::value, HF = decltype(hftag)::value;
-    if (ASR_GK_ABL & 8) {
-#pragma unroll
-      for (int e = 8 * HF; e < 8 * HF + 8; ++e) asm volatile("" ::"v"(acc[P][I][e]));
-    } else if constexpr (PLAIN) {
+    if constexpr (PLAIN) {
       // rows through the SGPR offset of the buffer store, this lane's column in the VGPR offset: no address arithmetic
       const int row0 = (mt * 128 + wm * 64 + I * 32) * ldcb;
 #pragma unroll
@@ -1929,7 +1825,7 @@ __global__ __launch_bounds__(512) void gemm_bfk_kernel(GemmArgs g, int groups) {
     // The loads of tile k + 2 go first, into the register set tile k's rows have left (the current tile's image was written
     // during the previous tile): vmcnt retires loads and stores in issue order, so a wait for these loads also waits for
     // every store issued before them - placed ahead of this tile's stores they only wait for stores of a tile ago.
-    if (has_next2 && !(ASR_GK_ABL & 2)) {
+    if (has_next2) {
 #define X_LDA2(u_) load_a(PT(), std::integral_constant<int, u_>(), mt + 2 * groups)
       BFK_FOR_PIECES(X_LDA2);
 #undef X_LDA2
@@ -1945,7 +1841,7 @@ __global__ __launch_bounds__(512) void gemm_bfk_kernel(GemmArgs g, int groups) {
       if ((ks_) + 1 < KS) read_fa(SN(), std::integral_constant<int, ((ks_) + 1 < KS ? (ks_) + 1 : 0)>(), PT());        \
       else if (has_next) read_fa(SN(), I0(), PN());                                                                     \
       if constexpr ((ks_) < KS - 1) {          /* (constexpr: the discarded branch would index past RA / acc) */         \
-        if (has_next && !(ASR_GK_ABL & 2)) {                                                                            \
+        if (has_next) {                                                                                                 \
           constexpr int u0 = (ks_) * HP / (KS - 1), u1 = ((ks_) + 1) * HP / (KS - 1);                                   \
           if constexpr (u0 < u1) BFK_UNIT(u0)                                                                           \
           if constexpr (u0 + 1 < u1) BFK_UNIT(u0 + 1)                                                                   \
@@ -2109,7 +2005,7 @@ extern "C" int asr_gw_trace_read(void* dst) {
 // Split-K factor of the 128 x 128 kernels when the caller passes split_k <= 0 (partials are added with f32 atomics; a
 // bias / ReLU epilogue then needs a second pass over C).  256 CUs hold two 128 x 128 workgroups each, so the target is
 // ~512 workgroups: floor(512 / tiles), at most 8 (16 for <= 32 tiles), every K slice at least 256 long.  Measured with
-// cold operands (tools/gemm_cold_split_sweep.py): 400 tiles -> 1, 200 -> 2, 144 -> 3, 128 -> 4, 64 -> 8.
+// cold operands (DESIGN_HISTORY 6): 400 tiles -> 1, 200 -> 2, 144 -> 3, 128 -> 4, 64 -> 8.
 static int narrow_split_k(int64_t M, int64_t N, int64_t K, int batch, bool epilogue, int ts = 128) {
   const int64_t tiles = ((M + ts - 1) / ts) * ((N + ts - 1) / ts) * batch;
   const int64_t target = 512;       // (64 x 64 tiles, tools/gemm_small_sweep.py: 400 tiles unsplit 28 us, split in two 41)
@@ -2196,25 +2092,25 @@ static int plan_gemm(const GemmArgs& g, bool akc, bool bkc, int batch, int split
     }
   }
   // Products too small to fill the chip with 128 x 128 tiles take 64 x 64 tiles (gemm_bf3_kernel<..., 64>): at most
-  // ASR_GEMM_SMALL_MAX workgroups of large tiles (the decoder-side projections and their gradients, the output layer); ASR_GEMM_TILE_SMALL
+  // SMALL_MAX workgroups of large tiles (the decoder-side projections and their gradients, the output layer); ASR_GEMM_TILE_SMALL
   // forces them (tests, measurements), ASR_GEMM_TILE_NARROW the 128 x 128 tile.
-  static const int64_t small_max = [] { const char* f = getenv("ASR_GEMM_SMALL_MAX"); return f ? (int64_t)atoll(f) : (int64_t)256; }();   // measurement
+  constexpr int64_t SMALL_MAX = 256;
   const int64_t tiles128 = ((M + BM - 1) / BM) * ((N + BN - 1) / BN) * batch;
   // ... i.e. when the large tiles, K split included, would be at most one workgroup per CU (tools/gemm_small_sweep.py:
   // [3 200 x 512] x K 512 28-31 us against 42-47, the output layer 31-37 against 46-48; a long K on 64 large tiles -
   // 512 workgroups after the split - stays on the large tiles: 76 against 83)
   const int64_t wgs128 = tiles128 * (auto_split ? ((epi && accumulate) ? 1 : narrow_split_k(M, N, K, batch, epi, 128)) : (split_k > 0 ? split_k : 1));
-  const bool small = ar != ASR_ARITH_F32 && ((arith & ASR_GEMM_TILE_SMALL) || (wgs128 <= small_max && !(arith & ASR_GEMM_TILE_NARROW)));
+  const bool small = ar != ASR_ARITH_F32 && ((arith & ASR_GEMM_TILE_SMALL) || (wgs128 <= SMALL_MAX && !(arith & ASR_GEMM_TILE_NARROW)));
   // The one-wave-per-SIMD kernel (gemm_bfs_kernel, same tile and K split policy): faster than both others on every shape
   // with enough work to fill the chip a few times (tools/gemm_shapes.py: 256 x 128 tiles x K tiles >= ~5 000; below
   // that its 4-wave workgroups cannot hide their prologue and the 128 x 128 kernel's two workgroups per CU win); its
   // buffer addressing wants byte offsets below 2^31.  ASR_GEMM_TILE_SP forces it for conforming shapes.
   const bool sp_shape = base_shape && (K % WK == 0 || (K % 4 == 0 && K > WK)) &&       // a K tail is masked (K = 80: the features)
                         (akc ? M : K) * lda < ((int64_t)1 << 29) && (bkc ? N : K) * ldb < ((int64_t)1 << 29);
-  static const int64_t sp_min_units = [] { const char* f = getenv("ASR_GEMM_SP_MIN"); return f ? (int64_t)atoll(f) : (int64_t)5000; }();   // measurement
+  constexpr int64_t SP_MIN_UNITS = 5000;
   // (K = 80: 223 us against the 128 x 128 kernel's 195 - three K tiles are all prologue; a LONG K with a masked tail - the
   // weight-gradient products over the packed rows of the encoder, K = sum of the utterances' extents - pays like any other)
-  const bool sp_pays = (K % WK == 0 || K >= 64 * WK) && wtiles * (K / WK) >= sp_min_units;
+  const bool sp_pays = (K % WK == 0 || K >= 64 * WK) && wtiles * (K / WK) >= SP_MIN_UNITS;
   const bool use_sp = ar != ASR_ARITH_F32 && sp_shape && (auto_split || split_k == 1) && (!small || (arith & ASR_GEMM_TILE_SP)) &&
                       ((arith & ASR_GEMM_TILE_SP) || (sp_pays && !(arith & (ASR_GEMM_TILE_NARROW | ASR_GEMM_TILE_WIDE | ASR_GEMM_TILE_SMALL))));
   const bool wide = use_sp || (ar != ASR_ARITH_F32 && !(arith & (ASR_GEMM_TILE_NARROW | ASR_GEMM_TILE_SP | ASR_GEMM_TILE_SMALL)) && wide_shape &&
@@ -2222,7 +2118,7 @@ static int plan_gemm(const GemmArgs& g, bool akc, bool bkc, int batch, int split
   if (wide) {
     // its own K split: 256 workgroup slots (one 8-wave workgroup per CU), cost in units of one stage = rounds x (stages
     // per slice + a fixed prologue / epilogue share) + what the atomics and the zero pass of a split cost per MB of output
-    // (tools/gemm_wide_split.py: 12800 x 512 x 4096 takes 215 us unsplit on 200 of the 256 CUs, 256 us split in two)
+    // (DESIGN_HISTORY 4.0.5: 12800 x 512 x 4096 takes 215 us unsplit on 200 of the 256 CUs, 256 us split in two)
     const int64_t tiles = wtiles, stages = (K + WK - 1) / WK;
     // A product with a bias / ReLU epilogue may be split as well: the atomics cannot carry the epilogue, so it becomes a
     // pass of its own over C (bias_act_kernel, as on the 128 x 128 kernels) - worth it where few tiles walk a long K
@@ -2238,8 +2134,6 @@ static int plan_gemm(const GemmArgs& g, bool akc, bool bkc, int batch, int split
         if (cost < best_cost) { best_cost = cost; best = sk; }
       }
     }
-    static const int forced_sk = [] { const char* f = getenv("ASR_GEMM_WIDE_SK"); return f ? atoi(f) : 0; }();   // measurement
-    if (forced_sk >= 1 && forced_sk <= stages && may_split) best = forced_sk;
     const bool late_epi = best > 1 && epi;
     p->family = use_sp ? ASR_GEMM_FAMILY_BFS : ASR_GEMM_FAMILY_BFW; p->tile = WM; p->block = use_sp ? 256 : 512;
     p->kt = use_sp && K % WK != 0;

@@ -22,55 +22,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "persist.h"
-#ifndef ASR_LP_ABL
-#define ASR_LP_ABL 0
-#endif
-#ifndef ASR_POLL_SLEEP
-#define ASR_POLL_SLEEP 1
-#endif
-#ifndef ASR_LSTM_BWD_B128      /* hand-off rows of the backward read with one 16-byte sc1 buffer load each */
-#define ASR_LSTM_BWD_B128 1
-#endif
-#ifndef ASR_LSTM_TOUCH
-#define ASR_LSTM_TOUCH 1
-#endif
-#ifndef ASR_LSTM_TOUCH_DIST
-#define ASR_LSTM_TOUCH_DIST 3
-#endif
-#ifndef ASR_LSTM_BWD_FULL_WAVES
-#define ASR_LSTM_BWD_FULL_WAVES 8  /* waves whose first poll attempt requests the whole tile (16-byte loads: 8 per lane); with the 8-byte loads only the pointwise waves (2) paid off: 3.85 (2) -> 3.78 (4) -> 3.62 (8) us per step */
-#endif
-#ifndef ASR_LSTM_FULL_WAVES
-#define ASR_LSTM_FULL_WAVES 2      /* waves 0..1 hold the pointwise threads (PUC*PRG <= 128) */
-#endif
 // measurement only: shader-clock stamps of workgroup (group 0, slice 0), time steps 8..15, into ctrl[16..]
-#ifndef ASR_LA      /* measurement only: forward (bf3) chain ablation: 1 no products, 2 no h staging, 4 no stores / prefetch, 8 no transcendental math */
-#define ASR_LA 0
-#endif
-#ifndef ASR_ABORT_PERIOD_MASK /* the abort word is polled when (step & mask) == 0; 0 = every step (first version) */
-#define ASR_ABORT_PERIOD_MASK 15
-#endif
-#ifndef ASR_POLL_FIRST        /* 1 (measurement): first poll attempt issued before the h staging: 2.22 vs 2.14 us - an attempt that
-                                 arrives before the data costs a second L2 round trip */
-#define ASR_POLL_FIRST 0
-#endif
-#ifndef ASR_POLL_FIRST_SLEEP
-#define ASR_POLL_FIRST_SLEEP 0
-#endif
-#ifndef ASR_LA_HALVES   /* forward, H = 512, 8-row groups, three terms: the wave's h tile as TWO load instructions - k 0-31 and k 32-63 of
-                           its range - and the split + products of the first half while the second is still arriving: 1.75 -> 1.68 us
-                           per time step, same box, bit-identical results (tools/persist_bench.py against -DASR_LA_HALVES=0) */
-#define ASR_LA_HALVES 1
-#endif
-#ifndef ASR_POLL_SENTINEL_ROWS /* forward (split-bf16) kernel: groups of at least this many rows spin on one quad per lane before requesting the tile (99 = never) */
-#define ASR_POLL_SENTINEL_ROWS 16
-#endif
-#ifndef ASR_STAGE_H_TOP       /* 0 (measurement): h staging behind the poll instead of at the top of the step: 2.27 vs 2.16 us */
-#define ASR_STAGE_H_TOP 1
-#endif
-#ifndef ASR_RA      /* measurement only: backward (exchanged partials) chain ablation: 1 no reduction, 2 no stores / prefetch, 4 no dh products, 8 no tanh, 16 no h prefetch, 32 no dy / gates / c prefetch, 64 no dG store, 128 no column-major dG copy (dW_hh operand), 256 no h staging, 512 h staging without its LDS stores, 1024 without its split arithmetic */
-#define ASR_RA 0
-#endif
 #ifdef ASR_LP_TRACE
 #define LP_MARK(k) do { if ((tid == 0 || tid == 448) && g == 0 && slice == 0 && s >= 8 && s < 16) \
     ((unsigned long long*)(a.ctrl + 16))[(tid ? 128 : 0) + (s - 8) * 16 + (k)] = clock64(); } while (0)
@@ -83,6 +35,19 @@
 #endif
 
 namespace {
+
+constexpr int ASR_LSTM_TOUCH = 1;
+constexpr int ASR_LSTM_TOUCH_DIST = 3;
+// waves whose first poll attempt requests the whole tile (16-byte loads: 8 per lane); with the 8-byte loads only the
+// pointwise waves (2) paid off: 3.85 (2) -> 3.78 (4) -> 3.62 (8) us per step
+constexpr int ASR_LSTM_BWD_FULL_WAVES = 8;
+constexpr int ASR_LSTM_FULL_WAVES = 2;            // waves 0..1 hold the pointwise threads (PUC*PRG <= 128)
+constexpr int ASR_ABORT_PERIOD_MASK = 15;         // the abort word is polled when (step & mask) == 0; 0 = every step (first version)
+// forward (split-bf16) kernel: groups of at least this many rows spin on one quad per lane before requesting the tile (99 = never)
+constexpr int ASR_POLL_SENTINEL_ROWS = 16;
+// s_sleep between two poll attempts.  0 / 1 / 2 / 4 / 8 measured 1.72 / 1.75 / 1.75 / 1.84 / 1.93 us per forward step and
+// 1.82 / 1.82 / 1.81 / 1.82 / 2.19 backward (H = 512, 8 rows): failed polls do not clog the L2 (DESIGN_HISTORY, round 4)
+constexpr int POLL_SLEEP = 1;
 
 // Hidden sizes: H % 32 == 0 and H <= 512 (a CU's H/32 units must fit the 16 MFMA blocks; instantiated for 128,
 // 256, 320, 512).  Blocks / lanes beyond a smaller H idle.
@@ -217,15 +182,12 @@ __global__ __launch_bounds__(PNT) void lstm_persist_fwd_kernel(PersistArgs a) {
         for (int j = 0; j < NR / 4; ++j) bits &= ~(gw[j].x ^ tb) & ~(gw[j].y ^ tb) & ~(gw[j].z ^ tb) & ~(gw[j].w ^ tb);
         LP_MARK(7);
         if (__all(!gl || (bits & 1u))) break;
-#ifdef ASR_NO_POLL
-        break;
-#endif
         if (++spins > SPIN_LIMIT || ((spins & 63u) == 0u && flag_load(a.ctrl + 8) != 0u)) {
           if (lane == 0) raise_abort(a.ctrl, 1u);
           aborted = true;
           break;
         }
-        __builtin_amdgcn_s_sleep(ASR_POLL_SLEEP);
+        __builtin_amdgcn_s_sleep(POLL_SLEEP);
       }
       LP_MARK(1);
 #ifdef ASR_LP_TRACE
@@ -247,7 +209,7 @@ __global__ __launch_bounds__(PNT) void lstm_persist_fwd_kernel(PersistArgs a) {
       // (wave-private LDS region: program order within the wave is enough)
       const int j = lane & 3;
 #pragma unroll
-      for (int k4 = 0; k4 < ((ASR_LP_ABL & 1) ? 1 : PKW / 4); ++k4) {
+      for (int k4 = 0; k4 < PKW / 4; ++k4) {
         // consecutive MFMAs alternate between two accumulators (a dependent chain on one would stall the pipe): rows
         // 0-3 / 4-7 with 8 rows per group, even / odd k (summed below) with 4
         const float4 b0 = *reinterpret_cast<const float4*>(&hs[wave][j][4 * k4]);
@@ -518,7 +480,10 @@ __global__ __launch_bounds__(PNT) void lstm_persist_fwd_bf3_kernel(PersistArgs a
     f32x4 acc[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) acc[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    constexpr bool HALVES = ASR_LA_HALVES != 0 && FOLD && PKW == 64 && NR == 8;
+    // H = 512, 8-row groups, three terms: the wave's h tile as TWO load instructions - k 0-31 and k 32-63 of its range - and
+    // the split + products of the first half while the second is still arriving: 1.75 -> 1.68 us per time step against one
+    // load per tile, same box, bit-identical results
+    constexpr bool HALVES = FOLD && PKW == 64 && NR == 8;
     // the products of k-step ks_ on the staged tile (FOLD form)
 #define LP_KSTEP(ks_)                                                                                                  \
     do {                                                                                                               \
@@ -568,23 +533,23 @@ __global__ __launch_bounds__(PNT) void lstm_persist_fwd_bf3_kernel(PersistArgs a
             aborted = true;
             break;
           }
-          __builtin_amdgcn_s_sleep(ASR_POLL_SLEEP);
+          __builtin_amdgcn_s_sleep(POLL_SLEEP);
           qa = __builtin_amdgcn_raw_buffer_load_b128(xrs, offa, 0, 16);
           qb = __builtin_amdgcn_raw_buffer_load_b128(xrs, offa + 32u * RG * 4u, 0, 16);
         }
-        if (!(ASR_LA & 2)) LP_STAGE(qa, 0);
-        if (!(ASR_LA & 1)) LP_KSTEP(0);
+        LP_STAGE(qa, 0);
+        LP_KSTEP(0);
         while (!aborted && !__all(quad_ok(qb, tb))) {
           if (++spins > spin_limit || ((spins & 63u) == 0u && flag_load(a.ctrl + 8) != 0u)) {
             if (lane == 0) raise_abort(a.ctrl, 1u);
             aborted = true;
             break;
           }
-          __builtin_amdgcn_s_sleep(ASR_POLL_SLEEP);
+          __builtin_amdgcn_s_sleep(POLL_SLEEP);
           qb = __builtin_amdgcn_raw_buffer_load_b128(xrs, offa + 32u * RG * 4u, 0, 16);
         }
         LP_MARK(7);
-        if (!(ASR_LA & 2)) LP_STAGE(qb, 1);
+        LP_STAGE(qb, 1);
 #undef LP_STAGE
       } else if constexpr (NR >= 8) {
         // single-stage hand-off: a lane owns two adjacent k of the wave's range for half of the rows (job = (k pair, row
@@ -620,7 +585,7 @@ __global__ __launch_bounds__(PNT) void lstm_persist_fwd_bf3_kernel(PersistArgs a
             const bool ok1 = !gl[0] || (((q.x ^ tb) | (q.y ^ tb) | (q.z ^ tb) | (q.w ^ tb)) & 1u) == 0u;
             if (__all(ok1)) break;
             if (++spins > spin_limit || ((spins & 63u) == 0u && flag_load(a.ctrl + 8) != 0u)) break;      // the loop below raises the abort
-            __builtin_amdgcn_s_sleep(ASR_POLL_SLEEP);
+            __builtin_amdgcn_s_sleep(POLL_SLEEP);
           }
         }
         while (true) {
@@ -647,12 +612,12 @@ __global__ __launch_bounds__(PNT) void lstm_persist_fwd_bf3_kernel(PersistArgs a
             aborted = true;
             break;
           }
-          __builtin_amdgcn_s_sleep(ASR_POLL_SLEEP);
+          __builtin_amdgcn_s_sleep(POLL_SLEEP);
         }
         LP_MARK(7);
   #pragma unroll
         for (int jc = 0; jc < NJC; ++jc)
-          if (gl[jc] && !(ASR_LA & 2)) {
+          if (gl[jc]) {
   #pragma unroll
             for (int i = 0; i < RJ; ++i) {
               unsigned tk[NT];
@@ -694,12 +659,12 @@ __global__ __launch_bounds__(PNT) void lstm_persist_fwd_bf3_kernel(PersistArgs a
             aborted = true;
             break;
           }
-          __builtin_amdgcn_s_sleep(ASR_POLL_SLEEP);
+          __builtin_amdgcn_s_sleep(POLL_SLEEP);
         }
         LP_MARK(7);
   #pragma unroll
         for (int kc = 0; kc < NKC; ++kc)
-          if (gl[kc] && !(ASR_LA & 2)) {
+          if (gl[kc]) {
   #pragma unroll
             for (int j = 0; j < NR / 4; ++j) {
               const float f[4] = {__uint_as_float(gw[kc][j].x), __uint_as_float(gw[kc][j].y), __uint_as_float(gw[kc][j].z),
@@ -715,19 +680,17 @@ __global__ __launch_bounds__(PNT) void lstm_persist_fwd_bf3_kernel(PersistArgs a
           }
       }
       LP_MARK(1);
-      if (st_gp && !(ASR_LA & 4)) {   // previous step's outputs (stores after the poll: vmcnt retires in order)
+      if (st_gp) {   // previous step's outputs (stores after the poll: vmcnt retires in order)
         *st_gp = st_g;
         a.c[st_so] = st_c;
         a.y[st_so] = st_y;
         st_gp = nullptr;
       }
-      if (prow_ok && s + 2 < T && !(ASR_LA & 4)) gx_n2 = *gx_ptr(s + 2);     // in flight for two steps
+      if (prow_ok && s + 2 < T) gx_n2 = *gx_ptr(s + 2);     // in flight for two steps
       // (wave-private LDS tile: program order within the wave is enough)
-      if constexpr (HALVES) {
-        if (!(ASR_LA & 1)) LP_KSTEP(1);
-      }
+      if constexpr (HALVES) LP_KSTEP(1);
 #pragma unroll
-      for (int ks = 0; ks < ((ASR_LA & 1) || HALVES ? 0 : KS); ++ks) {
+      for (int ks = 0; ks < (HALVES ? 0 : KS); ++ks) {
         if constexpr (FOLD) {
           // columns 8..15 of the batch side carry a second term (fold_halves): four MFMAs per tile and k-step
           const u32x4 b1 = *reinterpret_cast<const u32x4*>(&hh[ml >> 3][wave][ml & 7][32 * ks + 8 * kq]);
@@ -914,10 +877,8 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_kernel(PersistArgs a) {
   float4 dbacc = make_float4(0.f, 0.f, 0.f, 0.f);   // bias gradient of this thread's (unit, row): sum of dG over time
   float* xch_g = reinterpret_cast<float*>(a.xch) + (int64_t)g * PRG * 4 * PH;   // + parity * 8*PRG*4H
   const int64_t par_stride = (int64_t)8 * PRG * 4 * PH;
-#if ASR_LSTM_BWD_B128
   typedef unsigned u4v __attribute__((ext_vector_type(4)));
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(a.xch, 0, 0x7ffffff0, 0x00020000);   // raw dwords
-#endif
   bool aborted = false;
   // pointwise operands are fetched one step ahead (see the forward kernel)
   float n_dy = 0.f, n_ct = 0.f, n_cp = 0.f, n_y = 0.f;
@@ -930,7 +891,7 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_kernel(PersistArgs a) {
 #pragma unroll
     for (int u4 = 0; u4 < 4; ++u4) dwacc[kq][u4] = (f32x4){0.f, 0.f, 0.f, 0.f};
   auto fetch_step = [&](int sn) {
-    const int tt = (ASR_LP_ABL & 8) ? 1 : (d == 0 ? T - 1 - sn : sn);      // bit 8 (measurement): always the same, cached row
+    const int tt = d == 0 ? T - 1 - sn : sn;
     const int ttp = d == 0 ? tt - 1 : tt + 1;
     const bool hp = d == 0 ? (tt > 0) : (tt < T - 1);
     const int64_t so = ROW_AT(tt) * ldy + d * PH + punit;
@@ -959,20 +920,12 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_kernel(PersistArgs a) {
       float4 gr[NR];
       unsigned spins = 0;
       auto load_row = [&](int rr) {
-#if ASR_LSTM_BWD_B128
         // L1-bypassing 16-byte read in ONE instruction: buffer load with the sc1 cache policy (the same policy the
         // agent-scope atomic loads get, which exist only up to 8 bytes)
         const u4v v = __builtin_amdgcn_raw_buffer_load_b128(
             xrs, (unsigned)((src - reinterpret_cast<const float*>(a.xch)) + rr * 4 * PH) * 4u, 0, 16);
         gr[rr].x = __uint_as_float(v.x); gr[rr].y = __uint_as_float(v.y);
         gr[rr].z = __uint_as_float(v.z); gr[rr].w = __uint_as_float(v.w);
-#else
-        // L1-bypassing 16-byte read as two 8-byte agent-scope atomics
-        const u64 lo = granule_load(reinterpret_cast<const u64*>(src + (int64_t)rr * 4 * PH));
-        const u64 hi = granule_load(reinterpret_cast<const u64*>(src + (int64_t)rr * 4 * PH) + 1);
-        gr[rr].x = __uint_as_float((unsigned)lo); gr[rr].y = __uint_as_float((unsigned)(lo >> 32));
-        gr[rr].z = __uint_as_float((unsigned)hi); gr[rr].w = __uint_as_float((unsigned)(hi >> 32));
-#endif
       };
       auto row_bits = [&](int rr) -> unsigned {
         const unsigned m = (__float_as_uint(gr[rr].x) & 1u) | ((__float_as_uint(gr[rr].y) & 1u) << 1) |
@@ -1005,15 +958,12 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_kernel(PersistArgs a) {
             if (__all(!gl || bits == 0xFu)) break;
           }
         }
-#ifdef ASR_NO_POLL
-        break;
-#endif
         if (++spins > SPIN_LIMIT || ((spins & 63u) == 0u && flag_load(a.ctrl + 8) != 0u)) {
           if (lane == 0) raise_abort(a.ctrl, 3u);
           aborted = true;
           break;
         }
-        __builtin_amdgcn_s_sleep(ASR_POLL_SLEEP);
+        __builtin_amdgcn_s_sleep(POLL_SLEEP);
       }
       LP_MARK(1);
 #pragma unroll
@@ -1034,7 +984,7 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_kernel(PersistArgs a) {
         const float* h0 = &hs[wave][li][PQS * ks];
         const float* h1 = &hs[wave][4 + li][PQS * ks];
 #pragma unroll
-        for (int q4 = 0; q4 < ((ASR_LP_ABL & 1) ? 1 : PQ / 4); ++q4) {
+        for (int q4 = 0; q4 < PQ / 4; ++q4) {
           const float4 b0 = *reinterpret_cast<const float4*>(h0 + 4 * q4);
           if (NR > 4) {                      // alternating accumulators, see the forward kernel
             const float4 b1 = *reinterpret_cast<const float4*>(h1 + 4 * q4);
@@ -1060,7 +1010,7 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_kernel(PersistArgs a) {
       } else {
         // dh partial [16 units x rows] of this wave's K range
 #pragma unroll
-        for (int kt = 0; kt < ((ASR_LP_ABL & 1) ? 1 : KSB); ++kt) {
+        for (int kt = 0; kt < KSB; ++kt) {
           u32x4 bt[NT];
 #pragma unroll
           for (int k = 0; k < NT; ++k) bt[k] = *reinterpret_cast<const u32x4*>(&bsp[k][wave][ml & 7][32 * kt + 8 * kg]);
@@ -1139,7 +1089,7 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_kernel(PersistArgs a) {
                          __HIP_MEMORY_SCOPE_WORKGROUP);
       LP_MARK(11);
       if (prow_ok) {     // after the hand-off: the bulk store and the bias-gradient sum are off the serial chain
-        if (!(ASR_LP_ABL & 16) && (!PACKED || t < pext)) *gp = da;
+        if (!PACKED || t < pext) *gp = da;
         dbacc.x += da.x; dbacc.y += da.y; dbacc.z += da.z; dbacc.w += da.w;
       }
     }
@@ -1148,7 +1098,7 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_kernel(PersistArgs a) {
     // tile is still in this wave's LDS region and h_t is the partner of dG_{t_next} in both directions.  Placed
     // after the publish so that it fills the wait for the next hand-off.  Blocks = 16 groups of 4 gate columns,
     // A = dG (4 columns), B = h (4 units), K = one batch row per instruction.
-    if (fuse_dw && s > 0 && !(ASR_LP_ABL & 2)) {
+    if (fuse_dw && s > 0) {
       const int kb4 = lane;                      // column within the 64-column chunk (= 4*block + i)
       const int jj = lane & 3;
 #pragma unroll
@@ -1260,7 +1210,7 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_rs_kernel(PersistArgs a)
   //   dW_hh (every third step): A operand = 8 rows (k = slot * 8 + row) of a column  -> two ds_read_b64_tr_b16 (the
   //     hardware transpose read, tools/micro/tr_read_check.hip)
   // The first version kept a second, column-major copy for dW_hh that the pointwise threads filled with 24 two-byte LDS
-  // stores per step: 0.13 us of the serial chain (-DASR_RA=128).  h_{t_prev} stays [unit][slot][row].
+  // stores per step: 0.13 us of the serial chain.  h_{t_prev} stays [unit][slot][row].
   // Three terms (NT = 3, six products per product): dW_hh is NOT fused.  With three terms of W in registers (96 VGPRs)
   // the 64 accumulator registers of dW_hh do not fit, and a first version that kept the third term of W in LDS and the h
   // tile as fp32 measured the fused product at 1.08 us per time step (2 x the MFMAs of the two-term form, all of it on
@@ -1360,8 +1310,8 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_rs_kernel(PersistArgs a)
   const bool fuse_dw = FUSE && a.dw != nullptr && a.yfwd != nullptr;
   // gather role: the 16 lanes of DPP row rr = lane >> 4 sum the 32 sources of combo CPW wave + rr = (row, unit quad), two
   // sources (2 sp, 2 sp + 1) per lane: one add and a 16-lane DPP reduction per value.  (With one source per lane and 32
-  // lanes per combo the two DPP rows had to be joined through v_readlane: 0.29 us of the 2.52 us step, tools/persist_bench.py
-  // with -DASR_RA=1.)
+  // lanes per combo the two DPP rows had to be joined through v_readlane: 0.29 us of the 2.52 us step with the
+  // reduction taken out.)
   // h_{t_prev} loader: lane l < UPW of wave w owns unit UPW w + l (this wave's own dW unit tiles: wave-private LDS rows)
   const bool h_lane = fuse_dw && lane < UPW;
   const int hunit = UPW * wave + (lane < UPW ? lane : 0);
@@ -1386,7 +1336,7 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_rs_kernel(PersistArgs a)
   // serial chain); rows / times that do not exist are zeroed when the registers are staged (stage_h).
   // Addressing: one per-lane byte offset (its unit) + a scalar offset per row and step through a buffer resource whose base
   // is the time slab - eight bare buffer loads.  With per-lane 64-bit pointers hipcc spent ~10 VALU instructions (64-bit
-  // multiply-adds) in front of every load: 0.23 us of the 2.30 us step (tools/persist_bench.py, -DASR_RA=16).
+  // multiply-adds) in front of every load: 0.23 us of the 2.30 us step (measured against a build without the h prefetch).
   const unsigned h_voff = (unsigned)(d * PH + hunit) * 4u;
   auto fetch_h = [&](int sn) {
     const int tt = time_of(sn);
@@ -1473,7 +1423,7 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_rs_kernel(PersistArgs a)
     // barrier A, two transcendentals and ~25 dependent VALU instructions on the serial chain)
     float k_dc = 0.f, k_i = 0.f, k_f = 0.f, k_g = 0.f, k_o = 0.f, k_cn = 0.f;
     if (pw_thread) {
-      const float tc = (ASR_RA & 8) ? ct_ * 0.1f : asr_fast_tanh(ct_);
+      const float tc = asr_fast_tanh(ct_);
       const bool live = t < plen;
       k_dc = av.w * (1.f - tc * tc);
       k_i = live ? av.z * av.x * (1.f - av.x) : 0.f;
@@ -1483,21 +1433,10 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_rs_kernel(PersistArgs a)
       k_cn = live ? av.y : 0.f;
       asm volatile("" : "+v"(k_dc), "+v"(k_i), "+v"(k_f), "+v"(k_g), "+v"(k_o), "+v"(k_cn));
     }
-#if ASR_POLL_FIRST
-    if (s > 0 && !q_inflight) {
-#if ASR_POLL_FIRST_SLEEP
-      __builtin_amdgcn_s_sleep(ASR_POLL_FIRST_SLEEP);
-#endif
-#pragma unroll
-      for (int e = 0; e < NE; ++e) q[e] = __builtin_amdgcn_raw_buffer_load_b128(xrs, goff[e] + (unsigned)(((s - 1) & 1) * PARSZ) * 4u, 0, 16);
-      q_inflight = true;
-    }
-#endif
     // h tile of the NEXT step (fetched after the previous poll, a whole step ago) -> the other LDS slot, while this step's
-    // partials are still in flight
-#if ASR_STAGE_H_TOP
-    if (h_lane && s + 1 < T && !(ASR_RA & 256)) stage_h((s + 1) & 3, s + 1);
-#endif
+    // partials are still in flight.  (Behind the poll instead of here: 2.27 vs 2.16 us per step; a first poll attempt issued
+    // before this staging: 2.22 vs 2.14 us - an attempt that arrives before the data costs a second L2 round trip.)
+    if (h_lane && s + 1 < T) stage_h((s + 1) & 3, s + 1);
     float4* gp = nullptr;
     if (prow_ok) gp = reinterpret_cast<float4*>(a.gates + ROW_AT(t) * ldg + (int64_t)d * 4 * PH + punit * 4);
     // ---------------------------------------------------------------- (1) gather the partials addressed to this CU
@@ -1520,28 +1459,23 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_rs_kernel(PersistArgs a)
           aborted = true;
           break;
         }
-        __builtin_amdgcn_s_sleep(ASR_POLL_SLEEP);
+        __builtin_amdgcn_s_sleep(POLL_SLEEP);
       }
       LP_MARK(1);
-      if (!(ASR_RA & 1)) {
-        float v[4] = {__uint_as_float(q[0].x) + __uint_as_float(q[1].x), __uint_as_float(q[0].y) + __uint_as_float(q[1].y),
-                      __uint_as_float(q[0].z) + __uint_as_float(q[1].z), __uint_as_float(q[0].w) + __uint_as_float(q[1].w)};
-        row16_sum4(v);                               // every lane of a 16-lane row holds the row's total
-        if constexpr (ROWPW) dh_rec = (sp & 2) ? ((sp & 1) ? v[3] : v[2]) : ((sp & 1) ? v[1] : v[0]);
-        else if (sp == 0 && guse) *reinterpret_cast<float4*>(&dhs[grow][4 * guq]) = make_float4(v[0], v[1], v[2], v[3]);
-      }
+      float v[4] = {__uint_as_float(q[0].x) + __uint_as_float(q[1].x), __uint_as_float(q[0].y) + __uint_as_float(q[1].y),
+                    __uint_as_float(q[0].z) + __uint_as_float(q[1].z), __uint_as_float(q[0].w) + __uint_as_float(q[1].w)};
+      row16_sum4(v);                               // every lane of a 16-lane row holds the row's total
+      if constexpr (ROWPW) dh_rec = (sp & 2) ? ((sp & 1) ? v[3] : v[2]) : ((sp & 1) ? v[1] : v[0]);
+      else if (sp == 0 && guse) *reinterpret_cast<float4*>(&dhs[grow][4 * guq]) = make_float4(v[0], v[1], v[2], v[3]);
     }
-    if (st_gp && !(ASR_RA & (2 | 64))) { // previous step's dG (bulk store after the poll: vmcnt retires in order)
+    if (st_gp) { // previous step's dG (bulk store after the poll: vmcnt retires in order)
       *st_gp = st_da;
       st_gp = nullptr;
     }
     // prefetches: right after the poll, i.e. as far ahead of the next one as possible
-    if (prow_ok && s + 2 < T && !(ASR_RA & (2 | 32))) fetch_step(s + 2, n2_dy, n2_ct, n2_av);
+    if (prow_ok && s + 2 < T) fetch_step(s + 2, n2_dy, n2_ct, n2_av);
     if constexpr (FUSE) {
-#if !ASR_STAGE_H_TOP
-      if (h_lane && s + 1 < T && !(ASR_RA & 256)) stage_h((s + 1) & 3, s + 1);
-#endif
-      if (h_lane && s + 2 < T && !(ASR_RA & (2 | 16))) fetch_h(s + 2);
+      if (h_lane && s + 2 < T) fetch_h(s + 2);
       LP_MARK(2);
       __syncthreads();                 // A: the h tile / dG slots of the fused dW_hh block (the unfused kernel alternates two
       LP_MARK(3);                      // dG slots instead: a slot is rewritten two barriers B after its last reader)
@@ -1567,7 +1501,7 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_rs_kernel(PersistArgs a)
 #pragma unroll
           for (int k = 0; k < NT; ++k) *reinterpret_cast<uint2*>(&dgs[k][sl][pj][4 * pu]) = make_uint2(p0[k], p1[k]);
           if constexpr (FUSE) {
-            if (fuse_dw && !(ASR_RA & 128)) {              // must read as zero in the flush that does not cover it
+            if (fuse_dw) {              // must read as zero in the flush that does not cover it
 #pragma unroll
               for (int k = 0; k < NT; ++k) *reinterpret_cast<uint2*>(&dgs[k][zs][pj][4 * pu]) = make_uint2(0u, 0u);
             }
@@ -1589,7 +1523,7 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_rs_kernel(PersistArgs a)
 #pragma unroll
       for (int mt = 0; mt < MTW; ++mt) acc[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < ((ASR_RA & 4) ? 0 : KS); ++ks) {
+      for (int ks = 0; ks < KS; ++ks) {
         if constexpr (NT == 3) {
           // columns 8..15 of the batch side carry a second term (fold_halves): four MFMAs per tile and k-step
           const u32x4 b1 = *reinterpret_cast<const u32x4*>(&dgs[ml >> 3][s & 1][ml & 7][32 * ks + 8 * kq]);
@@ -1888,7 +1822,7 @@ __global__ __launch_bounds__(PNT) void lstm_persist_bwd_rs640_kernel(PersistArgs
           aborted = true;
           break;
         }
-        __builtin_amdgcn_s_sleep(ASR_POLL_SLEEP);
+        __builtin_amdgcn_s_sleep(POLL_SLEEP);
       }
       float v[4] = {__uint_as_float(q[0].x) + __uint_as_float(q[1].x), __uint_as_float(q[0].y) + __uint_as_float(q[1].y),
                     __uint_as_float(q[0].z) + __uint_as_float(q[1].z), __uint_as_float(q[0].w) + __uint_as_float(q[1].w)};

@@ -128,9 +128,6 @@ __device__ __forceinline__ void poll_pairs(const u64* const (&p)[N], unsigned wa
         if (__all(ok)) return;
       }
     }
-#ifdef ASR_NO_POLL   /* measurement only: never wait (results are garbage) */
-    return;
-#endif
     if (++spins > limit || ((spins & 63u) == 0u && flag_load(ctrl + 8) != 0u)) {
       if ((threadIdx.x & 63) == 0) raise_abort(ctrl, code);
       aborted = true;
@@ -178,9 +175,6 @@ __device__ __forceinline__ void poll_quads(__amdgpu_buffer_rsrc_t rs, const unsi
         if (__all(ok)) return;
       }
     }
-#ifdef ASR_NO_POLL
-    return;
-#endif
     if (++spins > limit || ((spins & 63u) == 0u && flag_load(ctrl + 8) != 0u)) {
       if ((threadIdx.x & 63) == 0) raise_abort(ctrl, code);
       aborted = true;

@@ -141,6 +141,31 @@ def test_both_sides_of_each_threshold(table, ar, nt):
     assert kernel(1, 0, 1280, 1024, 1024, ldb=1026).startswith("gemm_bf3_kernel")
 
 
+def _plan_child(rows):
+    """In a child process: the plans of `rows` as JSON on stdout (the parent built the library)."""
+    print(json.dumps([_plan(c) for c in rows]))
+
+
+def test_the_plan_does_not_read_the_environment(table):
+    """plan_gemm is a function of its arguments.  Three environment variables, read once per process (hence a fresh child),
+    used to move its thresholds and force the wide kernels' K split; with all three set, one row each that lands on 64 x 64
+    tiles, 128 x 128 tiles, the LDS-DMA kernel (split), the one-wave-per-SIMD kernel and the K = 80 kernel plans as the table has it."""
+    import subprocess
+    rows = [_row(table, X6, 1, 0, 1024, 1024, 1024), _row(table, X6, 0, 1, 4096, 2048, 608), _row(table, X6, 0, 1, 1368, 512, 2048),
+            _row(table, X6, 0, 1, 4096, 2048, 640), _row(table, X6, 0, 1, 1024, 128, 80)]
+    assert [_family(c) for c in rows] == ["64", "128", "wide", "bfs", "bfk"]
+    assert _product(rows[2])[1][1] not in (1, 4)          # (a forced split of 4 would show)
+    here = os.path.dirname(os.path.abspath(__file__))
+    paths = [here, ROOT, os.path.join(ROOT, "semi-supervised-asr_amd")]
+    code = "import sys; sys.path[:0] = %r; import test_gemm_plan_cpu as t; t._plan_child(%r)" % (paths, rows)
+    env = dict(os.environ, ASR_GEMM_SMALL_MAX="0", ASR_GEMM_SP_MIN="0", ASR_GEMM_WIDE_SK="4")
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    plans = json.loads(r.stdout.strip().splitlines()[-1])
+    for c, p in zip(rows, plans):
+        assert p["rc"] == c["rc"] and [[k, list(g), b] for k, g, b in p["launches"]] == c["launches"], (c, p)
+
+
 def test_f32_arithmetic_has_one_kernel(table):
     assert _product(_row(table, F32, 0, 1, 4096, 2048, 640))[0] == "gemm_f32_kernel<true,true>"
     assert _product(_row(table, F32, 1, 0, 1280, 1024, 1024, flags=WIDE))[0] == "gemm_f32_kernel<false,false>"

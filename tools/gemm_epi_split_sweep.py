@@ -1,6 +1,6 @@
 """Measurement: the bias(+ReLU) projections of the encoder (NT, K = 2048 / 512) on the 128 x 128 kernel by K split (cold
 operands).  A split product pays a zero pass and a bias/ReLU pass over C; an unsplit one runs 100-400 workgroups of
-64 serial K tiles.  SWEEP_SP_ONLY=1 with ASR_GEMM_WIDE_SK=n (read once per process): the 256 x 128 kernel with a forced split."""
+64 serial K tiles.  The 256 x 128 kernels run with the policy's own split ('policy', 'sp')."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, ROOT + '/semi-supervised-asr_amd']
@@ -16,8 +16,7 @@ for (M, N, K, bias, relu) in shapes:
     A = torch.randn(M, K, device=dev); B = torch.randn(N, K, device=dev); bv = torch.randn(N, device=dev) if bias else None
     out = torch.zeros(M, N, device=dev)
     line = []
-    modes = (('bf16x6', 0), ('bf16x6+sp', 0)) if os.environ.get('SWEEP_SP_ONLY') else (('bf16x6', 0), ('bf16x6+sp', 0), ('bf16x6+narrow', 1), ('bf16x6+narrow', 2), ('bf16x6+narrow', 3), ('bf16x6+narrow', 4), ('bf16x6+narrow', 5), ('bf16x6+narrow', 8))
-    for mode, sk in modes:
+    for mode, sk in (('bf16x6', 0), ('bf16x6+sp', 0), ('bf16x6+narrow', 1), ('bf16x6+narrow', 2), ('bf16x6+narrow', 3), ('bf16x6+narrow', 4), ('bf16x6+narrow', 5), ('bf16x6+narrow', 8)):
         ts = []
         for _ in range(4):
             flush.fill_(1.0); torch.cuda.synchronize()
