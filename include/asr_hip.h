@@ -865,6 +865,42 @@ int asr_sum_det_f32(int64_t n, const float* x, float scale, float* out, asr_stre
 int asr_dec_step_bwd_det(const asr_dec_bwd_t* p, int s, asr_stream_t stream);
 int asr_dec_seq_bwd_det(const asr_dec_bwd_t* p, int s_begin, int s_end, asr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * CTC loss on the encoder output (csrc/ctc.hip): the CTC branch of joint CTC-attention training,
+ * (1 - w) L_att + w L_ctc.  Not a reference operator - the reference has no CTC branch.  Three entries added to ABI version 8
+ * WITHOUT a version change, like the deterministic entries: additive.
+ *   logits        [B][T][V] fp32 RAW logits, row stride ld >= V floats; the log-softmax over V is taken inside (one
+ *                 log-sum-exp per frame is all that is stored of it).  Frames t >= frame_lens[b] are never read.
+ *   frame_lens    int32 [B] on the device (clamped to 0 .. T).
+ *   labels        ONE packed int64 tensor on the device; utterance b owns labels[label_offsets[b] .. label_offsets[b + 1]),
+ *                 label_offsets int32 [B + 1] on the device.  Blank = index 0, which is never a label: a label outside
+ *                 [1, V), or more than max_label_len labels, makes the utterance infeasible.
+ *   max_label_len an upper bound of every utterance's label count, known to the host (it sizes the workspace and picks the
+ *                 kernel: one wave per utterance up to 2 max_label_len + 1 = 64 states, one 256-thread workgroup beyond,
+ *                 states strided over the threads above 256).  At most ASR_CTC_MAX_LABELS; V >= 2: ASR_E_SHAPE otherwise.
+ *   asr_ctc_ws_bytes   the bytes of the workspace for these sizes: 4 ( B T (2 max_label_len + 2) + B (max_label_len + V + 1) ),
+ *                 each of the five parts rounded up to 64 words.  The forward fills it (log-sum-exps, alpha, the raw nll, the
+ *                 label-sorted position list of every utterance), the backward reads it and overwrites alpha with
+ *                 alpha + beta: one backward per forward, same arguments.
+ *   asr_ctc_loss_fwd   nll[b] = -log p(labels_b | logits_b), alpha in log space.  An utterance with no alignment (frames <
+ *                 labels + adjacent equal labels) has nll = +inf; with zero_infinity != 0 the output is 0 instead (the
+ *                 workspace keeps the raw value).  Two launches.
+ *   asr_ctc_loss_bwd   dlogits[b][t][k] = grad_nll[b] (softmax_k - exp(logsum_{s : l'_s = k} (alpha_t(s) + beta_t(s)) - logp_k
+ *                 + nll_b)), row stride lddz >= V; exact zeros for t >= frame_lens[b] and, with zero_infinity, for an
+ *                 infeasible utterance (without it: grad_nll[b] softmax_k).  Two launches.
+ * No floating-point atomics: the sum over the states of a label is taken by ONE lane in ascending position order (the blank's
+ * by the wave: lane-strided ascending, then the xor butterfly), so both calls are functions of their inputs and shapes only -
+ * the same bits in every run, in and outside deterministic mode.  No host synchronisation, no allocation.
+ * ------------------------------------------------------------------------------------- */
+#define ASR_CTC_MAX_LABELS 1023
+int asr_ctc_ws_bytes(int B, int T, int V, int max_label_len, int64_t* ws_bytes);
+int asr_ctc_loss_fwd(int B, int T, int V, const float* logits, int64_t ld, const int32_t* frame_lens, const int64_t* labels,
+                     const int32_t* label_offsets, int max_label_len, int zero_infinity, float* nll, void* ws,
+                     int64_t ws_bytes, asr_stream_t stream);
+int asr_ctc_loss_bwd(int B, int T, int V, const float* logits, int64_t ld, const int32_t* frame_lens, const int64_t* labels,
+                     const int32_t* label_offsets, int max_label_len, int zero_infinity, const float* grad_nll, void* ws,
+                     int64_t ws_bytes, float* dlogits, int64_t lddz, asr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@ EXPORTS = (
     "asr_edit_distance_i32",
     "asr_colsum_det_f32", "asr_gemm_det_f32", "asr_gemm_det_ws_bytes", "asr_embedding_grad_det_f32", "asr_rows_fill_grad_det_f32",
     "asr_sumsq_det_f32", "asr_gather_sumsq_det_f32", "asr_sum_det_f32", "asr_dec_step_bwd_det", "asr_dec_seq_bwd_det",
+    "asr_ctc_ws_bytes", "asr_ctc_loss_fwd", "asr_ctc_loss_bwd",
 )
 
 _lib = None
@@ -251,6 +252,9 @@ def load():
     lib.asr_gather_sumsq_f32.argtypes = [c_i, ctypes.POINTER(c_p), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_p, c_p, c_p]
     lib.asr_label_logprob_fwd.argtypes = [c_i64, c_i, c_p, c_i64, c_p, c_p, c_f, c_p, c_p, c_f, c_p, c_p]
     lib.asr_label_logprob_bwd.argtypes = [c_i64, c_i, c_p, c_i64, c_p, c_p, c_f, c_p, c_i64, c_f, c_p, c_i64, c_p]
+    lib.asr_ctc_ws_bytes.argtypes = [c_i, c_i, c_i, c_i, ctypes.POINTER(c_i64)]
+    lib.asr_ctc_loss_fwd.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i64, c_p]
+    lib.asr_ctc_loss_bwd.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i64, c_p, c_i64, c_p]
     lib.asr_dec_feedback_fwd.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_p, c_i64,
                                          c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
     lib.asr_dec_feedback_bwd.argtypes = [c_i, c_i, c_i, c_i, c_p, c_p, c_i64, c_p, c_p, c_p, c_f, c_p, c_p]
@@ -815,6 +819,47 @@ def dec_feedback_bwd(demb, gtop, probs, emb_w, w_out, scaling, dlog):
     assert probs.is_contiguous() and dlog.is_contiguous() and w_out.is_contiguous() and emb_w.is_contiguous()
     check(load().asr_dec_feedback_bwd(B, V, E, DO, ptr(demb), ptr(gtop), ldg, ptr(probs), ptr(emb_w), ptr(w_out),
                                       float(scaling), ptr(dlog), stream()), "asr_dec_feedback_bwd")
+
+
+CTC_MAX_LABELS = 1023     # ASR_CTC_MAX_LABELS
+
+
+def ctc_ws_bytes(B, T, V, max_label_len):
+    """asr_ctc_ws_bytes on plain integers (no tensors, no GPU) -> the workspace bytes of a CTC call; UnsupportedShape for
+    sizes the kernels refuse (more than CTC_MAX_LABELS labels, V < 2)."""
+    need = c_i64(0)
+    rc = load().asr_ctc_ws_bytes(int(B), int(T), int(V), int(max_label_len), ctypes.byref(need))
+    if rc == -2:
+        raise UnsupportedShape("ctc_loss: B %d, T %d, V %d, %d labels (at most %d labels, V >= 2)"
+                               % (B, T, V, max_label_len, CTC_MAX_LABELS))
+    check(rc, "asr_ctc_ws_bytes")
+    return need.value
+
+
+def _ctc_args(logits, ld, frame_lens, labels, label_offsets, max_label_len, zero_infinity):
+    B, T, V = logits.shape
+    if labels.dtype != torch.long or not labels.is_cuda:
+        raise RuntimeError("ctc_loss: labels must be one packed int64 tensor on the GPU")
+    return (B, T, V, ptr(logits), int(ld), ptr(frame_lens), c_p(labels.data_ptr()), ptr(label_offsets), int(max_label_len),
+            int(bool(zero_infinity)))
+
+
+def ctc_loss_fwd(logits, ld, frame_lens, labels, label_offsets, max_label_len, zero_infinity, nll, ws):
+    """asr_ctc_loss_fwd: logits [B, T, V] fp32 with row stride ld (a view of a wider buffer is fine), frame_lens int32 [B],
+    labels packed int64, label_offsets int32 [B + 1], all on the device; nll [B] and the workspace ws (a float32 tensor of at
+    least ctc_ws_bytes bytes) are the caller's.  The workspace goes to ctc_loss_bwd unchanged."""
+    args = _ctc_args(logits, ld, frame_lens, labels, label_offsets, max_label_len, zero_infinity)
+    check(load().asr_ctc_loss_fwd(*args, ptr(nll), ptr(ws), ws.numel() * 4, stream()), "asr_ctc_loss_fwd")
+    return nll
+
+
+def ctc_loss_bwd(logits, ld, frame_lens, labels, label_offsets, max_label_len, zero_infinity, grad_nll, ws, dlogits, lddz):
+    """asr_ctc_loss_bwd behind a ctc_loss_fwd with the same arguments and workspace: dlogits [B, T, >= V] with row stride lddz
+    gets grad_nll[b] d nll_b / d logits, exact zeros behind each utterance."""
+    args = _ctc_args(logits, ld, frame_lens, labels, label_offsets, max_label_len, zero_infinity)
+    check(load().asr_ctc_loss_bwd(*args, ptr(grad_nll), ptr(ws), ws.numel() * 4, ptr(dlogits), int(lddz), stream()),
+          "asr_ctc_loss_bwd")
+    return dlogits
 
 
 def colsum(X, out=None, accumulate=False):

@@ -432,7 +432,7 @@ class E2E(torch.nn.Module):
 
     def __init__(self, input_dim, enc_hidden_dim, enc_n_layers, subsample, dropout_rate, dec_hidden_dim, att_dim,
                  conv_channels, conv_kernel_size, att_odim, embedding_dim, output_dim, ls_weight, labeldist,
-                 pad=0, bos=1, eos=2):
+                 pad=0, bos=1, eos=2, ctc_weight=0.0):
         super(E2E, self).__init__()
         self.encoder = Encoder(input_dim=input_dim, hidden_dim=enc_hidden_dim, n_layers=enc_n_layers,
                                subsample=subsample, dropout_rate=dropout_rate)
@@ -442,6 +442,16 @@ class E2E(torch.nn.Module):
         self.decoder = Decoder(output_dim=output_dim, hidden_dim=dec_hidden_dim, embedding_dim=embedding_dim,
                                attention=self.attention, dropout_rate=dropout_rate, att_odim=att_odim,
                                ls_weight=ls_weight, labeldist=labeldist, bos=bos, eos=eos, pad=pad)
+        # `ctc_weight` (not in the reference): w > 0 adds a CTC branch on the encoder output and trains on
+        # (1 - w) L_att + w L_ctc.  The head exists only then: at 0 the parameters, the state_dict keys and
+        # every launch are the reference model's.  Blank = <PAD> = index 0, which is never a label.
+        self.ctc_weight = float(ctc_weight)
+        if not 0.0 <= self.ctc_weight <= 1.0:
+            raise ValueError("ctc_weight must lie in [0, 1], got %r" % (ctc_weight,))
+        if self.ctc_weight > 0:
+            if pad != 0:
+                raise ValueError("the CTC branch takes <PAD> = 0 as its blank; pad is %d" % pad)
+            self.ctc_lo = torch.nn.Linear(enc_hidden_dim, output_dim)
 
     accepts_loss_norm = True           # (parallel.sup_local_loss: this forward takes the loss's normaliser along)
 
@@ -450,9 +460,27 @@ class E2E(torch.nn.Module):
         if data.is_cuda:
             hb.upload_side_stream_for(data.shape[0] * data.shape[1])       # small uploads leave the compute stream when the GPU is the bottleneck
         enc_h, enc_lens = self.encoder(data, ilens, total_length)
-        return self.decoder(enc_h, enc_lens, ys, tf_rate=tf_rate, max_dec_timesteps=max_dec_timesteps, sample=sample,
-                            smooth=smooth, scaling=scaling, label_smoothing=label_smoothing, olength=olength,
-                            loss_norm=loss_norm)
+        out = self.decoder(enc_h, enc_lens, ys, tf_rate=tf_rate, max_dec_timesteps=max_dec_timesteps, sample=sample,
+                           smooth=smooth, scaling=scaling, label_smoothing=label_smoothing, olength=olength,
+                           loss_norm=loss_norm)
+        if self.ctc_weight > 0 and ys is not None and len(ys) > 0:
+            # the CTC term rides on ys_log_probs, where the attention loss's kernel sum rides already (Decoder.forward):
+            # parallel.local_loss forms (1 - w) L_att + w L_ctc from them.  Decoding (ys=None) never gets here.
+            nll = self.ctc_nll(enc_h, ys)
+            norm = float(loss_norm) if loss_norm else float(len(ys))
+            lp = out[1]
+            lp.ctc_nll, lp.ctc_loss, lp.ctc_norm, lp.ctc_weight = nll, nll.sum() * (1.0 / norm), norm, self.ctc_weight
+        return out
+
+    def ctc_nll(self, enc_h, ys):
+        """Per-utterance CTC negative log-likelihood [B] of the labels `ys` given the encoder output enc_h [B, T', H] of the
+        forward that has just run (the frame lengths are the encoder's device copy): ctc_lo over the B T' rows on the GEMM,
+        then ops.ctc_loss on the raw logits.  An utterance with fewer frames than its labels need counts as 0
+        (zero_infinity), like torch.nn.functional.ctc_loss(zero_infinity=True)."""
+        bsz, frames, hid = enc_h.shape
+        logits = ops.linear(enc_h.reshape(bsz * frames, hid), self.ctc_lo.weight, self.ctc_lo.bias).view(bsz, frames, -1)
+        labels = torch.cat([y.reshape(-1) for y in ys]).to(device=enc_h.device, dtype=torch.long)
+        return ops.ctc_loss(logits, self.encoder.enc2.last_lens_dev, labels, [int(y.size(0)) for y in ys], True)
 
     def recognize_beams(self, data, ilens, max_dec_timesteps, topk, length_penalty=0.0, nbest=False, *, lm=None,
                         lm_weight=0.0):

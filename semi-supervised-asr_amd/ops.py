@@ -935,6 +935,66 @@ def label_logprob(logits, index, labeldist=None, ls_weight=0.0, with_sum=False, 
     return res if len(res) > 1 else out
 
 
+class _CtcLoss(torch.autograd.Function):
+    """CTC negative log-likelihood per utterance of RAW logits [B, T', V] (blank = 0; the log-softmax is the kernel's) ->
+    nll [B]: asr_ctc_loss_fwd / _bwd (csrc/ctc.hip), two launches each way.  The workspace (alpha, the per-frame
+    log-sum-exps, the sorted label positions) is leased from the pool from the forward to the end of the backward, like the
+    other sequence operators'; without autograd a fresh tensor.  Ordered sums only: nothing here depends on
+    hb.is_deterministic().  No host synchronisation: the label lengths are host integers already."""
+
+    @staticmethod
+    def forward(ctx, logits, frame_lens, labels, label_lens, zero_infinity):
+        B, T, V = logits.shape
+        # a [B, T, V] view of a wider row-major buffer goes in as it is (row stride = ld)
+        if not (logits.stride(2) == 1 and logits.stride(1) >= V and logits.stride(0) == T * logits.stride(1)):
+            logits = logits.contiguous()
+        ld = logits.stride(1)
+        lens = [int(n) for n in label_lens]
+        if len(lens) != B:
+            raise ValueError("ctc_loss: %d label lengths for %d utterances" % (len(lens), B))
+        offsets = [0]
+        for n in lens:
+            offsets.append(offsets[-1] + n)
+        if offsets[-1] != labels.numel():
+            raise ValueError("ctc_loss: the label lengths sum to %d, the packed labels hold %d" % (offsets[-1], labels.numel()))
+        lmax = max(lens)
+        dev = logits.device
+        words = (hb.ctc_ws_bytes(B, T, V, lmax) + 3) // 4
+        if ctx.needs_input_grad[0]:                  # (grad mode is off inside forward: ask the node)
+            cap = _row_capacity(words)
+            ctx.lease = _POOL.acquire(("ctc", str(dev), cap), lambda: torch.empty(cap, device=dev, dtype=torch.float32))
+            ws = ctx.lease.ws
+        else:
+            ctx.lease, ws = None, torch.empty(words, device=dev, dtype=torch.float32)
+        offs_dev = hb.to_device_i32(offsets, dev)
+        labels = labels.contiguous()
+        nll = torch.empty(B, device=dev, dtype=torch.float32)
+        hb.ctc_loss_fwd(logits, ld, frame_lens, labels, offs_dev, lmax, zero_infinity, nll, ws)
+        ctx.save_for_backward(logits, frame_lens, labels, offs_dev)
+        ctx.ld, ctx.lmax, ctx.zero_infinity = ld, lmax, bool(zero_infinity)
+        return nll
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, frame_lens, labels, offs_dev = ctx.saved_tensors
+        if ctx.lease is None or ctx.lease.ws is None:
+            raise RuntimeError("ctc_loss: the backward runs once, behind a forward that ran with autograd enabled")
+        B, T, V = logits.shape
+        dz = torch.empty(B, T, V, device=logits.device, dtype=torch.float32)
+        hb.ctc_loss_bwd(logits, ctx.ld, frame_lens, labels, offs_dev, ctx.lmax, ctx.zero_infinity, g.contiguous(),
+                        ctx.lease.ws, dz, V)
+        ctx.lease.release()
+        return dz, None, None, None, None
+
+
+def ctc_loss(logits, frame_lens_dev, labels_packed, label_lens, zero_infinity=True):
+    """-> nll [B], the CTC negative log-likelihood of each utterance.  logits [B, T', V] fp32 raw (not log-softmaxed),
+    frame_lens_dev int32 [B] on the device (Encoder.last_lens_dev), labels_packed the batch's labels as ONE int64 device
+    tensor, label_lens their counts per utterance (host integers).  Blank = 0.  zero_infinity: an utterance without any
+    alignment gives loss 0 and a zero gradient (torch.nn.functional.ctc_loss's flag); otherwise +inf."""
+    return _CtcLoss.apply(logits, frame_lens_dev, labels_packed, label_lens, zero_infinity)
+
+
 def decoder_sequence(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo, w_out, b_out, w0, opts):
     opts = dict(opts)
     opts["pooled"] = torch.is_grad_enabled() and (P.requires_grad or w_hh.requires_grad)

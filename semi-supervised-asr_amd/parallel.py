@@ -88,11 +88,25 @@ def local_loss(log_probs, info):
     loss = getattr(log_probs, "fused_loss", None)
     if loss is not None:                     # the kernel scaled its sum already (Decoder.forward, loss_norm)
         have = log_probs.fused_loss_scale
-        return loss if abs(have - want) <= 1e-12 * abs(want) else loss * (want / have)
+        return joint_loss(loss if abs(have - want) <= 1e-12 * abs(want) else loss * (want / have), log_probs, info)
     total = getattr(log_probs, "fused_sum", None)
     if total is None:
         total = log_probs.sum()
-    return total * want
+    return joint_loss(total * want, log_probs, info)
+
+
+def joint_loss(att, log_probs, info):
+    """(1 - w) L_att + w L_ctc when the forward carried a CTC term along (E2E(ctc_weight > 0) sets, on its log-probs,
+    ctc_loss = this shard's sum of per-utterance CTC nll / ctc_norm, ctc_norm = the number of utterances it divided by, and
+    ctc_weight = w); the attention loss alone otherwise.  L_ctc is normalised per utterance by the GLOBAL batch size, like
+    L_att, so the rank-local joint losses sum to the single-process one."""
+    ctc = getattr(log_probs, "ctc_loss", None)
+    if ctc is None:
+        return att
+    w, have, want = float(log_probs.ctc_weight), float(log_probs.ctc_norm), float(info["b_global"])
+    if have != want:
+        ctc = ctc * (have / want)
+    return (1.0 - w) * att + w * ctc
 
 
 _ONE = {}

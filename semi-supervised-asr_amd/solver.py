@@ -107,8 +107,20 @@ class Solver(object):
 
     def load_model(self, model_path, load_optimizer):
         print(f"Load model from {model_path}.ckpt")
-        self.model.load_state_dict(torch.load(f"{model_path}.ckpt", map_location="cpu"))
+        state = torch.load(f"{model_path}.ckpt", map_location="cpu")
+        head = [k for k in self.model.state_dict() if k.startswith("ctc_lo.")]
+        headless = bool(head) and not any(k in state for k in head)
+        if headless:
+            # an attention-only checkpoint into a model with the CTC branch (`ctc_weight` > 0): everything else loads, the
+            # head keeps its initialisation
+            if self.rank == 0:
+                print(f"{model_path}.ckpt has no CTC head ({', '.join(head)}): the head keeps its initialisation")
+            state = dict(state, **{k: v for k, v in self.model.state_dict().items() if k in head})
+        self.model.load_state_dict(state)
         if load_optimizer:
+            if headless:
+                raise RuntimeError(f"{model_path}.opt belongs to a model without the CTC head: the optimiser state of an "
+                                   "attention-only run cannot be resumed with `ctc_weight` > 0 (set load_optimizer: false)")
             print(f"Load optmizer from {model_path}.opt")
             self.gen_opt.load_state_dict(torch.load(f"{model_path}.opt", map_location="cpu"))
 
@@ -191,7 +203,10 @@ class Solver(object):
             att_dim=cfg["att_dim"], conv_channels=cfg["conv_channels"], conv_kernel_size=cfg["conv_kernel_size"],
             att_odim=cfg["att_odim"], output_dim=len(self.vocab), embedding_dim=cfg["embedding_dim"],
             ls_weight=cfg["ls_weight"], labeldist=self.labeldist, pad=self.vocab["<PAD>"], bos=self.vocab["<BOS>"],
-            eos=self.vocab["<EOS>"]))
+            eos=self.vocab["<EOS>"],
+            # `ctc_weight` (not a reference key; default 0): w > 0 adds the CTC branch on the encoder and every labeled
+            # step trains on (1 - w) L_att + w L_ctc; at 0 the model is the reference's
+            ctc_weight=float(cfg.get("ctc_weight", 0.0))))
         # `dp_overlap` (not a reference key): issue the gradient all-reduce in buckets from inside the backward pass
         # (parallel.FlatBuffers.enable_overlap).  Off by default HERE: an RCCL kernel that is resident while a persistent
         # kernel is being placed could - if the two do not fit a CU together and a rank is late - hold that kernel's
@@ -297,7 +312,7 @@ class Solver(object):
         """Teacher-forced dev loss + greedy CER (solver.py:212-242); greedy pass runs without autograd."""
         self.flush()
         self.model.eval()
-        preds, refs, total = [], [], 0.0
+        preds, refs, total, ctc_total = [], [], 0.0, None
         for batch in self._feed(self.dev_loader, sharded=False):
             xs, ilens, ys = batch
             with torch.no_grad():
@@ -308,9 +323,18 @@ class Solver(object):
                     _, log_probs, _, _ = self.model(xs, ilens, ys=ys)
                     value = self.model.mask_and_cal_loss(log_probs, ys).item()
                 total += value
+                if getattr(log_probs, "ctc_loss", None) is not None:      # the CTC branch's own dev loss, per utterance
+                    ctc_total = (ctc_total or 0.0) + log_probs.ctc_loss.item()
             preds += self._greedy(xs, ilens)
             refs += batch.ys_host
         self.model.train()
+        # (the returned dev loss stays the attention loss, so that runs with and without the CTC branch compare)
+        self.val_ctc_loss = None if ctc_total is None else ctc_total / len(self.dev_loader)
+        if self.val_ctc_loss is not None:
+            self._val_rounds = getattr(self, "_val_rounds", 0) + 1
+            if self.rank == 0:
+                print(f"val_ctc_loss={self.val_ctc_loss:.4f}")
+            self.logger.scalar_summary(f"{self.config['tag']}/supervised/val_ctc_loss", self.val_ctc_loss, self._val_rounds - 1)
         cer, hyp_sents, ref_sents = self.ind2sent(preds, refs)
         return total / len(self.dev_loader), cer, hyp_sents, ref_sents
 
