@@ -901,6 +901,63 @@ int asr_ctc_loss_bwd(int B, int T, int V, const float* logits, int64_t ld, const
                      const int32_t* label_offsets, int max_label_len, int zero_infinity, const float* grad_nll, void* ws,
                      int64_t ws_bytes, float* dlogits, int64_t lddz, asr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Joint CTC-attention decoding: the CTC prefix score inside the beam search (csrc/ctc_prefix.hip, the CTC variants of the
+ * select kernel in csrc/beam.hip).  Four entries added to ABI version 8 WITHOUT a version change, like the CTC
+ * loss entries: additive - no existing entry, structure or constant changes, and asr_beam_select_f32 /
+ * asr_beam_select_lm_f32 launch the kernels they launched before.
+ * With x[t][v] = logits[b][t][v] - logsumexp_v logits[b][t] over the T_b = frame_lens[b] valid frames (frames behind T_b are
+ * never read), every beam row b*K+k carries, for its prefix g: r_n[t], r_b[t] (log-probability of g ending at frame t in a
+ * non-blank / a blank) as pairs state[slot][row][t][2], last[slot][row] (g's last token; -1: g is empty) and
+ * psi_prev[row] = psi(g).  (+) is log(exp a + exp b) with (-inf) (+) (-inf) = -inf.
+ *   asr_ctc_prefix_init_f32     once per search, one launch: lse [B][Tp], and for all B*K rows slot 0 = the empty prefix:
+ *                               r_n[t] = -inf, r_b[t] = sum_{tau <= t} x[tau][blank] (a wave scan: 64 frames per round,
+ *                               the earlier rounds' total added behind it - an order fixed by T_b), last = -1, psi_prev = 0.
+ *                               host_lens (may be NULL): the caller's host copy of frame_lens where it has one - a length
+ *                               < 1 or > Tp is ASR_E_SHAPE.  The kernels clamp the device value to 0 .. Tp: an utterance
+ *                               without frames scores every candidate -inf.
+ *   asr_ctc_prefix_score_f32    per step, before the select: for every row with score > -inf of an utterance that is not
+ *                               done (p: the search; other rows of psi are left as they are), from `slot`:
+ *                                 phi[t] = r_b[t] if c == last, else r_n[t] (+) r_b[t]
+ *                                 psi[row][c] = p0 (+) (+)_{t = 1 .. T_b-1} (phi[t-1] + x[t][c]),  p0 = x[0][c] if g is empty
+ *                                 else -inf;  psi[row][eos] = r_n[T_b-1] (+) r_b[T_b-1];  psi[row][blank] = -inf.
+ *                               A reduction over the frames, no state per candidate: memory is 2 R Tp 2 floats of state,
+ *                               R V of psi and B Tp of lse, whatever L is.
+ *   asr_beam_select_ctc_f32     asr_beam_select_f32 / asr_beam_select_lm_f32 (lm_logits NULL: no LM) on the candidate score
+ *                                 c = score[k] + (1 - ctc_weight) * logp[v];  c = c + ctc_weight * (psi[k][v] - psi_prev[k]);
+ *                                 with an LM: c = c + lm_weight * logp_lm[v]
+ *                               fp32, each operation (1 - ctc_weight and the difference included) rounded on its own, in
+ *                               this order.  A candidate that comes out -inf or NaN never enters, so a blank is never
+ *                               emitted.  ctc_weight must lie in [0, 1] (ASR_E_ARG); with ctc_weight = 0 psi is not read:
+ *                               the launch IS asr_beam_select_f32's (asr_beam_select_lm_f32's), the same kernel.
+ *   asr_ctc_prefix_advance_f32  per step, after the select: for every row b*K+j with score > -inf of an utterance that is
+ *                               not done, with src = b*K + bp_hist[t][b][j], c = tok_hist[t][b][j], phi of src_slot's row
+ *                               src as above: dst_slot's row gets n[0] = p0, b[0] = -inf,
+ *                                 n[t] = (n[t-1] (+) phi[t-1]) + x[t][c],  b[t] = (n[t-1] (+) b[t-1]) + x[t][blank],
+ *                               last = c, and psi_prev[row] = psi[src][c].  Out of place: src_slot == dst_slot (or state[0]
+ *                               == state[1]) is ASR_E_ARG.  One launch.
+ * K > ASR_BEAM_KMAX, V < 3, eos or blank outside [0, V), eos == blank, B*K > 65 535: ASR_E_SHAPE.  B, K, V, eos must be
+ * the search's (ASR_E_ARG).  No atomics, no host synchronisation, no allocation.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  int B, K, V, Tp;           /* utterances, beam width, vocabulary, padded encoder frames */
+  int blank, eos;
+  const float* logits;       /* [B][Tp] rows of ld >= V floats: RAW CTC logits */
+  int64_t ld;
+  const int32_t* frame_lens; /* [B] on the device */
+  float* lse;                /* [B][Tp] */
+  float* state[2];           /* [B*K][Tp][2] (r_n, r_b), two slots, 8-byte aligned (ASR_E_ALIGN) */
+  int32_t* last[2];          /* [B*K] last token of the prefix, -1 while it is empty */
+  float* psi;                /* [B*K][V] */
+  float* psi_prev;           /* [B*K] */
+} asr_ctc_prefix_t;
+int asr_ctc_prefix_init_f32(const asr_ctc_prefix_t* c, const int32_t* host_lens, asr_stream_t stream);
+int asr_ctc_prefix_score_f32(const asr_ctc_prefix_t* c, const asr_beam_t* p, int slot, asr_stream_t stream);
+int asr_beam_select_ctc_f32(const asr_beam_t* p, const float* lm_logits, float lm_weight, const float* psi,
+                            const float* psi_prev, float ctc_weight, int t, asr_stream_t stream);
+int asr_ctc_prefix_advance_f32(const asr_ctc_prefix_t* c, const asr_beam_t* p, int t, int src_slot, int dst_slot,
+                               asr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,8 @@
 //                 embedding of its new token;
 // With a language model (shallow fusion) the select kernel's LM variant adds lm_weight * log_softmax(lm_logits)
 // to every candidate, and beam_reorder_lm gathers the LM's h / c of every layer (and the decoder's state) in one launch.
+// With the CTC prefix score (joint CTC-attention decoding; csrc/ctc_prefix.hip computes psi) the select kernel's
+// CTC variants rank score + (1 - w) logp + w (psi - psi_prev) (+ lm_weight * logp_lm).
 // And once at the end
 //   beam_backtrack  one workgroup per utterance: rank the finished hypotheses, follow the backpointers into token rows.
 #include <float.h>
@@ -35,9 +37,21 @@ __device__ __forceinline__ float beam_wave_max(float v) {
 
 // M: the per-thread candidate list length, a power of two >= 2K.  LM: candidates are score + logp + lmw * logp_lm (each
 // operation rounded on its own, in this order); without it lm_logits / lmw are not read and the code is the plain select's.
-template <int M, bool LM>
+// CTC: the candidate starts as score + (1 - w) * logp, then + w * (psi - psi_prev), then the LM's term - every operation
+// rounded on its own again; without it the kernel has no CTC argument at all (an empty structure) and its code is the
+// plain / LM select's.
+template <bool CTC>
+struct beam_ctc_args {
+  const float* psi;        // [B*K][V]
+  const float* psi_prev;   // [B*K]
+  float w;
+};
+template <>
+struct beam_ctc_args<false> {};
+
+template <int M, bool LM, bool CTC>
 __global__ __launch_bounds__(BEAM_NT) void beam_select_kernel(asr_beam_t p, int t, const float* __restrict__ lm_logits,
-                                                              float lmw) {
+                                                              float lmw, beam_ctc_args<CTC> ca) {
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = p.K, V = p.V, B = p.B;
   if (p.done[b]) return;                                   // finished utterances are left untouched
@@ -89,8 +103,18 @@ __global__ __launch_bounds__(BEAM_NT) void beam_select_kernel(asr_beam_t p, int 
     const float* row = lg + (int64_t)k * V;
     const float* lrow = LM ? lm_logits + ((int64_t)b * K + k) * V : nullptr;
     const float lmm = LM ? s_lmmax[k] : 0.f, lml = LM ? s_lmlsum[k] : 0.f;
+    const float* prow = nullptr;
+    float pprev = 0.f, omw = 0.f, cw = 0.f;
+    if constexpr (CTC) {
+      prow = ca.psi + ((int64_t)b * K + k) * V;
+      pprev = ca.psi_prev[b * K + k], cw = ca.w, omw = __fsub_rn(1.f, cw);
+    }
     for (int v = tid; v < V; v += BEAM_NT) {
       float c = sc + ((row[v] - m) - ls);
+      if (CTC) {
+        c = __fadd_rn(sc, __fmul_rn(omw, (row[v] - m) - ls));
+        c = __fadd_rn(c, __fmul_rn(cw, __fsub_rn(prow[v], pprev)));
+      }
       if (LM) c = __fadd_rn(c, __fmul_rn(lmw, (lrow[v] - lmm) - lml));   // no fused multiply-add: the order is the contract
       if (c > lv[M - 1]) {                                 // -inf and NaN never enter
         int ci = k * V + v;
@@ -285,18 +309,24 @@ int check_beam(const asr_beam_t* p, bool need_logits) {
   return 0;
 }
 
-template <bool LM>
-int beam_select_launch(const asr_beam_t* p, const float* lm_logits, float lmw, int t, hipStream_t stream) {
+template <bool LM, bool CTC = false>
+int beam_select_launch(const asr_beam_t* p, const float* lm_logits, float lmw, int t, hipStream_t stream,
+                       const float* psi = nullptr, const float* psi_prev = nullptr, float cw = 0.f) {
   int rc = check_beam(p, true);
   if (rc) return rc;
   if (t < 0 || t >= p->L) return ASR_E_ARG;
   const dim3 grid(p->B), block(BEAM_NT);
   const int m = 2 * p->K;
-  if (m <= 2) hipLaunchKernelGGL((beam_select_kernel<2, LM>), grid, block, 0, stream, *p, t, lm_logits, lmw);
-  else if (m <= 4) hipLaunchKernelGGL((beam_select_kernel<4, LM>), grid, block, 0, stream, *p, t, lm_logits, lmw);
-  else if (m <= 8) hipLaunchKernelGGL((beam_select_kernel<8, LM>), grid, block, 0, stream, *p, t, lm_logits, lmw);
-  else if (m <= 16) hipLaunchKernelGGL((beam_select_kernel<16, LM>), grid, block, 0, stream, *p, t, lm_logits, lmw);
-  else hipLaunchKernelGGL((beam_select_kernel<32, LM>), grid, block, 0, stream, *p, t, lm_logits, lmw);
+  beam_ctc_args<CTC> ca;
+  if constexpr (CTC) ca.psi = psi, ca.psi_prev = psi_prev, ca.w = cw;
+#define BEAM_SELECT(M_) \
+  hipLaunchKernelGGL((beam_select_kernel<M_, LM, CTC>), grid, block, 0, stream, *p, t, lm_logits, lmw, ca)
+  if (m <= 2) BEAM_SELECT(2);
+  else if (m <= 4) BEAM_SELECT(4);
+  else if (m <= 8) BEAM_SELECT(8);
+  else if (m <= 16) BEAM_SELECT(16);
+  else BEAM_SELECT(32);
+#undef BEAM_SELECT
   ASR_CHECK_LAUNCH();
   return 0;
 }
@@ -319,6 +349,19 @@ extern "C" int asr_beam_select_lm_f32(const asr_beam_t* p, const float* lm_logit
                                       asr_stream_t stream_) {
   if (!lm_logits) return ASR_E_ARG;
   return beam_select_launch<true>(p, lm_logits, lm_weight, t, (hipStream_t)stream_);
+}
+
+extern "C" int asr_beam_select_ctc_f32(const asr_beam_t* p, const float* lm_logits, float lm_weight, const float* psi,
+                                       const float* psi_prev, float ctc_weight, int t, asr_stream_t stream_) {
+  if (!(ctc_weight >= 0.f && ctc_weight <= 1.f)) return ASR_E_ARG;
+  hipStream_t stream = (hipStream_t)stream_;
+  if (ctc_weight == 0.f)                                    // psi is not read: the plain / LM select, the same kernel
+    return lm_logits ? beam_select_launch<true>(p, lm_logits, lm_weight, t, stream)
+                     : beam_select_launch<false>(p, nullptr, 0.f, t, stream);
+  if (!psi || !psi_prev) return ASR_E_ARG;
+  if (p && p->V < 3) return ASR_E_SHAPE;
+  return lm_logits ? beam_select_launch<true, true>(p, lm_logits, lm_weight, t, stream, psi, psi_prev, ctc_weight)
+                   : beam_select_launch<false, true>(p, nullptr, 0.f, t, stream, psi, psi_prev, ctc_weight);
 }
 
 extern "C" int asr_beam_reorder_f32(const asr_beam_t* p, int t, const asr_beam_state_t* s, asr_stream_t stream_) {

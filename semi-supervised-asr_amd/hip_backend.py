@@ -29,6 +29,7 @@ EXPORTS = (
     "asr_colsum_det_f32", "asr_gemm_det_f32", "asr_gemm_det_ws_bytes", "asr_embedding_grad_det_f32", "asr_rows_fill_grad_det_f32",
     "asr_sumsq_det_f32", "asr_gather_sumsq_det_f32", "asr_sum_det_f32", "asr_dec_step_bwd_det", "asr_dec_seq_bwd_det",
     "asr_ctc_ws_bytes", "asr_ctc_loss_fwd", "asr_ctc_loss_bwd",
+    "asr_ctc_prefix_init_f32", "asr_ctc_prefix_score_f32", "asr_beam_select_ctc_f32", "asr_ctc_prefix_advance_f32",
 )
 
 _lib = None
@@ -94,6 +95,13 @@ class BeamLmState(ctypes.Structure):
     """asr_beam_lm_state_t"""
     _fields_ = [("n_layers", c_i), ("H", c_i), ("in_dim", c_i * LM_MAX_LAYERS)] + \
                [(n, c_p * LM_MAX_LAYERS) for n in ("x_src", "x_dst", "c_src", "c_dst")] + [("emb", c_p)]
+
+
+class CtcPrefix(ctypes.Structure):
+    """asr_ctc_prefix_t"""
+    _fields_ = [(n, c_i) for n in ("B", "K", "V", "Tp", "blank", "eos")] + \
+               [("logits", c_p), ("ld", ctypes.c_int64), ("frame_lens", c_p), ("lse", c_p), ("state", c_p * 2), ("last", c_p * 2),
+                ("psi", c_p), ("psi_prev", c_p)]
 
 
 class GemmPlan(ctypes.Structure):
@@ -255,6 +263,10 @@ def load():
     lib.asr_ctc_ws_bytes.argtypes = [c_i, c_i, c_i, c_i, ctypes.POINTER(c_i64)]
     lib.asr_ctc_loss_fwd.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i64, c_p]
     lib.asr_ctc_loss_bwd.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i64, c_p, c_i64, c_p]
+    lib.asr_ctc_prefix_init_f32.argtypes = [ctypes.POINTER(CtcPrefix), ctypes.POINTER(ctypes.c_int32), c_p]
+    lib.asr_ctc_prefix_score_f32.argtypes = [ctypes.POINTER(CtcPrefix), ctypes.POINTER(Beam), c_i, c_p]
+    lib.asr_beam_select_ctc_f32.argtypes = [ctypes.POINTER(Beam), c_p, c_f, c_p, c_p, c_f, c_i, c_p]
+    lib.asr_ctc_prefix_advance_f32.argtypes = [ctypes.POINTER(CtcPrefix), ctypes.POINTER(Beam), c_i, c_i, c_i, c_p]
     lib.asr_dec_feedback_fwd.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_p, c_i64,
                                          c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
     lib.asr_dec_feedback_bwd.argtypes = [c_i, c_i, c_i, c_i, c_p, c_p, c_i64, c_p, c_p, c_p, c_f, c_p, c_p]
@@ -618,6 +630,17 @@ class BeamSearch:
         check(load().asr_beam_select_lm_f32(ctypes.byref(self.struct), ptr(lm_logits), float(lm_weight), int(t), stream()),
               "asr_beam_select_lm_f32")
 
+    def select_ctc(self, logits, ctc, ctc_weight, t, lm_logits=None, lm_weight=0.0):
+        """select() / select_lm() (lm_logits given) with the CTC prefix score of `ctc` (CtcPrefixState, after its score()):
+        score + (1 - ctc_weight) * logp + ctc_weight * (psi - psi_prev) (+ lm_weight * logp_lm) - DESIGN 4.15.
+        ctc_weight = 0 launches the plain / LM select."""
+        assert logits.is_contiguous() and tuple(logits.shape) == (self.B * self.K, self.V)
+        assert lm_logits is None or (lm_logits.is_contiguous() and lm_logits.shape == logits.shape)
+        assert tuple(ctc.psi.shape) == (self.B * self.K, self.V)
+        self.struct.logits = ptr(logits)
+        check(load().asr_beam_select_ctc_f32(ctypes.byref(self.struct), ptr(lm_logits), float(lm_weight), ptr(ctc.psi),
+                                             ptr(ctc.psi_prev), float(ctc_weight), int(t), stream()), "asr_beam_select_ctc_f32")
+
     @staticmethod
     def _state(x_src, x_dst, c_src, c_dst, w_src, w_dst, emb, D, O):
         assert x_dst.stride(0) == x_src.stride(0) and emb.is_contiguous()
@@ -649,6 +672,61 @@ class BeamSearch:
         check(load().asr_beam_backtrack(ctypes.byref(self.struct), float(length_penalty), ptr(tokens), ptr(scores),
                                         ptr(lengths), stream()), "asr_beam_backtrack")
         return tokens, scores, lengths
+
+
+class CtcPrefixState:
+    """The CTC prefix scorer's state beside a BeamSearch (asr_ctc_prefix_t, csrc/ctc_prefix.hip): for the
+    R = B*K beam rows state [2, R, Tp, 2] ((r_n, r_b) per frame, two slots), last [2, R] (the prefix's last token, -1 while
+    it is empty), psi [R, V], psi_prev [R], and lse [B, Tp] - nothing that grows with the number of steps.
+    logits [B, Tp, V] fp32 RAW CTC logits (a view with unit column stride and row stride >= V is taken as it is),
+    frame_lens int32 [B] on the device; lens_host: the host's copy of them where it has one (checked: 1 .. Tp).
+    The constructor runs the init kernel (slot 0 = the empty prefix); per step score() before the select, advance(t)
+    after it - `cur` is the slot that holds the live prefixes."""
+
+    def __init__(self, search, logits, frame_lens, blank=0, lens_host=None):
+        B, Tp, V = logits.shape
+        if (B, V) != (search.B, search.V):
+            raise ValueError("CTC logits %s do not fit a search over %d utterances and %d tokens"
+                             % (tuple(logits.shape), search.B, search.V))
+        if frame_lens.dtype != torch.int32 or tuple(frame_lens.shape) != (B,):
+            raise ValueError("frame_lens must be int32 [%d] on the device" % B)
+        if not (logits.stride(2) == 1 and logits.stride(1) >= V and logits.stride(0) == Tp * logits.stride(1)):
+            logits = logits.contiguous()
+        dev = logits.device
+        R = B * search.K
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.search, self.logits, self.frame_lens, self.cur = search, _dev(logits, "ctc logits"), frame_lens, 0
+        self.lse = torch.empty(B, Tp, **f32)
+        self.state = torch.empty(2, R, Tp, 2, **f32)
+        self.last = torch.empty(2, R, dtype=torch.int32, device=dev)
+        self.psi = torch.full((R, V), float("-inf"), **f32)
+        self.psi_prev = torch.empty(R, **f32)
+        st = CtcPrefix(B=B, K=search.K, V=V, Tp=Tp, blank=blank, eos=search.eos, logits=ptr(self.logits),
+                       ld=self.logits.stride(1), frame_lens=ptr(frame_lens), lse=ptr(self.lse), psi=ptr(self.psi),
+                       psi_prev=ptr(self.psi_prev))
+        for i in range(2):
+            st.state[i], st.last[i] = self.state[i].data_ptr(), self.last[i].data_ptr()
+        self.struct = st
+        host = None
+        if lens_host is not None:
+            host = (ctypes.c_int32 * B)(*[int(n) for n in lens_host])
+        rc = load().asr_ctc_prefix_init_f32(ctypes.byref(st), host, stream())
+        if rc == ASR_E_SHAPE:
+            raise UnsupportedShape("ctc prefix scorer: K %d, V %d, blank %d, eos %d, frames %s of %d (V >= 3, blank != eos, "
+                                   "1 .. T' frames)" % (search.K, V, blank, search.eos, lens_host, Tp))
+        check(rc, "asr_ctc_prefix_init_f32")
+
+    def score(self):
+        """psi [R, V] of the live rows' candidates from slot `cur` (rows that are dead or done keep what they hold)."""
+        check(load().asr_ctc_prefix_score_f32(ctypes.byref(self.struct), ctypes.byref(self.search.struct), self.cur, stream()),
+              "asr_ctc_prefix_score_f32")
+
+    def advance(self, t):
+        """After the select of step t: every live row's extended prefix, from its predecessor in slot `cur` into the other
+        slot, which becomes `cur`."""
+        check(load().asr_ctc_prefix_advance_f32(ctypes.byref(self.struct), ctypes.byref(self.search.struct), int(t), self.cur,
+                                                1 - self.cur, stream()), "asr_ctc_prefix_advance_f32")
+        self.cur = 1 - self.cur
 
 
 ED_MAX_COLS = 4096         # ASR_ED_MAX_COLS

@@ -391,14 +391,29 @@ class Decoder(torch.nn.Module):
         return logits.transpose(0, 1), ys_log_probs, prediction, ws
 
     def recognize_beams(self, enc_pad, enc_len, max_dec_timesteps, topk, length_penalty=0.0, nbest=False, *, lm=None,
-                        lm_weight=0.0):
+                        lm_weight=0.0, ctc_logits=None, ctc_lens=None, ctc_decode_weight=0.0):
         """Beam search with beam width topk (1..16) - model.py:369-406, which the reference left unfinished; the semantics
         are DESIGN 4.8's.  Eval arithmetic (no dropout, attention temperature 2.0), per utterance; hypotheses are ranked by
         score / len**length_penalty (score: the sum of the tokens' log-probabilities, <EOS> included).
         lm (an LM module) with lm_weight != 0: shallow fusion - every candidate token's score is
         log p_asr + lm_weight * log p_lm, the LM stepped on the device beside the decoder, eval arithmetic.
+        ctc_logits [B, T', V] (raw logits of a CTC head on enc_pad, blank = <PAD> = 0) and ctc_lens (int32 [B] on the device:
+        the valid frames) with ctc_decode_weight in (0, 1]: joint CTC-attention decoding - a token scores
+        (1 - w) log p_asr + w (psi(g c) - psi(g)) with psi the CTC prefix score, computed on the device per step; it combines
+        with the LM's term.  At 0 (or without the logits) the search is the one without it.
         -> (prediction [B, L] int64, scores [B]): the best hypothesis, <EOS>-padded to L = max_dec_timesteps; with
         nbest=True all topk hypotheses, ranked: ([B, topk, L], [B, topk]).  topk = 1 is greedy decoding."""
+        ctc_decode_weight = float(ctc_decode_weight)
+        if not 0.0 <= ctc_decode_weight <= 1.0:
+            raise ValueError("ctc_decode_weight must lie in [0, 1], got %r" % (ctc_decode_weight,))
+        ctc_t = None
+        if ctc_decode_weight > 0:
+            if ctc_logits is None or ctc_lens is None:
+                raise ValueError("ctc_decode_weight %g needs ctc_logits and ctc_lens" % ctc_decode_weight)
+            if self.pad != 0:
+                raise ValueError("the CTC prefix score takes <PAD> = 0 as its blank; pad is %d" % self.pad)
+            host = [int(n) for n in enc_len] if isinstance(enc_len, (list, tuple)) else None
+            ctc_t = dict(logits=ctc_logits, frame_lens=ctc_lens, lens_host=host)
         lm_t = None
         if lm is not None:
             V = self.output_layer.weight.shape[0]
@@ -420,7 +435,8 @@ class Decoder(torch.nn.Module):
                 P, Q, self.embedding.weight, cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh,
                 att.mlp_dec.weight, att.loc_conv.weight, att.mlp_att.weight, att.gvec.weight, att.mlp_o.bias,
                 self.output_layer.weight, self.output_layer.bias, w0, int(topk), int(max_dec_timesteps), self.bos,
-                self.eos, length_penalty=float(length_penalty), lm=lm_t, lm_weight=float(lm_weight))
+                self.eos, length_penalty=float(length_penalty), lm=lm_t, lm_weight=float(lm_weight), ctc=ctc_t,
+                ctc_weight=ctc_decode_weight)
             tokens = tokens.long()
         if nbest:
             return tokens, scores
@@ -483,14 +499,27 @@ class E2E(torch.nn.Module):
         return ops.ctc_loss(logits, self.encoder.enc2.last_lens_dev, labels, [int(y.size(0)) for y in ys], True)
 
     def recognize_beams(self, data, ilens, max_dec_timesteps, topk, length_penalty=0.0, nbest=False, *, lm=None,
-                        lm_weight=0.0):
-        """Encoder, then Decoder.recognize_beams (not a reference method)."""
+                        lm_weight=0.0, ctc_decode_weight=0.0):
+        """Encoder, then Decoder.recognize_beams (not a reference method).  ctc_decode_weight in (0, 1]: joint CTC-attention
+        decoding with the model's CTC head - it needs a model built with ctc_weight > 0; the weight of the
+        training loss (self.ctc_weight) and this one are separate."""
+        ctc_decode_weight = float(ctc_decode_weight)
+        if not 0.0 <= ctc_decode_weight <= 1.0:
+            raise ValueError("ctc_decode_weight must lie in [0, 1], got %r" % (ctc_decode_weight,))
+        if ctc_decode_weight > 0 and not hasattr(self, "ctc_lo"):
+            raise ValueError("ctc_decode_weight %g needs the CTC head: build the model with ctc_weight > 0" % ctc_decode_weight)
         if data.is_cuda:
             hb.upload_side_stream_for(data.shape[0] * data.shape[1])
         with torch.no_grad():
             enc_h, enc_lens = self.encoder(data, ilens)
+            ctc_logits = ctc_lens = None
+            if ctc_decode_weight > 0:                  # the product ctc_nll forms, on the frames the decoder attends to
+                bsz, frames, hid = enc_h.shape
+                ctc_logits = ops.linear(enc_h.reshape(bsz * frames, hid), self.ctc_lo.weight, self.ctc_lo.bias).view(bsz, frames, -1)
+                ctc_lens = self.encoder.enc2.last_lens_dev
             return self.decoder.recognize_beams(enc_h, enc_lens, max_dec_timesteps, topk, length_penalty=length_penalty,
-                                                nbest=nbest, lm=lm, lm_weight=lm_weight)
+                                                nbest=nbest, lm=lm, lm_weight=lm_weight, ctc_logits=ctc_logits,
+                                                ctc_lens=ctc_lens, ctc_decode_weight=ctc_decode_weight)
 
     def mask_and_cal_loss(self, log_probs, ys, mask=None):
         if mask is None:

@@ -1025,7 +1025,7 @@ BEAM_POLL_STEPS = 8          # the host reads the all-done word of a beam search
 
 
 def beam_search(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo, w_out, b_out, w0, beam, L, bos, eos,
-                length_penalty=0.0, scaling=2.0, lm=None, lm_weight=0.0):
+                length_penalty=0.0, scaling=2.0, lm=None, lm_weight=0.0, ctc=None, ctc_weight=0.0):
     """Beam search over the decoder (Decoder.recognize_beams, model.py:369-406; semantics in DESIGN 4.8), eval arithmetic.
 
     Inputs as decoder_sequence's for B utterances; the search runs B*beam rows (row b*beam + k).  Every step is
@@ -1038,6 +1038,12 @@ def beam_search(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo
     step the LM consumes the decoder's input token (asr_lm_step_f32 per layer, the output GEMM) and the select ranks
     score + logp + lm_weight * logp_lm; the reorder gathers both states in one launch: 8 + n_layers launches.  Without it
     (or with lm_weight == 0) the search is the plain one, launch for launch.
+    ctc (with ctc_weight != 0, a value in [0, 1]): joint CTC-attention decoding - dict(logits [B, T', V] fp32
+    raw CTC logits of the encoder frames, frame_lens int32 [B] on the device, optionally lens_host: the host's copy).  Every
+    beam row carries its CTC prefix state; per step the prefix score kernel runs before the select, which ranks
+    score + (1 - ctc_weight) logp + ctc_weight (psi - psi_prev) (+ lm_weight logp_lm), and the advance kernel beside the
+    reorder: 2 launches on top of the plain (9) or the LM search (10 + n_layers), no host synchronisation added.  Without it
+    (or with ctc_weight == 0) the search is the plain / LM one, launch for launch and bit for bit.
     Returns tokens [B, beam, L] int32 (ranked, <EOS>-padded), scores [B, beam], lengths [B, beam]."""
     dev = P.device
     B, Tp, A = P.shape
@@ -1050,11 +1056,19 @@ def beam_search(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo
     R = B * beam
     f32 = dict(device=dev, dtype=torch.float32)
     fused = lm is not None and float(lm_weight) != 0.0
+    if not 0.0 <= float(ctc_weight) <= 1.0:
+        raise ValueError("ctc_weight must lie in [0, 1], got %r" % (ctc_weight,))
+    joint = ctc is not None and float(ctc_weight) != 0.0
+    if joint and (tuple(ctc["logits"].shape[:2]) != (B, Tp) or ctc["logits"].shape[2] != V):
+        raise ValueError("the CTC logits %s are not [%d utterances, %d frames, %d tokens]"
+                         % (tuple(ctc["logits"].shape), B, Tp, V))
     if fused and (tuple(lm["w_out"].shape) != (V, lm["layers"][-1][1].shape[1]) or lm["emb"].shape[0] != V):
         raise ValueError("the LM's vocabulary (%d outputs, %d embeddings) is not the decoder's (%d)"
                          % (lm["w_out"].shape[0], lm["emb"].shape[0], V))
     with torch.no_grad():
         search = hb.BeamSearch(B, beam, V, L, eos, dev)
+        if joint:
+            prefix = hb.CtcPrefixState(search, ctc["logits"].detach(), ctc["frame_lens"], 0, ctc.get("lens_host"))
         if fused:
             lms = hb.LmStepState(R, lm["emb"], lm["layers"], dev)
             lms.prime(bos)
@@ -1079,8 +1093,13 @@ def beam_search(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo
             if fused:
                 lms.step()
                 hb.gemm_skinny(lms.top(), lm_w_out, bias=lm_b_out, out=lm_logits)
-                search.select_lm(logits, lm_logits, lm_weight, t)
                 launches += lms.n + 1                      # the LM's layers and its output GEMM
+            if joint:
+                prefix.score()
+                search.select_ctc(logits, prefix, ctc_weight, t, lm_logits if fused else None, lm_weight)
+                launches += 1                              # the prefix score
+            elif fused:
+                search.select_lm(logits, lm_logits, lm_weight, t)
             else:
                 search.select(logits, t)
             steps += 1
@@ -1092,6 +1111,9 @@ def beam_search(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo
             else:
                 search.reorder(t, X[2], X[1], cst[1], cst[0], wts[1], wts[0], emb_c, D, O)
             launches += 1
+            if joint:
+                prefix.advance(t)
+                launches += 1
             if (t + 1) % BEAM_POLL_STEPS == 0:
                 # the word copied BEAM_POLL_STEPS steps ago: the host waits for that step at most, never for this one
                 if polled is not None:
@@ -1101,7 +1123,8 @@ def beam_search(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo
                 landing.copy_(search.ndone, non_blocking=True)
                 polled = torch.cuda.Event()
                 polled.record()
-        hb.LAUNCHES["beam_lm_step" if fused else "beam_step"] += steps
-        hb.LAUNCHES["beam_lm_launch" if fused else "beam_launch"] += launches
+        kind = "beam_ctc" if joint else ("beam_lm" if fused else "beam")      # (a joint search with an LM counts as beam_ctc)
+        hb.LAUNCHES[kind + "_step"] += steps
+        hb.LAUNCHES[kind + "_launch"] += launches
         out = search.backtrack(length_penalty)
     return out

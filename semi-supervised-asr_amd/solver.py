@@ -289,7 +289,7 @@ class Solver(object):
             out = run()
         return out
 
-    def _beam(self, xs, ilens, beam_size, lm_weight=0.0, nbest=False):
+    def _beam(self, xs, ilens, beam_size, lm_weight=0.0, nbest=False, ctc_decode_weight=0.0):
         """Best beam-search hypothesis ids for one batch (E2E.recognize_beams; lm_weight > 0: rescored by the judge, shallow
         fusion) - with nbest all beam_size of them per utterance, ranked ([B][K][L]).  The encoder still runs on the
         persistent LSTM kernels: the abort word is checked after the decode and the batch repeated on the per-step kernels,
@@ -298,7 +298,8 @@ class Solver(object):
             prediction, _ = self.model.recognize_beams(
                 xs, ilens, self.config["max_dec_timesteps"], beam_size,
                 length_penalty=float(self.config.get("beam_length_penalty", 0.0)), nbest=nbest,
-                lm=self.judge if lm_weight > 0 else None, lm_weight=lm_weight)
+                lm=self.judge if lm_weight > 0 else None, lm_weight=lm_weight,
+                **(dict(ctc_decode_weight=ctc_decode_weight) if ctc_decode_weight > 0 else {}))
             return prediction.cpu().numpy().tolist()
         out = run()
         if self._abort_seen(xs.device):
@@ -374,6 +375,10 @@ class Solver(object):
                 self.load_judge(self.config["load_judge_path"], False)
             judge_was_training = self.judge.training
             self.judge.eval()
+        # `ctc_decode_weight` (not a reference key): > 0 decodes with the CTC prefix score of the model's CTC head inside the
+        # search (joint CTC-attention decoding), also at beam_size 1; it combines with lm_weight and is separate
+        # from the training loss's `ctc_weight`, which must be > 0 for the head to exist
+        ctc_w = float(self.config.get("ctc_decode_weight", 0.0) or 0.0)
         test_set = self.config["test_set"]
         loader = get_data_loader(self._dataset(test_set, None, sort=False), batch_size=1, shuffle=False,
                                  drop_last=False)
@@ -385,11 +390,11 @@ class Solver(object):
         for batch in self._feed(loader, sharded=False):
             xs, ilens, _ = batch
             if nbest:
-                ranked = self._beam(xs, ilens, beam_size, lm_weight, nbest=True)
+                ranked = self._beam(xs, ilens, beam_size, lm_weight, nbest=True, ctc_decode_weight=ctc_w)
                 preds += [hyps[0] for hyps in ranked]
                 beams += ranked
-            elif lm_weight > 0:
-                preds += self._beam(xs, ilens, beam_size, lm_weight)
+            elif lm_weight > 0 or ctc_w > 0:
+                preds += self._beam(xs, ilens, beam_size, lm_weight, ctc_decode_weight=ctc_w)
             else:
                 preds += self._beam(xs, ilens, beam_size) if beam_size > 1 else self._greedy(xs, ilens)
             refs += batch.ys_host
