@@ -958,6 +958,53 @@ int asr_beam_select_ctc_f32(const asr_beam_t* p, const float* lm_logits, float l
 int asr_ctc_prefix_advance_f32(const asr_ctc_prefix_t* c, const asr_beam_t* p, int t, int src_slot, int dst_slot,
                                asr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * CTC forced alignment and best-path decoding (csrc/ctc_align.hip): the Viterbi (max-product) companions of
+ * the CTC loss on the same head.  Not reference operators - the reference has no CTC branch.  Three entries added to ABI
+ * version 8 WITHOUT a version change, like the CTC loss and prefix entries: additive.
+ * logits, ld, frame_lens, labels, label_offsets, max_label_len are asr_ctc_loss_fwd's: RAW logits [B][T][V] fp32 with row
+ * stride ld >= V, frame_lens int32 [B] on the device (clamped to 0 .. T; frames t >= frame_lens[b] are never read and may
+ * hold NaN), ONE packed int64 label tensor with int32 offsets [B + 1], blank = index 0.  x[t][v] = logits[b][t][v] -
+ * logsumexp_v logits[b][t]; l' = (0, l_1, 0, ..., l_L, 0), S = 2L + 1 states.
+ *   asr_ctc_align_f32   v[0][0] = x[0][0], v[0][1] = x[0][l_1], -inf elsewhere;
+ *                       v[t][s] = max(v[t-1][s], v[t-1][s-1], v[t-1][s-2] if s is odd, s >= 3 and l'_s != l'_{s-2}) + x[t][l'_s];
+ *                       score[b] = max(v[T_b-1][S-1], v[T_b-1][S-2]), and the path that attains it.
+ *                       TIE RULE (it makes the path a function of the inputs): a predecessor replaces the current best only
+ *                       when it is STRICTLY greater, tried in the order stay, s-1, s-2; at the end S-1 is taken unless
+ *                       v[S-2] is strictly greater.
+ *                         path       int32 [B][T]   the token of frame t (0 = blank); -1 for t >= T_b and for every frame of
+ *                                                   an infeasible utterance
+ *                         score      fp32 [B]       the log-probability of the best alignment
+ *                         first,last int32, packed like labels: the inclusive encoder frames label i occupies
+ *                         token_logp fp32, packed like labels: sum_{t = first .. last} x[t][l_i], summed by ONE lane in
+ *                                                   ascending frame order
+ *                       INFEASIBLE (T_b = 0, a label outside [1, V), more than max_label_len labels, v = -inf at the end:
+ *                       frames < labels + adjacent equal labels): score = -inf, first = last = -1, token_logp = -inf,
+ *                       path = -1.  An empty transcript with T_b >= 1 is feasible: all frames blank, score = sum_t x[t][0].
+ *                       Two launches: the frame log-sum-exps; then one workgroup per utterance (one wave up to 2
+ *                       max_label_len + 1 = 64 states, 256 threads beyond, states strided over the threads above 256) runs
+ *                       the chain, the backtrace (one lane) and the output passes.  Each state's choice is two bits; per
+ *                       (frame, 64 states) a pair of 64-bit words.  They stay in LDS when T_b ceil(S / 64) 16 bytes <=
+ *                       ASR_CTC_ALIGN_LDS_BYTES and go to the workspace otherwise.
+ *   asr_ctc_align_ws_bytes   the bytes of the workspace (8-byte aligned: ASR_E_ALIGN): with R = B T rounded up to 64,
+ *                       W = ceil((2 max_label_len + 1) / 64):  8 R  (log-sum-exps, the state of every frame)
+ *                       + 16 B T W  if T W 16 > ASR_CTC_ALIGN_LDS_BYTES (the back-pointers), + 0 otherwise.
+ *   asr_ctc_greedy_f32  best path: frame_tok[b][t] = argmax_v logits[b][t][v] over the RAW logits (no log-softmax is
+ *                       needed; NaN never wins, ties to the lowest index, a frame of NaN / -inf only gives 0), -1 for
+ *                       t >= T_b.  Frame t is kept when frame_tok[t] != 0 and (t == 0 or frame_tok[t] != frame_tok[t-1]);
+ *                       ids int32 [B][T] = the kept tokens in frame order, padded with -1; n int32 [B] their count.  One
+ *                       launch, one workgroup per utterance.  No arithmetic: exact.
+ * V < 2 or max_label_len > ASR_CTC_MAX_LABELS: ASR_E_SHAPE.  No floating-point atomics, no host synchronisation, no
+ * allocation; functions of their inputs and shapes only - the same bits in every run, in and outside deterministic mode.
+ * ------------------------------------------------------------------------------------- */
+#define ASR_CTC_ALIGN_LDS_BYTES 40960
+int asr_ctc_align_ws_bytes(int B, int T, int V, int max_label_len, int64_t* ws_bytes);
+int asr_ctc_align_f32(int B, int T, int V, const float* logits, int64_t ld, const int32_t* frame_lens, const int64_t* labels,
+                      const int32_t* label_offsets, int max_label_len, int32_t* path, float* score, int32_t* first,
+                      int32_t* last, float* token_logp, void* ws, int64_t ws_bytes, asr_stream_t stream);
+int asr_ctc_greedy_f32(int B, int T, int V, const float* logits, int64_t ld, const int32_t* frame_lens, int32_t* ids,
+                       int32_t* n, int32_t* frame_tok, asr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,7 @@ EXPORTS = (
     "asr_sumsq_det_f32", "asr_gather_sumsq_det_f32", "asr_sum_det_f32", "asr_dec_step_bwd_det", "asr_dec_seq_bwd_det",
     "asr_ctc_ws_bytes", "asr_ctc_loss_fwd", "asr_ctc_loss_bwd",
     "asr_ctc_prefix_init_f32", "asr_ctc_prefix_score_f32", "asr_beam_select_ctc_f32", "asr_ctc_prefix_advance_f32",
+    "asr_ctc_align_ws_bytes", "asr_ctc_align_f32", "asr_ctc_greedy_f32",
 )
 
 _lib = None
@@ -267,6 +268,9 @@ def load():
     lib.asr_ctc_prefix_score_f32.argtypes = [ctypes.POINTER(CtcPrefix), ctypes.POINTER(Beam), c_i, c_p]
     lib.asr_beam_select_ctc_f32.argtypes = [ctypes.POINTER(Beam), c_p, c_f, c_p, c_p, c_f, c_i, c_p]
     lib.asr_ctc_prefix_advance_f32.argtypes = [ctypes.POINTER(CtcPrefix), ctypes.POINTER(Beam), c_i, c_i, c_i, c_p]
+    lib.asr_ctc_align_ws_bytes.argtypes = [c_i, c_i, c_i, c_i, ctypes.POINTER(c_i64)]
+    lib.asr_ctc_align_f32.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
+    lib.asr_ctc_greedy_f32.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]
     lib.asr_dec_feedback_fwd.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_p, c_i64,
                                          c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
     lib.asr_dec_feedback_bwd.argtypes = [c_i, c_i, c_i, c_i, c_p, c_p, c_i64, c_p, c_p, c_p, c_f, c_p, c_p]
@@ -938,6 +942,62 @@ def ctc_loss_bwd(logits, ld, frame_lens, labels, label_offsets, max_label_len, z
     check(load().asr_ctc_loss_bwd(*args, ptr(grad_nll), ptr(ws), ws.numel() * 4, ptr(dlogits), int(lddz), stream()),
           "asr_ctc_loss_bwd")
     return dlogits
+
+
+CTC_ALIGN_LDS_BYTES = 40960     # ASR_CTC_ALIGN_LDS_BYTES: an utterance's back-pointers stay in LDS up to this size
+
+
+def ctc_align_ws_bytes(B, T, V, max_label_len):
+    """asr_ctc_align_ws_bytes on plain integers (no tensors, no GPU) -> the workspace bytes of a ctc_align call;
+    UnsupportedShape for sizes the kernels refuse (more than CTC_MAX_LABELS labels, V < 2)."""
+    need = c_i64(0)
+    rc = load().asr_ctc_align_ws_bytes(int(B), int(T), int(V), int(max_label_len), ctypes.byref(need))
+    if rc == -2:
+        raise UnsupportedShape("ctc_align: B %d, T %d, V %d, %d labels (at most %d labels, V >= 2)"
+                               % (B, T, V, max_label_len, CTC_MAX_LABELS))
+    check(rc, "asr_ctc_align_ws_bytes")
+    return need.value
+
+
+def _ctc_view(logits, what):
+    """A [B, T, V] fp32 view with unit column stride and row stride ld >= V goes in as it is -> (logits, ld)."""
+    B, T, V = _dev(logits, what).shape
+    if not (logits.stride(2) == 1 and logits.stride(1) >= V and logits.stride(0) == T * logits.stride(1)):
+        logits = logits.contiguous()
+    return logits, logits.stride(1)
+
+
+def ctc_align(logits, frame_lens, labels, label_offsets, max_label_len, path, score, first, last, token_logp, ws):
+    """asr_ctc_align_f32 (csrc/ctc_align.hip): the best CTC alignment of every utterance's labels.  logits
+    [B, T, V] fp32 raw (a view with row stride >= V is taken as it is), frame_lens int32 [B], labels packed int64,
+    label_offsets int32 [B + 1], all on the device; the outputs path int32 [B, T], score fp32 [B], first / last int32 and
+    token_logp fp32 (packed like labels) and the workspace ws (a float32 tensor of at least ctc_align_ws_bytes bytes) are the
+    caller's.  Two launches."""
+    logits, ld = _ctc_view(logits, "ctc logits")
+    B, T, V = logits.shape
+    if labels.dtype != torch.long or not labels.is_cuda:
+        raise RuntimeError("ctc_align: labels must be one packed int64 tensor on the GPU")
+    rc = load().asr_ctc_align_f32(B, T, V, ptr(logits), int(ld), ptr(frame_lens), c_p(labels.data_ptr()), ptr(label_offsets),
+                                  int(max_label_len), ptr(path), ptr(score), ptr(first), ptr(last), ptr(token_logp), ptr(ws),
+                                  ws.numel() * 4, stream())
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("ctc_align: B %d, T %d, V %d, %d labels (at most %d labels, V >= 2)"
+                               % (B, T, V, max_label_len, CTC_MAX_LABELS))
+    check(rc, "asr_ctc_align_f32")
+    LAUNCHES["ctc_align"] += 1
+
+
+def ctc_greedy(logits, frame_lens, ids, n, frame_tok):
+    """asr_ctc_greedy_f32: best-path CTC decoding of raw logits [B, T, V] (a view with row stride >= V is taken as it is) ->
+    ids int32 [B, T] (the hypothesis, padded with -1), n int32 [B] (its length), frame_tok int32 [B, T] (the argmax of every
+    frame, -1 behind the utterance), all the caller's.  One launch."""
+    logits, ld = _ctc_view(logits, "ctc logits")
+    B, T, V = logits.shape
+    rc = load().asr_ctc_greedy_f32(B, T, V, ptr(logits), int(ld), ptr(frame_lens), ptr(ids), ptr(n), ptr(frame_tok), stream())
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("ctc_greedy: V %d (V >= 2)" % V)
+    check(rc, "asr_ctc_greedy_f32")
+    LAUNCHES["ctc_greedy"] += 1
 
 
 def colsum(X, out=None, accumulate=False):

@@ -94,6 +94,15 @@ class pBLSTM(torch.nn.Module):
         self.subsample = subsample
         self.dropout_rate = dropout_rate
 
+    @property
+    def time_reduction(self):
+        """Input frames per output frame: 2 for every layer that subsamples (an utterance of n input frames leaves layer
+        after layer with (n + 1) // 2), read from the layers this stack was built with."""
+        r = 1
+        for i in range(len(self.layers)):
+            r *= 2 if self.subsample[i] > 1 else 1
+        return r
+
     def forward(self, xpad, ilens, total_length=None):
         """xpad [B,T,idim] zero padded, ilens descending host ints -> ([B,T',H], list[int]).
         `total_length` (list from padded_lengths) keeps a data-parallel shard at the global padded
@@ -520,6 +529,63 @@ class E2E(torch.nn.Module):
             return self.decoder.recognize_beams(enc_h, enc_lens, max_dec_timesteps, topk, length_penalty=length_penalty,
                                                 nbest=nbest, lm=lm, lm_weight=lm_weight, ctc_logits=ctc_logits,
                                                 ctc_lens=ctc_lens, ctc_decode_weight=ctc_decode_weight)
+
+    @property
+    def time_reduction(self):
+        """Input frames per encoder frame (an integer, from the encoder's own layers): encoder frame t of `align` covers the
+        input frames t * time_reduction .. (t + 1) * time_reduction - 1, and an utterance of n input frames has
+        ceil(n / time_reduction) encoder frames."""
+        return self.encoder.enc2.time_reduction
+
+    def _ctc_logits(self, data, ilens, what):
+        """Encoder, then ctc_lo on the rows ctc_nll uses -> (raw CTC logits [B, T', V], the frame lengths on the device, and
+        on the host).  Without the head: ValueError before any launch."""
+        if not hasattr(self, "ctc_lo"):
+            raise ValueError("%s needs the CTC head: build the model with ctc_weight > 0" % what)
+        if data.is_cuda:
+            hb.upload_side_stream_for(data.shape[0] * data.shape[1])
+        enc_h, enc_lens = self.encoder(data, ilens)
+        bsz, frames, hid = enc_h.shape
+        logits = ops.linear(enc_h.reshape(bsz * frames, hid), self.ctc_lo.weight, self.ctc_lo.bias).view(bsz, frames, -1)
+        return logits, self.encoder.enc2.last_lens_dev, enc_lens
+
+    def align(self, xs, ilens, ys):
+        """CTC forced alignment of the transcripts `ys` (a list of label tensors, as forward takes them) to the utterances
+        (not a reference method): encoder, the CTC head, ops.ctc_align.  -> one dict per utterance:
+        tokens (the label ids), first / last (the inclusive ENCODER frames of each token; times time_reduction for input
+        frames), confidence (exp(token_logp / (last - first + 1)): the geometric mean of the head's frame posteriors of the
+        token over its frames), score (the log-probability of the best alignment; -inf: the transcript does not fit the
+        frames - then first = last = -1 and the confidences are 0) and frames (the utterance's encoder frames).  The device
+        results are read once."""
+        with torch.no_grad():
+            logits, lens_dev, enc_lens = self._ctc_logits(xs, ilens, "align")
+            labels = torch.cat([y.reshape(-1) for y in ys]).to(device=logits.device, dtype=torch.long)
+            counts = [int(y.numel()) for y in ys]
+            res = ops.ctc_align(logits, lens_dev, labels, counts)
+            span = (res.last - res.first + 1).clamp(min=1).to(torch.float32)
+            conf = torch.exp(res.token_logp / span)
+            # one read: [first, last, confidence, labels] per label, then the scores
+            packed = torch.cat([res.first.double(), res.last.double(), conf.double(), labels.double(), res.score.double()]).cpu()
+        n = labels.numel()
+        first, last, conf, toks, score = (packed[:n].long().tolist(), packed[n:2 * n].long().tolist(), packed[2 * n:3 * n].tolist(),
+                                          packed[3 * n:4 * n].long().tolist(), packed[4 * n:].tolist())
+        out, o = [], 0
+        for b, c in enumerate(counts):
+            out.append(dict(tokens=toks[o:o + c], first=first[o:o + c], last=last[o:o + c], confidence=conf[o:o + c],
+                            score=score[b], frames=int(enc_lens[b])))
+            o += c
+        self.last_alignment = res                                # (the device tensors of the call, path included)
+        return out
+
+    def recognize_ctc(self, xs, ilens):
+        """Best-path decoding with the CTC head alone (not a reference method): the argmax token of every
+        encoder frame, repeats collapsed, blanks dropped (ops.ctc_greedy) -> one id list per utterance."""
+        with torch.no_grad():
+            logits, lens_dev, _ = self._ctc_logits(xs, ilens, "recognize_ctc")
+            ids, n, frame_tok = ops.ctc_greedy(logits, lens_dev)
+            host = torch.cat([n.view(-1, 1), ids], dim=1).cpu().tolist()
+        self.last_frame_tokens = frame_tok
+        return [row[1:1 + row[0]] for row in host]
 
     def mask_and_cal_loss(self, log_probs, ys, mask=None):
         if mask is None:

@@ -995,6 +995,58 @@ def ctc_loss(logits, frame_lens_dev, labels_packed, label_lens, zero_infinity=Tr
     return _CtcLoss.apply(logits, frame_lens_dev, labels_packed, label_lens, zero_infinity)
 
 
+class CtcAlignment(object):
+    """What ops.ctc_align returns, every field a device tensor: path int32 [B, T'] (the token of each encoder frame, 0 =
+    blank, -1 behind the utterance and in every frame of an infeasible one), score fp32 [B] (the best alignment's
+    log-probability, -inf: infeasible), and packed like the labels first / last int32 (the inclusive frames of label i, -1:
+    infeasible) and token_logp fp32 (the log-probability the path gives label i over its frames); offsets int32 [B + 1]
+    (utterance b owns [offsets[b], offsets[b + 1]) of the packed fields) with label_lens, the host's counts."""
+
+    __slots__ = ("path", "score", "first", "last", "token_logp", "offsets", "label_lens")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def ctc_align(logits, frame_lens_dev, labels_packed, label_lens):
+    """-> CtcAlignment: the best CTC alignment (Viterbi) of each utterance's labels, asr_ctc_align_f32 (csrc/ctc_align.hip,
+    DESIGN 4.16), two launches.  The arguments are ops.ctc_loss's: logits [B, T', V] fp32 raw, frame_lens_dev int32 [B] on
+    the device, labels_packed ONE int64 device tensor, label_lens host integers; blank = 0.  Forward only: logits that
+    require grad are accepted and nothing is recorded.  No host synchronisation."""
+    logits = logits.detach()
+    B, T, V = logits.shape
+    lens = [int(n) for n in label_lens]
+    if len(lens) != B:
+        raise ValueError("ctc_align: %d label lengths for %d utterances" % (len(lens), B))
+    offsets = [0]
+    for n in lens:
+        offsets.append(offsets[-1] + n)
+    if offsets[-1] != labels_packed.numel():
+        raise ValueError("ctc_align: the label lengths sum to %d, the packed labels hold %d" % (offsets[-1], labels_packed.numel()))
+    lmax, total, dev = max(lens), offsets[-1], logits.device
+    ws = torch.empty((hb.ctc_align_ws_bytes(B, T, V, lmax) + 3) // 4, device=dev, dtype=torch.float32)
+    offs_dev = hb.to_device_i32(offsets, dev)
+    i32, f32 = dict(device=dev, dtype=torch.int32), dict(device=dev, dtype=torch.float32)
+    out = CtcAlignment(path=torch.empty(B, T, **i32), score=torch.empty(B, **f32), first=torch.empty(total, **i32),
+                       last=torch.empty(total, **i32), token_logp=torch.empty(total, **f32), offsets=offs_dev, label_lens=lens)
+    hb.ctc_align(logits, frame_lens_dev, labels_packed.contiguous(), offs_dev, lmax, out.path, out.score, out.first, out.last,
+                 out.token_logp, ws)
+    return out
+
+
+def ctc_greedy(logits, frame_lens_dev):
+    """-> (ids int32 [B, T'] padded with -1, n int32 [B], frame_tok int32 [B, T']): best-path CTC decoding of raw logits
+    [B, T', V] - the argmax of every frame, repeats collapsed, blanks (index 0) dropped: asr_ctc_greedy_f32, one launch.
+    Forward only, no host synchronisation."""
+    logits = logits.detach()
+    B, T, _ = logits.shape
+    i32 = dict(device=logits.device, dtype=torch.int32)
+    ids, n, frame_tok = torch.empty(B, T, **i32), torch.empty(B, **i32), torch.empty(B, T, **i32)
+    hb.ctc_greedy(logits, frame_lens_dev, ids, n, frame_tok)
+    return ids, n, frame_tok
+
+
 def decoder_sequence(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo, w_out, b_out, w0, opts):
     opts = dict(opts)
     opts["pooled"] = torch.is_grad_enabled() and (P.requires_grad or w_hh.requires_grad)

@@ -309,6 +309,43 @@ class Solver(object):
             out = run()
         return out
 
+    def _ctc_best_path(self, xs, ilens):
+        """Best-path hypothesis ids of the CTC head for one batch (E2E.recognize_ctc); the abort word of the encoder's
+        persistent kernels is checked after the decode and the batch repeated on the per-step kernels, as in _greedy."""
+        out = self.model.recognize_ctc(xs, ilens)
+        if self._abort_seen(xs.device):
+            print("persistent kernels aborted during CTC best-path decoding (this rank's code %d): repeating the batch on "
+                  "the per-step kernels" % hb.persist_abort_code(xs.device))
+            hb.disable_persistent(xs.device)
+            out = self.model.recognize_ctc(xs, ilens)
+        return out
+
+    def align(self, loader=None):
+        """CTC forced alignment of every utterance of `loader` (default: the dev loader) to its transcript with the model's
+        CTC head (E2E.align; the model needs `ctc_weight` > 0) -> one record per utterance, in the loader's
+        order: tokens (the vocabulary's symbols), first / last (inclusive encoder frames; times model.time_reduction for
+        input frames), confidence (per token), score (the alignment's log-probability) and frames.  The device results are
+        read once per batch."""
+        self.flush()
+        loader = self.dev_loader if loader is None else loader
+        symbols = {i: s for s, i in self.vocab.items()}
+        was_training = self.model.training
+        self.model.eval()
+        records = []
+        try:
+            for batch in self._feed(loader, sharded=False):
+                xs, ilens, ys = batch
+                out = self.model.align(xs, ilens, ys)
+                if self._abort_seen(xs.device):                 # see _greedy
+                    hb.disable_persistent(xs.device)
+                    out = self.model.align(xs, ilens, ys)
+                for rec in out:
+                    rec["tokens"] = [symbols[i] for i in rec["tokens"]]
+                records += out
+        finally:
+            self.model.train(was_training)
+        return records
+
     def validation(self):
         """Teacher-forced dev loss + greedy CER (solver.py:212-242); greedy pass runs without autograd."""
         self.flush()
@@ -361,6 +398,14 @@ class Solver(object):
         return total / len(self.dev_loader), sents
 
     def test(self, state_dict=None, judge_state_dict=None):
+        # `ctc_greedy_decode` (not a reference key; default false): decode with the CTC head alone, best path
+        # (E2E.recognize_ctc) instead of the attention decoder - the head's own hypotheses.  It is a decoder
+        # of its own: no beam, no judge, no prefix score.
+        ctc_greedy = bool(self.config.get("ctc_greedy_decode", False))
+        if ctc_greedy and (int(self.config.get("beam_size", 1) or 1) > 1 or float(self.config.get("lm_weight", 0.0) or 0.0) > 0
+                           or float(self.config.get("ctc_decode_weight", 0.0) or 0.0) > 0):
+            raise ValueError("ctc_greedy_decode decodes with the CTC head alone: it does not combine with beam_size > 1, "
+                             "lm_weight > 0 or ctc_decode_weight > 0")
         if state_dict:
             self.model.load_state_dict(state_dict)
         else:
@@ -379,17 +424,19 @@ class Solver(object):
         # search (joint CTC-attention decoding), also at beam_size 1; it combines with lm_weight and is separate
         # from the training loss's `ctc_weight`, which must be > 0 for the head to exist
         ctc_w = float(self.config.get("ctc_decode_weight", 0.0) or 0.0)
+        beam_size = int(self.config.get("beam_size", 1) or 1)    # not reference keys: beam_size, beam_length_penalty
         test_set = self.config["test_set"]
         loader = get_data_loader(self._dataset(test_set, None, sort=False), batch_size=1, shuffle=False,
                                  drop_last=False)
         self.model.eval()
-        beam_size = int(self.config.get("beam_size", 1) or 1)    # not reference keys: beam_size, beam_length_penalty
         # with `cer_on_gpu` a beam search keeps all its K hypotheses per utterance: the best-of-K CER below
         nbest = beam_size > 1 and self._cer_device() is not None
         preds, refs, beams = [], [], []
         for batch in self._feed(loader, sharded=False):
             xs, ilens, _ = batch
-            if nbest:
+            if ctc_greedy:
+                preds += self._ctc_best_path(xs, ilens)
+            elif nbest:
                 ranked = self._beam(xs, ilens, beam_size, lm_weight, nbest=True, ctc_decode_weight=ctc_w)
                 preds += [hyps[0] for hyps in ranked]
                 beams += ranked
