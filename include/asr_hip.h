@@ -1005,6 +1005,71 @@ int asr_ctc_align_f32(int B, int T, int V, const float* logits, int64_t ld, cons
 int asr_ctc_greedy_f32(int B, int T, int V, const float* logits, int64_t ld, const int32_t* frame_lens, int32_t* ids,
                        int32_t* n, int32_t* frame_tok, asr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The front end (csrc/frontend.hip): packed waveforms -> the [B][T][D] features the encoder reads.  Not
+ * reference operators - the reference reads features that Kaldi computed.  Five entries added to ABI version 8 WITHOUT a
+ * version change: additive.
+ *   asr_fbank_num_frames  host integer arithmetic, no GPU: T = 1 + (n_samples - frame_length) / frame_shift when
+ *                       n_samples >= frame_length, else 0 (Kaldi's snip-edges).
+ *   asr_fbank_plan_bytes  the bytes of the table buffer ("plan") of asr_fbank_f32 for n_fft in {256, 512} (else ASR_E_SHAPE):
+ *                       4 (7 n_fft / 2 + 3 ASR_FBANK_MAX_MELS).  The CALLER fills it (float64 arithmetic, rounded to fp32),
+ *                       4-byte words in this order, M = n_fft / 2:
+ *                         window  fp32 [n_fft]    (0.5 - 0.5 cos(2 pi n / (L - 1)))^0.85 for n < L, 0 behind
+ *                         tw      fp32 [M/2][2]   (cos, -sin)(2 pi j / M)         the FFT's twiddles
+ *                         ut      fp32 [M][2]     (cos, -sin)(2 pi k / n_fft)     the untangle pass's
+ *                         start, len, woff  int32 [ASR_FBANK_MAX_MELS] each: mel bin j sums FFT bins start[j] .. start[j] +
+ *                                                 len[j] - 1 (all < M: the Nyquist bin is unused, as in Kaldi) with the weights
+ *                                                 w[woff[j] ..]; entries behind n_mels are ignored
+ *                         w       fp32 [n_fft]    the packed weights (a bin lies in at most two triangles)
+ *                       The kernel clamps start / len / woff into the buffer: a wrong plan gives wrong numbers, no fault.
+ *   asr_fbank_f32       Kaldi-convention filterbank energies, dither off.  samples: ONE packed buffer of int16
+ *                       (ASR_SAMPLES_I16) or fp32 (ASR_SAMPLES_F32; values in int16 range, as Kaldi expects), utterance b =
+ *                       samples[offsets[b] .. offsets[b + 1]), offsets int64 [B + 1] on the device.  Only the natural
+ *                       alignment of a sample is assumed (an int16 utterance may start at an odd element); no sample at or
+ *                       behind offsets[B] and none outside a frame is read.  T_b = asr_fbank_num_frames(N_b), clamped to
+ *                       T_max.  Per frame: subtract the frame mean; x[i] -= preemph x[i-1] (x[0] -= preemph x[0]); window;
+ *                       zero-pad to n_fft; power spectrum; E[j] = sum_i w[woff[j] + i] P[start[j] + i] in ascending i;
+ *                       out = E, or with use_log: logf(E) where E > FLT_EPSILON and the fp32 nearest to ln(FLT_EPSILON)
+ *                       elsewhere.  Row (b, t) is written at out[(b T_max + t) ld + col0 .. + n_mels); rows t >= T_b are not
+ *                       touched.  n_fft in {256, 512}, frame_length <= n_fft, 1 <= n_mels <= ASR_FBANK_MAX_MELS, B <= 65535:
+ *                       ASR_E_SHAPE otherwise.  One launch: a workgroup of four waves per tile of ASR_FBANK_FRAME_TILE
+ *                       consecutive frames of one utterance, one wave per frame.  The real FFT is a complex FFT of half the
+ *                       size on z[n] = x[2n] + i x[2n+1] (radix 2, decimation in frequency, in LDS) and an untangle pass.
+ *   asr_feat_cmvn_stats_f32  x fp32 [B][T] rows of ld >= n_mels floats, frame_lens int32 [B] on the device (clamped to 0 .. T)
+ *                       -> stats fp32 [B][2][n_mels]: the mean over the utterance's frames, and 1 / sqrt(max(var, 1e-10))
+ *                       with the biased variance taken about that mean (two passes).  One workgroup per utterance; four row
+ *                       groups (t mod 4) per bin, summed in ascending t and combined as (g0 + g1) + (g2 + g3).
+ *   asr_feat_finish_f32 one pass, x as above -> out fp32 [B][T][n_mels (1 + order)], contiguous.  In this order:
+ *                         CMVN of the static features y = (x - mean) istd: ASR_CMVN_NONE; ASR_CMVN_GLOBAL (stats fp32
+ *                           [2][n_mels]: mean, istd); ASR_CMVN_UTTERANCE (stats of asr_feat_cmvn_stats_f32);
+ *                         deltas, order in {0, 1, 2} (Kaldi add-deltas, window 2): block k = sum_d s_k[d] y[clamp(t + d, 0,
+ *                           T_b - 1)], s_1 = (-2, -1, 0, 1, 2) / 10 over d = -2 .. 2, s_2 = s_1 * s_1 (9 taps, d = -4 .. 4) -
+ *                           each order a filter over the STATIC rows, summed in ascending d;
+ *                         masks int32 [B][n_freq_masks + n_time_masks][2] of (start, width), frequency masks first: a
+ *                           frequency mask zeroes bins [f0, f0 + w) of every block, a time mask frames [t0, t0 + w); width 0
+ *                           masks nothing; masks may be null when both counts are 0;
+ *                         exact zeros in rows t >= T_b.
+ * No floating-point atomics, no host synchronisation, no allocation; functions of their inputs and shapes only - the same
+ * bits in every run, in and outside deterministic mode.
+ * ------------------------------------------------------------------------------------- */
+#define ASR_FBANK_FRAME_TILE 8
+#define ASR_FBANK_MAX_MELS 128
+#define ASR_SAMPLES_I16 0
+#define ASR_SAMPLES_F32 1
+#define ASR_CMVN_NONE 0
+#define ASR_CMVN_GLOBAL 1
+#define ASR_CMVN_UTTERANCE 2
+int asr_fbank_num_frames(int64_t n_samples, int frame_length, int frame_shift, int64_t* n_frames);
+int asr_fbank_plan_bytes(int n_fft, int64_t* bytes);
+int asr_fbank_f32(int B, int T_max, const void* samples, int sample_dtype, const int64_t* offsets, int frame_length,
+                  int frame_shift, int n_fft, int n_mels, float preemph, int use_log, const void* plan, float* out, int64_t ld,
+                  int64_t col0, asr_stream_t stream);
+int asr_feat_cmvn_stats_f32(int B, int T, int n_mels, const float* x, int64_t ld, const int32_t* frame_lens, float* stats,
+                            asr_stream_t stream);
+int asr_feat_finish_f32(int B, int T, int n_mels, int order, const float* x, int64_t ldx, const int32_t* frame_lens,
+                        int cmvn_mode, const float* stats, const int32_t* masks, int n_freq_masks, int n_time_masks, float* out,
+                        asr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

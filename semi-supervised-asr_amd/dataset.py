@@ -8,21 +8,28 @@ import numpy as np
 from torch.utils.data import Dataset
 
 
-def _within(entry, config):
-    frames = entry["feature"].shape[0]
+def _shape0(feature):
+    return feature.shape[0]
+
+
+def _within(entry, config, frames_of=_shape0):
+    frames = frames_of(entry["feature"])
     chars = len(entry["token_ids"])
     return (config["min_feature_length"] <= frames <= config["max_feature_length"]
             and config["min_text_length"] <= chars <= config["max_text_length"])
 
 
 class DictDataset(Dataset):
-    """Common behaviour over an {utt: {'feature', 'token_ids'}} dict."""
+    """Common behaviour over an {utt: {'feature', 'token_ids'}} dict.  `frames_of`: feature -> its frame count for the
+    length filter and the sort (default: shape[0]; with a front end the features are waveforms and it is the front end's
+    num_frames of the sample count)."""
 
-    def __init__(self, data_dict, config=None, sort=True):
+    def __init__(self, data_dict, config=None, sort=True, frames_of=None):
         self.data_dict = data_dict
-        keys = [k for k in data_dict if config is None or _within(data_dict[k], config)]
+        frames_of = frames_of or _shape0
+        keys = [k for k in data_dict if config is None or _within(data_dict[k], config, frames_of)]
         if sort:
-            keys.sort(key=lambda k: data_dict[k]["feature"].shape[0])
+            keys.sort(key=lambda k: frames_of(data_dict[k]["feature"]))
         self.keys = keys
 
     def __getitem__(self, index):
@@ -34,10 +41,10 @@ class DictDataset(Dataset):
 
 
 class PickleDataset(DictDataset):
-    def __init__(self, pickle_path, config=None, sort=True):
+    def __init__(self, pickle_path, config=None, sort=True, frames_of=None):
         with open(pickle_path, "rb") as f:
             data = pickle.load(f)
-        super().__init__(data, config=config, sort=sort)
+        super().__init__(data, config=config, sort=sort, frames_of=frames_of)
 
 
 def synthetic_utterances(n, input_dim, vocab_size, t_max, seed, ragged=True, label_ratio=0.125):
@@ -50,6 +57,26 @@ def synthetic_utterances(n, input_dim, vocab_size, t_max, seed, ragged=True, lab
         out["utt%06d" % i] = dict(
             feature=rs.normal(0.0, 1.0, size=(t, input_dim)).astype(np.float32),
             token_ids=rs.randint(3, vocab_size, size=(max(2, int(label_ratio * t)),)).tolist())
+    return out
+
+
+def synthetic_waveforms(n, vocab_size, seconds_max, seed, sample_rate=16000, ragged=True, label_ratio=0.125,
+                        frame_shift=160, dtype=np.int16):
+    """Waveform stand-ins for synthetic_utterances: durations U[0.6 s, s] when ragged, two sines of random pitch under
+    white noise at a random level, int16 (or float32 in int16 range); labels as there, from the utterance's frame count
+    at `frame_shift` samples per frame."""
+    rs = np.random.RandomState(seed)
+    n_max = int(round(seconds_max * sample_rate))
+    out = {}
+    for i in range(n):
+        m = int(rs.randint(int(0.6 * n_max), n_max + 1)) if ragged else n_max
+        t = np.arange(m) / float(sample_rate)
+        f1, f2 = rs.uniform(80.0, 400.0), rs.uniform(500.0, 0.45 * sample_rate)
+        wave = rs.uniform(500.0, 8000.0) * (np.sin(2 * np.pi * f1 * t) + 0.5 * np.sin(2 * np.pi * f2 * t + rs.uniform(0, 6.28)))
+        wave = np.clip(np.rint(wave + rs.normal(0.0, rs.uniform(50.0, 1000.0), m)), -32768, 32767)
+        frames = max(1, m // frame_shift)
+        out["utt%06d" % i] = dict(feature=wave.astype(dtype),
+                                  token_ids=rs.randint(3, vocab_size, size=(max(2, int(label_ratio * frames)),)).tolist())
     return out
 
 

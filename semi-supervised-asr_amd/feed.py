@@ -18,6 +18,11 @@ The optional Gaussian input noise (solver.py:370-373) is drawn here and added on
 generator per GLOBAL row of a batch, seeded from (the feed's seed - taken from the process's numpy stream when the feed is
 built, so data-parallel ranks agree -, the batch's index, the row).  A rank draws only the rows it uploads, and the union of
 the rank-local batches is the one-process batch.
+
+With a front end (`frontend=`, frontend.Frontend) an utterance's `feature` is a 1-D int16 or float32 WAVEFORM: the collate
+packs this rank's samples into the pinned slot (longest first), uploads them on the side stream and runs the front end's
+kernels there; the yielded `Batch` is the one a feed of precomputed features yields.  SpecAugment masks are drawn like the
+noise - one generator per global row - and only in training feeds (`train=True`).
 """
 import queue
 import threading
@@ -52,10 +57,13 @@ def _round_up(n, q):
 
 
 class _Slot(object):
-    """Pinned staging of one batch in flight: a float32 area (features) and an int64 area (labels), grown on demand."""
+    """Pinned staging of one batch in flight: a float32 area (features, or float32 samples), an int64 area (labels), and -
+    for a feed with a front end - an int16 area (samples) and a second int64 area (offsets, frame counts, masks), grown on
+    demand."""
 
     def __init__(self, pin):
         self.pin, self.f, self.i, self.event = pin, None, None, None
+        self.s, self.m = None, None
 
     def _area(self, old, n, dtype, quantum):
         if old is not None and old.numel() >= n:
@@ -69,6 +77,14 @@ class _Slot(object):
     def ints(self, n):
         self.i = self._area(self.i, n, torch.int64, 1 << 10)
         return self.i[:n]
+
+    def shorts(self, n):
+        self.s = self._area(self.s, n, torch.int16, 1 << 19)
+        return self.s[:n]
+
+    def meta(self, n):
+        self.m = self._area(self.m, n, torch.int64, 1 << 10)
+        return self.m[:n]
 
 
 # Pinning host memory is slow (hipHostMalloc: of the order of 100 ms for the 8 MB of a cfg-2 batch), so the staging slots
@@ -103,10 +119,21 @@ class DeviceFeed(object):
       rank/world  data-parallel position: world > 1 yields this rank's strided rows as a parallel.LocalShard
       noise_std   > 0: add N(0, noise_std) noise to the features (a generator per global row, see the module docstring)
       thread      collate + upload in a background thread (default) or inline in next()
+      frontend    a frontend.Frontend: features are 1-D waveforms and the front end runs on the side stream (GPU only)
+      train       with a front end that has SpecAugment masks: draw them (training feeds only)
     """
 
-    def __init__(self, source, device, kind="labeled", rank=0, world=1, depth=2, noise_std=0.0, thread=True):
+    def __init__(self, source, device, kind="labeled", rank=0, world=1, depth=2, noise_std=0.0, thread=True, frontend=None,
+                 train=False):
         assert kind in ("labeled", "speech", "text")
+        self.frontend = frontend
+        if frontend is not None:
+            if torch.device(device).type != "cuda":
+                raise RuntimeError("DeviceFeed: the front end runs on the GPU only: the HIP path has no CPU fallback")
+            if float(noise_std) > 0:
+                raise ValueError("DeviceFeed: the host-side input noise needs precomputed features (noise_std with a front end)")
+            # the mask seed: from the process's numpy stream, here, like the noise seed below
+            self.mask_seed = int(np.random.randint(0, 2 ** 31 - 1)) if train and frontend.n_masks > 0 else None
         self.source, self.kind, self.rank, self.world = source, kind, int(rank), int(world)
         self.device = torch.device(device)
         self.cuda = self.device.type == "cuda"
@@ -128,6 +155,8 @@ class DeviceFeed(object):
     # ---------------------------------------------------------------- one batch: host lists -> pinned -> device
     def _prepare(self, items):
         """-> (Batch, copy-done event or None).  Runs in the producer (thread or inline)."""
+        if self.frontend is not None and self.kind != "text":
+            return self._prepare_waveforms(items)
         slot = self._slots[self._n % len(self._slots)]
         self._n += 1
         if slot.event is not None:
@@ -183,6 +212,69 @@ class DeviceFeed(object):
         else:
             xs_out = xs_d
         return Batch(self.kind, xs_out, ilens, ys, ys_host), event, flat
+
+    def _prepare_waveforms(self, items):
+        """_prepare for a feed with a front end: samples -> pinned -> device -> features, all on the side stream."""
+        fe = self.frontend
+        slot = self._slots[self._n % len(self._slots)]
+        self._n += 1
+        if slot.event is not None:
+            slot.event.synchronize()
+            slot.event = None
+        items = sorted(items, key=lambda item: -int(item[0].shape[0]))       # sample count descending (stable)
+        rows = parallel.shard_indices(len(items), self.rank, self.world)
+        sharded = self.world > 1
+        n_all = [int(f.shape[0]) for f, _ in items]
+        lens_all = [fe.num_frames(n) for n in n_all]
+        t_max = max(lens_all)
+        if t_max < 1:
+            raise ValueError("DeviceFeed: no utterance of the batch has a whole frame")
+        ilens = [lens_all[i] for i in rows]
+        B, nm = len(rows), (fe.n_masks if self.mask_seed is not None else 0)
+        short = np.asarray(items[0][0]).dtype == np.int16
+        total = sum(n_all[i] for i in rows)
+        wav_h = slot.shorts(total) if short else slot.floats(total)
+        wav_n = wav_h.numpy()
+        offs = [0]
+        for i in rows:
+            wav_n[offs[-1]:offs[-1] + n_all[i]] = items[i][0]
+            offs.append(offs[-1] + n_all[i])
+        # one int64 area: offsets [B + 1] | frame counts int32 [B] (padded to a whole word) | masks int32 [B, nm, 2]
+        lw = (B + 1) // 2
+        meta_h = slot.meta(B + 1 + lw + B * nm)
+        meta_n = meta_h.numpy()
+        meta_n[:B + 1] = offs
+        meta_n[B + 1:] = 0
+        i32 = meta_n[B + 1:].view(np.int32)
+        i32[:B] = ilens
+        if nm:
+            for r, i in enumerate(rows):
+                i32[2 * lw + r * nm * 2:2 * lw + (r + 1) * nm * 2] = fe.draw_masks(self.mask_seed, self._n - 1, i,
+                                                                                   lens_all[i]).reshape(-1)
+        ys_h = ys_lens = ys_host = None
+        info = dict(b_global=len(items), t_max=t_max, olength=None)
+        if self.kind != "speech":
+            tok_all = [items[i][1] for i in range(len(items))]
+            len_all = [len(t) for t in tok_all]
+            ys_lens = [len_all[i] for i in rows]
+            ys_host = [list(tok_all[i]) for i in rows]
+            ys_h = slot.ints(sum(ys_lens))
+            if ys_lens:
+                ys_h.numpy()[:] = np.concatenate([np.asarray(t, dtype=np.int64) for t in ys_host]) if sum(ys_lens) else 0
+            info.update(olength=max(len_all) + 1, text_norm=float(sum(n + 5 for n in len_all)))
+        with torch.cuda.stream(self._side):
+            wav_d = wav_h.to(self.device, non_blocking=True)
+            meta_d = meta_h.to(self.device, non_blocking=True)
+            ys_d = ys_h.to(self.device, non_blocking=True) if ys_h is not None else None
+            i32_d = meta_d[B + 1:].view(torch.int32)
+            masks_d = i32_d[2 * lw:2 * lw + B * nm * 2].view(B, nm, 2) if nm else None
+            xs_d = fe.run(wav_d, meta_d[:B + 1], i32_d[:B], t_max, masks_d)
+            event = torch.cuda.Event()
+            event.record(self._side)
+        slot.event = event
+        ys = list(torch.split(ys_d, ys_lens)) if ys_d is not None else None
+        xs_out = parallel.LocalShard(xs_d, ilens, ys, info) if sharded else xs_d
+        return Batch(self.kind, xs_out, ilens, ys, ys_host), event, (xs_d, ys_d)
 
     def _hand_over(self, prepared):
         """Consumer side: order the compute stream behind the upload and tell the allocator who uses the memory."""

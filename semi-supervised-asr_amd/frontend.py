@@ -1,0 +1,127 @@
+"""The front end: packed waveforms -> the [B, T_max, D] features the encoder reads, on the GPU (csrc/frontend.hip).
+
+Kaldi-convention log-mel filterbank energies (dither off, snip-edges), then - in dump.sh's order - CMVN, deltas and, in
+training feeds, SpecAugment masks; rows behind an utterance are exact zeros.  Three launches (fbank; the per-utterance
+statistics, in `utterance` mode only; the finish pass), no host synchronisation: every frame count follows from a sample
+count, which the host has.  There is no CPU path.
+
+Config (the `frontend` sub-dictionary; not a reference key):
+  sample_rate 16000, frame_length_ms 25, frame_shift_ms 10, n_fft 512, n_mels 80, low_freq 20, high_freq 0 (<= 0: from the
+  Nyquist frequency), preemph 0.97, delta_order 0 | 1 | 2,
+  cmvn      "none" | "utterance" | the path of an .npz with `mean` and `istd` (or `std`) vectors of n_mels entries
+  specaug   {n_freq_masks, max_freq_width, n_time_masks, max_time_width}; absent: no masks
+"""
+import numpy as np
+import torch
+
+import hip_backend as hb
+
+
+class Frontend(object):
+    def __init__(self, cfg=None):
+        cfg = dict(cfg or {})
+        sr = int(cfg.get("sample_rate", 16000))
+        self.plan = hb.FbankPlan(sample_rate=sr,
+                                 frame_length=int(round(sr * float(cfg.get("frame_length_ms", 25.0)) / 1000.0)),
+                                 frame_shift=int(round(sr * float(cfg.get("frame_shift_ms", 10.0)) / 1000.0)),
+                                 n_fft=int(cfg.get("n_fft", 512)), n_mels=int(cfg.get("n_mels", 80)),
+                                 low_freq=float(cfg.get("low_freq", 20.0)), high_freq=float(cfg.get("high_freq", 0.0)),
+                                 preemph=float(cfg.get("preemph", 0.97)))
+        self.n_mels = self.plan.n_mels
+        self.delta_order = int(cfg.get("delta_order", 0))
+        if self.delta_order not in (0, 1, 2):
+            raise hb.UnsupportedShape("frontend: delta_order %d (0, 1 or 2)" % self.delta_order)
+        cmvn = cfg.get("cmvn", "none") or "none"
+        self._global = None                                    # host [2, n_mels]: mean, istd
+        self._global_dev = {}
+        if cmvn == "none":
+            self.cmvn = hb.CMVN_NONE
+        elif cmvn == "utterance":
+            self.cmvn = hb.CMVN_UTTERANCE
+        else:
+            self.cmvn = hb.CMVN_GLOBAL
+            with np.load(cmvn) as z:
+                mean = np.asarray(z["mean"], dtype=np.float64).reshape(-1)
+                istd = (np.asarray(z["istd"], dtype=np.float64) if "istd" in z.files
+                        else 1.0 / np.asarray(z["std"], dtype=np.float64)).reshape(-1)
+            if mean.size != self.n_mels or istd.size != self.n_mels:
+                raise ValueError("frontend: %s holds %d / %d entries for %d mel bins" % (cmvn, mean.size, istd.size, self.n_mels))
+            self._global = np.stack([mean, istd]).astype(np.float32)
+        sa = dict(cfg.get("specaug") or {})
+        self.n_freq_masks, self.max_freq_width = int(sa.get("n_freq_masks", 0)), int(sa.get("max_freq_width", 0))
+        self.n_time_masks, self.max_time_width = int(sa.get("n_time_masks", 0)), int(sa.get("max_time_width", 0))
+        if not 0 <= self.max_freq_width <= self.n_mels or self.max_time_width < 0 or min(self.n_freq_masks, self.n_time_masks) < 0:
+            raise ValueError("frontend: specaug widths and counts must be >= 0, max_freq_width <= n_mels")
+
+    # ------------------------------------------------------------------ host arithmetic
+    @property
+    def output_dim(self):
+        return self.n_mels * (1 + self.delta_order)
+
+    @property
+    def n_masks(self):
+        return self.n_freq_masks + self.n_time_masks
+
+    def num_frames(self, n_samples):
+        return self.plan.num_frames(n_samples)
+
+    def frames_of(self, waveform):
+        """The length filter's and the sort's view of an utterance (dataset.DictDataset(frames_of=...))."""
+        return self.num_frames(waveform.shape[0])
+
+    def draw_masks(self, seed, batch_index, global_row, T_b):
+        """The SpecAugment masks of one utterance: int32 [n_masks, 2] of (start, width), frequency masks first.  One numpy
+        generator per GLOBAL row of a batch, seeded from (seed, batch, row) - feed.py's scheme for its input noise: a rank
+        draws its own rows only and the union of the rank-local batches is the one-process batch.  Widths are uniform in
+        [0, max width] (time: at most T_b), starts uniform over the positions that keep the mask inside."""
+        rs = np.random.RandomState([int(seed), int(batch_index), int(global_row)])
+        out = np.zeros((self.n_masks, 2), dtype=np.int32)
+        for m in range(self.n_freq_masks):
+            w = int(rs.randint(0, self.max_freq_width + 1))
+            out[m] = (int(rs.randint(0, self.n_mels - w + 1)), w)
+        for m in range(self.n_freq_masks, self.n_masks):
+            w = int(rs.randint(0, min(self.max_time_width, int(T_b)) + 1))
+            out[m] = (int(rs.randint(0, max(int(T_b) - w, 0) + 1)), w)
+        return out
+
+    # ------------------------------------------------------------------ device
+    def _stats_global(self, device):
+        key = str(device)
+        t = self._global_dev.get(key)
+        if t is None:
+            t = self._global_dev[key] = torch.from_numpy(self._global).to(device)
+        return t
+
+    def run(self, samples, offsets, frame_lens, t_max, masks=None):
+        """Device tensors in (packed samples int16 / float32, offsets int64 [B + 1], frame_lens int32 [B] = num_frames of
+        every sample count, masks int32 [B, n_masks, 2] or None), launches on the current stream -> xs [B, t_max, D]."""
+        B = offsets.numel() - 1
+        dev = samples.device
+        static = torch.empty(B, int(t_max), self.n_mels, device=dev, dtype=torch.float32)
+        hb.fbank(self.plan, samples, offsets, int(t_max), static, use_log=True)
+        stats = None
+        if self.cmvn == hb.CMVN_UTTERANCE:
+            stats = hb.feat_cmvn_stats(static, self.n_mels, frame_lens,
+                                       torch.empty(B, 2, self.n_mels, device=dev, dtype=torch.float32))
+        elif self.cmvn == hb.CMVN_GLOBAL:
+            stats = self._stats_global(dev)
+        out = torch.empty(B, int(t_max), self.output_dim, device=dev, dtype=torch.float32)
+        with_masks = masks is not None and self.n_masks > 0
+        return hb.feat_finish(static, self.n_mels, frame_lens, out, order=self.delta_order, cmvn=self.cmvn, stats=stats,
+                              masks=masks if with_masks else None, n_freq_masks=self.n_freq_masks if with_masks else 0,
+                              n_time_masks=self.n_time_masks if with_masks else 0)
+
+    def __call__(self, samples, offsets, masks=None, t_max=None):
+        """samples: ONE packed 1-D int16 / float32 tensor on the GPU; offsets: B + 1 host integers; masks: host int32
+        [B, n_masks, 2] or None -> (xs [B, T_max, D], ilens: host list)."""
+        if not samples.is_cuda:
+            raise RuntimeError("Frontend: samples must live on the GPU: the HIP path has no CPU fallback")
+        offs = [int(o) for o in offsets]
+        ilens = [self.num_frames(b - a) for a, b in zip(offs[:-1], offs[1:])]
+        t_max = max(ilens) if t_max is None else int(t_max)
+        if t_max < 1:
+            raise ValueError("Frontend: no utterance of the batch has a whole frame (%d samples)" % self.plan.frame_length)
+        dev = samples.device
+        masks_d = hb.to_device_i32(np.asarray(masks, dtype=np.int32), dev) if masks is not None and self.n_masks else None
+        xs = self.run(samples, hb.to_device_i64(offs, dev), hb.to_device_i32(ilens, dev), t_max, masks_d)
+        return xs, ilens

@@ -31,6 +31,7 @@ EXPORTS = (
     "asr_ctc_ws_bytes", "asr_ctc_loss_fwd", "asr_ctc_loss_bwd",
     "asr_ctc_prefix_init_f32", "asr_ctc_prefix_score_f32", "asr_beam_select_ctc_f32", "asr_ctc_prefix_advance_f32",
     "asr_ctc_align_ws_bytes", "asr_ctc_align_f32", "asr_ctc_greedy_f32",
+    "asr_fbank_num_frames", "asr_fbank_plan_bytes", "asr_fbank_f32", "asr_feat_cmvn_stats_f32", "asr_feat_finish_f32",
 )
 
 _lib = None
@@ -271,6 +272,11 @@ def load():
     lib.asr_ctc_align_ws_bytes.argtypes = [c_i, c_i, c_i, c_i, ctypes.POINTER(c_i64)]
     lib.asr_ctc_align_f32.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
     lib.asr_ctc_greedy_f32.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]
+    lib.asr_fbank_num_frames.argtypes = [c_i64, c_i, c_i, ctypes.POINTER(c_i64)]
+    lib.asr_fbank_plan_bytes.argtypes = [c_i, ctypes.POINTER(c_i64)]
+    lib.asr_fbank_f32.argtypes = [c_i, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_i64, c_i64, c_p]
+    lib.asr_feat_cmvn_stats_f32.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p]
+    lib.asr_feat_finish_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p]
     lib.asr_dec_feedback_fwd.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_p, c_i64,
                                          c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
     lib.asr_dec_feedback_bwd.argtypes = [c_i, c_i, c_i, c_i, c_p, c_p, c_i64, c_p, c_p, c_p, c_f, c_p, c_p]
@@ -998,6 +1004,153 @@ def ctc_greedy(logits, frame_lens, ids, n, frame_tok):
         raise UnsupportedShape("ctc_greedy: V %d (V >= 2)" % V)
     check(rc, "asr_ctc_greedy_f32")
     LAUNCHES["ctc_greedy"] += 1
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The front end (csrc/frontend.hip): waveforms -> features.
+FBANK_FRAME_TILE = 8       # ASR_FBANK_FRAME_TILE
+FBANK_MAX_MELS = 128       # ASR_FBANK_MAX_MELS
+SAMPLES_I16, SAMPLES_F32 = 0, 1
+CMVN_NONE, CMVN_GLOBAL, CMVN_UTTERANCE = 0, 1, 2
+
+
+def fbank_num_frames(n_samples, frame_length, frame_shift):
+    """asr_fbank_num_frames on plain integers (no tensors, no GPU): Kaldi's snip-edges frame count."""
+    out = c_i64(0)
+    check(load().asr_fbank_num_frames(int(n_samples), int(frame_length), int(frame_shift), ctypes.byref(out)),
+          "asr_fbank_num_frames")
+    return int(out.value)
+
+
+def fbank_plan_bytes(n_fft):
+    """asr_fbank_plan_bytes (no GPU); UnsupportedShape for an n_fft the kernel has no instantiation for."""
+    out = c_i64(0)
+    rc = load().asr_fbank_plan_bytes(int(n_fft), ctypes.byref(out))
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("fbank: n_fft %d (256 or 512)" % n_fft)
+    check(rc, "asr_fbank_plan_bytes")
+    return int(out.value)
+
+
+def _mel(f):
+    import numpy as np
+    return 1127.0 * np.log(1.0 + np.asarray(f, dtype=np.float64) / 700.0)
+
+
+class FbankPlan(object):
+    """The geometry of asr_fbank_f32 and its tables (window, twiddles, mel weights: float64 on the host, rounded to fp32, in
+    the layout include/asr_hip.h gives).  `words` is the host image (no GPU needed); `on(device)` is its device copy, made
+    once per device.  high_freq <= 0 counts from the Nyquist frequency, as in Kaldi."""
+
+    def __init__(self, sample_rate=16000, frame_length=400, frame_shift=160, n_fft=512, n_mels=80, low_freq=20.0,
+                 high_freq=0.0, preemph=0.97):
+        import numpy as np
+        self.sample_rate, self.frame_length, self.frame_shift = int(sample_rate), int(frame_length), int(frame_shift)
+        self.n_fft, self.n_mels, self.preemph = int(n_fft), int(n_mels), float(preemph)
+        nyquist = 0.5 * self.sample_rate
+        self.low_freq = float(low_freq)
+        self.high_freq = float(high_freq) if high_freq and high_freq > 0 else nyquist + float(high_freq or 0.0)
+        if (self.n_fft not in (256, 512) or not 0 < self.frame_length <= self.n_fft or self.frame_shift <= 0
+                or not 1 <= self.n_mels <= FBANK_MAX_MELS):
+            raise UnsupportedShape("fbank: n_fft %d (256 or 512), frame length %d (<= n_fft), shift %d, %d mel bins (1 .. %d)"
+                                   % (self.n_fft, self.frame_length, self.frame_shift, self.n_mels, FBANK_MAX_MELS))
+        if not 0.0 <= self.low_freq < self.high_freq <= nyquist:
+            raise ValueError("fbank: need 0 <= low_freq < high_freq <= Nyquist, got %g, %g" % (self.low_freq, self.high_freq))
+        N, M, L = self.n_fft, self.n_fft // 2, self.frame_length
+        window = np.zeros(N)
+        window[:L] = (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(L) / max(L - 1, 1))) ** 0.85
+        a = 2.0 * np.pi * np.arange(M // 2) / M
+        tw = np.stack([np.cos(a), -np.sin(a)], 1).reshape(-1)
+        a = 2.0 * np.pi * np.arange(M) / N
+        ut = np.stack([np.cos(a), -np.sin(a)], 1).reshape(-1)
+        edges = _mel(self.low_freq) + (_mel(self.high_freq) - _mel(self.low_freq)) * np.arange(self.n_mels + 2) / (self.n_mels + 1)
+        mel_bins = _mel(np.arange(M) * (self.sample_rate / float(N)))
+        start = np.zeros(FBANK_MAX_MELS, np.int32)
+        length = np.zeros(FBANK_MAX_MELS, np.int32)
+        woff = np.zeros(FBANK_MAX_MELS, np.int32)
+        packed = np.zeros(N)
+        used = 0
+        for j in range(self.n_mels):
+            left, centre, right = edges[j], edges[j + 1], edges[j + 2]
+            up = (mel_bins - left) / (centre - left)
+            down = (right - mel_bins) / (right - centre)
+            w = np.where((mel_bins > left) & (mel_bins < right), np.where(mel_bins <= centre, up, down), 0.0)
+            nz = np.nonzero(w)[0]
+            if nz.size:
+                start[j], length[j], woff[j] = nz[0], nz[-1] - nz[0] + 1, used
+                packed[used:used + length[j]] = w[nz[0]:nz[-1] + 1]
+                used += int(length[j])
+        assert used <= N
+        self.words = np.concatenate([window.astype(np.float32).view(np.int32), tw.astype(np.float32).view(np.int32),
+                                     ut.astype(np.float32).view(np.int32), start, length, woff,
+                                     packed.astype(np.float32).view(np.int32)])
+        assert self.words.size * 4 == fbank_plan_bytes(N)
+        self._dev = {}
+
+    def num_frames(self, n_samples):
+        n = int(n_samples)
+        return 1 + (n - self.frame_length) // self.frame_shift if n >= self.frame_length else 0
+
+    def on(self, device):
+        key = str(torch.device(device))
+        buf = self._dev.get(key)
+        if buf is None:
+            buf = self._dev[key] = torch.from_numpy(self.words).to(device)
+        return buf
+
+
+def fbank(plan, samples, offsets, T_max, out, col0=0, use_log=True):
+    """asr_fbank_f32: samples = ONE packed 1-D int16 or float32 tensor, offsets int64 [B + 1] on the device -> rows (b, t) of
+    out [B, T_max, ld] at columns col0 .. col0 + n_mels (rows behind an utterance's frames are not touched)."""
+    if not (samples.is_cuda and offsets.is_cuda and out.is_cuda):
+        raise RuntimeError("fbank: tensors must live on the GPU: the HIP path has no CPU fallback")
+    if samples.dtype not in (torch.int16, torch.float32) or samples.dim() != 1 or not samples.is_contiguous():
+        raise RuntimeError("fbank: samples must be one packed 1-D int16 or float32 tensor")
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or offsets.numel() < 2:
+        raise RuntimeError("fbank: offsets must be int64 [B + 1]")
+    B = offsets.numel() - 1
+    if out.dtype != torch.float32 or out.dim() != 3 or out.shape[0] != B or out.shape[1] != T_max or out.stride(2) != 1 \
+            or out.stride(0) != T_max * out.stride(1):
+        raise RuntimeError("fbank: out must be float32 [B, T_max, ld] with rows of one leading dimension")
+    rc = load().asr_fbank_f32(B, int(T_max), c_p(samples.data_ptr()), SAMPLES_I16 if samples.dtype == torch.int16 else SAMPLES_F32,
+                              c_p(offsets.data_ptr()), plan.frame_length, plan.frame_shift, plan.n_fft, plan.n_mels,
+                              plan.preemph, 1 if use_log else 0, c_p(plan.on(out.device).data_ptr()), ptr(out),
+                              int(out.stride(1)), int(col0), stream())
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("fbank: B %d, n_fft %d, frame length %d, %d mel bins" % (B, plan.n_fft, plan.frame_length, plan.n_mels))
+    check(rc, "asr_fbank_f32")
+    LAUNCHES["fbank"] += 1
+    return out
+
+
+def feat_cmvn_stats(x, n_mels, frame_lens, stats):
+    """asr_feat_cmvn_stats_f32: x [B, T, ld >= n_mels], frame_lens int32 [B] -> stats [B, 2, n_mels] (mean, 1 / std)."""
+    B, T = int(x.shape[0]), int(x.shape[1])
+    rc = load().asr_feat_cmvn_stats_f32(B, T, int(n_mels), ptr(x), int(x.stride(1)), ptr(frame_lens), ptr(stats), stream())
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("feat_cmvn_stats: %d bins (at most %d)" % (n_mels, FBANK_MAX_MELS))
+    check(rc, "asr_feat_cmvn_stats_f32")
+    LAUNCHES["feat_cmvn_stats"] += 1
+    return stats
+
+
+def feat_finish(x, n_mels, frame_lens, out, order=0, cmvn=CMVN_NONE, stats=None, masks=None, n_freq_masks=0, n_time_masks=0):
+    """asr_feat_finish_f32: static features x [B, T, ld >= n_mels] -> out [B, T, n_mels (1 + order)]: CMVN, deltas, masks
+    (int32 [B, n_freq_masks + n_time_masks, 2] of (start, width)), zeros behind every utterance."""
+    B, T = int(x.shape[0]), int(x.shape[1])
+    if tuple(out.shape) != (B, T, n_mels * (1 + order)) or not out.is_contiguous() or x.stride(2) != 1 \
+            or x.stride(0) != T * x.stride(1):
+        raise RuntimeError("feat_finish: out must be contiguous [B, T, n_mels (1 + order)], x [B, T, ld]")
+    if masks is not None and (masks.dtype != torch.int32 or tuple(masks.shape) != (B, n_freq_masks + n_time_masks, 2)
+                              or not masks.is_contiguous()):
+        raise RuntimeError("feat_finish: masks must be int32 [B, n_freq_masks + n_time_masks, 2]")
+    rc = load().asr_feat_finish_f32(B, T, int(n_mels), int(order), ptr(x), int(x.stride(1)), ptr(frame_lens), int(cmvn),
+                                    ptr(stats), ptr(masks), int(n_freq_masks), int(n_time_masks), ptr(out), stream())
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("feat_finish: %d bins (at most %d), delta order %d (0 .. 2)" % (n_mels, FBANK_MAX_MELS, order))
+    check(rc, "asr_feat_finish_f32")
+    LAUNCHES["feat_finish"] += 1
+    return out
 
 
 def colsum(X, out=None, accumulate=False):

@@ -70,6 +70,16 @@ StepScalar.__hash__ = lambda self: hash(float(self))
 class Solver(object):
     def __init__(self, config, load_model=False):
         self.config = config
+        # `frontend` (not a reference key; absent by default): the datasets hold 1-D waveforms and the features are computed
+        # on the GPU (frontend.Frontend); absent, the datasets hold feature matrices as in the reference
+        self.frontend = None
+        if config.get("frontend") is not None:
+            from frontend import Frontend
+            self.frontend = Frontend(config["frontend"])
+            if int(config["input_dim"]) != self.frontend.output_dim:
+                raise ValueError("config: input_dim %d, but the front end gives %d features per frame (n_mels %d x (1 + "
+                                 "delta_order %d))" % (int(config["input_dim"]), self.frontend.output_dim,
+                                                       self.frontend.n_mels, self.frontend.delta_order))
         self._paths_reported = False
         self._pending = []                 # train steps whose host read (scalars + abort latch) is outstanding, oldest first
         self._pinned = None                # their landing slots in pinned host memory
@@ -146,12 +156,14 @@ class Solver(object):
         return counts / counts.sum()
 
     def calculate_length_proportion(self):
-        frames = sum(x.shape[0] for x, _ in self.train_lab_dataset)
+        frames_of = self.frontend.frames_of if self.frontend is not None else (lambda x: x.shape[0])
+        frames = sum(frames_of(x) for x, _ in self.train_lab_dataset)
         chars = sum(len(y) for _, y in self.train_lab_dataset)
         return chars / frames
 
     def _dataset(self, name, config, sort=True):
-        return PickleDataset(os.path.join(self.config["dataset_root_dir"], f"{name}.pkl"), config=config, sort=sort)
+        return PickleDataset(os.path.join(self.config["dataset_root_dir"], f"{name}.pkl"), config=config, sort=sort,
+                             frames_of=self.frontend.frames_of if self.frontend is not None else None)
 
     def _loader(self, dataset, batch_size, shuffle, drop_last, **kw):
         # every rank must draw the SAME global batches: seed the sampler identically
@@ -174,7 +186,7 @@ class Solver(object):
         self.dev_dataset = self._dataset(cfg["dev_set"], None)
         self.dev_loader = self._loader(self.dev_dataset, cfg["batch_size"] // 2, False, False)
 
-    def _feed(self, loader, kind="labeled", sharded=True, noise_std=0.0, endless=False):
+    def _feed(self, loader, kind="labeled", sharded=True, noise_std=0.0, endless=False, train=False):
         """The device-side view of a loader: the same batches in the same order (the loader's own batch sampler), collated
         one step ahead into pinned memory and uploaded on a side stream (feed.DeviceFeed) - this rank's strided rows only
         when `sharded` and the run is data parallel.  Config keys (not reference keys): `prefetch_batches` (default 2),
@@ -187,11 +199,11 @@ class Solver(object):
         rank, world = (self.rank, self.world) if sharded else (0, 1)
         return DeviceFeed(infinite_iter(raw) if endless else raw, "cuda" if torch.cuda.is_available() else "cpu", kind=kind,
                           rank=rank, world=world, depth=int(self.config.get("prefetch_batches", 2)), noise_std=noise_std,
-                          thread=bool(self.config.get("prefetch_thread", True)))
+                          thread=bool(self.config.get("prefetch_thread", True)), frontend=self.frontend, train=train)
 
     def get_infinite_iter(self):
-        self.lab_iter = iter(self._feed(self.train_lab_loader, endless=True))
-        self.unlab_x_iter = iter(self._feed(self.train_unlab_x_loader, kind="speech", endless=True))
+        self.lab_iter = iter(self._feed(self.train_lab_loader, endless=True, train=True))
+        self.unlab_x_iter = iter(self._feed(self.train_unlab_x_loader, kind="speech", endless=True, train=True))
         self.unlab_y_iter = iter(self._feed(self.train_unlab_y_loader, kind="text", endless=True))
 
     # ------------------------------------------------------------------ model + optimisers
@@ -753,7 +765,7 @@ class Solver(object):
         push, done = self._lagged(log)
         # input noise (solver.py:370-373) is added by the feed, on the host, before the upload
         noise = float(cfg["gaussian_std"]) if cfg["add_gaussian"] and epoch >= cfg["gaussian_epoch"] else 0.0
-        for it, (xs, ilens, ys) in enumerate(self._feed(self.train_lab_loader, noise_std=noise)):
+        for it, (xs, ilens, ys) in enumerate(self._feed(self.train_lab_loader, noise_std=noise, train=True)):
             push((it, self.sup_train_one_iteration(xs, ilens, ys, tf_rate)))
         done()
         return running[0] / steps_per_epoch

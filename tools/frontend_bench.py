@@ -1,0 +1,169 @@
+"""What the GPU front end costs.  Two measurements, each appended as one JSON line to --out (default
+profiles/frontend_bench.jsonl):
+
+  front_end   a cfg-2 batch of waveforms (32 ragged utterances, U[0.6, 1] x 8 s of int16 at 16 kHz, 80 bins; delta_order 0
+              and 2, utterance CMVN) through frontend.Frontend - samples already in HBM, device events around `--iters`
+              calls - against the same computation in torch on the CPU (torch.stft-based, fp32, this machine's CPU share).
+  epoch_loop  Solver.sup_train_one_iteration at cfg-2 fed by feed.DeviceFeed from waveforms (front end on the side stream)
+              against the same Solver fed from precomputed features of the same frame counts, ALTERNATING in one process:
+              `--rounds` rounds of (features, waveforms), each a window of `--steps` steps behind `--warmup` steps, wall
+              clock around a window that ends in flush + device synchronise.  Reports the median window of either feed and
+              the spread of each feed's own windows (a difference inside it is not one).
+"""
+import argparse
+import contextlib
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def cpu_frontend(waves, order, threads):
+    """The same computation in torch on the CPU, fp32: frames -> mean, pre-emphasis, Povey window -> torch.stft-style
+    rfft power -> mel -> log -> utterance CMVN -> deltas, padded.  -> seconds per batch (best of 3)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import frontend_ref as R
+    torch.set_num_threads(threads)
+    W = torch.from_numpy(R.mel_weights(80, 512, 16000, 20.0, 8000.0).astype(np.float32))
+    window = torch.from_numpy(R.povey_window(400).astype(np.float32))
+    taps = [None, torch.from_numpy(R.S1.astype(np.float32)), torch.from_numpy(R.S2.astype(np.float32))]
+    xs = [torch.from_numpy(w.astype(np.float32)) for w in waves]
+
+    def once():
+        feats = []
+        for x in xs:
+            fr = x.unfold(0, 400, 160)
+            fr = fr - fr.mean(1, keepdim=True)
+            fr = (fr - 0.97 * torch.cat([fr[:, :1], fr[:, :-1]], 1)) * window
+            # torch.stft on pre-cut frames: one frame per "signal", no centring, a rectangular window of n_fft
+            spec = torch.stft(torch.nn.functional.pad(fr, (0, 112)), 512, hop_length=512, win_length=512, center=False,
+                              window=torch.ones(512), return_complex=True)[:, :256, 0]
+            logmel = torch.log(torch.clamp((spec.real ** 2 + spec.imag ** 2) @ W.T, min=R.FLT_EPSILON))
+            y = (logmel - logmel.mean(0)) / logmel.var(0, unbiased=False).clamp(min=1e-10).sqrt()
+            blocks = [y]
+            for k in range(1, order + 1):
+                w = 2 * k
+                idx = (torch.arange(y.shape[0])[:, None] + torch.arange(-w, w + 1)[None, :]).clamp(0, y.shape[0] - 1)
+                blocks.append((y[idx] * taps[k][None, :, None]).sum(1))
+            feats.append(torch.cat(blocks, 1))
+        return torch.nn.utils.rnn.pad_sequence(feats, batch_first=True)
+    once()
+    best = 1e9
+    for _ in range(3):
+        t0 = time.perf_counter()
+        once()
+        best = min(best, time.perf_counter() - t0)
+    return best
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--skip-epoch-loop", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frontend_bench.jsonl"))
+    args = ap.parse_args()
+    import __graft_entry__ as entry
+    entry.build()
+    import bench
+    import hip_backend as hb
+    from dataset import synthetic_utterances, synthetic_waveforms
+    from feed import DeviceFeed
+    from frontend import Frontend
+    assert torch.cuda.is_available(), "frontend_bench.py measures on the GPU"
+    dev = torch.device("cuda")
+    spec = bench.CONFIGS["cfg2"]
+    c, B, T = dict(spec["model"]), spec["batch"], spec["frames"]
+    data = synthetic_waveforms(B, c["output_dim"], 8.0, seed=1234)
+    items = sorted([(v["feature"], v["token_ids"]) for v in data.values()], key=lambda it: -len(it[0]))
+    waves = [f for f, _ in items]
+    offs = np.concatenate([[0], np.cumsum([len(w) for w in waves])]).tolist()
+    samples = torch.from_numpy(np.concatenate(waves)).to(dev)
+    threads = bench.usable_cpus()
+    lines = []
+
+    for order in (0, 2):
+        fe = Frontend(dict(n_mels=80, delta_order=order, cmvn="utterance"))
+        for _ in range(5):
+            xs, ilens = fe(samples, offs)
+        torch.cuda.synchronize()
+        hb.LAUNCHES.clear()
+        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        for _ in range(args.iters):
+            xs, ilens = fe(samples, offs)
+        stop.record()
+        torch.cuda.synchronize()
+        gpu_ms = start.elapsed_time(stop) / args.iters
+        cpu_ms = cpu_frontend(waves, order, threads) * 1e3
+        frames = sum(ilens)
+        lines.append(dict(tool="tools/frontend_bench.py", measurement="front_end", delta_order=order, cmvn="utterance",
+                          workload="%d ragged utterances, U[0.6, 1] x 8 s int16 at 16 kHz, 80 bins" % B, frames=frames,
+                          samples=int(samples.numel()), upload_bytes_waveform=int(samples.numel()) * 2,
+                          upload_bytes_features=B * max(ilens) * fe.output_dim * 4,
+                          gpu_ms_per_batch=round(gpu_ms, 4), launches_per_batch={k: v // args.iters for k, v in hb.LAUNCHES.items()},
+                          timing="device events around %d calls (host enqueue included), samples resident" % args.iters,
+                          cpu_torch_ms_per_batch=round(cpu_ms, 2), cpu_threads=threads, cpu_over_gpu=round(cpu_ms / gpu_ms, 1)))
+
+    if not args.skip_epoch_loop:
+        tmp = tempfile.mkdtemp(prefix="frontend_bench_")
+        fe = Frontend(dict(n_mels=80, delta_order=0, cmvn="utterance"))
+        assert fe.output_dim == c["input_dim"]
+        sv = bench.make_solver(c, B, T, os.path.join(tmp, "cfg2"))
+        feats = synthetic_utterances(B, c["input_dim"], c["output_dim"], T, seed=1234)
+        f_items = sorted([(v["feature"], v["token_ids"]) for v in feats.values()], key=lambda it: -len(it[0]))
+        # the same frame counts and labels on either side: features cut to the front end's frame count of each waveform
+        f_items = [(np.resize(f, (fe.num_frames(len(w)), c["input_dim"])).astype(np.float32), y)
+                   for (f, _), (w, y) in zip(f_items, items)]
+        n = args.warmup + args.steps
+
+        def window(kind):
+            source = [items if kind == "waveforms" else f_items] * n
+            feed = DeviceFeed(source, dev, frontend=fe if kind == "waveforms" else None)
+            with contextlib.redirect_stdout(sys.stderr):
+                for i, (xs, ilens, ys) in enumerate(feed):
+                    if i == args.warmup:
+                        sv.flush()
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                    last = sv.sup_train_one_iteration(xs, ilens, ys, 1.0)
+                sv.flush()
+                torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / args.steps * 1e3, float(last)
+        windows, loss = {"features": [], "waveforms": []}, {}
+        for _ in range(args.rounds):
+            for kind in ("features", "waveforms"):
+                ms, loss[kind] = window(kind)
+                windows[kind].append(ms)
+        med = {k: statistics.median(w) for k, w in windows.items()}
+        lines.append(dict(tool="tools/frontend_bench.py", measurement="epoch_loop", call="Solver.sup_train_one_iteration",
+                          workload="%s, batch %d, 80 x <= %d frames, fed by feed.DeviceFeed" % (spec["name"], B, fe.num_frames(128000)),
+                          rounds=args.rounds, steps_per_window=args.steps, warmup_steps=args.warmup,
+                          ms_per_step_features=round(med["features"], 3), ms_per_step_waveforms=round(med["waveforms"], 3),
+                          waveforms_over_features=round(med["waveforms"] / med["features"], 4),
+                          windows_ms_features=[round(w, 3) for w in windows["features"]],
+                          windows_ms_waveforms=[round(w, 3) for w in windows["waveforms"]],
+                          spread_features=round((max(windows["features"]) - min(windows["features"])) / med["features"], 4),
+                          spread_waveforms=round((max(windows["waveforms"]) - min(windows["waveforms"])) / med["waveforms"], 4),
+                          last_loss=loss, arith=hb.arith_name()))
+
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as f:
+        for rec in lines:
+            line = json.dumps(rec)
+            print(line)
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
