@@ -1006,6 +1006,42 @@ int asr_ctc_greedy_f32(int B, int T, int V, const float* logits, int64_t ld, con
                        int32_t* n, int32_t* frame_tok, asr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * CTC prefix beam search (csrc/ctc_beam.hip): the K best label sequences of the CTC head, the first pass of
+ * two-pass decoding.  Not a reference operator.  Two entries added to ABI version 8 WITHOUT a version change, like the other
+ * CTC entries: additive.
+ * logits, ld, frame_lens are asr_ctc_align_f32's: RAW logits [B][T][V] fp32 with row stride ld >= V, frame_lens int32 [B] on
+ * the device (clamped to 0 .. T; frames t >= T_b = frame_lens[b] are never read and may hold NaN), blank = index 0,
+ * x[t][v] = logits[b][t][v] - logsumexp_v logits[b][t].  (+) is log(exp a + exp b) with (-inf) (+) x = x.
+ *   The beam of an utterance holds at most K prefixes (token sequences), each with pb / pnb - the log-mass of its paths that
+ *   end in blank / in a non-blank - and tot = pb (+) pnb; it starts as the empty prefix at (0, -inf).  Frame t's candidates:
+ *     stay    of entry k (prefix p), flat index k:  pb' = tot + x[t][0];  pnb' = pnb + x[t][last(p)] (-inf for the empty p)
+ *     extend  entry k by c in 1 .. V-1, flat index K + k (V - 1) + (c - 1):  pb' = -inf,
+ *             pnb' = pb + x[t][c] if c == last(p), tot + x[t][c] otherwise
+ *     merge   where p.c IS the prefix of entry k' (as token sequences) the extension is no candidate: its pnb' is added with
+ *             (+) to the pnb' of the stay candidate of k' (entries in ascending order; at most one can match)
+ *   The new beam: the K candidates of greatest tot', ties to the lower flat index, -inf never selected (fewer than K entries
+ *   may be live), in that order.  No vocabulary pruning, no blank threshold.  After frame T_b - 1 the beam is the result:
+ *     hyp      int32 [B][K][T]  the tokens of rank r, padded with -1 (at most T_b tokens)
+ *     hyp_len  int32 [B][K]     their count; -1 in an unused slot
+ *     score    fp32 [B][K]      tot, descending; -inf in an unused slot
+ *   An utterance with T_b = 0 gets the empty hypothesis at score 0 in slot 0.
+ *   Prefix identity inside the kernel: a 64-bit hash of the token sequence (h' = mix(h + token), the splitmix64 finaliser),
+ *   with the length - p.c and q are taken as equal when hash, length and last token agree.
+ *   Two launches: the frame log-sum-exps; then one workgroup per utterance (one wave when K V <= ASR_CTC_BEAM_ONE_WAVE_KV,
+ *   256 threads beyond) runs every frame, the ranking and the backtrace.  The per-frame history (parent slot, token) stays
+ *   in LDS when T K <= ASR_CTC_BEAM_LDS_ENTRIES and goes to the workspace otherwise.
+ *   asr_ctc_beam_ws_bytes  the bytes of the workspace (8-byte aligned: ASR_E_ALIGN):  4 R with R = B T rounded up to 64 (the
+ *   log-sum-exps) + 8 B T K if T K > ASR_CTC_BEAM_LDS_ENTRIES.
+ * V < 2, K outside 1 .. ASR_BEAM_KMAX, K V > INT_MAX / 2: ASR_E_SHAPE.  No floating-point atomics, no host synchronisation, no
+ * allocation; a function of its inputs and shapes only - the same bits in every run, in and outside deterministic mode.
+ * ------------------------------------------------------------------------------------- */
+#define ASR_CTC_BEAM_ONE_WAVE_KV 1024
+#define ASR_CTC_BEAM_LDS_ENTRIES 4096
+int asr_ctc_beam_ws_bytes(int B, int T, int V, int K, int64_t* ws_bytes);
+int asr_ctc_beam_f32(int B, int T, int V, int K, const float* logits, int64_t ld, const int32_t* frame_lens, int32_t* hyp,
+                     int32_t* hyp_len, float* score, void* ws, asr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * The front end (csrc/frontend.hip): packed waveforms -> the [B][T][D] features the encoder reads.  Not
  * reference operators - the reference reads features that Kaldi computed.  Five entries added to ABI version 8 WITHOUT a
  * version change: additive.

@@ -31,6 +31,7 @@ EXPORTS = (
     "asr_ctc_ws_bytes", "asr_ctc_loss_fwd", "asr_ctc_loss_bwd",
     "asr_ctc_prefix_init_f32", "asr_ctc_prefix_score_f32", "asr_beam_select_ctc_f32", "asr_ctc_prefix_advance_f32",
     "asr_ctc_align_ws_bytes", "asr_ctc_align_f32", "asr_ctc_greedy_f32",
+    "asr_ctc_beam_ws_bytes", "asr_ctc_beam_f32",
     "asr_fbank_num_frames", "asr_fbank_plan_bytes", "asr_fbank_f32", "asr_feat_cmvn_stats_f32", "asr_feat_finish_f32",
 )
 
@@ -272,6 +273,8 @@ def load():
     lib.asr_ctc_align_ws_bytes.argtypes = [c_i, c_i, c_i, c_i, ctypes.POINTER(c_i64)]
     lib.asr_ctc_align_f32.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
     lib.asr_ctc_greedy_f32.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]
+    lib.asr_ctc_beam_ws_bytes.argtypes = [c_i, c_i, c_i, c_i, ctypes.POINTER(c_i64)]
+    lib.asr_ctc_beam_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p]
     lib.asr_fbank_num_frames.argtypes = [c_i64, c_i, c_i, ctypes.POINTER(c_i64)]
     lib.asr_fbank_plan_bytes.argtypes = [c_i, ctypes.POINTER(c_i64)]
     lib.asr_fbank_f32.argtypes = [c_i, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_i64, c_i64, c_p]
@@ -1004,6 +1007,40 @@ def ctc_greedy(logits, frame_lens, ids, n, frame_tok):
         raise UnsupportedShape("ctc_greedy: V %d (V >= 2)" % V)
     check(rc, "asr_ctc_greedy_f32")
     LAUNCHES["ctc_greedy"] += 1
+
+
+CTC_BEAM_ONE_WAVE_KV = 1024      # ASR_CTC_BEAM_ONE_WAVE_KV: K V up to this runs one wave per utterance
+CTC_BEAM_LDS_ENTRIES = 4096      # ASR_CTC_BEAM_LDS_ENTRIES: an utterance's T K history entries stay in LDS up to this count
+
+
+def ctc_beam_ws_bytes(B, T, V, K):
+    """asr_ctc_beam_ws_bytes on plain integers (no tensors, no GPU) -> the workspace bytes of a ctc_beam call;
+    UnsupportedShape for sizes the kernel refuses (V < 2, a beam width outside 1 .. BEAM_KMAX)."""
+    need = c_i64(0)
+    rc = load().asr_ctc_beam_ws_bytes(int(B), int(T), int(V), int(K), ctypes.byref(need))
+    if rc == -2:
+        raise UnsupportedShape("ctc_beam: B %d, T %d, V %d, beam %d (beam 1 .. %d, V >= 2)" % (B, T, V, K, BEAM_KMAX))
+    check(rc, "asr_ctc_beam_ws_bytes")
+    return need.value
+
+
+def ctc_beam(logits, frame_lens, K, hyp, hyp_len, score, ws):
+    """asr_ctc_beam_f32 (csrc/ctc_beam.hip): the CTC prefix beam search of every utterance.  logits [B, T, V]
+    fp32 raw (a view with row stride >= V is taken as it is), frame_lens int32 [B] on the device; the outputs hyp int32
+    [B, K, T] (padded with -1), hyp_len int32 [B, K] (-1: an unused slot), score fp32 [B, K] (descending, -inf: unused) and
+    the workspace ws (a float32 tensor of at least ctc_beam_ws_bytes bytes) are the caller's.  Two launches."""
+    logits, ld = _ctc_view(logits, "ctc logits")
+    B, T, V = logits.shape
+    need = ctc_beam_ws_bytes(B, T, V, K)
+    if ws.numel() * 4 < need or tuple(hyp.shape) != (B, K, T) or hyp_len.numel() != B * K or score.numel() != B * K:
+        raise RuntimeError("ctc_beam: the workspace or an output is smaller than B %d, T %d, beam %d need" % (B, T, K))
+    if not (hyp.is_contiguous() and hyp_len.is_contiguous() and score.is_contiguous()):
+        raise RuntimeError("ctc_beam: the outputs must be contiguous")
+    rc = load().asr_ctc_beam_f32(B, T, V, int(K), ptr(logits), int(ld), ptr(frame_lens), ptr(hyp), ptr(hyp_len), ptr(score),
+                                 ptr(ws), stream())
+    check(rc, "asr_ctc_beam_f32")
+    LAUNCHES["ctc_beam"] += 1
+    LAUNCHES["ctc_beam_launch"] += 2
 
 
 # ---------------------------------------------------------------------------------------------------------------------

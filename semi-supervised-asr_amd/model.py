@@ -451,6 +451,90 @@ class Decoder(torch.nn.Module):
             return tokens, scores
         return tokens[:, 0], scores[:, 0]
 
+    def score_hypotheses(self, enc_pad, enc_len, hyp, hyp_len):
+        """The second pass of two-pass decoding: hyp int32 [B, K, T] (padded, as ops.ctc_beam returns them) and
+        hyp_len int32 [B, K] (-1: an unused slot, scored as the empty hypothesis and masked by the caller), both on the device
+        -> (att fp32 [B, K]: the sum of the decoder's log-probabilities of hypothesis k's tokens and its <EOS> given utterance
+        b, tok_out int64 [B K, T + 1]: every hypothesis with its <EOS>, <EOS>-padded, mask bool [B K, T + 1]: its len + 1
+        positions).  One teacher-forced pass of T + 1 steps over B K rows on the sequence kernels, every row attending to its
+        utterance's frames; eval arithmetic (no dropout, no label smoothing) whatever the module's mode, no autograd, and no
+        host read: the lengths stay on the device, the step count is the shape's."""
+        bsz, K, T = hyp.shape
+        rows, steps, dev = bsz * K, T + 1, enc_pad.device
+        att = self.attention
+        att.reset()
+        with torch.no_grad():
+            n = hyp_len.reshape(rows, 1).clamp(min=0).long()
+            pos = torch.arange(steps, device=dev).unsqueeze(0)
+            body = torch.cat([hyp.reshape(rows, T).long(), torch.full((rows, 1), self.eos, dtype=torch.long, device=dev)], dim=1)
+            tok_out = torch.where(pos < n, body, torch.full_like(body, self.eos))             # [y, <EOS>, <EOS>, ...]
+            tok_in = torch.cat([torch.full((rows, 1), self.bos, dtype=torch.long, device=dev), tok_out[:, :-1]], dim=1)
+            mask = pos <= n
+            enc_rep = enc_pad.repeat_interleave(K, dim=0)
+            len_rep = [int(l) for l in enc_len for _ in range(K)]
+            opts = dict(scaling=2.0, smooth=False, smooth_scaling=1.0, sample=False, bos=self.bos, eos=self.eos,
+                        tokens=tok_in.contiguous(), tf_flags=[True] * steps, skip_pred=True, L=steps)
+            P = ops.linear(enc_rep, att.mlp_enc.weight, att.mlp_enc.bias)
+            Q = ops.linear(enc_rep, att.mlp_o.weight, None)
+            w0 = AttLoc.initial_weights(len_rep, enc_rep.shape[1], dev)
+            cell = self.LSTMCell
+            logits, _, _ = ops.decoder_sequence(
+                P, Q, self.embedding.weight, cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh,
+                att.mlp_dec.weight, att.loc_conv.weight, att.mlp_att.weight, att.gvec.weight, att.mlp_o.bias,
+                self.output_layer.weight, self.output_layer.bias, w0, opts)
+            logp = ops.label_logprob(logits, tok_out.t().contiguous())                        # [L, B K], time-major
+            att_score = torch.where(mask, logp.t(), torch.zeros((), device=dev)).sum(dim=1).view(bsz, K)
+        return att_score, tok_out, mask
+
+    def check_lm(self, lm):
+        """ValueError unless lm (an LM module, or None) predicts the decoder's vocabulary with its <BOS> / <EOS>."""
+        if lm is None:
+            return
+        V = self.output_layer.weight.shape[0]
+        if lm.output_dim != V:
+            raise ValueError("the LM predicts %d tokens, the decoder %d" % (lm.output_dim, V))
+        if (lm.bos, lm.eos) != (self.bos, self.eos):
+            raise ValueError("the LM's <BOS>/<EOS> (%d, %d) are not the decoder's (%d, %d)" % (lm.bos, lm.eos, self.bos, self.eos))
+
+    def rescore_ctc_beams(self, enc_pad, enc_len, ctc_logits, ctc_lens, topk, ctc_weight=0.5, length_penalty=0.0, *, lm=None,
+                          lm_weight=0.0):
+        """Two-pass decoding behind the encoder (E2E.recognize_two_pass): ops.ctc_beam over ctc_logits [B, T', V]
+        (raw logits of a CTC head on enc_pad, blank = <PAD> = 0; ctc_lens int32 [B] on the device), score_hypotheses over
+        the B topk rows, with lm and lm_weight != 0 LM.forward over the same rows, then the combination
+        ((1 - w) att + w ctc + lm_weight lm) / (len + 1)**length_penalty and the ranking, ties to the search's order.
+        -> (tokens int64 [B, topk, T' + 1] ranked and <EOS>-padded, scores [B, topk] with -inf in unused slots, the parts:
+        dict(hyp, hyp_len, ctc, att, lm, order)).  No host read."""
+        K, w = int(topk), float(ctc_weight)
+        if self.pad != 0:
+            raise ValueError("the CTC search takes <PAD> = 0 as its blank; pad is %d" % self.pad)
+        self.check_lm(lm)
+        use_lm = lm is not None and float(lm_weight) != 0.0
+        with torch.no_grad():
+            hyp, hyp_len, ctc = ops.ctc_beam(ctc_logits, ctc_lens, K)
+            bsz, _, T = hyp.shape
+            att, tok_out, mask = self.score_hypotheses(enc_pad, enc_len, hyp, hyp_len)
+            lm_score = None
+            if use_lm:
+                was_training = lm.training
+                lm.eval()
+                try:
+                    lm_logp, _, _ = lm(tok_out, discrete_input=False)
+                finally:
+                    lm.train(was_training)
+                lm_score = torch.where(mask, lm_logp, torch.zeros((), device=lm_logp.device)).sum(dim=1).view(bsz, K)
+            # (1 - w) att + w ctc + lm_weight lm: one rounding per operation (torch's elementwise kernels do not contract)
+            w_t = torch.tensor(w, dtype=torch.float32)
+            total = att * float(1.0 - w_t) + ctc * float(w_t)
+            if use_lm:
+                total = total + lm_score * float(torch.tensor(float(lm_weight), dtype=torch.float32))
+            if float(length_penalty) != 0.0:
+                total = total / (hyp_len.clamp(min=0) + 1).to(torch.float32).pow(float(length_penalty))
+            total = torch.where(hyp_len >= 0, total, torch.full_like(total, float("-inf")))
+            order = torch.sort(total, dim=1, descending=True, stable=True).indices                # ties to the lower k
+            scores = torch.gather(total, 1, order)
+            tokens = torch.gather(tok_out.view(bsz, K, T + 1), 1, order.unsqueeze(2).expand(bsz, K, T + 1))
+        return tokens, scores, dict(hyp=hyp, hyp_len=hyp_len, ctc=ctc, att=att, lm=lm_score, order=order)
+
 
 class E2E(torch.nn.Module):
     """model.py:408-456."""
@@ -540,6 +624,10 @@ class E2E(torch.nn.Module):
     def _ctc_logits(self, data, ilens, what):
         """Encoder, then ctc_lo on the rows ctc_nll uses -> (raw CTC logits [B, T', V], the frame lengths on the device, and
         on the host).  Without the head: ValueError before any launch."""
+        return self._encode_ctc(data, ilens, what)[:3]
+
+    def _encode_ctc(self, data, ilens, what):
+        """_ctc_logits with the encoder output behind it: (logits, frame lengths on the device, on the host, enc_h)."""
         if not hasattr(self, "ctc_lo"):
             raise ValueError("%s needs the CTC head: build the model with ctc_weight > 0" % what)
         if data.is_cuda:
@@ -547,7 +635,7 @@ class E2E(torch.nn.Module):
         enc_h, enc_lens = self.encoder(data, ilens)
         bsz, frames, hid = enc_h.shape
         logits = ops.linear(enc_h.reshape(bsz * frames, hid), self.ctc_lo.weight, self.ctc_lo.bias).view(bsz, frames, -1)
-        return logits, self.encoder.enc2.last_lens_dev, enc_lens
+        return logits, self.encoder.enc2.last_lens_dev, enc_lens, enc_h
 
     def align(self, xs, ilens, ys):
         """CTC forced alignment of the transcripts `ys` (a list of label tensors, as forward takes them) to the utterances
@@ -586,6 +674,57 @@ class E2E(torch.nn.Module):
             host = torch.cat([n.view(-1, 1), ids], dim=1).cpu().tolist()
         self.last_frame_tokens = frame_tok
         return [row[1:1 + row[0]] for row in host]
+
+    @staticmethod
+    def _beam_width(topk):
+        K = int(topk)
+        if not 1 <= K <= hb.BEAM_KMAX:
+            raise ValueError("beam width %d outside 1..%d" % (K, hb.BEAM_KMAX))
+        return K
+
+    def recognize_ctc_beams(self, xs, ilens, topk, nbest=False):
+        """CTC prefix beam search with the CTC head alone (not a reference method): encoder, the head,
+        ops.ctc_beam with beam width topk (1..16) -> (ids, scores): per utterance the best label sequence (an id list) and
+        its log-mass; with nbest=True per utterance the ranked list of all hypotheses the search kept (at most topk) and
+        the list of their scores.  The device results are read once."""
+        K = self._beam_width(topk)
+        with torch.no_grad():
+            logits, lens_dev, _ = self._ctc_logits(xs, ilens, "recognize_ctc_beams")
+            hyp, hyp_len, score = ops.ctc_beam(logits, lens_dev, K)
+            bsz, _, T = hyp.shape
+            host = torch.cat([hyp_len.view(bsz, K, 1).double(), score.view(bsz, K, 1).double(), hyp.double()], dim=2).cpu().tolist()
+        self.last_ctc_beams = (hyp, hyp_len, score)              # (the device tensors of the call)
+        ids = [[[int(v) for v in row[2:2 + int(row[0])]] for row in utt if row[0] >= 0] for utt in host]
+        scores = [[row[1] for row in utt if row[0] >= 0] for utt in host]
+        if nbest:
+            return ids, scores
+        return [u[0] for u in ids], [u[0] for u in scores]
+
+    def recognize_two_pass(self, xs, ilens, topk, ctc_weight=0.5, length_penalty=0.0, nbest=False, *, lm=None, lm_weight=0.0):
+        """Two-pass decoding (not a reference method): the CTC prefix beam search of the head proposes topk
+        (1..16) hypotheses per utterance, ONE teacher-forced pass of the attention decoder over the B topk rows scores them
+        (Decoder.score_hypotheses), and with lm (an LM module) and lm_weight != 0 one teacher-forced pass of the LM too.
+        Hypothesis k of utterance b scores ((1 - w) att + w ctc + lm_weight lm) / (len + 1)**length_penalty with w =
+        ctc_weight in [0, 1]: fp32, every operation rounded on its own, in this order; att and lm are sums of token
+        log-probabilities, <EOS> included, ctc the search's log-mass.  Ranked per utterance, ties to the search's order; a
+        slot the search left unused stays at -inf.
+        -> (prediction [B, L] int64, scores [B]): the best hypothesis, <EOS>-padded to L = T' + 1; with nbest=True all topk,
+        ranked: ([B, topk, L], [B, topk]) - the shapes of recognize_beams.  Device tensors: no host read in here, and none
+        between the passes.  self.last_two_pass keeps the parts (hyp, hyp_len, ctc, att, lm, order)."""
+        K = self._beam_width(topk)
+        w = float(ctc_weight)
+        if not 0.0 <= w <= 1.0:
+            raise ValueError("ctc_weight must lie in [0, 1], got %r" % (ctc_weight,))
+        dec = self.decoder
+        dec.check_lm(lm)
+        with torch.no_grad():
+            logits, lens_dev, enc_lens, enc_h = self._encode_ctc(xs, ilens, "recognize_two_pass")
+            tokens, scores, parts = dec.rescore_ctc_beams(enc_h, enc_lens, logits, lens_dev, K, ctc_weight=w,
+                                                          length_penalty=length_penalty, lm=lm, lm_weight=lm_weight)
+        self.last_two_pass = parts
+        if nbest:
+            return tokens, scores
+        return tokens[:, 0], scores[:, 0]
 
     def mask_and_cal_loss(self, log_probs, ys, mask=None):
         if mask is None:

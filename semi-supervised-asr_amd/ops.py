@@ -1047,6 +1047,21 @@ def ctc_greedy(logits, frame_lens_dev):
     return ids, n, frame_tok
 
 
+def ctc_beam(logits, frame_lens_dev, beam):
+    """-> (hyp int32 [B, beam, T'] padded with -1, hyp_len int32 [B, beam] with -1 in unused slots, score fp32 [B, beam]
+    descending with -inf in unused slots): the CTC prefix beam search of raw logits [B, T', V] (blank = 0), asr_ctc_beam_f32
+    (csrc/ctc_beam.hip), two launches.  Forward only, no host synchronisation."""
+    logits = logits.detach()
+    B, T, V = logits.shape
+    K, dev = int(beam), logits.device
+    ws = torch.empty((hb.ctc_beam_ws_bytes(B, T, V, K) + 3) // 4, device=dev, dtype=torch.float32)
+    hyp = torch.empty(B, K, T, device=dev, dtype=torch.int32)
+    hyp_len = torch.empty(B, K, device=dev, dtype=torch.int32)
+    score = torch.empty(B, K, device=dev, dtype=torch.float32)
+    hb.ctc_beam(logits, frame_lens_dev, K, hyp, hyp_len, score, ws)
+    return hyp, hyp_len, score
+
+
 def decoder_sequence(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo, w_out, b_out, w0, opts):
     opts = dict(opts)
     opts["pooled"] = torch.is_grad_enabled() and (P.requires_grad or w_hh.requires_grad)

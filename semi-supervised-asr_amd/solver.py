@@ -332,6 +332,38 @@ class Solver(object):
             out = self.model.recognize_ctc(xs, ilens)
         return out
 
+    @staticmethod
+    def two_pass_config(config, has_ctc_head):
+        """`two_pass_decode` (not a reference key; default false): test() decodes with E2E.recognize_two_pass -
+        the CTC prefix beam search proposes `beam_size` hypotheses, the attention decoder (and with `lm_weight` > 0 the judge)
+        rescores them in one teacher-forced pass; `ctc_decode_weight` is the CTC score's weight in the combination.  -> the
+        key as a bool; ValueError where it cannot hold: together with `ctc_greedy_decode` (a decoder of its own), or on a model
+        without the CTC head."""
+        on = bool(config.get("two_pass_decode", False))
+        if on and bool(config.get("ctc_greedy_decode", False)):
+            raise ValueError("two_pass_decode and ctc_greedy_decode are two decoders: set one of them")
+        if on and not has_ctc_head:
+            raise ValueError("two_pass_decode needs the CTC head: build the model with ctc_weight > 0")
+        return on
+
+    def _two_pass(self, xs, ilens, beam_size, ctc_weight, lm_weight=0.0, nbest=False):
+        """Two-pass hypothesis ids for one batch (E2E.recognize_two_pass) - with nbest all beam_size of them per utterance,
+        ranked ([B][K][L]); the abort word of the persistent kernels is checked after the decode and the batch repeated on
+        the per-step kernels, as in _greedy."""
+        def run():
+            prediction, _ = self.model.recognize_two_pass(
+                xs, ilens, beam_size, ctc_weight=ctc_weight,
+                length_penalty=float(self.config.get("beam_length_penalty", 0.0)), nbest=nbest,
+                lm=self.judge if lm_weight > 0 else None, lm_weight=lm_weight)
+            return prediction.cpu().numpy().tolist()
+        out = run()
+        if self._abort_seen(xs.device):
+            print("persistent kernels aborted during two-pass decoding (this rank's code %d): repeating the batch on the "
+                  "per-step kernels" % hb.persist_abort_code(xs.device))
+            hb.disable_persistent(xs.device)
+            out = run()
+        return out
+
     def align(self, loader=None):
         """CTC forced alignment of every utterance of `loader` (default: the dev loader) to its transcript with the model's
         CTC head (E2E.align; the model needs `ctc_weight` > 0) -> one record per utterance, in the loader's
@@ -418,6 +450,7 @@ class Solver(object):
                            or float(self.config.get("ctc_decode_weight", 0.0) or 0.0) > 0):
             raise ValueError("ctc_greedy_decode decodes with the CTC head alone: it does not combine with beam_size > 1, "
                              "lm_weight > 0 or ctc_decode_weight > 0")
+        two_pass = self.two_pass_config(self.config, hasattr(self.model, "ctc_lo"))
         if state_dict:
             self.model.load_state_dict(state_dict)
         else:
@@ -448,6 +481,12 @@ class Solver(object):
             xs, ilens, _ = batch
             if ctc_greedy:
                 preds += self._ctc_best_path(xs, ilens)
+            elif two_pass and nbest:
+                ranked = self._two_pass(xs, ilens, beam_size, ctc_w, lm_weight, nbest=True)
+                preds += [hyps[0] for hyps in ranked]
+                beams += ranked
+            elif two_pass:
+                preds += self._two_pass(xs, ilens, beam_size, ctc_w, lm_weight)
             elif nbest:
                 ranked = self._beam(xs, ilens, beam_size, lm_weight, nbest=True, ctc_decode_weight=ctc_w)
                 preds += [hyps[0] for hyps in ranked]
