@@ -2009,7 +2009,8 @@ def rows_unpack_fwd(packed, rows, T, fill, mask, fill_relu=False):
 
 def rows_unpack_bwd(dout, rows, C, mask, want_fill, relu_of=None, dfill=None):
     """-> (drows [R, C], dfill [C] or None).  relu_of: the fill vector in front of its relu (fill_relu of the forward): its
-    gradient is masked by relu_of > 0.  dfill: a zeroed accumulator to use instead of a fresh one."""
+    gradient is masked by relu_of > 0.  dfill: a zeroed accumulator to use instead of a fresh one (the kernel adds to it).
+    UnsupportedShape where the kernels refuse C: not a multiple of 4, or more than 512 float4 with the fill gradient."""
     B, T, _ = dout.shape
     drows = torch.empty(rows.R, C, device=dout.device, dtype=torch.float32)
     if not want_fill:
@@ -2019,9 +2020,11 @@ def rows_unpack_bwd(dout, rows, C, mask, want_fill, relu_of=None, dfill=None):
     seeded = isinstance(mask, SeededMask)
     margs = (None if (mask is None or seeded) else ptr(mask), mask.seed if seeded else 0, mask.p if seeded else 0.0)
     det = DETERMINISTIC[0] and dfill is not None
-    check(load().asr_rows_unpack_bwd_f32(B, T, C, ptr(dout), ptr(rows.lens), ptr(rows.base), ptr(rows.ext), rows.ext_max,
-                                         *margs, ptr(drows), None if det else ptr(dfill), ptr(relu_of), stream()),
-          "asr_rows_unpack_bwd_f32")
+    rc = load().asr_rows_unpack_bwd_f32(B, T, C, ptr(dout), ptr(rows.lens), ptr(rows.base), ptr(rows.ext), rows.ext_max,
+                                        *margs, ptr(drows), None if det else ptr(dfill), ptr(relu_of), stream())
+    if rc == ASR_E_SHAPE:                          # (refused before anything is launched: neither output is written)
+        raise UnsupportedShape("rows_unpack_bwd: C %d (a multiple of 4; at most 2048 with the fill gradient)" % C)
+    check(rc, "asr_rows_unpack_bwd_f32")
     if det:
         ws, nbytes = det_workspace(dout.device, B * C * 4)
         check(load().asr_rows_fill_grad_det_f32(B, T, C, ptr(dout), ptr(rows.lens), *margs, ptr(dfill), ptr(relu_of), ws, nbytes,

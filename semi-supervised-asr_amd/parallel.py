@@ -21,6 +21,7 @@ right after the unlabeled decode and waited for after the labeled forward pass (
 pass); the gradient exchange itself stays the single flat-buffer all-reduce.  Scalars for logging ride in four
 spare floats at the end of that buffer (`FlatBuffers.aux`).
 """
+import ctypes
 import math
 
 import os
@@ -618,7 +619,10 @@ class FlatAdam(object):
         clip = self.max_grad_norm if max_grad_norm is None else max_grad_norm
         g = self.param_groups[0]
         self.t += 1
-        b1, b2 = g["betas"]
+        # the kernel takes the betas as floats and forms 1 - beta from them: the bias corrections are those of the values it
+        # multiplies by (from the decimal beta2 = 0.999, 1 - beta2^t is 1.3e-5 off the kernel's own 1 - float(beta2) at small t,
+        # a step scaled by 1 + 6e-6 - tests/test_stream_kernels_gpu.py)
+        b1, b2 = (ctypes.c_float(b).value for b in g["betas"])
         lib = hb.load()
         n = self.buf.total
         gptr = nxt = None
@@ -632,8 +636,8 @@ class FlatAdam(object):
             gptr = hb.ptr(self.gnorm_sq)
         hb.check(lib.asr_adam_clip_f32(n, hb.ptr(self.buf.flat_p), hb.ptr(self.buf.flat_g), hb.ptr(self.m),
                                        hb.ptr(self.v), hb.ptr(self.vmax), gptr,
-                                       float(clip if clip is not None else 0.0), float(g["lr"]), float(b1),
-                                       float(b2), float(g["eps"]), float(g["weight_decay"]),
+                                       float(clip if clip is not None else 0.0), float(g["lr"]), b1,
+                                       b2, float(g["eps"]), float(g["weight_decay"]),
                                        1.0 - b1 ** self.t, 1.0 - b2 ** self.t,
                                        None if skip_if is None else hb.c_p(skip_if.data_ptr()), nxt, hb.stream()),
                  "asr_adam_clip_f32")
