@@ -811,12 +811,13 @@ template <int DD, int AA, int OO>
 struct DecBwdDims {
   static constexpr int GK = 4 * DD;        // K of the dX product
   static constexpr int GKW = GK / 8;       // per wave
-  static constexpr int GKS = GK / 16;      // per (wave, k-sub): registers per lane
+  static constexpr int GKS = GK / 16;      // W_cat^T registers per lane: 4 column-group passes x GKB
+  static constexpr int GKB = GK / 64;      // per (wave, k block)
   static constexpr int GS = GK + 4;        // padded LDS row of the gathered dgates
   static constexpr int DU = DD / 32, AU = AA / 32, OU = OO / 32;
   static constexpr int AKW = AA / 8, AQ = AA / 32;   // dz product: k's per wave / per (wave, k-sub)
   static constexpr int DS = AA + 4;        // padded LDS row of the gathered dD
-  static_assert(DD % 32 == 0 && AA % 32 == 0 && OO % 32 == 0 && GKS % 4 == 0, "slice sizes");
+  static_assert(DD % 32 == 0 && AA % 32 == 0 && OO % 32 == 0 && GKB % 4 == 0, "slice sizes");
   static_assert(DU <= 16 && AU <= 16 && OU <= 16 && DD <= 512 && OO <= 512 && AA <= 512, "mappings");
 };
 
@@ -843,6 +844,10 @@ __host__ __device__ inline BwdLds bwd_lds_plan(int Tp, int C, int K, int fbV = 0
   l.fs = o; o += RG * C * TpP;
   l.dps = o; o += ((TpP + 16 / RG - 1) / (16 / RG)) * 4 * 64;       // [tiles of 16 / RG frames][4 pairs][64 lanes]
   l.Fs = o; o += C * (l.taps4 + 8);     // rows zero padded by 8: the Toeplitz products read up to 6 taps past the end
+  // (the SWEEP dw path reads further: its 16-byte filter reads start 12 floats before row 0 of Fs - in dPs - and end up to 4
+  // floats behind the last row - in dfh - and its d(features) reads run up to 12 floats past a dfh row, into the next row
+  // or wph.  Every such product has its FILTER operand selected to zero; the other operand only has to be finite, which
+  // it is: all of LDS is zeroed before use and holds finite values from then on.  0 * NaN would reach valid outputs.)
   l.dfh = o; o += C * l.dfs_stride;
   l.wph = o; o += l.dfs_stride;
   l.des = o; o += RG * TPM;
@@ -880,8 +885,9 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_bwd_kernel(DecPersistBwdArg
   constexpr int LT = RG == 4 ? 7 : 8;        // log2(TPM)
   static_assert((1 << LT) == TPM && RG * TPM == DP_NT, "one thread per (row, frame) of the attention weights");
   constexpr int KX = DD + OO + EE;
-  constexpr int GK = BM::GK, GKW = BM::GKW, GKS = BM::GKS, GS = BM::GS, DU = BM::DU, AU = BM::AU, OU = BM::OU;
+  constexpr int GK = BM::GK, GKW = BM::GKW, GKS = BM::GKS, GKB = BM::GKB, GS = BM::GS, DU = BM::DU, AU = BM::AU, OU = BM::OU;
   constexpr int AKW = BM::AKW, AQ = BM::AQ, DS = BM::DS;
+  constexpr bool SWEEP = !FB && RG == 4;      // the rewritten dX and conv-backward products (see the weights below)
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int Tp = a.Tp, C = a.C, K = a.K, B = a.B, L = a.L, nb = a.nb;
   const int TpP = (Tp + 3) & ~3;
@@ -924,20 +930,48 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_bwd_kernel(DecPersistBwdArg
   const int abc = ab_ok ? ab : r0;
 
   // ---------------------------------------------------------------- weights in registers
-  // dX product: block = 2*cg + ks; column group cg < 4: z columns DU*slice + 4cg + i, cg >= 4: ctx columns
-  // D + OU*slice + 4(cg-4) + i; k = wave*GKW + ks*GKS + q
+  // SWEEP: the 4-row instantiations without feedback (cfg-2, cfg-1) run the dX product with one dgates quad against four
+  // column groups and the conv backward on the 16x16x4 MFMA / 16-byte filter reads.  The others keep the earlier form of
+  // both phases: the feedback instantiations sit at the 256-register limit (57 dwords of scratch at D = 512) and the four
+  // accumulators of the swept product put 5 more dwords and 4 more tight loads on their chain; the 2-row instantiations
+  // leave the windows of tests/golden/isa_table.json with it (DESIGN 4.6.5 has the numbers).
   float wx[GKS];
-  {
-    const int blk = lane >> 2, i = lane & 3, cg = blk >> 1, ks = blk & 1;
-    const int cl = 4 * (cg & 3) + i;
-    const bool ok = cg < 4 ? cl < DU : cl < OU;
-    const int col = cg < 4 ? DU * slice + (ok ? cl : 0) : DD + OU * slice + (ok ? cl : 0);
-    const float* wr = a.wcatT + (int64_t)col * GK + wave * GKW + ks * GKS;
+  if constexpr (SWEEP) {
+    // dX product: block = 2*kb + cgl (k block kb < 8, column-group parity cgl); pass p < 4 multiplies column group
+    // cg = 2p + cgl against the SAME dgates fragment.  cg < 4: z columns DU*slice + 4cg + i, cg >= 4: ctx columns
+    // D + OU*slice + 4(cg-4) + i; k = wave*GKW + 4*(kb + 8*q4) + e (the 8 k blocks of a wave read consecutive quads)
+    {
+      const int blk = lane >> 2, i = lane & 3, kb = blk >> 1, cgl = blk & 1;
 #pragma unroll
-    for (int q4 = 0; q4 < GKS / 4; ++q4) {
-      const float4 v = *reinterpret_cast<const float4*>(wr + 4 * q4);
-      wx[4 * q4] = ok ? v.x : 0.f; wx[4 * q4 + 1] = ok ? v.y : 0.f;
-      wx[4 * q4 + 2] = ok ? v.z : 0.f; wx[4 * q4 + 3] = ok ? v.w : 0.f;
+      for (int p = 0; p < 4; ++p) {
+        const int cg = 2 * p + cgl;
+        const int cl = 4 * (cg & 3) + i;
+        const bool ok = cg < 4 ? cl < DU : cl < OU;
+        const int col = cg < 4 ? DU * slice + (ok ? cl : 0) : DD + OU * slice + (ok ? cl : 0);
+        const float* wr = a.wcatT + (int64_t)col * GK + wave * GKW + 4 * kb;
+#pragma unroll
+        for (int q4 = 0; q4 < GKB / 4; ++q4) {
+          const float4 v = *reinterpret_cast<const float4*>(wr + 32 * q4);
+          float* w = wx + p * GKB + 4 * q4;
+          w[0] = ok ? v.x : 0.f; w[1] = ok ? v.y : 0.f; w[2] = ok ? v.z : 0.f; w[3] = ok ? v.w : 0.f;
+        }
+      }
+    }
+  } else {
+    // dX product: block = 2*cg + ks; column group cg < 4: z columns DU*slice + 4cg + i, cg >= 4: ctx columns
+    // D + OU*slice + 4(cg-4) + i; k = wave*GKW + ks*GKS + q
+    {
+      const int blk = lane >> 2, i = lane & 3, cg = blk >> 1, ks = blk & 1;
+      const int cl = 4 * (cg & 3) + i;
+      const bool ok = cg < 4 ? cl < DU : cl < OU;
+      const int col = cg < 4 ? DU * slice + (ok ? cl : 0) : DD + OU * slice + (ok ? cl : 0);
+      const float* wr = a.wcatT + (int64_t)col * GK + wave * GKW + ks * GKS;
+#pragma unroll
+      for (int q4 = 0; q4 < GKS / 4; ++q4) {
+        const float4 v = *reinterpret_cast<const float4*>(wr + 4 * q4);
+        wx[4 * q4] = ok ? v.x : 0.f; wx[4 * q4 + 1] = ok ? v.y : 0.f;
+        wx[4 * q4 + 2] = ok ? v.z : 0.f; wx[4 * q4 + 3] = ok ? v.w : 0.f;
+      }
     }
   }
   // dz product: block = 4*ks + ug; lane 4*blk+i holds unit DU*slice + 4ug + i, k (= attention column) = wave*AKW + ks*AQ + q
@@ -1214,68 +1248,146 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_bwd_kernel(DecPersistBwdArg
     __syncthreads();
     {
       DP_MARK(10);
-      // Both conv-backward contractions are Toeplitz products on the 4x4x1 MFMA with block = channel:
-      //   D[c][i][jj] += A[c][i] * B[c][jj], one instruction per summation index, K range dealt round-robin to waves.
-      // (1) dw path of the next iteration, dwext[t'] = sum_c sum_j F[c][j] df[c][t' - j + K] for t' = t0 + 4i + jj:
-      //     A = dfh[c][t0 + 4i + 2K - j], B = F[c][j + jj]   (substituting j -> j + jj keeps A independent of jj)
-      const int cb = lane_ >> 2, li = lane_ & 3;
+      const int cb = lane_ >> 2, li = lane_ & 3;      // 4x4x1 forms: block = channel
       const bool cok = cb < C;
       const int cc = cok ? cb : 0;
-      {
-        f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f}, accb = (f32x4){0.f, 0.f, 0.f, 0.f};   // alternating partials
-        // The summation index runs from -3: output jj needs the taps j + jj >= 0, i.e. j >= -jj (their operands are d(conv
-        // features) of frames beyond t0 + 4i + K, which are zero only while T' <= K + 1 - the case of every test of
-        // round 1).  js = j + 4 >= 0 is the loop variable; taps with j + jj < 0 are masked.
-        const float* ap = dfh + cc * DFS + 16 * aq + 4 * li + 2 * K + 4;
-        const float* bp = Fs + cc * FSS + li - 4;
-        const int jend = taps + 3 + 4;
-        for (int j = wave; j < jend; j += 32) {      // 4 taps per trip: 8 LDS reads in flight, then 4 MFMAs
-          float av[4], bv[4];
+      if constexpr (SWEEP) {
+        // (1) dw path of the next iteration, dwext[t'] = sum_c sum_j F[c][j] df[c][t' - j + K], a Toeplitz product on the 4x4x1
+        //     MFMA with block = channel and output t' = t0 + i + 4jj:  D[c][i][jj] += A[c][i] * B[c][jj] with, for the
+        //     summation index j, A = dfh[c][t0 + i + 2K - j] and B = F[c][j + 4jj] (the tap of output jj; A does not depend
+        //     on jj).  j runs from -12 (output jj = 3 needs tap 0 at j = -12) in groups of four: B of the group is ONE
+        //     aligned 16-byte read per lane (filter rows are 16-byte aligned), taps outside [0, taps) are masked.
+        {
+          f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f}, accb = (f32x4){0.f, 0.f, 0.f, 0.f};   // alternating partials
+          const float* ap = dfh + cc * DFS + 16 * aq + li + 2 * K + 12;
+          const float* bp = Fs + cc * FSS + 4 * li - 12;
+          const int nr = (taps4 >> 2) + 3;             // groups of 4 summation indices: j = 4 r - 12 + e, dealt round-robin
+          // one group per trip, the operands of the next group (1 + 4 LDS reads) in flight under the 4 MFMAs of this one
+          const int rf = wave < nr ? wave : 0;
+          float4 bn = *reinterpret_cast<const float4*>(bp + 4 * rf);
+          float an[4];
 #pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int jc = j + 8 * u < jend ? j + 8 * u : j;
-            av[u] = ap[-jc];
-            bv[u] = bp[jc];
+          for (int e = 0; e < 4; ++e) an[e] = ap[-(4 * rf + e)];
+          for (int r = wave; r < nr; r += 8) {
+            const float4 bv = bn;
+            float av[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) av[e] = an[e];
+            const int rn = r + 8 < nr ? r + 8 : r;
+            bn = *reinterpret_cast<const float4*>(bp + 4 * rn);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) an[e] = ap[-(4 * rn + e)];
+            const int tp = 4 * r - 12 + 4 * li;      // tap of element 0 of this lane's quad
+            const float b0 = (cok && tp >= 0 && tp < taps) ? bv.x : 0.f;
+            const float b1 = (cok && tp + 1 >= 0 && tp + 1 < taps) ? bv.y : 0.f;
+            const float b2 = (cok && tp + 2 >= 0 && tp + 2 < taps) ? bv.z : 0.f;
+            const float b3 = (cok && tp + 3 >= 0 && tp + 3 < taps) ? bv.w : 0.f;
+            acc = __builtin_amdgcn_mfma_f32_4x4x1f32(av[0], b0, acc, 0, 0, 0);
+            accb = __builtin_amdgcn_mfma_f32_4x4x1f32(av[1], b1, accb, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_4x4x1f32(av[2], b2, acc, 0, 0, 0);
+            accb = __builtin_amdgcn_mfma_f32_4x4x1f32(av[3], b3, accb, 0, 0, 0);
           }
+          float* pp = part + (wave * 64 + lane_) * 5;
 #pragma unroll
-          for (int u = 0; u < 4; u += 2) {
-            const int j0 = j + 8 * u, j1 = j + 8 * (u + 1);
-            acc = __builtin_amdgcn_mfma_f32_4x4x1f32((cok && j0 < jend) ? av[u] : 0.f, j0 - 4 + li >= 0 ? bv[u] : 0.f, acc, 0, 0, 0);
-            accb = __builtin_amdgcn_mfma_f32_4x4x1f32((cok && j1 < jend) ? av[u + 1] : 0.f, j1 - 4 + li >= 0 ? bv[u + 1] : 0.f, accb, 0, 0, 0);
+          for (int i = 0; i < 4; ++i) pp[i] = acc[i] + accb[i];
+        }
+      } else {
+        // Both conv-backward contractions are Toeplitz products on the 4x4x1 MFMA with block = channel:
+        //   D[c][i][jj] += A[c][i] * B[c][jj], one instruction per summation index, K range dealt round-robin to waves.
+        // (1) dw path of the next iteration, dwext[t'] = sum_c sum_j F[c][j] df[c][t' - j + K] for t' = t0 + 4i + jj:
+        //     A = dfh[c][t0 + 4i + 2K - j], B = F[c][j + jj]   (substituting j -> j + jj keeps A independent of jj)
+        {
+          f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f}, accb = (f32x4){0.f, 0.f, 0.f, 0.f};   // alternating partials
+          // The summation index runs from -3: output jj needs the taps j + jj >= 0, i.e. j >= -jj (their operands are d(conv
+          // features) of frames beyond t0 + 4i + K, which are zero only while T' <= K + 1 - the case of every test of
+          // round 1).  js = j + 4 >= 0 is the loop variable; taps with j + jj < 0 are masked.
+          const float* ap = dfh + cc * DFS + 16 * aq + 4 * li + 2 * K + 4;
+          const float* bp = Fs + cc * FSS + li - 4;
+          const int jend = taps + 3 + 4;
+          for (int j = wave; j < jend; j += 32) {      // 4 taps per trip: 8 LDS reads in flight, then 4 MFMAs
+            float av[4], bv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              const int jc = j + 8 * u < jend ? j + 8 * u : j;
+              av[u] = ap[-jc];
+              bv[u] = bp[jc];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u += 2) {
+              const int j0 = j + 8 * u, j1 = j + 8 * (u + 1);
+              acc = __builtin_amdgcn_mfma_f32_4x4x1f32((cok && j0 < jend) ? av[u] : 0.f, j0 - 4 + li >= 0 ? bv[u] : 0.f, acc, 0, 0, 0);
+              accb = __builtin_amdgcn_mfma_f32_4x4x1f32((cok && j1 < jend) ? av[u + 1] : 0.f, j1 - 4 + li >= 0 ? bv[u + 1] : 0.f, accb, 0, 0, 0);
+            }
+          }
+          float* pp = part + (wave * 64 + lane_) * 5;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) pp[i] = acc[i] + accb[i];
+        }
+      }
+      if constexpr (SWEEP) {
+        // (2) dconv[c][j] += sum_u w_{s-1}[u + j - K] df[c][u], a matrix product on the 16x16x4 MFMA: M = the 16 taps of a tile
+        //     (A[m][k] = wph[u0 + k + j0 + m]), N = channel (B[k][c] = dfh[c][K + u0 + k]), four frames u per instruction, the
+        //     groups of four frames dealt round-robin to the waves.  This CU owns the 16-tap tiles aq and aq + PPR of its row;
+        //     accumulators (lane: channel lane & 15, taps j0 + 4 (lane >> 4) + i) live in registers for the whole sequence.
+        {
+          constexpr int NUG = TPM / 32;                // groups per wave
+          constexpr int UCH = 4;                       // groups whose operands are in flight together
+          const int cn = lane_ & 15, kq = lane_ >> 4;
+          const bool cnok = cn < C;
+          const float* bq = dfh + (cnok ? cn : 0) * DFS + K + kq;
+          const float* a0 = wph + 16 * aq + cn + kq;
+          const bool two = 16 * (aq + PPR) < taps;
+#pragma unroll
+          for (int h = 0; h < NUG; h += UCH) {
+            float bv[UCH], a0v[UCH], a1v[UCH];
+#pragma unroll
+            for (int k = 0; k < UCH; ++k) {
+              const int u0 = 4 * (wave + 8 * (h + k));
+              const int uc = u0 < TpP ? u0 : 0;
+              bv[k] = bq[uc];
+              a0v[k] = a0[uc];
+              a1v[k] = a0[uc + 16 * PPR];              // (beyond the last tap: inside the LDS plan, never used)
+            }
+#pragma unroll
+            for (int k = 0; k < UCH; ++k) {
+              if (4 * (wave + 8 * (h + k)) < TpP) {
+                const float b = cnok ? bv[k] : 0.f;
+                acc_cv0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0v[k], b, acc_cv0, 0, 0, 0);
+                acc_cv1 = __builtin_amdgcn_mfma_f32_16x16x4f32(two ? a1v[k] : 0.f, b, acc_cv1, 0, 0, 0);
+              }
+            }
           }
         }
-        float* pp = part + (wave * 64 + lane_) * 5;
+      } else {
+        // (2) dconv[c][j0 + 4i + jj] += sum_u w_{s-1}[u + j0 + 4i - K] df[c][u - jj]: A = wph[u + j0 + 4i], B = dfh[c][K + u - jj];
+        //     this CU owns the 16-tap tiles aq and aq + PPR of its row; accumulators live in registers for the whole sequence
+        {
+          const float* bq = dfh + cc * DFS + K - li;
+          const float* a0 = wph + 16 * aq + 4 * li;
+          const bool two = 16 * (aq + PPR) < taps;
+          const int uend = Tp + 3;
+          for (int u = wave; u < uend; u += 32) {
+            float bv[4], a0v[4], a1v[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) pp[i] = acc[i] + accb[i];
-      }
-      // (2) dconv[c][j0 + 4i + jj] += sum_u w_{s-1}[u + j0 + 4i - K] df[c][u - jj]: A = wph[u + j0 + 4i], B = dfh[c][K + u - jj];
-      //     this CU owns the 16-tap tiles aq and aq + PPR of its row; accumulators live in registers for the whole sequence
-      {
-        const float* bq = dfh + cc * DFS + K - li;
-        const float* a0 = wph + 16 * aq + 4 * li;
-        const bool two = 16 * (aq + PPR) < taps;
-        const int uend = Tp + 3;
-        for (int u = wave; u < uend; u += 32) {
-          float bv[4], a0v[4], a1v[4];
+            for (int k = 0; k < 4; ++k) {
+              const int uc = u + 8 * k < uend ? u + 8 * k : u;
+              bv[k] = bq[uc];
+              a0v[k] = a0[uc];
+              a1v[k] = a0[two ? uc + 16 * PPR : uc];
+            }
 #pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const int uc = u + 8 * k < uend ? u + 8 * k : u;
-            bv[k] = bq[uc];
-            a0v[k] = a0[uc];
-            a1v[k] = a0[two ? uc + 16 * PPR : uc];
-          }
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const float b = (cok && u + 8 * k < uend) ? bv[k] : 0.f;
-            acc_cv0 = __builtin_amdgcn_mfma_f32_4x4x1f32(a0v[k], b, acc_cv0, 0, 0, 0);
-            acc_cv1 = __builtin_amdgcn_mfma_f32_4x4x1f32(two ? a1v[k] : 0.f, b, acc_cv1, 0, 0, 0);
+            for (int k = 0; k < 4; ++k) {
+              const float b = (cok && u + 8 * k < uend) ? bv[k] : 0.f;
+              acc_cv0 = __builtin_amdgcn_mfma_f32_4x4x1f32(a0v[k], b, acc_cv0, 0, 0, 0);
+              acc_cv1 = __builtin_amdgcn_mfma_f32_4x4x1f32(two ? a1v[k] : 0.f, b, acc_cv1, 0, 0, 0);
+            }
           }
         }
       }
       DP_MARK(11);
       __syncthreads();
       if (tid_ < 128) {      // (wave w, output o = 4i + jj): sum over channels
-        const int w2 = tid_ >> 4, o = tid_ & 15, i = o >> 2, jj = o & 3;
+        const int w2 = tid_ >> 4, o = tid_ & 15, i = SWEEP ? o & 3 : o >> 2, jj = SWEEP ? o >> 2 : o & 3;
         float v = 0.f;
         for (int c = 0; c < C; ++c) v += part[(w2 * 64 + 4 * c + jj) * 5 + i];
         dDp[w2 * 16 + o] = v;
@@ -1401,32 +1513,76 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_bwd_kernel(DecPersistBwdArg
     // from here the next poll is ~2 us away and the data is consumed ~4 us later.
     prefetchA(s - 1, zv);
     {
-      f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f}, accb = (f32x4){0.f, 0.f, 0.f, 0.f};   // even / odd k partials
-      DP_MARK(8);
-      const float* gr = dgs + ((lane_ & 3) % RG) * GS + wave * GKW + ((lane_ >> 2) & 1) * GKS;   // rows >= RG alias
+      if constexpr (SWEEP) {
+        // One dgates quad feeds 16 products: the lane's 4 k's against the 4 column groups of its passes.  The 8 k blocks of
+        // the wave are then summed inside the wave, halving the kept passes at each exchange (lanes 32 apart keep passes
+        // {0,1} / {2,3}, lanes 16 apart one of those), so that `part` takes one quad per lane as before.
+        f32x4 acc[4];
 #pragma unroll
-      for (int q4 = 0; q4 < GKS / 4; ++q4) {
-        const float4 b = *reinterpret_cast<const float4*>(gr + 4 * q4);
-        acc = __builtin_amdgcn_mfma_f32_4x4x1f32(wx[4 * q4], b.x, acc, 0, 0, 0);
-        accb = __builtin_amdgcn_mfma_f32_4x4x1f32(wx[4 * q4 + 1], b.y, accb, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_4x4x1f32(wx[4 * q4 + 2], b.z, acc, 0, 0, 0);
-        accb = __builtin_amdgcn_mfma_f32_4x4x1f32(wx[4 * q4 + 3], b.w, accb, 0, 0, 0);
+        for (int p = 0; p < 4; ++p) acc[p] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        DP_MARK(8);
+        const float* gr = dgs + ((lane_ & 3) % RG) * GS + wave * GKW + 4 * (lane_ >> 3);   // rows >= RG alias
+#pragma unroll
+        for (int q4 = 0; q4 < GKB / 4; ++q4) {
+          const float4 b = *reinterpret_cast<const float4*>(gr + 32 * q4);
+#pragma unroll
+          for (int p = 0; p < 4; ++p) {
+            const float* w = wx + p * GKB + 4 * q4;
+            acc[p] = __builtin_amdgcn_mfma_f32_4x4x1f32(w[0], b.x, acc[p], 0, 0, 0);
+            acc[p] = __builtin_amdgcn_mfma_f32_4x4x1f32(w[1], b.y, acc[p], 0, 0, 0);
+            acc[p] = __builtin_amdgcn_mfma_f32_4x4x1f32(w[2], b.z, acc[p], 0, 0, 0);
+            acc[p] = __builtin_amdgcn_mfma_f32_4x4x1f32(w[3], b.w, acc[p], 0, 0, 0);
+          }
+        }
+        const bool h5 = (lane_ & 32) != 0, h4 = (lane_ & 16) != 0;
+        float* pp = part + (wave * 64 + lane_) * 5;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float k0 = (h5 ? acc[2][i] : acc[0][i]) + __shfl_xor(h5 ? acc[0][i] : acc[2][i], 32, 64);
+          const float k1 = (h5 ? acc[3][i] : acc[1][i]) + __shfl_xor(h5 ? acc[1][i] : acc[3][i], 32, 64);
+          float v = (h4 ? k1 : k0) + __shfl_xor(h4 ? k0 : k1, 16, 64);
+          v += __shfl_xor(v, 8, 64);
+          pp[i] = v;
+        }
+      } else {
+        f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f}, accb = (f32x4){0.f, 0.f, 0.f, 0.f};   // even / odd k partials
+        DP_MARK(8);
+        const float* gr = dgs + ((lane_ & 3) % RG) * GS + wave * GKW + ((lane_ >> 2) & 1) * GKS;   // rows >= RG alias
+#pragma unroll
+        for (int q4 = 0; q4 < GKS / 4; ++q4) {
+          const float4 b = *reinterpret_cast<const float4*>(gr + 4 * q4);
+          acc = __builtin_amdgcn_mfma_f32_4x4x1f32(wx[4 * q4], b.x, acc, 0, 0, 0);
+          accb = __builtin_amdgcn_mfma_f32_4x4x1f32(wx[4 * q4 + 1], b.y, accb, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_4x4x1f32(wx[4 * q4 + 2], b.z, acc, 0, 0, 0);
+          accb = __builtin_amdgcn_mfma_f32_4x4x1f32(wx[4 * q4 + 3], b.w, accb, 0, 0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] += accb[i];
+        float* pp = part + (wave * 64 + lane_) * 5;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) pp[i] = acc[i];
       }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[i] += accb[i];
-      float* pp = part + (wave * 64 + lane_) * 5;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) pp[i] = acc[i];
     }
     __syncthreads();
     float vdx = 0.f, vfb = 0.f;               // dX of (column ci = tid >> 2, row = tid & 3), threads tid < 128; FB: + dl W_out
-    if (tid_ < 128) {
-      // (column index ci = tid>>2: 0..15 z, 16..31 ctx; row = tid&3): lanes 4*(2*cg + ks) + row, register ci&3
-      const int ci = tid_ >> 2, row = tid_ & 3, cg = ci >> 2, ii = ci & 3;
+    if constexpr (SWEEP) {
+      if (tid_ < 128) {
+        // (column index ci = tid>>2: 0..15 z, 16..31 ctx; row = tid&3): column group cg = 2p + cgl sits in lane
+        // 32 (p>>1) + 16 (p&1) + 4 cgl + row of every wave, register ci&3
+        const int ci = tid_ >> 2, row = tid_ & 3, cg = ci >> 2, ii = ci & 3;
+        const int pl = 32 * (cg >> 2) + 16 * ((cg >> 1) & 1) + 4 * (cg & 1) + row;
 #pragma unroll
-      for (int w2 = 0; w2 < 8; ++w2)
+        for (int w2 = 0; w2 < 8; ++w2) vdx += part[(w2 * 64 + pl) * 5 + ii];
+      }
+    } else {
+      if (tid_ < 128) {
+        // (column index ci = tid>>2: 0..15 z, 16..31 ctx; row = tid&3): lanes 4*(2*cg + ks) + row, register ci&3
+        const int ci = tid_ >> 2, row = tid_ & 3, cg = ci >> 2, ii = ci & 3;
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) vdx += part[(w2 * 64 + 4 * (2 * cg + ks) + row) * 5 + ii];
+        for (int w2 = 0; w2 < 8; ++w2)
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks) vdx += part[(w2 * 64 + 4 * (2 * cg + ks) + row) * 5 + ii];
+      }
     }
     if (FB) {
       // ---- (g2) d(emb_s) of my 4 embedding columns, my share of d(probabilities)
@@ -1556,21 +1712,23 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_bwd_kernel(DecPersistBwdArg
   }
   if (sc_oke) atomicAdd(a.dgvec_part + (int64_t)r0 * AA + acole, dgl);
   {
-    const int c = lane & 15;
+    // (SWEEP: from the opaque copy of the lane id, so that nothing of the thread id stays live across the loop for this)
+    const int c = SWEEP ? a_le : lane & 15;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int al = 4 * (lane >> 4) + i;
+      const int al = 4 * (SWEEP ? q4e : lane >> 4) + i;
       if (c < C && al < AU) atomicAdd(a.dwatt_part + ((int64_t)r0 * AA + AU * slice + al) * C + c, acc_watt[i]);
     }
   }
   {
-    // lane (channel c = lane>>2, jj = lane&3), register i: tap j0 + 4i + jj of tiles aq (j0 = 16 aq) and aq + 8; every wave
-    // holds a partial sum over its share of the frames
-    const int c = lane_e >> 2, jj = lane_e & 3;
+    // lane (channel c = lane&15, quarter jj = lane>>4), register i: tap j0 + 4jj + i of tiles aq (j0 = 16 aq) and aq + PPR;
+    // every wave holds a partial sum over its share of the frames
+    // (the earlier form: channel lane>>2, jj = lane&3, tap j0 + 4i + jj)
+    const int c = SWEEP ? lane_e & 15 : lane_e >> 2, jj = SWEEP ? lane_e >> 4 : lane_e & 3;
     if (c < C && ab_ok) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const int j0 = 16 * aq + 4 * i + jj, j1 = j0 + 16 * PPR;
+        const int j0 = 16 * aq + (SWEEP ? 4 * jj + i : 4 * i + jj), j1 = j0 + 16 * PPR;
         if (j0 < taps) atomicAdd(a.dconv_part + ((int64_t)ab * C + c) * taps + j0, acc_cv0[i]);
         if (j1 < taps) atomicAdd(a.dconv_part + ((int64_t)ab * C + c) * taps + j1, acc_cv1[i]);
       }
