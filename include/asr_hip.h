@@ -1106,6 +1106,45 @@ int asr_feat_finish_f32(int B, int T, int n_mels, int order, const float* x, int
                         int cmvn_mode, const float* stats, const int32_t* masks, int n_freq_masks, int n_time_masks, float* out,
                         asr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Minimum error rate training on an n-best list (csrc/mwer.hip): the expected number of edit errors under the
+ * model's sequence probabilities renormalised over the K hypotheses of an utterance (Prabhavalkar et al. 2018).  Not a
+ * reference operator.  Two entries added to ABI version 8 WITHOUT a version change, like the beam and edit-distance entries:
+ * additive.  Rows are r = b K + k (utterance b, hypothesis k), R = B K.
+ *   logits   [L][R][V] fp32 RAW logits, time-major, row stride ld >= V floats (what the decoder sequence returns).
+ *   tokens   int64 [L][R]: the hypothesis with its <EOS>, <EOS>-padded.  A value outside [0, V) is read as the nearest
+ *            valid token: no access leaves the row.
+ *   npos     int32 [R]: the scored positions n_r = len_r + 1, clamped to 1 .. L; <= 0 marks an unused slot.
+ *   err      int32 [R]: the edit distance of hypothesis r to its utterance's reference.
+ *   scale    the caller passes 1 / B.
+ *   asr_mwer_fwd_f32
+ *       s_r    = sum_{l < n_r} (logits[l][r][tokens[l][r]] - logsumexp_v logits[l][r][:]), summed in increasing l;
+ *       over the live slots of utterance b, with m_b their maximum of s and Wbar_b their mean of err:
+ *       phat_r = exp(s_r - m_b) / sum_j exp(s_j - m_b)            (the sum in increasing j)
+ *       risk_b = sum_k phat_k (err_k - Wbar_b)                    (in increasing k)
+ *       coef_r = phat_r (err_r - Wbar_b - risk_b)                 (= d risk_b / d s_r)
+ *       loss   = scale sum_b risk_b                               (in increasing b)
+ *       An unused slot gets s = phat = coef = 0; an utterance with no live slot has risk_b = 0.
+ *       Outputs seq_logp [R], post [R] (phat), coef [R], risk [B], loss [1].  ws: L R floats (ASR_E_ARG when ws_bytes is
+ *       smaller) that take the per-position log-probabilities; positions l >= n_r are neither read nor written.  Two launches:
+ *       a wave per (l, r) row, then ONE workgroup - a thread per row for the sum over l, a thread per utterance for the K
+ *       slots, one thread for the B risks.
+ *   asr_mwer_bwd_f32   grad_loss: one device scalar g, the gradient of loss; grad_scale = the forward's scale; coef the
+ *       forward's.  dlogits[l][r][v] = g grad_scale coef_r (1[v = tokens[l][r]] - softmax(logits[l][r][:])_v) for l < n_r,
+ *       row stride lddz >= V; exact zeros for l >= n_r and for unused rows, whose logits are not read (nor are those of a row
+ *       whose coef is 0).  One launch, a wave per (l, r) row.
+ * B, K, L, V <= 0, a NULL pointer, ld or lddz < V: ASR_E_ARG.  K > ASR_BEAM_KMAX, or L B K above 4 INT_MAX: ASR_E_SHAPE.
+ * Both are answered before anything is launched.  No floating-point atomics and no sum across lanes other than the
+ * log-softmax's xor butterfly: functions of their inputs and shapes only - the same bits in every run, in and outside
+ * deterministic mode.  No host synchronisation, no allocation.
+ * ------------------------------------------------------------------------------------- */
+int asr_mwer_fwd_f32(int B, int K, int L, int V, const float* logits, int64_t ld, const int64_t* tokens, const int32_t* npos,
+                     const int32_t* err, float scale, float* seq_logp, float* post, float* coef, float* risk, float* loss,
+                     float* ws, int64_t ws_bytes, asr_stream_t stream);
+int asr_mwer_bwd_f32(int B, int K, int L, int V, const float* logits, int64_t ld, const int64_t* tokens, const int32_t* npos,
+                     const float* coef, const float* grad_loss, float grad_scale, float* dlogits, int64_t lddz,
+                     asr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

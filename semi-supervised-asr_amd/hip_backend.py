@@ -33,6 +33,7 @@ EXPORTS = (
     "asr_ctc_align_ws_bytes", "asr_ctc_align_f32", "asr_ctc_greedy_f32",
     "asr_ctc_beam_ws_bytes", "asr_ctc_beam_f32",
     "asr_fbank_num_frames", "asr_fbank_plan_bytes", "asr_fbank_f32", "asr_feat_cmvn_stats_f32", "asr_feat_finish_f32",
+    "asr_mwer_fwd_f32", "asr_mwer_bwd_f32",
 )
 
 _lib = None
@@ -280,6 +281,8 @@ def load():
     lib.asr_fbank_f32.argtypes = [c_i, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_i64, c_i64, c_p]
     lib.asr_feat_cmvn_stats_f32.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p]
     lib.asr_feat_finish_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p]
+    lib.asr_mwer_fwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
+    lib.asr_mwer_bwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_f, c_p, c_i64, c_p]
     lib.asr_dec_feedback_fwd.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_p, c_i64,
                                          c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
     lib.asr_dec_feedback_bwd.argtypes = [c_i, c_i, c_i, c_i, c_p, c_p, c_i64, c_p, c_p, c_p, c_f, c_p, c_p]
@@ -950,6 +953,43 @@ def ctc_loss_bwd(logits, ld, frame_lens, labels, label_offsets, max_label_len, z
     args = _ctc_args(logits, ld, frame_lens, labels, label_offsets, max_label_len, zero_infinity)
     check(load().asr_ctc_loss_bwd(*args, ptr(grad_nll), ptr(ws), ws.numel() * 4, ptr(dlogits), int(lddz), stream()),
           "asr_ctc_loss_bwd")
+    return dlogits
+
+
+def _mwer_dims(logits, tokens, B):
+    L, R, V = logits.shape
+    if tokens.dtype != torch.long or not tokens.is_cuda or tuple(tokens.shape) != (L, R) or not tokens.is_contiguous():
+        raise RuntimeError("mwer_loss: tokens must be a contiguous int64 [L, R] tensor on the GPU")
+    if logits.stride(2) != 1 or logits.stride(0) != R * logits.stride(1):
+        raise RuntimeError("mwer_loss: logits must be [L, R, V] with unit column stride and one row stride")
+    if B <= 0 or R % B:
+        raise RuntimeError("mwer_loss: %d rows are not K hypotheses for each of %d utterances" % (R, B))
+    return int(B), R // int(B), L, V, int(logits.stride(1))
+
+
+def mwer_fwd(logits, tokens, npos, err, B, scale, seq_logp, post, coef, risk, loss, ws):
+    """asr_mwer_fwd_f32 (csrc/mwer.hip): logits [L, R, V] fp32 time-major (R = B K rows r = b K + k; a row stride wider than V
+    is fine), tokens int64 [L, R], npos / err int32 [R]; outputs seq_logp / post / coef [R], risk [B], loss [1] and the
+    workspace ws (fp32, at least L R elements) are the caller's.  Raises UnsupportedShape for K above BEAM_KMAX."""
+    Bk, K, L, V, ld = _mwer_dims(logits, tokens, B)
+    rc = load().asr_mwer_fwd_f32(Bk, K, L, V, ptr(logits), ld, c_p(tokens.data_ptr()), ptr(npos), ptr(err), float(scale),
+                                 ptr(seq_logp), ptr(post), ptr(coef), ptr(risk), ptr(loss), ptr(ws), ws.numel() * 4, stream())
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("asr_mwer_fwd_f32: B %d, K %d, L %d (K at most %d)" % (Bk, K, L, BEAM_KMAX))
+    check(rc, "asr_mwer_fwd_f32")
+    LAUNCHES["mwer"] += 2
+
+
+def mwer_bwd(logits, tokens, npos, coef, B, grad_loss, grad_scale, dlogits):
+    """asr_mwer_bwd_f32 behind a mwer_fwd on the same inputs: dlogits [L, R, V] contiguous gets grad_loss (one device scalar)
+    grad_scale d(sum_b risk_b) / d logits, exact zeros behind each hypothesis and in unused rows."""
+    Bk, K, L, V, ld = _mwer_dims(logits, tokens, B)
+    rc = load().asr_mwer_bwd_f32(Bk, K, L, V, ptr(logits), ld, c_p(tokens.data_ptr()), ptr(npos), ptr(coef), ptr(grad_loss),
+                                 float(grad_scale), ptr(dlogits), V, stream())
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("asr_mwer_bwd_f32: B %d, K %d, L %d (K at most %d)" % (Bk, K, L, BEAM_KMAX))
+    check(rc, "asr_mwer_bwd_f32")
+    LAUNCHES["mwer"] += 1
     return dlogits
 
 

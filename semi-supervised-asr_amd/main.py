@@ -1,5 +1,5 @@
 """Same CLI as the reference main.py:6-41 (flags -config/-c, --sup_pretrain, --judge_pretrain, --ssl_train,
---load_model, --load_judge, --test); yaml.safe_load because bare yaml.load() raises on PyYAML 6.
+--load_model, --load_judge, --test, and --mwer_train: minimum error rate fine-tuning, not a reference flag); yaml.safe_load because bare yaml.load() raises on PyYAML 6.
 Launch under torch.distributed.run for data parallelism (one process per GPU)."""
 from argparse import ArgumentParser
 
@@ -10,7 +10,8 @@ from solver import Solver
 if __name__ == "__main__":
     parser = ArgumentParser()
     parser.add_argument("-config", "-c", default="config.yaml")
-    for flag in ("--sup_pretrain", "--judge_pretrain", "--ssl_train", "--load_model", "--load_judge", "--test"):
+    for flag in ("--sup_pretrain", "--judge_pretrain", "--ssl_train", "--load_model", "--load_judge", "--test",
+                 "--mwer_train"):
         parser.add_argument(flag, action="store_true")
     args = parser.parse_args()
     with open(args.config, "r") as f:
@@ -24,5 +25,7 @@ if __name__ == "__main__":
         solver.judge_pretrain()
     if args.ssl_train:
         solver.ssl_train()
+    if args.mwer_train:
+        solver.mwer_train()
     if args.test:
         solver.test()

@@ -486,6 +486,52 @@ class Decoder(torch.nn.Module):
             att_score = torch.where(mask, logp.t(), torch.zeros((), device=dev)).sum(dim=1).view(bsz, K)
         return att_score, tok_out, mask
 
+    def score_hypotheses_grad(self, enc_pad, enc_len, hyp_tokens, hyp_len, scores=True):
+        """score_hypotheses with the graph behind it - the scoring pass of MWER training: hyp_tokens int32 or
+        int64 [B, K, T] and hyp_len int32 [B, K] (< 0: an unused slot) on the device -> (att [B, K] or None without `scores`,
+        logits [T + 1, B K, V] time-major with the graph behind them, tok_out_lb int64 [T + 1, B K], npos int32 [B K]: len + 1,
+        0 for an unused slot - the operands of ops.mwer_loss).  The same teacher-forced pass of T + 1 steps over B K rows;
+        what differs: P and Q are formed ONCE over the B utterances and their rows replicated K times by expand + reshape, so
+        the backward is an ordered sum over K and not an index-add; dropout follows the module's mode through xmask; no label
+        smoothing (the sequence probability is the model's own); the attention temperature is the search's (2.0).  No host
+        read."""
+        bsz, K, T = hyp_tokens.shape
+        rows, steps, dev = bsz * K, T + 1, enc_pad.device
+        att = self.attention
+        att.reset()
+        with torch.no_grad():
+            n = hyp_len.reshape(rows, 1).clamp(min=0).long()
+            pos = torch.arange(steps, device=dev).unsqueeze(0)
+            body = torch.cat([hyp_tokens.reshape(rows, T).long(),
+                              torch.full((rows, 1), self.eos, dtype=torch.long, device=dev)], dim=1)
+            tok_out = torch.where(pos < n, body, torch.full_like(body, self.eos))             # [y, <EOS>, <EOS>, ...]
+            tok_in = torch.cat([torch.full((rows, 1), self.bos, dtype=torch.long, device=dev), tok_out[:, :-1]], dim=1)
+            tok_out_lb = tok_out.t().contiguous()
+            live = hyp_len.reshape(rows) >= 0
+            npos = torch.where(live, hyp_len.reshape(rows).clamp(max=T) + 1, torch.zeros_like(hyp_len.reshape(rows))).int()
+        opts = dict(scaling=2.0, smooth=False, smooth_scaling=1.0, sample=False, bos=self.bos, eos=self.eos,
+                    tokens=tok_in.contiguous(), tf_flags=[True] * steps, skip_pred=True, L=steps)
+        p = self.dropout_rate
+        if self.training and p > 0:
+            opts["xmask"] = _mask_tensor(_drop_mask((steps, rows, self.att_odim + self.embedding.embedding_dim), p, dev))
+        P = ops.linear(enc_pad, att.mlp_enc.weight, att.mlp_enc.bias)
+        Q = ops.linear(enc_pad, att.mlp_o.weight, None)
+        frames = enc_pad.shape[1]
+        P = P.unsqueeze(1).expand(bsz, K, frames, P.shape[2]).reshape(rows, frames, P.shape[2])
+        Q = Q.unsqueeze(1).expand(bsz, K, frames, Q.shape[2]).reshape(rows, frames, Q.shape[2])
+        w0 = AttLoc.initial_weights([int(l) for l in enc_len for _ in range(K)], frames, dev)
+        cell = self.LSTMCell
+        logits, _, _ = ops.decoder_sequence(
+            P, Q, self.embedding.weight, cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh,
+            att.mlp_dec.weight, att.loc_conv.weight, att.mlp_att.weight, att.gvec.weight, att.mlp_o.bias,
+            self.output_layer.weight, self.output_layer.bias, w0, opts)
+        att_score = None
+        if scores:
+            logp = ops.label_logprob(logits, tok_out_lb)                                      # [L, B K], time-major
+            mask = (pos <= n).t()
+            att_score = torch.where(mask, logp, torch.zeros((), device=dev)).sum(dim=0).view(bsz, K)
+        return att_score, logits, tok_out_lb, npos
+
     def check_lm(self, lm):
         """ValueError unless lm (an LM module, or None) predicts the decoder's vocabulary with its <BOS> / <EOS>."""
         if lm is None:
@@ -725,6 +771,62 @@ class E2E(torch.nn.Module):
         if nbest:
             return tokens, scores
         return tokens[:, 0], scores[:, 0]
+
+    MWER_EXTRA_STEPS = 5          # the n-best search of an MWER step runs at most this many steps past the longest reference
+
+    def mwer_forward(self, xs, ilens, ys, beam, ce_weight=0.01, max_dec_timesteps=200, hyps=None):
+        """The loss of one minimum-error-rate training step (not a reference method; DESIGN 4.20, Prabhavalkar et al. 2018):
+        L_mwer + ce_weight L_ce with L_mwer = mean_b sum_k phat_k (err_k - mean err) over the `beam` (1..16) hypotheses of the
+        n-best list, phat the model's sequence probabilities renormalised over the list.
+          the encoder runs once, in the module's mode;
+          under no_grad Decoder.recognize_beams(nbest=True) on that output, min(max_dec_timesteps, longest reference +
+            MWER_EXTRA_STEPS) steps - or `hyps` = (tokens int [B, beam, T] <EOS>-padded, lengths int32 [B, beam] or None: up to
+            the first <EOS>; < 0: an unused slot) instead of the search;
+          hb.edit_distance of the B beam hypotheses (cut at <EOS>, nothing filtered) to the B references;
+          Decoder.score_hypotheses_grad and ops.mwer_loss with scale = 1 / B;
+          with ce_weight > 0 the supervised loss of E2E.forward on the same encoder output (teacher-forced, label smoothing
+            and dropout as there, the CTC term when ctc_weight > 0).
+        -> the loss, a device scalar.  self.last_mwer keeps the parts: tokens, hyp_len, err, npos, seq_logp, post, risk, coef,
+        mwer, ce.  Nothing is read on the host."""
+        K = self._beam_width(beam)
+        if xs.is_cuda:
+            hb.upload_side_stream_for(xs.shape[0] * xs.shape[1])
+        enc_h, enc_lens = self.encoder(xs, ilens)
+        dec = self.decoder
+        bsz, dev = enc_h.shape[0], enc_h.device
+        with torch.no_grad():
+            if hyps is None:
+                steps = max(1, min(int(max_dec_timesteps), max(int(y.size(0)) for y in ys) + self.MWER_EXTRA_STEPS))
+                tokens, scores = dec.recognize_beams(enc_h.detach(), enc_lens, steps, K, nbest=True)
+                hyp_len = None
+                unused = scores == float("-inf")                  # a rank the search left without a hypothesis
+            else:
+                tokens, hyp_len = hyps
+                if tuple(tokens.shape[:2]) != (bsz, K):
+                    raise ValueError("hyps: tokens %s are not [%d utterances, %d hypotheses, T]" % (tuple(tokens.shape), bsz, K))
+                unused = None if hyp_len is None else hyp_len < 0
+            T = tokens.shape[2]
+            to_eos = ((tokens == dec.eos).to(torch.int32).cumsum(dim=2) == 0).sum(dim=2).to(torch.int32)     # tokens before <EOS>
+            hyp_len = to_eos if hyp_len is None else torch.minimum(hyp_len.to(torch.int32), to_eos)
+            if unused is not None:
+                hyp_len = torch.where(unused, torch.full_like(hyp_len, -1), hyp_len)
+            ref = dec._label_matrices(ys)[1].to(torch.int32).contiguous()       # [B, longest + 1]: <EOS>-padded, read to ref_len
+            ref_len = hb_to_device([int(y.size(0)) for y in ys], dev)
+            ref_index = (torch.arange(bsz * K, device=dev, dtype=torch.int32) // K).int()
+            err, _, _ = hb.edit_distance(tokens.reshape(bsz * K, T), ref, ref_len, hyp_len=hyp_len.reshape(-1).clamp(min=0),
+                                         ref_index=ref_index, eos=dec.eos)
+        _, logits, tok_out_lb, npos = dec.score_hypotheses_grad(enc_h, enc_lens, tokens, hyp_len, scores=False)
+        mwer, parts = ops.mwer_loss(logits, tok_out_lb, npos, err, 1.0 / bsz, n_utts=bsz)
+        loss, ce = mwer, None
+        if float(ce_weight) > 0:
+            lp = dec(enc_h, enc_lens, ys, loss_norm=bsz)[1]
+            ce = lp.fused_loss                                   # -sum(log-probs) / (B olength): E2E.forward's loss
+            if self.ctc_weight > 0:
+                ce = (1.0 - self.ctc_weight) * ce + self.ctc_weight * (self.ctc_nll(enc_h, ys).sum() * (1.0 / bsz))
+            loss = mwer + float(ce_weight) * ce
+        self.last_mwer = dict(parts, tokens=tokens, hyp_len=hyp_len, err=err, npos=npos, mwer=mwer.detach(),
+                              ce=None if ce is None else ce.detach())
+        return loss
 
     def mask_and_cal_loss(self, log_probs, ys, mask=None):
         if mask is None:

@@ -995,6 +995,46 @@ def ctc_loss(logits, frame_lens_dev, labels_packed, label_lens, zero_infinity=Tr
     return _CtcLoss.apply(logits, frame_lens_dev, labels_packed, label_lens, zero_infinity)
 
 
+class _MwerLoss(torch.autograd.Function):
+    """The expected number of edit errors over the n-best list (csrc/mwer.hip): logits [L, R, V] RAW, time-major, R = B K rows
+    -> (loss, seq_logp [R], post [R], risk [B], coef [R]); only `loss` carries a gradient.  Two launches forward, one
+    backward; the backward recomputes the rows' softmax from the saved logits and reads the saved coef.  Ordered sums only:
+    nothing here depends on hb.is_deterministic().  No host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, logits, tokens_lb, npos, err, B, scale):
+        L, R, V = logits.shape
+        if not (logits.stride(2) == 1 and logits.stride(1) >= V and logits.stride(0) == R * logits.stride(1)):
+            logits = logits.contiguous()
+        dev = logits.device
+        tokens_lb, npos, err = tokens_lb.contiguous(), npos.contiguous(), err.contiguous()
+        out = torch.empty(3 * R + int(B) + 1, device=dev, dtype=torch.float32)
+        seq_logp, post, coef, risk, loss = out[:R], out[R:2 * R], out[2 * R:3 * R], out[3 * R:3 * R + B], out[3 * R + B:]
+        ws = torch.empty(L * R, device=dev, dtype=torch.float32)
+        hb.mwer_fwd(logits, tokens_lb, npos, err, B, scale, seq_logp, post, coef, risk, loss, ws)
+        ctx.save_for_backward(logits, tokens_lb, npos, coef)
+        ctx.B, ctx.scale = int(B), float(scale)
+        ctx.mark_non_differentiable(seq_logp, post, risk, coef)
+        return loss.view(()), seq_logp, post, risk, coef
+
+    @staticmethod
+    def backward(ctx, g, *_unused):
+        logits, tokens_lb, npos, coef = ctx.saved_tensors
+        dz = torch.empty(logits.shape, device=logits.device, dtype=torch.float32)
+        hb.mwer_bwd(logits, tokens_lb, npos, coef, ctx.B, g.contiguous(), ctx.scale, dz)
+        return dz, None, None, None, None, None
+
+
+def mwer_loss(logits, tokens_lb, npos, err, scale, n_utts=None):
+    """-> (loss, parts): loss = scale * sum_b risk_b, a device scalar with the graph behind it; parts = dict(seq_logp [R],
+    post [R], risk [B], coef [R]) without one.  logits [L, R, V] fp32 raw, time-major (ops.decoder_sequence's), rows
+    r = b K + k; tokens_lb int64 [L, R] (each hypothesis with its <EOS>, <EOS>-padded); npos int32 [R] (len + 1; <= 0: an
+    unused slot); err int32 [R] (edit distances); scale: the caller's 1 / B.  n_utts: B (default round(1 / scale))."""
+    B = int(n_utts) if n_utts is not None else int(round(1.0 / float(scale)))
+    loss, seq_logp, post, risk, coef = _MwerLoss.apply(logits, tokens_lb, npos, err, B, float(scale))
+    return loss, dict(seq_logp=seq_logp, post=post, risk=risk, coef=coef)
+
+
 class CtcAlignment(object):
     """What ops.ctc_align returns, every field a device tensor: path int32 [B, T'] (the token of each encoder frame, 0 =
     blank, -1 behind the utterance and in every frame of an infeasible one), score fp32 [B] (the best alignment's

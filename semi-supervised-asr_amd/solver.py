@@ -838,6 +838,86 @@ class Solver(object):
             self.save_model(f"{path}-{epoch:03d}")
         return best_model, best_cer
 
+    # ------------------------------------------------------------------ minimum error rate training
+    @staticmethod
+    def mwer_config(config, world=1):
+        """The MWER keys of the configuration -> (K, ce_weight, epochs), or None when `mwer_beam` is absent (off).  ValueError
+        for a beam outside 2..16, a negative weight, no epochs, or more than one process."""
+        if config.get("mwer_beam") is None:
+            return None
+        K = int(config["mwer_beam"])
+        if not 2 <= K <= hb.BEAM_KMAX:
+            raise ValueError("mwer_beam %d outside 2..%d" % (K, hb.BEAM_KMAX))
+        ce_weight, epochs = float(config.get("mwer_ce_weight", 0.01)), int(config.get("mwer_epochs", 1))
+        if ce_weight < 0 or epochs < 1:
+            raise ValueError("mwer_ce_weight %g must be >= 0 and mwer_epochs %d >= 1" % (ce_weight, epochs))
+        if int(world) > 1:
+            raise ValueError("MWER training runs in one process: data-parallel MWER (world size %d) is not supported" % world)
+        return K, ce_weight, epochs
+
+    def mwer_train_one_iteration(self, xs, ilens, ys, hyps=None):
+        """One minimum-error-rate step on a batch already on the device: E2E.mwer_forward (encoder, n-best
+        search under no_grad - or the given `hyps` -, edit distances, scoring pass, risk loss, + mwer_ce_weight times the
+        supervised loss), backward, the fused clip + Adam.  -> (loss, mean risk) as StepScalars; nothing is read on the host
+        inside the step."""
+        mw = self.mwer_config(self.config, self.world)
+        if mw is None:
+            raise ValueError("mwer_train_one_iteration needs `mwer_beam` in the configuration")
+        K, ce_weight, _ = mw
+        xs, ilens, ys, _ = parallel.shard_batch(xs, ilens, ys, 0, 1)      # (a LocalShard of a one-process feed passes through)
+
+        def make_local():
+            loss = self.model.mwer_forward(xs, ilens, ys, K, ce_weight=ce_weight,
+                                           max_dec_timesteps=self.config["max_dec_timesteps"], hyps=hyps)
+            return loss, [loss, self.model.last_mwer["mwer"]]
+        loss, risk = self._step(make_local, self.gen_opt, 2)
+        return loss, risk
+
+    def mwer_train(self):
+        """`mwer_epochs` epochs of MWER steps over the labeled set, the dev CER after each as sup_pretrain reports it;
+        checkpoints by sup_pretrain's rule (the best CER under model_name, every epoch under model_name-mwer-NNN)."""
+        cfg = self.config
+        mw = self.mwer_config(cfg, self.world)
+        if mw is None:
+            raise ValueError("mwer_train needs `mwer_beam` in the configuration")
+        K, ce_weight, epochs = mw
+        self.model.train()
+        best_cer, best_model = 200, None
+        path = os.path.join(cfg["model_dir"], cfg["model_name"])
+        steps_per_epoch = len(self.train_lab_loader)
+        print("------minimum error rate training (%d-best, ce weight %g)-------" % (K, ce_weight))
+        for epoch in range(epochs):
+            running = [0.0, 0.0]
+
+            def log(item):
+                it, (loss, risk) = item
+                running[0] += float(loss)
+                running[1] += float(risk)
+                if self.rank == 0:
+                    print(f"epoch: {epoch}, [{it + 1}/{steps_per_epoch}], loss: {loss:.3f}, risk: {risk:.3f}", end="\r")
+                self.logger.scalar_summary(tag=f"{cfg['tag']}/mwer/train_loss", value=float(loss),
+                                           step=epoch * steps_per_epoch + it + 1)
+            push, done = self._lagged(log)
+            for it, (xs, ilens, ys) in enumerate(self._feed(self.train_lab_loader, train=True)):
+                push((it, self.mwer_train_one_iteration(xs, ilens, ys)))
+            done()
+            train_loss, train_risk = running[0] / steps_per_epoch, running[1] / steps_per_epoch
+            val_loss, cer, hyps, refs = self.validation()
+            print(f"Epoch: {epoch}, train_loss={train_loss:.4f}, train_risk={train_risk:.4f}, "
+                  f"valid_loss={val_loss:.4f}, CER={cer:.4f}")
+            tag = cfg["tag"]
+            self.logger.scalar_summary(f"{tag}/mwer/cer", cer, epoch)
+            self.logger.scalar_summary(f"{tag}/mwer/val_loss", val_loss, epoch)
+            self.logger.scalar_summary(f"{tag}/mwer/avg_train_loss", train_loss, epoch)
+            self.logger.scalar_summary(f"{tag}/mwer/avg_train_risk", train_risk, epoch)
+            if cer < best_cer:
+                best_cer = cer
+                self.save_model(path)
+                best_model = self.model.state_dict()
+                print(f"Save #{epoch} model, val_loss={val_loss:.3f}, CER={cer:.3f}")
+            self.save_model(f"{path}-mwer-{epoch:03d}")
+        return best_model, best_cer
+
     # ------------------------------------------------------------------ semi-supervised training
     def gen_train_one_iteration(self, lab_xs, lab_ilens, lab_ys, unlab_xs, unlab_ilens):
         """The LM-judge auxiliary loss (solver.py:460-495): greedy smooth-embedding decode of unlabeled
