@@ -14,8 +14,7 @@
 // And once at the end
 //   beam_backtrack  one workgroup per utterance: rank the finished hypotheses, follow the backpointers into token rows.
 #include <float.h>
-#include <limits.h>
-#include "common.h"
+#include "seq_common.h"
 
 namespace {
 
@@ -23,17 +22,6 @@ constexpr int BEAM_NT = 256;               // threads of the select / reorder / 
 constexpr int BEAM_WAVES = BEAM_NT / 64;
 constexpr int BEAM_KMAX = ASR_BEAM_KMAX;
 constexpr int BEAM_FCAP = ASR_BEAM_FCAP;   // finished entries per utterance (< 2K can be held: include/asr_hip.h)
-
-// candidate order: higher score first, lower flat index on ties
-__device__ __forceinline__ bool beam_better(float av, int ai, float bv, int bi) {
-  return av > bv || (av == bv && ai < bi);
-}
-
-__device__ __forceinline__ float beam_wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
 
 // M: the per-thread candidate list length, a power of two >= 2K.  LM: candidates are score + logp + lmw * logp_lm (each
 // operation rounded on its own, in this order); without it lm_logits / lmw are not read and the code is the plain select's.
@@ -69,33 +57,21 @@ __global__ __launch_bounds__(BEAM_NT) void beam_select_kernel(asr_beam_t p, int 
   const float* lg = p.logits + (int64_t)b * K * V;
   for (int k = wave; k < K; k += BEAM_WAVES) {
     if (s_score[k] == -INFINITY) continue;                 // wave-uniform
-    const float* row = lg + (int64_t)k * V;
-    float m = -INFINITY;
-    for (int v = lane; v < V; v += 64) m = fmaxf(m, row[v]);
-    m = beam_wave_max(m);
-    float s = 0.f;
-    for (int v = lane; v < V; v += 64) s += expf(row[v] - m);
-    s = wave_sum(s);
+    float m, s;
+    wave_row_max_sumexp(lg + (int64_t)k * V, V, lane, m, s);
     if (lane == 0) { s_max[k] = m; s_lsum[k] = logf(s); }
     if (LM) {
-      const float* lrow = lm_logits + ((int64_t)b * K + k) * V;
-      float lm = -INFINITY;
-      for (int v = lane; v < V; v += 64) lm = fmaxf(lm, lrow[v]);
-      lm = beam_wave_max(lm);
-      float lsum = 0.f;
-      for (int v = lane; v < V; v += 64) lsum += expf(lrow[v] - lm);
-      lsum = wave_sum(lsum);
-      if (lane == 0) { s_lmmax[k] = lm; s_lmlsum[k] = logf(lsum); }
+      wave_row_max_sumexp(lm_logits + ((int64_t)b * K + k) * V, V, lane, m, s);
+      if (lane == 0) { s_lmmax[k] = m; s_lmlsum[k] = logf(s); }
     }
   }
   __syncthreads();
 
-  // every thread keeps its best M candidates, sorted, in registers (fully unrolled: no scratch); it visits flat indices
-  // in increasing order, so an equal score never displaces an entry
+  // every thread keeps its best M candidates (score desc, flat index k*V+v asc on ties), visiting flat indices in
+  // increasing order
   float lv[M];
   int li[M];
-#pragma unroll
-  for (int j = 0; j < M; ++j) { lv[j] = -INFINITY; li[j] = INT_MAX; }
+  top_clear(lv, li);
   for (int k = 0; k < K; ++k) {
     const float sc = s_score[k];
     if (sc == -INFINITY) continue;
@@ -116,19 +92,7 @@ __global__ __launch_bounds__(BEAM_NT) void beam_select_kernel(asr_beam_t p, int 
         c = __fadd_rn(c, __fmul_rn(cw, __fsub_rn(prow[v], pprev)));
       }
       if (LM) c = __fadd_rn(c, __fmul_rn(lmw, (lrow[v] - lmm) - lml));   // no fused multiply-add: the order is the contract
-      if (c > lv[M - 1]) {                                 // -inf and NaN never enter
-        int ci = k * V + v;
-#pragma unroll
-        for (int j = 0; j < M; ++j) {
-          const bool sw = beam_better(c, ci, lv[j], li[j]);
-          const float tv = lv[j];
-          const int ti = li[j];
-          lv[j] = sw ? c : tv;
-          li[j] = sw ? ci : ti;
-          c = sw ? tv : c;
-          ci = sw ? ti : ci;
-        }
-      }
+      top_insert(lv, li, c, k * V + v);
     }
   }
 
@@ -136,29 +100,11 @@ __global__ __launch_bounds__(BEAM_NT) void beam_select_kernel(asr_beam_t p, int 
   const int want = 2 * K;
   int ntop = 0;
   for (int r = 0; r < want; ++r) {
-    float v = lv[0];
-    int i = li[0];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ov = __shfl_xor(v, off, 64);
-      const int oi = __shfl_xor(i, off, 64);
-      if (beam_better(ov, oi, v, i)) { v = ov; i = oi; }
-    }
-    const int buf = r & 1;                                  // double-buffered: one barrier per round
-    if (lane == 0) { red_v[buf][wave] = v; red_i[buf][wave] = i; }
-    __syncthreads();
-    v = red_v[buf][0];
-    i = red_i[buf][0];
-#pragma unroll
-    for (int w = 1; w < BEAM_WAVES; ++w)
-      if (beam_better(red_v[buf][w], red_i[buf][w], v, i)) { v = red_v[buf][w]; i = red_i[buf][w]; }
+    float v;
+    int i;
+    top_round(lv[0], li[0], red_v[r & 1], red_i[r & 1], BEAM_WAVES, v, i);
     if (v == -INFINITY) break;                              // fewer than 2K finite candidates (uniform)
-    if (li[0] == i) {
-#pragma unroll
-      for (int j = 0; j < M - 1; ++j) { lv[j] = lv[j + 1]; li[j] = li[j + 1]; }
-      lv[M - 1] = -INFINITY;
-      li[M - 1] = INT_MAX;
-    }
+    top_pop_if_head(lv, li, i);
     if (tid == 0) { top_v[r] = v; top_i[r] = i; }
     ntop = r + 1;
   }

@@ -1,8 +1,6 @@
 // ctc.hip — CTC loss on the encoder output (the CTC branch of joint CTC-attention training), forward and backward.
-// Blank = index 0.  Per utterance the extended label sequence l' = (0, l_1, 0, l_2, ..., l_L, 0) has S = 2L + 1 states;
-// alpha / beta are kept in log space.  Four kernels, no floating-point atomics, every sum in an order fixed by the shapes:
-//   ctc_lse_kernel    one wave per valid frame (b, t < len_b): lse[b][t] = logsumexp_v logits[b][t][v] - the log-softmax
-//                     lives in that one number per frame; no [B, T', V] log-prob tensor exists
+// The conventions (blank, extended labels, x = z - lse, ordered sums) are seq_common.h's; alpha / beta are kept in log space.
+// Behind seq_common.h's frame_lse_kernel (the log-softmax lives in that one number per frame) three kernels:
 //   ctc_alpha_kernel  one workgroup per utterance (one wave when max S <= 64): the label-sorted position list of the
 //                     utterance (once), then alpha over the frames - states across threads (strided when S exceeds the
 //                     workgroup), frames in sequence, the hand-off between frames through two rows of LDS with one barrier
@@ -10,12 +8,10 @@
 //   ctc_beta_kernel   the same chain backwards; writes alpha_t(s) + beta_t(s) over alpha_t(s)
 //   ctc_grad_kernel   one wave per frame: the blank's states are summed by the whole wave, every other vocabulary entry by
 //                     the lane that owns it, walking its run of the sorted position list in ascending order
-#include "common.h"
+#include "seq_common.h"
 
 namespace {
 
-constexpr int kMaxL = ASR_CTC_MAX_LABELS;
-constexpr int kMaxS = 2 * kMaxL + 1;
 constexpr int kHeadShift = 12;                 // head entry = (first index in the sorted list << 12) | run length; 0: absent
 static_assert(kMaxL < (1 << kHeadShift), "the run length must fit the low bits of a head entry");
 
@@ -27,8 +23,6 @@ struct CtcWs {
   int* head;       // [B][V]
   int64_t bytes;
 };
-
-inline int64_t round64(int64_t n) { return (n + 63) / 64 * 64; }
 
 CtcWs ctc_ws(void* base, int B, int T, int V, int Lmax) {
   const int64_t Sp = 2 * (int64_t)Lmax + 1, Lo = Lmax > 0 ? Lmax : 1;
@@ -51,39 +45,6 @@ __device__ __forceinline__ float lse3(float a, float b, float c) {
   return m + logf(expf(a - m) + expf(b - m) + expf(c - m));
 }
 
-__global__ __launch_bounds__(256) void ctc_lse_kernel(int B, int T, int V, const float* __restrict__ z, int64_t ld,
-                                                      const int32_t* __restrict__ lens, float* __restrict__ lse) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= (int64_t)B * T) return;
-  const int b = (int)(row / T), t = (int)(row % T);
-  if (t >= lens[b]) return;                                 // frames behind the utterance are never read
-  const float* zr = z + row * ld;
-  float mx = -INFINITY;
-  for (int v = lane; v < V; v += 64) mx = fmaxf(mx, zr[v]);
-  mx = wave_max(mx);
-  float se = 0.f;
-  for (int v = lane; v < V; v += 64) se += expf(zr[v] - mx);
-  se = wave_sum(se);
-  if (lane == 0) lse[row] = mx + logf(se);
-}
-
-// The labels of utterance b into LDS.  -> false (for every thread) when the utterance cannot be scored: a label outside
-// [1, V) or more labels than the workspace was sized for.
-__device__ __forceinline__ bool ctc_load_labels(const int64_t* __restrict__ labels, int o0, int L, int Lmax, int V, int* lab,
-                                                int* bad) {
-  if (threadIdx.x == 0) *bad = (L < 0 || L > Lmax) ? 1 : 0;
-  __syncthreads();
-  if (*bad) return false;
-  for (int i = threadIdx.x; i < L; i += blockDim.x) {
-    const int64_t v = labels[o0 + i];
-    if (v < 1 || v >= V) atomicOr(bad, 1);
-    lab[i] = (v < 1 || v >= V) ? 1 : (int)v;
-  }
-  __syncthreads();
-  return *bad == 0;
-}
-
 template <int NS>
 __global__ __launch_bounds__(256) void ctc_alpha_kernel(int T, int V, const float* __restrict__ z, int64_t ld,
                                                         const int32_t* __restrict__ lens,
@@ -96,8 +57,7 @@ __global__ __launch_bounds__(256) void ctc_alpha_kernel(int T, int V, const floa
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   const int o0 = offs[b], L = offs[b + 1] - o0, S = 2 * L + 1;
   const int Sp = 2 * Lmax + 1, Lo = Lmax > 0 ? Lmax : 1;
-  int len = lens[b];
-  len = len < 0 ? 0 : (len > T ? T : len);
+  const int len = clamp_len(lens[b], T);
   for (int k = tid; k < V; k += nt) w.head[(int64_t)b * V + k] = 0;
   for (int i = tid; i < 2 * (kMaxS + 5); i += nt) (&buf[0][0])[i] = -INFINITY;
   const bool ok = ctc_load_labels(labels, o0, L, Lmax, V, lab, &bad);      // (its barriers order the fills above)
@@ -198,8 +158,7 @@ __global__ __launch_bounds__(256) void ctc_beta_kernel(int T, int V, const float
   if (!(w.raw[b] < INFINITY)) return;          // infeasible: the gradient kernel does not read alpha + beta
   const int o0 = offs[b], L = offs[b + 1] - o0, S = 2 * L + 1;
   const int Sp = 2 * Lmax + 1;
-  int len = lens[b];
-  len = len < 0 ? 0 : (len > T ? T : len);
+  const int len = clamp_len(lens[b], T);
   for (int i = tid; i < 2 * (kMaxS + 5); i += nt) (&buf[0][0])[i] = -INFINITY;
   if (!ctc_load_labels(labels, o0, L, Lmax, V, lab, &bad) || len == 0) return;
   const float* zb = z + (int64_t)b * T * ld;
@@ -331,8 +290,9 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(int B, int T, int V, cons
 }
 
 int ctc_check(int B, int T, int V, int64_t ld, int Lmax, const void* ws, int64_t ws_bytes) {
-  if (B <= 0 || T <= 0 || V <= 0 || Lmax < 0 || ld < V || !ws) return ASR_E_ARG;
-  if (V < 2 || Lmax > kMaxL || ((int64_t)B * T + 3) / 4 > 0x7fffffffLL) return ASR_E_SHAPE;
+  const int rc = ctc_shape_check(B, T, V, Lmax);
+  if (rc == ASR_E_ARG || ld < V || !ws) return ASR_E_ARG;
+  if (rc) return rc;
   if (ws_bytes < ctc_ws(nullptr, B, T, V, Lmax).bytes) return ASR_E_ARG;
   return 0;
 }
@@ -353,16 +313,10 @@ extern "C" int asr_ctc_loss_fwd(int B, int T, int V, const float* logits, int64_
   const int rc = ctc_check(B, T, V, ld, max_label_len, ws, ws_bytes);
   if (rc) return rc;
   const CtcWs w = ctc_ws(ws, B, T, V, max_label_len);
-  const unsigned rows4 = (unsigned)(((int64_t)B * T + 3) / 4);
-  hipLaunchKernelGGL(ctc_lse_kernel, dim3(rows4), dim3(256), 0, (hipStream_t)stream, B, T, V, logits, ld, frame_lens, w.lse);
+  launch_frame_lse(B, T, V, logits, ld, frame_lens, w.lse, (hipStream_t)stream);
   ASR_CHECK_LAUNCH();
-  const int Sp = 2 * max_label_len + 1;
-  if (Sp <= 256)
-    hipLaunchKernelGGL(ctc_alpha_kernel<1>, dim3(B), dim3(Sp <= 64 ? 64 : 256), 0, (hipStream_t)stream, T, V, logits, ld,
-                       frame_lens, labels, label_offsets, max_label_len, zero_infinity, nll, w);
-  else
-    hipLaunchKernelGGL(ctc_alpha_kernel<8>, dim3(B), dim3(256), 0, (hipStream_t)stream, T, V, logits, ld, frame_lens,
-                       labels, label_offsets, max_label_len, zero_infinity, nll, w);
+  launch_by_states(2 * max_label_len + 1, ctc_alpha_kernel<1>, ctc_alpha_kernel<8>, B, (hipStream_t)stream, T, V, logits, ld,
+                   frame_lens, labels, label_offsets, max_label_len, zero_infinity, nll, w);
   ASR_CHECK_LAUNCH();
   return 0;
 }
@@ -375,13 +329,8 @@ extern "C" int asr_ctc_loss_bwd(int B, int T, int V, const float* logits, int64_
   const int rc = ctc_check(B, T, V, ld, max_label_len, ws, ws_bytes);
   if (rc) return rc;
   const CtcWs w = ctc_ws(ws, B, T, V, max_label_len);
-  const int Sp = 2 * max_label_len + 1;
-  if (Sp <= 256)
-    hipLaunchKernelGGL(ctc_beta_kernel<1>, dim3(B), dim3(Sp <= 64 ? 64 : 256), 0, (hipStream_t)stream, T, V, logits, ld,
-                       frame_lens, labels, label_offsets, max_label_len, w);
-  else
-    hipLaunchKernelGGL(ctc_beta_kernel<8>, dim3(B), dim3(256), 0, (hipStream_t)stream, T, V, logits, ld, frame_lens, labels,
-                       label_offsets, max_label_len, w);
+  launch_by_states(2 * max_label_len + 1, ctc_beta_kernel<1>, ctc_beta_kernel<8>, B, (hipStream_t)stream, T, V, logits, ld,
+                   frame_lens, labels, label_offsets, max_label_len, w);
   ASR_CHECK_LAUNCH();
   const unsigned rows4 = (unsigned)(((int64_t)B * T + 3) / 4);
   hipLaunchKernelGGL(ctc_grad_kernel, dim3(rows4), dim3(256), 0, (hipStream_t)stream, B, T, V, logits, ld, frame_lens,

@@ -1,7 +1,5 @@
 // ctc_align.hip — the Viterbi (max-product) companions of ctc.hip on the CTC head's logits: forced alignment of a transcript
-// and best-path (greedy) decoding.  Blank = index 0; the conventions are ctc.hip's: extended labels l' = (0, l_1, 0, ...,
-// l_L, 0) with S = 2L + 1 states, x[t][v] = logits[t][v] - lse[t], frames behind an utterance never read.
-//   ctc_align_lse_kernel  one wave per valid frame: lse[b][t] = logsumexp_v logits[b][t][v] (ctc_lse_kernel's pass)
+// and best-path (greedy) decoding.  The conventions are seq_common.h's; its frame_lse_kernel runs first.
 //   ctc_align_kernel      one workgroup per utterance (one wave when max S <= 64, states strided over 256 threads above 256
 //                         states).  Four phases in one launch:
 //                           chain      v over the frames with max in place of logsumexp - adds and compares only; two rows of
@@ -18,13 +16,10 @@
 //   ctc_greedy_kernel     one workgroup per utterance: a wave takes a frame's argmax over the raw logits (NaN never wins,
 //                         ties to the lowest index); then one wave compacts the kept frames (non-blank, not a repeat of the
 //                         frame before) in frame order by ballot and popcount
-// No floating-point atomics, every sum in an order fixed by the shapes: the same bits in every run.
-#include "common.h"
+#include "seq_common.h"
 
 namespace {
 
-constexpr int kMaxL = ASR_CTC_MAX_LABELS;
-constexpr int kMaxS = 2 * kMaxL + 1;
 constexpr int kBpLdsBytes = ASR_CTC_ALIGN_LDS_BYTES;      // the back-pointers of an utterance stay in LDS up to this size
 constexpr int kBpLdsWords = kBpLdsBytes / 8;
 static_assert(kBpLdsBytes % 16 == 0, "a (frame, 64 states) entry is a pair of 64-bit words");
@@ -39,8 +34,6 @@ struct AlignWs {
   int64_t bytes;
 };
 
-inline int64_t round64(int64_t n) { return (n + 63) / 64 * 64; }
-
 AlignWs align_ws(void* base, int B, int T, int Lmax) {
   const int64_t nwp = (2 * (int64_t)Lmax + 1 + 63) / 64;
   const int64_t n_bt = round64((int64_t)B * T);
@@ -51,23 +44,6 @@ AlignWs align_ws(void* base, int B, int T, int Lmax) {
   w.state = (int*)(w.lse + n_bt);
   w.bytes = 8 * n_bp + 4 * 2 * n_bt;
   return w;
-}
-
-__global__ __launch_bounds__(256) void ctc_align_lse_kernel(int B, int T, int V, const float* __restrict__ z, int64_t ld,
-                                                            const int32_t* __restrict__ lens, float* __restrict__ lse) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= (int64_t)B * T) return;
-  const int b = (int)(row / T), t = (int)(row % T);
-  if (t >= lens[b]) return;                                 // frames behind the utterance are never read
-  const float* zr = z + row * ld;
-  float mx = -INFINITY;
-  for (int v = lane; v < V; v += 64) mx = fmaxf(mx, zr[v]);
-  mx = wave_max(mx);
-  float se = 0.f;
-  for (int v = lane; v < V; v += 64) se += expf(zr[v] - mx);
-  se = wave_sum(se);
-  if (lane == 0) lse[row] = mx + logf(se);
 }
 
 template <int NS>
@@ -85,11 +61,11 @@ __global__ __launch_bounds__(256) void ctc_align_kernel(int T, int V, const floa
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int o0 = offs[b], L = offs[b + 1] - o0, S = 2 * L + 1;
-  int len = lens[b];
-  len = len < 0 ? 0 : (len > T ? T : len);
+  const int len = clamp_len(lens[b], T);
   int32_t* pathb = path + (int64_t)b * T;
   for (int i = tid; i < 2 * (kMaxS + 5); i += nt) (&buf[0][0])[i] = -INFINITY;
   // the labels into LDS; a label outside [1, V) or more labels than the launch was sized for: no alignment
+  // (seq_common.h's ctc_load_labels with both barriers always taken: this kernel's code keeps that shape)
   if (tid == 0) bad = (L < 0 || L > Lmax) ? 1 : 0;
   __syncthreads();
   if (!bad) {
@@ -229,8 +205,7 @@ __global__ __launch_bounds__(256) void ctc_greedy_kernel(int T, int V, const flo
   __shared__ int kept_total;
   const int b = blockIdx.x, tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
-  int len = lens[b];
-  len = len < 0 ? 0 : (len > T ? T : len);
+  const int len = clamp_len(lens[b], T);
   const float* zb = z + (int64_t)b * T * ld;
   int32_t* ft = frame_tok + (int64_t)b * T;
   int32_t* idb = ids + (int64_t)b * T;
@@ -281,17 +256,11 @@ __global__ __launch_bounds__(256) void ctc_greedy_kernel(int T, int V, const flo
   for (int t = kept_total + tid; t < T; t += 256) idb[t] = -1;
 }
 
-int align_check(int B, int T, int V, int Lmax) {
-  if (B <= 0 || T <= 0 || V <= 0 || Lmax < 0) return ASR_E_ARG;
-  if (V < 2 || Lmax > kMaxL || ((int64_t)B * T + 3) / 4 > 0x7fffffffLL) return ASR_E_SHAPE;
-  return 0;
-}
-
 }  // namespace
 
 extern "C" int asr_ctc_align_ws_bytes(int B, int T, int V, int max_label_len, int64_t* ws_bytes) {
   if (!ws_bytes) return ASR_E_ARG;
-  const int rc = align_check(B, T, V, max_label_len);
+  const int rc = ctc_shape_check(B, T, V, max_label_len);
   if (rc) return rc;
   *ws_bytes = align_ws(nullptr, B, T, max_label_len).bytes;
   return 0;
@@ -303,22 +272,15 @@ extern "C" int asr_ctc_align_f32(int B, int T, int V, const float* logits, int64
                                  asr_stream_t stream) {
   if (!logits || !frame_lens || !label_offsets || !path || !score || !ws || ld < V) return ASR_E_ARG;
   if (max_label_len > 0 && (!labels || !first || !last || !token_logp)) return ASR_E_ARG;
-  const int rc = align_check(B, T, V, max_label_len);
+  const int rc = ctc_shape_check(B, T, V, max_label_len);
   if (rc) return rc;
   if ((((uintptr_t)ws) & 7u) != 0) return ASR_E_ALIGN;
   const AlignWs w = align_ws(ws, B, T, max_label_len);
   if (ws_bytes < w.bytes) return ASR_E_ARG;
-  const unsigned rows4 = (unsigned)(((int64_t)B * T + 3) / 4);
-  hipLaunchKernelGGL(ctc_align_lse_kernel, dim3(rows4), dim3(256), 0, (hipStream_t)stream, B, T, V, logits, ld, frame_lens,
-                     w.lse);
+  launch_frame_lse(B, T, V, logits, ld, frame_lens, w.lse, (hipStream_t)stream);
   ASR_CHECK_LAUNCH();
-  const int Sp = 2 * max_label_len + 1;
-  if (Sp <= 256)
-    hipLaunchKernelGGL(ctc_align_kernel<1>, dim3(B), dim3(Sp <= 64 ? 64 : 256), 0, (hipStream_t)stream, T, V, logits, ld,
-                       frame_lens, labels, label_offsets, max_label_len, path, score, first, last, token_logp, w);
-  else
-    hipLaunchKernelGGL(ctc_align_kernel<8>, dim3(B), dim3(256), 0, (hipStream_t)stream, T, V, logits, ld, frame_lens, labels,
-                       label_offsets, max_label_len, path, score, first, last, token_logp, w);
+  launch_by_states(2 * max_label_len + 1, ctc_align_kernel<1>, ctc_align_kernel<8>, B, (hipStream_t)stream, T, V, logits, ld,
+                   frame_lens, labels, label_offsets, max_label_len, path, score, first, last, token_logp, w);
   ASR_CHECK_LAUNCH();
   return 0;
 }

@@ -1,7 +1,5 @@
 // ctc_beam.hip — CTC prefix beam search over the CTC head's logits: the n-best list of the head itself, the
-// first pass of two-pass decoding.  Blank = index 0; the conventions are ctc.hip's and ctc_align.hip's: x[t][v] = logits[t][v]
-// - lse[t], frames behind an utterance never read.
-//   ctc_beam_lse_kernel   one wave per valid frame: lse[b][t] = logsumexp_v logits[b][t][v] (ctc_align_lse_kernel's pass)
+// first pass of two-pass decoding.  The conventions are seq_common.h's; its frame_lse_kernel runs first.
 //   ctc_beam_kernel       one workgroup per utterance (one wave when K V <= kOneWaveKV, four beyond), looping over its frames.
 //                         The beam (at most K prefixes: pb, pnb, tot, last token, length, 64-bit prefix hash) lives in LDS, two
 //                         slots.  Per frame:
@@ -10,18 +8,16 @@
 //                           candidates thread j < live forms the stay candidate of entry j (flat index j), the masses of the
 //                                      extensions that ARE entry j added to its pnb' in ascending entry order; all threads walk
 //                                      the extensions (entry-major, tokens strided over the threads: ascending flat index
-//                                      K + k (V - 1) + (c - 1)) and keep their best M >= K in a sorted register list
-//                           select     K rounds of a workgroup arg-best over the list heads (greater tot', lower flat index on
-//                                      ties; -inf never wins); the thread whose number is the round keeps the winner
+//                                      K + k (V - 1) + (c - 1)) and keep their best M >= K in a sorted register list (top_insert)
+//                           select     K rounds of a workgroup arg-best over the list heads (seq_common.h's order; -inf
+//                                      never wins); the thread whose number is the round keeps the winner
 //                           update     thread r < selected writes entry r of the other slot and (parent slot, token) of the
 //                                      frame into the history - LDS when T_b K entries fit kHistLds, the workspace otherwise
 //                         The emissions of the frame ahead are in registers (kStage tokens per thread) while a frame runs and go
 //                         to LDS at its end; a token behind kStage * threads is read from memory where it is used.
 //                         After the last frame the beam IS the ranking (the select's order); thread r walks the history back
 //                         into hyp[r].
-// No floating-point atomics, every sum in an order fixed by the shapes: the same bits in every run.
-#include <limits.h>
-#include "common.h"
+#include "seq_common.h"
 
 namespace {
 
@@ -41,8 +37,6 @@ struct BeamWs {
   int64_t bytes;
 };
 
-inline int64_t round64(int64_t n) { return (n + 63) / 64 * 64; }
-
 BeamWs beam_ws(void* base, int B, int T, int K) {
   const int64_t n_h = (int64_t)T * K > kHistLds ? (int64_t)B * T * K : 0;
   BeamWs w;
@@ -52,24 +46,8 @@ BeamWs beam_ws(void* base, int B, int T, int K) {
   return w;
 }
 
-__global__ __launch_bounds__(256) void ctc_beam_lse_kernel(int B, int T, int V, const float* __restrict__ z, int64_t ld,
-                                                           const int32_t* __restrict__ lens, float* __restrict__ lse) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= (int64_t)B * T) return;
-  const int b = (int)(row / T), t = (int)(row % T);
-  if (t >= lens[b]) return;                                 // frames behind the utterance are never read
-  const float* zr = z + row * ld;
-  float mx = -INFINITY;
-  for (int v = lane; v < V; v += 64) mx = fmaxf(mx, zr[v]);
-  mx = wave_max(mx);
-  float se = 0.f;
-  for (int v = lane; v < V; v += 64) se += expf(zr[v] - mx);
-  se = wave_sum(se);
-  if (lane == 0) lse[row] = mx + logf(se);
-}
-
 // log(exp a + exp b); (-inf) (+) (-inf) = -inf, and -inf (+) x = x exactly
+// (not ctc_prefix.hip's lae: log1pf here, logf(1 + .) there - they round differently, and each search's bits are its own)
 __device__ __forceinline__ float logaddexp(float a, float b) {
   const float m = fmaxf(a, b), n = fminf(a, b);
   if (n == -INFINITY) return m;
@@ -83,24 +61,6 @@ __device__ __forceinline__ u64 prefix_hash(u64 h, int c) {
   h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
   h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
   return h ^ (h >> 31);
-}
-
-// candidate order: greater tot' first, lower flat index on ties
-__device__ __forceinline__ bool cand_better(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
-
-template <int M>
-__device__ __forceinline__ void cand_insert(float (&lv)[M], int (&li)[M], float c, int ci) {
-  if (!(c > lv[M - 1])) return;                              // -inf and NaN never enter; indices come in ascending order
-#pragma unroll
-  for (int j = 0; j < M; ++j) {
-    const bool sw = cand_better(c, ci, lv[j], li[j]);
-    const float tv = lv[j];
-    const int ti = li[j];
-    lv[j] = sw ? c : tv;
-    li[j] = sw ? ci : ti;
-    c = sw ? tv : c;
-    ci = sw ? ti : ci;
-  }
 }
 
 template <int M>
@@ -119,8 +79,7 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
   __shared__ int2 s_hist[kHistLds];
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   const int lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
-  int len = lens[b];
-  len = len < 0 ? 0 : (len > T ? T : len);
+  const int len = clamp_len(lens[b], T);
   int32_t* hypb = hyp + (int64_t)b * K * T;
   if (len == 0) {                                            // no frames: the empty hypothesis at score 0
     for (int64_t i = tid; i < (int64_t)K * T; i += nt) hypb[i] = -1;
@@ -194,7 +153,7 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
           npnb = logaddexp(npnb, (s_last[p][i] == cj ? s_pb[p][i] : s_tot[p][i]) + xj);
       s_spb[tid] = npb;
       s_spnb[tid] = npnb;
-      cand_insert<M>(lv, li, logaddexp(npb, npnb), tid);
+      top_insert(lv, li, logaddexp(npb, npnb), tid);
     }
     // the extensions, entry-major
     for (int k = 0; k < nlive; ++k) {
@@ -208,10 +167,12 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
         float val = (c == ck ? pbk : totk) + xc;
         for (unsigned m = mkk; m; m &= m - 1)                // prefix_k . c is in the beam: not a candidate of its own
           if (s_last[p][__ffs(m) - 1] == c) val = -INFINITY;
-        cand_insert<M>(lv, li, val, base + c);
+        top_insert(lv, li, val, base + c);
       }
     }
-    // select: K rounds of a workgroup arg-best over the list heads; the owner of the winner pops its head
+    // select: K rounds of the workgroup arg-best over the list heads; the owner of the winner pops its head.  The list's clear
+    // above, the round and the pop are seq_common.h's top_clear / top_round / top_pop_if_head spelled out: this loop runs K
+    // times per frame on the serial chain, and through the helpers the compiler gives it another shape
     int nsel = 0, my_i = INT_MAX;
     float my_v = -INFINITY;
     for (int r = 0; r < K; ++r) {
@@ -221,7 +182,7 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
       for (int off = 32; off > 0; off >>= 1) {
         const float ov = __shfl_xor(v, off, 64);
         const int oi = __shfl_xor(i, off, 64);
-        if (cand_better(ov, oi, v, i)) {
+        if (better(ov, oi, v, i)) {
           v = ov;
           i = oi;
         }
@@ -236,7 +197,7 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
         v = red_v[buf][0];
         i = red_i[buf][0];
         for (int ww = 1; ww < nw; ++ww)
-          if (cand_better(red_v[buf][ww], red_i[buf][ww], v, i)) {
+          if (better(red_v[buf][ww], red_i[buf][ww], v, i)) {
             v = red_v[buf][ww];
             i = red_i[buf][ww];
           }
@@ -319,7 +280,8 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
 
 int beam_check(int B, int T, int V, int K) {
   if (B <= 0 || T <= 0 || V <= 0) return ASR_E_ARG;
-  if (V < 2 || K < 1 || K > kKmax || (int64_t)K * V > INT_MAX / 2 || ((int64_t)B * T + 3) / 4 > 0x7fffffffLL) return ASR_E_SHAPE;
+  if (V < 2 || K < 1 || K > kKmax || (int64_t)K * V > INT_MAX / 2 || ((int64_t)B * T + kLseWaves - 1) / kLseWaves > 0x7fffffffLL)
+    return ASR_E_SHAPE;
   return 0;
 }
 
@@ -340,9 +302,7 @@ extern "C" int asr_ctc_beam_f32(int B, int T, int V, int K, const float* logits,
   if (rc) return rc;
   if ((((uintptr_t)ws) & 7u) != 0) return ASR_E_ALIGN;
   const BeamWs w = beam_ws(ws, B, T, K);
-  const unsigned rows4 = (unsigned)(((int64_t)B * T + 3) / 4);
-  hipLaunchKernelGGL(ctc_beam_lse_kernel, dim3(rows4), dim3(256), 0, (hipStream_t)stream, B, T, V, logits, ld, frame_lens,
-                     w.lse);
+  launch_frame_lse(B, T, V, logits, ld, frame_lens, w.lse, (hipStream_t)stream);
   ASR_CHECK_LAUNCH();
   const dim3 grid(B), block((int64_t)K * V <= kOneWaveKV ? 64 : kMaxThreads);
 #define CTC_BEAM(M_) \

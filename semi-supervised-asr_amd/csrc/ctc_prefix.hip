@@ -1,6 +1,6 @@
 // ctc_prefix.hip — the CTC prefix score of joint CTC-attention beam search (Watanabe et al. 2017) on the
-// device.  Blank = <PAD> = index 0 by convention (the caller names it).  With x[t][v] = logits[b][t][v] - lse[b][t] over the
-// T_b valid frames of utterance b, every beam row carries r_n[t], r_b[t] - the log-probability of its prefix g ending at
+// device.  Blank = <PAD> = index 0 by convention (the caller names it); x[t][v] = logits[b][t][v] - lse[b][t] and the valid
+// frames of utterance b are seq_common.h's.  Every beam row carries r_n[t], r_b[t] - the log-probability of its prefix g ending at
 // frame t in a non-blank / a blank - as (r_n, r_b) pairs [row][t][2] in two slots, its last token (-1: g is empty) and
 // psi_prev = psi(g).  Three kernels, no atomics, every sum in an order fixed by the shapes:
 //   ctc_prefix_init_kernel     one workgroup per utterance, once per search: lse[b][t] (a wave per frame), then wave 0 scans
@@ -15,11 +15,12 @@
 //                              x[t][blank] and the predecessor's phi[t-1] (the next round's loads are issued before this
 //                              round's chain runs), then the n / b chain walks the 64 frames through readlane
 #include <float.h>
-#include "common.h"
+#include "seq_common.h"
 
 namespace {
 
 // log(exp(a) + exp(b)); (-inf, -inf) -> -inf, never NaN for arguments below +inf
+// (not ctc_beam.hip's logaddexp: logf(1 + .) here, log1pf there - they round differently, and each search's bits are its own)
 __device__ __forceinline__ float lae(float a, float b) {
   const float m = fmaxf(a, b);
   if (m == -INFINITY) return -INFINITY;
@@ -30,21 +31,14 @@ __device__ __forceinline__ float lane_read(float v, int j) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), j));
 }
 
-__device__ __forceinline__ int clamp_len(int len, int Tp) { return len < 0 ? 0 : (len > Tp ? Tp : len); }
-
 __global__ __launch_bounds__(256) void ctc_prefix_init_kernel(asr_ctc_prefix_t c) {
   const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int len = clamp_len(c.frame_lens[b], c.Tp), V = c.V, K = c.K;
   const float* zb = c.logits + (int64_t)b * c.Tp * c.ld;
   float* lse = c.lse + (int64_t)b * c.Tp;
   for (int t = wave; t < len; t += 4) {                        // frames behind the utterance are never read
-    const float* zr = zb + (int64_t)t * c.ld;
-    float mx = -INFINITY;
-    for (int v = lane; v < V; v += 64) mx = fmaxf(mx, zr[v]);
-    mx = wave_max(mx);
-    float se = 0.f;
-    for (int v = lane; v < V; v += 64) se += expf(zr[v] - mx);
-    se = wave_sum(se);
+    float mx, se;
+    wave_row_max_sumexp(zb + (int64_t)t * c.ld, V, lane, mx, se);
     if (lane == 0) lse[t] = mx + logf(se);
   }
   __syncthreads();

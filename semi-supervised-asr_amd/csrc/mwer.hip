@@ -13,22 +13,21 @@
 //   dlogits[l][r][v] = g scale coef_r (1[v = tokens[l][r]] - softmax(logits[l][r][:])_v)  for l < n_r;  exact zeros for
 //                      l >= n_r and for unused rows, whose logits are not read (nor are those of a row with coef_r = 0)
 // Three kernels, no floating-point atomics, every sum in an order fixed by the shapes:
-//   mwer_logp_kernel    one wave per (l, r) with l < n_r: the log-softmax of the row (lane-strided, then the xor butterfly)
+//   mwer_logp_kernel    one wave per (l, r) with l < n_r: the log-softmax of the row (seq_common.h's row pass)
 //                       and the gather -> lp[l][r] in the workspace; positions behind n_r are neither read nor written
 //   mwer_risk_kernel    ONE workgroup: a thread per row sums lp over l (rows strided over the threads: the loads of a step
 //                       are coalesced and independent, only the adds chain), a thread per utterance then walks its K <= 16
 //                       slots three times (maximum and error mean; normaliser; risk) and writes phat, coef and risk, and
 //                       thread 0 adds the B risks.  Nothing is reduced across threads, so no order depends on scheduling.
 //   mwer_grad_kernel    one wave per (l, r): the row's softmax again (V is small) and the scaled difference, or zeros
-#include "common.h"
+#include "seq_common.h"
 
 namespace {
 
 constexpr int kMaxK = ASR_BEAM_KMAX;
 
 __device__ __forceinline__ int mwer_npos(const int32_t* __restrict__ npos, int r, int L) {
-  const int n = npos[r];
-  return n <= 0 ? 0 : (n > L ? L : n);
+  return clamp_len(npos[r], L);
 }
 
 // a token outside [0, V) is read as the nearest valid one: no access leaves the row
@@ -46,12 +45,8 @@ __global__ __launch_bounds__(256) void mwer_logp_kernel(int R, int L, int V, con
   const int l = (int)(row / R), r = (int)(row % R);
   if (l >= mwer_npos(npos, r, L)) return;
   const float* zr = z + row * ld;
-  float mx = -INFINITY;
-  for (int v = lane; v < V; v += 64) mx = fmaxf(mx, zr[v]);
-  mx = wave_max(mx);
-  float se = 0.f;
-  for (int v = lane; v < V; v += 64) se += expf(zr[v] - mx);
-  se = wave_sum(se);
+  float mx, se;
+  wave_row_max_sumexp(zr, V, lane, mx, se);
   if (lane == 0) lp[row] = zr[mwer_token(tokens, row, V)] - (mx + logf(se));
 }
 
@@ -130,12 +125,8 @@ __global__ __launch_bounds__(256) void mwer_grad_kernel(int R, int L, int V, con
     return;
   }
   const float* zr = z + row * ld;
-  float mx = -INFINITY;
-  for (int v = lane; v < V; v += 64) mx = fmaxf(mx, zr[v]);
-  mx = wave_max(mx);
-  float se = 0.f;
-  for (int v = lane; v < V; v += 64) se += expf(zr[v] - mx);
-  se = wave_sum(se);
+  float mx, se;
+  wave_row_max_sumexp(zr, V, lane, mx, se);
   const float inv = 1.0f / se, gr = g[0] * gscale * c;
   const int tok = mwer_token(tokens, row, V);
   for (int v = lane; v < V; v += 64) dzr[v] = gr * ((v == tok ? 1.f : 0.f) - expf(zr[v] - mx) * inv);
