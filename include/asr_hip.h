@@ -1145,6 +1145,46 @@ int asr_mwer_bwd_f32(int B, int K, int L, int V, const float* logits, int64_t ld
                      const float* coef, const float* grad_loss, float grad_scale, float* dlogits, int64_t lddz,
                      asr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Speed perturbation (csrc/resample.hip): a polyphase resampler over packed waveforms, in front of
+ * asr_fbank_f32.  Not a reference operator.  Two entries added to ABI version 8 WITHOUT a version change, like the front
+ * end's: additive.
+ * A speed factor s at sample rate sr is the rational orig / new = round(s sr) / sr in lowest terms (0.9 -> 9 / 10); the
+ * result is read at sr again, so tempo and pitch change together (sox `speed`).  With lpw = 6, rolloff = 0.99:
+ *   base = min(orig, new) rolloff, width = ceil(lpw orig / base), taps = 2 width + orig,
+ *   t = clip(((k - width) / orig - j / new) base, -lpw, lpw),  h[j][k] = sinc(pi t) cos^2(pi t / (2 lpw)) base / orig,
+ *   out[i new + j] = sum_k h[j][k] x[i orig + k - width] (k ascending, one fp32 running sum, fmaf), x zero outside [0, n),
+ *   ceil(new n / orig) output samples for n input samples.
+ * geometry: HOST int32 [n_factors][5] = (orig, new, width, taps, table offset in floats); tables: DEVICE fp32, factor f's
+ * bank h[new][taps] at its offset, filled by the CALLER (float64 arithmetic, rounded to fp32 once).
+ *   asr_resample_plan_bytes  no GPU: 4 * max_f (offset_f + new_f taps_f), the bytes the tables need.
+ *   asr_resample_f32    samples: ONE packed buffer of in_count int16 (ASR_SAMPLES_I16) or fp32 (ASR_SAMPLES_F32) elements,
+ *                       utterance b = samples[in_offsets[b] .. in_offsets[b + 1]) filtered with factor factor_index[b]
+ *                       (int32 [B], clamped into the plan) into out[out_offsets[b] ..): ONE packed fp32 buffer of out_count
+ *                       elements.  All three index arrays are on the device.  A row's length is ceil(new n / orig), clamped to
+ *                       out_offsets[b + 1] - out_offsets[b]; what the host leaves between rows is not touched.  Offsets are
+ *                       clamped into the two buffers: nothing at or behind in_offsets[B] is read, nothing at or behind
+ *                       out_offsets[B] written, a neighbour in the packed buffer is not an utterance's padding.  A factor with
+ *                       orig == new == 1 copies by value (int16 -> fp32 exactly, fp32 bit for bit).  max_out: the longest
+ *                       row's output length (an upper bound will do: it sizes the grid).  One launch, grid (ceil(max_out /
+ *                       ASR_RESAMPLE_TILE), B): a workgroup stages its tile's input span and the factor's bank in LDS once.
+ * n_factors > ASR_RESAMPLE_MAX_FACTORS, new > ASR_RESAMPLE_MAX_PHASES, taps > ASR_RESAMPLE_MAX_TAPS, a tile span
+ * ((ASR_RESAMPLE_TILE - 1) / new + 1) orig + taps above ASR_RESAMPLE_MAX_SPAN (speed factors above 2), B > 65535, a
+ * sample_dtype that is neither of the two: ASR_E_SHAPE.  taps != 2 width + orig, tables smaller than the geometry addresses,
+ * a NULL pointer: ASR_E_ARG.  Both before anything is launched.  No atomics, no host synchronisation, no allocation; a
+ * function of its inputs only - the same bits in every run, in and outside deterministic mode.
+ * ------------------------------------------------------------------------------------- */
+#define ASR_RESAMPLE_TILE 1024
+#define ASR_RESAMPLE_MAX_FACTORS 8
+#define ASR_RESAMPLE_MAX_PHASES 32
+#define ASR_RESAMPLE_MAX_TAPS 64
+#define ASR_RESAMPLE_MAX_SPAN 2176
+int asr_resample_plan_bytes(int n_factors, const int32_t* geometry, int64_t* bytes);
+int asr_resample_f32(int B, int64_t max_out, const void* samples, int sample_dtype, int64_t in_count,
+                     const int64_t* in_offsets, const int32_t* factor_index, const int64_t* out_offsets, int n_factors,
+                     const int32_t* geometry, const void* tables, int64_t table_bytes, float* out, int64_t out_count,
+                     asr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,12 @@ With a front end (`frontend=`, frontend.Frontend) an utterance's `feature` is a 
 packs this rank's samples into the pinned slot (longest first), uploads them on the side stream and runs the front end's
 kernels there; the yielded `Batch` is the one a feed of precomputed features yields.  SpecAugment masks are drawn like the
 noise - one generator per global row - and only in training feeds (`train=True`).
+
+With `speed_perturb` in the front end's config a training feed also draws a speed factor per utterance (`plan_speed_batch`:
+every rank draws the factors of ALL rows of the global batch, in collated order), sorts the batch by PERTURBED sample count,
+takes `ilens`, `T_max` and the masks' `T_b` from the perturbed counts and uploads its own rows' raw samples with their factor
+indices and output offsets; the resampler runs on the side stream in front of the fbank.  Validation, test and align feeds
+never perturb.
 """
 import queue
 import threading
@@ -110,6 +116,18 @@ def _return_slots(slots):
         _SLOT_POOL[slots[0].pin].extend(slots)
 
 
+def plan_speed_batch(frontend, speed_seed, batch_index, sample_counts):
+    """Host arithmetic of a speed-perturbed batch.  sample_counts: the raw sample counts of ALL rows of the global batch in
+    collated order -> (order, factor_index, perturbed): `order` sorts the rows by perturbed sample count descending (stable),
+    and factor_index / perturbed are the draws (frontend.draw_speed on the COLLATED row, so the draw does not depend on the
+    sort) and the perturbed counts IN THAT SORTED ORDER.  Every rank computes the same three lists and takes its strided
+    rows of them, so the union of the rank-local batches is the one-process batch."""
+    draws = [frontend.draw_speed(speed_seed, batch_index, i) for i in range(len(sample_counts))]
+    counts = [frontend.perturbed_samples(n, f) for n, f in zip(sample_counts, draws)]
+    order = sorted(range(len(counts)), key=lambda i: -counts[i])
+    return order, [draws[i] for i in order], [counts[i] for i in order]
+
+
 class DeviceFeed(object):
     """Iterate `source` (batches of raw utterances: lists of (feature [T, D] float32, token_ids), in the collated order -
     dataloader.get_data_loader(raw=True), or any iterable of such lists) and yield `Batch`es on `device`, prepared `depth`
@@ -120,7 +138,8 @@ class DeviceFeed(object):
       noise_std   > 0: add N(0, noise_std) noise to the features (a generator per global row, see the module docstring)
       thread      collate + upload in a background thread (default) or inline in next()
       frontend    a frontend.Frontend: features are 1-D waveforms and the front end runs on the side stream (GPU only)
-      train       with a front end that has SpecAugment masks: draw them (training feeds only)
+      train       with a front end that has SpecAugment masks: draw them; with one that has `speed_perturb`: draw a speed
+                  factor per utterance and resample (training feeds only)
     """
 
     def __init__(self, source, device, kind="labeled", rank=0, world=1, depth=2, noise_std=0.0, thread=True, frontend=None,
@@ -134,6 +153,8 @@ class DeviceFeed(object):
                 raise ValueError("DeviceFeed: the host-side input noise needs precomputed features (noise_std with a front end)")
             # the mask seed: from the process's numpy stream, here, like the noise seed below
             self.mask_seed = int(np.random.randint(0, 2 ** 31 - 1)) if train and frontend.n_masks > 0 else None
+            # the speed seed: after the mask seed, and only with the feature on - the streams of every other feed stay put
+            self.speed_seed = int(np.random.randint(0, 2 ** 31 - 1)) if train and frontend.n_speeds > 0 else None
         self.source, self.kind, self.rank, self.world = source, kind, int(rank), int(world)
         self.device = torch.device(device)
         self.cuda = self.device.type == "cuda"
@@ -221,11 +242,19 @@ class DeviceFeed(object):
         if slot.event is not None:
             slot.event.synchronize()
             slot.event = None
-        items = sorted(items, key=lambda item: -int(item[0].shape[0]))       # sample count descending (stable)
+        speed = self.speed_seed is not None
+        if speed:
+            # perturbed sample count descending (stable); n_all stays the RAW count of a row, p_all is what the fbank sees
+            order, f_all, p_all = plan_speed_batch(fe, self.speed_seed, self._n - 1, [int(f.shape[0]) for f, _ in items])
+            items = [items[i] for i in order]
+        else:
+            items = sorted(items, key=lambda item: -int(item[0].shape[0]))   # sample count descending (stable)
         rows = parallel.shard_indices(len(items), self.rank, self.world)
         sharded = self.world > 1
         n_all = [int(f.shape[0]) for f, _ in items]
-        lens_all = [fe.num_frames(n) for n in n_all]
+        if not speed:
+            p_all = n_all
+        lens_all = [fe.num_frames(n) for n in p_all]
         t_max = max(lens_all)
         if t_max < 1:
             raise ValueError("DeviceFeed: no utterance of the batch has a whole frame")
@@ -239,14 +268,19 @@ class DeviceFeed(object):
         for i in rows:
             wav_n[offs[-1]:offs[-1] + n_all[i]] = items[i][0]
             offs.append(offs[-1] + n_all[i])
-        # one int64 area: offsets [B + 1] | frame counts int32 [B] (padded to a whole word) | masks int32 [B, nm, 2]
+        # one int64 area: offsets [B + 1] | frame counts int32 [B] (padded to a whole word) | masks int32 [B, nm, 2]; with
+        # speed perturbation behind them: output offsets [B + 1] | factor indices int32 [B] (padded to a whole word)
         lw = (B + 1) // 2
-        meta_h = slot.meta(B + 1 + lw + B * nm)
+        base = B + 1 + lw + B * nm
+        meta_h = slot.meta(base + (B + 1 + lw if speed else 0))
         meta_n = meta_h.numpy()
         meta_n[:B + 1] = offs
         meta_n[B + 1:] = 0
-        i32 = meta_n[B + 1:].view(np.int32)
+        i32 = meta_n[B + 1:base].view(np.int32)
         i32[:B] = ilens
+        if speed:
+            meta_n[base:base + B + 1] = np.concatenate([[0], np.cumsum([p_all[i] for i in rows])])
+            meta_n[base + B + 1:].view(np.int32)[:B] = [f_all[i] for i in rows]
         if nm:
             for r, i in enumerate(rows):
                 i32[2 * lw + r * nm * 2:2 * lw + (r + 1) * nm * 2] = fe.draw_masks(self.mask_seed, self._n - 1, i,
@@ -266,9 +300,13 @@ class DeviceFeed(object):
             wav_d = wav_h.to(self.device, non_blocking=True)
             meta_d = meta_h.to(self.device, non_blocking=True)
             ys_d = ys_h.to(self.device, non_blocking=True) if ys_h is not None else None
-            i32_d = meta_d[B + 1:].view(torch.int32)
+            i32_d = meta_d[B + 1:base].view(torch.int32)
             masks_d = i32_d[2 * lw:2 * lw + B * nm * 2].view(B, nm, 2) if nm else None
-            xs_d = fe.run(wav_d, meta_d[:B + 1], i32_d[:B], t_max, masks_d)
+            speed_d = None
+            if speed:
+                speed_d = (meta_d[base + B + 1:].view(torch.int32)[:B], meta_d[base:base + B + 1],
+                           sum(p_all[i] for i in rows), max(p_all[i] for i in rows))
+            xs_d = fe.run(wav_d, meta_d[:B + 1], i32_d[:B], t_max, masks_d, speed_d)
             event = torch.cuda.Event()
             event.record(self._side)
         slot.event = event

@@ -5,11 +5,19 @@ training feeds, SpecAugment masks; rows behind an utterance are exact zeros.  Th
 statistics, in `utterance` mode only; the finish pass), no host synchronisation: every frame count follows from a sample
 count, which the host has.  There is no CPU path.
 
+Speed perturbation (csrc/resample.hip; training feeds only) is a fourth launch IN FRONT of the fbank: every
+utterance is resampled by a factor drawn on the host (`draw_speed`: one generator per row of the batch in collated order),
+so the host knows every perturbed sample count (`perturbed_samples`) and frame count before anything is uploaded; the fbank
+then reads the resampled float32 buffer.  A factor of exactly 1 copies the samples by value.
+
 Config (the `frontend` sub-dictionary; not a reference key):
   sample_rate 16000, frame_length_ms 25, frame_shift_ms 10, n_fft 512, n_mels 80, low_freq 20, high_freq 0 (<= 0: from the
   Nyquist frequency), preemph 0.97, delta_order 0 | 1 | 2,
   cmvn      "none" | "utterance" | the path of an .npz with `mean` and `istd` (or `std`) vectors of n_mels entries
   specaug   {n_freq_masks, max_freq_width, n_time_masks, max_time_width}; absent: no masks
+  speed_perturb  a list of speed factors chosen uniformly per utterance and epoch, e.g. [0.9, 1.0, 1.1] (Kaldi's three-way
+            perturbation; factor s plays round(s sample_rate) samples per second at sample_rate, as sox `speed` does); absent
+            or empty: off, and every launch sequence is the one without this key
 """
 import numpy as np
 import torch
@@ -52,6 +60,8 @@ class Frontend(object):
         self.n_time_masks, self.max_time_width = int(sa.get("n_time_masks", 0)), int(sa.get("max_time_width", 0))
         if not 0 <= self.max_freq_width <= self.n_mels or self.max_time_width < 0 or min(self.n_freq_masks, self.n_time_masks) < 0:
             raise ValueError("frontend: specaug widths and counts must be >= 0, max_freq_width <= n_mels")
+        self.speed_factors = [float(s) for s in (cfg.get("speed_perturb") or [])]
+        self.resample_plan = hb.ResamplePlan(sr, self.speed_factors) if self.speed_factors else None
 
     # ------------------------------------------------------------------ host arithmetic
     @property
@@ -66,8 +76,25 @@ class Frontend(object):
         return self.plan.num_frames(n_samples)
 
     def frames_of(self, waveform):
-        """The length filter's and the sort's view of an utterance (dataset.DictDataset(frames_of=...))."""
+        """The length filter's and the bucket sort's view of an utterance (dataset.DictDataset(frames_of=...)): the
+        UNPERTURBED frame count, also with `speed_perturb` - they see the corpus, not an epoch's draw."""
         return self.num_frames(waveform.shape[0])
+
+    @property
+    def n_speeds(self):
+        return len(self.speed_factors)
+
+    def draw_speed(self, seed, batch_index, row):
+        """The speed factor of one utterance -> its index into `speed_perturb`, uniform.  One numpy generator per row of a
+        batch IN COLLATED ORDER (before the feed sorts by perturbed length: the sort depends on the draw, so the draw must
+        not depend on the sort), seeded from (seed, batch, row) like draw_masks."""
+        rs = np.random.RandomState([int(seed), int(batch_index), int(row)])
+        return int(rs.randint(0, self.n_speeds))
+
+    def perturbed_samples(self, n_samples, factor_index):
+        """The sample count of an utterance of n_samples after factor `factor_index`: ceil(new n / orig), integers;
+        num_frames of it is the perturbed frame count."""
+        return self.resample_plan.out_samples(n_samples, factor_index)
 
     def draw_masks(self, seed, batch_index, global_row, T_b):
         """The SpecAugment masks of one utterance: int32 [n_masks, 2] of (start, width), frequency masks first.  One numpy
@@ -92,11 +119,19 @@ class Frontend(object):
             t = self._global_dev[key] = torch.from_numpy(self._global).to(device)
         return t
 
-    def run(self, samples, offsets, frame_lens, t_max, masks=None):
+    def run(self, samples, offsets, frame_lens, t_max, masks=None, speed=None):
         """Device tensors in (packed samples int16 / float32, offsets int64 [B + 1], frame_lens int32 [B] = num_frames of
-        every sample count, masks int32 [B, n_masks, 2] or None), launches on the current stream -> xs [B, t_max, D]."""
+        every sample count, masks int32 [B, n_masks, 2] or None), launches on the current stream -> xs [B, t_max, D].
+        speed: None, or (factor_index int32 [B], out_offsets int64 [B + 1] on the device, the host integers out_offsets[B]
+        and the longest perturbed sample count): the resample launch runs first, the fbank reads its float32 output, and
+        frame_lens are the PERTURBED frame counts."""
         B = offsets.numel() - 1
         dev = samples.device
+        if speed is not None:
+            factor_index, out_offsets, total, longest = speed
+            resampled = torch.empty(int(total), device=dev, dtype=torch.float32)
+            samples = hb.resample(self.resample_plan, samples, offsets, factor_index, out_offsets, resampled, max_out=int(longest))
+            offsets = out_offsets
         static = torch.empty(B, int(t_max), self.n_mels, device=dev, dtype=torch.float32)
         hb.fbank(self.plan, samples, offsets, int(t_max), static, use_log=True)
         stats = None
@@ -111,17 +146,30 @@ class Frontend(object):
                               masks=masks if with_masks else None, n_freq_masks=self.n_freq_masks if with_masks else 0,
                               n_time_masks=self.n_time_masks if with_masks else 0)
 
-    def __call__(self, samples, offsets, masks=None, t_max=None):
+    def __call__(self, samples, offsets, masks=None, t_max=None, factor_index=None):
         """samples: ONE packed 1-D int16 / float32 tensor on the GPU; offsets: B + 1 host integers; masks: host int32
-        [B, n_masks, 2] or None -> (xs [B, T_max, D], ilens: host list)."""
+        [B, n_masks, 2] or None; factor_index: B host indices into `speed_perturb` or None -> (xs [B, T_max, D], ilens: host
+        list; with factor_index the perturbed frame counts)."""
         if not samples.is_cuda:
             raise RuntimeError("Frontend: samples must live on the GPU: the HIP path has no CPU fallback")
         offs = [int(o) for o in offsets]
-        ilens = [self.num_frames(b - a) for a, b in zip(offs[:-1], offs[1:])]
+        counts = [b - a for a, b in zip(offs[:-1], offs[1:])]
+        speed = None
+        if factor_index is not None:
+            if self.resample_plan is None:
+                raise ValueError("Frontend: factor indices need the `speed_perturb` key")
+            fi = [int(f) for f in factor_index]
+            if len(fi) != len(counts) or min(fi) < 0 or max(fi) >= self.n_speeds:
+                raise hb.UnsupportedShape("Frontend: factor indices %s for %d rows, %d factors" % (fi, len(counts), self.n_speeds))
+            counts = [self.perturbed_samples(n, f) for n, f in zip(counts, fi)]
+            out_offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        ilens = [self.num_frames(n) for n in counts]
         t_max = max(ilens) if t_max is None else int(t_max)
         if t_max < 1:
             raise ValueError("Frontend: no utterance of the batch has a whole frame (%d samples)" % self.plan.frame_length)
         dev = samples.device
         masks_d = hb.to_device_i32(np.asarray(masks, dtype=np.int32), dev) if masks is not None and self.n_masks else None
-        xs = self.run(samples, hb.to_device_i64(offs, dev), hb.to_device_i32(ilens, dev), t_max, masks_d)
+        if factor_index is not None:
+            speed = (hb.to_device_i32(fi, dev), hb.to_device_i64(out_offs, dev), int(out_offs[-1]), max(counts))
+        xs = self.run(samples, hb.to_device_i64(offs, dev), hb.to_device_i32(ilens, dev), t_max, masks_d, speed)
         return xs, ilens

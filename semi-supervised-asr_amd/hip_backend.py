@@ -34,6 +34,7 @@ EXPORTS = (
     "asr_ctc_beam_ws_bytes", "asr_ctc_beam_f32",
     "asr_fbank_num_frames", "asr_fbank_plan_bytes", "asr_fbank_f32", "asr_feat_cmvn_stats_f32", "asr_feat_finish_f32",
     "asr_mwer_fwd_f32", "asr_mwer_bwd_f32",
+    "asr_resample_plan_bytes", "asr_resample_f32",
 )
 
 _lib = None
@@ -281,6 +282,8 @@ def load():
     lib.asr_fbank_f32.argtypes = [c_i, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_i64, c_i64, c_p]
     lib.asr_feat_cmvn_stats_f32.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p]
     lib.asr_feat_finish_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p]
+    lib.asr_resample_plan_bytes.argtypes = [c_i, c_p, ctypes.POINTER(c_i64)]
+    lib.asr_resample_f32.argtypes = [c_i, c_i64, c_p, c_i, c_i64, c_p, c_p, c_p, c_i, c_p, c_p, c_i64, c_p, c_i64, c_p]
     lib.asr_mwer_fwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
     lib.asr_mwer_bwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_f, c_p, c_i64, c_p]
     lib.asr_dec_feedback_fwd.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_p, c_i64,
@@ -1227,6 +1230,129 @@ def feat_finish(x, n_mels, frame_lens, out, order=0, cmvn=CMVN_NONE, stats=None,
         raise UnsupportedShape("feat_finish: %d bins (at most %d), delta order %d (0 .. 2)" % (n_mels, FBANK_MAX_MELS, order))
     check(rc, "asr_feat_finish_f32")
     LAUNCHES["feat_finish"] += 1
+    return out
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Speed perturbation (csrc/resample.hip): a polyphase resampler in front of the fbank.
+RESAMPLE_TILE = 1024          # ASR_RESAMPLE_TILE: output samples per workgroup
+RESAMPLE_MAX_FACTORS = 8      # ASR_RESAMPLE_MAX_FACTORS
+RESAMPLE_MAX_PHASES = 32      # ASR_RESAMPLE_MAX_PHASES
+RESAMPLE_MAX_TAPS = 64        # ASR_RESAMPLE_MAX_TAPS
+RESAMPLE_MAX_SPAN = 2176      # ASR_RESAMPLE_MAX_SPAN
+RESAMPLE_LPW, RESAMPLE_ROLLOFF = 6, 0.99
+
+
+def resample_plan_bytes(geometry):
+    """asr_resample_plan_bytes (no GPU) on an int32 [F, 5] array of (orig, new, width, taps, table offset); UnsupportedShape
+    beyond the header's limits."""
+    import numpy as np
+    g = np.ascontiguousarray(geometry, dtype=np.int32).reshape(-1, 5)
+    out = c_i64(0)
+    rc = load().asr_resample_plan_bytes(int(g.shape[0]), c_p(g.ctypes.data), ctypes.byref(out))
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("resample: %d factors (at most %d), phases %s (at most %d), taps %s (at most %d), speed at most 2"
+                               % (g.shape[0], RESAMPLE_MAX_FACTORS, g[:, 1].tolist(), RESAMPLE_MAX_PHASES, g[:, 3].tolist(),
+                                  RESAMPLE_MAX_TAPS))
+    check(rc, "asr_resample_plan_bytes")
+    return int(out.value)
+
+
+class ResamplePlan(object):
+    """The polyphase banks of asr_resample_f32 for a list of speed factors at one sample rate (include/asr_hip.h gives the
+    definition): factor s resamples from orig = round(s sample_rate) to new = sample_rate, both over their gcd.  The taps
+    are computed in float64 here and rounded to fp32 once.  `geometry` int32 [F, 5] = (orig, new, width, taps, table offset),
+    `tables` the fp32 host image (no GPU needed); `on(device)` is its device copy, made once per device."""
+
+    def __init__(self, sample_rate, factors):
+        import math
+        import numpy as np
+        self.sample_rate, self.factors = int(sample_rate), [float(s) for s in factors]
+        if self.sample_rate <= 0 or not self.factors or min(self.factors) <= 0:
+            raise ValueError("resample: need a positive sample rate and positive speed factors, got %d, %s"
+                             % (self.sample_rate, self.factors))
+        if len(self.factors) > RESAMPLE_MAX_FACTORS:
+            raise UnsupportedShape("resample: %d factors (at most %d)" % (len(self.factors), RESAMPLE_MAX_FACTORS))
+        geometry, banks, used = [], [], 0
+        for s in self.factors:
+            orig, new = int(round(s * self.sample_rate)), self.sample_rate
+            g = math.gcd(orig, new)
+            orig, new = orig // g, new // g
+            base = min(orig, new) * RESAMPLE_ROLLOFF
+            width = int(math.ceil(RESAMPLE_LPW * orig / base))
+            taps = 2 * width + orig
+            if new > RESAMPLE_MAX_PHASES or taps > RESAMPLE_MAX_TAPS:       # (before a table of that size is built)
+                raise UnsupportedShape("resample: factor %g at %d Hz is %d / %d: %d phases (at most %d), %d taps (at most %d)"
+                                       % (s, self.sample_rate, orig, new, new, RESAMPLE_MAX_PHASES, taps, RESAMPLE_MAX_TAPS))
+            t = ((np.arange(taps, dtype=np.float64)[None, :] - width) / orig - np.arange(new, dtype=np.float64)[:, None] / new) * base
+            t = np.clip(t, -RESAMPLE_LPW, RESAMPLE_LPW)
+            window = np.cos(t * np.pi / RESAMPLE_LPW / 2.0) ** 2
+            a = t * np.pi
+            sinc = np.where(a == 0, 1.0, np.sin(a) / np.where(a == 0, 1.0, a))
+            banks.append((sinc * window * (base / orig)).astype(np.float32))
+            geometry.append((orig, new, width, taps, used))
+            used += new * taps
+        self.geometry = np.asarray(geometry, dtype=np.int32)
+        self.tables = np.concatenate([b.reshape(-1) for b in banks])
+        assert self.tables.size * 4 == resample_plan_bytes(self.geometry)
+        self._dev = {}
+
+    def __len__(self):
+        return len(self.factors)
+
+    def bank(self, f):
+        """The fp32 taps [new, taps] of factor f (a view of the host image)."""
+        orig, new, width, taps, off = (int(v) for v in self.geometry[f])
+        return self.tables[off:off + new * taps].reshape(new, taps)
+
+    def out_samples(self, n_samples, f):
+        """ceil(new n / orig): the samples factor f makes of n (integer arithmetic)."""
+        orig, new = int(self.geometry[f, 0]), int(self.geometry[f, 1])
+        return -(-new * int(n_samples) // orig)
+
+    def on(self, device):
+        key = str(torch.device(device))
+        buf = self._dev.get(key)
+        if buf is None:
+            buf = self._dev[key] = torch.from_numpy(self.tables).to(device)
+        return buf
+
+
+def resample(plan, samples, in_offsets, factor_index, out_offsets, out, max_out=None):
+    """asr_resample_f32: samples = ONE packed 1-D int16 or float32 tensor, in_offsets / out_offsets int64 [B + 1] and
+    factor_index int32 [B] on the device -> utterance b resampled by plan factor factor_index[b] at out[out_offsets[b] ..),
+    `out` ONE packed 1-D float32 tensor.  factor_index may also be a host sequence: it is then checked against the plan
+    (UnsupportedShape outside it) and uploaded; a device tensor is trusted, and the kernel clamps it into the plan.  max_out:
+    the longest row's output length (default: out.numel(), an upper bound)."""
+    if not (samples.is_cuda and in_offsets.is_cuda and out_offsets.is_cuda and out.is_cuda):
+        raise RuntimeError("resample: tensors must live on the GPU: the HIP path has no CPU fallback")
+    if samples.dtype not in (torch.int16, torch.float32) or samples.dim() != 1 or not samples.is_contiguous():
+        raise RuntimeError("resample: samples must be one packed 1-D int16 or float32 tensor")
+    B = in_offsets.numel() - 1
+    for name, o in (("in_offsets", in_offsets), ("out_offsets", out_offsets)):
+        if o.dtype != torch.int64 or o.dim() != 1 or not o.is_contiguous() or o.numel() != B + 1 or B < 1:
+            raise RuntimeError("resample: %s must be int64 [B + 1]" % name)
+    if out.dtype != torch.float32 or out.dim() != 1 or not out.is_contiguous():
+        raise RuntimeError("resample: out must be one packed 1-D float32 tensor")
+    if not torch.is_tensor(factor_index):
+        import numpy as np
+        fi = np.asarray(factor_index, dtype=np.int64).reshape(-1)
+        if fi.size != B or (fi.size and (fi.min() < 0 or fi.max() >= len(plan))):
+            raise UnsupportedShape("resample: factor indices %s for %d rows and a plan of %d factors" % (fi.tolist(), B, len(plan)))
+        factor_index = to_device_i32(fi, out.device)
+    if not factor_index.is_cuda or factor_index.dtype != torch.int32 or factor_index.numel() != B or not factor_index.is_contiguous():
+        raise RuntimeError("resample: factor_index must be int32 [B] on the GPU (or a host sequence)")
+    max_out = int(out.numel() if max_out is None else max_out)
+    if max_out <= 0:
+        return out
+    tables = plan.on(out.device)
+    rc = load().asr_resample_f32(B, max_out, c_p(samples.data_ptr()), SAMPLES_I16 if samples.dtype == torch.int16 else SAMPLES_F32,
+                                 int(samples.numel()), c_p(in_offsets.data_ptr()), c_p(factor_index.data_ptr()),
+                                 c_p(out_offsets.data_ptr()), len(plan), c_p(plan.geometry.ctypes.data),
+                                 c_p(tables.data_ptr()), int(tables.numel()) * 4, ptr(out), int(out.numel()), stream())
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("resample: B %d (at most 65535), %d factors" % (B, len(plan)))
+    check(rc, "asr_resample_f32")
+    LAUNCHES["resample"] += 1
     return out
 
 

@@ -9,6 +9,15 @@ profiles/frontend_bench.jsonl):
               `--rounds` rounds of (features, waveforms), each a window of `--steps` steps behind `--warmup` steps, wall
               clock around a window that ends in flush + device synchronise.  Reports the median window of either feed and
               the spread of each feed's own windows (a difference inside it is not one).
+
+With --speed two other measurements are taken instead:
+
+  resample    the resample launch alone (hb.resample) on the same cfg-2 waveform batch, factors 0.9 / 1.0 / 1.1 in turn over
+              its rows, samples resident, device events around `--iters` calls.
+  epoch_loop_speed  the cfg-2 step fed from waveforms by training feeds WITHOUT and WITH `speed_perturb: [0.9, 1.0, 1.1]`,
+              alternating windows in one process as above.  The waveforms are U[0.6, 1] x 7.2 s here, so that an utterance
+              slowed to 0.9 stays inside cfg-2's 800 frames; every record carries its mean frames per batch, because a
+              perturbed batch is a different amount of work.
 """
 import argparse
 import contextlib
@@ -64,6 +73,86 @@ def cpu_frontend(waves, order, threads):
     return best
 
 
+SPEEDS = [0.9, 1.0, 1.1]
+
+
+def speed_lines(args, bench, hb, spec, items, samples, offs):
+    """--speed: the resample launch alone, then the epoch loop without / with speed perturbation -> the records."""
+    from dataset import synthetic_waveforms
+    from feed import DeviceFeed
+    from frontend import Frontend
+    dev = samples.device
+    c, B, T = dict(spec["model"]), spec["batch"], spec["frames"]
+    lines = []
+    fe = Frontend(dict(n_mels=80, delta_order=0, cmvn="utterance", speed_perturb=SPEEDS))
+    fidx = [b % len(SPEEDS) for b in range(B)]
+    counts = [fe.perturbed_samples(b - a, f) for a, b, f in zip(offs[:-1], offs[1:], fidx)]
+    out_offs = np.concatenate([[0], np.cumsum(counts)])
+    offs_d, out_offs_d = hb.to_device_i64(offs, dev), hb.to_device_i64(out_offs, dev)
+    fidx_d = hb.to_device_i32(fidx, dev)
+    out = torch.empty(int(out_offs[-1]), device=dev)
+    for _ in range(5):
+        hb.resample(fe.resample_plan, samples, offs_d, fidx_d, out_offs_d, out, max_out=max(counts))
+    torch.cuda.synchronize()
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(args.iters):
+        hb.resample(fe.resample_plan, samples, offs_d, fidx_d, out_offs_d, out, max_out=max(counts))
+    stop.record()
+    torch.cuda.synchronize()
+    ms = start.elapsed_time(stop) / args.iters
+    moved = int(samples.numel()) * 2 + int(out.numel()) * 4
+    lines.append(dict(tool="tools/frontend_bench.py", measurement="resample", factors=SPEEDS,
+                      workload="%d ragged utterances, U[0.6, 1] x 8 s int16 at 16 kHz, factors in turn over the rows" % B,
+                      samples_in=int(samples.numel()), samples_out=int(out.numel()), gpu_ms_per_launch=round(ms, 4),
+                      bytes_moved=moved, gb_per_s=round(moved / ms / 1e6, 1),
+                      timing="device events around %d launches (host enqueue included), samples resident" % args.iters))
+    if args.skip_epoch_loop:
+        return lines
+    tmp = tempfile.mkdtemp(prefix="frontend_bench_")
+    sv = bench.make_solver(c, B, T, os.path.join(tmp, "cfg2"))
+    data = synthetic_waveforms(B, c["output_dim"], 7.2, seed=1234)
+    short = [(v["feature"], v["token_ids"]) for v in data.values()]
+    fes = {"plain": Frontend(dict(n_mels=80, delta_order=0, cmvn="utterance")), "speed_perturb": fe}
+    n = args.warmup + args.steps
+
+    def window(kind):
+        feed = DeviceFeed([short] * n, dev, frontend=fes[kind], train=True)
+        frames = []
+        with contextlib.redirect_stdout(sys.stderr):
+            for i, (xs, ilens, ys) in enumerate(feed):
+                if i == args.warmup:
+                    sv.flush()
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                if i >= args.warmup:
+                    frames.append(sum(ilens))
+                last = sv.sup_train_one_iteration(xs, ilens, ys, 1.0)
+            sv.flush()
+            torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.steps * 1e3, float(np.mean(frames)), float(last)
+    windows, frames, loss = {k: [] for k in fes}, {k: [] for k in fes}, {}
+    np.random.seed(1234)                                  # the feeds' speed seeds
+    for _ in range(args.rounds):
+        for kind in fes:
+            ms, fr, loss[kind] = window(kind)
+            windows[kind].append(ms)
+            frames[kind].append(fr)
+    med = {k: statistics.median(w) for k, w in windows.items()}
+    for kind in fes:
+        lines.append(dict(tool="tools/frontend_bench.py", measurement="epoch_loop_speed", feed=kind,
+                          call="Solver.sup_train_one_iteration",
+                          workload="%s, batch %d, waveforms U[0.6, 1] x 7.2 s, training feed.DeviceFeed" % (spec["name"], B),
+                          speed_perturb=SPEEDS if kind == "speed_perturb" else None, rounds=args.rounds,
+                          steps_per_window=args.steps, warmup_steps=args.warmup, ms_per_step=round(med[kind], 3),
+                          windows_ms=[round(w, 3) for w in windows[kind]],
+                          spread=round((max(windows[kind]) - min(windows[kind])) / med[kind], 4),
+                          mean_frames_per_batch=round(float(np.mean(frames[kind])), 1),
+                          us_per_frame=round(med[kind] * 1e3 / float(np.mean(frames[kind])), 4),
+                          over_plain=round(med[kind] / med["plain"], 4), last_loss=loss[kind], arith=hb.arith_name()))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
@@ -71,6 +160,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--skip-epoch-loop", action="store_true")
+    ap.add_argument("--speed", action="store_true", help="measure speed perturbation instead (resample, epoch_loop_speed)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frontend_bench.jsonl"))
     args = ap.parse_args()
     import __graft_entry__ as entry
@@ -92,7 +182,9 @@ def main():
     threads = bench.usable_cpus()
     lines = []
 
-    for order in (0, 2):
+    if args.speed:
+        lines = speed_lines(args, bench, hb, spec, items, samples, offs)
+    for order in (() if args.speed else (0, 2)):
         fe = Frontend(dict(n_mels=80, delta_order=order, cmvn="utterance"))
         for _ in range(5):
             xs, ilens = fe(samples, offs)
@@ -115,7 +207,7 @@ def main():
                           timing="device events around %d calls (host enqueue included), samples resident" % args.iters,
                           cpu_torch_ms_per_batch=round(cpu_ms, 2), cpu_threads=threads, cpu_over_gpu=round(cpu_ms / gpu_ms, 1)))
 
-    if not args.skip_epoch_loop:
+    if not args.skip_epoch_loop and not args.speed:
         tmp = tempfile.mkdtemp(prefix="frontend_bench_")
         fe = Frontend(dict(n_mels=80, delta_order=0, cmvn="utterance"))
         assert fe.output_dim == c["input_dim"]
