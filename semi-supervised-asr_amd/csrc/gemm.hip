@@ -114,6 +114,117 @@ __device__ __forceinline__ void tile_coords(int tid, int tiles_m, int tiles_n, i
   tn = in / rows;
 }
 
+// ------------------------------------------------------------------------------------------ the frame of a tile kernel
+// What every family shares around its K loop: which tile and K slice a workgroup owns, and how an accumulator tile
+// reaches C.  A new family brings its K loop, nothing else.
+
+// XCD-aware tile order: consecutive tile ids share an A row-panel; the hardware deals workgroups round-robin over the
+// 8 XCDs, so give each XCD a contiguous chunk of ids.
+__device__ __forceinline__ int xcd_tile_id(int tid, int ntile) {
+  const int q = ntile >> 3, rmd = ntile & 7, xcd = tid & 7, idx = tid >> 3;
+  return (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q) + idx;
+}
+
+// Grid row z = batch element bz x K slice: K tiles [kt_begin, kt_end) of depth TK, S of them (<= 0: nothing to do).
+// ROUND_UP: the last K tile may be partial (guarded or masked by the kernel); otherwise K % TK == 0.
+struct KSlice {
+  int bz;
+  int64_t kt_begin, kt_end;
+  int S;
+};
+template <int TK, bool ROUND_UP>
+__device__ __forceinline__ KSlice k_slice(const GemmArgs& g, int z) {
+  const int bz = z / g.split_k, kz = z % g.split_k;
+  const int64_t ktiles = ROUND_UP ? (g.K + TK - 1) / TK : g.K / TK;
+  const int64_t per = (ktiles + g.split_k - 1) / g.split_k;
+  const int64_t kt_begin = kz * per;
+  const int64_t kt_end = kt_begin + per < ktiles ? kt_begin + per : ktiles;
+  return {bz, kt_begin, kt_end, (int)(kt_end - kt_begin)};
+}
+
+template <int NI, int NJ>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[NI][NJ]) {
+#pragma unroll
+  for (int i = 0; i < NI; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+}
+
+// One element of C: a K slice of a split product adds its part with an atomic (bias and ReLU follow in bias_act_kernel);
+// otherwise (v + bias) + old, then ReLU - in this order everywhere, so that every family rounds alike.
+__device__ __forceinline__ void store_c_elem(float* dst, float v, float bv, bool split, bool accum, bool relu) {
+  if (split) {
+    atomicAdd(dst, v);
+  } else {
+    float o = v + bv;
+    if (accum) o += *dst;
+    if (relu) o = fmaxf(o, 0.f);
+    *dst = o;
+  }
+}
+
+// The C epilogue of a wave that holds NB_I x NB_J blocks of 32 x 32 with their first element at (mrow0, ncol0).  The C/D
+// lane map of the 32x32 MFMAs does not depend on the input type: lane l owns column l31 = l & 31 of a block, element e is row
+// (e & 3) + 8 (e >> 2) + 4 kh, kh = l >> 5.  Interior tiles (edge = false): no bounds checks, 32-bit row offsets from one base
+// pointer per block, the accumulate form with its 16 old values loaded ahead of the arithmetic (the guarded path costs
+// ~30 VALU instructions per element, which is visible for short K).  Edge tiles: every element guarded, its address a
+// 64-bit row product.  ATOMIC_ALWAYS: the partial products of the queue kernel always meet in atomics.
+template <int NB_I, int NB_J, bool ATOMIC_ALWAYS>
+__device__ __forceinline__ void store_c_tile(const f32x16 (&acc)[NB_I][NB_J], const GemmArgs& g, float* C, int64_t mrow0,
+                                             int64_t ncol0, int l31, int kh, bool edge) {
+  const unsigned ldc = (unsigned)g.ldc;
+  const bool split = ATOMIC_ALWAYS || g.split_k > 1, accum = g.accumulate != 0, relu = g.relu != 0;
+  if (!edge) {
+#pragma unroll
+    for (int j = 0; j < NB_J; ++j) {
+      const int64_t n = ncol0 + j * 32 + l31;
+      const float bv = g.bias ? g.bias[n] : 0.f;
+#pragma unroll
+      for (int i = 0; i < NB_I; ++i) {
+        float* base = C + (mrow0 + i * 32 + 4 * kh) * g.ldc + n;
+        if (split) {
+#pragma unroll
+          for (int e = 0; e < 16; ++e) atomicAdd(base + (unsigned)((e & 3) + 8 * (e >> 2)) * ldc, acc[i][j][e]);
+        } else if (accum) {
+          float old[16];
+#pragma unroll
+          for (int e = 0; e < 16; ++e) old[e] = base[(unsigned)((e & 3) + 8 * (e >> 2)) * ldc];
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            float v = acc[i][j][e] + bv + old[e];
+            if (relu) v = fmaxf(v, 0.f);
+            base[(unsigned)((e & 3) + 8 * (e >> 2)) * ldc] = v;
+          }
+        } else {
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            float v = acc[i][j][e] + bv;
+            if (relu) v = fmaxf(v, 0.f);
+            base[(unsigned)((e & 3) + 8 * (e >> 2)) * ldc] = v;
+          }
+        }
+      }
+    }
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < NB_J; ++j) {
+    const int64_t n = ncol0 + j * 32 + l31;
+    if (n >= g.N) continue;
+    const float bv = g.bias ? g.bias[n] : 0.f;
+#pragma unroll
+    for (int i = 0; i < NB_I; ++i) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int64_t m = mrow0 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh;
+        if (m < g.M) store_c_elem(C + m * g.ldc + n, acc[i][j][e], bv, split, accum, relu);
+      }
+    }
+  }
+}
+
 template <bool AKC, bool BKC>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
   constexpr int SA = TileCfg<AKC>::S, SB = TileCfg<BKC>::S;
@@ -121,40 +232,24 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
   float* As = smem;
   float* Bs = smem + BK * SA;
 
-  // XCD-aware tile order: consecutive tile ids share an A row-panel; the hardware deals
-  // workgroups round-robin over the 8 XCDs, so give each XCD a contiguous chunk of ids.
-  const int ntile = g.tiles_m * g.tiles_n;
-  int tid = blockIdx.x;
-  {
-    const int q = ntile >> 3, rmd = ntile & 7, xcd = tid & 7, idx = tid >> 3;
-    tid = (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q) + idx;
-  }
+  const int tid = xcd_tile_id(blockIdx.x, g.tiles_m * g.tiles_n);
   const int tm = tid / g.tiles_n, tn = tid % g.tiles_n;
-  const int z = blockIdx.y;
-  const int bz = z / g.split_k, kz = z % g.split_k;
+  const KSlice sl = k_slice<BK, true>(g, blockIdx.y);
+  const int64_t kt_begin = sl.kt_begin, kt_end = sl.kt_end;
 
   MatView A = g.A, B = g.B;
-  A.p += bz * g.sA;
-  B.p += bz * g.sB;
-  float* C = g.C + bz * g.sC;
+  A.p += sl.bz * g.sA;
+  B.p += sl.bz * g.sB;
+  float* C = g.C + sl.bz * g.sC;
 
   const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
-  const int64_t ktiles = (g.K + BK - 1) / BK;
-  const int64_t per = (ktiles + g.split_k - 1) / g.split_k;
-  const int64_t kt_begin = kz * per;
-  const int64_t kt_end = kt_begin + per < ktiles ? kt_begin + per : ktiles;
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int l31 = lane & 31, kh = lane >> 5;
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
 
   // Fast operand path for interior tiles and full K tiles: one uniform base pointer per operand (advanced by the K
   // offset) + a 32-bit per-thread element offset computed once, i.e. 8 unguarded float4 loads per K tile and no
@@ -235,72 +330,11 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
     __syncthreads();
   }
 
-  // epilogue: lane owns column n, rows (e&3) + 8*(e>>2) + 4*kh of each 32x32 tile
-  if (m0 + BM <= g.M && n0 + BN <= g.N) {
-    // interior tile: no bounds checks, 32-bit row offsets from one base pointer per 32x32 tile (the generic path
-    // below costs ~30 VALU instructions per element, which is visible for short K)
-    const unsigned ldc = (unsigned)g.ldc;
-    const bool split = g.split_k > 1, accum = g.accumulate != 0, relu = g.relu != 0;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int64_t n = n0 + wn * 64 + j * 32 + l31;
-      const float bv = g.bias ? g.bias[n] : 0.f;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        float* base = C + (m0 + wm * 64 + i * 32 + 4 * kh) * g.ldc + n;
-        if (split) {
-#pragma unroll
-          for (int e = 0; e < 16; ++e) atomicAdd(base + (unsigned)((e & 3) + 8 * (e >> 2)) * ldc, acc[i][j][e]);
-        } else if (accum) {
-          float old[16];
-#pragma unroll
-          for (int e = 0; e < 16; ++e) old[e] = base[(unsigned)((e & 3) + 8 * (e >> 2)) * ldc];
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            float v = acc[i][j][e] + bv + old[e];
-            if (relu) v = fmaxf(v, 0.f);
-            base[(unsigned)((e & 3) + 8 * (e >> 2)) * ldc] = v;
-          }
-        } else {
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            float v = acc[i][j][e] + bv;
-            if (relu) v = fmaxf(v, 0.f);
-            base[(unsigned)((e & 3) + 8 * (e >> 2)) * ldc] = v;
-          }
-        }
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int64_t n = n0 + wn * 64 + j * 32 + l31;
-    if (n >= g.N) continue;
-    const float bv = g.bias ? g.bias[n] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int64_t m = m0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh;
-        if (m >= g.M) continue;
-        float v = acc[i][j][e];
-        float* dst = C + m * g.ldc + n;
-        if (g.split_k > 1) {
-          atomicAdd(dst, v);
-        } else {
-          v += bv;
-          if (g.accumulate) v += *dst;
-          if (g.relu) v = fmaxf(v, 0.f);
-          *dst = v;
-        }
-      }
-    }
-  }
+  store_c_tile<2, 2, false>(acc, g, C, m0 + wm * 64, n0 + wn * 64, l31, kh, !(m0 + BM <= g.M && n0 + BN <= g.N));
 }
 
 // ------------------------------------------------------------------------------------------ split-bf16 product
-// Same tiling, operand fetch, split-K and epilogue as gemm_f32_kernel; the product runs on v_mfma_f32_32x32x16_bf16
+// Same tiling and operand fetch as gemm_f32_kernel; the product runs on v_mfma_f32_32x32x16_bf16
 // with both fp32 operands split in two bf16 terms while they are staged into LDS (x = hi + lo, hi = the upper 16 bits
 // of the fp32 word, lo = bf16(x - hi) rounded to nearest: 16 significand bits) and three products hi*hi + hi*lo + lo*hi
 // accumulated in fp32.  Dropped: lo*lo and the rounding of lo, <= 2^-16 relative per product (fp32: 2^-24), far inside
@@ -314,6 +348,8 @@ typedef __bf16 gbf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 gbf16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned gu32x4 __attribute__((ext_vector_type(4)));
 constexpr int BS = 40;                       // LDS row stride in bf16 (80 bytes)
+// c += a b on v_mfma_f32_32x32x16_bf16: a, b fragments of 8 bf16 held as four 32-bit words, c a 32 x 32 block
+#define MFMA_BF16(a_, b_, c_) c_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(gbf16x8, a_), __builtin_bit_cast(gbf16x8, b_), c_, 0, 0, 0)
 
 __device__ __forceinline__ unsigned bf3g_hi2(float a, float b) {      // {hi(a), hi(b)}: upper halves of the two words
   return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
@@ -445,34 +481,25 @@ __global__ __launch_bounds__(256, QUEUE ? 4 : (TS == 64 ? ASR_GEMM_SMALL_OCC : 1
     tid = (int)(tk % (unsigned)ntile);
     z = (int)(tk / (unsigned)ntile);
   } else {
-    const int q = ntile >> 3, rmd = ntile & 7, xcd = tid & 7, idx = tid >> 3;
-    tid = (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q) + idx;
+    tid = xcd_tile_id(tid, ntile);
   }
   const int tm = tid / g.tiles_n, tn = tid % g.tiles_n;
-  const int bz = z / g.split_k, kz = z % g.split_k;
+  const KSlice sl = k_slice<BK, true>(g, z);
+  const int64_t kt_begin = sl.kt_begin, kt_end = sl.kt_end;
 
   MatView A = g.A, B = g.B;
-  A.p += bz * g.sA;
-  B.p += bz * g.sB;
-  float* C = g.C + bz * g.sC;
+  A.p += sl.bz * g.sA;
+  B.p += sl.bz * g.sB;
+  float* C = g.C + sl.bz * g.sC;
 
   const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
-  const int64_t ktiles = (g.K + BK - 1) / BK;
-  const int64_t per = (ktiles + g.split_k - 1) / g.split_k;
-  const int64_t kt_begin = kz * per;
-  const int64_t kt_end = kt_begin + per < ktiles ? kt_begin + per : ktiles;
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int l31 = lane & 31, kh = lane >> 5;
 
   f32x16 acc[NB][NB];
-#pragma unroll
-  for (int i = 0; i < NB; ++i)
-#pragma unroll
-    for (int j = 0; j < NB; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
 
   // interior tiles and full K tiles: uniform base + 32-bit per-thread offsets (see gemm_f32_kernel)
   const bool fast_a = A.vec && (AKC ? (m0 + BM <= A.R) : (m0 + BM <= A.Cn)) && A.R * A.ld < (int64_t)1 << 30;
@@ -536,7 +563,6 @@ __global__ __launch_bounds__(256, QUEUE ? 4 : (TS == 64 ? ASR_GEMM_SMALL_OCC : 1
           af[i][k] = *reinterpret_cast<const gu32x4*>(Ai + k * BM * BS + ao + 32 * i * BS + 16 * ks);
           bf[i][k] = *reinterpret_cast<const gu32x4*>(Bi + k * BM * BS + bo + 32 * i * BS + 16 * ks);
         }
-#define BF3G(a_, b_, c_) c_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(gbf16x8, a_), __builtin_bit_cast(gbf16x8, b_), c_, 0, 0, 0)
       // term pairs (p, q) with p + q < NT: 3 products for two terms, 6 for three
 #pragma unroll
       for (int o = 0; o < NT; ++o)
@@ -545,8 +571,7 @@ __global__ __launch_bounds__(256, QUEUE ? 4 : (TS == 64 ? ASR_GEMM_SMALL_OCC : 1
 #pragma unroll
           for (int i = 0; i < NB; ++i)
 #pragma unroll
-            for (int j = 0; j < NB; ++j) BF3G(af[i][p], bf[j][o - p], acc[i][j]);
-#undef BF3G
+            for (int j = 0; j < NB; ++j) MFMA_BF16(af[i][p], bf[j][o - p], acc[i][j]);
     }
   };
   // full K tiles of interior workgroups run the bare-load loop; a K tail (K % 32 != 0, e.g. the 80-dim features) and edge
@@ -631,66 +656,7 @@ __global__ __launch_bounds__(256, QUEUE ? 4 : (TS == 64 ? ASR_GEMM_SMALL_OCC : 1
     }
   }
 
-  // epilogue (as gemm_f32_kernel: the C/D lane map of the 32x32 MFMAs does not depend on the input type)
-  if (m0 + BM <= g.M && n0 + BN <= g.N) {
-    const unsigned ldc = (unsigned)g.ldc;
-    const bool split = QUEUE || g.split_k > 1, accum = g.accumulate != 0, relu = g.relu != 0;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      const int64_t n = n0 + wn * (TS / 2) + j * 32 + l31;
-      const float bv = g.bias ? g.bias[n] : 0.f;
-#pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        float* base = C + (m0 + wm * (TS / 2) + i * 32 + 4 * kh) * g.ldc + n;
-        if (split) {
-#pragma unroll
-          for (int e = 0; e < 16; ++e) atomicAdd(base + (unsigned)((e & 3) + 8 * (e >> 2)) * ldc, acc[i][j][e]);
-        } else if (accum) {
-          float old[16];
-#pragma unroll
-          for (int e = 0; e < 16; ++e) old[e] = base[(unsigned)((e & 3) + 8 * (e >> 2)) * ldc];
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            float v = acc[i][j][e] + bv + old[e];
-            if (relu) v = fmaxf(v, 0.f);
-            base[(unsigned)((e & 3) + 8 * (e >> 2)) * ldc] = v;
-          }
-        } else {
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            float v = acc[i][j][e] + bv;
-            if (relu) v = fmaxf(v, 0.f);
-            base[(unsigned)((e & 3) + 8 * (e >> 2)) * ldc] = v;
-          }
-        }
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < NB; ++j) {
-    const int64_t n = n0 + wn * (TS / 2) + j * 32 + l31;
-    if (n >= g.N) continue;
-    const float bv = g.bias ? g.bias[n] : 0.f;
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int64_t m = m0 + wm * (TS / 2) + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh;
-        if (m >= g.M) continue;
-        float v = acc[i][j][e];
-        float* dst = C + m * g.ldc + n;
-        if (QUEUE || g.split_k > 1) {
-          atomicAdd(dst, v);
-        } else {
-          v += bv;
-          if (g.accumulate) v += *dst;
-          if (g.relu) v = fmaxf(v, 0.f);
-          *dst = v;
-        }
-      }
-    }
-  }
+  store_c_tile<NB, NB, QUEUE>(acc, g, C, m0 + wm * (TS / 2), n0 + wn * (TS / 2), l31, kh, !(m0 + BM <= g.M && n0 + BN <= g.N));
 }
 
 // ------------------------------------------------------------------------------------------ split-bf16, wide tile
@@ -722,18 +688,9 @@ __device__ __forceinline__ void glds16(const float* src, float* lds_dst) {
                : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
 }
 
-__device__ __forceinline__ void bf3w_split(const float (&v)[8], gu32x4& hi, gu32x4& lo) {
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    hi[p] = bf3g_hi2(v[2 * p], v[2 * p + 1]);
-    lo[p] = bf3g_lo2(v[2 * p], v[2 * p + 1]);
-  }
-}
-
-// the 8 consecutive k of this lane for one 32-row block of an operand stage
+// the 8 consecutive k of this lane for one 32-row block of an operand stage (fp32, before the kernel's own split)
 template <bool KC, int ROWS>
-__device__ __forceinline__ void bf3w_frag(const float* st, int row, int kq0s, int kq1s, int k0, gu32x4& hi, gu32x4& lo) {
-  float v[8];
+__device__ __forceinline__ void wide_frag8(const float* st, int row, int kq0s, int kq1s, int k0, float (&v)[8]) {
   if (KC) {
     const float4 x = *reinterpret_cast<const float4*>(st + row * WK + kq0s);
     const float4 y = *reinterpret_cast<const float4*>(st + row * WK + kq1s);
@@ -742,7 +699,17 @@ __device__ __forceinline__ void bf3w_frag(const float* st, int row, int kq0s, in
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = st[(k0 + e) * ROWS + row];
   }
-  bf3w_split(v, hi, lo);
+}
+
+template <bool KC, int ROWS>
+__device__ __forceinline__ void bf3w_frag(const float* st, int row, int kq0s, int kq1s, int k0, gu32x4& hi, gu32x4& lo) {
+  float v[8];
+  wide_frag8<KC, ROWS>(st, row, kq0s, kq1s, k0, v);
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    hi[p] = bf3g_hi2(v[2 * p], v[2 * p + 1]);
+    lo[p] = bf3g_lo2(v[2 * p], v[2 * p + 1]);
+  }
 }
 
 template <int I0>
@@ -755,6 +722,8 @@ __device__ __forceinline__ void bf3w_send(float* xs, const f32x16 (&acc)[4][2], 
       for (int e = 0; e < 16; ++e) xs[((b * 2 + j) * 16 + e) * 64 + lane] = acc[I0 + b][j][e];
 }
 
+// store_c_tile's element map and store for the two row blocks I0, I0 + 1, with the partner's half added first (which is
+// why it is not store_c_tile: the interior form there works on the accumulators as they are)
 template <int I0, bool EDGE>
 __device__ __forceinline__ void bf3w_finish(const float* xr, f32x16 (&acc)[4][2], const GemmArgs& g, float* C, int64_t mrow0,
                                             int64_t ncol0, int lane) {
@@ -777,15 +746,7 @@ __device__ __forceinline__ void bf3w_finish(const float* xr, f32x16 (&acc)[4][2]
       for (int e = 0; e < 16; ++e) {
         const int r = (e & 3) + 8 * (e >> 2);
         if (EDGE && !(nok && mb + r < g.M)) continue;
-        float* dst = base + (unsigned)r * ldc;
-        if (split) {
-          atomicAdd(dst, v[e]);
-        } else {
-          float o = v[e] + bv;
-          if (accum) o += *dst;
-          if (relu) o = fmaxf(o, 0.f);
-          *dst = o;
-        }
+        store_c_elem(base + (unsigned)r * ldc, v[e], bv, split, accum, relu);
       }
     }
 }
@@ -800,68 +761,63 @@ __device__ unsigned long long asr_gw_trace_buf[2 * 64 * 8];
 #define GW_COARSE(m) do {} while (0)
 #endif
 
+// What gemm_bf3w_kernel and gemm_bf6w_kernel share around their stage bodies: this lane's DMA sources, the issue of a
+// stage, the fragment addressing, and (below) the sum of the two K halves with the store.
+//   wave = 4 kg + 2 wm + wn: K half of a stage, 128-row half and 64-column half of the tile.
+//   DMA source offsets (floats, relative to the operand's first element at the stage's first k): rows and columns past
+//   the matrix edge are clamped to the last valid ones - what they deliver only reaches accumulator rows / columns that the
+//   guarded epilogue does not store; k-contiguous pieces carry the swizzle of the kernel's header comment.
+//   Fragments: granules (4 kg + 2 kh, + 1) of the lane's row, swizzled by (row >> 1) & 7 = (l31 >> 1) & 7.
 template <bool AKC, bool BKC>
-__global__ __launch_bounds__(512) void gemm_bf3w_kernel(GemmArgs g) {
-  __shared__ __attribute__((aligned(1024))) float smem[W_STAGES * W_STAGE_FLOATS];
-
-  const int ntile = g.tiles_m * g.tiles_n;
-  int tid = blockIdx.x;
-  {
-    const int q = ntile >> 3, rmd = ntile & 7, xcd = tid & 7, idx = tid >> 3;
-    tid = (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q) + idx;
-  }
-  const int tm = tid / g.tiles_n, tn = tid % g.tiles_n;
-  const int z = blockIdx.y;
-  const int bz = z / g.split_k, kz = z % g.split_k;
-  const float* Ap = g.A.p + bz * g.sA;
-  const float* Bp = g.B.p + bz * g.sB;
-  float* C = g.C + bz * g.sC;
-  const int64_t m0 = (int64_t)tm * WM, n0 = (int64_t)tn * WN;
-  const int64_t ktiles = g.K / WK;
-  const int64_t per = (ktiles + g.split_k - 1) / g.split_k;
-  const int64_t kt_begin = kz * per;
-  const int64_t kt_end = kt_begin + per < ktiles ? kt_begin + per : ktiles;
-  const int S = (int)(kt_end - kt_begin);
-  if (S <= 0) return;
-
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int kg = wave >> 2, wm = (wave >> 1) & 1, wn = wave & 1;
-  const int l31 = lane & 31, kh = lane >> 5;
-
-  // ---- DMA source offsets of this lane (floats, relative to the operand's first element at the stage's first k).  Rows
-  // and columns past the matrix edge are clamped to the last valid ones: what they deliver only reaches accumulator
-  // rows / columns that the guarded epilogue does not store.
-  const int64_t lda = g.A.ld, ldb = g.B.ld;
+struct WideDma {
   unsigned offa[4], offb[2];
+  const float *basea, *baseb;           // the K slice's first stage; stage st at base + st * step
+  int64_t stepa, stepb;
+  int kq0s, kq1s, kfirst, arow, brow;   // wide_frag8's arguments for this lane
+
+  __device__ __forceinline__ WideDma(const GemmArgs& g, const float* Ap, const float* Bp, int64_t m0, int64_t n0, int64_t kt_begin,
+                                     int wave, int lane) {
+    const int64_t lda = g.A.ld, ldb = g.B.ld;
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int p = 4 * wave + q;
-    if (AKC) {
-      const int r = 8 * p + (lane >> 3);
-      const int64_t row = m0 + r < g.M ? m0 + r : g.M - 1;
-      offa[q] = (unsigned)(row * lda + 4 * ((lane & 7) ^ ((r >> 1) & 7)));
-    } else {
-      const int64_t col = m0 + 4 * lane + 4 <= g.M ? m0 + 4 * lane : g.M - 4;
-      offa[q] = (unsigned)(p * lda + col);
+    for (int q = 0; q < 4; ++q) {
+      const int p = 4 * wave + q;
+      if (AKC) {
+        const int r = 8 * p + (lane >> 3);
+        const int64_t row = m0 + r < g.M ? m0 + r : g.M - 1;
+        offa[q] = (unsigned)(row * lda + 4 * ((lane & 7) ^ ((r >> 1) & 7)));
+      } else {
+        const int64_t col = m0 + 4 * lane + 4 <= g.M ? m0 + 4 * lane : g.M - 4;
+        offa[q] = (unsigned)(p * lda + col);
+      }
     }
-  }
 #pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int p = 2 * wave + q;
-    if (BKC) {
-      const int r = 8 * p + (lane >> 3);
-      const int64_t row = n0 + r < g.N ? n0 + r : g.N - 1;
-      offb[q] = (unsigned)(row * ldb + 4 * ((lane & 7) ^ ((r >> 1) & 7)));
-    } else {
-      const int64_t col = n0 + 4 * (lane & 31) + 4 <= g.N ? n0 + 4 * (lane & 31) : g.N - 4;
-      offb[q] = (unsigned)((2 * p + (lane >> 5)) * ldb + col);
+    for (int q = 0; q < 2; ++q) {
+      const int p = 2 * wave + q;
+      if (BKC) {
+        const int r = 8 * p + (lane >> 3);
+        const int64_t row = n0 + r < g.N ? n0 + r : g.N - 1;
+        offb[q] = (unsigned)(row * ldb + 4 * ((lane & 7) ^ ((r >> 1) & 7)));
+      } else {
+        const int64_t col = n0 + 4 * (lane & 31) + 4 <= g.N ? n0 + 4 * (lane & 31) : g.N - 4;
+        offb[q] = (unsigned)((2 * p + (lane >> 5)) * ldb + col);
+      }
     }
+    basea = AKC ? Ap + kt_begin * WK : Ap + kt_begin * WK * lda;
+    baseb = BKC ? Bp + kt_begin * WK : Bp + kt_begin * WK * ldb;
+    stepa = AKC ? WK : WK * lda;
+    stepb = BKC ? WK : WK * ldb;
+    const int kg = wave >> 2, wm = (wave >> 1) & 1, wn = wave & 1;
+    const int l31 = lane & 31, kh = lane >> 5;
+    const int sw = (l31 >> 1) & 7;
+    kq0s = 4 * ((4 * kg + 2 * kh) ^ sw);
+    kq1s = kq0s ^ 4;
+    kfirst = 16 * kg + 8 * kh;
+    arow = wm * 128 + l31;
+    brow = wn * 64 + l31;
   }
-  const float* basea = AKC ? Ap + kt_begin * WK : Ap + kt_begin * WK * lda;
-  const float* baseb = BKC ? Bp + kt_begin * WK : Bp + kt_begin * WK * ldb;
-  const int64_t stepa = AKC ? WK : WK * lda, stepb = BKC ? WK : WK * ldb;
-  auto issue = [&](int st, int buf) {
+
+  // this wave's six pieces of stage st into ring buffer buf
+  __device__ __forceinline__ void issue(float* smem, int wave, int st, int buf) const {
     float* sb = smem + buf * W_STAGE_FLOATS;
     const float* pa = basea + st * stepa;
     const float* pb = baseb + st * stepb;
@@ -869,21 +825,69 @@ __global__ __launch_bounds__(512) void gemm_bf3w_kernel(GemmArgs g) {
     for (int q = 0; q < 4; ++q) glds16(pa + offa[q], sb + (4 * wave + q) * 256);
 #pragma unroll
     for (int q = 0; q < 2; ++q) glds16(pb + offb[q], sb + W_A_FLOATS + (2 * wave + q) * 256);
-  };
+  }
+
+  // fill the ring (up to three of the S stages) and wait until stage 0 is complete in LDS
+  __device__ __forceinline__ void prime(float* smem, int wave, int S) const {
+    issue(smem, wave, 0, 0);
+    if (S > 1) issue(smem, wave, 1, 1);
+    if (S > 2) issue(smem, wave, 2, 2);
+    if (S > 2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+    else if (S > 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+  }
+};
+
+// Sum the two K halves and store: each wave hands the 64 rows it does not write to its partner (same wm, wn) through LDS.
+// TRACE: gemm_bf3w_kernel's ASR_GW_TRACE mark between the exchange and the stores.
+template <bool TRACE>
+__device__ __forceinline__ void wide_sum_halves_and_store(float* smem, f32x16 (&acc)[4][2], const GemmArgs& g, float* C, int64_t m0,
+                                                          int64_t n0, int wave, int lane) {
+  const int kg = wave >> 2, wm = (wave >> 1) & 1, wn = wave & 1;
+  __syncthreads();
+  const int w4 = wave & 3;
+  float* xs = smem + ((w4 * 2 + (1 - kg)) * 64) * 64;       // read by the partner
+  const float* xr = smem + ((w4 * 2 + kg) * 64) * 64;       // written by the partner
+  if (kg == 0) bf3w_send<2>(xs, acc, lane); else bf3w_send<0>(xs, acc, lane);
+  __syncthreads();
+  const int64_t mrow0 = m0 + wm * 128, ncol0 = n0 + wn * 64;
+  if (TRACE) GW_COARSE(3);
+  if (m0 + WM <= g.M && n0 + WN <= g.N) {
+    if (kg == 0) bf3w_finish<0, false>(xr, acc, g, C, mrow0, ncol0, lane);
+    else bf3w_finish<2, false>(xr, acc, g, C, mrow0, ncol0, lane);
+  } else {
+    if (kg == 0) bf3w_finish<0, true>(xr, acc, g, C, mrow0, ncol0, lane);
+    else bf3w_finish<2, true>(xr, acc, g, C, mrow0, ncol0, lane);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// compile-time tags of the unrolled pipelines: register-set parity, and "no conditionals in the body"
+typedef std::integral_constant<int, 0> P0;
+typedef std::integral_constant<int, 1> P1;
+typedef std::integral_constant<bool, true> Full;
+typedef std::integral_constant<bool, false> Tail;
+
+template <bool AKC, bool BKC>
+__global__ __launch_bounds__(512) void gemm_bf3w_kernel(GemmArgs g) {
+  __shared__ __attribute__((aligned(1024))) float smem[W_STAGES * W_STAGE_FLOATS];
+
+  const int tid = xcd_tile_id(blockIdx.x, g.tiles_m * g.tiles_n);
+  const int tm = tid / g.tiles_n, tn = tid % g.tiles_n;
+  const KSlice sl = k_slice<WK, false>(g, blockIdx.y);
+  const int S = sl.S;
+  if (S <= 0) return;
+  float* C = g.C + sl.bz * g.sC;
+  const int64_t m0 = (int64_t)tm * WM, n0 = (int64_t)tn * WN;
+
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const WideDma<AKC, BKC> w(g, g.A.p + sl.bz * g.sA, g.B.p + sl.bz * g.sB, m0, n0, sl.kt_begin, wave, lane);
 
   f32x16 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-  // fragment addressing: granules (4 kg + 2 kh, + 1) of the lane's row, swizzled by (row >> 1) & 7 = (l31 >> 1) & 7
-  const int sw = (l31 >> 1) & 7;
-  const int kq0s = 4 * ((4 * kg + 2 * kh) ^ sw), kq1s = kq0s ^ 4;
-  const int kfirst = 16 * kg + 8 * kh;
-  const int arow = wm * 128 + l31, brow = wn * 64 + l31;
+  zero_acc(acc);
 
   // Software pipeline inside every wave (all 8 waves in step, one barrier per stage, in its middle):
   //   H1(s): 12 MFMAs  A rows 0-63 x B of stage s          || read + split A rows 64-127 of stage s
@@ -895,7 +899,6 @@ __global__ __launch_bounds__(512) void gemm_bf3w_kernel(GemmArgs g) {
   // matrix pipe, and with the two K halves running in opposite phases (second version) 5 250: tools/gemm_wide_trace.py
   // showed 1 040-1 550 cycles per fragment phase (three exposed LDS round trips + 120 VALU) and 125 cycles per DMA issue.
   gu32x4 bh[2][2], bl[2][2], a0h[2], a0l[2], a1h[2], a1l[2];
-#define BF3W(a_, b_, c_) c_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(gbf16x8, a_), __builtin_bit_cast(gbf16x8, b_), c_, 0, 0, 0)
   auto stage = [&](int st, int buf, auto ptag, auto ftag) {
     constexpr int P = decltype(ptag)::value;
     constexpr bool FULL = decltype(ftag)::value;       // stages st + 1 and st + 3 exist: no conditionals in the body
@@ -907,17 +910,17 @@ __global__ __launch_bounds__(512) void gemm_bf3w_kernel(GemmArgs g) {
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) BF3W(a0h[a], bh[P][j], acc[a][j]);
+      for (int j = 0; j < 2; ++j) MFMA_BF16(a0h[a], bh[P][j], acc[a][j]);
 #pragma unroll
-    for (int a = 0; a < 2; ++a) bf3w_frag<AKC, WM>(sa, arow + 32 * (2 + a), kq0s, kq1s, kfirst, a1h[a], a1l[a]);
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) BF3W(a0h[a], bl[P][j], acc[a][j]);
+    for (int a = 0; a < 2; ++a) bf3w_frag<AKC, WM>(sa, w.arow + 32 * (2 + a), w.kq0s, w.kq1s, w.kfirst, a1h[a], a1l[a]);
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) BF3W(a0l[a], bh[P][j], acc[a][j]);
+      for (int j = 0; j < 2; ++j) MFMA_BF16(a0h[a], bl[P][j], acc[a][j]);
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) MFMA_BF16(a0l[a], bh[P][j], acc[a][j]);
     // ---- mid
     const bool next = FULL || st + 1 < S;
     GW_MARK(1);
@@ -932,61 +935,49 @@ __global__ __launch_bounds__(512) void gemm_bf3w_kernel(GemmArgs g) {
     // ---- H2
     const bool dma = FULL || st + 3 < S;
     float* sb = smem + buf * W_STAGE_FLOATS;           // stage st + 3 goes where stage st was
-    const float* pa = basea + (st + 3) * stepa;
-    const float* pb = baseb + (st + 3) * stepb;
+    const float* pa = w.basea + (st + 3) * w.stepa;
+    const float* pb = w.baseb + (st + 3) * w.stepb;
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) BF3W(a1h[a], bh[P][j], acc[2 + a][j]);
+      for (int j = 0; j < 2; ++j) MFMA_BF16(a1h[a], bh[P][j], acc[2 + a][j]);
     if (dma) {
-      glds16(pa + offa[0], sb + (4 * wave + 0) * 256);
-      glds16(pa + offa[1], sb + (4 * wave + 1) * 256);
+      glds16(pa + w.offa[0], sb + (4 * wave + 0) * 256);
+      glds16(pa + w.offa[1], sb + (4 * wave + 1) * 256);
     }
     if (next) {
 #pragma unroll
-      for (int j = 0; j < 2; ++j) bf3w_frag<BKC, WN>(sa1 + W_A_FLOATS, brow + 32 * j, kq0s, kq1s, kfirst, bh[1 - P][j], bl[1 - P][j]);
+      for (int j = 0; j < 2; ++j) bf3w_frag<BKC, WN>(sa1 + W_A_FLOATS, w.brow + 32 * j, w.kq0s, w.kq1s, w.kfirst, bh[1 - P][j], bl[1 - P][j]);
     }
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) BF3W(a1h[a], bl[P][j], acc[2 + a][j]);
+      for (int j = 0; j < 2; ++j) MFMA_BF16(a1h[a], bl[P][j], acc[2 + a][j]);
     if (dma) {
-      glds16(pa + offa[2], sb + (4 * wave + 2) * 256);
-      glds16(pa + offa[3], sb + (4 * wave + 3) * 256);
+      glds16(pa + w.offa[2], sb + (4 * wave + 2) * 256);
+      glds16(pa + w.offa[3], sb + (4 * wave + 3) * 256);
     }
     if (next) {
 #pragma unroll
-      for (int a = 0; a < 2; ++a) bf3w_frag<AKC, WM>(sa1, arow + 32 * a, kq0s, kq1s, kfirst, a0h[a], a0l[a]);
+      for (int a = 0; a < 2; ++a) bf3w_frag<AKC, WM>(sa1, w.arow + 32 * a, w.kq0s, w.kq1s, w.kfirst, a0h[a], a0l[a]);
     }
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) BF3W(a1l[a], bh[P][j], acc[2 + a][j]);
+      for (int j = 0; j < 2; ++j) MFMA_BF16(a1l[a], bh[P][j], acc[2 + a][j]);
     if (dma) {
-      glds16(pb + offb[0], sb + W_A_FLOATS + (2 * wave + 0) * 256);
-      glds16(pb + offb[1], sb + W_A_FLOATS + (2 * wave + 1) * 256);
+      glds16(pb + w.offb[0], sb + W_A_FLOATS + (2 * wave + 0) * 256);
+      glds16(pb + w.offb[1], sb + W_A_FLOATS + (2 * wave + 1) * 256);
     }
     GW_MARK(4);
   };
-#undef BF3W
-  typedef std::integral_constant<int, 0> P0;
-  typedef std::integral_constant<int, 1> P1;
-  typedef std::integral_constant<bool, true> Full;
-  typedef std::integral_constant<bool, false> Tail;
 
   GW_COARSE(0);
-  issue(0, 0);
-  if (S > 1) issue(1, 1);
-  if (S > 2) issue(2, 2);
-  if (S > 2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-  else if (S > 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
+  w.prime(smem, wave, S);
 #pragma unroll
-  for (int j = 0; j < 2; ++j) bf3w_frag<BKC, WN>(smem + W_A_FLOATS, brow + 32 * j, kq0s, kq1s, kfirst, bh[0][j], bl[0][j]);
+  for (int j = 0; j < 2; ++j) bf3w_frag<BKC, WN>(smem + W_A_FLOATS, w.brow + 32 * j, w.kq0s, w.kq1s, w.kfirst, bh[0][j], bl[0][j]);
 #pragma unroll
-  for (int a = 0; a < 2; ++a) bf3w_frag<AKC, WM>(smem, arow + 32 * a, kq0s, kq1s, kfirst, a0h[a], a0l[a]);
+  for (int a = 0; a < 2; ++a) bf3w_frag<AKC, WM>(smem, w.arow + 32 * a, w.kq0s, w.kq1s, w.kfirst, a0h[a], a0l[a]);
   int st = 0, buf = 0;
   GW_COARSE(1);
   for (; st + 4 < S; st += 2) {                  // both stages of the pair have st + 3 < S
@@ -1004,24 +995,8 @@ __global__ __launch_bounds__(512) void gemm_bf3w_kernel(GemmArgs g) {
     }
   }
 
-  // ---- sum the two K halves: each wave hands the 64 rows it does not write to its partner (same wm, wn)
   GW_COARSE(2);
-  __syncthreads();
-  const int w4 = wave & 3;
-  float* xs = smem + ((w4 * 2 + (1 - kg)) * 64) * 64;       // read by the partner
-  const float* xr = smem + ((w4 * 2 + kg) * 64) * 64;       // written by the partner
-  if (kg == 0) bf3w_send<2>(xs, acc, lane); else bf3w_send<0>(xs, acc, lane);
-  __syncthreads();
-  const int64_t mrow0 = m0 + wm * 128, ncol0 = n0 + wn * 64;
-  GW_COARSE(3);
-  if (m0 + WM <= g.M && n0 + WN <= g.N) {
-    if (kg == 0) bf3w_finish<0, false>(xr, acc, g, C, mrow0, ncol0, lane);
-    else bf3w_finish<2, false>(xr, acc, g, C, mrow0, ncol0, lane);
-  } else {
-    if (kg == 0) bf3w_finish<0, true>(xr, acc, g, C, mrow0, ncol0, lane);
-    else bf3w_finish<2, true>(xr, acc, g, C, mrow0, ncol0, lane);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wide_sum_halves_and_store<true>(smem, acc, g, C, m0, n0, wave, lane);
   GW_COARSE(4);
 }
 
@@ -1042,14 +1017,7 @@ __global__ __launch_bounds__(512) void gemm_bf3w_kernel(GemmArgs g) {
 template <bool KC, int ROWS>
 __device__ __forceinline__ void bf6w_frag(const float* st, int row, int kq0s, int kq1s, int k0, gu32x4 (&t)[3]) {
   float v[8];
-  if (KC) {
-    const float4 x = *reinterpret_cast<const float4*>(st + row * WK + kq0s);
-    const float4 y = *reinterpret_cast<const float4*>(st + row * WK + kq1s);
-    v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w; v[4] = y.x; v[5] = y.y; v[6] = y.z; v[7] = y.w;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = st[(k0 + e) * ROWS + row];
-  }
+  wide_frag8<KC, ROWS>(st, row, kq0s, kq1s, k0, v);
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
     unsigned q[3];
@@ -1062,89 +1030,25 @@ template <bool AKC, bool BKC>
 __global__ __launch_bounds__(512) void gemm_bf6w_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(1024))) float smem[W_STAGES * W_STAGE_FLOATS];
 
-  const int ntile = g.tiles_m * g.tiles_n;
-  int tid = blockIdx.x;
-  {
-    const int q = ntile >> 3, rmd = ntile & 7, xcd = tid & 7, idx = tid >> 3;
-    tid = (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q) + idx;
-  }
+  const int tid = xcd_tile_id(blockIdx.x, g.tiles_m * g.tiles_n);
   const int tm = tid / g.tiles_n, tn = tid % g.tiles_n;
-  const int z = blockIdx.y;
-  const int bz = z / g.split_k, kz = z % g.split_k;
-  const float* Ap = g.A.p + bz * g.sA;
-  const float* Bp = g.B.p + bz * g.sB;
-  float* C = g.C + bz * g.sC;
-  const int64_t m0 = (int64_t)tm * WM, n0 = (int64_t)tn * WN;
-  const int64_t ktiles = g.K / WK;
-  const int64_t per = (ktiles + g.split_k - 1) / g.split_k;
-  const int64_t kt_begin = kz * per;
-  const int64_t kt_end = kt_begin + per < ktiles ? kt_begin + per : ktiles;
-  const int S = (int)(kt_end - kt_begin);
+  const KSlice sl = k_slice<WK, false>(g, blockIdx.y);
+  const int S = sl.S;
   if (S <= 0) return;
+  float* C = g.C + sl.bz * g.sC;
+  const int64_t m0 = (int64_t)tm * WM, n0 = (int64_t)tn * WN;
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int kg = wave >> 2, wm = (wave >> 1) & 1, wn = wave & 1;
-  const int l31 = lane & 31, kh = lane >> 5;
-
-  // DMA source offsets of this lane: as in gemm_bf3w_kernel (edge rows / columns clamped, k-contiguous pieces swizzled)
-  const int64_t lda = g.A.ld, ldb = g.B.ld;
-  unsigned offa[4], offb[2];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int p = 4 * wave + q;
-    if (AKC) {
-      const int r = 8 * p + (lane >> 3);
-      const int64_t row = m0 + r < g.M ? m0 + r : g.M - 1;
-      offa[q] = (unsigned)(row * lda + 4 * ((lane & 7) ^ ((r >> 1) & 7)));
-    } else {
-      const int64_t col = m0 + 4 * lane + 4 <= g.M ? m0 + 4 * lane : g.M - 4;
-      offa[q] = (unsigned)(p * lda + col);
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int p = 2 * wave + q;
-    if (BKC) {
-      const int r = 8 * p + (lane >> 3);
-      const int64_t row = n0 + r < g.N ? n0 + r : g.N - 1;
-      offb[q] = (unsigned)(row * ldb + 4 * ((lane & 7) ^ ((r >> 1) & 7)));
-    } else {
-      const int64_t col = n0 + 4 * (lane & 31) + 4 <= g.N ? n0 + 4 * (lane & 31) : g.N - 4;
-      offb[q] = (unsigned)((2 * p + (lane >> 5)) * ldb + col);
-    }
-  }
-  const float* basea = AKC ? Ap + kt_begin * WK : Ap + kt_begin * WK * lda;
-  const float* baseb = BKC ? Bp + kt_begin * WK : Bp + kt_begin * WK * ldb;
-  const int64_t stepa = AKC ? WK : WK * lda, stepb = BKC ? WK : WK * ldb;
-  auto issue = [&](int st, int buf) {
-    float* sb = smem + buf * W_STAGE_FLOATS;
-    const float* pa = basea + st * stepa;
-    const float* pb = baseb + st * stepb;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) glds16(pa + offa[q], sb + (4 * wave + q) * 256);
-#pragma unroll
-    for (int q = 0; q < 2; ++q) glds16(pb + offb[q], sb + W_A_FLOATS + (2 * wave + q) * 256);
-  };
+  const WideDma<AKC, BKC> w(g, g.A.p + sl.bz * g.sA, g.B.p + sl.bz * g.sB, m0, n0, sl.kt_begin, wave, lane);
 
   f32x16 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-  const int sw = (l31 >> 1) & 7;
-  const int kq0s = 4 * ((4 * kg + 2 * kh) ^ sw), kq1s = kq0s ^ 4;
-  const int kfirst = 16 * kg + 8 * kh;
-  const int arow = wm * 128 + l31, brow = wn * 64 + l31;
+  zero_acc(acc);
 
   gu32x4 bq[2][3], a0[2][3], a1[2][3];
-#define BF6W(a_, b_, c_) c_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(gbf16x8, a_), __builtin_bit_cast(gbf16x8, b_), c_, 0, 0, 0)
   // the six products of (A half, B block): term pairs in order of significance sum; consecutive MFMAs alternate between
   // the two accumulators of the quarter
-#define BF6W_PAIR(ah_, b_, i0_, j_, p_, q_) do { BF6W(ah_[0][p_], b_[q_], acc[i0_][j_]); BF6W(ah_[1][p_], b_[q_], acc[i0_ + 1][j_]); } while (0)
+#define BF6W_PAIR(ah_, b_, i0_, j_, p_, q_) do { MFMA_BF16(ah_[0][p_], b_[q_], acc[i0_][j_]); MFMA_BF16(ah_[1][p_], b_[q_], acc[i0_ + 1][j_]); } while (0)
   auto stage = [&](int st, int buf, auto ptag, auto ftag) {
     constexpr int P = decltype(ptag)::value;
     constexpr bool FULL = decltype(ftag)::value;       // stages st + 1 and st + 3 exist: no conditionals in the body
@@ -1157,17 +1061,17 @@ __global__ __launch_bounds__(512) void gemm_bf6w_kernel(GemmArgs g) {
     // ---- Q1
     BF6W_PAIR(a0, b0, 0, 0, 0, 0);
     BF6W_PAIR(a0, b0, 0, 0, 0, 1);
-    bf6w_frag<BKC, WN>(sa + W_A_FLOATS, brow + 32, kq0s, kq1s, kfirst, b1);
+    bf6w_frag<BKC, WN>(sa + W_A_FLOATS, w.brow + 32, w.kq0s, w.kq1s, w.kfirst, b1);
     BF6W_PAIR(a0, b0, 0, 0, 1, 0);
     BF6W_PAIR(a0, b0, 0, 0, 0, 2);
     BF6W_PAIR(a0, b0, 0, 0, 2, 0);
     BF6W_PAIR(a0, b0, 0, 0, 1, 1);
     // ---- Q2
     BF6W_PAIR(a0, b1, 0, 1, 0, 0);
-    bf6w_frag<AKC, WM>(sa, arow + 64, kq0s, kq1s, kfirst, a1[0]);
+    bf6w_frag<AKC, WM>(sa, w.arow + 64, w.kq0s, w.kq1s, w.kfirst, a1[0]);
     BF6W_PAIR(a0, b1, 0, 1, 0, 1);
     BF6W_PAIR(a0, b1, 0, 1, 1, 0);
-    bf6w_frag<AKC, WM>(sa, arow + 96, kq0s, kq1s, kfirst, a1[1]);
+    bf6w_frag<AKC, WM>(sa, w.arow + 96, w.kq0s, w.kq1s, w.kfirst, a1[1]);
     BF6W_PAIR(a0, b1, 0, 1, 0, 2);
     BF6W_PAIR(a0, b1, 0, 1, 2, 0);
     BF6W_PAIR(a0, b1, 0, 1, 1, 1);
@@ -1181,53 +1085,42 @@ __global__ __launch_bounds__(512) void gemm_bf6w_kernel(GemmArgs g) {
     // ---- Q3
     const bool dma = FULL || st + 3 < S;
     float* sb = smem + buf * W_STAGE_FLOATS;           // stage st + 3 goes where stage st was
-    const float* pa = basea + (st + 3) * stepa;
-    const float* pb = baseb + (st + 3) * stepb;
+    const float* pa = w.basea + (st + 3) * w.stepa;
+    const float* pb = w.baseb + (st + 3) * w.stepb;
     BF6W_PAIR(a1, b1, 2, 1, 0, 0);
     if (dma) {
-      glds16(pa + offa[0], sb + (4 * wave + 0) * 256);
-      glds16(pa + offa[1], sb + (4 * wave + 1) * 256);
+      glds16(pa + w.offa[0], sb + (4 * wave + 0) * 256);
+      glds16(pa + w.offa[1], sb + (4 * wave + 1) * 256);
     }
-    if (next) bf6w_frag<AKC, WM>(sa1, arow, kq0s, kq1s, kfirst, a0[0]);
+    if (next) bf6w_frag<AKC, WM>(sa1, w.arow, w.kq0s, w.kq1s, w.kfirst, a0[0]);
     BF6W_PAIR(a1, b1, 2, 1, 0, 1);
     BF6W_PAIR(a1, b1, 2, 1, 1, 0);
     if (dma) {
-      glds16(pa + offa[2], sb + (4 * wave + 2) * 256);
-      glds16(pa + offa[3], sb + (4 * wave + 3) * 256);
+      glds16(pa + w.offa[2], sb + (4 * wave + 2) * 256);
+      glds16(pa + w.offa[3], sb + (4 * wave + 3) * 256);
     }
-    if (next) bf6w_frag<AKC, WM>(sa1, arow + 32, kq0s, kq1s, kfirst, a0[1]);
+    if (next) bf6w_frag<AKC, WM>(sa1, w.arow + 32, w.kq0s, w.kq1s, w.kfirst, a0[1]);
     BF6W_PAIR(a1, b1, 2, 1, 0, 2);
     BF6W_PAIR(a1, b1, 2, 1, 2, 0);
     BF6W_PAIR(a1, b1, 2, 1, 1, 1);
     // ---- Q4 (b1 is dead: its registers receive B cols 0-31 of the next stage)
     BF6W_PAIR(a1, b0, 2, 0, 0, 0);
     if (dma) {
-      glds16(pb + offb[0], sb + W_A_FLOATS + (2 * wave + 0) * 256);
-      glds16(pb + offb[1], sb + W_A_FLOATS + (2 * wave + 1) * 256);
+      glds16(pb + w.offb[0], sb + W_A_FLOATS + (2 * wave + 0) * 256);
+      glds16(pb + w.offb[1], sb + W_A_FLOATS + (2 * wave + 1) * 256);
     }
     BF6W_PAIR(a1, b0, 2, 0, 0, 1);
-    if (next) bf6w_frag<BKC, WN>(sa1 + W_A_FLOATS, brow, kq0s, kq1s, kfirst, b1);
+    if (next) bf6w_frag<BKC, WN>(sa1 + W_A_FLOATS, w.brow, w.kq0s, w.kq1s, w.kfirst, b1);
     BF6W_PAIR(a1, b0, 2, 0, 1, 0);
     BF6W_PAIR(a1, b0, 2, 0, 0, 2);
     BF6W_PAIR(a1, b0, 2, 0, 2, 0);
     BF6W_PAIR(a1, b0, 2, 0, 1, 1);
   };
-  typedef std::integral_constant<int, 0> P0;
-  typedef std::integral_constant<int, 1> P1;
-  typedef std::integral_constant<bool, true> Full;
-  typedef std::integral_constant<bool, false> Tail;
 
-  issue(0, 0);
-  if (S > 1) issue(1, 1);
-  if (S > 2) issue(2, 2);
-  if (S > 2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-  else if (S > 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  bf6w_frag<BKC, WN>(smem + W_A_FLOATS, brow, kq0s, kq1s, kfirst, bq[0]);
-  bf6w_frag<AKC, WM>(smem, arow, kq0s, kq1s, kfirst, a0[0]);
-  bf6w_frag<AKC, WM>(smem, arow + 32, kq0s, kq1s, kfirst, a0[1]);
+  w.prime(smem, wave, S);
+  bf6w_frag<BKC, WN>(smem + W_A_FLOATS, w.brow, w.kq0s, w.kq1s, w.kfirst, bq[0]);
+  bf6w_frag<AKC, WM>(smem, w.arow, w.kq0s, w.kq1s, w.kfirst, a0[0]);
+  bf6w_frag<AKC, WM>(smem, w.arow + 32, w.kq0s, w.kq1s, w.kfirst, a0[1]);
   int st = 0, buf = 0;
   for (; st + 4 < S; st += 2) {                  // both stages of the pair have st + 3 < S
     stage(st, buf, P0(), Full());
@@ -1244,24 +1137,8 @@ __global__ __launch_bounds__(512) void gemm_bf6w_kernel(GemmArgs g) {
     }
   }
 #undef BF6W_PAIR
-#undef BF6W
 
-  // ---- sum the two K halves and store: as gemm_bf3w_kernel
-  __syncthreads();
-  const int w4 = wave & 3;
-  float* xs = smem + ((w4 * 2 + (1 - kg)) * 64) * 64;       // read by the partner
-  const float* xr = smem + ((w4 * 2 + kg) * 64) * 64;       // written by the partner
-  if (kg == 0) bf3w_send<2>(xs, acc, lane); else bf3w_send<0>(xs, acc, lane);
-  __syncthreads();
-  const int64_t mrow0 = m0 + wm * 128, ncol0 = n0 + wn * 64;
-  if (m0 + WM <= g.M && n0 + WN <= g.N) {
-    if (kg == 0) bf3w_finish<0, false>(xr, acc, g, C, mrow0, ncol0, lane);
-    else bf3w_finish<2, false>(xr, acc, g, C, mrow0, ncol0, lane);
-  } else {
-    if (kg == 0) bf3w_finish<0, true>(xr, acc, g, C, mrow0, ncol0, lane);
-    else bf3w_finish<2, true>(xr, acc, g, C, mrow0, ncol0, lane);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wide_sum_halves_and_store<false>(smem, acc, g, C, m0, n0, wave, lane);
 }
 
 // ------------------------------------------------------------------------------ split-bf16, one wave per SIMD
@@ -1314,24 +1191,14 @@ __global__ __launch_bounds__(256, 1) void gemm_bfs_kernel(GemmArgs g) {
   constexpr int PLA = 2 * SP_A, PLB = 2 * SP_B;        // bytes of one A / B image
   constexpr int BUFB = NT * (PLA + PLB);               // bytes of one buffer: NT A images, then NT B images
 
-  const int ntile = g.tiles_m * g.tiles_n;
-  int tid = blockIdx.x;
-  {
-    const int q = ntile >> 3, rmd = ntile & 7, xcd = tid & 7, idx = tid >> 3;
-    tid = (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q) + idx;
-  }
   int tm, tn;
-  tile_coords(tid, g.tiles_m, g.tiles_n, ASR_GEMM_GM, tm, tn);
-  const int z = blockIdx.y;
-  const int bz = z / g.split_k, kz = z % g.split_k;
+  tile_coords(xcd_tile_id(blockIdx.x, g.tiles_m * g.tiles_n), g.tiles_m, g.tiles_n, ASR_GEMM_GM, tm, tn);
+  const KSlice sl = k_slice<SK, KT>(g, blockIdx.y);                   // KT: K % 32 != 0 (K % 4 == 0): the last K tile is masked
+  const int bz = sl.bz, S = sl.S;
+  const int64_t kt_begin = sl.kt_begin;
+  if (S <= 0) return;
   float* C = g.C + bz * g.sC;
   const int64_t m0 = (int64_t)tm * SM, n0 = (int64_t)tn * SN;
-  const int64_t ktiles = KT ? (g.K + SK - 1) / SK : g.K / SK;         // KT: K % 32 != 0 (K % 4 == 0): the last K tile is masked
-  const int64_t per = (ktiles + g.split_k - 1) / g.split_k;
-  const int64_t kt_begin = kz * per;
-  const int64_t kt_end = kt_begin + per < ktiles ? kt_begin + per : ktiles;
-  const int S = (int)(kt_end - kt_begin);
-  if (S <= 0) return;
 
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -1403,12 +1270,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bfs_kernel(GemmArgs g) {
   }
 
   f32x16 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
 
   gu32x4 RA[2][8], RB[2][4];                 // staging registers (raw fp32 bits) of K tiles of even / odd parity
   gu32x4 FA[2][4][NT], FB[2][2][NT];         // fragment sets F0 (k 0-15), F1 (k 16-31)
@@ -1490,16 +1352,15 @@ __global__ __launch_bounds__(256, 1) void gemm_bfs_kernel(GemmArgs g) {
       if constexpr (NT > 2) FB[KS][Qs - 4][2] = *lds_at<lds_q4ptr>(a + 2 * PLB);
     }
   };
-#define BFS(a_, b_, c_) c_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(gbf16x8, a_), __builtin_bit_cast(gbf16x8, b_), c_, 0, 0, 0)
   // the 8 MFMAs of term pair number tp (in order of significance sum) of k half KS
   auto products = [&](auto kstag, auto tptag) __attribute__((always_inline)) {
     constexpr int KS = decltype(kstag)::value, TP = decltype(tptag)::value;
     constexpr int o = TP == 0 ? 0 : TP < 3 ? 1 : 2, p = TP == 0 ? 0 : TP < 3 ? TP - 1 : TP - 3;
     if constexpr (o < NT) {
-      BFS(FA[KS][0][p], FB[KS][0][o - p], acc[0][0]); BFS(FA[KS][0][p], FB[KS][1][o - p], acc[0][1]);
-      BFS(FA[KS][1][p], FB[KS][0][o - p], acc[1][0]); BFS(FA[KS][1][p], FB[KS][1][o - p], acc[1][1]);
-      BFS(FA[KS][2][p], FB[KS][0][o - p], acc[2][0]); BFS(FA[KS][2][p], FB[KS][1][o - p], acc[2][1]);
-      BFS(FA[KS][3][p], FB[KS][0][o - p], acc[3][0]); BFS(FA[KS][3][p], FB[KS][1][o - p], acc[3][1]);
+      MFMA_BF16(FA[KS][0][p], FB[KS][0][o - p], acc[0][0]); MFMA_BF16(FA[KS][0][p], FB[KS][1][o - p], acc[0][1]);
+      MFMA_BF16(FA[KS][1][p], FB[KS][0][o - p], acc[1][0]); MFMA_BF16(FA[KS][1][p], FB[KS][1][o - p], acc[1][1]);
+      MFMA_BF16(FA[KS][2][p], FB[KS][0][o - p], acc[2][0]); MFMA_BF16(FA[KS][2][p], FB[KS][1][o - p], acc[2][1]);
+      MFMA_BF16(FA[KS][3][p], FB[KS][0][o - p], acc[3][0]); MFMA_BF16(FA[KS][3][p], FB[KS][1][o - p], acc[3][1]);
     }
   };
   // One half of a K tile: 48 MFMAs of k half KS, slot by slot with the fragment reads of the other k half (from buffer RD),
@@ -1570,8 +1431,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bfs_kernel(GemmArgs g) {
     if (n1) barrier();
     half(I1(), PT(), I0(), PN(), n1, PT(), n2, st + 2, st + 4, FULL || st + 4 < S);
   };
-  typedef std::integral_constant<bool, true> Full;
-  typedef std::integral_constant<bool, false> Tail;
   int st = 0;
   for (; st + 5 < S; st += 2) {
     ktile(st, I0(), Full());
@@ -1581,62 +1440,8 @@ __global__ __launch_bounds__(256, 1) void gemm_bfs_kernel(GemmArgs g) {
     ktile(st, I0(), Tail());
     if (st + 1 < S) ktile(st + 1, I1(), Tail());
   }
-#undef BFS
 
-  // ---- epilogue: lane owns column n, rows (e & 3) + 8 (e >> 2) + 4 kh of each 32 x 32 block
-  const int64_t mrow0 = m0 + wm * 128, ncol0 = n0 + wn * 64;
-  const unsigned ldc = (unsigned)g.ldc;
-  const bool split = g.split_k > 1, accum = g.accumulate != 0, relu = g.relu != 0;
-  const bool edge = !(m0 + SM <= g.M && n0 + SN <= g.N);
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int64_t n = ncol0 + j * 32 + l31;
-    const bool nok = !edge || n < g.N;
-    const float bv = (g.bias && nok) ? g.bias[n] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int64_t mb = mrow0 + i * 32 + 4 * kh;
-      float* base = C + mb * g.ldc + n;
-      if (!edge) {
-        if (split) {
-#pragma unroll
-          for (int e = 0; e < 16; ++e) atomicAdd(base + (unsigned)((e & 3) + 8 * (e >> 2)) * ldc, acc[i][j][e]);
-        } else if (accum) {
-          float old[16];
-#pragma unroll
-          for (int e = 0; e < 16; ++e) old[e] = base[(unsigned)((e & 3) + 8 * (e >> 2)) * ldc];
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            float v = acc[i][j][e] + bv + old[e];
-            if (relu) v = fmaxf(v, 0.f);
-            base[(unsigned)((e & 3) + 8 * (e >> 2)) * ldc] = v;
-          }
-        } else {
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            float v = acc[i][j][e] + bv;
-            if (relu) v = fmaxf(v, 0.f);
-            base[(unsigned)((e & 3) + 8 * (e >> 2)) * ldc] = v;
-          }
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int r = (e & 3) + 8 * (e >> 2);
-          if (!(nok && mb + r < g.M)) continue;
-          float* dst = base + (unsigned)r * ldc;
-          if (split) {
-            atomicAdd(dst, acc[i][j][e]);
-          } else {
-            float o = acc[i][j][e] + bv;
-            if (accum) o += *dst;
-            if (relu) o = fmaxf(o, 0.f);
-            *dst = o;
-          }
-        }
-      }
-    }
-  }
+  store_c_tile<4, 2, false>(acc, g, C, m0 + wm * 128, n0 + wn * 64, l31, kh, !(m0 + SM <= g.M && n0 + SN <= g.N));
 }
 
 // ------------------------------------------------------------------------------ split-bf16, short K, weights stationary
@@ -1723,18 +1528,16 @@ __global__ __launch_bounds__(512) void gemm_bfk_kernel(GemmArgs g, int groups) {
       if constexpr (NT > 2) FA[SL][i][2] = *lds_at<lds_q4ptr>(a + 2 * PLANE);
     }
   };
-#define BFK(a_, b_, c_) c_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(gbf16x8, a_), __builtin_bit_cast(gbf16x8, b_), c_, 0, 0, 0)
   auto products = [&](auto slottag, auto kstag, auto settag) __attribute__((always_inline)) {
     constexpr int SL = decltype(slottag)::value, KSI = decltype(kstag)::value, P = decltype(settag)::value;
 #pragma unroll
     for (int o = 0; o < NT; ++o)
 #pragma unroll
       for (int p = 0; p <= o; ++p) {
-        BFK(FA[SL][0][p], FB[KSI][o - p], acc[P][0]);
-        BFK(FA[SL][1][p], FB[KSI][o - p], acc[P][1]);
+        MFMA_BF16(FA[SL][0][p], FB[KSI][o - p], acc[P][0]);
+        MFMA_BF16(FA[SL][1][p], FB[KSI][o - p], acc[P][1]);
       }
   };
-#undef BFK
   const bool accum = g.accumulate != 0, relu = g.relu != 0;
   const int64_t ncol = n0 + wn * 32 + l31;
   const float bv = (g.bias && ncol < g.N) ? g.bias[ncol] : 0.f;
