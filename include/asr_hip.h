@@ -1185,6 +1185,53 @@ int asr_resample_f32(int B, int64_t max_out, const void* samples, int sample_dty
                      const int32_t* geometry, const void* tables, int64_t table_bytes, float* out, int64_t out_count,
                      asr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Reverberation and additive noise (csrc/augment.hip): two passes over packed waveforms between
+ * asr_resample_f32 and asr_fbank_f32.  Not reference operators.  Two entries added to ABI version 8 WITHOUT a version
+ * change, like the resampler's: additive.  Both keep every row's length: the output is packed by the SAME offsets as the
+ * input, so sample counts and frame counts stay host arithmetic.
+ *   asr_reverb_f32      utterance b = samples[offsets[b] .. offsets[b + 1]) (int16 or fp32, as asr_resample_f32) with
+ *                       r = rir_index[b] (DEVICE int32 [B]):  r < 0 copies the row by value (int16 -> fp32 exactly, fp32 bit
+ *                       for bit);  otherwise  y[n] = sum_{k = 0}^{L - 1} h[k] x[n + d - k]  for n in [0, N), x zero outside
+ *                       [0, N): the row convolved with RIR r and shifted back by the RIR's direct-path index d, so the output
+ *                       is not delayed (Kaldi wav-reverberate --shift-output=true).  geometry: HOST int64 [n_rirs][3] =
+ *                       (offset into bank in floats, taps L, d), checked here; geometry_dev: the same array on the DEVICE,
+ *                       read by the kernel (clamped into the bank, so a copy that differs gives wrong numbers, not a wrong
+ *                       access); bank: DEVICE fp32 [bank_count], filled by the CALLER (cut, scaled to unit energy in
+ *                       float64, rounded once).  One launch, grid (ceil(max_len / ASR_REVERB_TILE), B), max_len = the
+ *                       longest row (an upper bound will do).  A wave of the workgroup forms 1024 outputs as one 32 x 32
+ *                       accumulator of v_mfma_f32_32x32x2_f32 - a banded matrix product, an exact fp32 fmaf chain per
+ *                       output - over the taps in chunks of ASR_REVERB_CHUNK; input span and band are staged in LDS per
+ *                       chunk (33 KB whatever L), so ASR_REVERB_MAX_TAPS bounds the work of a tile, not the LDS.
+ *                       out must not alias samples.
+ *   asr_noise_mix_f32   z[n] = y[n] + g v[n],  v[n] = clip[(start[b] + n) mod len(clip)],  clip = clip_index[b] (DEVICE int32
+ *                       [B]; < 0: no clip),  g = scale[b] sqrt(P_y / P_v)  with P_y = sum y[n]^2, P_v = sum v[n]^2 over the
+ *                       row's N samples in float64 (per-tile partials of ASR_NOISE_TILE samples in ws, added in tile order),
+ *                       g formed in float64 and rounded once; g = 0 when either sum is 0.  scale[b] = 10^(-snr_db / 20)
+ *                       comes from the host (DEVICE fp32 [B]); start: DEVICE int64 [B], taken mod len.  clip_offsets: HOST
+ *                       int64 [n_clips + 1] into bank (DEVICE fp32 [bank_count]), checked here; clip_offsets_dev: the same
+ *                       on the DEVICE.  ws: at least 16 B ceil(max_len / ASR_NOISE_TILE) bytes, 8-byte aligned.  out may be
+ *                       the fp32 samples buffer itself (in place): rows without a clip and rows with g = 0 are then not
+ *                       written at all; into another buffer they are copied by value.  gains: NULL or DEVICE fp32 [B] = g.
+ *                       Two launches (sums, then mix) on the same grid.
+ * Offsets are clamped into the buffers as in asr_resample_f32; nothing at or behind offsets[B] is read or written, nothing
+ * behind a RIR or a clip is read.  A RIR of more than ASR_REVERB_MAX_TAPS taps, B > 65535, a sample_dtype that is neither of
+ * the two: ASR_E_SHAPE.  A NULL pointer, geometry or clip offsets outside the bank, d outside [0, L), an empty clip, too small
+ * a workspace, reverb in place, an int16 mix in place: ASR_E_ARG.  Both before anything is launched.  No atomics, no host
+ * synchronisation, no allocation; the same bits in every run, in and outside deterministic mode.
+ * ------------------------------------------------------------------------------------- */
+#define ASR_REVERB_TILE 4096
+#define ASR_REVERB_CHUNK 2048
+#define ASR_REVERB_MAX_TAPS 8192
+#define ASR_NOISE_TILE 4096
+int asr_reverb_f32(int B, int64_t max_len, const void* samples, int sample_dtype, int64_t in_count, const int64_t* offsets,
+                   const int32_t* rir_index, int n_rirs, const int64_t* geometry, const int64_t* geometry_dev,
+                   const float* bank, int64_t bank_count, float* out, int64_t out_count, asr_stream_t stream);
+int asr_noise_mix_f32(int B, int64_t max_len, const void* samples, int sample_dtype, int64_t in_count,
+                      const int64_t* offsets, const int32_t* clip_index, const int64_t* start, const float* scale, int n_clips,
+                      const int64_t* clip_offsets, const int64_t* clip_offsets_dev, const float* bank, int64_t bank_count,
+                      void* ws, int64_t ws_bytes, float* out, int64_t out_count, float* gains, asr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,11 @@ every rank draws the factors of ALL rows of the global batch, in collated order)
 takes `ilens`, `T_max` and the masks' `T_b` from the perturbed counts and uploads its own rows' raw samples with their factor
 indices and output offsets; the resampler runs on the side stream in front of the fbank.  Validation, test and align feeds
 never perturb.
+
+With `reverb` or `noise` in the front end's config a training feed also draws, for each row it uploads, an RIR, a noise clip,
+its start and an SNR (frontend.draw_augment on the row's COLLATED index, from `augment_seed`) and the two passes of
+csrc/augment.hip run on the side stream between the resampler and the fbank.  Neither changes a sample count: the sort,
+`ilens`, `T_max` and the masks are those of a feed without the keys.  Validation, test and align feeds never augment.
 """
 import queue
 import threading
@@ -128,6 +133,17 @@ def plan_speed_batch(frontend, speed_seed, batch_index, sample_counts):
     return order, [draws[i] for i in order], [counts[i] for i in order]
 
 
+def draw_feed_seeds(frontend, train):
+    """The seeds a feed with a front end takes from the process's numpy stream when it is built (the consumer's thread, so
+    identically seeded data-parallel ranks agree) -> (mask seed, speed seed, augment seed), None where the feed does not draw.
+    The order is fixed - masks, then speed, then reverb / noise - and a seed is taken only in a training feed whose front end
+    has the feature on: the streams of every other feed stay where they are."""
+    mask = int(np.random.randint(0, 2 ** 31 - 1)) if train and frontend.n_masks > 0 else None
+    speed = int(np.random.randint(0, 2 ** 31 - 1)) if train and frontend.n_speeds > 0 else None
+    augment = int(np.random.randint(0, 2 ** 31 - 1)) if train and frontend.augments else None
+    return mask, speed, augment
+
+
 class DeviceFeed(object):
     """Iterate `source` (batches of raw utterances: lists of (feature [T, D] float32, token_ids), in the collated order -
     dataloader.get_data_loader(raw=True), or any iterable of such lists) and yield `Batch`es on `device`, prepared `depth`
@@ -139,7 +155,8 @@ class DeviceFeed(object):
       thread      collate + upload in a background thread (default) or inline in next()
       frontend    a frontend.Frontend: features are 1-D waveforms and the front end runs on the side stream (GPU only)
       train       with a front end that has SpecAugment masks: draw them; with one that has `speed_perturb`: draw a speed
-                  factor per utterance and resample (training feeds only)
+                  factor per utterance and resample; with one that has `reverb` / `noise`: draw and apply them (training
+                  feeds only)
     """
 
     def __init__(self, source, device, kind="labeled", rank=0, world=1, depth=2, noise_std=0.0, thread=True, frontend=None,
@@ -151,10 +168,7 @@ class DeviceFeed(object):
                 raise RuntimeError("DeviceFeed: the front end runs on the GPU only: the HIP path has no CPU fallback")
             if float(noise_std) > 0:
                 raise ValueError("DeviceFeed: the host-side input noise needs precomputed features (noise_std with a front end)")
-            # the mask seed: from the process's numpy stream, here, like the noise seed below
-            self.mask_seed = int(np.random.randint(0, 2 ** 31 - 1)) if train and frontend.n_masks > 0 else None
-            # the speed seed: after the mask seed, and only with the feature on - the streams of every other feed stay put
-            self.speed_seed = int(np.random.randint(0, 2 ** 31 - 1)) if train and frontend.n_speeds > 0 else None
+            self.mask_seed, self.speed_seed, self.augment_seed = draw_feed_seeds(frontend, train)
         self.source, self.kind, self.rank, self.world = source, kind, int(rank), int(world)
         self.device = torch.device(device)
         self.cuda = self.device.type == "cuda"
@@ -246,9 +260,9 @@ class DeviceFeed(object):
         if speed:
             # perturbed sample count descending (stable); n_all stays the RAW count of a row, p_all is what the fbank sees
             order, f_all, p_all = plan_speed_batch(fe, self.speed_seed, self._n - 1, [int(f.shape[0]) for f, _ in items])
-            items = [items[i] for i in order]
         else:
-            items = sorted(items, key=lambda item: -int(item[0].shape[0]))   # sample count descending (stable)
+            order = sorted(range(len(items)), key=lambda i: -int(items[i][0].shape[0]))   # sample count descending (stable)
+        items = [items[i] for i in order]
         rows = parallel.shard_indices(len(items), self.rank, self.world)
         sharded = self.world > 1
         n_all = [int(f.shape[0]) for f, _ in items]
@@ -269,10 +283,14 @@ class DeviceFeed(object):
             wav_n[offs[-1]:offs[-1] + n_all[i]] = items[i][0]
             offs.append(offs[-1] + n_all[i])
         # one int64 area: offsets [B + 1] | frame counts int32 [B] (padded to a whole word) | masks int32 [B, nm, 2]; with
-        # speed perturbation behind them: output offsets [B + 1] | factor indices int32 [B] (padded to a whole word)
+        # speed perturbation behind them: output offsets [B + 1] | factor indices int32 [B] (padded to a whole word); with
+        # reverb / noise behind those: RIR indices int32 [B] | clip indices int32 [B] | scales float32 [B] (each padded to a
+        # whole word) | noise starts int64 [B]
+        augment = self.augment_seed is not None
         lw = (B + 1) // 2
         base = B + 1 + lw + B * nm
-        meta_h = slot.meta(base + (B + 1 + lw if speed else 0))
+        abase = base + (B + 1 + lw if speed else 0)
+        meta_h = slot.meta(abase + (3 * lw + B if augment else 0))
         meta_n = meta_h.numpy()
         meta_n[:B + 1] = offs
         meta_n[B + 1:] = 0
@@ -280,7 +298,14 @@ class DeviceFeed(object):
         i32[:B] = ilens
         if speed:
             meta_n[base:base + B + 1] = np.concatenate([[0], np.cumsum([p_all[i] for i in rows])])
-            meta_n[base + B + 1:].view(np.int32)[:B] = [f_all[i] for i in rows]
+            meta_n[base + B + 1:abase].view(np.int32)[:B] = [f_all[i] for i in rows]
+        if augment:
+            # a rank draws its own rows only, each by its index in the collated batch: the draw does not depend on the sort
+            draws = [fe.draw_augment(self.augment_seed, self._n - 1, order[i]) for i in rows]
+            meta_n[abase:abase + lw].view(np.int32)[:B] = [a[0] for a in draws]
+            meta_n[abase + lw:abase + 2 * lw].view(np.int32)[:B] = [a[1] for a in draws]
+            meta_n[abase + 2 * lw:abase + 3 * lw].view(np.float32)[:B] = [fe.snr_scale(a[3]) for a in draws]
+            meta_n[abase + 3 * lw:abase + 3 * lw + B] = [a[2] for a in draws]
         if nm:
             for r, i in enumerate(rows):
                 i32[2 * lw + r * nm * 2:2 * lw + (r + 1) * nm * 2] = fe.draw_masks(self.mask_seed, self._n - 1, i,
@@ -304,9 +329,14 @@ class DeviceFeed(object):
             masks_d = i32_d[2 * lw:2 * lw + B * nm * 2].view(B, nm, 2) if nm else None
             speed_d = None
             if speed:
-                speed_d = (meta_d[base + B + 1:].view(torch.int32)[:B], meta_d[base:base + B + 1],
+                speed_d = (meta_d[base + B + 1:abase].view(torch.int32)[:B], meta_d[base:base + B + 1],
                            sum(p_all[i] for i in rows), max(p_all[i] for i in rows))
-            xs_d = fe.run(wav_d, meta_d[:B + 1], i32_d[:B], t_max, masks_d, speed_d)
+            augment_d = None
+            if augment:
+                augment_d = (meta_d[abase:abase + lw].view(torch.int32)[:B], meta_d[abase + lw:abase + 2 * lw].view(torch.int32)[:B],
+                             meta_d[abase + 3 * lw:abase + 3 * lw + B], meta_d[abase + 2 * lw:abase + 3 * lw].view(torch.float32)[:B],
+                             sum(p_all[i] for i in rows), max(p_all[i] for i in rows))
+            xs_d = fe.run(wav_d, meta_d[:B + 1], i32_d[:B], t_max, masks_d, speed_d, augment_d)
             event = torch.cuda.Event()
             event.record(self._side)
         slot.event = event

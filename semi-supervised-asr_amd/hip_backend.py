@@ -35,6 +35,7 @@ EXPORTS = (
     "asr_fbank_num_frames", "asr_fbank_plan_bytes", "asr_fbank_f32", "asr_feat_cmvn_stats_f32", "asr_feat_finish_f32",
     "asr_mwer_fwd_f32", "asr_mwer_bwd_f32",
     "asr_resample_plan_bytes", "asr_resample_f32",
+    "asr_reverb_f32", "asr_noise_mix_f32",
 )
 
 _lib = None
@@ -284,6 +285,9 @@ def load():
     lib.asr_feat_finish_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p]
     lib.asr_resample_plan_bytes.argtypes = [c_i, c_p, ctypes.POINTER(c_i64)]
     lib.asr_resample_f32.argtypes = [c_i, c_i64, c_p, c_i, c_i64, c_p, c_p, c_p, c_i, c_p, c_p, c_i64, c_p, c_i64, c_p]
+    lib.asr_reverb_f32.argtypes = [c_i, c_i64, c_p, c_i, c_i64, c_p, c_p, c_i, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p]
+    lib.asr_noise_mix_f32.argtypes = [c_i, c_i64, c_p, c_i, c_i64, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p,
+                                      c_i64, c_p, c_p]
     lib.asr_mwer_fwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
     lib.asr_mwer_bwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_f, c_p, c_i64, c_p]
     lib.asr_dec_feedback_fwd.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_p, c_i64,
@@ -1353,6 +1357,194 @@ def resample(plan, samples, in_offsets, factor_index, out_offsets, out, max_out=
         raise UnsupportedShape("resample: B %d (at most 65535), %d factors" % (B, len(plan)))
     check(rc, "asr_resample_f32")
     LAUNCHES["resample"] += 1
+    return out
+
+
+# Reverberation and additive noise (csrc/augment.hip): two passes between the resampler and the fbank.
+REVERB_TILE = 4096            # ASR_REVERB_TILE: output samples per workgroup
+REVERB_CHUNK = 2048           # ASR_REVERB_CHUNK: taps staged in LDS at a time
+REVERB_MAX_TAPS = 8192        # ASR_REVERB_MAX_TAPS
+REVERB_PRE = 32               # taps kept in front of the direct path
+NOISE_TILE = 4096             # ASR_NOISE_TILE: samples per power partial
+
+
+def load_bank(bank):
+    """An `.npz` path, or a dict, with `samples` (1-D int16 / float32) and `offsets` (int64 [n + 1]) -> the list of clips."""
+    import numpy as np
+    if isinstance(bank, (str, bytes, os.PathLike)):
+        with np.load(bank) as z:
+            samples, offsets = np.asarray(z["samples"]), np.asarray(z["offsets"])
+    else:
+        samples, offsets = np.asarray(bank["samples"]), np.asarray(bank["offsets"])
+    offsets = offsets.astype(np.int64).reshape(-1)
+    if samples.ndim != 1 or samples.dtype not in (np.int16, np.float32):
+        raise ValueError("bank: `samples` must be 1-D int16 or float32, got %s %s" % (samples.dtype, samples.shape))
+    if offsets.size < 2 or offsets[0] < 0 or offsets[-1] > samples.size or (np.diff(offsets) <= 0).any():
+        raise ValueError("bank: `offsets` must be n + 1 ascending positions inside `samples`, no empty clip")
+    return [samples[a:b] for a, b in zip(offsets[:-1], offsets[1:])]
+
+
+class ReverbPlan(object):
+    """The RIR bank of asr_reverb_f32, prepared on the host (no GPU needed): every RIR's direct path d is the first index of
+    max |h|; the RIR is cut to [d - pre, d - pre + max_taps) with pre = min(d, REVERB_PRE) - a longer one is cut, not refused -
+    scaled to unit energy in float64, rounded to fp32 once and packed.  (normalize=False keeps the taps' values and a larger
+    `pre` keeps more of the head: the kernel takes any d in [0, taps); the tests use both.)  `geometry` int64 [n, 3] = (offset, taps, d after the cut), `bank` the fp32 host image; `on(device)` -> (bank,
+    geometry) on the device, copied once per device."""
+
+    def __init__(self, rirs, max_taps=4096, normalize=True, pre=REVERB_PRE):
+        import numpy as np
+        self.max_taps, keep = int(max_taps), int(pre)
+        if not 1 <= self.max_taps <= REVERB_MAX_TAPS:
+            raise UnsupportedShape("reverb: max_taps %d (1 .. %d)" % (self.max_taps, REVERB_MAX_TAPS))
+        geometry, taps, used = [], [], 0
+        for h in rirs:
+            h = np.asarray(h, dtype=np.float64).reshape(-1)
+            if h.size == 0 or not np.isfinite(h).all() or not np.abs(h).max() > 0:
+                raise ValueError("reverb: an RIR must be finite and not all zero")
+            d = int(np.argmax(np.abs(h)))                  # (argmax: the FIRST index of the maximum)
+            pre = min(d, keep)
+            h = h[d - pre:d - pre + self.max_taps]
+            if normalize:
+                h = h / np.sqrt((h * h).sum())
+            taps.append(h.astype(np.float32))
+            geometry.append((used, h.size, pre))
+            used += h.size
+        if not geometry:
+            raise ValueError("reverb: an empty RIR bank")
+        self.geometry = np.asarray(geometry, dtype=np.int64)
+        self.bank = np.concatenate(taps)
+        self._dev = {}
+
+    def __len__(self):
+        return int(self.geometry.shape[0])
+
+    def rir(self, r):
+        """-> (the fp32 taps of RIR r as the kernel reads them, d)"""
+        off, n, d = (int(v) for v in self.geometry[r])
+        return self.bank[off:off + n], d
+
+    def on(self, device):
+        key = str(torch.device(device))
+        pair = self._dev.get(key)
+        if pair is None:
+            pair = self._dev[key] = (torch.from_numpy(self.bank).to(device), torch.from_numpy(self.geometry).to(device))
+        return pair
+
+
+class NoiseBank(object):
+    """The clips of asr_noise_mix_f32, packed as fp32 with offsets (int16 clips are converted by value); `on(device)` ->
+    (bank, offsets) on the device, copied once per device."""
+
+    def __init__(self, clips):
+        import numpy as np
+        clips = [np.asarray(c).reshape(-1).astype(np.float32) for c in clips]
+        if not clips or min(c.size for c in clips) == 0:
+            raise ValueError("noise: an empty bank, or an empty clip")
+        self.offsets = np.concatenate([[0], np.cumsum([c.size for c in clips])]).astype(np.int64)
+        self.bank = np.concatenate(clips)
+        self._dev = {}
+
+    def __len__(self):
+        return int(self.offsets.size - 1)
+
+    def clip(self, c):
+        return self.bank[int(self.offsets[c]):int(self.offsets[c + 1])]
+
+    def clip_len(self, c):
+        return int(self.offsets[c + 1] - self.offsets[c])
+
+    def on(self, device):
+        key = str(torch.device(device))
+        pair = self._dev.get(key)
+        if pair is None:
+            pair = self._dev[key] = (torch.from_numpy(self.bank).to(device), torch.from_numpy(self.offsets).to(device))
+        return pair
+
+
+def _augment_args(name, samples, offsets, out):
+    if not (samples.is_cuda and offsets.is_cuda and out.is_cuda):
+        raise RuntimeError("%s: tensors must live on the GPU: the HIP path has no CPU fallback" % name)
+    if samples.dtype not in (torch.int16, torch.float32) or samples.dim() != 1 or not samples.is_contiguous():
+        raise RuntimeError("%s: samples must be one packed 1-D int16 or float32 tensor" % name)
+    B = offsets.numel() - 1
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or B < 1:
+        raise RuntimeError("%s: offsets must be int64 [B + 1]" % name)
+    if out.dtype != torch.float32 or out.dim() != 1 or not out.is_contiguous():
+        raise RuntimeError("%s: out must be one packed 1-D float32 tensor" % name)
+    return B
+
+
+def _row_index(name, index, B, n, device):
+    """A per-row index: a host sequence is checked against the bank (UnsupportedShape outside [-1, n)) and uploaded; a device
+    tensor is trusted, and the kernel clamps it."""
+    if not torch.is_tensor(index):
+        import numpy as np
+        idx = np.asarray(index, dtype=np.int64).reshape(-1)
+        if idx.size != B or (idx.size and (idx.min() < -1 or idx.max() >= n)):
+            raise UnsupportedShape("%s: indices %s for %d rows and a bank of %d" % (name, idx.tolist(), B, n))
+        index = to_device_i32(idx, device)
+    if not index.is_cuda or index.dtype != torch.int32 or index.numel() != B or not index.is_contiguous():
+        raise RuntimeError("%s: the row indices must be int32 [B] on the GPU (or a host sequence)" % name)
+    return index
+
+
+def reverb(plan, samples, offsets, rir_index, out, max_len=None):
+    """asr_reverb_f32: samples = ONE packed 1-D int16 or float32 tensor, offsets int64 [B + 1] on the device, rir_index int32
+    [B] on the device or a host sequence (-1: the row is copied by value) -> every row convolved with its RIR of `plan`,
+    undelayed, at the same offsets of `out` (ONE packed 1-D float32 tensor, not `samples`).  max_len: the longest row
+    (default: out.numel(), an upper bound)."""
+    B = _augment_args("reverb", samples, offsets, out)
+    rir_index = _row_index("reverb", rir_index, B, len(plan), out.device)
+    max_len = int(out.numel() if max_len is None else max_len)
+    if max_len <= 0:
+        return out
+    bank, geometry = plan.on(out.device)
+    rc = load().asr_reverb_f32(B, max_len, c_p(samples.data_ptr()), SAMPLES_I16 if samples.dtype == torch.int16 else SAMPLES_F32,
+                               int(samples.numel()), c_p(offsets.data_ptr()), c_p(rir_index.data_ptr()), len(plan),
+                               c_p(plan.geometry.ctypes.data), c_p(geometry.data_ptr()), c_p(bank.data_ptr()),
+                               int(bank.numel()), ptr(out), int(out.numel()), stream())
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("reverb: B %d (at most 65535), taps at most %d" % (B, REVERB_MAX_TAPS))
+    check(rc, "asr_reverb_f32")
+    LAUNCHES["reverb"] += 1
+    return out
+
+
+def noise_mix(noise_bank, samples, offsets, clip_index, start, scale, out=None, max_len=None, gains=None):
+    """asr_noise_mix_f32: row b of the packed samples + g * its clip of `noise_bank` read cyclically from start[b], g =
+    scale[b] sqrt(P_row / P_clip), scale = 10^(-snr_db / 20) from the host.  clip_index int32 [B] (-1: no clip), start int64
+    [B], scale float32 [B]: device tensors or host sequences.  out: None mixes a float32 `samples` in place; gains: None or
+    float32 [B] on the device, filled with g.  -> out."""
+    out = samples if out is None else out
+    B = _augment_args("noise_mix", samples, offsets, out)
+    dev = out.device
+    clip_index = _row_index("noise_mix", clip_index, B, len(noise_bank), dev)
+    if not torch.is_tensor(start):
+        start = to_device_i64(start, dev)
+    if not torch.is_tensor(scale):
+        scale = to_device_f32(scale, dev)
+    if (not start.is_cuda or start.dtype != torch.int64 or start.numel() != B or not start.is_contiguous()
+            or not scale.is_cuda or scale.dtype != torch.float32 or scale.numel() != B or not scale.is_contiguous()):
+        raise RuntimeError("noise_mix: start must be int64 [B] and scale float32 [B] on the GPU (or host sequences)")
+    if gains is not None and (not gains.is_cuda or gains.dtype != torch.float32 or gains.numel() != B or not gains.is_contiguous()):
+        raise RuntimeError("noise_mix: gains must be float32 [B] on the GPU")
+    if out.data_ptr() == samples.data_ptr() and samples.dtype != torch.float32:
+        raise RuntimeError("noise_mix: int16 samples cannot be mixed in place")
+    max_len = int(out.numel() if max_len is None else max_len)
+    if max_len <= 0:
+        return out
+    bank, offs_d = noise_bank.on(dev)
+    ws = torch.empty(2 * B * (-(-max_len // NOISE_TILE)), device=dev, dtype=torch.float64)
+    rc = load().asr_noise_mix_f32(B, max_len, c_p(samples.data_ptr()), SAMPLES_I16 if samples.dtype == torch.int16 else SAMPLES_F32,
+                                  int(samples.numel()), c_p(offsets.data_ptr()), c_p(clip_index.data_ptr()),
+                                  c_p(start.data_ptr()), c_p(scale.data_ptr()), len(noise_bank),
+                                  c_p(noise_bank.offsets.ctypes.data), c_p(offs_d.data_ptr()), c_p(bank.data_ptr()),
+                                  int(bank.numel()), c_p(ws.data_ptr()), int(ws.numel()) * 8, ptr(out), int(out.numel()),
+                                  c_p(gains.data_ptr()) if gains is not None else None, stream())
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("noise_mix: B %d (at most 65535)" % B)
+    check(rc, "asr_noise_mix_f32")
+    LAUNCHES["noise_mix"] += 1
     return out
 
 

@@ -18,6 +18,14 @@ With --speed two other measurements are taken instead:
               alternating windows in one process as above.  The waveforms are U[0.6, 1] x 7.2 s here, so that an utterance
               slowed to 0.9 stays inside cfg-2's 800 frames; every record carries its mean frames per batch, because a
               perturbed batch is a different amount of work.
+
+With --augment three others:
+
+  reverb      the reverb launch alone (hb.reverb) on the same cfg-2 waveform batch, EVERY row reverberated, with RIRs of 1024
+              and of 4096 taps; the achieved TFLOP/s count 2 N L flop per row (the band's 31 / L extra products not counted).
+  noise_mix   the mix alone (hb.noise_mix, its two launches) on the same batch, every row mixed, in place on float32.
+  epoch_loop_augment  the cfg-2 step fed from waveforms by training feeds WITHOUT and WITH `reverb` and `noise` at prob 0.5
+              (synthetic banks: 8 RIRs of 4096 taps, 8 clips of 1 - 4 s), alternating windows in one process as above.
 """
 import argparse
 import contextlib
@@ -153,6 +161,99 @@ def speed_lines(args, bench, hb, spec, items, samples, offs):
     return lines
 
 
+def _timed(fn, iters):
+    for _ in range(5):
+        fn()
+    torch.cuda.synchronize()
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(iters):
+        fn()
+    stop.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(stop) / iters
+
+
+def _bank(clips):
+    return dict(samples=np.concatenate(clips).astype(np.float32),
+                offsets=np.concatenate([[0], np.cumsum([len(c) for c in clips])]).astype(np.int64))
+
+
+def augment_lines(args, bench, hb, spec, items, samples, offs):
+    """--augment: the reverb launch alone at 1024 and 4096 taps, the mix alone, then the epoch loop without / with both."""
+    from feed import DeviceFeed
+    from frontend import Frontend
+    dev = samples.device
+    c, B, T = dict(spec["model"]), spec["batch"], spec["frames"]
+    rs = np.random.RandomState(1234)
+    counts = [b - a for a, b in zip(offs[:-1], offs[1:])]
+    offs_d = hb.to_device_i64(offs, dev)
+    workload = "%d ragged utterances, U[0.6, 1] x 8 s int16 at 16 kHz" % B
+    timing = "device events around %d calls (host enqueue included), samples resident" % args.iters
+    lines = []
+
+    def rirs(taps, n=8):
+        return [rs.randn(taps) * np.exp(-np.arange(taps) / (taps / 6.0)) * 0.3 + (np.arange(taps) == 20) for _ in range(n)]
+    out = torch.empty(int(samples.numel()), device=dev)
+    for taps in (1024, 4096):
+        plan = hb.ReverbPlan(rirs(taps), max_taps=taps)
+        ridx = hb.to_device_i32([b % len(plan) for b in range(B)], dev)
+        ms = _timed(lambda: hb.reverb(plan, samples, offs_d, ridx, out, max_len=max(counts)), args.iters)
+        flop = 2.0 * sum(counts) * taps
+        lines.append(dict(tool="tools/frontend_bench.py", measurement="reverb", taps=taps, workload=workload + ", every row reverberated",
+                          samples=int(samples.numel()), gpu_ms_per_launch=round(ms, 4), gflop=round(flop / 1e9, 2),
+                          tflop_per_s=round(flop / ms / 1e9, 2), timing=timing))
+    clips = [rs.randn(int(16000 * s)) * 500 for s in np.linspace(1.0, 4.0, 8)]
+    bank = hb.NoiseBank(clips)
+    wav = samples.float()
+    cidx = hb.to_device_i32([b % len(bank) for b in range(B)], dev)
+    start = hb.to_device_i64([(977 * b) % 16000 for b in range(B)], dev)
+    scale = hb.to_device_f32(np.full(B, 0.1, np.float32), dev)
+    ms = _timed(lambda: hb.noise_mix(bank, wav, offs_d, cidx, start, scale, max_len=max(counts)), args.iters)
+    moved = int(wav.numel()) * 4 * 5                        # y and v read twice, z written once
+    lines.append(dict(tool="tools/frontend_bench.py", measurement="noise_mix", workload=workload + " as float32, every row mixed, in place",
+                      samples=int(wav.numel()), gpu_ms_per_call=round(ms, 4), launches_per_call=2, bytes_moved=moved,
+                      gb_per_s=round(moved / ms / 1e6, 1), timing=timing))
+    if args.skip_epoch_loop:
+        return lines
+    tmp = tempfile.mkdtemp(prefix="frontend_bench_")
+    sv = bench.make_solver(c, B, T, os.path.join(tmp, "cfg2"))
+    base = dict(n_mels=80, delta_order=0, cmvn="utterance")
+    keys = dict(reverb=dict(bank=_bank(rirs(4096)), prob=0.5, max_taps=4096), noise=dict(bank=_bank(clips), prob=0.5, snr_db=[5, 20]))
+    fes = {"plain": Frontend(base), "augment": Frontend(dict(base, **keys))}
+    n = args.warmup + args.steps
+
+    def window(kind):
+        feed = DeviceFeed([items] * n, dev, frontend=fes[kind], train=True)
+        with contextlib.redirect_stdout(sys.stderr):
+            for i, (xs, ilens, ys) in enumerate(feed):
+                if i == args.warmup:
+                    sv.flush()
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                last = sv.sup_train_one_iteration(xs, ilens, ys, 1.0)
+            sv.flush()
+            torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.steps * 1e3, float(last)
+    windows, loss = {k: [] for k in fes}, {}
+    np.random.seed(1234)                                  # the feeds' augment seeds
+    for _ in range(args.rounds):
+        for kind in fes:
+            ms, loss[kind] = window(kind)
+            windows[kind].append(ms)
+    med = {k: statistics.median(w) for k, w in windows.items()}
+    for kind in fes:
+        lines.append(dict(tool="tools/frontend_bench.py", measurement="epoch_loop_augment", feed=kind,
+                          call="Solver.sup_train_one_iteration",
+                          workload="%s, batch %d, waveforms U[0.6, 1] x 8 s, training feed.DeviceFeed" % (spec["name"], B),
+                          augment="reverb 8 x 4096 taps prob 0.5, noise 8 clips prob 0.5 snr_db [5, 20]" if kind == "augment" else None,
+                          rounds=args.rounds, steps_per_window=args.steps, warmup_steps=args.warmup,
+                          ms_per_step=round(med[kind], 3), windows_ms=[round(w, 3) for w in windows[kind]],
+                          spread=round((max(windows[kind]) - min(windows[kind])) / med[kind], 4),
+                          over_plain=round(med[kind] / med["plain"], 4), last_loss=loss[kind], arith=hb.arith_name()))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
@@ -161,6 +262,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--skip-epoch-loop", action="store_true")
     ap.add_argument("--speed", action="store_true", help="measure speed perturbation instead (resample, epoch_loop_speed)")
+    ap.add_argument("--augment", action="store_true",
+                    help="measure reverberation and noise instead (reverb, noise_mix, epoch_loop_augment)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frontend_bench.jsonl"))
     args = ap.parse_args()
     import __graft_entry__ as entry
@@ -184,7 +287,9 @@ def main():
 
     if args.speed:
         lines = speed_lines(args, bench, hb, spec, items, samples, offs)
-    for order in (() if args.speed else (0, 2)):
+    if args.augment:
+        lines = augment_lines(args, bench, hb, spec, items, samples, offs)
+    for order in (() if args.speed or args.augment else (0, 2)):
         fe = Frontend(dict(n_mels=80, delta_order=order, cmvn="utterance"))
         for _ in range(5):
             xs, ilens = fe(samples, offs)
@@ -207,7 +312,7 @@ def main():
                           timing="device events around %d calls (host enqueue included), samples resident" % args.iters,
                           cpu_torch_ms_per_batch=round(cpu_ms, 2), cpu_threads=threads, cpu_over_gpu=round(cpu_ms / gpu_ms, 1)))
 
-    if not args.skip_epoch_loop and not args.speed:
+    if not args.skip_epoch_loop and not args.speed and not args.augment:
         tmp = tempfile.mkdtemp(prefix="frontend_bench_")
         fe = Frontend(dict(n_mels=80, delta_order=0, cmvn="utterance"))
         assert fe.output_dim == c["input_dim"]
