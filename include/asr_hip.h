@@ -1042,6 +1042,48 @@ int asr_ctc_beam_f32(int B, int T, int V, int K, const float* logits, int64_t ld
                      int32_t* hyp_len, float* score, void* ws, asr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * A backoff n-gram LM on the device (csrc/ngram.hip, csrc/ctc_beam.hip).  Not reference operators.  Two entries
+ * added to ABI version 8 WITHOUT a version change, like the other additive groups: callers pin the number.
+ * The LM arrives compiled (ngram.py, NgramLM.compile): a deterministic automaton over S states with every backoff resolved,
+ *     lm_logp  fp32  [S][V]  ln p(c | state); column 0 (the CTC blank) holds 0 and is never read; every value is finite
+ *     lm_next  int32 [S][V]  the state after c, in 0 .. S-1
+ *     lm_start               the state of the context <s>
+ * S V <= INT_MAX, lm_start in 0 .. S-1: ASR_E_SHAPE otherwise.  The CONTENTS of the table are trusted - the host validates them
+ * when it compiles the model - so a successor outside 0 .. S-1 is the caller's error.
+ *
+ *   asr_ngram_score_f32   N padded id sequences ids int32 [N][ld >= L] with lens int32 [N] (clamped to L; < 0: an unused slot,
+ *       score -inf) -> score fp32 [N]: the sum over the tokens IN ORDER of lm_logp[state][id], state walking the automaton
+ *       from lm_start, plus lm_logp[state][eos] behind the last token when eos >= 0 (eos < 0: no end term; eos >= V:
+ *       ASR_E_SHAPE) - an fp32 sum, one thread per sequence.  tok_score fp32 [N][L] or NULL: the term of every token, 0
+ *       behind the sequence.  An id outside 0 .. V-1 inside the length makes that sequence's score (and its tok_score from
+ *       there to the length) NaN; nothing is indexed with it.  One launch, no atomics: the same bits in every run.
+ *
+ *   asr_ctc_beam_lm_f32   asr_ctc_beam_f32 with the LM inside the search.  An entry of the beam additionally carries its
+ *       automaton state and lm, the fp32 sum of lm_logp[state][c] over its tokens in order (functions of the token sequence:
+ *       equal prefixes hold equal bits, prefix identity and the merge are unchanged).  pb, pnb and tot stay the CTC masses of
+ *       asr_ctc_beam_f32, operation for operation.  Every candidate ranks by
+ *           rank = (tot' + alpha lm') + beta len'        fp32, each of the four operations rounded on its own (no fma)
+ *       - the stay candidate with the entry's lm and len, an extension by c with lm + lm_logp[state][c] and len + 1.  Candidate
+ *       order and tie rule are asr_ctc_beam_f32's.  After the last frame, with lm_eos >= 0, lm += lm_logp[state][lm_eos], the
+ *       rank is formed again from (tot, lm, len) and the entries are ranked once more, ties to the search's order.  Outputs:
+ *           hyp, hyp_len   as asr_ctc_beam_f32
+ *           score      fp32 [B][K]  the rank, descending; -inf in an unused slot
+ *           ctc_score  fp32 [B][K]  tot;  -inf in an unused slot
+ *           lm_score   fp32 [B][K]  lm, the end term included when it is on;  -inf in an unused slot
+ *       An utterance of no frames gets the empty hypothesis in slot 0 (ctc_score 0, lm_score the end term or 0).  With
+ *       alpha = beta = 0 and no end term, hyp, hyp_len and ctc_score are asr_ctc_beam_f32's bits.  alpha and beta must be
+ *       finite (ASR_E_ARG).  The workspace, the launches (two), the limits on K and V and the LDS history are those of
+ *       asr_ctc_beam_f32 (asr_ctc_beam_ws_bytes); the LM rows are read through L2 where a candidate is formed, so memory
+ *       does not depend on the LM's order.  No atomics, no host synchronisation, no allocation.
+ * ------------------------------------------------------------------------------------- */
+int asr_ngram_score_f32(int N, int L, int S, int V, const float* lm_logp, const int32_t* lm_next, int lm_start, int eos,
+                        const int32_t* ids, int64_t ld, const int32_t* lens, float* score, float* tok_score, asr_stream_t stream);
+int asr_ctc_beam_lm_f32(int B, int T, int V, int K, const float* logits, int64_t ld, const int32_t* frame_lens, int S,
+                        const float* lm_logp, const int32_t* lm_next, int lm_start, int lm_eos, float alpha, float beta,
+                        int32_t* hyp, int32_t* hyp_len, float* score, float* ctc_score, float* lm_score, void* ws,
+                        asr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * The front end (csrc/frontend.hip): packed waveforms -> the [B][T][D] features the encoder reads.  Not
  * reference operators - the reference reads features that Kaldi computed.  Five entries added to ABI version 8 WITHOUT a
  * version change: additive.

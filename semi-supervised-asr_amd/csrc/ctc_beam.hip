@@ -17,6 +17,15 @@
 //                         to LDS at its end; a token behind kStage * threads is read from memory where it is used.
 //                         After the last frame the beam IS the ranking (the select's order); thread r walks the history back
 //                         into hyp[r].
+//   ctc_beam_kernel<M, true>   the search with an n-gram LM inside (the table is ngram.hip's): an entry also
+//                         carries its automaton state and lm, the fp32 sum of logp[state][c] over its tokens in order - both
+//                         functions of the token sequence, so equal prefixes hold equal bits and the merge is unchanged.  The
+//                         masses pb / pnb / tot are the plain kernel's, operation for operation; only the value a candidate
+//                         is ranked by differs (lm_rank).  The LM row of an entry is read through L2 where it is used: one
+//                         coalesced read per (entry, token), beside the emission's.  The list holds ranks, so update forms
+//                         the winner's mass again (the same operations on the same operands: the same bits).  After the last
+//                         frame the end-of-sentence term joins lm and the (at most K) entries are ranked once more.
+#include <float.h>
 #include "seq_common.h"
 
 namespace {
@@ -27,7 +36,11 @@ constexpr int kMaxThreads = 256;
 constexpr int kOneWaveKV = ASR_CTC_BEAM_ONE_WAVE_KV;       // K V up to this: one wave per utterance
 constexpr int kHistLds = ASR_CTC_BEAM_LDS_ENTRIES;         // (frame, slot) history entries that stay in LDS
 static_assert(kKmax <= 32, "the merge map of an entry is one 32-bit mask");
+// (2048: the beam's two slots, the candidates' and the reduction's arrays - with the LM's state, lm, stay mass, rank and
+// position of every entry 1664 bytes at kKmax = 16)
 static_assert(kHistLds * 8 + kStage * kMaxThreads * 4 + 2048 <= 64 * 1024, "the static LDS of a workgroup");
+static_assert((3 * 2 + 2 * 2 + 2 * 2 + 1 + 2 + 2 * 2 + 1 + 1 + 1 + 1) * 4 * kKmax + 2 * 2 * (kMaxThreads / 64) * 4 <= 2048,
+              "the beam's arrays, the LM's included, inside the 2048 bytes above");
 
 typedef unsigned long long u64;
 
@@ -63,11 +76,29 @@ __device__ __forceinline__ u64 prefix_hash(u64 h, int c) {
   return h ^ (h >> 31);
 }
 
-template <int M>
+// the LM of a fused search (LM = true; all zero otherwise and never read)
+struct BeamLm {
+  const float* logp;       // [S][V]
+  const int32_t* next;     // [S][V]
+  float* ctc_score;        // [B][K]
+  float* lm_score;         // [B][K]
+  int start, eos;          // eos < 0: no end-of-sentence term
+  float alpha, beta;
+};
+
+// what a candidate of the fused search is ranked by: (tot + alpha lm) + beta len, fp32, every operation rounded on its own
+// (no contraction into an fma) - tests/ngram_ref.py restates exactly this
+__device__ __forceinline__ float lm_rank(float tot, float lm, int len, float alpha, float beta) {
+  return __fadd_rn(__fadd_rn(tot, __fmul_rn(alpha, lm)), __fmul_rn(beta, (float)len));
+}
+
+template <int M, bool LM>
 __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int K, const float* __restrict__ z, int64_t ld,
                                                                const int32_t* __restrict__ lens, int32_t* __restrict__ hyp,
                                                                int32_t* __restrict__ hyp_len, float* __restrict__ score,
-                                                               BeamWs w) {
+                                                               BeamWs w, BeamLm g) {
+  __shared__ int s_state[2][kKmax], s_pos[kKmax];            // (LM only, like the next line: unused arrays take no LDS)
+  __shared__ float s_lm[2][kKmax], s_stot[kKmax], s_rank[kKmax];
   __shared__ float s_pb[2][kKmax], s_pnb[2][kKmax], s_tot[2][kKmax];
   __shared__ int s_last[2][kKmax], s_len[2][kKmax];
   __shared__ u64 s_hash[2][kKmax];
@@ -84,7 +115,14 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
   if (len == 0) {                                            // no frames: the empty hypothesis at score 0
     for (int64_t i = tid; i < (int64_t)K * T; i += nt) hypb[i] = -1;
     if (tid < K) {
-      score[(int64_t)b * K + tid] = tid == 0 ? 0.f : -INFINITY;
+      if constexpr (LM) {
+        const float lm0 = g.eos >= 0 ? g.logp[(int64_t)g.start * V + g.eos] : 0.f;
+        score[(int64_t)b * K + tid] = tid == 0 ? lm_rank(0.f, lm0, 0, g.alpha, g.beta) : -INFINITY;
+        g.ctc_score[(int64_t)b * K + tid] = tid == 0 ? 0.f : -INFINITY;
+        g.lm_score[(int64_t)b * K + tid] = tid == 0 ? lm0 : -INFINITY;
+      } else {
+        score[(int64_t)b * K + tid] = tid == 0 ? 0.f : -INFINITY;
+      }
       hyp_len[(int64_t)b * K + tid] = tid == 0 ? 0 : -1;
     }
     return;
@@ -100,6 +138,10 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
     s_last[0][tid] = -1;
     s_len[0][tid] = 0;
     s_hash[0][tid] = 0;
+    if constexpr (LM) {
+      s_state[0][tid] = g.start;
+      s_lm[0][tid] = 0.f;
+    }
   }
   float zn[kStage];
   float ln = lse[0];
@@ -153,7 +195,13 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
           npnb = logaddexp(npnb, (s_last[p][i] == cj ? s_pb[p][i] : s_tot[p][i]) + xj);
       s_spb[tid] = npb;
       s_spnb[tid] = npnb;
-      top_insert(lv, li, logaddexp(npb, npnb), tid);
+      if constexpr (LM) {
+        const float st = logaddexp(npb, npnb);
+        s_stot[tid] = st;
+        top_insert(lv, li, lm_rank(st, s_lm[p][tid], lj, g.alpha, g.beta), tid);
+      } else {
+        top_insert(lv, li, logaddexp(npb, npnb), tid);
+      }
     }
     // the extensions, entry-major
     for (int k = 0; k < nlive; ++k) {
@@ -161,12 +209,21 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
       const float pbk = s_pb[p][k], totk = s_tot[p][k];
       const unsigned mkk = s_mk[k];
       const int base = K + k * (V - 1) - 1;
+      float lmk = 0.f;
+      const float* lrow = nullptr;
+      int lenk1 = 0;
+      if constexpr (LM) {
+        lmk = s_lm[p][k];
+        lrow = g.logp + (int64_t)s_state[p][k] * V;
+        lenk1 = s_len[p][k] + 1;
+      }
       for (int c = tid; c < V; c += nt) {
         if (c == 0) continue;
         const float xc = c < nstage ? xs[c] : zr[c] - lcur;
         float val = (c == ck ? pbk : totk) + xc;
         for (unsigned m = mkk; m; m &= m - 1)                // prefix_k . c is in the beam: not a candidate of its own
           if (s_last[p][__ffs(m) - 1] == c) val = -INFINITY;
+        if constexpr (LM) val = lm_rank(val, lmk + lrow[c], lenk1, g.alpha, g.beta);       // (-inf stays -inf: lm is finite)
         top_insert(lv, li, val, base + c);
       }
     }
@@ -231,21 +288,37 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
           s_last[q][tid] = s_last[p][k];
           s_len[q][tid] = s_len[p][k];
           s_hash[q][tid] = s_hash[p][k];
+          if constexpr (LM) {
+            s_tot[q][tid] = s_stot[k];
+            s_lm[q][tid] = s_lm[p][k];
+            s_state[q][tid] = s_state[p][k];
+          }
         } else {
           const int e = my_i - K;
           k = e / (V - 1), tok = e - k * (V - 1) + 1;
           s_pb[q][tid] = -INFINITY;
-          s_pnb[q][tid] = my_v;
+          if constexpr (LM) {                                    // my_v is a rank: the candidate's mass once more
+            const float xc = tok < nstage ? xs[tok] : zr[tok] - lcur;
+            const float mass = (tok == s_last[p][k] ? s_pb[p][k] : s_tot[p][k]) + xc;
+            const int64_t at = (int64_t)s_state[p][k] * V + tok;
+            s_pnb[q][tid] = mass;
+            s_tot[q][tid] = mass;
+            s_lm[q][tid] = s_lm[p][k] + g.logp[at];
+            s_state[q][tid] = g.next[at];
+          } else {
+            s_pnb[q][tid] = my_v;
+          }
           s_last[q][tid] = tok;
           s_len[q][tid] = s_len[p][k] + 1;
           s_hash[q][tid] = prefix_hash(s_hash[p][k], tok);
         }
-        s_tot[q][tid] = my_v;
+        if constexpr (!LM) s_tot[q][tid] = my_v;
         hist[(int64_t)t * K + tid] = make_int2(k, tok);
       } else {
         s_tot[q][tid] = -INFINITY;
       }
     }
+    if constexpr (LM) __syncthreads();                         // update has read xs
     if (t + 1 < len) {
 #pragma unroll
       for (int i = 0; i < kStage; ++i) xs[tid + i * nt] = zn[i] - ln;
@@ -253,6 +326,49 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
     __syncthreads();
     p = q;
     nlive = nsel;
+  }
+  if constexpr (LM) {
+    // the end-of-sentence term joins lm; the entries rank by lm_rank once more, ties to the search's order (without the term
+    // every rank is the select's and the order stays); thread r walks the history of entry r back into the row of its rank
+    if (tid < nlive) {
+      float lm = s_lm[p][tid];
+      if (g.eos >= 0) lm += g.logp[(int64_t)s_state[p][tid] * V + g.eos];
+      s_lm[p][tid] = lm;
+      s_rank[tid] = lm_rank(s_tot[p][tid], lm, s_len[p][tid], g.alpha, g.beta);
+    }
+    __syncthreads();
+    if (tid < K) {
+      int at = tid;
+      if (tid < nlive) {
+        const float rv = s_rank[tid];
+        at = 0;
+        for (int j = 0; j < nlive; ++j) at += j != tid && better(s_rank[j], j, rv, tid) ? 1 : 0;
+        int32_t* row = hypb + (int64_t)at * T;
+        const int n = s_len[p][tid];
+        int pos = n - 1, slot = tid;
+        for (int t = len - 1; t >= 0; --t) {
+          const int2 e = hist[(int64_t)t * K + slot];
+          if (e.y != 0 && pos >= 0) row[pos--] = e.y;
+          slot = e.x;
+        }
+        score[(int64_t)b * K + at] = rv;
+        g.ctc_score[(int64_t)b * K + at] = s_tot[p][tid];
+        g.lm_score[(int64_t)b * K + at] = s_lm[p][tid];
+        hyp_len[(int64_t)b * K + at] = n;
+      } else {
+        score[(int64_t)b * K + tid] = -INFINITY;
+        g.ctc_score[(int64_t)b * K + tid] = -INFINITY;
+        g.lm_score[(int64_t)b * K + tid] = -INFINITY;
+        hyp_len[(int64_t)b * K + tid] = -1;
+      }
+      s_pos[tid] = at;
+    }
+    __syncthreads();
+    for (int r = 0; r < K; ++r) {
+      const int n = r < nlive ? s_len[p][r] : 0;
+      for (int i = n + tid; i < T; i += nt) hypb[(int64_t)s_pos[r] * T + i] = -1;
+    }
+    return;
   }
   // the beam is the ranking; thread r walks the history of entry r back into its row
   if (tid < K) {
@@ -285,6 +401,20 @@ int beam_check(int B, int T, int V, int K) {
   return 0;
 }
 
+template <bool LM>
+void launch_ctc_beam(int B, int T, int V, int K, const float* logits, int64_t ld, const int32_t* frame_lens, int32_t* hyp,
+                     int32_t* hyp_len, float* score, const BeamWs& w, const BeamLm& g, hipStream_t stream) {
+  const dim3 grid(B), block((int64_t)K * V <= kOneWaveKV ? 64 : kMaxThreads);
+#define CTC_BEAM(M_) \
+  hipLaunchKernelGGL((ctc_beam_kernel<M_, LM>), grid, block, 0, stream, T, V, K, logits, ld, frame_lens, hyp, hyp_len, score, w, g)
+  if (K <= 1) CTC_BEAM(1);
+  else if (K <= 2) CTC_BEAM(2);
+  else if (K <= 4) CTC_BEAM(4);
+  else if (K <= 8) CTC_BEAM(8);
+  else CTC_BEAM(16);
+#undef CTC_BEAM
+}
+
 }  // namespace
 
 extern "C" int asr_ctc_beam_ws_bytes(int B, int T, int V, int K, int64_t* ws_bytes) {
@@ -304,16 +434,29 @@ extern "C" int asr_ctc_beam_f32(int B, int T, int V, int K, const float* logits,
   const BeamWs w = beam_ws(ws, B, T, K);
   launch_frame_lse(B, T, V, logits, ld, frame_lens, w.lse, (hipStream_t)stream);
   ASR_CHECK_LAUNCH();
-  const dim3 grid(B), block((int64_t)K * V <= kOneWaveKV ? 64 : kMaxThreads);
-#define CTC_BEAM(M_) \
-  hipLaunchKernelGGL((ctc_beam_kernel<M_>), grid, block, 0, (hipStream_t)stream, T, V, K, logits, ld, frame_lens, hyp, hyp_len, \
-                     score, w)
-  if (K <= 1) CTC_BEAM(1);
-  else if (K <= 2) CTC_BEAM(2);
-  else if (K <= 4) CTC_BEAM(4);
-  else if (K <= 8) CTC_BEAM(8);
-  else CTC_BEAM(16);
-#undef CTC_BEAM
+  launch_ctc_beam<false>(B, T, V, K, logits, ld, frame_lens, hyp, hyp_len, score, w, BeamLm{}, (hipStream_t)stream);
+  ASR_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int asr_ctc_beam_lm_f32(int B, int T, int V, int K, const float* logits, int64_t ld, const int32_t* frame_lens, int S,
+                                   const float* lm_logp, const int32_t* lm_next, int lm_start, int lm_eos, float alpha, float beta,
+                                   int32_t* hyp, int32_t* hyp_len, float* score, float* ctc_score, float* lm_score, void* ws,
+                                   asr_stream_t stream) {
+  if (!logits || !frame_lens || !hyp || !hyp_len || !score || !ws || ld < V || !lm_logp || !lm_next || !ctc_score || !lm_score ||
+      S <= 0 || !(fabsf(alpha) <= FLT_MAX) || !(fabsf(beta) <= FLT_MAX))
+    return ASR_E_ARG;
+  const int rc = beam_check(B, T, V, K);
+  if (rc) return rc;
+  if ((int64_t)S * V > INT_MAX || lm_start < 0 || lm_start >= S || lm_eos >= V) return ASR_E_SHAPE;
+  if ((((uintptr_t)ws) & 7u) != 0) return ASR_E_ALIGN;
+  const BeamWs w = beam_ws(ws, B, T, K);
+  launch_frame_lse(B, T, V, logits, ld, frame_lens, w.lse, (hipStream_t)stream);
+  ASR_CHECK_LAUNCH();
+  BeamLm g;
+  g.logp = lm_logp, g.next = lm_next, g.ctc_score = ctc_score, g.lm_score = lm_score;
+  g.start = lm_start, g.eos = lm_eos < 0 ? -1 : lm_eos, g.alpha = alpha, g.beta = beta;
+  launch_ctc_beam<true>(B, T, V, K, logits, ld, frame_lens, hyp, hyp_len, score, w, g, (hipStream_t)stream);
   ASR_CHECK_LAUNCH();
   return 0;
 }

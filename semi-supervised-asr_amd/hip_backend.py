@@ -31,7 +31,7 @@ EXPORTS = (
     "asr_ctc_ws_bytes", "asr_ctc_loss_fwd", "asr_ctc_loss_bwd",
     "asr_ctc_prefix_init_f32", "asr_ctc_prefix_score_f32", "asr_beam_select_ctc_f32", "asr_ctc_prefix_advance_f32",
     "asr_ctc_align_ws_bytes", "asr_ctc_align_f32", "asr_ctc_greedy_f32",
-    "asr_ctc_beam_ws_bytes", "asr_ctc_beam_f32",
+    "asr_ctc_beam_ws_bytes", "asr_ctc_beam_f32", "asr_ctc_beam_lm_f32", "asr_ngram_score_f32",
     "asr_fbank_num_frames", "asr_fbank_plan_bytes", "asr_fbank_f32", "asr_feat_cmvn_stats_f32", "asr_feat_finish_f32",
     "asr_mwer_fwd_f32", "asr_mwer_bwd_f32",
     "asr_resample_plan_bytes", "asr_resample_f32",
@@ -278,6 +278,9 @@ def load():
     lib.asr_ctc_greedy_f32.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]
     lib.asr_ctc_beam_ws_bytes.argtypes = [c_i, c_i, c_i, c_i, ctypes.POINTER(c_i64)]
     lib.asr_ctc_beam_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p]
+    lib.asr_ctc_beam_lm_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_i, c_p, c_p, c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_p, c_p,
+                                        c_p, c_p]
+    lib.asr_ngram_score_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p]
     lib.asr_fbank_num_frames.argtypes = [c_i64, c_i, c_i, ctypes.POINTER(c_i64)]
     lib.asr_fbank_plan_bytes.argtypes = [c_i, ctypes.POINTER(c_i64)]
     lib.asr_fbank_f32.argtypes = [c_i, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_i64, c_i64, c_p]
@@ -1088,6 +1091,66 @@ def ctc_beam(logits, frame_lens, K, hyp, hyp_len, score, ws):
     check(rc, "asr_ctc_beam_f32")
     LAUNCHES["ctc_beam"] += 1
     LAUNCHES["ctc_beam_launch"] += 2
+
+
+def _ngram_table(table, V, what):
+    """The device form of an n-gram LM (ngram.NgramTable after .to(device)): logp fp32 [S, V], nxt int32 [S, V], contiguous."""
+    logp, nxt = table.logp, table.nxt
+    if not (isinstance(logp, torch.Tensor) and logp.is_cuda and nxt.is_cuda):
+        raise RuntimeError("%s: the n-gram table is not on the device (NgramLM.to(device))" % what)
+    if logp.dtype != torch.float32 or nxt.dtype != torch.int32 or logp.shape != nxt.shape or logp.dim() != 2 or \
+            not (logp.is_contiguous() and nxt.is_contiguous()):
+        raise RuntimeError("%s: the n-gram table must be contiguous fp32 / int32 [S, V]" % what)
+    if logp.shape[1] != V:
+        raise UnsupportedShape("%s: the n-gram LM predicts %d tokens, the sequences are over %d" % (what, logp.shape[1], V))
+    return logp, nxt, int(logp.shape[0])
+
+
+def ngram_score(table, ids, lens, score, tok_score=None, eos_term=True):
+    """asr_ngram_score_f32 (csrc/ngram.hip): the n-gram LM's log-probability of N padded id sequences.  table:
+    the LM on the device; ids int32 [N, L] (a view with row stride >= L is taken as it is), lens int32 [N] (-1: an unused
+    slot, -inf), both on the device; score fp32 [N] and tok_score (fp32 [N, L] or None) are the caller's.  One launch."""
+    if ids.dim() != 2 or ids.dtype != torch.int32 or ids.stride(1) != 1 or lens.dtype != torch.int32:
+        raise RuntimeError("ngram_score: ids must be int32 [N, L] with unit column stride, lens int32")
+    N, L = ids.shape
+    logp, nxt, S = _ngram_table(table, table.V, "ngram_score")
+    if lens.numel() != N or score.numel() != N or not (lens.is_contiguous() and score.is_contiguous()) or \
+            score.dtype != torch.float32:
+        raise RuntimeError("ngram_score: lens and score must be contiguous with %d elements" % N)
+    if tok_score is not None and (tuple(tok_score.shape) != (N, L) or not tok_score.is_contiguous() or
+                                  tok_score.dtype != torch.float32):
+        raise RuntimeError("ngram_score: tok_score must be contiguous fp32 [%d, %d]" % (N, L))
+    rc = load().asr_ngram_score_f32(N, L, S, table.V, ptr(logp), ptr(nxt), int(table.start), int(table.eos) if eos_term else -1,
+                                    ptr(ids), int(ids.stride(0)), ptr(lens), ptr(score),
+                                    ptr(tok_score) if tok_score is not None else None, stream())
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("ngram_score: %d states x %d tokens, start %d, eos %d" % (S, table.V, table.start, table.eos))
+    check(rc, "asr_ngram_score_f32")
+    LAUNCHES["ngram_score"] += 1
+
+
+def ctc_beam_lm(logits, frame_lens, K, table, alpha, beta, eos_term, hyp, hyp_len, score, ctc_score, lm_score, ws):
+    """asr_ctc_beam_lm_f32 (csrc/ctc_beam.hip): ctc_beam with the n-gram LM `table` (on the device) inside the
+    search - candidates rank by (tot + alpha lm) + beta len.  The arguments and outputs of ctc_beam, and ctc_score / lm_score
+    fp32 [B, K]: the CTC log-mass and the LM's sum (with the end term when eos_term) of every hypothesis; score is the
+    rank.  Two launches."""
+    logits, ld = _ctc_view(logits, "ctc logits")
+    B, T, V = logits.shape
+    logp, nxt, S = _ngram_table(table, V, "ctc_beam_lm")
+    need = ctc_beam_ws_bytes(B, T, V, K)
+    outs = (hyp_len, score, ctc_score, lm_score)
+    if ws.numel() * 4 < need or tuple(hyp.shape) != (B, K, T) or any(o.numel() != B * K for o in outs):
+        raise RuntimeError("ctc_beam_lm: the workspace or an output is smaller than B %d, T %d, beam %d need" % (B, T, K))
+    if not (hyp.is_contiguous() and all(o.is_contiguous() for o in outs)):
+        raise RuntimeError("ctc_beam_lm: the outputs must be contiguous")
+    rc = load().asr_ctc_beam_lm_f32(B, T, V, int(K), ptr(logits), int(ld), ptr(frame_lens), S, ptr(logp), ptr(nxt),
+                                    int(table.start), int(table.eos) if eos_term else -1, float(alpha), float(beta), ptr(hyp),
+                                    ptr(hyp_len), ptr(score), ptr(ctc_score), ptr(lm_score), ptr(ws), stream())
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("ctc_beam_lm: %d states x %d tokens, start %d, eos %d" % (S, V, table.start, table.eos))
+    check(rc, "asr_ctc_beam_lm_f32")
+    LAUNCHES["ctc_beam_lm"] += 1
+    LAUNCHES["ctc_beam_lm_launch"] += 2
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -542,21 +542,46 @@ class Decoder(torch.nn.Module):
         if (lm.bos, lm.eos) != (self.bos, self.eos):
             raise ValueError("the LM's <BOS>/<EOS> (%d, %d) are not the decoder's (%d, %d)" % (lm.bos, lm.eos, self.bos, self.eos))
 
+    def check_ngram(self, ngram):
+        """ValueError unless ngram (an ngram.NgramLM, or None) is over the decoder's vocabulary with its <BOS> / <EOS>, and
+        <PAD> = 0 is free to be the CTC blank."""
+        if ngram is None:
+            return
+        V = self.output_layer.weight.shape[0]
+        if ngram.V != V:
+            raise ValueError("the n-gram LM predicts %d tokens, the decoder %d" % (ngram.V, V))
+        if (ngram.bos, ngram.eos) != (self.bos, self.eos):
+            raise ValueError("the n-gram LM's <BOS>/<EOS> (%d, %d) are not the decoder's (%d, %d)"
+                             % (ngram.bos, ngram.eos, self.bos, self.eos))
+        if self.pad != 0:
+            raise ValueError("the n-gram LM keeps id 0 for the CTC blank; pad is %d" % self.pad)
+
     def rescore_ctc_beams(self, enc_pad, enc_len, ctc_logits, ctc_lens, topk, ctc_weight=0.5, length_penalty=0.0, *, lm=None,
-                          lm_weight=0.0):
+                          lm_weight=0.0, ngram=None, ngram_weight=0.0, ngram_bonus=0.0):
         """Two-pass decoding behind the encoder (E2E.recognize_two_pass): ops.ctc_beam over ctc_logits [B, T', V]
         (raw logits of a CTC head on enc_pad, blank = <PAD> = 0; ctc_lens int32 [B] on the device), score_hypotheses over
         the B topk rows, with lm and lm_weight != 0 LM.forward over the same rows, then the combination
         ((1 - w) att + w ctc + lm_weight lm) / (len + 1)**length_penalty and the ranking, ties to the search's order.
         -> (tokens int64 [B, topk, T' + 1] ranked and <EOS>-padded, scores [B, topk] with -inf in unused slots, the parts:
-        dict(hyp, hyp_len, ctc, att, lm, order)).  No host read."""
+        dict(hyp, hyp_len, ctc, att, lm, order)).  No host read.
+        With ngram (an ngram.NgramLM) the first pass is the fused search - ops.ctc_beam with the LM inside,
+        ranking by (ctc + ngram_weight lm_ngram) + ngram_bonus len, the end-of-sentence term on - and the combination is
+        ((1 - w) att + w ctc + lm_weight lm + ngram_weight lm_ngram + ngram_bonus len) / (len + 1)**length_penalty, ctc
+        the search's ctc_score and lm_ngram its lm_score; the parts then also hold ngram (lm_ngram) and rank (the search's
+        score)."""
         K, w = int(topk), float(ctc_weight)
         if self.pad != 0:
             raise ValueError("the CTC search takes <PAD> = 0 as its blank; pad is %d" % self.pad)
         self.check_lm(lm)
+        self.check_ngram(ngram)
         use_lm = lm is not None and float(lm_weight) != 0.0
         with torch.no_grad():
-            hyp, hyp_len, ctc = ops.ctc_beam(ctc_logits, ctc_lens, K)
+            ng = rank = None
+            if ngram is None:
+                hyp, hyp_len, ctc = ops.ctc_beam(ctc_logits, ctc_lens, K)
+            else:
+                hyp, hyp_len, rank, ctc, ng = ops.ctc_beam(ctc_logits, ctc_lens, K, ngram=ngram, ngram_weight=ngram_weight,
+                                                           ngram_bonus=ngram_bonus, eos_term=True)
             bsz, _, T = hyp.shape
             att, tok_out, mask = self.score_hypotheses(enc_pad, enc_len, hyp, hyp_len)
             lm_score = None
@@ -573,13 +598,19 @@ class Decoder(torch.nn.Module):
             total = att * float(1.0 - w_t) + ctc * float(w_t)
             if use_lm:
                 total = total + lm_score * float(torch.tensor(float(lm_weight), dtype=torch.float32))
+            if ngram is not None:
+                total = total + ng * float(torch.tensor(float(ngram_weight), dtype=torch.float32))
+                total = total + hyp_len.clamp(min=0).to(torch.float32) * float(torch.tensor(float(ngram_bonus), dtype=torch.float32))
             if float(length_penalty) != 0.0:
                 total = total / (hyp_len.clamp(min=0) + 1).to(torch.float32).pow(float(length_penalty))
             total = torch.where(hyp_len >= 0, total, torch.full_like(total, float("-inf")))
             order = torch.sort(total, dim=1, descending=True, stable=True).indices                # ties to the lower k
             scores = torch.gather(total, 1, order)
             tokens = torch.gather(tok_out.view(bsz, K, T + 1), 1, order.unsqueeze(2).expand(bsz, K, T + 1))
-        return tokens, scores, dict(hyp=hyp, hyp_len=hyp_len, ctc=ctc, att=att, lm=lm_score, order=order)
+        parts = dict(hyp=hyp, hyp_len=hyp_len, ctc=ctc, att=att, lm=lm_score, order=order)
+        if ngram is not None:
+            parts.update(ngram=ng, rank=rank)
+        return tokens, scores, parts
 
 
 class E2E(torch.nn.Module):
@@ -728,25 +759,54 @@ class E2E(torch.nn.Module):
             raise ValueError("beam width %d outside 1..%d" % (K, hb.BEAM_KMAX))
         return K
 
-    def recognize_ctc_beams(self, xs, ilens, topk, nbest=False):
+    def recognize_ctc_beams(self, xs, ilens, topk, nbest=False, *, ngram=None, ngram_weight=0.0, ngram_bonus=0.0):
         """CTC prefix beam search with the CTC head alone (not a reference method): encoder, the head,
         ops.ctc_beam with beam width topk (1..16) -> (ids, scores): per utterance the best label sequence (an id list) and
         its log-mass; with nbest=True per utterance the ranked list of all hypotheses the search kept (at most topk) and
-        the list of their scores.  The device results are read once."""
+        the list of their scores.  The device results are read once.
+        With ngram (an ngram.NgramLM over the decoder's vocabulary) the LM sits inside the search: hypotheses
+        rank by (log-mass + ngram_weight lm) + ngram_bonus len with the LM's end-of-sentence term, and the scores are
+        those ranks; self.last_ctc_beams then also holds ctc_score and lm_score."""
         K = self._beam_width(topk)
+        self.decoder.check_ngram(ngram)
         with torch.no_grad():
             logits, lens_dev, _ = self._ctc_logits(xs, ilens, "recognize_ctc_beams")
-            hyp, hyp_len, score = ops.ctc_beam(logits, lens_dev, K)
+            if ngram is None:
+                hyp, hyp_len, score = beams = ops.ctc_beam(logits, lens_dev, K)
+            else:
+                beams = ops.ctc_beam(logits, lens_dev, K, ngram=ngram, ngram_weight=ngram_weight, ngram_bonus=ngram_bonus,
+                                     eos_term=True)
+                hyp, hyp_len, score = beams[:3]
             bsz, _, T = hyp.shape
             host = torch.cat([hyp_len.view(bsz, K, 1).double(), score.view(bsz, K, 1).double(), hyp.double()], dim=2).cpu().tolist()
-        self.last_ctc_beams = (hyp, hyp_len, score)              # (the device tensors of the call)
+        self.last_ctc_beams = tuple(beams)                       # (the device tensors of the call)
         ids = [[[int(v) for v in row[2:2 + int(row[0])]] for row in utt if row[0] >= 0] for utt in host]
         scores = [[row[1] for row in utt if row[0] >= 0] for utt in host]
         if nbest:
             return ids, scores
         return [u[0] for u in ids], [u[0] for u in scores]
 
-    def recognize_two_pass(self, xs, ilens, topk, ctc_weight=0.5, length_penalty=0.0, nbest=False, *, lm=None, lm_weight=0.0):
+    def ngram_score(self, ngram, ids, eos_term=True):
+        """The n-gram LM's log-probability (ops.ngram_score) of hypotheses this model produced, to rescore any
+        list with: ids a device tensor [..., L] of label ids, <EOS>-padded as recognize_beams(nbest=True) and
+        recognize_two_pass return them (a row counts up to its first <EOS>) - or a list of id lists.  -> fp32 [...] on the
+        device (a list: [N]), the end-of-sentence term included when eos_term.  No host read for a tensor."""
+        self.decoder.check_ngram(ngram)
+        if not isinstance(ids, torch.Tensor):
+            rows = [[int(c) for c in row] for row in ids]
+            L = max([len(r) for r in rows] + [1])
+            dev = next(self.parameters()).device
+            flat = torch.tensor([r + [self.decoder.eos] * (L - len(r)) for r in rows], dtype=torch.int32).to(dev)
+            lens = hb.to_device_i32([len(r) for r in rows], dev)
+            return ops.ngram_score(ngram, flat, lens, eos_term=eos_term)
+        L = ids.shape[-1]
+        flat = ids.reshape(-1, L)
+        is_eos = flat == self.decoder.eos
+        first = torch.where(is_eos.any(dim=1), is_eos.to(torch.int32).argmax(dim=1), torch.full_like(flat[:, 0], L)).to(torch.int32)
+        return ops.ngram_score(ngram, flat, first, eos_term=eos_term).view(ids.shape[:-1])
+
+    def recognize_two_pass(self, xs, ilens, topk, ctc_weight=0.5, length_penalty=0.0, nbest=False, *, lm=None, lm_weight=0.0,
+                           ngram=None, ngram_weight=0.0, ngram_bonus=0.0):
         """Two-pass decoding (not a reference method): the CTC prefix beam search of the head proposes topk
         (1..16) hypotheses per utterance, ONE teacher-forced pass of the attention decoder over the B topk rows scores them
         (Decoder.score_hypotheses), and with lm (an LM module) and lm_weight != 0 one teacher-forced pass of the LM too.
@@ -756,17 +816,22 @@ class E2E(torch.nn.Module):
         slot the search left unused stays at -inf.
         -> (prediction [B, L] int64, scores [B]): the best hypothesis, <EOS>-padded to L = T' + 1; with nbest=True all topk,
         ranked: ([B, topk, L], [B, topk]) - the shapes of recognize_beams.  Device tensors: no host read in here, and none
-        between the passes.  self.last_two_pass keeps the parts (hyp, hyp_len, ctc, att, lm, order)."""
+        between the passes.  self.last_two_pass keeps the parts (hyp, hyp_len, ctc, att, lm, order).
+        With ngram (an ngram.NgramLM) the first pass is the search with the LM inside, and the score is
+        ((1 - w) att + w ctc + lm_weight lm + ngram_weight lm_ngram + ngram_bonus len) / (len + 1)**length_penalty, in this
+        order, with ctc the search's ctc_score and lm_ngram its lm_score (parts: also ngram and rank)."""
         K = self._beam_width(topk)
         w = float(ctc_weight)
         if not 0.0 <= w <= 1.0:
             raise ValueError("ctc_weight must lie in [0, 1], got %r" % (ctc_weight,))
         dec = self.decoder
         dec.check_lm(lm)
+        dec.check_ngram(ngram)
+        extra = {} if ngram is None else dict(ngram=ngram, ngram_weight=ngram_weight, ngram_bonus=ngram_bonus)
         with torch.no_grad():
             logits, lens_dev, enc_lens, enc_h = self._encode_ctc(xs, ilens, "recognize_two_pass")
             tokens, scores, parts = dec.rescore_ctc_beams(enc_h, enc_lens, logits, lens_dev, K, ctc_weight=w,
-                                                          length_penalty=length_penalty, lm=lm, lm_weight=lm_weight)
+                                                          length_penalty=length_penalty, lm=lm, lm_weight=lm_weight, **extra)
         self.last_two_pass = parts
         if nbest:
             return tokens, scores

@@ -1087,10 +1087,14 @@ def ctc_greedy(logits, frame_lens_dev):
     return ids, n, frame_tok
 
 
-def ctc_beam(logits, frame_lens_dev, beam):
+def ctc_beam(logits, frame_lens_dev, beam, ngram=None, ngram_weight=0.0, ngram_bonus=0.0, eos_term=True):
     """-> (hyp int32 [B, beam, T'] padded with -1, hyp_len int32 [B, beam] with -1 in unused slots, score fp32 [B, beam]
     descending with -inf in unused slots): the CTC prefix beam search of raw logits [B, T', V] (blank = 0), asr_ctc_beam_f32
-    (csrc/ctc_beam.hip), two launches.  Forward only, no host synchronisation."""
+    (csrc/ctc_beam.hip), two launches.  Forward only, no host synchronisation.
+    With ngram (an ngram.NgramLM, or its table on the device) the LM sits inside the search (asr_ctc_beam_lm_f32, DESIGN
+    4.23, two launches): candidates rank by (tot + ngram_weight lm) + ngram_bonus len, eos_term adds the LM's
+    end-of-sentence term after the last frame -> (hyp, hyp_len, score: the rank, ctc_score fp32 [B, beam]: tot, lm_score
+    fp32 [B, beam]: lm).  Without ngram the call, its launches and its bits are what they were."""
     logits = logits.detach()
     B, T, V = logits.shape
     K, dev = int(beam), logits.device
@@ -1098,8 +1102,38 @@ def ctc_beam(logits, frame_lens_dev, beam):
     hyp = torch.empty(B, K, T, device=dev, dtype=torch.int32)
     hyp_len = torch.empty(B, K, device=dev, dtype=torch.int32)
     score = torch.empty(B, K, device=dev, dtype=torch.float32)
-    hb.ctc_beam(logits, frame_lens_dev, K, hyp, hyp_len, score, ws)
-    return hyp, hyp_len, score
+    if ngram is None:
+        hb.ctc_beam(logits, frame_lens_dev, K, hyp, hyp_len, score, ws)
+        return hyp, hyp_len, score
+    ctc_score, lm_score = torch.empty_like(score), torch.empty_like(score)
+    hb.ctc_beam_lm(logits, frame_lens_dev, K, _ngram_table(ngram, dev), float(ngram_weight), float(ngram_bonus), bool(eos_term),
+                   hyp, hyp_len, score, ctc_score, lm_score, ws)
+    return hyp, hyp_len, score, ctc_score, lm_score
+
+
+def _ngram_table(ngram, dev):
+    """An ngram.NgramLM (compiled and uploaded once per device) or an ngram.NgramTable -> the table on dev."""
+    return ngram.to(dev)
+
+
+def ngram_score(ngram, ids, lens, eos_term=True, per_token=False):
+    """-> score fp32 [N] (and with per_token the terms fp32 [N, L]): the n-gram LM's log-probability of the padded id
+    sequences ids [N, L] (int32 or int64, on the device) with lens int32 [N] (-1: an unused slot, -inf), the tokens in order
+    from the context <s>, with the end-of-sentence term when eos_term: asr_ngram_score_f32 (csrc/ngram.hip), one
+    launch.  An id outside 0 .. V-1 inside the length gives NaN for that sequence.  No host synchronisation."""
+    ids = ids.detach()
+    if ids.dtype != torch.int32:
+        ids = ids.to(torch.int32)
+    if ids.dim() != 2:
+        raise ValueError("ngram_score: ids must be [N, L], got %r" % (tuple(ids.shape),))
+    if ids.stride(1) != 1:
+        ids = ids.contiguous()
+    N, L = ids.shape
+    dev = ids.device
+    score = torch.empty(N, device=dev, dtype=torch.float32)
+    tok = torch.empty(N, L, device=dev, dtype=torch.float32) if per_token else None
+    hb.ngram_score(_ngram_table(ngram, dev), ids, lens.to(torch.int32).contiguous(), score, tok, eos_term=eos_term)
+    return (score, tok) if per_token else score
 
 
 def decoder_sequence(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo, w_out, b_out, w0, opts):

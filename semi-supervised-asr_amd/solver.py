@@ -346,15 +346,67 @@ class Solver(object):
             raise ValueError("two_pass_decode needs the CTC head: build the model with ctc_weight > 0")
         return on
 
-    def _two_pass(self, xs, ilens, beam_size, ctc_weight, lm_weight=0.0, nbest=False):
+    @staticmethod
+    def ngram_config(config, two_pass, has_ctc_head):
+        """The n-gram LM keys (not reference keys; absent by default): `ctc_beam_decode` (default false) makes
+        test() decode with the CTC prefix beam search alone (E2E.recognize_ctc_beams, beam width `beam_size`); `ngram_lm` is
+        the path of an ARPA file over the vocabulary's symbols, used inside that search with `ctc_beam_decode` and inside
+        the first pass (and the combination) with `two_pass_decode`; `ngram_weight` and `ngram_bonus` weigh its
+        log-probability and the hypothesis length.  -> (ctc_beam_decode as a bool, the path or None, weight, bonus);
+        ValueError where the keys cannot hold: `ctc_beam_decode` beside another decoder or on a model without the CTC head,
+        `ngram_lm` with a decoder that has no place for it, a weight or bonus without `ngram_lm`."""
+        ctc_beam = bool(config.get("ctc_beam_decode", False))
+        if ctc_beam and (two_pass or bool(config.get("ctc_greedy_decode", False))):
+            raise ValueError("ctc_beam_decode, two_pass_decode and ctc_greedy_decode are three decoders: set one of them")
+        if ctc_beam and not has_ctc_head:
+            raise ValueError("ctc_beam_decode needs the CTC head: build the model with ctc_weight > 0")
+        if ctc_beam and (float(config.get("lm_weight", 0.0) or 0.0) > 0 or float(config.get("ctc_decode_weight", 0.0) or 0.0) > 0):
+            raise ValueError("ctc_beam_decode decodes with the CTC head alone: it does not combine with lm_weight > 0 or "
+                             "ctc_decode_weight > 0 (ngram_lm is the LM of this search)")
+        path = config.get("ngram_lm")
+        if path is None:
+            for key in ("ngram_weight", "ngram_bonus"):
+                if key in config:
+                    raise ValueError("%s is set without ngram_lm, the ARPA file it weighs" % key)
+            return ctc_beam, None, 0.0, 0.0
+        if not (ctc_beam or two_pass):
+            raise ValueError("ngram_lm is used by the CTC prefix beam search: set ctc_beam_decode or two_pass_decode - the "
+                             "attention beam search, greedy and ctc_greedy_decode have no place for an n-gram LM")
+        return ctc_beam, path, float(config.get("ngram_weight", 0.0) or 0.0), float(config.get("ngram_bonus", 0.0) or 0.0)
+
+    def _ctc_beams(self, xs, ilens, beam_size, ngram=None, nbest=False):
+        """Hypothesis ids of the CTC prefix beam search for one batch (E2E.recognize_ctc_beams, with the n-gram LM inside
+        when there is one) - with nbest beam_size id lists per utterance, ranked, a rank the search left unused as a row
+        of <EOS>; the abort word of the encoder's persistent kernels is checked after the decode, as in _greedy."""
+        lm, w, bonus = ngram if ngram is not None else (None, 0.0, 0.0)
+
+        def run():
+            ids, _ = self.model.recognize_ctc_beams(xs, ilens, beam_size, nbest=nbest,
+                                                    **({} if lm is None else dict(ngram=lm, ngram_weight=w, ngram_bonus=bonus)))
+            if nbest:
+                eos = self.vocab["<EOS>"]
+                width = max(len(h) for hyps in ids for h in hyps) + 1
+                ids = [[h + [eos] * (width - len(h)) for h in hyps + [[]] * (beam_size - len(hyps))] for hyps in ids]
+            return ids
+        out = run()
+        if self._abort_seen(xs.device):
+            print("persistent kernels aborted during CTC beam decoding (this rank's code %d): repeating the batch on the "
+                  "per-step kernels" % hb.persist_abort_code(xs.device))
+            hb.disable_persistent(xs.device)
+            out = run()
+        return out
+
+    def _two_pass(self, xs, ilens, beam_size, ctc_weight, lm_weight=0.0, nbest=False, ngram=None):
         """Two-pass hypothesis ids for one batch (E2E.recognize_two_pass) - with nbest all beam_size of them per utterance,
         ranked ([B][K][L]); the abort word of the persistent kernels is checked after the decode and the batch repeated on
-        the per-step kernels, as in _greedy."""
+        the per-step kernels, as in _greedy.  ngram: (the NgramLM, its weight, the length bonus) or None."""
+        extra = {} if ngram is None else dict(ngram=ngram[0], ngram_weight=ngram[1], ngram_bonus=ngram[2])
+
         def run():
             prediction, _ = self.model.recognize_two_pass(
                 xs, ilens, beam_size, ctc_weight=ctc_weight,
                 length_penalty=float(self.config.get("beam_length_penalty", 0.0)), nbest=nbest,
-                lm=self.judge if lm_weight > 0 else None, lm_weight=lm_weight)
+                lm=self.judge if lm_weight > 0 else None, lm_weight=lm_weight, **extra)
             return prediction.cpu().numpy().tolist()
         out = run()
         if self._abort_seen(xs.device):
@@ -451,6 +503,12 @@ class Solver(object):
             raise ValueError("ctc_greedy_decode decodes with the CTC head alone: it does not combine with beam_size > 1, "
                              "lm_weight > 0 or ctc_decode_weight > 0")
         two_pass = self.two_pass_config(self.config, hasattr(self.model, "ctc_lo"))
+        ctc_beam, ngram_path, ngram_w, ngram_bonus = self.ngram_config(self.config, two_pass, hasattr(self.model, "ctc_lo"))
+        ngram = None
+        if ngram_path is not None:
+            from ngram import NgramLM
+            ngram = (NgramLM.from_arpa(ngram_path, {s: i for s, i in self.vocab.items() if s not in ("<s>", "</s>")},
+                                       self.vocab["<BOS>"], self.vocab["<EOS>"], V=len(self.vocab)), ngram_w, ngram_bonus)
         if state_dict:
             self.model.load_state_dict(state_dict)
         else:
@@ -481,12 +539,18 @@ class Solver(object):
             xs, ilens, _ = batch
             if ctc_greedy:
                 preds += self._ctc_best_path(xs, ilens)
+            elif ctc_beam and nbest:
+                ranked = self._ctc_beams(xs, ilens, beam_size, ngram, nbest=True)
+                preds += [hyps[0] for hyps in ranked]
+                beams += ranked
+            elif ctc_beam:
+                preds += self._ctc_beams(xs, ilens, beam_size, ngram)
             elif two_pass and nbest:
-                ranked = self._two_pass(xs, ilens, beam_size, ctc_w, lm_weight, nbest=True)
+                ranked = self._two_pass(xs, ilens, beam_size, ctc_w, lm_weight, nbest=True, ngram=ngram)
                 preds += [hyps[0] for hyps in ranked]
                 beams += ranked
             elif two_pass:
-                preds += self._two_pass(xs, ilens, beam_size, ctc_w, lm_weight)
+                preds += self._two_pass(xs, ilens, beam_size, ctc_w, lm_weight, ngram=ngram)
             elif nbest:
                 ranked = self._beam(xs, ilens, beam_size, lm_weight, nbest=True, ctc_decode_weight=ctc_w)
                 preds += [hyps[0] for hyps in ranked]
