@@ -762,6 +762,21 @@ int asr_edit_distance_i32(int n_pairs, const void* hyp, int hyp_elem_bytes, int6
                           const int32_t* hyp_len, const int32_t* ref, int64_t ldr, const int32_t* ref_len,
                           const int32_t* ref_of_pair, int eos, const uint8_t* skip, int V, int32_t* dist, int32_t* hyp_n,
                           int32_t* ref_n, long long* totals, asr_stream_t stream);
+/*   asr_word_edit_distance_i32   the same call with `space`, on WORDS (the scoring half of WER).  Added to ABI
+ *                           version 8 WITHOUT a version change: additive.  Each side is cut and filtered as above; a word is
+ *                           a maximal run of the kept tokens that are not `space` - str.split() of the rendered text:
+ *                           leading, trailing and repeated spaces make no words, and a dropped token between two letters
+ *                           joins them into one word.  Two words are equal iff their token sequences are equal (a hash
+ *                           only pre-filters; the tokens decide).  dist[p] = the Levenshtein distance (unit costs) between
+ *                           the two word sequences; hyp_n[p], ref_n[p] = the word counts; totals[0] += sum of dist,
+ *                           totals[1] += sum of ref_n.  Empty sides are legal.  A `space` that the skip table drops is never
+ *                           seen: each side is then at most one word.
+ *                           Limits and refusals as above (a side holds at most ASR_ED_MAX_COLS / 2 words); space < 0:
+ *                           ASR_E_ARG.  One launch, no host synchronisation, no allocation. */
+int asr_word_edit_distance_i32(int n_pairs, const void* hyp, int hyp_elem_bytes, int64_t ldh, int hyp_cols,
+                               const int32_t* hyp_len, const int32_t* ref, int64_t ldr, const int32_t* ref_len,
+                               const int32_t* ref_of_pair, int eos, const uint8_t* skip, int V, int space, int32_t* dist,
+                               int32_t* hyp_n, int32_t* ref_n, long long* totals, asr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Optimiser on a flat fp32 buffer (solver.py:152-153,384-385: clip_grad_norm_ + Adam(amsgrad,

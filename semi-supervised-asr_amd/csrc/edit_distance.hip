@@ -12,6 +12,8 @@
 //            References wider than 1 024 columns (64 lanes x 16) are processed in strips of 1 024: the last lane of a strip
 //            leaves its column in LDS as the next strip's boundary.
 // Results leave with ordinary vector stores; the totals with 64-bit integer atomics (order-independent).
+// The second kernel of the file aligns WORDS instead of tokens (WER) with the same two helpers; its phases and
+// its LDS figure (3 KiB for a WSJ-like pair, 80 KiB at the limit) stand in front of it.
 #include "common.h"
 
 namespace {
@@ -155,7 +157,170 @@ __global__ __launch_bounds__(64) void edit_distance_kernel(EdArgs a) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The same distance on WORDS (the scoring half of WER): asr_word_edit_distance_i32.  One wave per pair again:
+//   phase 1  both sides compacted as above into one LDS token row, the reference first;
+//   phase 2  words: a token that is not `space` starts a word when it has no such token before it and ends one when it has
+//            none behind it (ballot of the starts + popcount prefix = the word's index, 64 tokens per round; a word may
+//            start in one round and end in a later one).  The words of both sides go into ONE list, the reference's first;
+//   phase 3  a hash per word (one lane per word), then every word takes as its id the index of the first earlier word of
+//            the reference with the same hash, length AND tokens - the hash only spares token compares, the tokens decide -
+//            or its own index.  Only hypothesis-to-reference equality enters the table, so a hypothesis word is looked up
+//            among the reference's words alone;
+//   phase 4  the table on the ids, through ed_strip as above (at most 2 048 words a side: two strips).
+// LDS is sized by the launch from the raw widths (cr = ldr, ch = hyp_cols columns; wr = (cr + 1) / 2, wh = (ch + 1) / 2
+// words at most): tokens 4 (cr + ch) bytes, word start and end 2 x 2 (wr + wh), hash and id 2 x 4 (wr + wh); the boundary
+// column (4 wh) lies over the starts and ends, which are dead by then.  A WSJ-like pair (150 columns a side) takes 3 KiB;
+// the limit, 4 096 columns a side, 80 KiB = 32 + 16 + 32, half of a CU's 160 KiB.
+struct WedArgs {
+  EdArgs e;
+  int space;
+  int ref_cap, hyp_cap;                    // cr, ch: entries of the two token rows
+};
+
+// Words of the compacted row tok[0 .. ntok): word w's tokens are tok[wstart[w] - off .. wend[w] - off).  Returns the count.
+__device__ __forceinline__ int ed_words(const int* tok, int ntok, int off, int space, unsigned short* wstart,
+                                        unsigned short* wend, int lane) {
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int count = 0;
+  for (int base = 0; base < ntok; base += 64) {
+    const int i = base + lane;
+    const bool in_word = i < ntok && tok[i] != space;
+    const bool start = in_word && (i == 0 || tok[i - 1] == space);
+    const bool end = in_word && (i + 1 == ntok || tok[i + 1] == space);
+    const unsigned long long starts = __ballot(start);
+    const int before = count + __popcll(starts & below);               // words that start left of this token
+    if (start) wstart[before] = (unsigned short)(off + i);
+    if (end) wend[before + (start ? 1 : 0) - 1] = (unsigned short)(off + i + 1);
+    count += __popcll(starts);
+  }
+  return count;
+}
+
+// The whole table over hyp_s[0 .. n) x ref_s[0 .. m), bnd[i] = i + 1 on entry: the strips of edit_distance_kernel.
+__device__ __forceinline__ int ed_table(const int* hyp_s, const int* ref_s, int* bnd, int n, int m, int lane) {
+  if (n == 0) return m;
+  int d = n;                                                           // m == 0
+  for (int col0 = 0; col0 < m; col0 += ED_STRIP) {
+    const int W = min(m - col0, ED_STRIP);
+    const bool more = col0 + ED_STRIP < m;
+    if (W <= 64) d = ed_strip<1>(hyp_s, ref_s, bnd, n, m, col0, false, lane);
+    else if (W <= 128) d = ed_strip<2>(hyp_s, ref_s, bnd, n, m, col0, false, lane);
+    else if (W <= 256) d = ed_strip<4>(hyp_s, ref_s, bnd, n, m, col0, false, lane);
+    else if (W <= 512) d = ed_strip<8>(hyp_s, ref_s, bnd, n, m, col0, false, lane);
+    else d = ed_strip<ED_CMAX>(hyp_s, ref_s, bnd, n, m, col0, more, lane);
+    if (more) __syncthreads();
+  }
+  return d;
+}
+
+__global__ __launch_bounds__(64) void word_edit_distance_kernel(WedArgs w) {
+  extern __shared__ int wed_lds[];
+  const EdArgs& a = w.e;
+  const int nwords = (w.ref_cap + 1) / 2 + (w.hyp_cap + 1) / 2;
+  int* tok = wed_lds;                                                  // [ref_cap | hyp_cap]
+  unsigned* hash = (unsigned*)(tok + w.ref_cap + w.hyp_cap);           // [nwords]
+  int* id = (int*)(hash + nwords);                                     // [nwords]
+  unsigned short* wstart = (unsigned short*)(id + nwords);             // [nwords]
+  unsigned short* wend = wstart + nwords;                              // [nwords]
+  int* bnd = (int*)wstart;                                             // [(hyp_cap + 1) / 2], once the ids stand
+  const int p = blockIdx.x, lane = threadIdx.x;
+  const int64_t rrow = a.ref_of_pair ? a.ref_of_pair[p] : p;
+
+  const int rlim = (int)max((int64_t)0, min((int64_t)a.ref_len[rrow], (int64_t)w.ref_cap));
+  const int32_t* rf = a.ref + rrow * a.ldr;
+  const int mt = ed_compact([=](int c) { return (int)rf[c]; }, rlim, -1, a.skip, a.V, tok, lane);
+  int hlim = a.hyp_len ? a.hyp_len[p] : a.hyp_cols;
+  hlim = max(0, min(hlim, a.hyp_cols));
+  int nt;
+  if (a.hyp_wide) {
+    const int64_t* h = (const int64_t*)a.hyp + (int64_t)p * a.ldh;
+    nt = ed_compact([=](int c) { return (int)h[c]; }, hlim, a.eos, a.skip, a.V, tok + w.ref_cap, lane);
+  } else {
+    const int32_t* h = (const int32_t*)a.hyp + (int64_t)p * a.ldh;
+    nt = ed_compact([=](int c) { return (int)h[c]; }, hlim, a.eos, a.skip, a.V, tok + w.ref_cap, lane);
+  }
+  __syncthreads();
+
+  const int m = ed_words(tok, mt, 0, w.space, wstart, wend, lane);
+  const int n = ed_words(tok + w.ref_cap, nt, w.ref_cap, w.space, wstart + m, wend + m, lane);
+  __syncthreads();
+
+  for (int x = lane; x < m + n; x += 64) {
+    const int s = wstart[x], len = wend[x] - s;
+    unsigned h = (unsigned)len;
+    for (int k = 0; k < len; ++k) h = asr_mix32(h + (unsigned)tok[s + k]);
+    hash[x] = h;
+  }
+  __syncthreads();
+  for (int x = lane; x < m + n; x += 64) {
+    const int s = wstart[x], len = wend[x] - s;
+    const unsigned h = hash[x];
+    const int earlier = min(x, m);
+    int first = x;
+    for (int v = 0; v < earlier; ++v) {
+      if (hash[v] != h) continue;
+      const int sv = wstart[v];
+      if (wend[v] - sv != len) continue;
+      int k = 0;
+      while (k < len && tok[sv + k] == tok[s + k]) ++k;
+      if (k == len) {
+        first = v;
+        break;
+      }
+    }
+    id[x] = first;
+  }
+  __syncthreads();                                                     // the starts and ends are dead: bnd takes their place
+  for (int i = lane; i < n; i += 64) bnd[i] = i + 1;                   // D[i + 1][0]
+  __syncthreads();
+
+  const int d = ed_table(id + m, id, bnd, n, m, lane);
+  if (lane == 0) {
+    a.dist[p] = d;
+    if (a.hyp_n) a.hyp_n[p] = n;
+    if (a.ref_n) a.ref_n[p] = m;
+    if (a.totals) {
+      atomicAdd(a.totals, (unsigned long long)d);
+      atomicAdd(a.totals + 1, (unsigned long long)m);
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" int asr_word_edit_distance_i32(int n_pairs, const void* hyp, int hyp_elem_bytes, int64_t ldh, int hyp_cols,
+                                          const int32_t* hyp_len, const int32_t* ref, int64_t ldr, const int32_t* ref_len,
+                                          const int32_t* ref_of_pair, int eos, const uint8_t* skip, int V, int space,
+                                          int32_t* dist, int32_t* hyp_n, int32_t* ref_n, long long* totals,
+                                          asr_stream_t stream_) {
+  if (n_pairs <= 0 || !hyp || !ref || !ref_len || !dist || space < 0) return ASR_E_ARG;
+  if ((hyp_elem_bytes != 4 && hyp_elem_bytes != 8) || hyp_cols < 0 || ldh < hyp_cols || ldr < 0) return ASR_E_ARG;
+  if (hyp_cols > ED_MAX || ldr > ED_MAX) return ASR_E_SHAPE;
+  WedArgs w;
+  EdArgs& a = w.e;
+  a.n_pairs = n_pairs;
+  a.hyp = hyp; a.hyp_wide = hyp_elem_bytes == 8; a.ldh = ldh; a.hyp_cols = hyp_cols;
+  a.hyp_len = hyp_len;
+  a.ref = ref; a.ldr = ldr; a.ref_len = ref_len;
+  a.ref_of_pair = ref_of_pair;
+  a.eos = eos;
+  a.skip = V > 0 ? skip : nullptr; a.V = V;
+  a.dist = dist; a.hyp_n = hyp_n; a.ref_n = ref_n;
+  a.totals = (unsigned long long*)totals;
+  w.space = space;
+  w.ref_cap = (int)ldr; w.hyp_cap = hyp_cols;
+  const int nwords = (w.ref_cap + 1) / 2 + (w.hyp_cap + 1) / 2;
+  const int lds = 4 * (w.ref_cap + w.hyp_cap) + 12 * nwords;
+  if (lds > 64 * 1024) {                                               // beyond the default bound of dynamic LDS
+    hipError_t e = hipFuncSetAttribute((const void*)word_edit_distance_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       4 * 2 * ED_MAX + 12 * ED_MAX);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL(word_edit_distance_kernel, dim3(n_pairs), dim3(64), lds, (hipStream_t)stream_, w);
+  ASR_CHECK_LAUNCH();
+  return 0;
+}
 
 extern "C" int asr_edit_distance_i32(int n_pairs, const void* hyp, int hyp_elem_bytes, int64_t ldh, int hyp_cols,
                                      const int32_t* hyp_len, const int32_t* ref, int64_t ldr, const int32_t* ref_len,

@@ -25,7 +25,7 @@ EXPORTS = (
     "asr_adam_clip_f32", "asr_sumsq_f32", "asr_gather_sumsq_f32",
     "asr_beam_select_f32", "asr_beam_reorder_f32", "asr_beam_backtrack",
     "asr_lm_step_f32", "asr_beam_select_lm_f32", "asr_beam_reorder_lm_f32",
-    "asr_edit_distance_i32",
+    "asr_edit_distance_i32", "asr_word_edit_distance_i32",
     "asr_colsum_det_f32", "asr_gemm_det_f32", "asr_gemm_det_ws_bytes", "asr_embedding_grad_det_f32", "asr_rows_fill_grad_det_f32",
     "asr_sumsq_det_f32", "asr_gather_sumsq_det_f32", "asr_sum_det_f32", "asr_dec_step_bwd_det", "asr_dec_seq_bwd_det",
     "asr_ctc_ws_bytes", "asr_ctc_loss_fwd", "asr_ctc_loss_bwd",
@@ -252,6 +252,8 @@ def load():
                                             ctypes.POINTER(BeamLmState), c_p]
     lib.asr_edit_distance_i32.argtypes = [c_i, c_p, c_i, c_i64, c_i, c_p, c_p, c_i64, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p,
                                           c_p, c_p]
+    lib.asr_word_edit_distance_i32.argtypes = [c_i, c_p, c_i, c_i64, c_i, c_p, c_p, c_i64, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p,
+                                               c_p, c_p, c_p]
     lib.asr_att_step_fwd.argtypes = [ctypes.POINTER(DecFwd), c_i, c_p]
     lib.asr_dec_seq_fwd.argtypes = [ctypes.POINTER(DecFwd), c_i, c_i, c_p]
     lib.asr_dec_seq_fwd_persist.argtypes = [ctypes.POINTER(DecFwd), c_p, c_p, c_p]
@@ -774,14 +776,8 @@ def _ints(t, name, dtypes, dim):
     return c_p(t.data_ptr())
 
 
-def edit_distance(hyp, ref, ref_len, *, hyp_len=None, ref_index=None, eos=-1, skip=None, totals=None, out=None):
-    """asr_edit_distance_i32 (csrc/edit_distance.hip): the Levenshtein distance of every hypothesis row to its reference row
-    on token ids, one launch.  hyp [N, cols] int32 or int64 (row p runs to hyp_len[p], int32 [N]; None: to cols; cut before
-    its first `eos` unless eos < 0); ref [R, cols] int32 with ref_len int32 [R]; pair p scores against reference row p, or
-    ref_index[p] (int32 [N]: K hypotheses per reference); skip: uint8 [V], tokens with a non-zero entry are dropped from
-    both sides (utils.cer_token_table); totals: int64 [2], += (sum of distances, sum of reference lengths).
-    -> (dist, hyp_n, ref_n), int32 [N] device tensors: distance and the two filtered lengths - rows of `out` (int32 [3, N])
-    when it is given.  Raises UnsupportedShape beyond ED_MAX_COLS columns: there is no other device path."""
+def _edit_distance(entry, space, hyp, ref, ref_len, hyp_len, ref_index, eos, skip, totals, out):
+    """The argument checks and the launch that asr_edit_distance_i32 (space None) and asr_word_edit_distance_i32 share."""
     N = hyp.shape[0]
     hp = _ints(hyp, "hyp", (torch.int32, torch.int64), 2)
     rp, rlp = _ints(ref, "ref", (torch.int32,), 2), _ints(ref_len, "ref_len", (torch.int32,), 1)
@@ -797,15 +793,35 @@ def edit_distance(hyp, ref, ref_len, *, hyp_len=None, ref_index=None, eos=-1, sk
     op = _ints(out, "out", (torch.int32,), 2)
     if tuple(out.shape) != (3, N) or not out.is_contiguous():
         raise RuntimeError("out must be a contiguous int32 [3, %d]" % N)
-    rc = load().asr_edit_distance_i32(
+    rc = getattr(load(), entry)(
         N, hp, hyp.element_size(), hyp.stride(0) if N > 1 else max(hyp.shape[1], 1), hyp.shape[1], hlp, rp,
         ref.stride(0) if ref.shape[0] > 1 else max(ref.shape[1], 1), rlp, rip, int(eos), sp,
-        0 if skip is None else skip.shape[0], op, c_p(out[1].data_ptr()), c_p(out[2].data_ptr()), tp, stream())
+        0 if skip is None else skip.shape[0], *(() if space is None else (int(space),)),
+        op, c_p(out[1].data_ptr()), c_p(out[2].data_ptr()), tp, stream())
     if rc == ASR_E_SHAPE:
-        raise UnsupportedShape("asr_edit_distance_i32: more than %d columns (hyp %d, ref %d)"
-                               % (ED_MAX_COLS, hyp.shape[1], ref.shape[1]))
-    check(rc, "asr_edit_distance_i32")
+        raise UnsupportedShape("%s: more than %d columns (hyp %d, ref %d)" % (entry, ED_MAX_COLS, hyp.shape[1], ref.shape[1]))
+    check(rc, entry)
     return out[0], out[1], out[2]
+
+
+def edit_distance(hyp, ref, ref_len, *, hyp_len=None, ref_index=None, eos=-1, skip=None, totals=None, out=None):
+    """asr_edit_distance_i32 (csrc/edit_distance.hip): the Levenshtein distance of every hypothesis row to its reference row
+    on token ids, one launch.  hyp [N, cols] int32 or int64 (row p runs to hyp_len[p], int32 [N]; None: to cols; cut before
+    its first `eos` unless eos < 0); ref [R, cols] int32 with ref_len int32 [R]; pair p scores against reference row p, or
+    ref_index[p] (int32 [N]: K hypotheses per reference); skip: uint8 [V], tokens with a non-zero entry are dropped from
+    both sides (utils.cer_token_table); totals: int64 [2], += (sum of distances, sum of reference lengths).
+    -> (dist, hyp_n, ref_n), int32 [N] device tensors: distance and the two filtered lengths - rows of `out` (int32 [3, N])
+    when it is given.  Raises UnsupportedShape beyond ED_MAX_COLS columns: there is no other device path."""
+    return _edit_distance("asr_edit_distance_i32", None, hyp, ref, ref_len, hyp_len, ref_index, eos, skip, totals, out)
+
+
+def word_edit_distance(hyp, ref, ref_len, space, *, hyp_len=None, ref_index=None, eos=-1, skip=None, totals=None, out=None):
+    """asr_word_edit_distance_i32 (csrc/edit_distance.hip): edit_distance on WORDS, one launch.  The arguments
+    are edit_distance's; `space` is the id that separates words: after the cut and the filter a word is a maximal run of
+    tokens other than `space` (str.split() of the rendered text), and two words are equal iff their tokens are.
+    -> (dist, hyp_n, ref_n): the word-level distance and the two word counts; totals += (sum of distances, sum of reference
+    word counts).  A negative `space` is an error of the call; UnsupportedShape beyond ED_MAX_COLS columns."""
+    return _edit_distance("asr_word_edit_distance_i32", space, hyp, ref, ref_len, hyp_len, ref_index, eos, skip, totals, out)
 
 
 def lm_step(R, H, In, xin, wcat, bcat, c_prev, c_out, h_out, h_out2=None):

@@ -838,8 +838,9 @@ class E2E(torch.nn.Module):
         return tokens[:, 0], scores[:, 0]
 
     MWER_EXTRA_STEPS = 5          # the n-best search of an MWER step runs at most this many steps past the longest reference
+    space_id = None               # the id of <space>, set by the Solver: what mwer_forward(unit="word") splits words at
 
-    def mwer_forward(self, xs, ilens, ys, beam, ce_weight=0.01, max_dec_timesteps=200, hyps=None):
+    def mwer_forward(self, xs, ilens, ys, beam, ce_weight=0.01, max_dec_timesteps=200, hyps=None, unit="token"):
         """The loss of one minimum-error-rate training step (not a reference method; DESIGN 4.20, Prabhavalkar et al. 2018):
         L_mwer + ce_weight L_ce with L_mwer = mean_b sum_k phat_k (err_k - mean err) over the `beam` (1..16) hypotheses of the
         n-best list, phat the model's sequence probabilities renormalised over the list.
@@ -847,13 +848,18 @@ class E2E(torch.nn.Module):
           under no_grad Decoder.recognize_beams(nbest=True) on that output, min(max_dec_timesteps, longest reference +
             MWER_EXTRA_STEPS) steps - or `hyps` = (tokens int [B, beam, T] <EOS>-padded, lengths int32 [B, beam] or None: up to
             the first <EOS>; < 0: an unused slot) instead of the search;
-          hb.edit_distance of the B beam hypotheses (cut at <EOS>, nothing filtered) to the B references;
+          hb.edit_distance of the B beam hypotheses (cut at <EOS>, nothing filtered) to the B references - with unit="word"
+            hb.word_edit_distance at self.space_id: err counts word errors (DESIGN 4.24), nothing else changes;
           Decoder.score_hypotheses_grad and ops.mwer_loss with scale = 1 / B;
           with ce_weight > 0 the supervised loss of E2E.forward on the same encoder output (teacher-forced, label smoothing
             and dropout as there, the CTC term when ctc_weight > 0).
         -> the loss, a device scalar.  self.last_mwer keeps the parts: tokens, hyp_len, err, npos, seq_logp, post, risk, coef,
         mwer, ce.  Nothing is read on the host."""
         K = self._beam_width(beam)
+        if unit not in ("token", "word"):
+            raise ValueError("mwer_forward: unit %r is neither 'token' nor 'word'" % (unit,))
+        if unit == "word" and self.space_id is None:
+            raise ValueError("mwer_forward(unit='word') needs E2E.space_id, the id of <space>")
         if xs.is_cuda:
             hb.upload_side_stream_for(xs.shape[0] * xs.shape[1])
         enc_h, enc_lens = self.encoder(xs, ilens)
@@ -878,8 +884,11 @@ class E2E(torch.nn.Module):
             ref = dec._label_matrices(ys)[1].to(torch.int32).contiguous()       # [B, longest + 1]: <EOS>-padded, read to ref_len
             ref_len = hb_to_device([int(y.size(0)) for y in ys], dev)
             ref_index = (torch.arange(bsz * K, device=dev, dtype=torch.int32) // K).int()
-            err, _, _ = hb.edit_distance(tokens.reshape(bsz * K, T), ref, ref_len, hyp_len=hyp_len.reshape(-1).clamp(min=0),
-                                         ref_index=ref_index, eos=dec.eos)
+            pairs = dict(hyp_len=hyp_len.reshape(-1).clamp(min=0), ref_index=ref_index, eos=dec.eos)
+            if unit == "word":
+                err, _, _ = hb.word_edit_distance(tokens.reshape(bsz * K, T), ref, ref_len, int(self.space_id), **pairs)
+            else:
+                err, _, _ = hb.edit_distance(tokens.reshape(bsz * K, T), ref, ref_len, **pairs)
         _, logits, tok_out_lb, npos = dec.score_hypotheses_grad(enc_h, enc_lens, tokens, hyp_len, scores=False)
         mwer, parts = ops.mwer_loss(logits, tok_out_lb, npos, err, 1.0 / bsz, n_utts=bsz)
         loss, ce = mwer, None

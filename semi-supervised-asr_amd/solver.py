@@ -22,8 +22,8 @@ from dataset import PickleDataset
 from feed import DeviceFeed
 from model import E2E, LM
 from parallel import FlatAdam
-from utils import (Logger, adjust_learning_rate, calculate_cer, calculate_cer_ids, cc, infinite_iter, remove_pad_eos,
-                   to_sents)
+from utils import (Logger, adjust_learning_rate, calculate_cer, calculate_cer_ids, calculate_wer_ids, cc, infinite_iter,
+                   remove_pad_eos, to_sents)
 
 
 class StepScalar(object):
@@ -95,11 +95,13 @@ class Solver(object):
             print(self.config)
         self.logger = Logger(config["logdir"])
         self.load_vocab()
+        self.mwer_space = self.mwer_unit_config(config, self.vocab)
         self.get_data_loaders()
         self.labeldist = self.get_label_dist(self.train_lab_dataset)
         self.unlab_labeldist = self.get_label_dist(self.train_unlab_y_dataset)
         self.proportion = self.calculate_length_proportion()
         self.build_model(load_model=load_model)
+        self.model.space_id = self.mwer_space      # E2E.mwer_forward(unit="word") splits the hypotheses at this id
         self.settle_host_memory()          # the corpora stay for good: keep the garbage collector from walking them mid-epoch
 
     # ------------------------------------------------------------------ checkpoints (.ckpt/.opt/.judge.*)
@@ -258,6 +260,12 @@ class Solver(object):
         Levenshtein loop per utterance; None: the host loop."""
         dev = next(self.model.parameters()).device
         return dev if self.config.get("cer_on_gpu", False) and dev.type == "cuda" else None
+
+    def _wer_device(self):
+        """The device that scores WER when `wer_on_gpu` (not a reference key; default false) is set and the model is on a GPU
+        (utils.calculate_wer_ids); None: Solver.test reports no WER.  Independent of `cer_on_gpu`."""
+        dev = next(self.model.parameters()).device
+        return dev if self.config.get("wer_on_gpu", False) and dev.type == "cuda" else None
 
     def _score_ids(self, hyp_ids, ref_ids, ref_index=None):
         return calculate_cer_ids(hyp_ids, ref_ids, self.vocab, self.non_lang_syms, self.vocab["<EOS>"], self._cer_device(),
@@ -532,8 +540,11 @@ class Solver(object):
         loader = get_data_loader(self._dataset(test_set, None, sort=False), batch_size=1, shuffle=False,
                                  drop_last=False)
         self.model.eval()
-        # with `cer_on_gpu` a beam search keeps all its K hypotheses per utterance: the best-of-K CER below
-        nbest = beam_size > 1 and self._cer_device() is not None
+        # with `cer_on_gpu` a beam search keeps all its K hypotheses per utterance: the best-of-K CER below; with `wer_on_gpu`
+        # for the best-of-K WER (rank 0 of the list is the hypothesis the search returns without it)
+        wer_dev = self._wer_device()
+        nbest_cer = beam_size > 1 and self._cer_device() is not None
+        nbest = nbest_cer or (beam_size > 1 and wer_dev is not None)
         preds, refs, beams = [], [], []
         for batch in self._feed(loader, sharded=False):
             xs, ilens, _ = batch
@@ -564,7 +575,7 @@ class Solver(object):
         if lm_weight > 0:
             self.judge.train(judge_was_training)
         self.last_test = dict(cer=None, best_of_k_cer=None, dist=None, ref_n=None)
-        if nbest:
+        if nbest_cer:
             # every hypothesis of every utterance against the utterance's reference in one launch; a rank the search left
             # without a hypothesis is a row of <EOS>: an empty hypothesis.  The rank-0 rows give the CER itself.
             K = beam_size
@@ -579,10 +590,25 @@ class Solver(object):
         else:
             cer, hyp_sents, _ = self.ind2sent(preds, refs)
         self.last_test["cer"] = cer
+        words = ""
+        if wer_dev is not None:
+            # the same on words, one launch: the K hypotheses of every utterance (K = 1 without a beam) against its reference
+            K = beam_size if nbest else 1
+            _, wdist, wref_n = calculate_wer_ids([h for hyps in beams for h in hyps] if nbest else preds, refs, self.vocab,
+                                                 self.non_lang_syms, self.vocab["<EOS>"], wer_dev,
+                                                 ref_index=[b for b in range(len(refs)) for _ in range(K)])
+            wdist = [wdist[b * K:(b + 1) * K] for b in range(len(refs))]
+            wref_n = wref_n[::K]
+            wer = float(sum(d[0] for d in wdist)) / float(sum(wref_n))
+            self.last_test.update(wer=wer, word_dist=wdist, word_ref_n=wref_n)
+            words = f", WER={wer:.4f}"
+            if nbest:
+                self.last_test["best_of_k_wer"] = float(sum(min(d) for d in wdist)) / float(sum(wref_n))
+                words += f", best of {beam_size}: WER={self.last_test['best_of_k_wer']:.4f}"
         with open(f"{test_set}.txt", "w") as f:
             f.writelines(f"{p}\n" for p in hyp_sents)
         print(f"{test_set}: {len(hyp_sents)} utterances, CER={cer:.4f}"
-              + (f", best of {beam_size} hypotheses: CER={self.last_test['best_of_k_cer']:.4f}" if nbest else ""))
+              + (f", best of {beam_size} hypotheses: CER={self.last_test['best_of_k_cer']:.4f}" if nbest_cer else "") + words)
         return cer
 
     # ------------------------------------------------------------------ judge (LM) pre-training
@@ -919,6 +945,20 @@ class Solver(object):
             raise ValueError("MWER training runs in one process: data-parallel MWER (world size %d) is not supported" % world)
         return K, ce_weight, epochs
 
+    @staticmethod
+    def mwer_unit_config(config, vocab):
+        """`mwer_unit` (not a reference key): `token` (default; the risk counts token errors) or `word` (word errors: the
+        hypotheses and references are split at <space>) -> None for `token`, the id of <space> for `word`.
+        ValueError for any other value, and for `word` with a vocabulary that has no <space>."""
+        unit = config.get("mwer_unit", "token")
+        if unit not in ("token", "word"):
+            raise ValueError("mwer_unit %r is neither 'token' nor 'word'" % (unit,))
+        if unit == "token":
+            return None
+        if "<space>" not in vocab:
+            raise ValueError("mwer_unit 'word' needs <space> in the vocabulary: words are what lies between two of them")
+        return int(vocab["<space>"])
+
     def mwer_train_one_iteration(self, xs, ilens, ys, hyps=None):
         """One minimum-error-rate step on a batch already on the device: E2E.mwer_forward (encoder, n-best
         search under no_grad - or the given `hyps` -, edit distances, scoring pass, risk loss, + mwer_ce_weight times the
@@ -932,7 +972,8 @@ class Solver(object):
 
         def make_local():
             loss = self.model.mwer_forward(xs, ilens, ys, K, ce_weight=ce_weight,
-                                           max_dec_timesteps=self.config["max_dec_timesteps"], hyps=hyps)
+                                           max_dec_timesteps=self.config["max_dec_timesteps"], hyps=hyps,
+                                           unit="token" if self.mwer_space is None else "word")
             return loss, [loss, self.model.last_mwer["mwer"]]
         loss, risk = self._step(make_local, self.gen_opt, 2)
         return loss, risk

@@ -3,7 +3,8 @@
 remove_pad_eos 192-201, to_sents/ind2character/char_list_to_str 160-163,212-235, calculate_cer
 222-228, Logger 237-245, infinite_iter 247-254).  tensorboardX and editdistance are optional:
 absent here, so logging degrades to a no-op and the edit distance is computed locally - on the host (edit_distance), or for
-whole sets of hypotheses on the GPU (calculate_cer_ids; not reference functions: cer_token_table, calculate_cer_ids).
+whole sets of hypotheses on the GPU (calculate_cer_ids, calculate_wer_ids; not reference functions: cer_token_table,
+calculate_cer_ids, calculate_wer, calculate_wer_ids).
 """
 import numpy as np
 import torch
@@ -110,9 +111,10 @@ def cer_token_table(vocab, non_lang_syms):
 _SKIP_TABLES = {}          # (device, table bytes) -> the table on that device
 
 
-def _device_cer(hyp_ids, ref_ids, table, eos, device, ref_index):
+def _device_score(hyp_ids, ref_ids, table, eos, device, ref_index, space=None):
     """One upload (both id matrices, their lengths and the reference index in one int32 buffer), one launch of
-    asr_edit_distance_i32, one read-back -> (sum dist, sum ref_n, dist, ref_n); None when the kernel declines the shape."""
+    asr_edit_distance_i32 - with `space`, of asr_word_edit_distance_i32 -, one read-back -> (sum dist, sum ref_n, dist,
+    ref_n); None when the kernel declines the shape."""
     import hip_backend as hb
     n, nr = len(hyp_ids), len(ref_ids)
     if n == 0 or nr == 0:
@@ -138,9 +140,12 @@ def _device_cer(hyp_ids, ref_ids, table, eos, device, ref_index):
         _SKIP_TABLES[key] = torch.from_numpy(table).to(device)
     res = torch.zeros(4 + 3 * n, dtype=torch.int32, device=device)       # the two 64-bit totals, then dist | hyp_n | ref_n
     try:
-        hb.edit_distance(d_hyp.view(n, lh), d_ref.view(nr, lr), d_ref_len, hyp_len=d_hyp_len,
-                         ref_index=d_index if ref_index is not None else None, eos=eos, skip=_SKIP_TABLES[key],
-                         totals=res[:4].view(torch.int64), out=res[4:].view(3, n))
+        kw = dict(hyp_len=d_hyp_len, ref_index=d_index if ref_index is not None else None, eos=eos, skip=_SKIP_TABLES[key],
+                  totals=res[:4].view(torch.int64), out=res[4:].view(3, n))
+        if space is None:
+            hb.edit_distance(d_hyp.view(n, lh), d_ref.view(nr, lr), d_ref_len, **kw)
+        else:
+            hb.word_edit_distance(d_hyp.view(n, lh), d_ref.view(nr, lr), d_ref_len, space, **kw)
     except hb.UnsupportedShape:
         return None
     got = res.cpu().numpy()
@@ -158,10 +163,41 @@ def calculate_cer_ids(hyp_ids, ref_ids, vocab, non_lang_syms, eos, device, ref_i
     correspond one to one (cer_token_table) or beyond the kernel's limits the same three values come from the host loop."""
     device = torch.device(device)
     table = cer_token_table(vocab, non_lang_syms) if device.type == "cuda" else None
-    got = _device_cer(hyp_ids, ref_ids, table, eos, device, ref_index) if table is not None else None
+    got = _device_score(hyp_ids, ref_ids, table, eos, device, ref_index) if table is not None else None
     if got is None:
         hyps = to_sents(remove_pad_eos(hyp_ids, eos=eos), vocab, non_lang_syms)
         refs = to_sents(ref_ids, vocab, non_lang_syms)
+        if ref_index is not None:
+            refs = [refs[int(i)] for i in ref_index]
+        dist = [edit_distance(h, r) for h, r in zip(hyps, refs)]
+        ref_n = [len(r) for r in refs]
+        got = sum(dist), sum(ref_n), dist, ref_n
+    total_dis, total_len, dist, ref_n = got
+    return float(total_dis) / float(total_len), dist, ref_n
+
+
+def calculate_wer(hyps, refs):
+    """Word error rate of strings: calculate_cer over their words (str.split())."""
+    return calculate_cer([h.split() for h in hyps], [r.split() for r in refs])
+
+
+def calculate_wer_ids(hyp_ids, ref_ids, vocab, non_lang_syms, eos, device, ref_index=None):
+    """calculate_wer from token ids, scored on the GPU (asr_word_edit_distance_i32, one launch per call): the
+    arguments and the pairing are calculate_cer_ids'.  -> (wer, dist, ref_n): wer = float(sum dist) / float(sum ref_n), the
+    per-pair word distances and the references' word counts as host lists.  The device scores when ids and characters
+    correspond one to one (cer_token_table) and <space> is a kept id; on a CPU device, without such a table or <space>, or
+    beyond the kernel's limits the same three values come from the host loop over the words of the rendered strings."""
+    device = torch.device(device)
+    table = cer_token_table(vocab, non_lang_syms) if device.type == "cuda" else None
+    space = vocab.get("<space>")
+    got = None
+    # (str.split() also cuts at any other white-space character: a vocabulary that keeps one is scored on the host)
+    if (table is not None and space is not None and table[int(space)] == 0
+            and not any(s.isspace() for s, i in vocab.items() if table[int(i)] == 0)):
+        got = _device_score(hyp_ids, ref_ids, table, eos, device, ref_index, space=int(space))
+    if got is None:
+        hyps = [h.split() for h in to_sents(remove_pad_eos(hyp_ids, eos=eos), vocab, non_lang_syms)]
+        refs = [r.split() for r in to_sents(ref_ids, vocab, non_lang_syms)]
         if ref_index is not None:
             refs = [refs[int(i)] for i in ref_index]
         dist = [edit_distance(h, r) for h, r in zip(hyps, refs)]
