@@ -1099,6 +1099,66 @@ int asr_ctc_beam_lm_f32(int B, int T, int V, int K, const float* logits, int64_t
                         asr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * A word-level backoff n-gram LM behind a lexicon (csrc/word_lm.h, csrc/word_lm.hip, csrc/ctc_beam.hip).  Not
+ * reference operators.  Two entries added to ABI version 8 WITHOUT a version change: additive.
+ * The LM arrives compiled (word_lm.py, WordLM.compile, which validates every index and value: the kernels trust the tables).
+ * All arrays are device memory:
+ *     trie_next int32 [N][V]  the lexicon's trie over token ids: the child node, or -1; node 0 is the root
+ *     trie_word int32 [N]     the word id (0 .. W-1) that ends at the node, or -1
+ *     arc_off   int32 [S+1]   the arcs of word state s are arc_off[s] .. arc_off[s+1]-1
+ *     arc_word  int32 [A]     ascending inside a state;   arc_logp fp32 [A];   arc_next int32 [A] the state after the word
+ *     bo_logp   fp32  [S]     the backoff weight of the state;   bo_state int32 [S] the state backed off to
+ *     uni_logp  fp32  [W]     the empty context, direct-indexed;   uni_next int32 [W] the state after the word from there,
+ *                             or -1: the word has no unigram and scores uni_logp[w] (the LM's oov_logp) from every context,
+ *                             the state going to `empty`
+ *     space: the token id words are split at;  start: the state of <s>;  empty: the state of the empty context;  eos, unk:
+ *     the word ids of </s> and <unk>
+ * The words of a token row: split at `space`; a run of spaces is one boundary; leading and trailing spaces make no word.  A
+ * word is spelled down the trie from the root; one that leaves the trie or stops at a node with trie_word < 0 is `unk`.
+ * The lookup (state s, word w) -> (lp, next), fp32, every addition rounded on its own:  uni_next[w] < 0: (uni_logp[w], empty).
+ * Otherwise acc = 0; while s != empty: binary search for w among the arcs of s - found: (acc + arc_logp, arc_next); not
+ * found: acc += bo_logp[s], s = bo_state[s]; at empty: (acc + uni_logp[w], uni_next[w]).
+ *   asr_word_lm_score_f32   N padded TOKEN id rows ids int32 [N][ld >= L] with lens int32 [N] (clamped to L; < 0: an unused
+ *       slot: score -inf, n_words 0) -> score fp32 [N]: the fp32 sum in word order of the lookups of the row's words from
+ *       `start`, plus the lookup of `eos` from the final state when eos_term != 0;  n_words int32 [N]: the number of words;
+ *       word_score fp32 [N][L] or NULL: the term of word j at column j, 0 behind the last word.  An id outside 0 .. V-1 inside
+ *       the length makes the row's score NaN; the id is never used as an index.  One thread per row, one launch, no atomics.
+ *   asr_ctc_beam_wlm_f32    asr_ctc_beam_f32 with the lexicon and the word LM inside the search.  An entry additionally
+ *       carries its trie node (-1: off the trie), its word state, lm (the fp32 sum over its COMPLETED words) and nw (their
+ *       count) - functions of the token sequence, so prefix identity and the merge are unchanged, and pb, pnb, tot are
+ *       asr_ctc_beam_f32's operation for operation.  A candidate ranks by (tot' + alpha lm') + beta nw', fp32, each of the four
+ *       operations rounded on its own; an extension by `space` from a node that is not the root has lm' = lm + lp and
+ *       nw' = nw + 1 with (lp, state') the lookup of the pending word, every other candidate keeps lm and nw.  After the last
+ *       frame a pending word closes, with eos_term != 0 the lookup of `eos` joins lm, and the entries are ranked once more.
+ *       lexicon_only != 0: an extension that leaves the trie, and a `space` at a node that ends no word, are no candidates; an
+ *       entry whose pending node ends no word after the last frame becomes an unused slot.  Outputs as asr_ctc_beam_lm_f32
+ *       (score: the rank; ctc_score: tot; lm_score: lm) and n_words int32 [B][K] (-1 in an unused slot).  With alpha = beta =
+ *       0, no end term and lexicon_only off, hyp, hyp_len and ctc_score are asr_ctc_beam_f32's bits.  lm->V must be V
+ *       (ASR_E_SHAPE); alpha and beta finite (ASR_E_ARG).  Workspace, launches (two) and limits are asr_ctc_beam_f32's.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  int32_t V, N, S, W;     /* tokens, trie nodes, word states, word ids */
+  int64_t A;              /* arcs */
+  int32_t space, start, empty, eos, unk;
+  const int32_t* trie_next;
+  const int32_t* trie_word;
+  const int32_t* arc_off;
+  const int32_t* arc_word;
+  const float* arc_logp;
+  const int32_t* arc_next;
+  const float* bo_logp;
+  const int32_t* bo_state;
+  const float* uni_logp;
+  const int32_t* uni_next;
+} asr_word_lm_t;
+int asr_word_lm_score_f32(int N, int L, const asr_word_lm_t* lm, int eos_term, const int32_t* ids, int64_t ld,
+                          const int32_t* lens, float* score, int32_t* n_words, float* word_score, asr_stream_t stream);
+int asr_ctc_beam_wlm_f32(int B, int T, int V, int K, const float* logits, int64_t ld, const int32_t* frame_lens,
+                         const asr_word_lm_t* lm, float alpha, float beta, int eos_term, int lexicon_only, int32_t* hyp,
+                         int32_t* hyp_len, float* score, float* ctc_score, float* lm_score, int32_t* n_words, void* ws,
+                         asr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * The front end (csrc/frontend.hip): packed waveforms -> the [B][T][D] features the encoder reads.  Not
  * reference operators - the reference reads features that Kaldi computed.  Five entries added to ABI version 8 WITHOUT a
  * version change: additive.

@@ -25,8 +25,18 @@
 //                         coalesced read per (entry, token), beside the emission's.  The list holds ranks, so update forms
 //                         the winner's mass again (the same operations on the same operands: the same bits).  After the last
 //                         frame the end-of-sentence term joins lm and the (at most K) entries are ranked once more.
+//   ctc_beam_kernel<M, kWordLm>   the search with a lexicon and a word-level n-gram LM inside (the tables and
+//                         the lookup are word_lm.h's): an entry carries its trie node, its word state, lm (the fp32 sum over
+//                         its COMPLETED words) and nw (their count) - again functions of the token sequence - and the "close"
+//                         pair (lp, next state) of its pending word, looked up ONCE by the thread that creates the entry
+//                         (update) and read from LDS by the candidate walk; a stay entry copies it.  Only an extension by
+//                         <space> from a node that is not the root changes lm and nw.  Ranks are lm_rank's with nw for len.
+//                         With lexicon_only the walk also reads the entry's trie row (one coalesced read per (entry, token),
+//                         as the n-gram variant reads its LM row) and drops what leaves the lexicon.
 #include <float.h>
+#include <type_traits>
 #include "seq_common.h"
+#include "word_lm.h"
 
 namespace {
 
@@ -41,6 +51,10 @@ static_assert(kKmax <= 32, "the merge map of an entry is one 32-bit mask");
 static_assert(kHistLds * 8 + kStage * kMaxThreads * 4 + 2048 <= 64 * 1024, "the static LDS of a workgroup");
 static_assert((3 * 2 + 2 * 2 + 2 * 2 + 1 + 2 + 2 * 2 + 1 + 1 + 1 + 1) * 4 * kKmax + 2 * 2 * (kMaxThreads / 64) * 4 <= 2048,
               "the beam's arrays, the LM's included, inside the 2048 bytes above");
+// (the word-LM variant: no s_rank / s_pos - its final ranking reuses s_spb / s_mk, dead by then -, and node, nw and the close
+// pair in two slots each: 17 + 5 + 8 = 30 words per entry)
+static_assert((3 * 2 + 2 * 2 + 2 * 2 + 1 + 2 + 2 * 2 + 1 + 4 * 2) * 4 * kKmax + 2 * 2 * (kMaxThreads / 64) * 4 <= 2048,
+              "the beam's arrays of the word-LM variant inside the same 2048 bytes");
 
 typedef unsigned long long u64;
 
@@ -92,13 +106,28 @@ __device__ __forceinline__ float lm_rank(float tot, float lm, int len, float alp
   return __fadd_rn(__fadd_rn(tot, __fmul_rn(alpha, lm)), __fmul_rn(beta, (float)len));
 }
 
-template <int M, bool LM>
+// the lexicon and word LM of a fused search (MODE = kWordLm)
+struct BeamWlm {
+  wlm::WordLm w;
+  float* ctc_score;        // [B][K]
+  float* lm_score;         // [B][K]
+  int32_t* n_words;        // [B][K]
+  float alpha, beta;
+  int eos_term, lexicon_only;
+};
+
+constexpr int kPlain = 0, kNgram = 1, kWordLm = 2;           // what sits inside the search
+
+template <int M, int MODE>
 __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int K, const float* __restrict__ z, int64_t ld,
                                                                const int32_t* __restrict__ lens, int32_t* __restrict__ hyp,
                                                                int32_t* __restrict__ hyp_len, float* __restrict__ score,
-                                                               BeamWs w, BeamLm g) {
+                                                               BeamWs w, std::conditional_t<MODE == kWordLm, BeamWlm, BeamLm> g) {
+  constexpr bool LM = MODE == kNgram, WLM = MODE == kWordLm, RK = MODE != kPlain;      // RK: the list holds ranks
   __shared__ int s_state[2][kKmax], s_pos[kKmax];            // (LM only, like the next line: unused arrays take no LDS)
   __shared__ float s_lm[2][kKmax], s_stot[kKmax], s_rank[kKmax];
+  __shared__ int s_node[2][kKmax], s_nw[2][kKmax], s_cnx[2][kKmax];      // (word LM only: trie node, words, close pair)
+  __shared__ float s_clp[2][kKmax];
   __shared__ float s_pb[2][kKmax], s_pnb[2][kKmax], s_tot[2][kKmax];
   __shared__ int s_last[2][kKmax], s_len[2][kKmax];
   __shared__ u64 s_hash[2][kKmax];
@@ -115,7 +144,15 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
   if (len == 0) {                                            // no frames: the empty hypothesis at score 0
     for (int64_t i = tid; i < (int64_t)K * T; i += nt) hypb[i] = -1;
     if (tid < K) {
-      if constexpr (LM) {
+      if constexpr (WLM) {
+        float lm0 = 0.f;
+        int nx;
+        if (g.eos_term) wlm::lookup(g.w, g.w.start, g.w.eos, lm0, nx);
+        score[(int64_t)b * K + tid] = tid == 0 ? lm_rank(0.f, lm0, 0, g.alpha, g.beta) : -INFINITY;
+        g.ctc_score[(int64_t)b * K + tid] = tid == 0 ? 0.f : -INFINITY;
+        g.lm_score[(int64_t)b * K + tid] = tid == 0 ? lm0 : -INFINITY;
+        g.n_words[(int64_t)b * K + tid] = tid == 0 ? 0 : -1;
+      } else if constexpr (LM) {
         const float lm0 = g.eos >= 0 ? g.logp[(int64_t)g.start * V + g.eos] : 0.f;
         score[(int64_t)b * K + tid] = tid == 0 ? lm_rank(0.f, lm0, 0, g.alpha, g.beta) : -INFINITY;
         g.ctc_score[(int64_t)b * K + tid] = tid == 0 ? 0.f : -INFINITY;
@@ -141,6 +178,14 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
     if constexpr (LM) {
       s_state[0][tid] = g.start;
       s_lm[0][tid] = 0.f;
+    }
+    if constexpr (WLM) {
+      s_state[0][tid] = g.w.start;
+      s_lm[0][tid] = 0.f;
+      s_node[0][tid] = 0;
+      s_nw[0][tid] = 0;
+      s_clp[0][tid] = 0.f;
+      s_cnx[0][tid] = g.w.start;
     }
   }
   float zn[kStage];
@@ -199,6 +244,10 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
         const float st = logaddexp(npb, npnb);
         s_stot[tid] = st;
         top_insert(lv, li, lm_rank(st, s_lm[p][tid], lj, g.alpha, g.beta), tid);
+      } else if constexpr (WLM) {
+        const float st = logaddexp(npb, npnb);
+        s_stot[tid] = st;
+        top_insert(lv, li, lm_rank(st, s_lm[p][tid], s_nw[p][tid], g.alpha, g.beta), tid);
       } else {
         top_insert(lv, li, logaddexp(npb, npnb), tid);
       }
@@ -217,6 +266,22 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
         lrow = g.logp + (int64_t)s_state[p][k] * V;
         lenk1 = s_len[p][k] + 1;
       }
+      // (word LM) what an extension by <space> and by any other token carry: only a <space> behind a pending word closes it
+      float lm_sp = 0.f;
+      int nwk = 0, nw_sp = 0;
+      bool no_sp = false;
+      const int32_t* trow = nullptr;
+      if constexpr (WLM) {
+        const int nodek = s_node[p][k];
+        lmk = s_lm[p][k];
+        nwk = s_nw[p][k];
+        lm_sp = nodek != 0 ? __fadd_rn(lmk, s_clp[p][k]) : lmk;
+        nw_sp = nodek != 0 ? nwk + 1 : nwk;
+        if (g.lexicon_only) {                                    // (the node of an entry is never off the trie then)
+          no_sp = nodek != 0 && s_cnx[p][k] < 0;
+          trow = g.w.trie_next + (int64_t)nodek * V;
+        }
+      }
       for (int c = tid; c < V; c += nt) {
         if (c == 0) continue;
         const float xc = c < nstage ? xs[c] : zr[c] - lcur;
@@ -224,6 +289,11 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
         for (unsigned m = mkk; m; m &= m - 1)                // prefix_k . c is in the beam: not a candidate of its own
           if (s_last[p][__ffs(m) - 1] == c) val = -INFINITY;
         if constexpr (LM) val = lm_rank(val, lmk + lrow[c], lenk1, g.alpha, g.beta);       // (-inf stays -inf: lm is finite)
+        if constexpr (WLM) {
+          const bool sp = c == g.w.space;
+          if (g.lexicon_only && (sp ? no_sp : trow[c] < 0)) val = -INFINITY;
+          val = lm_rank(val, sp ? lm_sp : lmk, sp ? nw_sp : nwk, g.alpha, g.beta);
+        }
         top_insert(lv, li, val, base + c);
       }
     }
@@ -288,10 +358,16 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
           s_last[q][tid] = s_last[p][k];
           s_len[q][tid] = s_len[p][k];
           s_hash[q][tid] = s_hash[p][k];
-          if constexpr (LM) {
+          if constexpr (RK) {
             s_tot[q][tid] = s_stot[k];
             s_lm[q][tid] = s_lm[p][k];
             s_state[q][tid] = s_state[p][k];
+          }
+          if constexpr (WLM) {
+            s_node[q][tid] = s_node[p][k];
+            s_nw[q][tid] = s_nw[p][k];
+            s_clp[q][tid] = s_clp[p][k];
+            s_cnx[q][tid] = s_cnx[p][k];
           }
         } else {
           const int e = my_i - K;
@@ -305,6 +381,30 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
             s_tot[q][tid] = mass;
             s_lm[q][tid] = s_lm[p][k] + g.logp[at];
             s_state[q][tid] = g.next[at];
+          } else if constexpr (WLM) {
+            const float xc = tok < nstage ? xs[tok] : zr[tok] - lcur;
+            const float mass = (tok == s_last[p][k] ? s_pb[p][k] : s_tot[p][k]) + xc;
+            s_pnb[q][tid] = mass;
+            s_tot[q][tid] = mass;
+            const int nk = s_node[p][k];
+            float lmn = s_lm[p][k];
+            int nwn = s_nw[p][k], sn = s_state[p][k], nn = 0;
+            if (tok != g.w.space) {
+              nn = wlm::trie_step(g.w, nk, tok);
+            } else if (nk != 0) {                                  // the pending word closes
+              lmn = __fadd_rn(lmn, s_clp[p][k]);
+              nwn += 1;
+              sn = s_cnx[p][k];
+            }
+            float cl = 0.f;
+            int cn = sn;
+            if (nn != 0) wlm::close_word(g.w, nn, sn, g.lexicon_only != 0, cl, cn);        // the new entry's close pair, once
+            s_lm[q][tid] = lmn;
+            s_state[q][tid] = sn;
+            s_node[q][tid] = nn;
+            s_nw[q][tid] = nwn;
+            s_clp[q][tid] = cl;
+            s_cnx[q][tid] = cn;
           } else {
             s_pnb[q][tid] = my_v;
           }
@@ -312,13 +412,13 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
           s_len[q][tid] = s_len[p][k] + 1;
           s_hash[q][tid] = prefix_hash(s_hash[p][k], tok);
         }
-        if constexpr (!LM) s_tot[q][tid] = my_v;
+        if constexpr (!RK) s_tot[q][tid] = my_v;
         hist[(int64_t)t * K + tid] = make_int2(k, tok);
       } else {
         s_tot[q][tid] = -INFINITY;
       }
     }
-    if constexpr (LM) __syncthreads();                         // update has read xs
+    if constexpr (RK) __syncthreads();                         // update has read xs
     if (t + 1 < len) {
 #pragma unroll
       for (int i = 0; i < kStage; ++i) xs[tid + i * nt] = zn[i] - ln;
@@ -326,6 +426,74 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
     __syncthreads();
     p = q;
     nlive = nsel;
+  }
+  if constexpr (WLM) {
+    // a pending word closes, the end-of-sentence term joins lm, and the entries rank once more as below; with lexicon_only
+    // an entry whose pending node ends no word leaves the list (rank -inf: behind every other, an unused slot).  s_spb and
+    // s_mk are dead after the last frame: they hold the ranks and the positions
+    float* const s_rk = s_spb;
+    int* const s_at = (int*)s_mk;
+    if (tid < nlive) {
+      float lm = s_lm[p][tid];
+      int nwe = s_nw[p][tid], st = s_state[p][tid];
+      bool dead = false;
+      if (s_node[p][tid] != 0) {
+        if (s_cnx[p][tid] < 0) {
+          dead = true;
+        } else {
+          lm = __fadd_rn(lm, s_clp[p][tid]);
+          nwe += 1;
+          st = s_cnx[p][tid];
+        }
+      }
+      if (g.eos_term && !dead) {
+        float lp;
+        int nx;
+        wlm::lookup(g.w, st, g.w.eos, lp, nx);
+        lm = __fadd_rn(lm, lp);
+      }
+      s_lm[p][tid] = lm;
+      s_nw[p][tid] = nwe;
+      s_rk[tid] = dead ? -INFINITY : lm_rank(s_tot[p][tid], lm, nwe, g.alpha, g.beta);
+    }
+    __syncthreads();
+    if (tid < K) {
+      int at = tid;
+      if (tid < nlive) {
+        const float rv = s_rk[tid];
+        at = 0;
+        for (int j = 0; j < nlive; ++j) at += j != tid && better(s_rk[j], j, rv, tid) ? 1 : 0;
+      }
+      const int64_t o = (int64_t)b * K + at;
+      if (tid < nlive && s_rk[tid] != -INFINITY) {
+        int32_t* row = hypb + (int64_t)at * T;
+        const int n = s_len[p][tid];
+        int pos = n - 1, slot = tid;
+        for (int t = len - 1; t >= 0; --t) {
+          const int2 e = hist[(int64_t)t * K + slot];
+          if (e.y != 0 && pos >= 0) row[pos--] = e.y;
+          slot = e.x;
+        }
+        score[o] = s_rk[tid];
+        g.ctc_score[o] = s_tot[p][tid];
+        g.lm_score[o] = s_lm[p][tid];
+        g.n_words[o] = s_nw[p][tid];
+        hyp_len[o] = n;
+      } else {
+        score[o] = -INFINITY;
+        g.ctc_score[o] = -INFINITY;
+        g.lm_score[o] = -INFINITY;
+        g.n_words[o] = -1;
+        hyp_len[o] = -1;
+      }
+      s_at[tid] = at;
+    }
+    __syncthreads();
+    for (int r = 0; r < K; ++r) {
+      const int n = r < nlive && s_rk[r] != -INFINITY ? s_len[p][r] : 0;
+      for (int i = n + tid; i < T; i += nt) hypb[(int64_t)s_at[r] * T + i] = -1;
+    }
+    return;
   }
   if constexpr (LM) {
     // the end-of-sentence term joins lm; the entries rank by lm_rank once more, ties to the search's order (without the term
@@ -401,12 +569,12 @@ int beam_check(int B, int T, int V, int K) {
   return 0;
 }
 
-template <bool LM>
+template <int MODE, class G>
 void launch_ctc_beam(int B, int T, int V, int K, const float* logits, int64_t ld, const int32_t* frame_lens, int32_t* hyp,
-                     int32_t* hyp_len, float* score, const BeamWs& w, const BeamLm& g, hipStream_t stream) {
+                     int32_t* hyp_len, float* score, const BeamWs& w, const G& g, hipStream_t stream) {
   const dim3 grid(B), block((int64_t)K * V <= kOneWaveKV ? 64 : kMaxThreads);
 #define CTC_BEAM(M_) \
-  hipLaunchKernelGGL((ctc_beam_kernel<M_, LM>), grid, block, 0, stream, T, V, K, logits, ld, frame_lens, hyp, hyp_len, score, w, g)
+  hipLaunchKernelGGL((ctc_beam_kernel<M_, MODE>), grid, block, 0, stream, T, V, K, logits, ld, frame_lens, hyp, hyp_len, score, w, g)
   if (K <= 1) CTC_BEAM(1);
   else if (K <= 2) CTC_BEAM(2);
   else if (K <= 4) CTC_BEAM(4);
@@ -434,7 +602,7 @@ extern "C" int asr_ctc_beam_f32(int B, int T, int V, int K, const float* logits,
   const BeamWs w = beam_ws(ws, B, T, K);
   launch_frame_lse(B, T, V, logits, ld, frame_lens, w.lse, (hipStream_t)stream);
   ASR_CHECK_LAUNCH();
-  launch_ctc_beam<false>(B, T, V, K, logits, ld, frame_lens, hyp, hyp_len, score, w, BeamLm{}, (hipStream_t)stream);
+  launch_ctc_beam<kPlain>(B, T, V, K, logits, ld, frame_lens, hyp, hyp_len, score, w, BeamLm{}, (hipStream_t)stream);
   ASR_CHECK_LAUNCH();
   return 0;
 }
@@ -456,7 +624,32 @@ extern "C" int asr_ctc_beam_lm_f32(int B, int T, int V, int K, const float* logi
   BeamLm g;
   g.logp = lm_logp, g.next = lm_next, g.ctc_score = ctc_score, g.lm_score = lm_score;
   g.start = lm_start, g.eos = lm_eos < 0 ? -1 : lm_eos, g.alpha = alpha, g.beta = beta;
-  launch_ctc_beam<true>(B, T, V, K, logits, ld, frame_lens, hyp, hyp_len, score, w, g, (hipStream_t)stream);
+  launch_ctc_beam<kNgram>(B, T, V, K, logits, ld, frame_lens, hyp, hyp_len, score, w, g, (hipStream_t)stream);
+  ASR_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int asr_ctc_beam_wlm_f32(int B, int T, int V, int K, const float* logits, int64_t ld, const int32_t* frame_lens,
+                                    const asr_word_lm_t* lm, float alpha, float beta, int eos_term, int lexicon_only,
+                                    int32_t* hyp, int32_t* hyp_len, float* score, float* ctc_score, float* lm_score,
+                                    int32_t* n_words, void* ws, asr_stream_t stream) {
+  if (!logits || !frame_lens || !hyp || !hyp_len || !score || !ws || ld < V || !ctc_score || !lm_score || !n_words ||
+      !(fabsf(alpha) <= FLT_MAX) || !(fabsf(beta) <= FLT_MAX))
+    return ASR_E_ARG;
+  int rc = wlm::check_abi(lm);
+  if (rc) return rc;
+  rc = beam_check(B, T, V, K);
+  if (rc) return rc;
+  if (lm->V != V) return ASR_E_SHAPE;
+  if ((((uintptr_t)ws) & 7u) != 0) return ASR_E_ALIGN;
+  const BeamWs w = beam_ws(ws, B, T, K);
+  launch_frame_lse(B, T, V, logits, ld, frame_lens, w.lse, (hipStream_t)stream);
+  ASR_CHECK_LAUNCH();
+  BeamWlm g;
+  g.w = wlm::from_abi(*lm);
+  g.ctc_score = ctc_score, g.lm_score = lm_score, g.n_words = n_words;
+  g.alpha = alpha, g.beta = beta, g.eos_term = eos_term != 0, g.lexicon_only = lexicon_only != 0;
+  launch_ctc_beam<kWordLm>(B, T, V, K, logits, ld, frame_lens, hyp, hyp_len, score, w, g, (hipStream_t)stream);
   ASR_CHECK_LAUNCH();
   return 0;
 }

@@ -32,6 +32,7 @@ EXPORTS = (
     "asr_ctc_prefix_init_f32", "asr_ctc_prefix_score_f32", "asr_beam_select_ctc_f32", "asr_ctc_prefix_advance_f32",
     "asr_ctc_align_ws_bytes", "asr_ctc_align_f32", "asr_ctc_greedy_f32",
     "asr_ctc_beam_ws_bytes", "asr_ctc_beam_f32", "asr_ctc_beam_lm_f32", "asr_ngram_score_f32",
+    "asr_word_lm_score_f32", "asr_ctc_beam_wlm_f32",
     "asr_fbank_num_frames", "asr_fbank_plan_bytes", "asr_fbank_f32", "asr_feat_cmvn_stats_f32", "asr_feat_finish_f32",
     "asr_mwer_fwd_f32", "asr_mwer_bwd_f32",
     "asr_resample_plan_bytes", "asr_resample_f32",
@@ -50,6 +51,14 @@ class LstmPackJob(ctypes.Structure):
     """asr_lstm_pack_job_t"""
     _fields_ = [("H", c_i), ("I", c_i), ("ndir", c_i), ("w_ih", c_p * 2), ("w_hh", c_p * 2), ("b_ih", c_p * 2),
                 ("b_hh", c_p * 2), ("w_ih_cat", c_p), ("w_hh_il", c_p), ("bias", c_p)]
+
+
+class WordLmTable(ctypes.Structure):
+    """asr_word_lm_t"""
+    _fields_ = [("V", ctypes.c_int32), ("N", ctypes.c_int32), ("S", ctypes.c_int32), ("W", ctypes.c_int32), ("A", c_i64),
+                ("space", ctypes.c_int32), ("start", ctypes.c_int32), ("empty", ctypes.c_int32), ("eos", ctypes.c_int32),
+                ("unk", ctypes.c_int32), ("trie_next", c_p), ("trie_word", c_p), ("arc_off", c_p), ("arc_word", c_p),
+                ("arc_logp", c_p), ("arc_next", c_p), ("bo_logp", c_p), ("bo_state", c_p), ("uni_logp", c_p), ("uni_next", c_p)]
 
 
 class LstmUnpackJob(ctypes.Structure):
@@ -283,6 +292,9 @@ def load():
     lib.asr_ctc_beam_lm_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_i, c_p, c_p, c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_p, c_p,
                                         c_p, c_p]
     lib.asr_ngram_score_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p]
+    lib.asr_word_lm_score_f32.argtypes = [c_i, c_i, ctypes.POINTER(WordLmTable), c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]
+    lib.asr_ctc_beam_wlm_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, ctypes.POINTER(WordLmTable), c_f, c_f, c_i, c_i, c_p, c_p,
+                                         c_p, c_p, c_p, c_p, c_p, c_p]
     lib.asr_fbank_num_frames.argtypes = [c_i64, c_i, c_i, ctypes.POINTER(c_i64)]
     lib.asr_fbank_plan_bytes.argtypes = [c_i, ctypes.POINTER(c_i64)]
     lib.asr_fbank_f32.argtypes = [c_i, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_i64, c_i64, c_p]
@@ -1167,6 +1179,80 @@ def ctc_beam_lm(logits, frame_lens, K, table, alpha, beta, eos_term, hyp, hyp_le
     check(rc, "asr_ctc_beam_lm_f32")
     LAUNCHES["ctc_beam_lm"] += 1
     LAUNCHES["ctc_beam_lm_launch"] += 2
+
+
+_WORD_LM_DTYPES = dict(trie_next=torch.int32, trie_word=torch.int32, arc_off=torch.int32, arc_word=torch.int32,
+                       arc_logp=torch.float32, arc_next=torch.int32, bo_logp=torch.float32, bo_state=torch.int32,
+                       uni_logp=torch.float32, uni_next=torch.int32)
+
+
+def _word_lm_table(table, what):
+    """The device form of a word LM (word_lm.WordTable after .to(device)) -> asr_word_lm_t; the tensors stay the table's."""
+    t = WordLmTable()
+    for name, dtype in _WORD_LM_DTYPES.items():
+        a = getattr(table, name)
+        if not (isinstance(a, torch.Tensor) and a.is_cuda):
+            raise RuntimeError("%s: the word LM's tables are not on the device (WordLM.to(device))" % what)
+        if a.dtype != dtype or not a.is_contiguous() or a.numel() == 0:
+            raise RuntimeError("%s: the word LM's %s must be a contiguous, non-empty %s tensor" % (what, name, dtype))
+        setattr(t, name, ptr(a))
+    shapes = dict(trie_next=table.N * table.V, trie_word=table.N, arc_off=table.S + 1, arc_word=max(table.A, 1),
+                  arc_logp=max(table.A, 1), arc_next=max(table.A, 1), bo_logp=table.S, bo_state=table.S, uni_logp=table.W,
+                  uni_next=table.W)
+    for name, n in shapes.items():
+        if getattr(table, name).numel() != n:
+            raise RuntimeError("%s: the word LM's %s holds %d elements, its sizes say %d" % (what, name, getattr(table, name).numel(), n))
+    t.V, t.N, t.S, t.W, t.A = table.V, table.N, table.S, table.W, table.A
+    t.space, t.start, t.empty, t.eos, t.unk = table.space, table.start, table.empty, table.eos, table.unk
+    return t
+
+
+def word_lm_score(table, ids, lens, score, n_words, word_score=None, eos_term=True):
+    """asr_word_lm_score_f32 (csrc/word_lm.hip): the word LM's log-probability of N padded TOKEN id rows.
+    table: the LM on the device; ids int32 [N, L] (a view with row stride >= L is taken as it is), lens int32 [N] (-1: an
+    unused slot, -inf); score fp32 [N], n_words int32 [N] and word_score (fp32 [N, L] or None) are the caller's.  One launch."""
+    if ids.dim() != 2 or ids.dtype != torch.int32 or ids.stride(1) != 1 or lens.dtype != torch.int32:
+        raise RuntimeError("word_lm_score: ids must be int32 [N, L] with unit column stride, lens int32")
+    N, L = ids.shape
+    t = _word_lm_table(table, "word_lm_score")
+    if lens.numel() != N or score.numel() != N or n_words.numel() != N or score.dtype != torch.float32 or \
+            n_words.dtype != torch.int32 or not (lens.is_contiguous() and score.is_contiguous() and n_words.is_contiguous()):
+        raise RuntimeError("word_lm_score: lens, score and n_words must be contiguous with %d elements" % N)
+    if word_score is not None and (tuple(word_score.shape) != (N, L) or not word_score.is_contiguous() or
+                                   word_score.dtype != torch.float32):
+        raise RuntimeError("word_lm_score: word_score must be contiguous fp32 [%d, %d]" % (N, L))
+    rc = load().asr_word_lm_score_f32(N, L, ctypes.byref(t), 1 if eos_term else 0, ptr(ids), int(ids.stride(0)), ptr(lens),
+                                      ptr(score), ptr(n_words), ptr(word_score) if word_score is not None else None, stream())
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("word_lm_score: a table of %d x %d trie entries, %d states, %d words" % (t.N, t.V, t.S, t.W))
+    check(rc, "asr_word_lm_score_f32")
+    LAUNCHES["word_lm_score"] += 1
+
+
+def ctc_beam_wlm(logits, frame_lens, K, table, alpha, beta, eos_term, lexicon_only, hyp, hyp_len, score, ctc_score, lm_score,
+                 n_words, ws):
+    """asr_ctc_beam_wlm_f32 (csrc/ctc_beam.hip): ctc_beam with the lexicon and the word LM `table` (on the
+    device) inside the search - candidates rank by (tot + alpha lm) + beta n_words.  The arguments and outputs of
+    ctc_beam_lm, and n_words int32 [B, K].  Two launches."""
+    logits, ld = _ctc_view(logits, "ctc logits")
+    B, T, V = logits.shape
+    if table.V != V:
+        raise UnsupportedShape("ctc_beam_wlm: the word LM spells in %d tokens, the logits are over %d" % (table.V, V))
+    t = _word_lm_table(table, "ctc_beam_wlm")
+    need = ctc_beam_ws_bytes(B, T, V, K)
+    outs = (hyp_len, score, ctc_score, lm_score, n_words)
+    if ws.numel() * 4 < need or tuple(hyp.shape) != (B, K, T) or any(o.numel() != B * K for o in outs):
+        raise RuntimeError("ctc_beam_wlm: the workspace or an output is smaller than B %d, T %d, beam %d need" % (B, T, K))
+    if not (hyp.is_contiguous() and all(o.is_contiguous() for o in outs)):
+        raise RuntimeError("ctc_beam_wlm: the outputs must be contiguous")
+    rc = load().asr_ctc_beam_wlm_f32(B, T, V, int(K), ptr(logits), int(ld), ptr(frame_lens), ctypes.byref(t), float(alpha),
+                                     float(beta), 1 if eos_term else 0, 1 if lexicon_only else 0, ptr(hyp), ptr(hyp_len),
+                                     ptr(score), ptr(ctc_score), ptr(lm_score), ptr(n_words), ptr(ws), stream())
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("ctc_beam_wlm: B %d, T %d, V %d, beam %d, a word LM over %d tokens" % (B, T, V, K, table.V))
+    check(rc, "asr_ctc_beam_wlm_f32")
+    LAUNCHES["ctc_beam_wlm"] += 1
+    LAUNCHES["ctc_beam_wlm_launch"] += 2
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -556,8 +556,27 @@ class Decoder(torch.nn.Module):
         if self.pad != 0:
             raise ValueError("the n-gram LM keeps id 0 for the CTC blank; pad is %d" % self.pad)
 
+    def check_word_lm(self, word_lm, ngram=None):
+        """ValueError unless word_lm (a word_lm.WordLM, or None) spells in the decoder's vocabulary, its <BOS> / <EOS> (where it
+        names them) are the decoder's, <PAD> = 0 is free to be the CTC blank, and no n-gram LM is given beside it."""
+        if word_lm is None:
+            return
+        if ngram is not None:
+            raise ValueError("ngram and word_lm are two LMs for one search: pass one of them")
+        V = self.output_layer.weight.shape[0]
+        if word_lm.V != V:
+            raise ValueError("the word LM spells in %d tokens, the decoder predicts %d" % (word_lm.V, V))
+        for name, mine, theirs in (("<BOS>", self.bos, word_lm.bos), ("<EOS>", self.eos, word_lm.eos)):
+            if theirs is not None and theirs != mine:
+                raise ValueError("the word LM's %s (%d) is not the decoder's (%d)" % (name, theirs, mine))
+        if word_lm.space in (self.bos, self.eos, self.pad):
+            raise ValueError("the word LM's <space> (%d) is the decoder's <BOS>, <EOS> or <PAD>" % word_lm.space)
+        if self.pad != 0:
+            raise ValueError("the word LM keeps id 0 for the CTC blank; pad is %d" % self.pad)
+
     def rescore_ctc_beams(self, enc_pad, enc_len, ctc_logits, ctc_lens, topk, ctc_weight=0.5, length_penalty=0.0, *, lm=None,
-                          lm_weight=0.0, ngram=None, ngram_weight=0.0, ngram_bonus=0.0):
+                          lm_weight=0.0, ngram=None, ngram_weight=0.0, ngram_bonus=0.0, word_lm=None, word_lm_weight=0.0,
+                          word_bonus=0.0, lexicon_only=False, eos_term=True):
         """Two-pass decoding behind the encoder (E2E.recognize_two_pass): ops.ctc_beam over ctc_logits [B, T', V]
         (raw logits of a CTC head on enc_pad, blank = <PAD> = 0; ctc_lens int32 [B] on the device), score_hypotheses over
         the B topk rows, with lm and lm_weight != 0 LM.forward over the same rows, then the combination
@@ -568,16 +587,26 @@ class Decoder(torch.nn.Module):
         ranking by (ctc + ngram_weight lm_ngram) + ngram_bonus len, the end-of-sentence term on - and the combination is
         ((1 - w) att + w ctc + lm_weight lm + ngram_weight lm_ngram + ngram_bonus len) / (len + 1)**length_penalty, ctc
         the search's ctc_score and lm_ngram its lm_score; the parts then also hold ngram (lm_ngram) and rank (the search's
-        score)."""
+        score).
+        With word_lm (a word_lm.WordLM) the first pass is the search with the lexicon and the word LM inside
+        (lexicon_only and eos_term are the search's), and the combination is
+        ((((1 - w) att + w ctc) + lm_weight lm) + word_lm_weight lm_word) + word_bonus n_words, then / (len + 1)**length_penalty:
+        fp32, the two products and the two sums of the word term each rounded on their own, where the n-gram term stands;
+        the parts then also hold word_lm (lm_word), n_words and rank."""
         K, w = int(topk), float(ctc_weight)
         if self.pad != 0:
             raise ValueError("the CTC search takes <PAD> = 0 as its blank; pad is %d" % self.pad)
         self.check_lm(lm)
         self.check_ngram(ngram)
+        self.check_word_lm(word_lm, ngram)
         use_lm = lm is not None and float(lm_weight) != 0.0
         with torch.no_grad():
-            ng = rank = None
-            if ngram is None:
+            ng = rank = n_words = None
+            if word_lm is not None:
+                hyp, hyp_len, rank, ctc, ng, n_words = ops.ctc_beam(ctc_logits, ctc_lens, K, word_lm=word_lm,
+                                                                    word_lm_weight=word_lm_weight, word_bonus=word_bonus,
+                                                                    lexicon_only=lexicon_only, eos_term=eos_term)
+            elif ngram is None:
                 hyp, hyp_len, ctc = ops.ctc_beam(ctc_logits, ctc_lens, K)
             else:
                 hyp, hyp_len, rank, ctc, ng = ops.ctc_beam(ctc_logits, ctc_lens, K, ngram=ngram, ngram_weight=ngram_weight,
@@ -601,6 +630,9 @@ class Decoder(torch.nn.Module):
             if ngram is not None:
                 total = total + ng * float(torch.tensor(float(ngram_weight), dtype=torch.float32))
                 total = total + hyp_len.clamp(min=0).to(torch.float32) * float(torch.tensor(float(ngram_bonus), dtype=torch.float32))
+            if word_lm is not None:
+                total = total + ng * float(torch.tensor(float(word_lm_weight), dtype=torch.float32))
+                total = total + n_words.clamp(min=0).to(torch.float32) * float(torch.tensor(float(word_bonus), dtype=torch.float32))
             if float(length_penalty) != 0.0:
                 total = total / (hyp_len.clamp(min=0) + 1).to(torch.float32).pow(float(length_penalty))
             total = torch.where(hyp_len >= 0, total, torch.full_like(total, float("-inf")))
@@ -610,6 +642,8 @@ class Decoder(torch.nn.Module):
         parts = dict(hyp=hyp, hyp_len=hyp_len, ctc=ctc, att=att, lm=lm_score, order=order)
         if ngram is not None:
             parts.update(ngram=ng, rank=rank)
+        if word_lm is not None:
+            parts.update(word_lm=ng, n_words=n_words, rank=rank)
         return tokens, scores, parts
 
 
@@ -759,19 +793,29 @@ class E2E(torch.nn.Module):
             raise ValueError("beam width %d outside 1..%d" % (K, hb.BEAM_KMAX))
         return K
 
-    def recognize_ctc_beams(self, xs, ilens, topk, nbest=False, *, ngram=None, ngram_weight=0.0, ngram_bonus=0.0):
+    def recognize_ctc_beams(self, xs, ilens, topk, nbest=False, *, ngram=None, ngram_weight=0.0, ngram_bonus=0.0, word_lm=None,
+                            word_lm_weight=0.0, word_bonus=0.0, lexicon_only=False, eos_term=True):
         """CTC prefix beam search with the CTC head alone (not a reference method): encoder, the head,
         ops.ctc_beam with beam width topk (1..16) -> (ids, scores): per utterance the best label sequence (an id list) and
         its log-mass; with nbest=True per utterance the ranked list of all hypotheses the search kept (at most topk) and
         the list of their scores.  The device results are read once.
         With ngram (an ngram.NgramLM over the decoder's vocabulary) the LM sits inside the search: hypotheses
         rank by (log-mass + ngram_weight lm) + ngram_bonus len with the LM's end-of-sentence term, and the scores are
-        those ranks; self.last_ctc_beams then also holds ctc_score and lm_score."""
+        those ranks; self.last_ctc_beams then also holds ctc_score and lm_score.
+        With word_lm (a word_lm.WordLM spelled in the decoder's vocabulary) the lexicon and the word LM sit
+        inside the search: hypotheses rank by (log-mass + word_lm_weight lm) + word_bonus n_words, lexicon_only keeps only
+        sequences of lexicon words (an utterance may then keep no hypothesis: an empty list; without nbest the empty id
+        list at -inf); self.last_ctc_beams then holds ctc_score, lm_score and n_words too."""
         K = self._beam_width(topk)
         self.decoder.check_ngram(ngram)
+        self.decoder.check_word_lm(word_lm, ngram)
         with torch.no_grad():
             logits, lens_dev, _ = self._ctc_logits(xs, ilens, "recognize_ctc_beams")
-            if ngram is None:
+            if word_lm is not None:
+                beams = ops.ctc_beam(logits, lens_dev, K, word_lm=word_lm, word_lm_weight=word_lm_weight, word_bonus=word_bonus,
+                                     lexicon_only=lexicon_only, eos_term=eos_term)
+                hyp, hyp_len, score = beams[:3]
+            elif ngram is None:
                 hyp, hyp_len, score = beams = ops.ctc_beam(logits, lens_dev, K)
             else:
                 beams = ops.ctc_beam(logits, lens_dev, K, ngram=ngram, ngram_weight=ngram_weight, ngram_bonus=ngram_bonus,
@@ -784,7 +828,28 @@ class E2E(torch.nn.Module):
         scores = [[row[1] for row in utt if row[0] >= 0] for utt in host]
         if nbest:
             return ids, scores
+        if word_lm is not None:                                  # (lexicon_only may leave an utterance without a hypothesis)
+            return [u[0] if u else [] for u in ids], [u[0] if u else float("-inf") for u in scores]
         return [u[0] for u in ids], [u[0] for u in scores]
+
+    def word_lm_score(self, word_lm, ids, eos_term=True):
+        """The word LM's log-probability (ops.word_lm_score) of hypotheses this model produced, to rescore any
+        list with: ids as E2E.ngram_score takes them (a device tensor [..., L], <EOS>-padded, a row counting up to its first
+        <EOS> - or a list of id lists).  -> (fp32 [...] scores, int32 [...] numbers of words) on the device."""
+        self.decoder.check_word_lm(word_lm)
+        if not isinstance(ids, torch.Tensor):
+            rows = [[int(c) for c in row] for row in ids]
+            L = max([len(r) for r in rows] + [1])
+            dev = next(self.parameters()).device
+            flat = torch.tensor([r + [self.decoder.eos] * (L - len(r)) for r in rows], dtype=torch.int32).to(dev)
+            lens = hb.to_device_i32([len(r) for r in rows], dev)
+            return ops.word_lm_score(word_lm, flat, lens, eos_term=eos_term)
+        L = ids.shape[-1]
+        flat = ids.reshape(-1, L)
+        is_eos = flat == self.decoder.eos
+        first = torch.where(is_eos.any(dim=1), is_eos.to(torch.int32).argmax(dim=1), torch.full_like(flat[:, 0], L)).to(torch.int32)
+        score, n_words = ops.word_lm_score(word_lm, flat, first, eos_term=eos_term)
+        return score.view(ids.shape[:-1]), n_words.view(ids.shape[:-1])
 
     def ngram_score(self, ngram, ids, eos_term=True):
         """The n-gram LM's log-probability (ops.ngram_score) of hypotheses this model produced, to rescore any
@@ -806,7 +871,8 @@ class E2E(torch.nn.Module):
         return ops.ngram_score(ngram, flat, first, eos_term=eos_term).view(ids.shape[:-1])
 
     def recognize_two_pass(self, xs, ilens, topk, ctc_weight=0.5, length_penalty=0.0, nbest=False, *, lm=None, lm_weight=0.0,
-                           ngram=None, ngram_weight=0.0, ngram_bonus=0.0):
+                           ngram=None, ngram_weight=0.0, ngram_bonus=0.0, word_lm=None, word_lm_weight=0.0, word_bonus=0.0,
+                           lexicon_only=False, eos_term=True):
         """Two-pass decoding (not a reference method): the CTC prefix beam search of the head proposes topk
         (1..16) hypotheses per utterance, ONE teacher-forced pass of the attention decoder over the B topk rows scores them
         (Decoder.score_hypotheses), and with lm (an LM module) and lm_weight != 0 one teacher-forced pass of the LM too.
@@ -819,7 +885,10 @@ class E2E(torch.nn.Module):
         between the passes.  self.last_two_pass keeps the parts (hyp, hyp_len, ctc, att, lm, order).
         With ngram (an ngram.NgramLM) the first pass is the search with the LM inside, and the score is
         ((1 - w) att + w ctc + lm_weight lm + ngram_weight lm_ngram + ngram_bonus len) / (len + 1)**length_penalty, in this
-        order, with ctc the search's ctc_score and lm_ngram its lm_score (parts: also ngram and rank)."""
+        order, with ctc the search's ctc_score and lm_ngram its lm_score (parts: also ngram and rank).
+        With word_lm (a word_lm.WordLM) the first pass is the search with the lexicon and the word LM inside, and
+        the score gains + word_lm_weight lm_word + word_bonus n_words where the n-gram term stands, before the length
+        penalty (parts: also word_lm, n_words and rank)."""
         K = self._beam_width(topk)
         w = float(ctc_weight)
         if not 0.0 <= w <= 1.0:
@@ -827,7 +896,11 @@ class E2E(torch.nn.Module):
         dec = self.decoder
         dec.check_lm(lm)
         dec.check_ngram(ngram)
+        dec.check_word_lm(word_lm, ngram)
         extra = {} if ngram is None else dict(ngram=ngram, ngram_weight=ngram_weight, ngram_bonus=ngram_bonus)
+        if word_lm is not None:
+            extra = dict(word_lm=word_lm, word_lm_weight=word_lm_weight, word_bonus=word_bonus, lexicon_only=lexicon_only,
+                         eos_term=eos_term)
         with torch.no_grad():
             logits, lens_dev, enc_lens, enc_h = self._encode_ctc(xs, ilens, "recognize_two_pass")
             tokens, scores, parts = dec.rescore_ctc_beams(enc_h, enc_lens, logits, lens_dev, K, ctc_weight=w,

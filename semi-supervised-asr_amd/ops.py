@@ -1087,14 +1087,21 @@ def ctc_greedy(logits, frame_lens_dev):
     return ids, n, frame_tok
 
 
-def ctc_beam(logits, frame_lens_dev, beam, ngram=None, ngram_weight=0.0, ngram_bonus=0.0, eos_term=True):
+def ctc_beam(logits, frame_lens_dev, beam, ngram=None, ngram_weight=0.0, ngram_bonus=0.0, eos_term=True, *, word_lm=None,
+             word_lm_weight=0.0, word_bonus=0.0, lexicon_only=False):
     """-> (hyp int32 [B, beam, T'] padded with -1, hyp_len int32 [B, beam] with -1 in unused slots, score fp32 [B, beam]
     descending with -inf in unused slots): the CTC prefix beam search of raw logits [B, T', V] (blank = 0), asr_ctc_beam_f32
     (csrc/ctc_beam.hip), two launches.  Forward only, no host synchronisation.
     With ngram (an ngram.NgramLM, or its table on the device) the LM sits inside the search (asr_ctc_beam_lm_f32, DESIGN
     4.23, two launches): candidates rank by (tot + ngram_weight lm) + ngram_bonus len, eos_term adds the LM's
     end-of-sentence term after the last frame -> (hyp, hyp_len, score: the rank, ctc_score fp32 [B, beam]: tot, lm_score
-    fp32 [B, beam]: lm).  Without ngram the call, its launches and its bits are what they were."""
+    fp32 [B, beam]: lm).  Without ngram the call, its launches and its bits are what they were.
+    With word_lm (a word_lm.WordLM, or its table on the device) the lexicon and the word-level LM sit inside the search
+    (asr_ctc_beam_wlm_f32, DESIGN 4.25, two launches): candidates rank by (tot + word_lm_weight lm) + word_bonus n_words with
+    lm the sum over the completed words; lexicon_only keeps only sequences of lexicon words -> (hyp, hyp_len, score,
+    ctc_score, lm_score, n_words int32 [B, beam] with -1 in unused slots).  ngram and word_lm together: ValueError."""
+    if ngram is not None and word_lm is not None:
+        raise ValueError("ctc_beam: ngram and word_lm are two LMs for one search: pass one of them")
     logits = logits.detach()
     B, T, V = logits.shape
     K, dev = int(beam), logits.device
@@ -1102,10 +1109,15 @@ def ctc_beam(logits, frame_lens_dev, beam, ngram=None, ngram_weight=0.0, ngram_b
     hyp = torch.empty(B, K, T, device=dev, dtype=torch.int32)
     hyp_len = torch.empty(B, K, device=dev, dtype=torch.int32)
     score = torch.empty(B, K, device=dev, dtype=torch.float32)
-    if ngram is None:
+    if ngram is None and word_lm is None:
         hb.ctc_beam(logits, frame_lens_dev, K, hyp, hyp_len, score, ws)
         return hyp, hyp_len, score
     ctc_score, lm_score = torch.empty_like(score), torch.empty_like(score)
+    if word_lm is not None:
+        n_words = torch.empty_like(hyp_len)
+        hb.ctc_beam_wlm(logits, frame_lens_dev, K, word_lm.to(dev), float(word_lm_weight), float(word_bonus), bool(eos_term),
+                        bool(lexicon_only), hyp, hyp_len, score, ctc_score, lm_score, n_words, ws)
+        return hyp, hyp_len, score, ctc_score, lm_score, n_words
     hb.ctc_beam_lm(logits, frame_lens_dev, K, _ngram_table(ngram, dev), float(ngram_weight), float(ngram_bonus), bool(eos_term),
                    hyp, hyp_len, score, ctc_score, lm_score, ws)
     return hyp, hyp_len, score, ctc_score, lm_score
@@ -1134,6 +1146,28 @@ def ngram_score(ngram, ids, lens, eos_term=True, per_token=False):
     tok = torch.empty(N, L, device=dev, dtype=torch.float32) if per_token else None
     hb.ngram_score(_ngram_table(ngram, dev), ids, lens.to(torch.int32).contiguous(), score, tok, eos_term=eos_term)
     return (score, tok) if per_token else score
+
+
+def word_lm_score(word_lm, ids, lens, eos_term=True, per_word=False):
+    """-> (score fp32 [N], n_words int32 [N]) (and with per_word the terms fp32 [N, L], word j at column j): the word LM's
+    log-probability of the padded TOKEN id rows ids [N, L] (int32 or int64, on the device) with lens int32 [N] (-1: an unused
+    slot, -inf) - the row's words (split at <space>, spelled through the lexicon, <unk> outside it) in order from the context
+    <s>, with the end-of-sentence term when eos_term: asr_word_lm_score_f32 (csrc/word_lm.hip), one launch.  An
+    id outside 0 .. V-1 inside the length gives NaN for that row.  No host synchronisation."""
+    ids = ids.detach()
+    if ids.dtype != torch.int32:
+        ids = ids.to(torch.int32)
+    if ids.dim() != 2:
+        raise ValueError("word_lm_score: ids must be [N, L], got %r" % (tuple(ids.shape),))
+    if ids.stride(1) != 1:
+        ids = ids.contiguous()
+    N, L = ids.shape
+    dev = ids.device
+    score = torch.empty(N, device=dev, dtype=torch.float32)
+    n_words = torch.empty(N, device=dev, dtype=torch.int32)
+    terms = torch.empty(N, L, device=dev, dtype=torch.float32) if per_word else None
+    hb.word_lm_score(word_lm.to(dev), ids, lens.to(torch.int32).contiguous(), score, n_words, terms, eos_term=eos_term)
+    return (score, n_words, terms) if per_word else (score, n_words)
 
 
 def decoder_sequence(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo, w_out, b_out, w0, opts):

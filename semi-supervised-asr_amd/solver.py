@@ -382,15 +382,50 @@ class Solver(object):
                              "attention beam search, greedy and ctc_greedy_decode have no place for an n-gram LM")
         return ctc_beam, path, float(config.get("ngram_weight", 0.0) or 0.0), float(config.get("ngram_bonus", 0.0) or 0.0)
 
+    @staticmethod
+    def word_lm_config(config, two_pass, ctc_beam):
+        """The word LM keys (not reference keys; absent by default): `word_lm` is the path of an ARPA file over
+        WORDS spelled in the vocabulary's characters, used with its lexicon inside the CTC prefix beam search
+        (`ctc_beam_decode`) or the first pass and the combination of `two_pass_decode`; `lexicon` an optional path, one word
+        per line (default: the ARPA unigrams); `word_lm_weight` and `word_bonus` weigh its log-probability and the number of
+        words; `lexicon_only` keeps only sequences of lexicon words.  -> (path or None, lexicon path or None, weight,
+        bonus, lexicon_only).  ValueError: `word_lm` with any other decoder or beside `ngram_lm`, another of the keys
+        without `word_lm`."""
+        path = config.get("word_lm")
+        if path is None:
+            for key in ("lexicon", "word_lm_weight", "word_bonus", "lexicon_only"):
+                if config.get(key):
+                    raise ValueError("%s is set without word_lm, the ARPA file it goes with" % key)
+            return None, None, 0.0, 0.0, False
+        if config.get("ngram_lm") is not None:
+            raise ValueError("word_lm and ngram_lm are two LMs for one search: set one of them")
+        if not (ctc_beam or two_pass):
+            raise ValueError("word_lm is used by the CTC prefix beam search: set ctc_beam_decode or two_pass_decode - the "
+                             "other decoders have no place for it")
+        return path, config.get("lexicon"), float(config.get("word_lm_weight", 0.0) or 0.0), \
+            float(config.get("word_bonus", 0.0) or 0.0), bool(config.get("lexicon_only", False))
+
+    def load_word_lm(self, path, lexicon_path=None):
+        """The WordLM of an ARPA file over words spelled in this vocabulary's one-character symbols, split at <space>."""
+        from word_lm import WordLM
+        if "<space>" not in self.vocab:
+            raise ValueError("word_lm needs <space> in the vocabulary: words are what lies between two of them")
+        lexicon = None
+        if lexicon_path is not None:
+            with open(lexicon_path, "r", encoding="utf-8") as f:
+                lexicon = [line.split()[0] for line in f if line.strip()]
+        chars = {s: i for s, i in self.vocab.items() if len(s) == 1}
+        return WordLM.from_arpa(path, chars, self.vocab["<space>"], lexicon=lexicon, bos=self.vocab["<BOS>"],
+                                eos=self.vocab["<EOS>"], V=len(self.vocab))
+
     def _ctc_beams(self, xs, ilens, beam_size, ngram=None, nbest=False):
         """Hypothesis ids of the CTC prefix beam search for one batch (E2E.recognize_ctc_beams, with the n-gram LM inside
         when there is one) - with nbest beam_size id lists per utterance, ranked, a rank the search left unused as a row
         of <EOS>; the abort word of the encoder's persistent kernels is checked after the decode, as in _greedy."""
-        lm, w, bonus = ngram if ngram is not None else (None, 0.0, 0.0)
+        extra = self._lm_kwargs(ngram)
 
         def run():
-            ids, _ = self.model.recognize_ctc_beams(xs, ilens, beam_size, nbest=nbest,
-                                                    **({} if lm is None else dict(ngram=lm, ngram_weight=w, ngram_bonus=bonus)))
+            ids, _ = self.model.recognize_ctc_beams(xs, ilens, beam_size, nbest=nbest, **extra)
             if nbest:
                 eos = self.vocab["<EOS>"]
                 width = max(len(h) for hyps in ids for h in hyps) + 1
@@ -404,11 +439,20 @@ class Solver(object):
             out = run()
         return out
 
+    @staticmethod
+    def _lm_kwargs(ngram):
+        """ngram: None, (the NgramLM, its weight, the length bonus), or the keyword arguments of a word LM as a dict."""
+        if ngram is None:
+            return {}
+        if isinstance(ngram, dict):
+            return ngram
+        return dict(ngram=ngram[0], ngram_weight=ngram[1], ngram_bonus=ngram[2])
+
     def _two_pass(self, xs, ilens, beam_size, ctc_weight, lm_weight=0.0, nbest=False, ngram=None):
         """Two-pass hypothesis ids for one batch (E2E.recognize_two_pass) - with nbest all beam_size of them per utterance,
         ranked ([B][K][L]); the abort word of the persistent kernels is checked after the decode and the batch repeated on
         the per-step kernels, as in _greedy.  ngram: (the NgramLM, its weight, the length bonus) or None."""
-        extra = {} if ngram is None else dict(ngram=ngram[0], ngram_weight=ngram[1], ngram_bonus=ngram[2])
+        extra = self._lm_kwargs(ngram)
 
         def run():
             prediction, _ = self.model.recognize_two_pass(
@@ -517,6 +561,10 @@ class Solver(object):
             from ngram import NgramLM
             ngram = (NgramLM.from_arpa(ngram_path, {s: i for s, i in self.vocab.items() if s not in ("<s>", "</s>")},
                                        self.vocab["<BOS>"], self.vocab["<EOS>"], V=len(self.vocab)), ngram_w, ngram_bonus)
+        wlm_path, lexicon_path, wlm_w, word_bonus, lexicon_only = self.word_lm_config(self.config, two_pass, ctc_beam)
+        if wlm_path is not None:
+            ngram = dict(word_lm=self.load_word_lm(wlm_path, lexicon_path), word_lm_weight=wlm_w, word_bonus=word_bonus,
+                         lexicon_only=lexicon_only)
         if state_dict:
             self.model.load_state_dict(state_dict)
         else:
