@@ -37,6 +37,10 @@ def _load(golden_dir, name):
 # Product arithmetics of asr_gemm_f32 (include/asr_hip.h) and the tolerance each is held to, relative to the largest
 # output: the default bf16x6 (three-term split, six products) is fp32-equivalent and gets the fp32 tolerance.
 GEMM_ARITH = [("bf16x6", 1e-5), ("f32", 1e-5), ("bf16x3", 3e-5)]
+GEMM_ATOL = 1e-4
+# the LSTM layer against the oracle: outputs, gradients (shared with tests/test_poison_gpu.py)
+LSTM_Y_GATE = dict(rtol=1e-4, atol=1e-5)
+LSTM_GRAD_GATE = dict(rtol=1e-3, atol=1e-5)
 
 
 @pytest.mark.parametrize("arith,rtol", GEMM_ARITH)
@@ -54,7 +58,7 @@ def test_gemm_variants(ta, tb, M, N, K, arith, rtol):
     B = torch.randn((N, K) if tb else (K, N), generator=g)
     bias = torch.randn(N, generator=g)
     ref = (A.double().t() if ta else A.double()) @ (B.double().t() if tb else B.double())
-    tol = dict(rtol=rtol, atol=1e-4)
+    tol = dict(rtol=rtol, atol=GEMM_ATOL)
     with hb.arith(arith):
         out = hb.gemm(A.to(dev), B.to(dev), trans_a=ta, trans_b=tb)
         _close(out, ref.float(), what="plain", **tol)
@@ -311,13 +315,13 @@ def test_lstm_layer_fwd_bwd(ndir, B, T, I, H, lens):
     gp = [p.to(dev).requires_grad_(True) for p in prm]
     xg = x.to(dev).requires_grad_(True)
     got = ops.lstm_layer(xg.transpose(0, 1), torch.tensor(lens, dtype=torch.int32, device=dev), gp, ndir)
-    _close(got.transpose(0, 1), ref, rtol=1e-4, atol=1e-5, what="y")
+    _close(got.transpose(0, 1), ref, what="y", **LSTM_Y_GATE)
     dy = torch.randn(ref.shape, generator=g)
     ref.backward(dy)
     got.backward(dy.transpose(0, 1).contiguous().to(dev))
-    _close(xg.grad, xc.grad, rtol=1e-3, atol=1e-5, what="dx")
+    _close(xg.grad, xc.grad, what="dx", **LSTM_GRAD_GATE)
     for i, (a, b) in enumerate(zip(gp, cp)):
-        _close(a.grad, b.grad, rtol=1e-3, atol=1e-5, what="param %d" % i)
+        _close(a.grad, b.grad, what="param %d" % i, **LSTM_GRAD_GATE)
 
 
 # ----------------------------------------------------------------------------------------- full model
@@ -804,9 +808,9 @@ def test_lstm_persistent_path(ndir, B, T, lens, H):
         got.backward(dy.transpose(0, 1).contiguous().to(dev))
     assert hb.LAUNCHES["lstm_fwd_persist"] == 1 and hb.LAUNCHES["lstm_bwd_persist"] == 1, dict(hb.LAUNCHES)
     assert hb.LAUNCHES["lstm_fwd_step"] == 0 and hb.LAUNCHES["lstm_bwd_step"] == 0, dict(hb.LAUNCHES)
-    _close(xg.grad, xc.grad, rtol=1e-3, atol=1e-5, what="dx")
+    _close(xg.grad, xc.grad, what="dx", **LSTM_GRAD_GATE)
     for i, (a, b) in enumerate(zip(gp, cp)):
-        _close(a.grad, b.grad, rtol=1e-3, atol=1e-5, what="param %d" % i)
+        _close(a.grad, b.grad, what="param %d" % i, **LSTM_GRAD_GATE)
 
 
 def _packed_lstm_case(ndir, B, T, H, sub, lens=None, persistent=False, I=24):
@@ -847,7 +851,7 @@ def _packed_lstm_case(ndir, B, T, H, sub, lens=None, persistent=False, I=24):
     dyp = torch.randn(rows.R, ndir * H, generator=g)               # noise on the padding rows: must not reach any gradient
     for b_, n_ in enumerate(lens):
         r0, e_ = int(layout.base[0][b_]), int(layout.ext[0][b_])
-        _close(gy[r0:r0 + n_], ref[b_, :n_], rtol=1e-4, atol=1e-5, what="y of utterance %d" % b_)
+        _close(gy[r0:r0 + n_], ref[b_, :n_], what="y of utterance %d" % b_, **LSTM_Y_GATE)
         assert float(gy[r0 + n_:r0 + e_].abs().max()) == 0.0, "padding rows of a block hold zeros"
         dyp[r0:r0 + n_] = dy[b_, :n_]
     ref.backward(dy)
@@ -861,10 +865,10 @@ def _packed_lstm_case(ndir, B, T, H, sub, lens=None, persistent=False, I=24):
     gx = xp.grad.cpu()
     for b_, n_ in enumerate(lens):
         r0, e_ = int(layout.base[0][b_]), int(layout.ext[0][b_])
-        _close(gx[r0:r0 + n_], xc.grad[b_, :n_], rtol=1e-3, atol=1e-5, what="dx of utterance %d" % b_)
+        _close(gx[r0:r0 + n_], xc.grad[b_, :n_], what="dx of utterance %d" % b_, **LSTM_GRAD_GATE)
         assert float(gx[r0 + n_:r0 + e_].abs().max()) == 0.0
     for i, (a, b) in enumerate(zip(gp, cp)):
-        _close(a.grad, b.grad, rtol=1e-3, atol=1e-5, what="param %d" % i)
+        _close(a.grad, b.grad, what="param %d" % i, **LSTM_GRAD_GATE)
 
 
 @pytest.mark.parametrize("ndir,B,T,H,sub,lens", [(2, 3, 9, 16, 1, [9, 7, 4]), (1, 5, 6, 32, 2, [6, 6, 3, 2, 1]), (2, 33, 5, 64, 2, None),
@@ -1046,9 +1050,9 @@ def test_lstm_judge_width_h640(B, T, ndir):
     got.backward(dy.transpose(0, 1).contiguous().to(dev))
     assert hb.LAUNCHES["lstm_fwd_persist"] == 1 and hb.LAUNCHES["lstm_bwd_persist"] == 1, dict(hb.LAUNCHES)
     assert not hb.persist_aborted(dev)
-    _close(xg.grad, xc.grad, rtol=1e-3, atol=1e-5, what="dx")
+    _close(xg.grad, xc.grad, what="dx", **LSTM_GRAD_GATE)
     for i, (a, b) in enumerate(zip(gp, cp)):
-        _close(a.grad, b.grad, rtol=1e-3, atol=1e-5, what="param %d" % i)
+        _close(a.grad, b.grad, what="param %d" % i, **LSTM_GRAD_GATE)
 
 
 @pytest.mark.parametrize("dim,B,Tp,L,drop", [(512, 32, 100, 6, True), (512, 7, 37, 4, False), (320, 32, 100, 5, True),
