@@ -1349,6 +1349,60 @@ int asr_noise_mix_f32(int B, int64_t max_len, const void* samples, int sample_dt
                       const int64_t* clip_offsets, const int64_t* clip_offsets_dev, const float* bank, int64_t bank_count,
                       void* ws, int64_t ws_bytes, float* out, int64_t out_count, float* gains, asr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Transducer (RNN-T) head (csrc/rnnt.hip).  Blank = 0, never a label.  B utterances, T_b >= 1 frames
+ * (frame_lens, DEVICE int32 [B]), U_b >= 0 labels (label_offsets, DEVICE int32 [B + 1] into the packed DEVICE int64 labels, as
+ * asr_ctc_loss_fwd takes them), T = max T_b, U = max U_b given by the caller.  A node is (b, t, u), t < T_b, u <= U_b; the node
+ * matrices are [B][T][U + 1][.] row-major.  Nodes with t >= T_b or u > U_b are padding: never read, written as EXACT ZEROS
+ * in z, dlogits, dpe and dpp (no prior fill needed).
+ *   asr_rnnt_ws_bytes        plain integers, no GPU: 4 (3 B T (U + 1) + B) bytes rounded up per region (lse, alpha, beta,
+ *                            log P).  ASR_E_SHAPE for V < 2, J not a multiple of 4, U > ASR_RNNT_MAX_LABELS (the chains
+ *                            keep a diagonal in LDS), or a node matrix the launch grids cannot cover: offsets are 64-bit,
+ *                            the bound is B T (U + 1) max(J, V) <= 2^40 elements and B T (U + 1) / 4 workgroups <= 2^31 - 1.
+ *   asr_rnnt_joint_fwd_f32   z[b][t][u][:] = tanh(pe[b][t][:] + pp[b][u][:]); pe [B][T][J], pp [B][U + 1][J], z [B][T][U + 1][J],
+ *                            all contiguous and 16-byte aligned (ASR_E_ALIGN).  One launch.
+ *   asr_rnnt_joint_bwd_f32   dz (1 - z^2) summed over u = 0 .. U_b in ascending order into dpe [B][T][J] and over t = 0 ..
+ *                            T_b - 1 in ascending order into dpp [B][U + 1][J]; reads valid nodes only.  One launch.
+ *   asr_rnnt_loss_fwd_f32    RAW logits [B][T][U + 1][V] with row stride ld >= V (the log-softmax is the kernel's): the
+ *                            node log-sum-exps, then alpha by anti-diagonals in log space, one workgroup per utterance:
+ *                              alpha(0,0) = 0, alpha(t,u) = logaddexp(alpha(t-1,u) + lp_0(t-1,u), alpha(t,u-1) + lp_{y_u}(t,u-1))
+ *                              nll[b] = -(alpha(T_b-1,U_b) + lp_0(T_b-1,U_b))
+ *                            Every utterance with T_b >= 1 has an alignment; +inf only for a label outside [1, V), more than U
+ *                            labels or no frame (the gradient of such an utterance is zero).  Two launches.
+ *   asr_rnnt_loss_bwd_f32    behind a loss_fwd with the same arguments and workspace: beta from the far corner, then
+ *                              dlogits[b][t][u][k] = grad_nll[b] (softmax_k gamma - [k = 0] exp(alpha + lp_0 + beta(t+1,u) - log P)
+ *                                                   - [k = y_{u+1}] exp(alpha + lp_k + beta(t,u+1) - log P)),
+ *                              gamma = exp(alpha + beta - log P), beta(T_b, U_b) = 0 for the closing blank, a term off the
+ *                            lattice absent.  dlogits has row stride lddz >= V.  Two launches.
+ *   asr_rnnt_greedy_step_f32 ONE iteration of greedy decoding for all rows; all state on the DEVICE: t_cur, n_out, n_frame,
+ *                            last int32 [B], out int32 [B][L], score fp32 [B], advance int32 [B].  A row with t_cur == T_b
+ *                            or n_out == L does nothing (advance = 0).  A row that has emitted max_symbols tokens at this
+ *                            frame moves on: t_cur += 1, n_frame = 0, advance = 0.  Otherwise logits = w_out tanh(pe[b][t_cur]
+ *                            + pp[b]) + b_out (pp [B][J]: the row's current prediction-network projection; w_out [V][J];
+ *                            b_out [V] or NULL) and their argmax - GREATER VALUE FIRST, THE LOWER INDEX ON TIES: blank ->
+ *                            t_cur += 1, n_frame = 0, advance = 0; a token k -> out[b][n_out++] = k, last[b] = k, n_frame += 1,
+ *                            score[b] += log softmax_k, advance = 1.  (J + V) floats of LDS: ASR_E_SHAPE above 64 KB, for
+ *                            V < 2 or J not a multiple of 4.  One launch.
+ * No floating-point atomics, every sum in an order fixed by the shapes: the same bits in every run, in and outside
+ * deterministic mode.  No host synchronisation, no allocation.
+ * ------------------------------------------------------------------------------------- */
+#define ASR_RNNT_MAX_LABELS 1023
+int asr_rnnt_ws_bytes(int B, int T, int U, int J, int V, int64_t* ws_bytes);
+int asr_rnnt_joint_fwd_f32(int B, int T, int U, int J, const float* pe, const float* pp, const int32_t* frame_lens,
+                           const int32_t* label_offsets, float* z, asr_stream_t stream);
+int asr_rnnt_joint_bwd_f32(int B, int T, int U, int J, const float* dz, const float* z, const int32_t* frame_lens,
+                           const int32_t* label_offsets, float* dpe, float* dpp, asr_stream_t stream);
+int asr_rnnt_loss_fwd_f32(int B, int T, int U, int V, const float* logits, int64_t ld, const int32_t* frame_lens,
+                          const int64_t* labels, const int32_t* label_offsets, float* nll, void* ws, int64_t ws_bytes,
+                          asr_stream_t stream);
+int asr_rnnt_loss_bwd_f32(int B, int T, int U, int V, const float* logits, int64_t ld, const int32_t* frame_lens,
+                          const int64_t* labels, const int32_t* label_offsets, const float* grad_nll, void* ws,
+                          int64_t ws_bytes, float* dlogits, int64_t lddz, asr_stream_t stream);
+int asr_rnnt_greedy_step_f32(int B, int T, int J, int V, int L, int max_symbols, const float* pe, const float* pp,
+                             const float* w_out, const float* b_out, const int32_t* frame_lens, int32_t* t_cur,
+                             int32_t* n_out, int32_t* n_frame, int32_t* out, int32_t* last, float* score, int32_t* advance,
+                             asr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

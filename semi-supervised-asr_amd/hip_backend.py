@@ -37,6 +37,8 @@ EXPORTS = (
     "asr_mwer_fwd_f32", "asr_mwer_bwd_f32",
     "asr_resample_plan_bytes", "asr_resample_f32",
     "asr_reverb_f32", "asr_noise_mix_f32",
+    "asr_rnnt_ws_bytes", "asr_rnnt_joint_fwd_f32", "asr_rnnt_joint_bwd_f32", "asr_rnnt_loss_fwd_f32", "asr_rnnt_loss_bwd_f32",
+    "asr_rnnt_greedy_step_f32",
 )
 
 _lib = None
@@ -305,6 +307,12 @@ def load():
     lib.asr_reverb_f32.argtypes = [c_i, c_i64, c_p, c_i, c_i64, c_p, c_p, c_i, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p]
     lib.asr_noise_mix_f32.argtypes = [c_i, c_i64, c_p, c_i, c_i64, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p,
                                       c_i64, c_p, c_p]
+    lib.asr_rnnt_ws_bytes.argtypes = [c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(c_i64)]
+    lib.asr_rnnt_joint_fwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]
+    lib.asr_rnnt_joint_bwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p]
+    lib.asr_rnnt_loss_fwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
+    lib.asr_rnnt_loss_bwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p]
+    lib.asr_rnnt_greedy_step_f32.argtypes = [c_i] * 6 + [c_p] * 13
     lib.asr_mwer_fwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
     lib.asr_mwer_bwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_f, c_p, c_i64, c_p]
     lib.asr_dec_feedback_fwd.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_p, c_i64,
@@ -992,6 +1000,107 @@ def ctc_loss_bwd(logits, ld, frame_lens, labels, label_offsets, max_label_len, z
     check(load().asr_ctc_loss_bwd(*args, ptr(grad_nll), ptr(ws), ws.numel() * 4, ptr(dlogits), int(lddz), stream()),
           "asr_ctc_loss_bwd")
     return dlogits
+
+
+RNNT_MAX_LABELS = 1023       # ASR_RNNT_MAX_LABELS
+
+
+def rnnt_ws_bytes(B, T, U, J, V):
+    """asr_rnnt_ws_bytes on plain integers (no tensors, no GPU) -> the workspace bytes of an rnnt_loss call over B utterances
+    of at most T frames and U labels, joint width J, vocabulary V; UnsupportedShape for sizes the kernels refuse (V < 2, J not
+    a multiple of 4, more than RNNT_MAX_LABELS labels, a node matrix B T (U + 1) max(J, V) the launches cannot cover)."""
+    need = c_i64(0)
+    rc = load().asr_rnnt_ws_bytes(int(B), int(T), int(U), int(J), int(V), ctypes.byref(need))
+    if rc == -2:
+        raise UnsupportedShape("rnnt: B %d, T %d, U %d, J %d, V %d (V >= 2, J a multiple of 4, at most %d labels, "
+                               "B T (U + 1) max(J, V) <= 2^40)" % (B, T, U, J, V, RNNT_MAX_LABELS))
+    check(rc, "asr_rnnt_ws_bytes")
+    return int(need.value)
+
+
+def _rnnt_lens(frame_lens, label_offsets, B):
+    if frame_lens.dtype != torch.int32 or label_offsets.dtype != torch.int32 or frame_lens.numel() != B or \
+            label_offsets.numel() != B + 1:
+        raise RuntimeError("rnnt: frame_lens int32 [B] and label_offsets int32 [B + 1] on the GPU")
+
+
+def rnnt_joint_fwd(pe, pp, frame_lens, label_offsets, z):
+    """asr_rnnt_joint_fwd_f32: z [B, T, U + 1, J] = tanh(pe [B, T, J] + pp [B, U + 1, J]) on the lattice of every utterance,
+    exact zeros on padding.  All contiguous; z is the caller's.  UnsupportedShape before anything is written."""
+    B, T, J = pe.shape
+    U = pp.shape[1] - 1
+    if tuple(pp.shape) != (B, U + 1, J) or tuple(z.shape) != (B, T, U + 1, J) or not (pe.is_contiguous() and pp.is_contiguous()
+                                                                                      and z.is_contiguous()):
+        raise RuntimeError("rnnt_joint_fwd: pe [B, T, J], pp [B, U + 1, J], z [B, T, U + 1, J], contiguous")
+    _rnnt_lens(frame_lens, label_offsets, B)
+    rnnt_ws_bytes(B, T, U, J, 2)
+    check(load().asr_rnnt_joint_fwd_f32(B, T, U, J, ptr(pe), ptr(pp), ptr(frame_lens), ptr(label_offsets), ptr(z), stream()),
+          "asr_rnnt_joint_fwd_f32")
+    LAUNCHES["rnnt_joint"] += 1
+    return z
+
+
+def rnnt_joint_bwd(dz, z, frame_lens, label_offsets, dpe, dpp):
+    """asr_rnnt_joint_bwd_f32: dz (1 - z^2) summed in a fixed order into dpe [B, T, J] and dpp [B, U + 1, J] (the caller's)."""
+    B, T, U1, J = z.shape
+    if tuple(dz.shape) != (B, T, U1, J) or tuple(dpe.shape) != (B, T, J) or tuple(dpp.shape) != (B, U1, J) or \
+            not (dz.is_contiguous() and z.is_contiguous() and dpe.is_contiguous() and dpp.is_contiguous()):
+        raise RuntimeError("rnnt_joint_bwd: dz, z [B, T, U + 1, J], dpe [B, T, J], dpp [B, U + 1, J], contiguous")
+    _rnnt_lens(frame_lens, label_offsets, B)
+    rnnt_ws_bytes(B, T, U1 - 1, J, 2)
+    check(load().asr_rnnt_joint_bwd_f32(B, T, U1 - 1, J, ptr(dz), ptr(z), ptr(frame_lens), ptr(label_offsets), ptr(dpe), ptr(dpp),
+                                        stream()), "asr_rnnt_joint_bwd_f32")
+    LAUNCHES["rnnt_joint_bwd"] += 1
+    return dpe, dpp
+
+
+def _rnnt_loss_args(logits, ld, frame_lens, labels, label_offsets):
+    B, T, U1, V = logits.shape
+    if labels.dtype != torch.int64 or not labels.is_cuda:
+        raise RuntimeError("rnnt_loss: labels must be one packed int64 tensor on the GPU")
+    _rnnt_lens(frame_lens, label_offsets, B)
+    return (B, T, U1 - 1, V, ptr(logits), int(ld), ptr(frame_lens), c_p(labels.data_ptr()), ptr(label_offsets))
+
+
+def rnnt_loss_fwd(logits, ld, frame_lens, labels, label_offsets, nll, ws):
+    """asr_rnnt_loss_fwd_f32: raw logits [B, T, U + 1, V] fp32 with row stride ld (a view of a wider buffer is fine), frame_lens
+    int32 [B], labels int64 packed, label_offsets int32 [B + 1] - all on the device; nll [B] and ws (a float32 tensor of at
+    least rnnt_ws_bytes bytes) are the caller's.  The workspace goes to rnnt_loss_bwd unchanged."""
+    args = _rnnt_loss_args(logits, ld, frame_lens, labels, label_offsets)
+    rnnt_ws_bytes(args[0], args[1], args[2], 4, args[3])
+    check(load().asr_rnnt_loss_fwd_f32(*args, ptr(nll), ptr(ws), ws.numel() * 4, stream()), "asr_rnnt_loss_fwd_f32")
+    LAUNCHES["rnnt_loss"] += 1
+    return nll
+
+
+def rnnt_loss_bwd(logits, ld, frame_lens, labels, label_offsets, grad_nll, ws, dlogits, lddz):
+    """asr_rnnt_loss_bwd_f32 behind an rnnt_loss_fwd with the same arguments and workspace: dlogits [B, T, U + 1, >= V] with
+    row stride lddz, zeros on padding."""
+    args = _rnnt_loss_args(logits, ld, frame_lens, labels, label_offsets)
+    check(load().asr_rnnt_loss_bwd_f32(*args, ptr(grad_nll), ptr(ws), ws.numel() * 4, ptr(dlogits), int(lddz), stream()),
+          "asr_rnnt_loss_bwd_f32")
+    LAUNCHES["rnnt_loss_bwd"] += 1
+    return dlogits
+
+
+def rnnt_greedy_step(pe, pp, w_out, b_out, frame_lens, t_cur, n_out, n_frame, out, last, score, advance, max_symbols):
+    """asr_rnnt_greedy_step_f32: one iteration of transducer greedy decoding for all rows (include/asr_hip.h).  pe [B, T, J],
+    pp [B, J], w_out [V, J], b_out [V] or None; the state - t_cur, n_out, n_frame, last, advance int32 [B], out int32 [B, L],
+    score fp32 [B] - lives on the device.  The argmax takes the lower index on ties."""
+    B, T, J = pe.shape
+    V, L = w_out.shape[0], out.shape[1]
+    state = (t_cur, n_out, n_frame, last, advance)
+    if tuple(pp.shape) != (B, J) or w_out.shape[1] != J or tuple(out.shape) != (B, L) or score.numel() != B or \
+            any(s.dtype != torch.int32 or s.numel() != B for s in state) or out.dtype != torch.int32 or \
+            not all(x.is_contiguous() for x in (pe, pp, w_out, out)):
+        raise RuntimeError("rnnt_greedy_step: pe [B, T, J], pp [B, J], w_out [V, J], int32 state [B], out int32 [B, L], contiguous")
+    rc = load().asr_rnnt_greedy_step_f32(B, T, J, V, L, int(max_symbols), ptr(pe), ptr(pp), ptr(w_out), ptr(b_out),
+                                         ptr(frame_lens), ptr(t_cur), ptr(n_out), ptr(n_frame), ptr(out), ptr(last), ptr(score),
+                                         ptr(advance), stream())
+    if rc == -2:
+        raise UnsupportedShape("rnnt_greedy_step: J %d, V %d (V >= 2, J a multiple of 4, (J + V) floats within 64 KB)" % (J, V))
+    check(rc, "asr_rnnt_greedy_step_f32")
+    LAUNCHES["rnnt_greedy_step"] += 1
 
 
 def _mwer_dims(logits, tokens, B):

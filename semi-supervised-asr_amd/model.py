@@ -647,12 +647,98 @@ class Decoder(torch.nn.Module):
         return tokens, scores, parts
 
 
+class TransducerHead(torch.nn.Module):
+    """The transducer (RNN-T) head on the encoder output (not in the reference): a prediction network - an
+    embedding and a one-layer unidirectional LSTM over <BOS>, y_1 .. y_U on ops.lstm_layer - and a joint network
+    logits(t, u) = lin_out(tanh(lin_enc(enc_h[t]) + lin_pred(pred_h[u]))) whose products run on ops.linear and whose
+    activations and loss are csrc/rnnt.hip's.  Blank = <PAD> = 0, never a label."""
+
+    def __init__(self, output_dim, embedding_dim, pred_dim, enc_hidden_dim, joint_dim, bos):
+        super(TransducerHead, self).__init__()
+        if joint_dim <= 0 or joint_dim % 4:
+            raise ValueError("rnnt_joint_dim must be a positive multiple of 4, got %r" % (joint_dim,))
+        self.bos, self.pred_dim, self.joint_dim, self.output_dim = bos, pred_dim, joint_dim, output_dim
+        self.embedding = torch.nn.Embedding(output_dim, embedding_dim)
+        self.lstm = _LstmWeights(embedding_dim, pred_dim, num_layers=1, bidirectional=False)
+        self.lin_enc = torch.nn.Linear(enc_hidden_dim, joint_dim)
+        self.lin_pred = torch.nn.Linear(pred_dim, joint_dim, bias=False)
+        self.lin_out = torch.nn.Linear(joint_dim, output_dim)
+
+    def project_enc(self, enc_h):
+        """enc_h [B, T', H] -> PE [B, T', J]."""
+        bsz, frames, hid = enc_h.shape
+        return ops.linear(enc_h.reshape(bsz * frames, hid), self.lin_enc.weight, self.lin_enc.bias).view(bsz, frames, -1)
+
+    def predict(self, ys):
+        """The prediction network over <BOS>, y_1 .. y_U of every utterance -> PP [B, U + 1, J] (U the longest transcript).
+        Every row runs all U + 1 steps on zero-padded tokens: the network is causal, so the positions u <= U_b do not see the
+        padding, and the positions behind them are padding nodes of the lattice, which nothing reads."""
+        dev = self.embedding.weight.device
+        bos = ys[0].new_tensor([self.bos])
+        tok = pad_list([torch.cat([bos, y.reshape(-1)]) for y in ys], 0).to(device=dev, dtype=torch.long)
+        bsz, steps = tok.shape
+        x_tm = self.embedding(tok).transpose(0, 1).contiguous()
+        h = ops.lstm_layer(x_tm, hb_to_device([steps] * bsz, dev), self.lstm.direction_params(0), 1)      # [U + 1, B, P]
+        h = h.transpose(0, 1).contiguous()
+        return ops.linear(h.view(bsz * steps, -1), self.lin_pred.weight).view(bsz, steps, -1)
+
+    def logits(self, enc_h, ys, frame_lens_dev):
+        """-> raw logits [B, T', U + 1, V] (zeros' image lin_out.bias on padding nodes, which the loss never reads)."""
+        counts = [int(y.numel()) for y in ys]
+        z = ops.rnnt_joint(self.project_enc(enc_h), self.predict(ys), frame_lens_dev, counts)
+        bsz, frames, u1, jdim = z.shape
+        return ops.linear(z.view(bsz * frames * u1, jdim), self.lin_out.weight, self.lin_out.bias).view(bsz, frames, u1, -1)
+
+    def nll(self, enc_h, ys, frame_lens_dev):
+        """Per-utterance transducer negative log-likelihood [B]."""
+        logits = self.logits(enc_h, ys, frame_lens_dev)
+        labels = torch.cat([y.reshape(-1) for y in ys]).to(device=enc_h.device, dtype=torch.long)
+        return ops.rnnt_loss(logits, frame_lens_dev, labels, [int(y.numel()) for y in ys])
+
+    def cell_step(self, tok, h, c):
+        """One prediction-network step for all rows (decoding; no autograd): tok int [B], h / c [B, P] -> (h', c').  The
+        products run on asr_gemm_f32, as LM.forward_step's do."""
+        w_ih, w_hh, b_ih, b_hh = self.lstm.direction_params(0)
+        x = self.embedding(tok.long()).contiguous()
+        gates = hb.gemm(x, w_ih, trans_b=True, bias=b_ih)
+        hb.gemm(h.contiguous(), w_hh, trans_b=True, bias=b_hh, out=gates, accumulate=True)
+        gi, gf, gg, go = gates.chunk(4, dim=1)
+        c2 = torch.sigmoid(gf) * c + torch.sigmoid(gi) * torch.tanh(gg)
+        return torch.sigmoid(go) * torch.tanh(c2), c2
+
+    def greedy(self, enc_h, frame_lens_dev, max_symbols, max_len):
+        """Greedy transducer decoding of enc_h [B, T', H]: lin_enc once, then a fixed T' + max_len iterations of (the greedy
+        step kernel, one prediction-network cell step for all rows with h, c and the projection committed only where the
+        kernel set `advance`).  No host read.  -> (tokens int32 [B, max_len], lengths int32 [B], scores fp32 [B]) on the
+        device; a row emits at most max_symbols tokens per frame and max_len in all."""
+        bsz, frames, _ = enc_h.shape
+        dev = enc_h.device
+        pe = self.project_enc(enc_h).contiguous()
+        i32 = dict(device=dev, dtype=torch.int32)
+        t_cur, n_out, n_frame, advance = (torch.zeros(bsz, **i32) for _ in range(4))
+        last = torch.full((bsz,), self.bos, **i32)
+        out = torch.zeros(bsz, max_len, **i32)
+        score = torch.zeros(bsz, device=dev, dtype=torch.float32)
+        zero = torch.zeros(bsz, self.pred_dim, device=dev, dtype=torch.float32)
+        h, c = self.cell_step(last, zero, zero)
+        w_out, b_out = self.lin_out.weight.contiguous(), self.lin_out.bias
+        pp = hb.gemm(h.contiguous(), self.lin_pred.weight, trans_b=True)
+        for _ in range(frames + max_len):
+            hb.rnnt_greedy_step(pe, pp, w_out, b_out, frame_lens_dev, t_cur, n_out, n_frame, out, last, score, advance,
+                                max_symbols)
+            h2, c2 = self.cell_step(last, h, c)
+            adv = advance.bool().unsqueeze(1)
+            h, c = torch.where(adv, h2, h), torch.where(adv, c2, c)
+            pp = hb.gemm(h.contiguous(), self.lin_pred.weight, trans_b=True)
+        return out, n_out, score
+
+
 class E2E(torch.nn.Module):
     """model.py:408-456."""
 
     def __init__(self, input_dim, enc_hidden_dim, enc_n_layers, subsample, dropout_rate, dec_hidden_dim, att_dim,
                  conv_channels, conv_kernel_size, att_odim, embedding_dim, output_dim, ls_weight, labeldist,
-                 pad=0, bos=1, eos=2, ctc_weight=0.0):
+                 pad=0, bos=1, eos=2, ctc_weight=0.0, rnnt_weight=0.0, rnnt_joint_dim=256, rnnt_pred_dim=None):
         super(E2E, self).__init__()
         self.encoder = Encoder(input_dim=input_dim, hidden_dim=enc_hidden_dim, n_layers=enc_n_layers,
                                subsample=subsample, dropout_rate=dropout_rate)
@@ -672,8 +758,22 @@ class E2E(torch.nn.Module):
             if pad != 0:
                 raise ValueError("the CTC branch takes <PAD> = 0 as its blank; pad is %d" % pad)
             self.ctc_lo = torch.nn.Linear(enc_hidden_dim, output_dim)
+        # `rnnt_weight` (not in the reference): w > 0 adds the transducer head and trains on
+        # (1 - w_ctc - w_rnnt) L_att + w_ctc L_ctc + w_rnnt L_rnnt.  Like the CTC branch the head exists only
+        # then: at 0 its parameters, its state_dict keys and every launch are absent.
+        self.rnnt_weight = float(rnnt_weight)
+        if not 0.0 <= self.rnnt_weight <= 1.0:
+            raise ValueError("rnnt_weight must lie in [0, 1], got %r" % (rnnt_weight,))
+        if self.ctc_weight + self.rnnt_weight > 1.0:
+            raise ValueError("ctc_weight + rnnt_weight must be at most 1, got %r + %r" % (ctc_weight, rnnt_weight))
+        if self.rnnt_weight > 0:
+            if pad != 0:
+                raise ValueError("the transducer head takes <PAD> = 0 as its blank; pad is %d" % pad)
+            self.rnnt = TransducerHead(output_dim=output_dim, embedding_dim=embedding_dim,
+                                       pred_dim=int(rnnt_pred_dim) if rnnt_pred_dim else dec_hidden_dim,
+                                       enc_hidden_dim=enc_hidden_dim, joint_dim=int(rnnt_joint_dim), bos=bos)
 
-    accepts_loss_norm = True           # (parallel.sup_local_loss: this forward takes the loss's normaliser along)
+    accepts_loss_norm = True          # (parallel.sup_local_loss: this forward takes the loss's normaliser along)
 
     def forward(self, data, ilens, ys=None, tf_rate=1.0, max_dec_timesteps=200, sample=False, smooth=False,
                 scaling=1.0, label_smoothing=True, total_length=None, olength=None, loss_norm=None):
@@ -690,7 +790,39 @@ class E2E(torch.nn.Module):
             norm = float(loss_norm) if loss_norm else float(len(ys))
             lp = out[1]
             lp.ctc_nll, lp.ctc_loss, lp.ctc_norm, lp.ctc_weight = nll, nll.sum() * (1.0 / norm), norm, self.ctc_weight
+        if self.rnnt_weight > 0 and ys is not None and len(ys) > 0:
+            # the transducer term rides the same way (parallel.joint_loss)
+            nll = self.rnnt_nll(enc_h, ys)
+            norm = float(loss_norm) if loss_norm else float(len(ys))
+            lp = out[1]
+            lp.rnnt_nll, lp.rnnt_loss, lp.rnnt_norm, lp.rnnt_weight = nll, nll.sum() * (1.0 / norm), norm, self.rnnt_weight
         return out
+
+    def rnnt_nll(self, enc_h, ys):
+        """Per-utterance transducer negative log-likelihood [B] of the labels `ys` given the encoder output enc_h [B, T', H]
+        of the forward that has just run (the frame lengths are the encoder's device copy): TransducerHead.nll."""
+        if not hasattr(self, "rnnt"):
+            raise ValueError("rnnt_nll needs the transducer head: build the model with rnnt_weight > 0")
+        return self.rnnt.nll(enc_h, ys, self.encoder.enc2.last_lens_dev)
+
+    def recognize_rnnt(self, xs, ilens, max_symbols=3, max_dec_timesteps=200):
+        """Greedy decoding with the transducer head alone (not a reference method): the encoder and lin_enc
+        once, then TransducerHead.greedy - at most max_symbols tokens per encoder frame, max_dec_timesteps in all, the lower
+        index on ties.  -> one id list per utterance, as recognize_ctc returns them; self.last_rnnt keeps the device
+        tensors of the call: dict(tokens int32 [B, max_dec_timesteps], lengths int32 [B], scores fp32 [B]: the sum of the
+        emitted tokens' log-probabilities).  One host read, behind the loop."""
+        if not hasattr(self, "rnnt"):
+            raise ValueError("recognize_rnnt needs the transducer head: build the model with rnnt_weight > 0")
+        if int(max_symbols) < 1 or int(max_dec_timesteps) < 1:
+            raise ValueError("recognize_rnnt: max_symbols and max_dec_timesteps must be at least 1")
+        if xs.is_cuda:
+            hb.upload_side_stream_for(xs.shape[0] * xs.shape[1])
+        with torch.no_grad():
+            enc_h, _ = self.encoder(xs, ilens)
+            out, n, score = self.rnnt.greedy(enc_h, self.encoder.enc2.last_lens_dev, int(max_symbols), int(max_dec_timesteps))
+            host = torch.cat([n.view(-1, 1), out], dim=1).cpu().tolist()
+        self.last_rnnt = dict(tokens=out, lengths=n, scores=score)
+        return [row[1:1 + row[0]] for row in host]
 
     def ctc_nll(self, enc_h, ys):
         """Per-utterance CTC negative log-likelihood [B] of the labels `ys` given the encoder output enc_h [B, T', H] of the

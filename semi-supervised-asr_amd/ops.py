@@ -995,6 +995,127 @@ def ctc_loss(logits, frame_lens_dev, labels_packed, label_lens, zero_infinity=Tr
     return _CtcLoss.apply(logits, frame_lens_dev, labels_packed, label_lens, zero_infinity)
 
 
+def _label_offsets(what, label_lens, B, n_labels=None):
+    """Host label counts -> (counts, offsets [B + 1], the largest count); ValueError where they do not fit the batch."""
+    lens = [int(n) for n in label_lens]
+    if len(lens) != B:
+        raise ValueError("%s: %d label lengths for %d utterances" % (what, len(lens), B))
+    offsets = [0]
+    for n in lens:
+        if n < 0:
+            raise ValueError("%s: a negative label length" % what)
+        offsets.append(offsets[-1] + n)
+    if n_labels is not None and offsets[-1] != n_labels:
+        raise ValueError("%s: the label lengths sum to %d, the packed labels hold %d" % (what, offsets[-1], n_labels))
+    return lens, offsets, max(lens)
+
+
+class _RnntJoint(torch.autograd.Function):
+    """The transducer's joint activations Z [B, T, U + 1, J] = tanh(PE [B, T, J] + PP [B, U + 1, J]) on every utterance's
+    lattice, exact zeros on padding: asr_rnnt_joint_fwd_f32 / _bwd_f32 (csrc/rnnt.hip), one launch each way.  Z is the memory
+    cost of the head - 4 B T (U + 1) J bytes - and is leased from the pool from the forward to the end of the backward like
+    the other sequence workspaces (the output aliases it: valid until this node's backward has run); without autograd a
+    fresh tensor.  Ordered sums only, no host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, pe, pp, frame_lens, label_lens):
+        B, T, J = pe.shape
+        _, offsets, umax = _label_offsets("rnnt_joint", label_lens, B)
+        if tuple(pp.shape) != (B, umax + 1, J):
+            raise ValueError("rnnt_joint: pp is %s, the labels need [%d, %d, %d]" % (tuple(pp.shape), B, umax + 1, J))
+        hb.rnnt_ws_bytes(B, T, umax, J, 2)           # (UnsupportedShape before anything is leased or written)
+        dev = pe.device
+        pe, pp = pe.contiguous(), pp.contiguous()
+        n = B * T * (umax + 1) * J
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            cap = _row_capacity(n)
+            ctx.lease = _POOL.acquire(("rnnt_z", str(dev), cap), lambda: torch.empty(cap, device=dev, dtype=torch.float32))
+            z = ctx.lease.ws[:n].view(B, T, umax + 1, J)
+        else:
+            ctx.lease, z = None, torch.empty(B, T, umax + 1, J, device=dev, dtype=torch.float32)
+        offs_dev = hb.to_device_i32(offsets, dev)
+        hb.rnnt_joint_fwd(pe, pp, frame_lens, offs_dev, z)
+        ctx.save_for_backward(frame_lens, offs_dev)
+        ctx.dims = (B, T, umax, J)
+        return z.detach()
+
+    @staticmethod
+    def backward(ctx, dz):
+        frame_lens, offs_dev = ctx.saved_tensors
+        if ctx.lease is None or ctx.lease.ws is None:
+            raise RuntimeError("rnnt_joint: the backward runs once, behind a forward that ran with autograd enabled")
+        B, T, umax, J = ctx.dims
+        z = ctx.lease.ws[:B * T * (umax + 1) * J].view(B, T, umax + 1, J)
+        dpe = torch.empty(B, T, J, device=dz.device, dtype=torch.float32)
+        dpp = torch.empty(B, umax + 1, J, device=dz.device, dtype=torch.float32)
+        hb.rnnt_joint_bwd(dz.contiguous(), z, frame_lens, offs_dev, dpe, dpp)
+        ctx.lease.release()
+        return dpe, dpp, None, None
+
+
+def rnnt_joint(pe, pp, frame_lens_dev, label_lens):
+    """-> Z [B, T, U + 1, J] = tanh(pe[b, t] + pp[b, u]) for t < T_b, u <= U_b, exact zeros elsewhere.  pe
+    [B, T, J] and pp [B, U + 1, J] fp32 (the two projections, from ops.linear), frame_lens_dev int32 [B] on the device
+    (Encoder.last_lens_dev), label_lens the label counts per utterance (host integers; U = their maximum).  J a multiple of
+    4: hb.UnsupportedShape otherwise."""
+    return _RnntJoint.apply(pe, pp, frame_lens_dev, label_lens)
+
+
+class _RnntLoss(torch.autograd.Function):
+    """Transducer negative log-likelihood per utterance of RAW logits [B, T, U + 1, V] (blank = 0; the log-softmax is the
+    kernel's) -> nll [B]: asr_rnnt_loss_fwd_f32 / _bwd_f32 (csrc/rnnt.hip), two launches each way.  The workspace (the node
+    log-sum-exps, alpha, beta) is leased from the pool from the forward to the end of the backward, like _CtcLoss's; without
+    autograd a fresh tensor.  Ordered sums only: nothing here depends on hb.is_deterministic().  No host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, logits, frame_lens, labels, label_lens):
+        B, T, U1, V = logits.shape
+        # a [B, T, U + 1, V] view of a wider row-major buffer goes in as it is (row stride = ld)
+        ld = logits.stride(2)
+        if not (logits.stride(3) == 1 and ld >= V and logits.stride(1) == U1 * ld and logits.stride(0) == T * U1 * ld):
+            logits = logits.contiguous()
+            ld = V
+        _, offsets, umax = _label_offsets("rnnt_loss", label_lens, B, labels.numel())
+        if umax + 1 != U1:
+            raise ValueError("rnnt_loss: the logits hold %d label positions, the longest transcript needs %d" % (U1, umax + 1))
+        dev = logits.device
+        words = (hb.rnnt_ws_bytes(B, T, umax, 4, V) + 3) // 4
+        if ctx.needs_input_grad[0]:                  # (grad mode is off inside forward: ask the node)
+            cap = _row_capacity(words)
+            ctx.lease = _POOL.acquire(("rnnt", str(dev), cap), lambda: torch.empty(cap, device=dev, dtype=torch.float32))
+            ws = ctx.lease.ws
+        else:
+            ctx.lease, ws = None, torch.empty(words, device=dev, dtype=torch.float32)
+        offs_dev = hb.to_device_i32(offsets, dev)
+        # (a batch of empty transcripts has no label to point at: the library wants a pointer all the same)
+        labels = labels.contiguous() if labels.numel() else torch.zeros(1, device=dev, dtype=torch.long)
+        nll = torch.empty(B, device=dev, dtype=torch.float32)
+        hb.rnnt_loss_fwd(logits, ld, frame_lens, labels, offs_dev, nll, ws)
+        ctx.save_for_backward(logits, frame_lens, labels, offs_dev)
+        ctx.ld = ld
+        return nll
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, frame_lens, labels, offs_dev = ctx.saved_tensors
+        if ctx.lease is None or ctx.lease.ws is None:
+            raise RuntimeError("rnnt_loss: the backward runs once, behind a forward that ran with autograd enabled")
+        B, T, U1, V = logits.shape
+        dz = torch.empty(B, T, U1, V, device=logits.device, dtype=torch.float32)
+        hb.rnnt_loss_bwd(logits, ctx.ld, frame_lens, labels, offs_dev, g.contiguous(), ctx.lease.ws, dz, V)
+        ctx.lease.release()
+        return dz, None, None, None
+
+
+def rnnt_loss(logits, frame_lens_dev, labels_packed, label_lens):
+    """-> nll [B], the transducer negative log-likelihood of each utterance.  logits [B, T, U + 1, V] fp32 raw
+    (not log-softmaxed; a view with row stride >= V is taken as it is), frame_lens_dev int32 [B] on the device
+    (Encoder.last_lens_dev; every T_b >= 1), labels_packed the batch's labels as ONE int64 device tensor, label_lens their
+    counts per utterance (host integers; U = their maximum).  Blank = 0.  Every utterance has an alignment: there is no
+    zero_infinity case."""
+    return _RnntLoss.apply(logits, frame_lens_dev, labels_packed, label_lens)
+
+
 class _MwerLoss(torch.autograd.Function):
     """The expected number of edit errors over the n-best list (csrc/mwer.hip): logits [L, R, V] RAW, time-major, R = B K rows
     -> (loss, seq_logp [R], post [R], risk [B], coef [R]); only `loss` carries a gradient.  Two launches forward, one

@@ -102,12 +102,23 @@ def joint_loss(att, log_probs, info):
     ctc_weight = w); the attention loss alone otherwise.  L_ctc is normalised per utterance by the GLOBAL batch size, like
     L_att, so the rank-local joint losses sum to the single-process one."""
     ctc = getattr(log_probs, "ctc_loss", None)
-    if ctc is None:
+    rnnt = getattr(log_probs, "rnnt_loss", None)
+    if ctc is None and rnnt is None:
         return att
-    w, have, want = float(log_probs.ctc_weight), float(log_probs.ctc_norm), float(info["b_global"])
+    w, want = 0.0, float(info["b_global"])
+    if ctc is not None:
+        w, have = float(log_probs.ctc_weight), float(log_probs.ctc_norm)
+        if have != want:
+            ctc = ctc * (have / want)
+    if rnnt is None:
+        return (1.0 - w) * att + w * ctc
+    # the transducer term (E2E(rnnt_weight > 0); DESIGN 4.27) rides the same way: (1 - w_ctc - w_rnnt) L_att + w_ctc L_ctc +
+    # w_rnnt L_rnnt, L_rnnt normalised per utterance by the global batch size
+    wr, have = float(log_probs.rnnt_weight), float(log_probs.rnnt_norm)
     if have != want:
-        ctc = ctc * (have / want)
-    return (1.0 - w) * att + w * ctc
+        rnnt = rnnt * (have / want)
+    loss = (1.0 - w - wr) * att + wr * rnnt
+    return loss if ctc is None else loss + w * ctc
 
 
 _ONE = {}

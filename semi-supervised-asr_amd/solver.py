@@ -128,8 +128,19 @@ class Solver(object):
             if self.rank == 0:
                 print(f"{model_path}.ckpt has no CTC head ({', '.join(head)}): the head keeps its initialisation")
             state = dict(state, **{k: v for k, v in self.model.state_dict().items() if k in head})
+        # the transducer head follows the same rule (`rnnt_weight` > 0): a checkpoint without it loads, the head keeps its
+        # initialisation; the optimiser state of such a run cannot be resumed
+        rnnt_head = [k for k in self.model.state_dict() if k.startswith("rnnt.")]
+        rnnt_headless = bool(rnnt_head) and not any(k in state for k in rnnt_head)
+        if rnnt_headless:
+            if self.rank == 0:
+                print(f"{model_path}.ckpt has no transducer head (rnnt.*): the head keeps its initialisation")
+            state = dict(state, **{k: v for k, v in self.model.state_dict().items() if k in rnnt_head})
         self.model.load_state_dict(state)
         if load_optimizer:
+            if rnnt_headless:
+                raise RuntimeError(f"{model_path}.opt belongs to a model without the transducer head: its optimiser state "
+                                   "cannot be resumed with `rnnt_weight` > 0 (set load_optimizer: false)")
             if headless:
                 raise RuntimeError(f"{model_path}.opt belongs to a model without the CTC head: the optimiser state of an "
                                    "attention-only run cannot be resumed with `ctc_weight` > 0 (set load_optimizer: false)")
@@ -220,7 +231,10 @@ class Solver(object):
             eos=self.vocab["<EOS>"],
             # `ctc_weight` (not a reference key; default 0): w > 0 adds the CTC branch on the encoder and every labeled
             # step trains on (1 - w) L_att + w L_ctc; at 0 the model is the reference's
-            ctc_weight=float(cfg.get("ctc_weight", 0.0))))
+            ctc_weight=float(cfg.get("ctc_weight", 0.0)),
+            # `rnnt_weight`, `rnnt_joint_dim`, `rnnt_pred_dim` (not reference keys; absent by default): w > 0 adds the
+            # transducer head and the term w L_rnnt; the keys reach the model only then
+            **self.rnnt_model_args(cfg)))
         # `dp_overlap` (not a reference key): issue the gradient all-reduce in buckets from inside the backward pass
         # (parallel.FlatBuffers.enable_overlap).  Off by default HERE: an RCCL kernel that is resident while a persistent
         # kernel is being placed could - if the two do not fit a CU together and a rank is late - hold that kernel's
@@ -327,6 +341,51 @@ class Solver(object):
                   "per-step kernels" % hb.persist_abort_code(xs.device))
             hb.disable_persistent(xs.device)
             out = run()
+        return out
+
+    @staticmethod
+    def rnnt_model_args(config):
+        """The transducer keys of the model (not reference keys; absent by default): `rnnt_weight` in [0, 1]
+        (with `ctc_weight` at most 1 in sum), `rnnt_joint_dim` (default 256, a multiple of 4), `rnnt_pred_dim` (default: the
+        decoder's width) -> the keyword arguments of E2E; none at weight 0, whatever the other two say."""
+        w = float(config.get("rnnt_weight", 0.0) or 0.0)
+        if not 0.0 <= w <= 1.0 or w + float(config.get("ctc_weight", 0.0) or 0.0) > 1.0:
+            raise ValueError("rnnt_weight must lie in [0, 1] and ctc_weight + rnnt_weight must be at most 1")
+        if w == 0:
+            return {}
+        return dict(rnnt_weight=w, rnnt_joint_dim=int(config.get("rnnt_joint_dim", 256) or 256),
+                    rnnt_pred_dim=config.get("rnnt_pred_dim", None))
+
+    @staticmethod
+    def rnnt_decode_config(config, has_rnnt_head):
+        """`rnnt_greedy_decode` (not a reference key; default false): test() decodes with the transducer head alone
+        (E2E.recognize_rnnt, at most `rnnt_max_symbols` - default 3 - tokens per encoder frame).  It is a decoder of its own
+        -> the key as a bool; ValueError on a model without the head or beside any other decoder or LM key."""
+        on = bool(config.get("rnnt_greedy_decode", False))
+        if not on:
+            return False
+        if not has_rnnt_head:
+            raise ValueError("rnnt_greedy_decode needs the transducer head: build the model with rnnt_weight > 0")
+        others = [k for k in ("two_pass_decode", "ctc_beam_decode", "ctc_greedy_decode", "ngram_lm", "word_lm") if config.get(k)]
+        if int(config.get("beam_size", 1) or 1) > 1:
+            others.append("beam_size > 1")
+        others += [k + " > 0" for k in ("lm_weight", "ctc_decode_weight") if float(config.get(k, 0.0) or 0.0) > 0]
+        if others:
+            raise ValueError("rnnt_greedy_decode decodes with the transducer head alone: it does not combine with %s"
+                             % ", ".join(others))
+        return True
+
+    def _rnnt_greedy(self, xs, ilens):
+        """Greedy hypothesis ids of the transducer head for one batch (E2E.recognize_rnnt); the abort word of the encoder's
+        persistent kernels is checked after the decode and the batch repeated on the per-step kernels, as in _greedy."""
+        kw = dict(max_symbols=int(self.config.get("rnnt_max_symbols", 3) or 3),
+                  max_dec_timesteps=int(self.config.get("max_dec_timesteps", 200) or 200))
+        out = self.model.recognize_rnnt(xs, ilens, **kw)
+        if self._abort_seen(xs.device):
+            print("persistent kernels aborted during transducer decoding (this rank's code %d): repeating the batch on the "
+                  "per-step kernels" % hb.persist_abort_code(xs.device))
+            hb.disable_persistent(xs.device)
+            out = self.model.recognize_rnnt(xs, ilens, **kw)
         return out
 
     def _ctc_best_path(self, xs, ilens):
@@ -498,7 +557,7 @@ class Solver(object):
         """Teacher-forced dev loss + greedy CER (solver.py:212-242); greedy pass runs without autograd."""
         self.flush()
         self.model.eval()
-        preds, refs, total, ctc_total = [], [], 0.0, None
+        preds, refs, total, ctc_total, rnnt_total = [], [], 0.0, None, None
         for batch in self._feed(self.dev_loader, sharded=False):
             xs, ilens, ys = batch
             with torch.no_grad():
@@ -511,6 +570,8 @@ class Solver(object):
                 total += value
                 if getattr(log_probs, "ctc_loss", None) is not None:      # the CTC branch's own dev loss, per utterance
                     ctc_total = (ctc_total or 0.0) + log_probs.ctc_loss.item()
+                if getattr(log_probs, "rnnt_loss", None) is not None:     # the transducer head's own dev loss, per utterance
+                    rnnt_total = (rnnt_total or 0.0) + log_probs.rnnt_loss.item()
             preds += self._greedy(xs, ilens)
             refs += batch.ys_host
         self.model.train()
@@ -521,6 +582,13 @@ class Solver(object):
             if self.rank == 0:
                 print(f"val_ctc_loss={self.val_ctc_loss:.4f}")
             self.logger.scalar_summary(f"{self.config['tag']}/supervised/val_ctc_loss", self.val_ctc_loss, self._val_rounds - 1)
+        self.val_rnnt_loss = None if rnnt_total is None else rnnt_total / len(self.dev_loader)
+        if self.val_rnnt_loss is not None:
+            self._val_rnnt_rounds = getattr(self, "_val_rnnt_rounds", 0) + 1
+            if self.rank == 0:
+                print(f"val_rnnt_loss={self.val_rnnt_loss:.4f}")
+            self.logger.scalar_summary(f"{self.config['tag']}/supervised/val_rnnt_loss", self.val_rnnt_loss,
+                                       self._val_rnnt_rounds - 1)
         cer, hyp_sents, ref_sents = self.ind2sent(preds, refs)
         return total / len(self.dev_loader), cer, hyp_sents, ref_sents
 
@@ -554,6 +622,7 @@ class Solver(object):
                            or float(self.config.get("ctc_decode_weight", 0.0) or 0.0) > 0):
             raise ValueError("ctc_greedy_decode decodes with the CTC head alone: it does not combine with beam_size > 1, "
                              "lm_weight > 0 or ctc_decode_weight > 0")
+        rnnt_greedy = self.rnnt_decode_config(self.config, hasattr(self.model, "rnnt"))
         two_pass = self.two_pass_config(self.config, hasattr(self.model, "ctc_lo"))
         ctc_beam, ngram_path, ngram_w, ngram_bonus = self.ngram_config(self.config, two_pass, hasattr(self.model, "ctc_lo"))
         ngram = None
@@ -596,7 +665,9 @@ class Solver(object):
         preds, refs, beams = [], [], []
         for batch in self._feed(loader, sharded=False):
             xs, ilens, _ = batch
-            if ctc_greedy:
+            if rnnt_greedy:
+                preds += self._rnnt_greedy(xs, ilens)
+            elif ctc_greedy:
                 preds += self._ctc_best_path(xs, ilens)
             elif ctc_beam and nbest:
                 ranked = self._ctc_beams(xs, ilens, beam_size, ngram, nbest=True)
