@@ -294,14 +294,24 @@ def e2e_forward(sd, cfg, xs, ilens, ys=None, tf_rate=1.0, max_dec_timesteps=200,
                 smooth=False, scaling=1.0, label_smoothing=True, training=True,
                 total_length=None, olength_override=None):
     """E2E.forward.  cfg keys: enc_n_layers, subsample, dropout_rate, ls_weight, labeldist."""
+    return e2e_forward_with_encoder(sd, cfg, xs, ilens, ys, tf_rate, max_dec_timesteps, sample, smooth, scaling,
+                                    label_smoothing, training, total_length, olength_override)[2]
+
+
+def e2e_forward_with_encoder(sd, cfg, xs, ilens, ys=None, tf_rate=1.0, max_dec_timesteps=200, sample=False,
+                             smooth=False, scaling=1.0, label_smoothing=True, training=True,
+                             total_length=None, olength_override=None):
+    """e2e_forward that also hands out what the heads on the encoder output read (not in the reference, which has
+    none): -> (enc_h [B, T', H], enc_lens, E2E.forward's four results)."""
     enc_h, enc_lens = encoder_forward(sd, xs, ilens, cfg["enc_n_layers"], cfg["subsample"],
                                       cfg.get("dropout_rate", 0.0), training, total_length)
-    return decoder_forward(sd, enc_h, enc_lens, ys, tf_rate=tf_rate,
-                           max_dec_timesteps=max_dec_timesteps, sample=sample, smooth=smooth,
-                           scaling=scaling, label_smoothing=label_smoothing, training=training,
-                           ls_weight=cfg.get("ls_weight", 0.0), labeldist=cfg.get("labeldist"),
-                           dropout_rate=cfg.get("dropout_rate", 0.0),
-                           olength_override=olength_override)
+    out = decoder_forward(sd, enc_h, enc_lens, ys, tf_rate=tf_rate,
+                          max_dec_timesteps=max_dec_timesteps, sample=sample, smooth=smooth,
+                          scaling=scaling, label_smoothing=label_smoothing, training=training,
+                          ls_weight=cfg.get("ls_weight", 0.0), labeldist=cfg.get("labeldist"),
+                          dropout_rate=cfg.get("dropout_rate", 0.0),
+                          olength_override=olength_override)
+    return enc_h, enc_lens, out
 
 
 def masked_loss(log_probs, ys):

@@ -990,6 +990,7 @@ def ctc_loss_fwd(logits, ld, frame_lens, labels, label_offsets, max_label_len, z
     least ctc_ws_bytes bytes) are the caller's.  The workspace goes to ctc_loss_bwd unchanged."""
     args = _ctc_args(logits, ld, frame_lens, labels, label_offsets, max_label_len, zero_infinity)
     check(load().asr_ctc_loss_fwd(*args, ptr(nll), ptr(ws), ws.numel() * 4, stream()), "asr_ctc_loss_fwd")
+    LAUNCHES["ctc_loss"] += 1
     return nll
 
 
@@ -999,6 +1000,7 @@ def ctc_loss_bwd(logits, ld, frame_lens, labels, label_offsets, max_label_len, z
     args = _ctc_args(logits, ld, frame_lens, labels, label_offsets, max_label_len, zero_infinity)
     check(load().asr_ctc_loss_bwd(*args, ptr(grad_nll), ptr(ws), ws.numel() * 4, ptr(dlogits), int(lddz), stream()),
           "asr_ctc_loss_bwd")
+    LAUNCHES["ctc_loss_bwd"] += 1
     return dlogits
 
 

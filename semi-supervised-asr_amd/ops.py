@@ -1110,9 +1110,11 @@ class _RnntLoss(torch.autograd.Function):
 def rnnt_loss(logits, frame_lens_dev, labels_packed, label_lens):
     """-> nll [B], the transducer negative log-likelihood of each utterance.  logits [B, T, U + 1, V] fp32 raw
     (not log-softmaxed; a view with row stride >= V is taken as it is), frame_lens_dev int32 [B] on the device
-    (Encoder.last_lens_dev; every T_b >= 1), labels_packed the batch's labels as ONE int64 device tensor, label_lens their
-    counts per utterance (host integers; U = their maximum).  Blank = 0.  Every utterance has an alignment: there is no
-    zero_infinity case."""
+    (Encoder.last_lens_dev; an encoder gives every T_b >= 1), labels_packed the batch's labels as ONE int64 device tensor,
+    label_lens their counts per utterance (host integers; U = their maximum).  Blank = 0.  Every utterance with a frame has
+    an alignment: there is no zero_infinity case.  A row the kernels cannot score - T_b = 0, or a label outside [1, V) -
+    gives nll = +inf and an exact-zero gradient for that row alone (lengths and labels live on the device: no host check,
+    no synchronisation); the other rows are not affected."""
     return _RnntLoss.apply(logits, frame_lens_dev, labels_packed, label_lens)
 
 

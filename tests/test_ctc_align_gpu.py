@@ -119,12 +119,13 @@ def _overflow_case(hb):
 ALIGN_GRID = [(V, g, 1.0) for V in VOCABS for g in sorted(GROUPS)] + [(34, g, 50.0) for g in sorted(GROUPS)]
 
 
-def _run(hb, c):
+def _run(hb, c, extra=0):
     """ops.ctc_align on the case: the logits are a [B, T, V] view of a [B, T, V + 3] buffer (ld = V + 3) whose padding - the
-    frames behind every length and the three extra columns - is NaN."""
+    frames behind every length and the three extra columns - is NaN.  extra: that many frames more than the longest
+    utterance has (NaN too)."""
     import ops
     z, utts, V = c["z"], c["utts"], c["V"]
-    B, T = z.shape[:2]
+    B, T = z.shape[0], z.shape[1] + extra
     buf = np.full((B, T, V + 3), np.nan, dtype=np.float32)
     for i, (t, _) in enumerate(utts):
         buf[i, :t, :V] = z[i, :t]
@@ -197,6 +198,22 @@ def _runs(p):
 def test_align_against_float64(hb, case):
     c = _case(*case)
     _check(c, _run(hb, c), "V=%d %s x%g" % case)
+
+
+def test_align_time_axis_past_every_utterance(hb):
+    """The smallest ragged case on a time axis five frames longer than its longest utterance (a rank of a data-parallel
+    step): the checks above, -1 on the extra frames, and paths, first / last frames, scores and token sums exactly those of
+    the run at T = max(t)."""
+    case = (VOCABS[0], sorted(GROUPS)[-1], 1.0)
+    assert case == (2, "wave", 1.0)
+    c = _case(*case)
+    T = c["z"].shape[1]
+    long, short = _run(hb, c, extra=5), _run(hb, c)
+    assert tuple(long.path.shape) == (len(c["utts"]), T + 5)
+    _check(c, long, "V=%d %s x%g T+5" % case)
+    assert torch.equal(long.path[:, :T], short.path) and bool((long.path[:, T:] == -1).all())
+    for name in ("score", "first", "last", "token_logp", "offsets"):
+        assert torch.equal(getattr(long, name), getattr(short, name)), name
 
 
 def test_exemption_cap():

@@ -56,15 +56,19 @@ def _utterances(V, group, seed):
 _CASES = {}
 
 
-def _case(V, group, scale):
-    """Inputs and the CPU results (float64 checker, float32 yardstick) of one case, computed once."""
-    key = (V, group, scale)
+def _case(V, group, scale, extra=0):
+    """Inputs and the CPU results (float64 checker, float32 yardstick) of one case, computed once.  extra: frames behind the
+    longest utterance - the same utterances and logits on a time axis of max(t) + extra, which no utterance fills (a rank of
+    a data-parallel step: the encoder is padded to the global T_max)."""
+    key = (V, group, scale, extra)
     if key in _CASES:
         return _CASES[key]
     utts = _utterances(V, group, 100 + V)
     rs = np.random.RandomState(7 * V + len(group))
     B, T = len(utts), max(t for t, _ in utts)
     z = torch.from_numpy((scale * rs.normal(0, 1, size=(B, T, V))).astype(np.float32))
+    if extra:
+        z, T = torch.cat([z, torch.zeros(B, extra, V)], 1), T + extra
     lens = [t for t, _ in utts]
     for i, t in enumerate(lens):
         z[i, t:] = 0.0
@@ -137,6 +141,23 @@ def test_kernel_against_float64(hb, V, group):
     bad = int((~c["feasible"]).nonzero()[0])
     assert float(nll[bad]) == 0.0 and bool((grad[bad] == 0).all())
     _check(c, nll, grad, torch.arange(c["B"]), "V=%d %s" % (V, group))
+
+
+@pytest.mark.parametrize("group", sorted(GROUPS))
+def test_time_axis_past_every_utterance(hb, group):
+    """T = max(t) + 5: NaN behind every length, the five frames no utterance has included; ld = V + 3.  The allowance and the
+    zero gradient behind every length as above, and the bits of the run at T = max(t): every sum of the kernels has one
+    owner and the extent only changes strides."""
+    c, short = _case(34, group, 3.0, extra=5), _case(34, group, 3.0)
+    assert c["T"] == short["T"] + 5 and torch.equal(c["z"][:, :short["T"]], short["z"])
+    nll, grad = _run(hb, c)
+    assert grad.shape[1] == c["T"]
+    _check(c, nll, grad, torch.arange(c["B"]), "V=34 %s T+5" % group)
+    nll0, grad0 = _run(hb, short)
+    assert torch.equal(nll, nll0), "nll differs from the run at T = max(t)"
+    assert torch.equal(grad[:, :short["T"]], grad0), "the gradient differs from the run at T = max(t)"
+    assert bool((grad[:, short["T"]:] == 0).all())
+    print("ctc_parity V=34 %s T+5: bit-identical to T=%d" % (group, short["T"]))
 
 
 @pytest.mark.parametrize("group", sorted(GROUPS))

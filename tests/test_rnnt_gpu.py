@@ -93,25 +93,32 @@ def _loss_case(lattices, V, seed=0, T=None):
     return dict(lattices=lattices, B=B, T=T, U=U, V=V, z=z, ys=ys, g=g, ref=ref, f32=f32)
 
 
-def _run_loss(hb, c, pad=3):
+def _run_loss(hb, c, pad=3, lens=None, ys=None):
     """ops.rnnt_loss on the case.  pad > 0: the logits are a [B, T, U + 1, V] view of a [.., V + pad] buffer (ld = V + pad);
-    the extra columns and every padded node hold NaN."""
+    the extra columns and every padded node hold NaN.  lens / ys: other frame counts / labels than the case's (the rows a
+    test means the kernels to leave unscored)."""
     import ops
     B, T, U, V = c["B"], c["T"], c["U"], c["V"]
+    lens = [t for t, _ in c["lattices"]] if lens is None else list(lens)
+    ys = c["ys"] if ys is None else ys
     buf = torch.full((B, T, U + 1, V + pad), float("nan"))
-    for b, (t, u) in enumerate(c["lattices"]):
-        buf[b, :t, :u + 1, :V] = torch.from_numpy(c["z"][b, :t, :u + 1])
+    for b, (_, u) in enumerate(c["lattices"]):
+        buf[b, :lens[b], :u + 1, :V] = torch.from_numpy(c["z"][b, :lens[b], :u + 1])
     buf = buf.to(DEV).requires_grad_()
-    labels = torch.from_numpy(np.concatenate(c["ys"]) if c["ys"] else np.zeros(0, np.int64)).to(DEV)
-    nll = ops.rnnt_loss(buf[..., :V], hb.to_device_i32([t for t, _ in c["lattices"]], DEV), labels, [u for _, u in c["lattices"]])
+    labels = torch.from_numpy(np.concatenate(ys) if ys else np.zeros(0, np.int64)).to(DEV)
+    nll = ops.rnnt_loss(buf[..., :V], hb.to_device_i32(lens, DEV), labels, [u for _, u in c["lattices"]])
     nll.backward(torch.from_numpy(c["g"]).to(DEV))
     return nll.detach().cpu().numpy(), buf.grad.cpu().numpy()
 
 
-def _check_loss(c, nll, grad, what):
+def _check_loss(c, nll, grad, what, unscored=()):
+    """unscored: rows the call was given no frame or a label outside [1, V) for - nll +inf, the gradient exact zeros."""
     V, w = c["V"], _Worst()
-    assert np.isfinite(nll).all()
+    assert np.isfinite(np.delete(nll, list(unscored))).all()
     for b, (t, u) in enumerate(c["lattices"]):
+        if b in unscored:
+            assert nll[b] == np.inf and (grad[b] == 0).all(), "%s: utterance %d was scored" % (what, b)
+            continue
         valid = np.zeros(grad.shape[1:3], bool)
         valid[:t, :u + 1] = True
         assert (grad[b][~valid] == 0).all(), "%s: utterance %d has a gradient on a padded node" % (what, b)
@@ -148,6 +155,54 @@ def test_loss_is_bit_reproducible(hb):
         assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
         first = a if not det else first
         assert np.array_equal(a[0], first[0]) and np.array_equal(a[1], first[1])       # ... and the same in both modes
+
+
+# A time axis longer than every utterance of the call - what a rank of a data-parallel step hands the head, its encoder
+# padded to the global T_max: (lattices, T, V of the loss, J of the joint).  The kernels give every sum one owner and the
+# extent only changes strides, so the results on the frames the shorter extent has are the SAME BITS.
+LONG_AXIS = ((SMALL, 12, 34, 32), (((64, 63), (5, 3)), 70, 5, 32), (((1, 0),), 9, 34, 32), (((3, 257),), 4, 5, 32))
+_LONG_IDS = ["small-T12", "wave-T70", "one-node-T9", "strided-T4"]
+
+
+def _trimmed(c, *keys):
+    """The case on the extent of its longest utterance: the same inputs, the extra frames cut off."""
+    tmax = max(t for t, _ in c["lattices"])
+    assert tmax < c["T"]
+    return dict(c, T=tmax, **{k: np.ascontiguousarray(c[k][:, :tmax]) for k in keys})
+
+
+@pytest.mark.parametrize("pad", (3, 0))
+@pytest.mark.parametrize("lattices,T,V,J", LONG_AXIS, ids=_LONG_IDS)
+def test_loss_time_axis_past_every_utterance(hb, lattices, T, V, J, pad):
+    """NaN on every frame t >= T_b, the extra ones included: the float64 restatement under the file's allowance, exact zeros in
+    dlogits on all of them (_check_loss), and the bits of the same lattices at T = max T_b."""
+    c = _loss_case(lattices, V, T=T)
+    nll, grad = _run_loss(hb, c, pad=pad)
+    assert grad.shape[1] == T
+    what = "loss %s T=%d V=%d ld=V+%d" % (lattices if len(lattices) < 3 else "SMALL", T, V, pad)
+    _check_loss(c, nll, grad, what)
+    short = _trimmed(c, "z")
+    nll0, grad0 = _run_loss(hb, short, pad=pad)
+    assert np.array_equal(nll, nll0), "%s: nll differs from the run at T = %d" % (what, short["T"])
+    assert np.array_equal(grad[:, :short["T"]], grad0), "%s: dlogits differs from the run at T = %d" % (what, short["T"])
+    assert (grad[:, short["T"]:] == 0).all()
+    print("rnnt-parity %-34s bit-identical to T=%d" % (what, short["T"]))
+
+
+@pytest.mark.parametrize("kind", ("no frame", "label V", "label 0"))
+def test_loss_leaves_one_row_unscored(hb, kind):
+    """A batch of three whose middle row cannot be scored - T_b = 0, or a label outside [1, V): that row's nll is +inf and its
+    gradient exact zeros (rnnt_alpha_kernel leaves log P at -inf, rnnt_grad_kernel writes zeros without reading alpha or
+    beta), the other rows stay within the allowance.  No host check refuses such a row: the lengths and the labels are on
+    the device."""
+    c = _loss_case(((4, 2), (3, 3), (2, 1)), 34)
+    lens, ys = [t for t, _ in c["lattices"]], [y.copy() for y in c["ys"]]
+    if kind == "no frame":
+        lens[1] = 0
+    else:
+        ys[1][1] = c["V"] if kind == "label V" else 0
+    nll, grad = _run_loss(hb, c, lens=lens, ys=ys)
+    _check_loss(c, nll, grad, "loss B=3, row 1: %s" % kind, unscored=(1,))
 
 
 # ------------------------------------------------------------------------------------------------ joint
@@ -201,6 +256,23 @@ def test_joint_ragged_batch(hb, J):
 def test_joint_one_utterance(hb, lattice):
     c = _joint_case((lattice,), 32)
     _check_joint(c, *_run_joint(hb, c), "joint T=%d U=%d J=32" % lattice)
+
+
+@pytest.mark.parametrize("lattices,T,V,J", LONG_AXIS, ids=_LONG_IDS)
+def test_joint_time_axis_past_every_utterance(hb, lattices, T, V, J):
+    """PE rows and NaN upstream gradients on frames that belong to no utterance: exact zeros in Z and dPE on every frame
+    t >= T_b (_check_joint), the allowance, and the bits of the same lattices at T = max T_b."""
+    c = _joint_case(lattices, J, T=T)
+    z, dpe, dpp = _run_joint(hb, c)
+    assert z.shape[1] == T and dpe.shape[1] == T
+    what = "joint %s T=%d J=%d" % (lattices if len(lattices) < 3 else "SMALL", T, J)
+    _check_joint(c, z, dpe, dpp, what)
+    short = _trimmed(c, "pe", "dz")
+    z0, dpe0, dpp0 = _run_joint(hb, short)
+    n = short["T"]
+    assert np.array_equal(z[:, :n], z0) and np.array_equal(dpe[:, :n], dpe0) and np.array_equal(dpp, dpp0), what
+    assert (z[:, n:] == 0).all() and (dpe[:, n:] == 0).all()
+    print("rnnt-parity %-34s bit-identical to T=%d" % (what, n))
 
 
 def test_joint_is_bit_reproducible(hb):
