@@ -1403,6 +1403,63 @@ int asr_rnnt_greedy_step_f32(int B, int T, int J, int V, int L, int max_symbols,
                              int32_t* n_out, int32_t* n_frame, int32_t* out, int32_t* last, float* score, int32_t* advance,
                              asr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Beam search over the transducer head, with an n-gram LM inside when one is given (csrc/rnnt_beam.hip).  Not a
+ * reference operator.  Five entries added to ABI version 8 WITHOUT a version change: additive, like the groups above.
+ * The search is alignment-length synchronous: at iteration i every entry of an utterance's beam (at most K, 1 <= K <=
+ * ASR_BEAM_KMAX) has t + u = i (u its label count, at most L; t its frame).  Each iteration every live entry proposes its
+ * blank (same sequence, node (t + 1, u)) and, while u < L, its V - 1 labels (node (t, u + 1)); the blank of entry h and the
+ * label candidate (h', k) with seq(h') . k = seq(h) are one candidate with the logaddexp of the two masses (sequences compare
+ * by a 64-bit hash and their length; collisions are accepted), which keeps the flat index and the prediction state of its
+ * BLANK parent.  The best K candidates by rank (greater first, the lower flat index parent V + token on ties) are the next
+ * beam; rank = tot, or with an LM (tot + lm_alpha lm) + lm_beta u, every operation rounded on its own.  A blank taken at
+ * t = T_b - 1 is a final: it leaves the beam for the utterance's final list, the best K finals by rank (the earlier one
+ * first on ties); with lm_eos >= 0 the LM's end-of-sentence term joins a final's lm.  T + L iterations finish every row.
+ * One iteration is four launches: asr_transducer_beam_step_f32, the gate product gates = xh [w_ih | w_hh]^T + (b_ih + b_hh)
+ * (asr_gemm_f32, the caller's), asr_transducer_beam_cell_f32, and the projection pp = h w_pred^T (asr_gemm_f32, the caller's).
+ *   asr_transducer_beam_t              the call: sizes, the head's tensors, the caller's state h, c [B K][P] and xh [B K][E + P],
+ *                                pp [B K][J] (the projection of h), the LM (lm_logp NULL: none; logp fp32 / next int32
+ *                                [lm_states][V] as asr_ctc_beam_lm_f32 takes them), the workspace (8-byte aligned)
+ *   asr_transducer_beam_ws_bytes       plain integers, no GPU.  ASR_E_SHAPE for K outside 1 .. ASR_BEAM_KMAX, V < 2, J not a
+ *                                multiple of 4, K (J + V) * 4 bytes of LDS above ASR_RNNT_BEAM_LDS_BYTES, or (T + L) B K or
+ *                                B K (E + 4 P) above INT_MAX
+ *   asr_transducer_beam_init_f32       the empty sequence at (0, 0) for every utterance with a frame; xh = [emb[bos] | 0] and
+ *                                advance = 1 for its slot, zeros elsewhere.  The caller then runs gate product, cell, projection.
+ *   asr_transducer_beam_step_f32       iteration `it` (0 .. T + L - 1, in order): reads pp, h, c; writes the beam, a history record
+ *                                per slot, the finals, xh = [emb[token] | h[parent]], c[parent] and the advance flags
+ *   asr_transducer_beam_cell_f32       h, c [B K][P] from gates [B K][4 P] (i, f, g, o) where advance is set; the parent's elsewhere
+ *   asr_transducer_beam_backtrace_f32  hyp int32 [B][K][L] padded with -1, hyp_len int32 [B][K] (-1: unused), score fp32 [B][K]
+ *                                (the rank, descending, -inf: unused); rnnt_score (tot) and lm_score fp32 [B][K] or NULL.
+ *                                An utterance without a frame gives the empty hypothesis at tot 0 and nothing else.
+ * No floating-point atomics, sums in an order fixed by the shapes, 64-bit offsets, no host synchronisation, no allocation;
+ * frames t >= T_b, slots that are not live and workspace words the call has not written are never read.
+ * ------------------------------------------------------------------------------------- */
+#define ASR_RNNT_BEAM_LDS_BYTES (56 * 1024)
+typedef struct {
+  int B, T, J, V, K, L, E, P;
+  const float* pe;            /* [B][T][J] */
+  const float* pp;            /* [B K][J] */
+  const float* w_out;         /* [V][J] */
+  const float* b_out;         /* [V] or NULL */
+  const float* emb;           /* [V][E] */
+  const int32_t* frame_lens;  /* [B] */
+  const float* h;             /* [B K][P] */
+  const float* c;             /* [B K][P] */
+  float* xh;                  /* [B K][E + P] */
+  int lm_states, lm_start, lm_eos;
+  float lm_alpha, lm_beta;
+  const float* lm_logp;
+  const int32_t* lm_next;
+  void* ws;
+  int64_t ws_bytes;
+} asr_transducer_beam_t;
+int asr_transducer_beam_ws_bytes(int B, int T, int J, int V, int K, int L, int E, int P, int64_t* ws_bytes);
+int asr_transducer_beam_init_f32(const asr_transducer_beam_t* a, int bos, asr_stream_t stream);
+int asr_transducer_beam_step_f32(const asr_transducer_beam_t* a, int it, asr_stream_t stream);
+int asr_transducer_beam_cell_f32(const asr_transducer_beam_t* a, const float* gates, float* h, float* c, asr_stream_t stream);
+int asr_transducer_beam_backtrace_f32(const asr_transducer_beam_t* a, int32_t* hyp, int32_t* hyp_len, float* score, float* rnnt_score,
+                                float* lm_score, asr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,8 @@ EXPORTS = (
     "asr_reverb_f32", "asr_noise_mix_f32",
     "asr_rnnt_ws_bytes", "asr_rnnt_joint_fwd_f32", "asr_rnnt_joint_bwd_f32", "asr_rnnt_loss_fwd_f32", "asr_rnnt_loss_bwd_f32",
     "asr_rnnt_greedy_step_f32",
+    "asr_transducer_beam_ws_bytes", "asr_transducer_beam_init_f32", "asr_transducer_beam_step_f32", "asr_transducer_beam_cell_f32",
+    "asr_transducer_beam_backtrace_f32",
 )
 
 _lib = None
@@ -119,6 +121,14 @@ class CtcPrefix(ctypes.Structure):
     _fields_ = [(n, c_i) for n in ("B", "K", "V", "Tp", "blank", "eos")] + \
                [("logits", c_p), ("ld", ctypes.c_int64), ("frame_lens", c_p), ("lse", c_p), ("state", c_p * 2), ("last", c_p * 2),
                 ("psi", c_p), ("psi_prev", c_p)]
+
+
+class RnntBeamArgs(ctypes.Structure):
+    """asr_transducer_beam_t"""
+    _fields_ = [(n, c_i) for n in ("B", "T", "J", "V", "K", "L", "E", "P")] + \
+               [(n, c_p) for n in ("pe", "pp", "w_out", "b_out", "emb", "frame_lens", "h", "c", "xh")] + \
+               [(n, c_i) for n in ("lm_states", "lm_start", "lm_eos")] + [("lm_alpha", c_f), ("lm_beta", c_f)] + \
+               [("lm_logp", c_p), ("lm_next", c_p), ("ws", c_p), ("ws_bytes", c_i64)]
 
 
 class GemmPlan(ctypes.Structure):
@@ -313,6 +323,11 @@ def load():
     lib.asr_rnnt_loss_fwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
     lib.asr_rnnt_loss_bwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p]
     lib.asr_rnnt_greedy_step_f32.argtypes = [c_i] * 6 + [c_p] * 13
+    lib.asr_transducer_beam_ws_bytes.argtypes = [c_i] * 8 + [ctypes.POINTER(c_i64)]
+    lib.asr_transducer_beam_init_f32.argtypes = [ctypes.POINTER(RnntBeamArgs), c_i, c_p]
+    lib.asr_transducer_beam_step_f32.argtypes = [ctypes.POINTER(RnntBeamArgs), c_i, c_p]
+    lib.asr_transducer_beam_cell_f32.argtypes = [ctypes.POINTER(RnntBeamArgs), c_p, c_p, c_p, c_p]
+    lib.asr_transducer_beam_backtrace_f32.argtypes = [ctypes.POINTER(RnntBeamArgs), c_p, c_p, c_p, c_p, c_p, c_p]
     lib.asr_mwer_fwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
     lib.asr_mwer_bwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_f, c_p, c_i64, c_p]
     lib.asr_dec_feedback_fwd.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_p, c_i64,
@@ -1103,6 +1118,90 @@ def rnnt_greedy_step(pe, pp, w_out, b_out, frame_lens, t_cur, n_out, n_frame, ou
         raise UnsupportedShape("rnnt_greedy_step: J %d, V %d (V >= 2, J a multiple of 4, (J + V) floats within 64 KB)" % (J, V))
     check(rc, "asr_rnnt_greedy_step_f32")
     LAUNCHES["rnnt_greedy_step"] += 1
+
+
+RNNT_BEAM_LDS_BYTES = 56 * 1024      # ASR_RNNT_BEAM_LDS_BYTES: K (J + V) floats of the step kernel's LDS
+
+
+def rnnt_beam_ws_bytes(B, T, J, V, K, L, E, P):
+    """asr_transducer_beam_ws_bytes on plain integers (no tensors, no GPU) -> the workspace bytes of a transducer beam search;
+    UnsupportedShape for sizes the kernels refuse."""
+    need = c_i64(0)
+    rc = load().asr_transducer_beam_ws_bytes(int(B), int(T), int(J), int(V), int(K), int(L), int(E), int(P), ctypes.byref(need))
+    if rc == -2:
+        raise UnsupportedShape("rnnt_beam: B %d, T %d, J %d, V %d, beam %d, L %d (beam 1 .. %d, V >= 2, J a multiple of 4, "
+                               "beam (J + V) floats within %d bytes of LDS)" % (B, T, J, V, K, L, BEAM_KMAX, RNNT_BEAM_LDS_BYTES))
+    check(rc, "asr_transducer_beam_ws_bytes")
+    return need.value
+
+
+class RnntBeam(object):
+    """One transducer beam search (csrc/rnnt_beam.hip) over the caller's tensors: pe [B, T, J], w_out [V, J],
+    b_out [V] or None, emb [V, E], frame_lens int32 [B]; the state h, c [B K, P], xh [B K, E + P], pp [B K, J] and the
+    workspace ws (float32, at least rnnt_beam_ws_bytes bytes) are the caller's too, all contiguous fp32 on the device.  table:
+    the n-gram LM on the device or None.  init(), then per iteration step(it) - between them the caller runs the gate
+    product, cell() and the projection - and backtrace() behind the loop.  Every method is one launch."""
+
+    def __init__(self, pe, w_out, b_out, emb, frame_lens, K, L, h, c, xh, pp, ws, table=None, alpha=0.0, beta=0.0,
+                 eos_term=True):
+        B, T, J = pe.shape
+        V, E, P = w_out.shape[0], emb.shape[1], h.shape[1]
+        K, L = int(K), int(L)
+        floats = [pe, w_out, emb, h, c, xh, pp, ws] + ([b_out] if b_out is not None else [])
+        if any(not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()) for t in floats) or \
+                not (frame_lens.is_cuda and frame_lens.dtype == torch.int32 and frame_lens.numel() == B):
+            raise RuntimeError("rnnt_beam: contiguous fp32 tensors and frame_lens int32 [B] on the GPU")
+        need = rnnt_beam_ws_bytes(B, T, J, V, K, L, E, P)
+        if tuple(w_out.shape) != (V, J) or emb.shape[0] != V or tuple(h.shape) != (B * K, P) or tuple(c.shape) != (B * K, P) or \
+                tuple(xh.shape) != (B * K, E + P) or tuple(pp.shape) != (B * K, J) or ws.numel() * 4 < need:
+            raise RuntimeError("rnnt_beam: w_out [V, J], emb [V, E], h / c [B K, P], xh [B K, E + P], pp [B K, J] and a "
+                               "workspace of %d bytes" % need)
+        a = RnntBeamArgs()
+        a.B, a.T, a.J, a.V, a.K, a.L, a.E, a.P = B, T, J, V, K, L, E, P
+        a.pe, a.pp, a.w_out, a.b_out, a.emb, a.frame_lens = ptr(pe), ptr(pp), ptr(w_out), ptr(b_out), ptr(emb), ptr(frame_lens)
+        a.h, a.c, a.xh, a.ws, a.ws_bytes = ptr(h), ptr(c), ptr(xh), ptr(ws), ws.numel() * 4
+        if table is not None:
+            logp, nxt, S = _ngram_table(table, V, "rnnt_beam")
+            a.lm_logp, a.lm_next, a.lm_states, a.lm_start = ptr(logp), ptr(nxt), S, int(table.start)
+            a.lm_eos, a.lm_alpha, a.lm_beta = (int(table.eos) if eos_term else -1), float(alpha), float(beta)
+        else:
+            a.lm_logp, a.lm_next, a.lm_states, a.lm_start, a.lm_eos, a.lm_alpha, a.lm_beta = None, None, 0, 0, -1, 0.0, 0.0
+        self.args, self.B, self.K, self.L, self.h, self.c = a, B, K, L, h, c
+        self._keep = (pe, w_out, b_out, emb, frame_lens, h, c, xh, pp, ws, table)
+
+    def _run(self, rc, what):
+        if rc == ASR_E_SHAPE:
+            raise UnsupportedShape("%s: refused the sizes or the n-gram table" % what)
+        check(rc, what)
+        LAUNCHES["rnnt_beam_launch"] += 1
+
+    def init(self, bos):
+        self._run(load().asr_transducer_beam_init_f32(ctypes.byref(self.args), int(bos), stream()), "asr_transducer_beam_init_f32")
+
+    def step(self, it):
+        self._run(load().asr_transducer_beam_step_f32(ctypes.byref(self.args), int(it), stream()), "asr_transducer_beam_step_f32")
+        LAUNCHES["rnnt_beam_step"] += 1
+
+    def cell(self, gates):
+        if tuple(gates.shape) != (self.h.shape[0], 4 * self.h.shape[1]) or not gates.is_contiguous():
+            raise RuntimeError("rnnt_beam: gates must be contiguous [B K, 4 P]")
+        self._run(load().asr_transducer_beam_cell_f32(ctypes.byref(self.args), ptr(gates), ptr(self.h), ptr(self.c), stream()),
+                  "asr_transducer_beam_cell_f32")
+
+    def product(self, x, w, out, bias=None):
+        """out = x w^T (+ bias) on asr_gemm_f32, unsplit: the same bits in and outside deterministic mode.  One launch."""
+        gemm(x, w, trans_b=True, bias=bias, out=out, split_k=1)
+        LAUNCHES["rnnt_beam_launch"] += 1
+
+    def backtrace(self, hyp, hyp_len, score, rnnt_score=None, lm_score=None):
+        B, K, L = self.B, self.K, self.L
+        outs = [hyp_len, score] + [t for t in (rnnt_score, lm_score) if t is not None]
+        if tuple(hyp.shape) != (B, K, L) or hyp.dtype != torch.int32 or not hyp.is_contiguous() or \
+                any(t.numel() != B * K or not t.is_contiguous() for t in outs):
+            raise RuntimeError("rnnt_beam: hyp int32 [B, K, L], hyp_len / score [B, K], contiguous")
+        self._run(load().asr_transducer_beam_backtrace_f32(ctypes.byref(self.args), ptr(hyp), ptr(hyp_len), ptr(score),
+                                                     ptr(rnnt_score), ptr(lm_score), stream()),
+                  "asr_transducer_beam_backtrace_f32")
 
 
 def _mwer_dims(logits, tokens, B):

@@ -1246,6 +1246,64 @@ def ctc_beam(logits, frame_lens_dev, beam, ngram=None, ngram_weight=0.0, ngram_b
     return hyp, hyp_len, score, ctc_score, lm_score
 
 
+def rnnt_beam(pe, frame_lens_dev, w_gate, b_gate, w_pred, w_out, b_out, emb, bos, beam, max_len, ngram=None, ngram_weight=0.0,
+              ngram_bonus=0.0, eos_term=True):
+    """Beam search over the transducer head (csrc/rnnt_beam.hip): pe [B, T', J] the projected encoder output,
+    w_gate [4 P, E + P] = [w_ih | w_hh] and b_gate = b_ih + b_hh of the prediction cell, w_pred [J, P], w_out [V, J], b_out
+    [V], emb [V, E] -> (hyp int32 [B, beam, max_len] padded with -1, hyp_len int32 [B, beam] with -1 in unused slots, score
+    fp32 [B, beam] descending with -inf in unused slots): the conventions of ctc_beam.  With ngram (an ngram.NgramLM, or its
+    table on the device) candidates rank by (tot + ngram_weight lm) + ngram_bonus u, eos_term adds the LM's end-of-sentence
+    term to a final -> (hyp, hyp_len, score: the rank, rnnt_score: tot, lm_score: lm).  A fixed T' + max_len iterations of
+    four launches (the step kernel, the gate product, the cell kernel, the projection; the last iteration is the step
+    kernel alone), four launches before the loop and the backtrace behind it: 4 (T' + max_len) + 2 in all.  The state and
+    the workspace are ONE buffer leased from the pool for the call; nothing in it is read before the call has written it.
+    Forward only, no host synchronisation."""
+    pe = pe.detach().contiguous()
+    B, T, J = pe.shape
+    K, L, dev = int(beam), int(max_len), pe.device
+    if L < 1:
+        raise ValueError("rnnt_beam: max_len must be at least 1, got %d" % L)
+    V, E, P = w_out.shape[0], emb.shape[1], w_pred.shape[1]
+    r64 = lambda n: (n + 63) // 64 * 64                              # noqa: E731
+    sizes = [r64((hb.rnnt_beam_ws_bytes(B, T, J, V, K, L, E, P) + 3) // 4)] + \
+        [r64(B * K * n) for n in (P, P, E + P, 4 * P, J)]
+    cap = _row_capacity(sum(sizes))
+    lease = _POOL.acquire(("rnnt_beam", str(dev), cap), lambda: torch.empty(cap, device=dev, dtype=torch.float32))
+    try:
+        cuts, at = [], 0
+        for n in sizes:
+            cuts.append(lease.ws[at:at + n])
+            at += n
+        ws = cuts[0]
+        h, c, xh, gates, pp = (t[:B * K * n].view(B * K, n) for t, n in zip(cuts[1:], (P, P, E + P, 4 * P, J)))
+        table = None if ngram is None else _ngram_table(ngram, dev)
+        run = hb.RnntBeam(pe, w_out.detach().contiguous(), None if b_out is None else b_out.detach().contiguous(),
+                          emb.detach().contiguous(), frame_lens_dev, K, L, h, c, xh, pp, ws, table, float(ngram_weight),
+                          float(ngram_bonus), bool(eos_term))
+        w_gate, b_gate, w_pred = w_gate.detach(), b_gate.detach(), w_pred.detach()
+        n_it = T + L
+        run.init(bos)
+        for it in range(n_it + 1):
+            if it > 0:
+                run.step(it - 1)
+                if it == n_it:
+                    break
+            run.product(xh, w_gate, gates, b_gate)
+            run.cell(gates)
+            run.product(h, w_pred, pp)
+        hyp = torch.empty(B, K, L, device=dev, dtype=torch.int32)
+        hyp_len = torch.empty(B, K, device=dev, dtype=torch.int32)
+        score = torch.empty(B, K, device=dev, dtype=torch.float32)
+        if table is None:
+            run.backtrace(hyp, hyp_len, score)
+            return hyp, hyp_len, score
+        rnnt_score, lm_score = torch.empty_like(score), torch.empty_like(score)
+        run.backtrace(hyp, hyp_len, score, rnnt_score, lm_score)
+        return hyp, hyp_len, score, rnnt_score, lm_score
+    finally:
+        lease.release()
+
+
 def _ngram_table(ngram, dev):
     """An ngram.NgramLM (compiled and uploaded once per device) or an ngram.NgramTable -> the table on dev."""
     return ngram.to(dev)

@@ -375,6 +375,52 @@ class Solver(object):
                              % ", ".join(others))
         return True
 
+    @staticmethod
+    def rnnt_beam_config(config, has_rnnt_head):
+        """`rnnt_beam_decode` (not a reference key; default false): test() decodes with the transducer head's beam
+        search (E2E.recognize_rnnt_beams, beam width `beam_size`, at most `max_dec_timesteps` labels), with `ngram_lm` inside
+        it when that is set (`ngram_weight`, `ngram_bonus`).  It is a decoder of its own -> the key as a bool; ValueError on a
+        model without the head or beside any other decoder's key, `word_lm` or `lm_weight`."""
+        if not bool(config.get("rnnt_beam_decode", False)):
+            return False
+        if not has_rnnt_head:
+            raise ValueError("rnnt_beam_decode needs the transducer head: build the model with rnnt_weight > 0")
+        others = [k for k in ("rnnt_greedy_decode", "two_pass_decode", "ctc_beam_decode", "ctc_greedy_decode", "word_lm")
+                  if config.get(k)]
+        others += [k + " > 0" for k in ("lm_weight", "ctc_decode_weight") if float(config.get(k, 0.0) or 0.0) > 0]
+        if others:
+            raise ValueError("rnnt_beam_decode decodes with the transducer head alone: it does not combine with %s "
+                             "(ngram_lm is the LM of this search)" % ", ".join(others))
+        if config.get("ngram_lm") is None:
+            for key in ("ngram_weight", "ngram_bonus"):
+                if key in config:
+                    raise ValueError("%s is set without ngram_lm, the ARPA file it weighs" % key)
+        return True
+
+    def _rnnt_beams(self, xs, ilens, beam_size, ngram=None, nbest=False):
+        """Hypothesis ids of the transducer beam search for one batch (E2E.recognize_rnnt_beams, with the n-gram LM inside
+        when there is one) - with nbest beam_size id lists per utterance, ranked, a rank the search left unused as a row of
+        <EOS>; the abort word of the encoder's persistent kernels is checked after the decode, as in _greedy."""
+        kw = dict(max_dec_timesteps=int(self.config.get("max_dec_timesteps", 200) or 200), **self._lm_kwargs(ngram))
+
+        def run():
+            ids = self.model.recognize_rnnt_beams(xs, ilens, beam_size, **kw)
+            if not nbest:
+                return ids
+            last = self.model.last_rnnt_beams
+            eos = self.vocab["<EOS>"]
+            rows = torch.cat([last["lengths"].unsqueeze(2), last["tokens"]], dim=2).cpu().tolist()
+            hyps = [[r[1:1 + max(r[0], 0)] for r in utt] for utt in rows]
+            width = max(len(h) for utt in hyps for h in utt) + 1
+            return [[h + [eos] * (width - len(h)) for h in utt] for utt in hyps]
+        out = run()
+        if self._abort_seen(xs.device):
+            print("persistent kernels aborted during transducer beam decoding (this rank's code %d): repeating the batch on "
+                  "the per-step kernels" % hb.persist_abort_code(xs.device))
+            hb.disable_persistent(xs.device)
+            out = run()
+        return out
+
     def _rnnt_greedy(self, xs, ilens):
         """Greedy hypothesis ids of the transducer head for one batch (E2E.recognize_rnnt); the abort word of the encoder's
         persistent kernels is checked after the decode and the batch repeated on the per-step kernels, as in _greedy."""
@@ -622,9 +668,19 @@ class Solver(object):
                            or float(self.config.get("ctc_decode_weight", 0.0) or 0.0) > 0):
             raise ValueError("ctc_greedy_decode decodes with the CTC head alone: it does not combine with beam_size > 1, "
                              "lm_weight > 0 or ctc_decode_weight > 0")
-        rnnt_greedy = self.rnnt_decode_config(self.config, hasattr(self.model, "rnnt"))
-        two_pass = self.two_pass_config(self.config, hasattr(self.model, "ctc_lo"))
-        ctc_beam, ngram_path, ngram_w, ngram_bonus = self.ngram_config(self.config, two_pass, hasattr(self.model, "ctc_lo"))
+        # `rnnt_beam_decode` (not a reference key; default false): the transducer head's beam search, a decoder
+        # of its own with a place for `ngram_lm`; the n-gram keys are its own then, and every other path below sees a
+        # configuration without them.  Absent, nothing here differs from a configuration that never had the key.
+        rnnt_beam = self.rnnt_beam_config(self.config, hasattr(self.model, "rnnt"))
+        cfg = self.config
+        if rnnt_beam:
+            cfg = {k: v for k, v in self.config.items() if k not in ("ngram_lm", "ngram_weight", "ngram_bonus", "beam_size")}
+        rnnt_greedy = self.rnnt_decode_config(cfg, hasattr(self.model, "rnnt"))
+        two_pass = self.two_pass_config(cfg, hasattr(self.model, "ctc_lo"))
+        ctc_beam, ngram_path, ngram_w, ngram_bonus = self.ngram_config(cfg, two_pass, hasattr(self.model, "ctc_lo"))
+        if rnnt_beam and self.config.get("ngram_lm") is not None:
+            ngram_path = self.config["ngram_lm"]
+            ngram_w, ngram_bonus = (float(self.config.get(k, 0.0) or 0.0) for k in ("ngram_weight", "ngram_bonus"))
         ngram = None
         if ngram_path is not None:
             from ngram import NgramLM
@@ -665,7 +721,13 @@ class Solver(object):
         preds, refs, beams = [], [], []
         for batch in self._feed(loader, sharded=False):
             xs, ilens, _ = batch
-            if rnnt_greedy:
+            if rnnt_beam and nbest:
+                ranked = self._rnnt_beams(xs, ilens, beam_size, ngram, nbest=True)
+                preds += [hyps[0] for hyps in ranked]
+                beams += ranked
+            elif rnnt_beam:
+                preds += self._rnnt_beams(xs, ilens, beam_size, ngram)
+            elif rnnt_greedy:
                 preds += self._rnnt_greedy(xs, ilens)
             elif ctc_greedy:
                 preds += self._ctc_best_path(xs, ilens)
