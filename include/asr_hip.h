@@ -1404,6 +1404,50 @@ int asr_rnnt_greedy_step_f32(int B, int T, int J, int V, int L, int max_symbols,
                              asr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Transducer forced alignment (csrc/rnnt_align.hip): the Viterbi (max-product) companion of asr_rnnt_loss_fwd_f32
+ * on the same inputs - where in the audio each label of a transcript sits.  Not a reference operator.  Two entries added to
+ * ABI version 8 WITHOUT a version change: additive, like the groups above (and named asr_transducer_* like the beam
+ * search's: the asr_rnnt_* group stays the six entries of csrc/rnnt.hip).
+ * B, T, U, V, logits, ld, frame_lens, labels, label_offsets are asr_rnnt_loss_fwd_f32's: RAW logits [B][T][U + 1][V] fp32 with
+ * row stride ld >= V, frame_lens DEVICE int32 [B], ONE packed DEVICE int64 label tensor with DEVICE int32 offsets [B + 1],
+ * blank = 0.  lp_k(t,u) = logits[b][t][u][k] - logsumexp_v logits[b][t][u]; nodes with t >= T_b or u > U_b are never read and
+ * may hold NaN.
+ *   asr_transducer_align_f32       v(0,0) = 0, v(t,u) = max(v(t-1,u) + lp_0(t-1,u), v(t,u-1) + lp_{y_u}(t,u-1)), a term off the
+ *                            lattice absent; score[b] = v(T_b-1,U_b) + lp_0(T_b-1,U_b), and the path that attains it.
+ *                            TIE RULE (it makes the path a function of the inputs): when the two candidates compare equal the
+ *                            BLANK predecessor (t-1,u) wins - on an all-equal lattice every label is emitted at frame 0.
+ *                              score        fp32 [B]      the log-probability of the best alignment
+ *                              emit_frame   int32, packed like labels: the frame t on whose arc (t,i-1) -> (t,i) label i
+ *                                                         (1-based) is emitted
+ *                              token_logp   fp32, packed like labels: lp_{y_i}(emit_frame_i, i-1)
+ *                              frame_labels int32 [B][T]  the u at which frame t's blank is taken: the labels emitted up to
+ *                                                         and including frame t; -1 for t >= T_b
+ *                              blank_logp   fp32 [B][T]   lp_0(t, frame_labels[t]); EXACT 0 for t >= T_b
+ *                            so that score = sum_i token_logp_i + sum_t blank_logp_t up to the order of the additions.
+ *                            NOT ALIGNED (T_b = 0, a label outside [1, V), more than U labels): score = -inf, emit_frame = -1,
+ *                            token_logp = -inf, frame_labels = -1, blank_logp = 0, for that row alone.  Every other utterance
+ *                            has an alignment.  Every output element is written (no prior fill needed).
+ *                            Two launches: a wave per node writes the node's two emissions lp_0 and lp_{y_{u+1}} (no
+ *                            [.., V] log-prob tensor exists); then one workgroup per utterance (one wave up to U + 1 = 64
+ *                            label positions, 256 threads beyond, positions strided over the workgroup above 256) runs the
+ *                            chain by anti-diagonals t + u = d, the backtrace (one wave) and the output passes.  Each node's
+ *                            choice is one bit, a 64-bit word per (diagonal, 64 label positions), in the workspace.
+ *   asr_transducer_align_ws_bytes  plain integers, no GPU: the bytes of the workspace (8-byte aligned: ASR_E_ALIGN): with N =
+ *                            B T (U + 1) rounded up to 64 and W = ceil((U + 1) / 64):  8 N  (the two emissions of every
+ *                            node) + 8 B (T + U) W  (the back-pointers).  ASR_E_SHAPE for V < 2, U > ASR_RNNT_MAX_LABELS, or a
+ *                            node matrix beyond asr_rnnt_ws_bytes's bounds (B T (U + 1) max(4, V) <= 2^40 elements and
+ *                            B T (U + 1) / 4 workgroups <= 2^31 - 1).
+ * No floating-point atomics, adds and compares only behind the row log-sum-exp, 64-bit offsets, no host synchronisation, no
+ * allocation; a function of the inputs and shapes only - the same bits in every run, in and outside deterministic mode, and
+ * for a row alone or inside a batch.
+ * ------------------------------------------------------------------------------------- */
+int asr_transducer_align_ws_bytes(int B, int T, int U, int V, int64_t* ws_bytes);
+int asr_transducer_align_f32(int B, int T, int U, int V, const float* logits, int64_t ld, const int32_t* frame_lens,
+                       const int64_t* labels, const int32_t* label_offsets, float* score, int32_t* emit_frame,
+                       float* token_logp, int32_t* frame_labels, float* blank_logp, void* ws, int64_t ws_bytes,
+                       asr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Beam search over the transducer head, with an n-gram LM inside when one is given (csrc/rnnt_beam.hip).  Not a
  * reference operator.  Five entries added to ABI version 8 WITHOUT a version change: additive, like the groups above.
  * The search is alignment-length synchronous: at iteration i every entry of an utterance's beam (at most K, 1 <= K <=

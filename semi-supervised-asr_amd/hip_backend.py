@@ -39,6 +39,7 @@ EXPORTS = (
     "asr_reverb_f32", "asr_noise_mix_f32",
     "asr_rnnt_ws_bytes", "asr_rnnt_joint_fwd_f32", "asr_rnnt_joint_bwd_f32", "asr_rnnt_loss_fwd_f32", "asr_rnnt_loss_bwd_f32",
     "asr_rnnt_greedy_step_f32",
+    "asr_transducer_align_ws_bytes", "asr_transducer_align_f32",
     "asr_transducer_beam_ws_bytes", "asr_transducer_beam_init_f32", "asr_transducer_beam_step_f32", "asr_transducer_beam_cell_f32",
     "asr_transducer_beam_backtrace_f32",
 )
@@ -323,6 +324,8 @@ def load():
     lib.asr_rnnt_loss_fwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
     lib.asr_rnnt_loss_bwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p]
     lib.asr_rnnt_greedy_step_f32.argtypes = [c_i] * 6 + [c_p] * 13
+    lib.asr_transducer_align_ws_bytes.argtypes = [c_i, c_i, c_i, c_i, ctypes.POINTER(c_i64)]
+    lib.asr_transducer_align_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
     lib.asr_transducer_beam_ws_bytes.argtypes = [c_i] * 8 + [ctypes.POINTER(c_i64)]
     lib.asr_transducer_beam_init_f32.argtypes = [ctypes.POINTER(RnntBeamArgs), c_i, c_p]
     lib.asr_transducer_beam_step_f32.argtypes = [ctypes.POINTER(RnntBeamArgs), c_i, c_p]
@@ -1118,6 +1121,38 @@ def rnnt_greedy_step(pe, pp, w_out, b_out, frame_lens, t_cur, n_out, n_frame, ou
         raise UnsupportedShape("rnnt_greedy_step: J %d, V %d (V >= 2, J a multiple of 4, (J + V) floats within 64 KB)" % (J, V))
     check(rc, "asr_rnnt_greedy_step_f32")
     LAUNCHES["rnnt_greedy_step"] += 1
+
+
+def rnnt_align_ws_bytes(B, T, U, V):
+    """asr_transducer_align_ws_bytes on plain integers (no tensors, no GPU) -> the workspace bytes of an rnnt_align call over B
+    utterances of at most T frames and U labels, vocabulary V; UnsupportedShape for sizes the kernels refuse (V < 2, more
+    than RNNT_MAX_LABELS labels, a node matrix beyond rnnt_ws_bytes's bounds)."""
+    need = c_i64(0)
+    rc = load().asr_transducer_align_ws_bytes(int(B), int(T), int(U), int(V), ctypes.byref(need))
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("rnnt_align: B %d, T %d, U %d, V %d (V >= 2, at most %d labels, B T (U + 1) max(4, V) <= 2^40)"
+                               % (B, T, U, V, RNNT_MAX_LABELS))
+    check(rc, "asr_transducer_align_ws_bytes")
+    return int(need.value)
+
+
+def rnnt_align(logits, ld, frame_lens, labels, label_offsets, score, emit_frame, token_logp, frame_labels, blank_logp, ws):
+    """asr_transducer_align_f32 (csrc/rnnt_align.hip): the best alignment of every utterance's labels on the
+    transducer lattice.  The inputs are rnnt_loss_fwd's; the outputs score fp32 [B], emit_frame int32 and token_logp fp32
+    (packed like labels), frame_labels int32 [B, T], blank_logp fp32 [B, T] and the workspace ws (a float32 tensor of at
+    least rnnt_align_ws_bytes bytes) are the caller's.  Two launches."""
+    args = _rnnt_loss_args(logits, ld, frame_lens, labels, label_offsets)
+    B, T = args[0], args[1]
+    if emit_frame.dtype != torch.int32 or frame_labels.dtype != torch.int32 or emit_frame.numel() != token_logp.numel() or \
+            score.numel() != B or tuple(frame_labels.shape) != (B, T) or tuple(blank_logp.shape) != (B, T) or \
+            not (frame_labels.is_contiguous() and blank_logp.is_contiguous()):
+        raise RuntimeError("rnnt_align: score [B], emit_frame int32 / token_logp packed like labels, frame_labels int32 and "
+                           "blank_logp [B, T], contiguous")
+    rnnt_align_ws_bytes(B, T, args[2], args[3])
+    check(load().asr_transducer_align_f32(*args, ptr(score), ptr(emit_frame), ptr(token_logp), ptr(frame_labels), ptr(blank_logp),
+                                    ptr(ws), ws.numel() * 4, stream()), "asr_transducer_align_f32")
+    LAUNCHES["rnnt_align"] += 1
+    LAUNCHES["rnnt_align_launch"] += 2
 
 
 RNNT_BEAM_LDS_BYTES = 56 * 1024      # ASR_RNNT_BEAM_LDS_BYTES: K (J + V) floats of the step kernel's LDS

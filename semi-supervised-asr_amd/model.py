@@ -944,6 +944,38 @@ class E2E(torch.nn.Module):
         self.last_alignment = res                                # (the device tensors of the call, path included)
         return out
 
+    def align_rnnt(self, xs, ilens, ys):
+        """Forced alignment of the transcripts `ys` (a list of label tensors, as forward takes them) to the utterances with
+        the transducer head (not a reference method): encoder, TransducerHead.logits, ops.rnnt_align.  -> one
+        dict per utterance: tokens (the label ids), frame (the ENCODER frame on which each token is emitted; times
+        time_reduction for input frames), confidence (exp(token_logp): the head's posterior of the token at its node; 0 on
+        a row that cannot be aligned, whose frames are -1), score (the log-probability of the best alignment; -inf: not
+        aligned) and frames (the utterance's encoder frames).  self.last_rnnt_alignment keeps the device result
+        (ops.RnntAlignment).  One host read."""
+        if not hasattr(self, "rnnt"):
+            raise ValueError("align_rnnt needs the transducer head: build the model with rnnt_weight > 0")
+        if xs.is_cuda:
+            hb.upload_side_stream_for(xs.shape[0] * xs.shape[1])
+        with torch.no_grad():
+            enc_h, enc_lens = self.encoder(xs, ilens)
+            lens_dev = self.encoder.enc2.last_lens_dev
+            labels = torch.cat([y.reshape(-1) for y in ys]).to(device=enc_h.device, dtype=torch.long)
+            counts = [int(y.numel()) for y in ys]
+            res = ops.rnnt_align(self.rnnt.logits(enc_h, ys, lens_dev), lens_dev, labels, counts)
+            # one read: [frame, confidence, label] per label, then the scores
+            packed = torch.cat([res.emit_frame.double(), torch.exp(res.token_logp).double(), labels.double(),
+                                res.score.double()]).cpu()
+        n = labels.numel()
+        frame, conf, toks, score = (packed[:n].long().tolist(), packed[n:2 * n].tolist(), packed[2 * n:3 * n].long().tolist(),
+                                    packed[3 * n:].tolist())
+        out, o = [], 0
+        for b, c in enumerate(counts):
+            out.append(dict(tokens=toks[o:o + c], frame=frame[o:o + c], confidence=conf[o:o + c], score=score[b],
+                            frames=int(enc_lens[b])))
+            o += c
+        self.last_rnnt_alignment = res
+        return out
+
     def recognize_ctc(self, xs, ilens):
         """Best-path decoding with the CTC head alone (not a reference method): the argmax token of every
         encoder frame, repeats collapsed, blanks dropped (ops.ctc_greedy) -> one id list per utterance."""

@@ -1198,6 +1198,50 @@ def ctc_align(logits, frame_lens_dev, labels_packed, label_lens):
     return out
 
 
+class RnntAlignment(object):
+    """What ops.rnnt_align returns, every field a device tensor: score fp32 [B] (the best alignment's log-probability, -inf:
+    the row cannot be aligned), packed like the labels emit_frame int32 (the encoder frame on which label i is emitted, -1:
+    not aligned) and token_logp fp32 (the log-probability of that emission), frame_labels int32 [B, T'] (the labels emitted
+    up to and including frame t, -1 behind the utterance) and blank_logp fp32 [B, T'] (the log-probability of the blank that
+    leaves frame t, 0 behind the utterance); offsets int32 [B + 1] (utterance b owns [offsets[b], offsets[b + 1]) of the
+    packed fields) with label_lens, the host's counts."""
+
+    __slots__ = ("score", "emit_frame", "token_logp", "frame_labels", "blank_logp", "offsets", "label_lens")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def rnnt_align(logits, frame_lens_dev, labels_packed, label_lens):
+    """-> RnntAlignment: the best alignment (Viterbi) of each utterance's labels on the transducer lattice,
+    asr_transducer_align_f32 (csrc/rnnt_align.hip), two launches.  The arguments are ops.rnnt_loss's: logits
+    [B, T', U + 1, V] fp32 raw (a view with row stride >= V is taken as it is), frame_lens_dev int32 [B] on the device,
+    labels_packed ONE int64 device tensor, label_lens host integers (U = their maximum); blank = 0, and the blank
+    predecessor wins a tie.  Forward only: logits that require grad are accepted and nothing is recorded.  No host
+    synchronisation."""
+    logits = logits.detach()
+    B, T, U1, V = logits.shape
+    ld = logits.stride(2)
+    if not (logits.stride(3) == 1 and ld >= V and logits.stride(1) == U1 * ld and logits.stride(0) == T * U1 * ld):
+        logits, ld = logits.contiguous(), V
+    lens, offsets, umax = _label_offsets("rnnt_align", label_lens, B, labels_packed.numel())
+    if umax + 1 != U1:
+        raise ValueError("rnnt_align: the logits hold %d label positions, the longest transcript needs %d" % (U1, umax + 1))
+    total, dev = offsets[-1], logits.device
+    ws = torch.empty((hb.rnnt_align_ws_bytes(B, T, umax, V) + 3) // 4, device=dev, dtype=torch.float32)
+    offs_dev = hb.to_device_i32(offsets, dev)
+    # (a batch of empty transcripts has no label to point at: the library wants a pointer all the same)
+    labels = labels_packed.contiguous() if total else torch.zeros(1, device=dev, dtype=torch.long)
+    i32, f32 = dict(device=dev, dtype=torch.int32), dict(device=dev, dtype=torch.float32)
+    out = RnntAlignment(score=torch.empty(B, **f32), emit_frame=torch.empty(total, **i32), token_logp=torch.empty(total, **f32),
+                        frame_labels=torch.empty(B, T, **i32), blank_logp=torch.empty(B, T, **f32), offsets=offs_dev,
+                        label_lens=lens)
+    hb.rnnt_align(logits, ld, frame_lens_dev, labels, offs_dev, out.score, out.emit_frame, out.token_logp, out.frame_labels,
+                  out.blank_logp, ws)
+    return out
+
+
 def ctc_greedy(logits, frame_lens_dev):
     """-> (ids int32 [B, T'] padded with -1, n int32 [B], frame_tok int32 [B, T']): best-path CTC decoding of raw logits
     [B, T', V] - the argmax of every frame, repeats collapsed, blanks (index 0) dropped: asr_ctc_greedy_f32, one launch.

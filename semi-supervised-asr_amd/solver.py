@@ -599,6 +599,32 @@ class Solver(object):
             self.model.train(was_training)
         return records
 
+    def align_rnnt(self, loader=None):
+        """Forced alignment of every utterance of `loader` (default: the dev loader) to its transcript with the model's
+        transducer head (E2E.align_rnnt; the model needs `rnnt_weight` > 0) -> one record per utterance, in
+        the loader's order: tokens (the vocabulary's symbols), frame (the encoder frame each token is emitted on; times
+        model.time_reduction for input frames), confidence (per token), score (the alignment's log-probability) and frames.
+        The device results are read once per batch."""
+        self.flush()
+        loader = self.dev_loader if loader is None else loader
+        symbols = {i: s for s, i in self.vocab.items()}
+        was_training = self.model.training
+        self.model.eval()
+        records = []
+        try:
+            for batch in self._feed(loader, sharded=False):
+                xs, ilens, ys = batch
+                out = self.model.align_rnnt(xs, ilens, ys)
+                if self._abort_seen(xs.device):                 # see _greedy
+                    hb.disable_persistent(xs.device)
+                    out = self.model.align_rnnt(xs, ilens, ys)
+                for rec in out:
+                    rec["tokens"] = [symbols[i] for i in rec["tokens"]]
+                records += out
+        finally:
+            self.model.train(was_training)
+        return records
+
     def validation(self):
         """Teacher-forced dev loss + greedy CER (solver.py:212-242); greedy pass runs without autograd."""
         self.flush()
