@@ -1504,6 +1504,47 @@ int asr_transducer_beam_cell_f32(const asr_transducer_beam_t* a, const float* ga
 int asr_transducer_beam_backtrace_f32(const asr_transducer_beam_t* a, int32_t* hyp, int32_t* hyp_len, float* score, float* rnnt_score,
                                 float* lm_score, asr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The transducer beam search with a lexicon and a word-level n-gram LM inside (csrc/rnnt_beam.hip, csrc/word_lm.h; DESIGN
+ * 4.30).  Not reference operators.  Four entries added to ABI version 8 WITHOUT a version change: additive.  The search is
+ * the group's above, entry for entry - the walk, the merge, the blank parent's slot, K, the T + L iterations, the finals -
+ * and asr_transducer_beam_t, asr_transducer_beam_ws_bytes, asr_transducer_beam_cell_f32 and the two products are used as they
+ * are; the LM is an asr_word_lm_t with its lookup as defined there, and a->lm_logp must be NULL (ASR_E_ARG).
+ * An entry additionally carries node (its lexicon trie node: 0 the root, -1 off the trie), wstate (its word-LM state), lm
+ * (the fp32 sum over its COMPLETED words) and nw (their count): functions of the token sequence, so a merge touches tot
+ * alone.  The blank candidate keeps all four.  A label k != space: node' = node >= 0 ? trie_next[node][k] : -1, the rest
+ * unchanged; with lexicon_only node' < 0 is no candidate.  The label `space` from the root changes nothing; elsewhere the
+ * pending word w = trie_word[node] (unk when node < 0 or trie_word[node] < 0) closes: (lp, s') the lookup (wstate, w),
+ * lm' = lm + lp, nw' = nw + 1, wstate' = s', node' = the root; with lexicon_only a `space` at a node that ends no word is
+ * no candidate.  A candidate ranks by (tot + alpha lm) + beta nw, the four operations rounded on their own.  A final closes
+ * its pending word the same way (with lexicon_only an entry whose pending node ends no word is no final), with eos_term the
+ * lookup of eos from the resulting state joins lm, and the final ranks by those values; the earlier final first on ties.
+ * With alpha = beta = 0, eos_term and lexicon_only off, hyp, hyp_len and rnnt_score are the plain search's bits; lm_score of
+ * a hypothesis is asr_word_lm_score_f32 of its tokens with the same eos_term.
+ *   asr_transducer_wbeam_ws_bytes       the EXTRA workspace in bytes, plain integers, no GPU: 4 * 7 * round64(B K) - node,
+ *                                 wstate and nw of two generations of the beam and the finals' nw (round64: up to a
+ *                                 multiple of 64).  B <= 0: ASR_E_ARG; K outside 1 .. ASR_BEAM_KMAX: ASR_E_SHAPE
+ *   asr_transducer_wbeam_init_f32       asr_transducer_beam_init_f32, and the root, lm->start and 0 words for the empty sequence
+ *   asr_transducer_wbeam_step_f32       asr_transducer_beam_step_f32 with the semantics above: one thread per live entry looks up
+ *                                 the entry's close pair (and a final's end term), the candidate walk reads them
+ *   asr_transducer_wbeam_backtrace_f32  asr_transducer_beam_backtrace_f32 and n_words int32 [B][K] (-1: unused).  An utterance
+ *                                 without a frame gives the empty hypothesis at tot 0, lm 0 (the lookup of eos from
+ *                                 lm->start with eos_term) and 0 words
+ * Each takes the call `a`, the LM, alpha, beta (finite, else ASR_E_ARG), eos_term, lexicon_only and the extra workspace wws
+ * (4-byte aligned, at least asr_transducer_wbeam_ws_bytes; else ASR_E_ARG); lm->V != a->V: ASR_E_SHAPE.  An iteration stays
+ * four launches, a search 4 (T + L) + 2.  What is read back from the workspace to index the LM's tables is clamped to them;
+ * no floating-point atomics, no host synchronisation, no allocation; a slot that is not live is never read.
+ * ------------------------------------------------------------------------------------- */
+int asr_transducer_wbeam_ws_bytes(int B, int K, int64_t* ws_bytes);
+int asr_transducer_wbeam_init_f32(const asr_transducer_beam_t* a, const asr_word_lm_t* lm, float alpha, float beta, int eos_term,
+                                  int lexicon_only, void* wws, int64_t wws_bytes, int bos, asr_stream_t stream);
+int asr_transducer_wbeam_step_f32(const asr_transducer_beam_t* a, const asr_word_lm_t* lm, float alpha, float beta, int eos_term,
+                                  int lexicon_only, void* wws, int64_t wws_bytes, int it, asr_stream_t stream);
+int asr_transducer_wbeam_backtrace_f32(const asr_transducer_beam_t* a, const asr_word_lm_t* lm, float alpha, float beta,
+                                       int eos_term, int lexicon_only, void* wws, int64_t wws_bytes, int32_t* hyp,
+                                       int32_t* hyp_len, float* score, float* rnnt_score, float* lm_score, int32_t* n_words,
+                                       asr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

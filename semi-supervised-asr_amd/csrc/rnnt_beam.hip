@@ -28,7 +28,16 @@
 //   rnnt_beam_backtrace_kernel  one thread per final: the history walked back into hyp
 // Frames t >= T_b, slots that are not live and workspace words that this call has not written are never read.
 // LDS of the step kernel: K (J + V) floats (dynamic) and under 2 KB of per-entry arrays: K (J + V) * 4 <= kBeamLds.
+// With a word LM and its lexicon inside the search (the kernels' WLM instantiations, the asr_transducer_wbeam_*
+// entries) an entry additionally carries its trie node, its word state, lm - the sum over its COMPLETED words - and their
+// count nw: functions of the token sequence, so the merge and prefix identity are untouched.  One thread per live entry
+// does the entry's lookups (csrc/word_lm.h: the pending word's close pair, which is what a `space` candidate and a final
+// both need, and a final's end-of-sentence term) into LDS; the candidate walk reads them, and with lexicon_only one
+// trie_next word per (entry, token).  The instantiations without it hold none of this.
+#include <float.h>
+#include <type_traits>
 #include "seq_common.h"
+#include "word_lm.h"
 
 namespace {
 
@@ -86,6 +95,21 @@ BeamWs beam_ws(void* base, int B, int T, int K, int L, int P) {
   return w;
 }
 
+// the word LM of a fused search and the entries' word state: the EXTRA workspace of the asr_transducer_wbeam_* entries
+struct BeamWlm {
+  wlm::WordLm w;
+  int N, S;                // trie nodes, word states: what is read back from the workspace is clamped to them
+  float alpha, beta;
+  int eos_term, lexicon_only;
+  int32_t* node;           // [2][B K]   the trie node of the entry's pending word (0: the root, -1: off the trie)
+  int32_t* wst;            // [2][B K]   its word-LM state
+  int32_t* nw;             // [2][B K]   its completed words
+  int32_t* fin_nw;         // [B K]      the finals' words
+};
+struct NoWlm {};
+
+int64_t wbeam_ws_bytes(int B, int K) { return 4 * 7 * round64((int64_t)B * K); }
+
 int beam_shape_check(int B, int T, int J, int V, int K, int L, int E, int P) {
   if (B <= 0 || T <= 0 || J <= 0 || V <= 0 || L <= 0 || E <= 0 || P <= 0) return ASR_E_ARG;
   if (K < 1 || K > kKmax || V < 2 || (J & 3) || (int64_t)K * ((int64_t)J + V) * 4 > kBeamLds) return ASR_E_SHAPE;
@@ -116,7 +140,9 @@ __device__ __forceinline__ float lm_rank(float tot, float lm, int u, float alpha
   return __fadd_rn(__fadd_rn(tot, __fmul_rn(alpha, lm)), __fmul_rn(beta, (float)u));
 }
 
-__global__ __launch_bounds__(kThreads) void rnnt_beam_init_kernel(asr_transducer_beam_t a, int bos, BeamWs w) {
+template <bool WLM>
+__global__ __launch_bounds__(kThreads) void rnnt_beam_init_kernel(asr_transducer_beam_t a, int bos, BeamWs w,
+                                                                  std::conditional_t<WLM, BeamWlm, NoWlm> g) {
   const int b = blockIdx.x, tid = threadIdx.x, K = a.K, EP = a.E + a.P;
   const int live = clamp_len(a.frame_lens[b], a.T) > 0 ? 1 : 0;
   if (tid == 0) {
@@ -130,6 +156,11 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_init_kernel(asr_transducer
       w.u[s] = 0;
       w.last[s] = -1;
       w.hash[s] = 0;
+      if constexpr (WLM) {
+        g.node[s] = 0;
+        g.wst[s] = g.w.start;
+        g.nw[s] = 0;
+      }
     }
   }
   if (tid < K) w.advance[(int64_t)b * K + tid] = (tid == 0 && live) ? 1 : 0;
@@ -139,12 +170,18 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_init_kernel(asr_transducer
   for (int i = tid; i < K * a.P; i += kThreads) cg[i] = 0.f;
 }
 
-__global__ __launch_bounds__(kThreads) void rnnt_beam_step_kernel(asr_transducer_beam_t a, int it, BeamWs w) {
+template <bool WLM>
+__global__ __launch_bounds__(kThreads) void rnnt_beam_step_kernel(asr_transducer_beam_t a, int it, BeamWs w,
+                                                                  std::conditional_t<WLM, BeamWlm, NoWlm> g) {
   extern __shared__ float sm[];
   __shared__ float s_tot[kKmax], s_lm[kKmax], s_lse[kKmax], s_btot[kKmax];
   __shared__ int s_u[kKmax], s_last[kKmax], s_state[kKmax], s_fin[kKmax], s_par[kKmax], s_tok[kKmax];
   __shared__ u64 s_hash[kKmax];
   __shared__ unsigned s_mk[kKmax];                           // entry h': the entries that are seq(h') + one label
+  // (word LM only: unused arrays take no LDS) the entry's node, word state and words; the close pair of its pending word
+  // (next < 0: lexicon_only and the node ends no word); lm, words and admission of the entry as a final
+  __shared__ int s_node[kKmax], s_wst[kKmax], s_nw[kKmax], s_snx[kKmax], s_fnw[kKmax], s_fok[kKmax];
+  __shared__ float s_slp[kKmax], s_flm[kKmax];
   __shared__ float red_v[2][kThreads / 64];
   __shared__ int red_i[2][kThreads / 64];
   const int B = a.B, T = a.T, J = a.J, V = a.V, K = a.K, L = a.L, E = a.E, P = a.P, EP = a.E + a.P;
@@ -155,7 +192,7 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_step_kernel(asr_transducer
   const int len = clamp_len(a.frame_lens[b], T);
   int nlive = w.nlive[(int64_t)(it & 1) * B + b];
   nlive = nlive < 0 ? 0 : (nlive > K ? K : nlive);
-  const bool lmode = a.lm_logp != nullptr;
+  const bool lmode = !WLM && a.lm_logp != nullptr;
   float* xh = a.xh + (int64_t)b * K * EP;
   float* cg = w.cg + (int64_t)b * K * P;
   if (nlive == 0) {                                          // every hypothesis of the row has finalised (or it has no frame)
@@ -172,6 +209,12 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_step_kernel(asr_transducer
     s_last[tid] = w.last[src + tid];
     s_state[tid] = w.state[src + tid];
     s_hash[tid] = w.hash[src + tid];
+    if constexpr (WLM) {                                     // (what indexes the tables is clamped)
+      const int nd = g.node[src + tid], st = g.wst[src + tid];
+      s_node[tid] = nd < 0 ? -1 : (nd >= g.N ? g.N - 1 : nd);
+      s_wst[tid] = st < 0 ? 0 : (st >= g.S ? g.S - 1 : st);
+      s_nw[tid] = g.nw[src + tid];
+    }
   }
   __syncthreads();
   // Z = tanh(PE[b][t_h] + PP[h]); t_h = it - u_h lies in [0, T_b) for a live entry (clamped for the address all the same)
@@ -215,6 +258,34 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_step_kernel(asr_transducer
     s_btot[tid] = bt;
     s_fin[tid] = fin;
     s_mk[tid] = mk;
+    if constexpr (WLM) {
+      // the close pair of the pending word: what a `space` candidate of this entry, and this entry as a final, add
+      const int nd = s_node[tid], st = s_wst[tid];
+      float lp = 0.f;
+      int nx = st;
+      if (nd != 0) wlm::close_word(g.w, nd, st, g.lexicon_only != 0, lp, nx);
+      s_slp[tid] = lp;
+      s_snx[tid] = nx;
+      if (fin) {
+        float fl = s_lm[tid];
+        int fn = s_nw[tid], fs = st;
+        const int ok = (nd != 0 && nx < 0) ? 0 : 1;
+        if (ok && nd != 0) {
+          fl = __fadd_rn(fl, lp);
+          ++fn;
+          fs = nx;
+        }
+        if (ok && g.eos_term) {
+          float el;
+          int en;
+          wlm::lookup(g.w, fs, g.w.eos, el, en);
+          fl = __fadd_rn(fl, el);
+        }
+        s_flm[tid] = fl;
+        s_fnw[tid] = fn;
+        s_fok[tid] = ok;
+      }
+    }
   }
   __syncthreads();
   // the candidates, entry-major: a thread meets its flat indices h V + k in ascending order
@@ -231,15 +302,30 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_step_kernel(asr_transducer
       int uv = uh;
       if (k == 0) {
         val = s_fin[h] ? -INFINITY : s_btot[h];
+        if constexpr (WLM) uv = s_nw[h];
       } else {
         if (uh >= L) continue;
+        if constexpr (WLM) {                                 // (uv: the candidate's completed words)
+          const int nd = s_node[h];
+          uv = s_nw[h];
+          if (k == g.w.space) {
+            if (nd != 0) {
+              if (s_snx[h] < 0) continue;
+              lmv = __fadd_rn(lmh, s_slp[h]);
+              ++uv;
+            }
+          } else if (g.lexicon_only && wlm::trie_step(g.w, nd, k) < 0) {
+            continue;
+          }
+        }
         val = toth + (lg[h * V + k] - lseh);
         for (unsigned m = mkh; m; m &= m - 1)                // seq(h) . k is in the beam: it joins that entry's blank
           if (s_last[__ffs(m) - 1] == k) val = -INFINITY;
         if (lmode) lmv = lmh + lrow[k];
-        uv = uh + 1;
+        if constexpr (!WLM) uv = uh + 1;
       }
-      top_insert(lv, li, lmode ? lm_rank(val, lmv, uv, a.lm_alpha, a.lm_beta) : val, h * V + k);
+      if constexpr (WLM) top_insert(lv, li, lm_rank(val, lmv, uv, g.alpha, g.beta), h * V + k);
+      else top_insert(lv, li, lmode ? lm_rank(val, lmv, uv, a.lm_alpha, a.lm_beta) : val, h * V + k);
     }
   }
   int nsel = 0, my_i = INT_MAX;
@@ -274,6 +360,24 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_step_kernel(asr_transducer
         w.hash[d] = prefix_hash(s_hash[h], k);
         adv = 1;
       }
+      if constexpr (WLM) {
+        int nd = s_node[h], st = s_wst[h], n = s_nw[h];
+        float l = s_lm[h];
+        if (k == g.w.space) {
+          if (nd != 0) {
+            l = __fadd_rn(l, s_slp[h]);
+            st = s_snx[h];
+            ++n;
+            nd = 0;
+          }
+        } else if (k != 0) {
+          nd = wlm::trie_step(g.w, nd, k);
+        }
+        w.lm[d] = l;
+        g.node[d] = nd;
+        g.wst[d] = st;
+        g.nw[d] = n;
+      }
       w.hist[((int64_t)it * B + b) * K + tid] = make_int2(k, h);
       s_par[tid] = h;
       s_tok[tid] = k;
@@ -289,9 +393,15 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_step_kernel(asr_transducer
     for (int h = 0; h < nlive; ++h) {
       if (!s_fin[h]) continue;
       const float ft = s_btot[h];
-      float fl = s_lm[h];
-      if (lmode && a.lm_eos >= 0) fl = fl + a.lm_logp[(int64_t)s_state[h] * V + a.lm_eos];
-      const float fr = lmode ? lm_rank(ft, fl, s_u[h], a.lm_alpha, a.lm_beta) : ft;
+      float fl = s_lm[h], fr;
+      if constexpr (WLM) {
+        if (!s_fok[h]) continue;                             // lexicon_only: the pending node ends no word
+        fl = s_flm[h];
+        fr = lm_rank(ft, fl, s_fnw[h], g.alpha, g.beta);
+      } else {
+        if (lmode && a.lm_eos >= 0) fl = fl + a.lm_logp[(int64_t)s_state[h] * V + a.lm_eos];
+        fr = lmode ? lm_rank(ft, fl, s_u[h], a.lm_alpha, a.lm_beta) : ft;
+      }
       if (!(fr > -INFINITY)) continue;
       int p = 0;
       while (p < n && w.fin_rank[f0 + p] >= fr) ++p;
@@ -304,6 +414,7 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_step_kernel(asr_transducer
         w.fin_tot[f0 + q] = w.fin_tot[f0 + q - 1];
         w.fin_lm[f0 + q] = w.fin_lm[f0 + q - 1];
         w.fin_rank[f0 + q] = w.fin_rank[f0 + q - 1];
+        if constexpr (WLM) g.fin_nw[f0 + q] = g.fin_nw[f0 + q - 1];
       }
       w.fin_it[f0 + p] = it;
       w.fin_slot[f0 + p] = h;
@@ -311,6 +422,7 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_step_kernel(asr_transducer
       w.fin_tot[f0 + p] = ft;
       w.fin_lm[f0 + p] = fl;
       w.fin_rank[f0 + p] = fr;
+      if constexpr (WLM) g.fin_nw[f0 + p] = s_fnw[h];
       if (n < K) ++n;
     }
     w.nfin[b] = n;
@@ -351,23 +463,34 @@ __global__ __launch_bounds__(256) void rnnt_beam_cell_kernel(int64_t total, int 
   c[idx] = c2;
 }
 
+template <bool WLM>
 __global__ __launch_bounds__(64) void rnnt_beam_backtrace_kernel(asr_transducer_beam_t a, BeamWs w, int32_t* __restrict__ hyp,
                                                                  int32_t* __restrict__ hyp_len, float* __restrict__ score,
-                                                                 float* __restrict__ rnnt_score, float* __restrict__ lm_score) {
+                                                                 float* __restrict__ rnnt_score, float* __restrict__ lm_score,
+                                                                 std::conditional_t<WLM, BeamWlm, NoWlm> g,
+                                                                 int32_t* __restrict__ n_words) {
   const int b = blockIdx.x, r = threadIdx.x, B = a.B, K = a.K, L = a.L;
   if (r >= K) return;
   const int64_t o = (int64_t)b * K + r;
   int32_t* hr = hyp + o * L;
   const int len = clamp_len(a.frame_lens[b], a.T);
-  const bool lmode = a.lm_logp != nullptr;
-  int n = 0, u = -1;
+  const bool lmode = !WLM && a.lm_logp != nullptr;
+  int n = 0, u = -1, words = -1;
   float tot = -INFINITY, lm = -INFINITY, rank = -INFINITY;
   if (len == 0) {                                            // no frames: the empty hypothesis at score 0, nothing else
     if (r == 0) {
       u = 0;
       tot = 0.f;
-      lm = (lmode && a.lm_eos >= 0) ? a.lm_logp[(int64_t)a.lm_start * a.V + a.lm_eos] : 0.f;
-      rank = lmode ? lm_rank(0.f, lm, 0, a.lm_alpha, a.lm_beta) : 0.f;
+      if constexpr (WLM) {
+        int nx;
+        lm = 0.f;
+        words = 0;
+        if (g.eos_term) wlm::lookup(g.w, g.w.start, g.w.eos, lm, nx);
+        rank = lm_rank(0.f, lm, 0, g.alpha, g.beta);
+      } else {
+        lm = (lmode && a.lm_eos >= 0) ? a.lm_logp[(int64_t)a.lm_start * a.V + a.lm_eos] : 0.f;
+        rank = lmode ? lm_rank(0.f, lm, 0, a.lm_alpha, a.lm_beta) : 0.f;
+      }
     }
   } else {
     n = w.nfin[b];
@@ -378,6 +501,7 @@ __global__ __launch_bounds__(64) void rnnt_beam_backtrace_kernel(asr_transducer_
       tot = w.fin_tot[o];
       lm = w.fin_lm[o];
       rank = w.fin_rank[o];
+      if constexpr (WLM) words = g.fin_nw[o];
       int s = w.fin_slot[o] & (kKmax - 1), pos = u - 1;
       for (int j = w.fin_it[o] - 1; j >= 0 && pos >= 0; --j) {
         const int2 rec = w.hist[((int64_t)j * B + b) * K + s];
@@ -392,6 +516,7 @@ __global__ __launch_bounds__(64) void rnnt_beam_backtrace_kernel(asr_transducer_
   score[o] = rank;
   if (rnnt_score) rnnt_score[o] = tot;
   if (lm_score) lm_score[o] = lm;
+  if constexpr (WLM) n_words[o] = words;
 }
 
 int beam_args_check(const asr_transducer_beam_t* a) {
@@ -402,6 +527,27 @@ int beam_args_check(const asr_transducer_beam_t* a) {
   if (a->lm_logp && (!a->lm_next || a->lm_states <= 0)) return ASR_E_ARG;
   if (a->lm_logp && (a->lm_start < 0 || a->lm_start >= a->lm_states || a->lm_eos >= a->V)) return ASR_E_SHAPE;
   if (a->ws_bytes < beam_ws(nullptr, a->B, a->T, a->K, a->L, a->P).bytes || (((uintptr_t)a->ws) & 7u)) return ASR_E_ARG;
+  return 0;
+}
+
+// the checks of an asr_transducer_wbeam_* call, and the device's view of its LM and extra workspace
+int wbeam_args(const asr_transducer_beam_t* a, const asr_word_lm_t* lm, float alpha, float beta, int eos_term, int lexicon_only,
+               void* wws, int64_t wws_bytes, BeamWlm* g) {
+  int rc = beam_args_check(a);
+  if (rc) return rc;
+  if (a->lm_logp || !wws || !(fabsf(alpha) <= FLT_MAX) || !(fabsf(beta) <= FLT_MAX)) return ASR_E_ARG;
+  rc = wlm::check_abi(lm);
+  if (rc) return rc;
+  if (lm->V != a->V) return ASR_E_SHAPE;
+  if (wws_bytes < wbeam_ws_bytes(a->B, a->K) || (((uintptr_t)wws) & 3u)) return ASR_E_ARG;
+  const int64_t n_bk = round64((int64_t)a->B * a->K);
+  g->w = wlm::from_abi(*lm);
+  g->N = lm->N, g->S = lm->S;
+  g->alpha = alpha, g->beta = beta, g->eos_term = eos_term != 0, g->lexicon_only = lexicon_only != 0;
+  g->node = (int32_t*)wws;
+  g->wst = g->node + 2 * n_bk;
+  g->nw = g->wst + 2 * n_bk;
+  g->fin_nw = g->nw + 2 * n_bk;
   return 0;
 }
 
@@ -419,8 +565,8 @@ extern "C" int asr_transducer_beam_init_f32(const asr_transducer_beam_t* a, int 
   const int rc = beam_args_check(a);
   if (rc) return rc;
   if (bos < 0 || bos >= a->V) return ASR_E_ARG;
-  hipLaunchKernelGGL(rnnt_beam_init_kernel, dim3(a->B), dim3(kThreads), 0, (hipStream_t)stream, *a, bos,
-                     beam_ws(a->ws, a->B, a->T, a->K, a->L, a->P));
+  hipLaunchKernelGGL(rnnt_beam_init_kernel<false>, dim3(a->B), dim3(kThreads), 0, (hipStream_t)stream, *a, bos,
+                     beam_ws(a->ws, a->B, a->T, a->K, a->L, a->P), NoWlm());
   ASR_CHECK_LAUNCH();
   return 0;
 }
@@ -429,8 +575,8 @@ extern "C" int asr_transducer_beam_step_f32(const asr_transducer_beam_t* a, int 
   const int rc = beam_args_check(a);
   if (rc) return rc;
   if (it < 0 || it >= a->T + a->L) return ASR_E_ARG;
-  hipLaunchKernelGGL(rnnt_beam_step_kernel, dim3(a->B), dim3(kThreads), (size_t)a->K * ((size_t)a->J + a->V) * 4,
-                     (hipStream_t)stream, *a, it, beam_ws(a->ws, a->B, a->T, a->K, a->L, a->P));
+  hipLaunchKernelGGL(rnnt_beam_step_kernel<false>, dim3(a->B), dim3(kThreads), (size_t)a->K * ((size_t)a->J + a->V) * 4,
+                     (hipStream_t)stream, *a, it, beam_ws(a->ws, a->B, a->T, a->K, a->L, a->P), NoWlm());
   ASR_CHECK_LAUNCH();
   return 0;
 }
@@ -452,8 +598,56 @@ extern "C" int asr_transducer_beam_backtrace_f32(const asr_transducer_beam_t* a,
   const int rc = beam_args_check(a);
   if (rc) return rc;
   if (!hyp || !hyp_len || !score) return ASR_E_ARG;
-  hipLaunchKernelGGL(rnnt_beam_backtrace_kernel, dim3(a->B), dim3(64), 0, (hipStream_t)stream, *a,
-                     beam_ws(a->ws, a->B, a->T, a->K, a->L, a->P), hyp, hyp_len, score, rnnt_score, lm_score);
+  hipLaunchKernelGGL(rnnt_beam_backtrace_kernel<false>, dim3(a->B), dim3(64), 0, (hipStream_t)stream, *a,
+                     beam_ws(a->ws, a->B, a->T, a->K, a->L, a->P), hyp, hyp_len, score, rnnt_score, lm_score, NoWlm(),
+                     (int32_t*)nullptr);
+  ASR_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int asr_transducer_wbeam_ws_bytes(int B, int K, int64_t* ws_bytes) {
+  if (!ws_bytes || B <= 0) return ASR_E_ARG;
+  if (K < 1 || K > kKmax) return ASR_E_SHAPE;
+  *ws_bytes = wbeam_ws_bytes(B, K);
+  return 0;
+}
+
+extern "C" int asr_transducer_wbeam_init_f32(const asr_transducer_beam_t* a, const asr_word_lm_t* lm, float alpha, float beta,
+                                             int eos_term, int lexicon_only, void* wws, int64_t wws_bytes, int bos,
+                                             asr_stream_t stream) {
+  BeamWlm g;
+  const int rc = wbeam_args(a, lm, alpha, beta, eos_term, lexicon_only, wws, wws_bytes, &g);
+  if (rc) return rc;
+  if (bos < 0 || bos >= a->V) return ASR_E_ARG;
+  hipLaunchKernelGGL(rnnt_beam_init_kernel<true>, dim3(a->B), dim3(kThreads), 0, (hipStream_t)stream, *a, bos,
+                     beam_ws(a->ws, a->B, a->T, a->K, a->L, a->P), g);
+  ASR_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int asr_transducer_wbeam_step_f32(const asr_transducer_beam_t* a, const asr_word_lm_t* lm, float alpha, float beta,
+                                             int eos_term, int lexicon_only, void* wws, int64_t wws_bytes, int it,
+                                             asr_stream_t stream) {
+  BeamWlm g;
+  const int rc = wbeam_args(a, lm, alpha, beta, eos_term, lexicon_only, wws, wws_bytes, &g);
+  if (rc) return rc;
+  if (it < 0 || it >= a->T + a->L) return ASR_E_ARG;
+  hipLaunchKernelGGL(rnnt_beam_step_kernel<true>, dim3(a->B), dim3(kThreads), (size_t)a->K * ((size_t)a->J + a->V) * 4,
+                     (hipStream_t)stream, *a, it, beam_ws(a->ws, a->B, a->T, a->K, a->L, a->P), g);
+  ASR_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int asr_transducer_wbeam_backtrace_f32(const asr_transducer_beam_t* a, const asr_word_lm_t* lm, float alpha, float beta,
+                                                  int eos_term, int lexicon_only, void* wws, int64_t wws_bytes, int32_t* hyp,
+                                                  int32_t* hyp_len, float* score, float* rnnt_score, float* lm_score,
+                                                  int32_t* n_words, asr_stream_t stream) {
+  BeamWlm g;
+  const int rc = wbeam_args(a, lm, alpha, beta, eos_term, lexicon_only, wws, wws_bytes, &g);
+  if (rc) return rc;
+  if (!hyp || !hyp_len || !score || !n_words) return ASR_E_ARG;
+  hipLaunchKernelGGL(rnnt_beam_backtrace_kernel<true>, dim3(a->B), dim3(64), 0, (hipStream_t)stream, *a,
+                     beam_ws(a->ws, a->B, a->T, a->K, a->L, a->P), hyp, hyp_len, score, rnnt_score, lm_score, g, n_words);
   ASR_CHECK_LAUNCH();
   return 0;
 }

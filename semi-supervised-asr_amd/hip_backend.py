@@ -42,6 +42,8 @@ EXPORTS = (
     "asr_transducer_align_ws_bytes", "asr_transducer_align_f32",
     "asr_transducer_beam_ws_bytes", "asr_transducer_beam_init_f32", "asr_transducer_beam_step_f32", "asr_transducer_beam_cell_f32",
     "asr_transducer_beam_backtrace_f32",
+    "asr_transducer_wbeam_ws_bytes", "asr_transducer_wbeam_init_f32", "asr_transducer_wbeam_step_f32",
+    "asr_transducer_wbeam_backtrace_f32",
 )
 
 _lib = None
@@ -331,6 +333,11 @@ def load():
     lib.asr_transducer_beam_step_f32.argtypes = [ctypes.POINTER(RnntBeamArgs), c_i, c_p]
     lib.asr_transducer_beam_cell_f32.argtypes = [ctypes.POINTER(RnntBeamArgs), c_p, c_p, c_p, c_p]
     lib.asr_transducer_beam_backtrace_f32.argtypes = [ctypes.POINTER(RnntBeamArgs), c_p, c_p, c_p, c_p, c_p, c_p]
+    wbeam = [ctypes.POINTER(RnntBeamArgs), ctypes.POINTER(WordLmTable), c_f, c_f, c_i, c_i, c_p, c_i64]
+    lib.asr_transducer_wbeam_ws_bytes.argtypes = [c_i, c_i, ctypes.POINTER(c_i64)]
+    lib.asr_transducer_wbeam_init_f32.argtypes = wbeam + [c_i, c_p]
+    lib.asr_transducer_wbeam_step_f32.argtypes = wbeam + [c_i, c_p]
+    lib.asr_transducer_wbeam_backtrace_f32.argtypes = wbeam + [c_p] * 7
     lib.asr_mwer_fwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
     lib.asr_mwer_bwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_f, c_p, c_i64, c_p]
     lib.asr_dec_feedback_fwd.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_p, c_i64,
@@ -1177,6 +1184,8 @@ class RnntBeam(object):
     the n-gram LM on the device or None.  init(), then per iteration step(it) - between them the caller runs the gate
     product, cell() and the projection - and backtrace() behind the loop.  Every method is one launch."""
 
+    COUNT = "rnnt_beam"                  # LAUNCHES[COUNT + "_launch"] counts every launch of a search
+
     def __init__(self, pe, w_out, b_out, emb, frame_lens, K, L, h, c, xh, pp, ws, table=None, alpha=0.0, beta=0.0,
                  eos_term=True):
         B, T, J = pe.shape
@@ -1208,7 +1217,7 @@ class RnntBeam(object):
         if rc == ASR_E_SHAPE:
             raise UnsupportedShape("%s: refused the sizes or the n-gram table" % what)
         check(rc, what)
-        LAUNCHES["rnnt_beam_launch"] += 1
+        LAUNCHES[self.COUNT + "_launch"] += 1
 
     def init(self, bos):
         self._run(load().asr_transducer_beam_init_f32(ctypes.byref(self.args), int(bos), stream()), "asr_transducer_beam_init_f32")
@@ -1226,7 +1235,7 @@ class RnntBeam(object):
     def product(self, x, w, out, bias=None):
         """out = x w^T (+ bias) on asr_gemm_f32, unsplit: the same bits in and outside deterministic mode.  One launch."""
         gemm(x, w, trans_b=True, bias=bias, out=out, split_k=1)
-        LAUNCHES["rnnt_beam_launch"] += 1
+        LAUNCHES[self.COUNT + "_launch"] += 1
 
     def backtrace(self, hyp, hyp_len, score, rnnt_score=None, lm_score=None):
         B, K, L = self.B, self.K, self.L
@@ -1237,6 +1246,60 @@ class RnntBeam(object):
         self._run(load().asr_transducer_beam_backtrace_f32(ctypes.byref(self.args), ptr(hyp), ptr(hyp_len), ptr(score),
                                                      ptr(rnnt_score), ptr(lm_score), stream()),
                   "asr_transducer_beam_backtrace_f32")
+
+
+def rnnt_wbeam_ws_bytes(B, K):
+    """asr_transducer_wbeam_ws_bytes on plain integers (no tensors, no GPU) -> the EXTRA workspace bytes of a transducer beam
+    search with a word LM inside: 4 * 7 * round64(B K); UnsupportedShape for a beam outside 1 .. BEAM_KMAX."""
+    need = c_i64(0)
+    rc = load().asr_transducer_wbeam_ws_bytes(int(B), int(K), ctypes.byref(need))
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("rnnt_wbeam: B %d, beam %d (beam 1 .. %d)" % (B, K, BEAM_KMAX))
+    check(rc, "asr_transducer_wbeam_ws_bytes")
+    return need.value
+
+
+class RnntWordBeam(RnntBeam):
+    """RnntBeam with a lexicon and a word-level LM inside the search (the asr_transducer_wbeam_* entries): table
+    is the word LM on the device (word_lm.WordTable after .to(device)), wws the extra workspace (float32 or int32, at least
+    rnnt_wbeam_ws_bytes bytes); candidates rank by (tot + alpha lm) + beta n_words.  cell() and product() are RnntBeam's;
+    init(), step() and backtrace() are one launch each, counted under LAUNCHES["rnnt_wbeam_launch"]."""
+
+    COUNT = "rnnt_wbeam"
+
+    def __init__(self, pe, w_out, b_out, emb, frame_lens, K, L, h, c, xh, pp, ws, table, wws, alpha=0.0, beta=0.0,
+                 eos_term=True, lexicon_only=False):
+        RnntBeam.__init__(self, pe, w_out, b_out, emb, frame_lens, K, L, h, c, xh, pp, ws)
+        V = w_out.shape[0]
+        if table.V != V:
+            raise UnsupportedShape("rnnt_wbeam: the word LM spells in %d tokens, the head is over %d" % (table.V, V))
+        self.lm = _word_lm_table(table, "rnnt_wbeam")
+        need = rnnt_wbeam_ws_bytes(self.B, self.K)
+        if not (wws.is_cuda and wws.is_contiguous() and wws.element_size() == 4 and wws.numel() * 4 >= need):
+            raise RuntimeError("rnnt_wbeam: an extra workspace of %d bytes on the GPU" % need)
+        self._wargs = (ctypes.byref(self.lm), float(alpha), float(beta), 1 if eos_term else 0, 1 if lexicon_only else 0,
+                       ptr(wws), wws.numel() * 4)
+        self._keep += (table, wws)
+
+    def init(self, bos):
+        self._run(load().asr_transducer_wbeam_init_f32(ctypes.byref(self.args), *self._wargs, int(bos), stream()),
+                  "asr_transducer_wbeam_init_f32")
+
+    def step(self, it):
+        self._run(load().asr_transducer_wbeam_step_f32(ctypes.byref(self.args), *self._wargs, int(it), stream()),
+                  "asr_transducer_wbeam_step_f32")
+        LAUNCHES["rnnt_wbeam_step"] += 1
+
+    def backtrace(self, hyp, hyp_len, score, rnnt_score, lm_score, n_words):
+        B, K, L = self.B, self.K, self.L
+        outs = [hyp_len, score, rnnt_score, lm_score, n_words]
+        if tuple(hyp.shape) != (B, K, L) or hyp.dtype != torch.int32 or not hyp.is_contiguous() or \
+                n_words.dtype != torch.int32 or any(t.numel() != B * K or not t.is_contiguous() for t in outs):
+            raise RuntimeError("rnnt_wbeam: hyp int32 [B, K, L], hyp_len / score / rnnt_score / lm_score / n_words [B, K], "
+                               "contiguous")
+        self._run(load().asr_transducer_wbeam_backtrace_f32(ctypes.byref(self.args), *self._wargs, ptr(hyp), ptr(hyp_len),
+                                                            ptr(score), ptr(rnnt_score), ptr(lm_score), ptr(n_words), stream()),
+                  "asr_transducer_wbeam_backtrace_f32")
 
 
 def _mwer_dims(logits, tokens, B):

@@ -732,17 +732,20 @@ class TransducerHead(torch.nn.Module):
             pp = hb.gemm(h.contiguous(), self.lin_pred.weight, trans_b=True)
         return out, n_out, score
 
-    def beam(self, enc_h, frame_lens_dev, beam, max_len, ngram=None, ngram_weight=0.0, ngram_bonus=0.0, eos_term=True):
+    def beam(self, enc_h, frame_lens_dev, beam, max_len, ngram=None, ngram_weight=0.0, ngram_bonus=0.0, eos_term=True, *,
+             word_lm=None, word_lm_weight=0.0, word_bonus=0.0, lexicon_only=False):
         """Beam search over the head on enc_h [B, T', H]: lin_enc once, the prediction cell's weights
         concatenated once ([w_ih | w_hh], b_ih + b_hh), then ops.rnnt_beam - a fixed T' + max_len iterations, no host read.
         -> (hyp int32 [B, beam, max_len] padded with -1, hyp_len int32 [B, beam], score fp32 [B, beam] descending) and, with
-        ngram, (rnnt_score, lm_score) behind them: the conventions of ops.ctc_beam."""
+        ngram, (rnnt_score, lm_score) behind them: the conventions of ops.ctc_beam.  With word_lm (a word_lm.WordLM; DESIGN
+        4.30) the lexicon and the word LM sit inside the search: (rnnt_score, lm_score, n_words) behind the three."""
         w_ih, w_hh, b_ih, b_hh = self.lstm.direction_params(0)
         w_gate = torch.cat([w_ih.detach(), w_hh.detach()], dim=1).contiguous()
         b_gate = (b_ih.detach() + b_hh.detach()).contiguous()
         return ops.rnnt_beam(self.project_enc(enc_h), frame_lens_dev, w_gate, b_gate, self.lin_pred.weight, self.lin_out.weight,
                              self.lin_out.bias, self.embedding.weight, self.bos, beam, max_len, ngram=ngram,
-                             ngram_weight=ngram_weight, ngram_bonus=ngram_bonus, eos_term=eos_term)
+                             ngram_weight=ngram_weight, ngram_bonus=ngram_bonus, eos_term=eos_term, word_lm=word_lm,
+                             word_lm_weight=word_lm_weight, word_bonus=word_bonus, lexicon_only=lexicon_only)
 
 
 class E2E(torch.nn.Module):
@@ -837,13 +840,15 @@ class E2E(torch.nn.Module):
         return [row[1:1 + row[0]] for row in host]
 
     def recognize_rnnt_beams(self, xs, ilens, beam_size, max_dec_timesteps=200, ngram=None, ngram_weight=0.0, ngram_bonus=0.0,
-                             eos_term=True):
+                             eos_term=True, *, word_lm=None, word_lm_weight=0.0, word_bonus=0.0, lexicon_only=False):
         """Beam search with the transducer head alone (not a reference method): the encoder once, then
         TransducerHead.beam with `beam_size` entries and at most max_dec_timesteps labels; ngram (an ngram.NgramLM) sits inside
         the search by shallow fusion.  -> the id list of the best hypothesis per utterance; self.last_rnnt_beams keeps the
         device n-best of the call: dict(tokens int32 [B, beam, max_dec_timesteps] padded with -1, lengths int32 [B, beam] with
-        -1 in unused slots, scores fp32 [B, beam] descending, parts: dict(rnnt, lm) with ngram, else empty).  One host read,
-        behind the loop."""
+        -1 in unused slots, scores fp32 [B, beam] descending, parts: dict(rnnt, lm) with ngram, else empty).  With word_lm (a
+        word_lm.WordLM) the lexicon and the word-level LM sit inside the search instead, weighed by word_lm_weight
+        and word_bonus (per completed word), lexicon_only keeping only sequences of lexicon words: parts is dict(rnnt, lm) and
+        n_words int32 [B, beam] joins the record.  One host read, behind the loop."""
         if not hasattr(self, "rnnt"):
             raise ValueError("recognize_rnnt_beams needs the transducer head: build the model with rnnt_weight > 0")
         if int(max_dec_timesteps) < 1:
@@ -853,11 +858,14 @@ class E2E(torch.nn.Module):
         with torch.no_grad():
             enc_h, _ = self.encoder(xs, ilens)
             out = self.rnnt.beam(enc_h, self.encoder.enc2.last_lens_dev, int(beam_size), int(max_dec_timesteps), ngram=ngram,
-                                 ngram_weight=ngram_weight, ngram_bonus=ngram_bonus, eos_term=eos_term)
+                                 ngram_weight=ngram_weight, ngram_bonus=ngram_bonus, eos_term=eos_term, word_lm=word_lm,
+                                 word_lm_weight=word_lm_weight, word_bonus=word_bonus, lexicon_only=lexicon_only)
             hyp, hyp_len, score = out[:3]
             host = torch.cat([hyp_len[:, :1], hyp[:, 0]], dim=1).cpu().tolist()
-        parts = dict(rnnt=out[3], lm=out[4]) if ngram is not None else {}
+        parts = dict(rnnt=out[3], lm=out[4]) if (ngram is not None or word_lm is not None) else {}
         self.last_rnnt_beams = dict(tokens=hyp, lengths=hyp_len, scores=score, parts=parts)
+        if word_lm is not None:
+            self.last_rnnt_beams["n_words"] = out[5]
         return [row[1:1 + max(row[0], 0)] for row in host]
 
     def ctc_nll(self, enc_h, ys):

@@ -1291,7 +1291,7 @@ def ctc_beam(logits, frame_lens_dev, beam, ngram=None, ngram_weight=0.0, ngram_b
 
 
 def rnnt_beam(pe, frame_lens_dev, w_gate, b_gate, w_pred, w_out, b_out, emb, bos, beam, max_len, ngram=None, ngram_weight=0.0,
-              ngram_bonus=0.0, eos_term=True):
+              ngram_bonus=0.0, eos_term=True, *, word_lm=None, word_lm_weight=0.0, word_bonus=0.0, lexicon_only=False):
     """Beam search over the transducer head (csrc/rnnt_beam.hip): pe [B, T', J] the projected encoder output,
     w_gate [4 P, E + P] = [w_ih | w_hh] and b_gate = b_ih + b_hh of the prediction cell, w_pred [J, P], w_out [V, J], b_out
     [V], emb [V, E] -> (hyp int32 [B, beam, max_len] padded with -1, hyp_len int32 [B, beam] with -1 in unused slots, score
@@ -1301,7 +1301,14 @@ def rnnt_beam(pe, frame_lens_dev, w_gate, b_gate, w_pred, w_out, b_out, emb, bos
     four launches (the step kernel, the gate product, the cell kernel, the projection; the last iteration is the step
     kernel alone), four launches before the loop and the backtrace behind it: 4 (T' + max_len) + 2 in all.  The state and
     the workspace are ONE buffer leased from the pool for the call; nothing in it is read before the call has written it.
+    With word_lm (a word_lm.WordLM, or its table on the device) the lexicon and the word-level LM sit inside the search (the
+    asr_transducer_wbeam_* entries; the same launches, the extra workspace in the same lease): candidates rank by
+    (tot + word_lm_weight lm) + word_bonus n_words with lm the sum over the completed words, a final closes its pending word,
+    lexicon_only keeps only sequences of lexicon words -> (hyp, hyp_len, score, rnnt_score, lm_score, n_words int32
+    [B, beam] with -1 in unused slots).  ngram and word_lm together: ValueError.
     Forward only, no host synchronisation."""
+    if ngram is not None and word_lm is not None:
+        raise ValueError("rnnt_beam: ngram and word_lm are two LMs for one search: pass one of them")
     pe = pe.detach().contiguous()
     B, T, J = pe.shape
     K, L, dev = int(beam), int(max_len), pe.device
@@ -1311,6 +1318,8 @@ def rnnt_beam(pe, frame_lens_dev, w_gate, b_gate, w_pred, w_out, b_out, emb, bos
     r64 = lambda n: (n + 63) // 64 * 64                              # noqa: E731
     sizes = [r64((hb.rnnt_beam_ws_bytes(B, T, J, V, K, L, E, P) + 3) // 4)] + \
         [r64(B * K * n) for n in (P, P, E + P, 4 * P, J)]
+    if word_lm is not None:
+        sizes.append(r64((hb.rnnt_wbeam_ws_bytes(B, K) + 3) // 4))
     cap = _row_capacity(sum(sizes))
     lease = _POOL.acquire(("rnnt_beam", str(dev), cap), lambda: torch.empty(cap, device=dev, dtype=torch.float32))
     try:
@@ -1319,11 +1328,15 @@ def rnnt_beam(pe, frame_lens_dev, w_gate, b_gate, w_pred, w_out, b_out, emb, bos
             cuts.append(lease.ws[at:at + n])
             at += n
         ws = cuts[0]
-        h, c, xh, gates, pp = (t[:B * K * n].view(B * K, n) for t, n in zip(cuts[1:], (P, P, E + P, 4 * P, J)))
+        h, c, xh, gates, pp = (t[:B * K * n].view(B * K, n) for t, n in zip(cuts[1:6], (P, P, E + P, 4 * P, J)))
         table = None if ngram is None else _ngram_table(ngram, dev)
-        run = hb.RnntBeam(pe, w_out.detach().contiguous(), None if b_out is None else b_out.detach().contiguous(),
-                          emb.detach().contiguous(), frame_lens_dev, K, L, h, c, xh, pp, ws, table, float(ngram_weight),
-                          float(ngram_bonus), bool(eos_term))
+        head = (pe, w_out.detach().contiguous(), None if b_out is None else b_out.detach().contiguous(),
+                emb.detach().contiguous(), frame_lens_dev, K, L, h, c, xh, pp, ws)
+        if word_lm is not None:
+            run = hb.RnntWordBeam(*head, word_lm.to(dev), cuts[6], float(word_lm_weight), float(word_bonus), bool(eos_term),
+                                  bool(lexicon_only))
+        else:
+            run = hb.RnntBeam(*head, table, float(ngram_weight), float(ngram_bonus), bool(eos_term))
         w_gate, b_gate, w_pred = w_gate.detach(), b_gate.detach(), w_pred.detach()
         n_it = T + L
         run.init(bos)
@@ -1338,6 +1351,10 @@ def rnnt_beam(pe, frame_lens_dev, w_gate, b_gate, w_pred, w_out, b_out, emb, bos
         hyp = torch.empty(B, K, L, device=dev, dtype=torch.int32)
         hyp_len = torch.empty(B, K, device=dev, dtype=torch.int32)
         score = torch.empty(B, K, device=dev, dtype=torch.float32)
+        if word_lm is not None:
+            rnnt_score, lm_score, n_words = torch.empty_like(score), torch.empty_like(score), torch.empty_like(hyp_len)
+            run.backtrace(hyp, hyp_len, score, rnnt_score, lm_score, n_words)
+            return hyp, hyp_len, score, rnnt_score, lm_score, n_words
         if table is None:
             run.backtrace(hyp, hyp_len, score)
             return hyp, hyp_len, score

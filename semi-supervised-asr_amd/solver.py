@@ -380,8 +380,15 @@ class Solver(object):
         """`rnnt_beam_decode` (not a reference key; default false): test() decodes with the transducer head's beam
         search (E2E.recognize_rnnt_beams, beam width `beam_size`, at most `max_dec_timesteps` labels), with `ngram_lm` inside
         it when that is set (`ngram_weight`, `ngram_bonus`).  It is a decoder of its own -> the key as a bool; ValueError on a
-        model without the head or beside any other decoder's key, `word_lm` or `lm_weight`."""
+        model without the head or beside any other decoder's key, `word_lm` or `lm_weight`.
+        `rnnt_word_lm` is this search's word-level LM, a sub-dictionary in the style of `frontend`: `arpa` (the
+        path of an ARPA file over words spelled in the vocabulary's characters), `lexicon` (an optional path, one word per
+        line), `weight`, `bonus` (per completed word), `lexicon_only`.  ValueError without `rnnt_beam_decode`, beside
+        `ngram_lm`, without `arpa` or with a key that is none of these."""
+        wlm = config.get("rnnt_word_lm")
         if not bool(config.get("rnnt_beam_decode", False)):
+            if wlm is not None:
+                raise ValueError("rnnt_word_lm is the word LM of the transducer beam search: set rnnt_beam_decode")
             return False
         if not has_rnnt_head:
             raise ValueError("rnnt_beam_decode needs the transducer head: build the model with rnnt_weight > 0")
@@ -395,11 +402,20 @@ class Solver(object):
             for key in ("ngram_weight", "ngram_bonus"):
                 if key in config:
                     raise ValueError("%s is set without ngram_lm, the ARPA file it weighs" % key)
+        if wlm is not None:
+            if config.get("ngram_lm") is not None:
+                raise ValueError("rnnt_word_lm and ngram_lm are two LMs for one search: set one of them")
+            unknown = sorted(set(wlm) - set(Solver.RNNT_WORD_LM_KEYS)) if isinstance(wlm, dict) else None
+            if unknown is None or unknown or not wlm.get("arpa"):
+                raise ValueError("rnnt_word_lm is a dictionary with `arpa` and optionally %s%s"
+                                 % (", ".join(Solver.RNNT_WORD_LM_KEYS[1:]), "; got %s" % ", ".join(unknown) if unknown else ""))
         return True
 
+    RNNT_WORD_LM_KEYS = ("arpa", "lexicon", "weight", "bonus", "lexicon_only")
+
     def _rnnt_beams(self, xs, ilens, beam_size, ngram=None, nbest=False):
-        """Hypothesis ids of the transducer beam search for one batch (E2E.recognize_rnnt_beams, with the n-gram LM inside
-        when there is one) - with nbest beam_size id lists per utterance, ranked, a rank the search left unused as a row of
+        """Hypothesis ids of the transducer beam search for one batch (E2E.recognize_rnnt_beams, with the n-gram LM - or, ngram
+        being the keyword arguments of a word LM, the lexicon and the word LM - inside when there is one) - with nbest beam_size id lists per utterance, ranked, a rank the search left unused as a row of
         <EOS>; the abort word of the encoder's persistent kernels is checked after the decode, as in _greedy."""
         kw = dict(max_dec_timesteps=int(self.config.get("max_dec_timesteps", 200) or 200), **self._lm_kwargs(ngram))
 
@@ -716,6 +732,11 @@ class Solver(object):
         if wlm_path is not None:
             ngram = dict(word_lm=self.load_word_lm(wlm_path, lexicon_path), word_lm_weight=wlm_w, word_bonus=word_bonus,
                          lexicon_only=lexicon_only)
+        if rnnt_beam and self.config.get("rnnt_word_lm") is not None:
+            # `rnnt_word_lm` (not a reference key): the lexicon and the word LM inside the transducer search
+            rw = self.config["rnnt_word_lm"]
+            ngram = dict(word_lm=self.load_word_lm(rw["arpa"], rw.get("lexicon")), word_lm_weight=float(rw.get("weight", 0.0) or 0.0),
+                         word_bonus=float(rw.get("bonus", 0.0) or 0.0), lexicon_only=bool(rw.get("lexicon_only", False)))
         if state_dict:
             self.model.load_state_dict(state_dict)
         else:
