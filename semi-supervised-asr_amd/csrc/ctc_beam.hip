@@ -15,9 +15,10 @@
 //                                      frame into the history - LDS when T_b K entries fit kHistLds, the workspace otherwise
 //                         The emissions of the frame ahead are in registers (kStage tokens per thread) while a frame runs and go
 //                         to LDS at its end; a token behind kStage * threads is read from memory where it is used.
-//                         After the last frame the beam IS the ranking (the select's order); thread r walks the history back
-//                         into hyp[r].
-//   ctc_beam_kernel<M, true>   the search with an n-gram LM inside (the table is ngram.hip's): an entry also
+//                         After the last frame the beam IS the ranking (the select's order): thread r walks the history of
+//                         entry r back into hyp[r].  The same tail serves the word-LM mode, which finishes and ranks its
+//                         entries first; the n-gram mode has its own.
+//   ctc_beam_kernel<M, kNgram>   the search with an n-gram LM inside (the table is ngram.hip's): an entry also
 //                         carries its automaton state and lm, the fp32 sum of logp[state][c] over its tokens in order - both
 //                         functions of the token sequence, so equal prefixes hold equal bits and the merge is unchanged.  The
 //                         masses pb / pnb / tot are the plain kernel's, operation for operation; only the value a candidate
@@ -30,7 +31,8 @@
 //                         its COMPLETED words) and nw (their count) - again functions of the token sequence - and the "close"
 //                         pair (lp, next state) of its pending word, looked up ONCE by the thread that creates the entry
 //                         (update) and read from LDS by the candidate walk; a stay entry copies it.  Only an extension by
-//                         <space> from a node that is not the root changes lm and nw.  Ranks are lm_rank's with nw for len.
+//                         <space> from a node that is not the root changes lm and nw (word_lm.h's after_token; the tail and
+//                         an utterance without frames use its finish).  Ranks are lm_rank's with nw for len.
 //                         With lexicon_only the walk also reads the entry's trie row (one coalesced read per (entry, token),
 //                         as the n-gram variant reads its LM row) and drops what leaves the lexicon.
 #include <float.h>
@@ -46,17 +48,12 @@ constexpr int kMaxThreads = 256;
 constexpr int kOneWaveKV = ASR_CTC_BEAM_ONE_WAVE_KV;       // K V up to this: one wave per utterance
 constexpr int kHistLds = ASR_CTC_BEAM_LDS_ENTRIES;         // (frame, slot) history entries that stay in LDS
 static_assert(kKmax <= 32, "the merge map of an entry is one 32-bit mask");
-// (2048: the beam's two slots, the candidates' and the reduction's arrays - with the LM's state, lm, stay mass, rank and
-// position of every entry 1664 bytes at kKmax = 16)
+// (2048: the beam's two slots, the candidates' and the reduction's arrays - at most, with the word LM inside: 17 words per
+// entry, the state, lm and stay mass of a search with an LM 5, and node, nw and the close pair in two slots each 8; the
+// n-gram mode's rank and position are 2 in their place)
 static_assert(kHistLds * 8 + kStage * kMaxThreads * 4 + 2048 <= 64 * 1024, "the static LDS of a workgroup");
-static_assert((3 * 2 + 2 * 2 + 2 * 2 + 1 + 2 + 2 * 2 + 1 + 1 + 1 + 1) * 4 * kKmax + 2 * 2 * (kMaxThreads / 64) * 4 <= 2048,
-              "the beam's arrays, the LM's included, inside the 2048 bytes above");
-// (the word-LM variant: no s_rank / s_pos - its final ranking reuses s_spb / s_mk, dead by then -, and node, nw and the close
-// pair in two slots each: 17 + 5 + 8 = 30 words per entry)
-static_assert((3 * 2 + 2 * 2 + 2 * 2 + 1 + 2 + 2 * 2 + 1 + 4 * 2) * 4 * kKmax + 2 * 2 * (kMaxThreads / 64) * 4 <= 2048,
-              "the beam's arrays of the word-LM variant inside the same 2048 bytes");
-
-typedef unsigned long long u64;
+static_assert((17 + 5 + 4 * 2) * 4 * kKmax + 2 * 2 * (kMaxThreads / 64) * 4 <= 2048,
+              "the beam's arrays of the word-LM variant inside the 2048 bytes above");
 
 struct BeamWs {
   int2* hist;      // [B][T][K] (parent slot, token; token 0: the entry stayed); absent when T K entries fit LDS
@@ -73,23 +70,6 @@ BeamWs beam_ws(void* base, int B, int T, int K) {
   return w;
 }
 
-// log(exp a + exp b); (-inf) (+) (-inf) = -inf, and -inf (+) x = x exactly
-// (not ctc_prefix.hip's lae: log1pf here, logf(1 + .) there - they round differently, and each search's bits are its own)
-__device__ __forceinline__ float logaddexp(float a, float b) {
-  const float m = fmaxf(a, b), n = fminf(a, b);
-  if (n == -INFINITY) return m;
-  return m + log1pf(expf(n - m));
-}
-
-// the hash of prefix . c from the hash of prefix (the splitmix64 finaliser over hash + token): with the length and the last
-// token it stands for the token sequence
-__device__ __forceinline__ u64 prefix_hash(u64 h, int c) {
-  h += (u64)(unsigned)c + 0x9E3779B97F4A7C15ull;
-  h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
-  h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
-  return h ^ (h >> 31);
-}
-
 // the LM of a fused search (LM = true; all zero otherwise and never read)
 struct BeamLm {
   const float* logp;       // [S][V]
@@ -99,12 +79,6 @@ struct BeamLm {
   int start, eos;          // eos < 0: no end-of-sentence term
   float alpha, beta;
 };
-
-// what a candidate of the fused search is ranked by: (tot + alpha lm) + beta len, fp32, every operation rounded on its own
-// (no contraction into an fma) - tests/ngram_ref.py restates exactly this
-__device__ __forceinline__ float lm_rank(float tot, float lm, int len, float alpha, float beta) {
-  return __fadd_rn(__fadd_rn(tot, __fmul_rn(alpha, lm)), __fmul_rn(beta, (float)len));
-}
 
 // the lexicon and word LM of a fused search (MODE = kWordLm)
 struct BeamWlm {
@@ -145,9 +119,9 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
     for (int64_t i = tid; i < (int64_t)K * T; i += nt) hypb[i] = -1;
     if (tid < K) {
       if constexpr (WLM) {
-        float lm0 = 0.f;
-        int nx;
-        if (g.eos_term) wlm::lookup(g.w, g.w.start, g.w.eos, lm0, nx);
+        wlm::WordPos e = wlm::start_pos(g.w);
+        wlm::finish(g.w, e, 0.f, e.state, g.eos_term != 0);
+        const float lm0 = e.lm;
         score[(int64_t)b * K + tid] = tid == 0 ? lm_rank(0.f, lm0, 0, g.alpha, g.beta) : -INFINITY;
         g.ctc_score[(int64_t)b * K + tid] = tid == 0 ? 0.f : -INFINITY;
         g.lm_score[(int64_t)b * K + tid] = tid == 0 ? lm0 : -INFINITY;
@@ -386,23 +360,15 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
             const float mass = (tok == s_last[p][k] ? s_pb[p][k] : s_tot[p][k]) + xc;
             s_pnb[q][tid] = mass;
             s_tot[q][tid] = mass;
-            const int nk = s_node[p][k];
-            float lmn = s_lm[p][k];
-            int nwn = s_nw[p][k], sn = s_state[p][k], nn = 0;
-            if (tok != g.w.space) {
-              nn = wlm::trie_step(g.w, nk, tok);
-            } else if (nk != 0) {                                  // the pending word closes
-              lmn = __fadd_rn(lmn, s_clp[p][k]);
-              nwn += 1;
-              sn = s_cnx[p][k];
-            }
-            float cl = 0.f;
-            int cn = sn;
-            if (nn != 0) wlm::close_word(g.w, nn, sn, g.lexicon_only != 0, cl, cn);        // the new entry's close pair, once
-            s_lm[q][tid] = lmn;
-            s_state[q][tid] = sn;
-            s_node[q][tid] = nn;
-            s_nw[q][tid] = nwn;
+            const wlm::WordPos e = wlm::after_token(g.w, wlm::WordPos{s_node[p][k], s_state[p][k], s_lm[p][k], s_nw[p][k]}, tok,
+                                                    s_clp[p][k], s_cnx[p][k]);
+            float cl;
+            int cn;
+            wlm::close_pair(g.w, e.node, e.state, g.lexicon_only != 0, cl, cn);               // the new entry's close pair, once
+            s_lm[q][tid] = e.lm;
+            s_state[q][tid] = e.state;
+            s_node[q][tid] = e.node;
+            s_nw[q][tid] = e.nw;
             s_clp[q][tid] = cl;
             s_cnx[q][tid] = cn;
           } else {
@@ -427,74 +393,8 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
     p = q;
     nlive = nsel;
   }
-  if constexpr (WLM) {
-    // a pending word closes, the end-of-sentence term joins lm, and the entries rank once more as below; with lexicon_only
-    // an entry whose pending node ends no word leaves the list (rank -inf: behind every other, an unused slot).  s_spb and
-    // s_mk are dead after the last frame: they hold the ranks and the positions
-    float* const s_rk = s_spb;
-    int* const s_at = (int*)s_mk;
-    if (tid < nlive) {
-      float lm = s_lm[p][tid];
-      int nwe = s_nw[p][tid], st = s_state[p][tid];
-      bool dead = false;
-      if (s_node[p][tid] != 0) {
-        if (s_cnx[p][tid] < 0) {
-          dead = true;
-        } else {
-          lm = __fadd_rn(lm, s_clp[p][tid]);
-          nwe += 1;
-          st = s_cnx[p][tid];
-        }
-      }
-      if (g.eos_term && !dead) {
-        float lp;
-        int nx;
-        wlm::lookup(g.w, st, g.w.eos, lp, nx);
-        lm = __fadd_rn(lm, lp);
-      }
-      s_lm[p][tid] = lm;
-      s_nw[p][tid] = nwe;
-      s_rk[tid] = dead ? -INFINITY : lm_rank(s_tot[p][tid], lm, nwe, g.alpha, g.beta);
-    }
-    __syncthreads();
-    if (tid < K) {
-      int at = tid;
-      if (tid < nlive) {
-        const float rv = s_rk[tid];
-        at = 0;
-        for (int j = 0; j < nlive; ++j) at += j != tid && better(s_rk[j], j, rv, tid) ? 1 : 0;
-      }
-      const int64_t o = (int64_t)b * K + at;
-      if (tid < nlive && s_rk[tid] != -INFINITY) {
-        int32_t* row = hypb + (int64_t)at * T;
-        const int n = s_len[p][tid];
-        int pos = n - 1, slot = tid;
-        for (int t = len - 1; t >= 0; --t) {
-          const int2 e = hist[(int64_t)t * K + slot];
-          if (e.y != 0 && pos >= 0) row[pos--] = e.y;
-          slot = e.x;
-        }
-        score[o] = s_rk[tid];
-        g.ctc_score[o] = s_tot[p][tid];
-        g.lm_score[o] = s_lm[p][tid];
-        g.n_words[o] = s_nw[p][tid];
-        hyp_len[o] = n;
-      } else {
-        score[o] = -INFINITY;
-        g.ctc_score[o] = -INFINITY;
-        g.lm_score[o] = -INFINITY;
-        g.n_words[o] = -1;
-        hyp_len[o] = -1;
-      }
-      s_at[tid] = at;
-    }
-    __syncthreads();
-    for (int r = 0; r < K; ++r) {
-      const int n = r < nlive && s_rk[r] != -INFINITY ? s_len[p][r] : 0;
-      for (int i = n + tid; i < T; i += nt) hypb[(int64_t)s_at[r] * T + i] = -1;
-    }
-    return;
-  }
+  // The n-gram mode keeps a tail of its own, with its ranks and positions in s_rank / s_pos: folded into the tail below it
+  // measured about 1 % slower at K = 4 (0.6948 -> 0.7011 ms at B = 32, T' = 100, V = 50), and the fold gave way.
   if constexpr (LM) {
     // the end-of-sentence term joins lm; the entries rank by lm_rank once more, ties to the search's order (without the term
     // every rank is the select's and the order stays); thread r walks the history of entry r back into the row of its rank
@@ -538,10 +438,49 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
     }
     return;
   }
-  // the beam is the ranking; thread r walks the history of entry r back into its row
-  if (tid < K) {
-    int32_t* row = hypb + (int64_t)tid * T;
+  // the score rows of list position `at`: a hypothesis of n tokens, or (n = -1, everything else -inf / -1) an unused slot
+  const auto put = [&](int at, int n, float rank, float tot, float lm, int words) {
+    const int64_t o = (int64_t)b * K + at;
+    score[o] = rank;
+    hyp_len[o] = n;
+    if constexpr (RK) {
+      g.ctc_score[o] = tot;
+      g.lm_score[o] = lm;
+    }
+    if constexpr (WLM) g.n_words[o] = words;
+  };
+  const auto put_unused = [&](int at) { put(at, -1, -INFINITY, -INFINITY, -INFINITY, -1); };
+  // The tail of the plain and the word-LM mode.  Plain: the beam IS the ranking - entry tid goes to row tid at rank tot.  With
+  // the word LM inside, entry tid first becomes a complete hypothesis (wlm::finish: its pending word closes, then the
+  // end-of-sentence term joins lm) and the (at most K) entries rank by lm_rank once more, ties to the search's order.  With
+  // lexicon_only an entry whose pending node ends no word leaves the list: rank -inf, behind every other, an unused slot.
+  // s_spb and s_mk are dead after the last frame: they hold the ranks and the positions.
+  float* const s_rk = s_spb;
+  int* const s_at = (int*)s_mk;
+  float rank = -INFINITY, lm = 0.f;
+  int at = tid, words = 0;
+  if (tid < nlive) {
+    rank = s_tot[p][tid];
+    if constexpr (WLM) {
+      wlm::WordPos e{s_node[p][tid], s_state[p][tid], s_lm[p][tid], s_nw[p][tid]};
+      const bool ok = wlm::finish(g.w, e, s_clp[p][tid], s_cnx[p][tid], g.eos_term != 0);
+      lm = e.lm, words = e.nw;
+      rank = ok ? lm_rank(rank, lm, words, g.alpha, g.beta) : -INFINITY;
+    }
+    if constexpr (WLM) s_rk[tid] = rank;
+  }
+  if constexpr (WLM) {
+    __syncthreads();
     if (tid < nlive) {
+      at = 0;
+      for (int j = 0; j < nlive; ++j) at += j != tid && better(s_rk[j], j, rank, tid) ? 1 : 0;
+    }
+    if (tid < K) s_at[tid] = at;
+  }
+  const auto kept = [&](int r, float rk) { return r < nlive && (!WLM || rk != -INFINITY); };      // entry r is a hypothesis
+  if (tid < K) {
+    if (kept(tid, rank)) {                                   // the history of entry tid, walked back into the row of its rank
+      int32_t* row = hypb + (int64_t)at * T;
       const int n = s_len[p][tid];
       int pos = n - 1, slot = tid;
       for (int t = len - 1; t >= 0; --t) {
@@ -549,16 +488,15 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
         if (e.y != 0 && pos >= 0) row[pos--] = e.y;
         slot = e.x;
       }
-      score[(int64_t)b * K + tid] = s_tot[p][tid];
-      hyp_len[(int64_t)b * K + tid] = n;
+      put(at, n, rank, s_tot[p][tid], lm, words);
     } else {
-      score[(int64_t)b * K + tid] = -INFINITY;
-      hyp_len[(int64_t)b * K + tid] = -1;
+      put_unused(at);
     }
   }
+  if constexpr (WLM) __syncthreads();
   for (int r = 0; r < K; ++r) {
-    const int n = r < nlive ? s_len[p][r] : 0;
-    for (int i = n + tid; i < T; i += nt) hypb[(int64_t)r * T + i] = -1;
+    const int n = kept(r, WLM ? s_rk[r] : 0.f) ? s_len[p][r] : 0;
+    for (int i = n + tid; i < T; i += nt) hypb[(int64_t)(WLM ? s_at[r] : r) * T + i] = -1;
   }
 }
 
@@ -569,9 +507,19 @@ int beam_check(int B, int T, int V, int K) {
   return 0;
 }
 
+// what the three entries check first, and what they do once their own checks have passed
+bool common_args_ok(const float* logits, int64_t ld, int V, const int32_t* frame_lens, const int32_t* hyp, const int32_t* hyp_len,
+                    const float* score, const void* ws) {
+  return logits && frame_lens && hyp && hyp_len && score && ws && ld >= V;
+}
+
 template <int MODE, class G>
-void launch_ctc_beam(int B, int T, int V, int K, const float* logits, int64_t ld, const int32_t* frame_lens, int32_t* hyp,
-                     int32_t* hyp_len, float* score, const BeamWs& w, const G& g, hipStream_t stream) {
+int launch(int B, int T, int V, int K, const float* logits, int64_t ld, const int32_t* frame_lens, int32_t* hyp, int32_t* hyp_len,
+           float* score, void* ws, const G& g, hipStream_t stream) {
+  if ((((uintptr_t)ws) & 7u) != 0) return ASR_E_ALIGN;
+  const BeamWs w = beam_ws(ws, B, T, K);
+  launch_frame_lse(B, T, V, logits, ld, frame_lens, w.lse, stream);
+  ASR_CHECK_LAUNCH();
   const dim3 grid(B), block((int64_t)K * V <= kOneWaveKV ? 64 : kMaxThreads);
 #define CTC_BEAM(M_) \
   hipLaunchKernelGGL((ctc_beam_kernel<M_, MODE>), grid, block, 0, stream, T, V, K, logits, ld, frame_lens, hyp, hyp_len, score, w, g)
@@ -581,6 +529,8 @@ void launch_ctc_beam(int B, int T, int V, int K, const float* logits, int64_t ld
   else if (K <= 8) CTC_BEAM(8);
   else CTC_BEAM(16);
 #undef CTC_BEAM
+  ASR_CHECK_LAUNCH();
+  return 0;
 }
 
 }  // namespace
@@ -595,45 +545,33 @@ extern "C" int asr_ctc_beam_ws_bytes(int B, int T, int V, int K, int64_t* ws_byt
 
 extern "C" int asr_ctc_beam_f32(int B, int T, int V, int K, const float* logits, int64_t ld, const int32_t* frame_lens,
                                 int32_t* hyp, int32_t* hyp_len, float* score, void* ws, asr_stream_t stream) {
-  if (!logits || !frame_lens || !hyp || !hyp_len || !score || !ws || ld < V) return ASR_E_ARG;
+  if (!common_args_ok(logits, ld, V, frame_lens, hyp, hyp_len, score, ws)) return ASR_E_ARG;
   const int rc = beam_check(B, T, V, K);
   if (rc) return rc;
-  if ((((uintptr_t)ws) & 7u) != 0) return ASR_E_ALIGN;
-  const BeamWs w = beam_ws(ws, B, T, K);
-  launch_frame_lse(B, T, V, logits, ld, frame_lens, w.lse, (hipStream_t)stream);
-  ASR_CHECK_LAUNCH();
-  launch_ctc_beam<kPlain>(B, T, V, K, logits, ld, frame_lens, hyp, hyp_len, score, w, BeamLm{}, (hipStream_t)stream);
-  ASR_CHECK_LAUNCH();
-  return 0;
+  return launch<kPlain>(B, T, V, K, logits, ld, frame_lens, hyp, hyp_len, score, ws, BeamLm{}, (hipStream_t)stream);
 }
 
 extern "C" int asr_ctc_beam_lm_f32(int B, int T, int V, int K, const float* logits, int64_t ld, const int32_t* frame_lens, int S,
                                    const float* lm_logp, const int32_t* lm_next, int lm_start, int lm_eos, float alpha, float beta,
                                    int32_t* hyp, int32_t* hyp_len, float* score, float* ctc_score, float* lm_score, void* ws,
                                    asr_stream_t stream) {
-  if (!logits || !frame_lens || !hyp || !hyp_len || !score || !ws || ld < V || !lm_logp || !lm_next || !ctc_score || !lm_score ||
+  if (!common_args_ok(logits, ld, V, frame_lens, hyp, hyp_len, score, ws) || !lm_logp || !lm_next || !ctc_score || !lm_score ||
       S <= 0 || !(fabsf(alpha) <= FLT_MAX) || !(fabsf(beta) <= FLT_MAX))
     return ASR_E_ARG;
   const int rc = beam_check(B, T, V, K);
   if (rc) return rc;
   if ((int64_t)S * V > INT_MAX || lm_start < 0 || lm_start >= S || lm_eos >= V) return ASR_E_SHAPE;
-  if ((((uintptr_t)ws) & 7u) != 0) return ASR_E_ALIGN;
-  const BeamWs w = beam_ws(ws, B, T, K);
-  launch_frame_lse(B, T, V, logits, ld, frame_lens, w.lse, (hipStream_t)stream);
-  ASR_CHECK_LAUNCH();
   BeamLm g;
   g.logp = lm_logp, g.next = lm_next, g.ctc_score = ctc_score, g.lm_score = lm_score;
   g.start = lm_start, g.eos = lm_eos < 0 ? -1 : lm_eos, g.alpha = alpha, g.beta = beta;
-  launch_ctc_beam<kNgram>(B, T, V, K, logits, ld, frame_lens, hyp, hyp_len, score, w, g, (hipStream_t)stream);
-  ASR_CHECK_LAUNCH();
-  return 0;
+  return launch<kNgram>(B, T, V, K, logits, ld, frame_lens, hyp, hyp_len, score, ws, g, (hipStream_t)stream);
 }
 
 extern "C" int asr_ctc_beam_wlm_f32(int B, int T, int V, int K, const float* logits, int64_t ld, const int32_t* frame_lens,
                                     const asr_word_lm_t* lm, float alpha, float beta, int eos_term, int lexicon_only,
                                     int32_t* hyp, int32_t* hyp_len, float* score, float* ctc_score, float* lm_score,
                                     int32_t* n_words, void* ws, asr_stream_t stream) {
-  if (!logits || !frame_lens || !hyp || !hyp_len || !score || !ws || ld < V || !ctc_score || !lm_score || !n_words ||
+  if (!common_args_ok(logits, ld, V, frame_lens, hyp, hyp_len, score, ws) || !ctc_score || !lm_score || !n_words ||
       !(fabsf(alpha) <= FLT_MAX) || !(fabsf(beta) <= FLT_MAX))
     return ASR_E_ARG;
   int rc = wlm::check_abi(lm);
@@ -641,15 +579,9 @@ extern "C" int asr_ctc_beam_wlm_f32(int B, int T, int V, int K, const float* log
   rc = beam_check(B, T, V, K);
   if (rc) return rc;
   if (lm->V != V) return ASR_E_SHAPE;
-  if ((((uintptr_t)ws) & 7u) != 0) return ASR_E_ALIGN;
-  const BeamWs w = beam_ws(ws, B, T, K);
-  launch_frame_lse(B, T, V, logits, ld, frame_lens, w.lse, (hipStream_t)stream);
-  ASR_CHECK_LAUNCH();
   BeamWlm g;
   g.w = wlm::from_abi(*lm);
   g.ctc_score = ctc_score, g.lm_score = lm_score, g.n_words = n_words;
   g.alpha = alpha, g.beta = beta, g.eos_term = eos_term != 0, g.lexicon_only = lexicon_only != 0;
-  launch_ctc_beam<kWordLm>(B, T, V, K, logits, ld, frame_lens, hyp, hyp_len, score, w, g, (hipStream_t)stream);
-  ASR_CHECK_LAUNCH();
-  return 0;
+  return launch<kWordLm>(B, T, V, K, logits, ld, frame_lens, hyp, hyp_len, score, ws, g, (hipStream_t)stream);
 }

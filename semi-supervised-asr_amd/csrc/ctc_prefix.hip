@@ -20,7 +20,7 @@
 namespace {
 
 // log(exp(a) + exp(b)); (-inf, -inf) -> -inf, never NaN for arguments below +inf
-// (not ctc_beam.hip's logaddexp: logf(1 + .) here, log1pf there - they round differently, and each search's bits are its own)
+// (not seq_common.h's logaddexp: logf(1 + .) here, log1pf there - they round differently, and each search's bits are its own)
 __device__ __forceinline__ float lae(float a, float b) {
   const float m = fmaxf(a, b);
   if (m == -INFINITY) return -INFINITY;

@@ -5,9 +5,8 @@
 // iteration - the blank to (t + 1, u), a label to (t, u + 1) - and a fixed T + L iterations finish every row: no host read.
 // Two candidates that are the same label sequence at the same node - the blank candidate of entry h and the label candidate
 // (h', k) with seq(h') . k = seq(h) - are ONE candidate whose mass is the logaddexp of the two: the lattice recursion
-// alpha(t, u) of the loss, restricted to the beam.  Equal sequences are found as ctc_beam.hip finds them: the 64-bit
-// sequence hash and the length (a collision of two different sequences of one length inside one beam would merge them:
-// the odds, 2^-64 per pair, are accepted here as they are there).  The merged candidate keeps the flat index, the
+// alpha(t, u) of the loss, restricted to the beam.  Equal sequences are found as ctc_beam.hip finds them, by
+// seq_common.h's merge identity (prefix_hash and the length), and ranks are its lm_rank.  The merged candidate keeps the flat index, the
 // prediction-network state and the history record of its BLANK parent: its bits are a function of the inputs.
 //   rnnt_beam_init_kernel       the empty sequence at (0, 0) in slot 0 of every utterance with a frame, the gathered cell
 //                               input [emb(<BOS>) | 0] with advance = 1 for it, zeros for the other slots
@@ -31,8 +30,8 @@
 // With a word LM and its lexicon inside the search (the kernels' WLM instantiations, the asr_transducer_wbeam_*
 // entries) an entry additionally carries its trie node, its word state, lm - the sum over its COMPLETED words - and their
 // count nw: functions of the token sequence, so the merge and prefix identity are untouched.  One thread per live entry
-// does the entry's lookups (csrc/word_lm.h: the pending word's close pair, which is what a `space` candidate and a final
-// both need, and a final's end-of-sentence term) into LDS; the candidate walk reads them, and with lexicon_only one
+// does the entry's lookups (word_lm.h's close_pair, which is what a `space` candidate and a final both need, and its finish
+// for a final) into LDS; the new beam moves by its after_token; the candidate walk reads them, and with lexicon_only one
 // trie_next word per (entry, token).  The instantiations without it hold none of this.
 #include <float.h>
 #include <type_traits>
@@ -46,8 +45,6 @@ constexpr int kThreads = 256;
 constexpr int kBeamLds = ASR_RNNT_BEAM_LDS_BYTES;
 static_assert(kKmax <= 32, "the merge map of an entry is one 32-bit mask");
 static_assert(kBeamLds + 4096 <= 64 * 1024, "dynamic and static LDS of the step kernel inside 64 KB");
-
-typedef unsigned long long u64;
 
 struct BeamWs {
   u64* hash;           // [2][B K]
@@ -117,27 +114,6 @@ int beam_shape_check(int B, int T, int J, int V, int K, int L, int E, int P) {
       ((int64_t)T + L) * B * K > INT_MAX)
     return ASR_E_SHAPE;
   return 0;
-}
-
-// log(exp a + exp b), symmetric in its arguments; -inf (+) x = x exactly
-__device__ __forceinline__ float logaddexp(float a, float b) {
-  const float m = fmaxf(a, b), n = fminf(a, b);
-  if (n == -INFINITY) return m;
-  return m + log1pf(expf(n - m));
-}
-
-// ctc_beam.hip's sequence hash: the splitmix64 finaliser over hash + token
-__device__ __forceinline__ u64 prefix_hash(u64 h, int c) {
-  h += (u64)(unsigned)c + 0x9E3779B97F4A7C15ull;
-  h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
-  h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
-  return h ^ (h >> 31);
-}
-
-// (tot + alpha lm) + beta u, every operation rounded on its own: the form of asr_ctc_beam_lm_f32.  alpha = beta = 0 with a
-// finite lm gives tot itself, so the plain search is this one at zero weights.
-__device__ __forceinline__ float lm_rank(float tot, float lm, int u, float alpha, float beta) {
-  return __fadd_rn(__fadd_rn(tot, __fmul_rn(alpha, lm)), __fmul_rn(beta, (float)u));
 }
 
 template <bool WLM>
@@ -260,30 +236,16 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_step_kernel(asr_transducer
     s_mk[tid] = mk;
     if constexpr (WLM) {
       // the close pair of the pending word: what a `space` candidate of this entry, and this entry as a final, add
-      const int nd = s_node[tid], st = s_wst[tid];
-      float lp = 0.f;
-      int nx = st;
-      if (nd != 0) wlm::close_word(g.w, nd, st, g.lexicon_only != 0, lp, nx);
+      wlm::WordPos e{s_node[tid], s_wst[tid], s_lm[tid], s_nw[tid]};
+      float lp;
+      int nx;
+      wlm::close_pair(g.w, e.node, e.state, g.lexicon_only != 0, lp, nx);
       s_slp[tid] = lp;
       s_snx[tid] = nx;
       if (fin) {
-        float fl = s_lm[tid];
-        int fn = s_nw[tid], fs = st;
-        const int ok = (nd != 0 && nx < 0) ? 0 : 1;
-        if (ok && nd != 0) {
-          fl = __fadd_rn(fl, lp);
-          ++fn;
-          fs = nx;
-        }
-        if (ok && g.eos_term) {
-          float el;
-          int en;
-          wlm::lookup(g.w, fs, g.w.eos, el, en);
-          fl = __fadd_rn(fl, el);
-        }
-        s_flm[tid] = fl;
-        s_fnw[tid] = fn;
-        s_fok[tid] = ok;
+        s_fok[tid] = wlm::finish(g.w, e, lp, nx, g.eos_term != 0) ? 1 : 0;
+        s_flm[tid] = e.lm;
+        s_fnw[tid] = e.nw;
       }
     }
   }
@@ -361,22 +323,12 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_step_kernel(asr_transducer
         adv = 1;
       }
       if constexpr (WLM) {
-        int nd = s_node[h], st = s_wst[h], n = s_nw[h];
-        float l = s_lm[h];
-        if (k == g.w.space) {
-          if (nd != 0) {
-            l = __fadd_rn(l, s_slp[h]);
-            st = s_snx[h];
-            ++n;
-            nd = 0;
-          }
-        } else if (k != 0) {
-          nd = wlm::trie_step(g.w, nd, k);
-        }
-        w.lm[d] = l;
-        g.node[d] = nd;
-        g.wst[d] = st;
-        g.nw[d] = n;
+        wlm::WordPos e{s_node[h], s_wst[h], s_lm[h], s_nw[h]};
+        if (k != 0) e = wlm::after_token(g.w, e, k, s_slp[h], s_snx[h]);
+        w.lm[d] = e.lm;
+        g.node[d] = e.node;
+        g.wst[d] = e.state;
+        g.nw[d] = e.nw;
       }
       w.hist[((int64_t)it * B + b) * K + tid] = make_int2(k, h);
       s_par[tid] = h;
@@ -482,10 +434,10 @@ __global__ __launch_bounds__(64) void rnnt_beam_backtrace_kernel(asr_transducer_
       u = 0;
       tot = 0.f;
       if constexpr (WLM) {
-        int nx;
-        lm = 0.f;
+        wlm::WordPos e = wlm::start_pos(g.w);
+        wlm::finish(g.w, e, 0.f, e.state, g.eos_term != 0);
+        lm = e.lm;
         words = 0;
-        if (g.eos_term) wlm::lookup(g.w, g.w.start, g.w.eos, lm, nx);
         rank = lm_rank(0.f, lm, 0, g.alpha, g.beta);
       } else {
         lm = (lmode && a.lm_eos >= 0) ? a.lm_logp[(int64_t)a.lm_start * a.V + a.lm_eos] : 0.f;
@@ -551,6 +503,35 @@ int wbeam_args(const asr_transducer_beam_t* a, const asr_word_lm_t* lm, float al
   return 0;
 }
 
+// The launches behind both entry families (g: NoWlm() or the BeamWlm of wbeam_args); `a` has passed the entry's checks.
+template <bool WLM>
+int launch_init(const asr_transducer_beam_t* a, int bos, const std::conditional_t<WLM, BeamWlm, NoWlm>& g, asr_stream_t stream) {
+  if (bos < 0 || bos >= a->V) return ASR_E_ARG;
+  hipLaunchKernelGGL(rnnt_beam_init_kernel<WLM>, dim3(a->B), dim3(kThreads), 0, (hipStream_t)stream, *a, bos,
+                     beam_ws(a->ws, a->B, a->T, a->K, a->L, a->P), g);
+  ASR_CHECK_LAUNCH();
+  return 0;
+}
+
+template <bool WLM>
+int launch_step(const asr_transducer_beam_t* a, int it, const std::conditional_t<WLM, BeamWlm, NoWlm>& g, asr_stream_t stream) {
+  if (it < 0 || it >= a->T + a->L) return ASR_E_ARG;
+  hipLaunchKernelGGL(rnnt_beam_step_kernel<WLM>, dim3(a->B), dim3(kThreads), (size_t)a->K * ((size_t)a->J + a->V) * 4,
+                     (hipStream_t)stream, *a, it, beam_ws(a->ws, a->B, a->T, a->K, a->L, a->P), g);
+  ASR_CHECK_LAUNCH();
+  return 0;
+}
+
+template <bool WLM>
+int launch_backtrace(const asr_transducer_beam_t* a, int32_t* hyp, int32_t* hyp_len, float* score, float* rnnt_score,
+                     float* lm_score, const std::conditional_t<WLM, BeamWlm, NoWlm>& g, int32_t* n_words, asr_stream_t stream) {
+  if (!hyp || !hyp_len || !score || (WLM && !n_words)) return ASR_E_ARG;
+  hipLaunchKernelGGL(rnnt_beam_backtrace_kernel<WLM>, dim3(a->B), dim3(64), 0, (hipStream_t)stream, *a,
+                     beam_ws(a->ws, a->B, a->T, a->K, a->L, a->P), hyp, hyp_len, score, rnnt_score, lm_score, g, n_words);
+  ASR_CHECK_LAUNCH();
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int asr_transducer_beam_ws_bytes(int B, int T, int J, int V, int K, int L, int E, int P, int64_t* ws_bytes) {
@@ -563,22 +544,12 @@ extern "C" int asr_transducer_beam_ws_bytes(int B, int T, int J, int V, int K, i
 
 extern "C" int asr_transducer_beam_init_f32(const asr_transducer_beam_t* a, int bos, asr_stream_t stream) {
   const int rc = beam_args_check(a);
-  if (rc) return rc;
-  if (bos < 0 || bos >= a->V) return ASR_E_ARG;
-  hipLaunchKernelGGL(rnnt_beam_init_kernel<false>, dim3(a->B), dim3(kThreads), 0, (hipStream_t)stream, *a, bos,
-                     beam_ws(a->ws, a->B, a->T, a->K, a->L, a->P), NoWlm());
-  ASR_CHECK_LAUNCH();
-  return 0;
+  return rc ? rc : launch_init<false>(a, bos, NoWlm(), stream);
 }
 
 extern "C" int asr_transducer_beam_step_f32(const asr_transducer_beam_t* a, int it, asr_stream_t stream) {
   const int rc = beam_args_check(a);
-  if (rc) return rc;
-  if (it < 0 || it >= a->T + a->L) return ASR_E_ARG;
-  hipLaunchKernelGGL(rnnt_beam_step_kernel<false>, dim3(a->B), dim3(kThreads), (size_t)a->K * ((size_t)a->J + a->V) * 4,
-                     (hipStream_t)stream, *a, it, beam_ws(a->ws, a->B, a->T, a->K, a->L, a->P), NoWlm());
-  ASR_CHECK_LAUNCH();
-  return 0;
+  return rc ? rc : launch_step<false>(a, it, NoWlm(), stream);
 }
 
 extern "C" int asr_transducer_beam_cell_f32(const asr_transducer_beam_t* a, const float* gates, float* h, float* c, asr_stream_t stream) {
@@ -596,13 +567,7 @@ extern "C" int asr_transducer_beam_cell_f32(const asr_transducer_beam_t* a, cons
 extern "C" int asr_transducer_beam_backtrace_f32(const asr_transducer_beam_t* a, int32_t* hyp, int32_t* hyp_len, float* score,
                                            float* rnnt_score, float* lm_score, asr_stream_t stream) {
   const int rc = beam_args_check(a);
-  if (rc) return rc;
-  if (!hyp || !hyp_len || !score) return ASR_E_ARG;
-  hipLaunchKernelGGL(rnnt_beam_backtrace_kernel<false>, dim3(a->B), dim3(64), 0, (hipStream_t)stream, *a,
-                     beam_ws(a->ws, a->B, a->T, a->K, a->L, a->P), hyp, hyp_len, score, rnnt_score, lm_score, NoWlm(),
-                     (int32_t*)nullptr);
-  ASR_CHECK_LAUNCH();
-  return 0;
+  return rc ? rc : launch_backtrace<false>(a, hyp, hyp_len, score, rnnt_score, lm_score, NoWlm(), nullptr, stream);
 }
 
 extern "C" int asr_transducer_wbeam_ws_bytes(int B, int K, int64_t* ws_bytes) {
@@ -617,12 +582,7 @@ extern "C" int asr_transducer_wbeam_init_f32(const asr_transducer_beam_t* a, con
                                              asr_stream_t stream) {
   BeamWlm g;
   const int rc = wbeam_args(a, lm, alpha, beta, eos_term, lexicon_only, wws, wws_bytes, &g);
-  if (rc) return rc;
-  if (bos < 0 || bos >= a->V) return ASR_E_ARG;
-  hipLaunchKernelGGL(rnnt_beam_init_kernel<true>, dim3(a->B), dim3(kThreads), 0, (hipStream_t)stream, *a, bos,
-                     beam_ws(a->ws, a->B, a->T, a->K, a->L, a->P), g);
-  ASR_CHECK_LAUNCH();
-  return 0;
+  return rc ? rc : launch_init<true>(a, bos, g, stream);
 }
 
 extern "C" int asr_transducer_wbeam_step_f32(const asr_transducer_beam_t* a, const asr_word_lm_t* lm, float alpha, float beta,
@@ -630,12 +590,7 @@ extern "C" int asr_transducer_wbeam_step_f32(const asr_transducer_beam_t* a, con
                                              asr_stream_t stream) {
   BeamWlm g;
   const int rc = wbeam_args(a, lm, alpha, beta, eos_term, lexicon_only, wws, wws_bytes, &g);
-  if (rc) return rc;
-  if (it < 0 || it >= a->T + a->L) return ASR_E_ARG;
-  hipLaunchKernelGGL(rnnt_beam_step_kernel<true>, dim3(a->B), dim3(kThreads), (size_t)a->K * ((size_t)a->J + a->V) * 4,
-                     (hipStream_t)stream, *a, it, beam_ws(a->ws, a->B, a->T, a->K, a->L, a->P), g);
-  ASR_CHECK_LAUNCH();
-  return 0;
+  return rc ? rc : launch_step<true>(a, it, g, stream);
 }
 
 extern "C" int asr_transducer_wbeam_backtrace_f32(const asr_transducer_beam_t* a, const asr_word_lm_t* lm, float alpha, float beta,
@@ -644,10 +599,5 @@ extern "C" int asr_transducer_wbeam_backtrace_f32(const asr_transducer_beam_t* a
                                                   int32_t* n_words, asr_stream_t stream) {
   BeamWlm g;
   const int rc = wbeam_args(a, lm, alpha, beta, eos_term, lexicon_only, wws, wws_bytes, &g);
-  if (rc) return rc;
-  if (!hyp || !hyp_len || !score || !n_words) return ASR_E_ARG;
-  hipLaunchKernelGGL(rnnt_beam_backtrace_kernel<true>, dim3(a->B), dim3(64), 0, (hipStream_t)stream, *a,
-                     beam_ws(a->ws, a->B, a->T, a->K, a->L, a->P), hyp, hyp_len, score, rnnt_score, lm_score, g, n_words);
-  ASR_CHECK_LAUNCH();
-  return 0;
+  return rc ? rc : launch_backtrace<true>(a, hyp, hyp_len, score, rnnt_score, lm_score, g, n_words, stream);
 }

@@ -1,10 +1,13 @@
 // seq_common.h — what the sequence kernels over a [rows][V] logit matrix share: ctc.hip, ctc_align.hip, ctc_beam.hip,
-// ctc_prefix.hip, beam.hip and mwer.hip.  The conventions that make two-pass decoding, joint search and MWER agree to the bit
-// live here and nowhere else:
+// ctc_prefix.hip, rnnt_beam.hip, beam.hip and mwer.hip.  The conventions that make two-pass decoding, joint search and MWER
+// agree to the bit live here and nowhere else:
 //   blank = 0; the extended labels of a transcript are l' = (0, l_1, 0, l_2, ..., l_L, 0), S = 2L + 1 states
 //   x[t][v] = z[t][v] - lse[t], with lse[t] = mx + logf(se) of wave_row_max_sumexp - no [rows][V] log-prob tensor exists
 //   frames behind an utterance (t >= clamp_len(len, T)) are never read
 //   candidates rank by greater value first, lower flat index on ties (better)
+//   two entries of a beam are the same token sequence when hash (prefix_hash), length and last token agree: the merge
+//   identity of ctc_beam.hip and rnnt_beam.hip, whose merged masses join by logaddexp
+//   a search with an LM inside ranks by (tot + alpha lm) + beta len (lm_rank)
 // No floating-point atomics, every sum in an order fixed by the shapes: the same bits in every run.
 #pragma once
 #include <limits.h>
@@ -22,6 +25,33 @@ __device__ __forceinline__ int clamp_len(int len, int T) { return len < 0 ? 0 : 
 
 // candidate order: greater value first, lower flat index on ties
 __device__ __forceinline__ bool better(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
+
+typedef unsigned long long u64;
+
+// log(exp a + exp b), symmetric in its arguments; (-inf) (+) (-inf) = -inf, and -inf (+) x = x exactly
+// (not ctc_prefix.hip's lae: log1pf here, logf(1 + .) there - they round differently, and each search's bits are its own)
+__device__ __forceinline__ float logaddexp(float a, float b) {
+  const float m = fmaxf(a, b), n = fminf(a, b);
+  if (n == -INFINITY) return m;
+  return m + log1pf(expf(n - m));
+}
+
+// the hash of prefix . c from the hash of prefix (the splitmix64 finaliser over hash + token): with the length and the last
+// token it stands for the token sequence (a collision of two different sequences of one length inside one beam would merge
+// them: the odds, 2^-64 per pair, are accepted)
+__device__ __forceinline__ u64 prefix_hash(u64 h, int c) {
+  h += (u64)(unsigned)c + 0x9E3779B97F4A7C15ull;
+  h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
+  h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
+  return h ^ (h >> 31);
+}
+
+// what a candidate of a search with an LM inside is ranked by: (tot + alpha lm) + beta len, fp32, every operation rounded on
+// its own (no contraction into an fma) - tests/ngram_ref.py restates exactly this.  alpha = beta = 0 with a finite lm gives
+// tot itself, so a plain search is the fused one at zero weights.
+__device__ __forceinline__ float lm_rank(float tot, float lm, int len, float alpha, float beta) {
+  return __fadd_rn(__fadd_rn(tot, __fmul_rn(alpha, lm)), __fmul_rn(beta, (float)len));
+}
 
 // One wave's pass over a row of V logits: lanes strided over V in ascending order, then the xor butterfly - the maximum,
 // and the sum of exp(x - max).  Every lane ends with both; log-sum-exp = mx + logf(se).

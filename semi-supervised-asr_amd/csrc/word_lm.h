@@ -1,5 +1,5 @@
 // word_lm.h — the device form of a word-level backoff n-gram LM behind a lexicon (the tables are word_lm.py's
-// WordTable, validated by WordLM.compile(): the kernels trust every index).  Shared by word_lm.hip and ctc_beam.hip.
+// WordTable, validated by WordLM.compile(): the kernels trust every index).  Shared by word_lm.hip, ctc_beam.hip and rnnt_beam.hip.
 //   the lexicon   a trie over token ids: trie_next int32 [N][V] (child node or -1; node 0 is the root), trie_word int32 [N]
 //                 (the word id that ends at the node, or -1)
 //   the LM        sparse: the arcs of state s are arc_off[s] .. arc_off[s + 1] - 1, arc_word ascending inside a state, with
@@ -96,6 +96,55 @@ __device__ __forceinline__ void close_word(const WordLm& g, int node, int s, boo
 // the trie node after token c (c in 0 .. V-1) from `node` (< 0: off the trie, and it stays there)
 __device__ __forceinline__ int trie_step(const WordLm& g, int node, int c) {
   return node < 0 ? -1 : g.trie_next[(int64_t)node * g.V + c];
+}
+
+// The word position of a hypothesis - a function of its token sequence - and its transitions, one thread's.  The searches
+// (ctc_beam.hip, rnnt_beam.hip) move through these and nothing else; the scorer (word_lm.hip) spells the same walk out for a
+// row, and a search's lm_score must be the scorer's to the bit: lm is the fp32 sum over the COMPLETED words in word order, every addition
+// rounded on its own; as a complete hypothesis the pending word joins first, then the end-of-sentence term.
+struct WordPos {
+  int node, state;         // the trie node of the pending word (0: the root, none pending; < 0: off the trie), the word state
+  float lm;
+  int nw;                  // the completed words
+};
+
+__device__ __forceinline__ WordPos start_pos(const WordLm& g) { return WordPos{0, g.start, 0.f, 0}; }
+
+// the close pair of the pending word: what a <space> and the end of the hypothesis add, and the state behind it
+// ((0, state) at the root; next < 0: lexicon_only and the node ends no word).  A search looks it up once per entry.
+__device__ __forceinline__ void close_pair(const WordLm& g, int node, int state, bool lexicon_only, float& lp, int& next) {
+  lp = 0.f;
+  next = state;
+  if (node != 0) close_word(g, node, state, lexicon_only, lp, next);
+}
+
+// the position after the non-blank token c, (lp, next) being p's close pair: only a <space> behind a pending word closes it
+__device__ __forceinline__ WordPos after_token(const WordLm& g, WordPos p, int c, float lp, int next) {
+  if (c != g.space) {
+    p.node = trie_step(g, p.node, c);
+  } else if (p.node != 0) {
+    p.lm = __fadd_rn(p.lm, lp);
+    p.nw += 1;
+    p.state = next;
+    p.node = 0;
+  }
+  return p;
+}
+
+// p as a complete hypothesis, (lp, next) being its close pair.  -> false: no hypothesis (lexicon_only and the pending node
+// ends no word)
+__device__ __forceinline__ bool finish(const WordLm& g, WordPos& p, float lp, int next, bool eos_term) {
+  if (p.node != 0) {
+    if (next < 0) return false;
+    p = after_token(g, p, g.space, lp, next);
+  }
+  if (eos_term) {
+    float el;
+    int en;
+    lookup(g, p.state, g.eos, el, en);
+    p.lm = __fadd_rn(p.lm, el);
+  }
+  return true;
 }
 
 }  // namespace wlm

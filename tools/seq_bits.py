@@ -1,4 +1,5 @@
-"""Bit-level record of the sequence kernels (csrc/ctc.hip, ctc_align.hip, ctc_beam.hip, ctc_prefix.hip, beam.hip, mwer.hip):
+"""Bit-level record of the sequence kernels (csrc/ctc.hip, ctc_align.hip, ctc_beam.hip, ctc_prefix.hip, beam.hip, mwer.hip,
+rnnt_beam.hip; the searches also with an n-gram LM and with a lexicon and word LM inside):
 
     python tools/seq_bits.py dump OUT.npz         fixed-seed inputs through every kernel, instantiation and switch -> all outputs
     python tools/seq_bits.py compare A.npz B.npz  exit 1 unless both hold the same arrays, equal as raw 32-bit words
@@ -12,6 +13,25 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+WORDS = ((2,), (3,), (4, 2), (2, 3, 4))      # the lexicon, <space> = 1: the nodes "4" and "2 3" end no word
+
+
+def _char_lm(V):
+    """A token 3-gram (bos 1, eos 2) estimated from fixed-seed text over a few labels of a vocabulary of V."""
+    from ngram import NgramLM
+    rs = np.random.RandomState(11)
+    return NgramLM.estimate([[int(t) for t in rs.randint(3, min(V, 12), rs.randint(2, 12))] for _ in range(200)], 3, V, 1, 2)
+
+
+def _word_lm(V):
+    """A word 3-gram over WORDS, estimated from fixed-seed word sequences, behind their lexicon in a vocabulary of V."""
+    from ngram import NgramLM
+    from word_lm import Lexicon, WordLM, W_FIRST
+    rs = np.random.RandomState(12)
+    text = [[W_FIRST + int(w) for w in rs.randint(0, len(WORDS), rs.randint(1, 8))] for _ in range(100)]
+    return WordLM(NgramLM.estimate(text, 3, W_FIRST + len(WORDS), 1, 2), Lexicon(list(WORDS), None, 1, None, None, V=V))
 
 
 def dump(path):
@@ -55,9 +75,47 @@ def dump(path):
     for V in (2, 70):
         keep("greedy_v%d" % V, *ops.ctc_greedy(logits(3, 65, V), i32((65, 40, 1))))
     # prefix beam search: one wave, four waves, tokens behind the staged ones, history in the workspace, an empty utterance
-    for name, B, T, V, K, flens in [("k1", 2, 20, 5, 1, (20, 13)), ("k4", 2, 20, 5, 4, (20, 13)), ("v300", 2, 20, 300, 4, (20, 0)),
-                                    ("v1100", 1, 6, 1100, 2, (6,)), ("k16", 1, 300, 5, 16, (300,))]:
-        keep("ctc_beam_" + name, *ops.ctc_beam(logits(B, T, V), i32(flens), K))
+    # - and the same searches with the n-gram LM and with the lexicon and word LM inside: eos term on / off, lexicon_only off / on
+    rng2 = np.random.RandomState(20250307)                          # (the later cases' inputs stay what they were)
+    beams = [("k1", 2, 20, 5, 1, (20, 13)), ("k4", 2, 20, 5, 4, (20, 13)), ("v300", 2, 20, 300, 4, (20, 0)),
+             ("v1100", 1, 6, 1100, 2, (6,)), ("k16", 1, 300, 5, 16, (300,)), ("k2", 2, 20, 5, 2, (20, 13)), ("k8", 2, 20, 5, 8, (20, 13))]
+    full = cut = 0                                                  # lexicon_only: utterances that kept K hypotheses / lost some
+    for name, B, T, V, K, flens in beams:
+        z = logits(B, T, V) if name not in ("k2", "k8") else torch.from_numpy((3.0 * rng2.randn(B, T, V)).astype(np.float32)).to(dev)
+        keep("ctc_beam_" + name, *ops.ctc_beam(z, i32(flens), K))
+        char, word = _char_lm(V), _word_lm(V)
+        for eos in (1, 0):
+            keep("ctc_beam_lm_%s_e%d" % (name, eos), *ops.ctc_beam(z, i32(flens), K, ngram=char, ngram_weight=0.6, ngram_bonus=0.4,
+                                                                    eos_term=bool(eos)))
+            for lo in (0, 1):
+                res = ops.ctc_beam(z, i32(flens), K, word_lm=word, word_lm_weight=0.6, word_bonus=0.4, eos_term=bool(eos),
+                                   lexicon_only=bool(lo))
+                keep("ctc_beam_wlm_%s_e%d_lo%d" % (name, eos, lo), *res)
+                n_hyp = (res[1] >= 0).sum(1).tolist()
+                if not lo:                                          # the scorer on the search's own list, unused slots included
+                    keep("word_lm_score_%s_e%d" % (name, eos), *ops.word_lm_score(word, res[0].view(B * K, T), res[1].view(-1),
+                                                                                  eos_term=bool(eos), per_word=True))
+                    whole = n_hyp
+                else:
+                    # utterances of at least 13 frames and K <= 8 whose free search filled its K slots: the walk of the lexicon
+                    # (three first letters, each with a continuation or <space>) fills a beam of 8 within two frames, so a
+                    # list shorter than K there is the tail's doing - an entry whose pending node ends no word
+                    seen = [n for n, w_, f in zip(n_hyp, whole, flens) if f >= 13 and K <= 8 and w_ == K]
+                    full, cut = full + sum(n == K for n in seen), cut + sum(n < K for n in seen)
+    out["ctc_beam_lexicon_only_counts.0"] = np.array([full, cut], dtype=np.uint32)
+    # the transducer search: plain, n-gram and word LM, one wave of entries and several, a short and an empty utterance
+    B, T, L, J, V, E = 3, 6, 5, 64, 34, 8
+    r = lambda *s, k=1.0: torch.from_numpy((k * rng2.randn(*s)).astype(np.float32)).to(dev)     # noqa: E731
+    head = (r(B, T, J), i32((6, 3, 0)), r(4 * E, 2 * E, k=0.5), r(4 * E, k=0.1), r(J, E, k=0.5), r(V, J, k=0.5), r(V, k=0.1), r(V, E), 33)
+    char, word = _char_lm(V), _word_lm(V)
+    for K in (1, 4, 16):
+        keep("rnnt_beam_k%d" % K, *ops.rnnt_beam(*head, K, L))
+        for eos in (1, 0):
+            keep("rnnt_beam_lm_k%d_e%d" % (K, eos), *ops.rnnt_beam(*head, K, L, ngram=char, ngram_weight=0.6, ngram_bonus=0.4,
+                                                                    eos_term=bool(eos)))
+            for lo in (0, 1):
+                keep("rnnt_beam_wlm_k%d_e%d_lo%d" % (K, eos, lo), *ops.rnnt_beam(
+                    *head, K, L, word_lm=word, word_lm_weight=0.6, word_bonus=0.4, eos_term=bool(eos), lexicon_only=bool(lo)))
     # BeamSearch.select / select_lm / select_ctc with the prefix scorer beside it: init, then three steps
     B, V, Tp, eos = 2, 70, 70, 1
     for K in (1, 4):
@@ -105,6 +163,10 @@ def compare(pa, pb):
         if not same:
             bad.append(k)
     cases = sorted({k.split(".")[0] for k in a.files})
+    for name, f in (("A", a), ("B", b)):
+        if "ctc_beam_lexicon_only_counts.0" in f.files:
+            print("%s: ctc_beam with lexicon_only: %d utterances kept K hypotheses, %d lost entries in the tail"
+                  % ((name,) + tuple(f["ctc_beam_lexicon_only_counts.0"])))
     print("%d cases, %d arrays: %s" % (len(cases), len(a.files), "PASS" if not bad else "FAIL (%s)" % ", ".join(bad)))
     return 1 if bad else 0
 
