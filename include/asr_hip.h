@@ -1545,6 +1545,65 @@ int asr_transducer_wbeam_backtrace_f32(const asr_transducer_beam_t* a, const asr
                                        int32_t* hyp_len, float* score, float* rnnt_score, float* lm_score, int32_t* n_words,
                                        asr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * An n-gram LM or a lexicon with a word-level LM inside the attention beam search (csrc/beam.hip, csrc/word_lm.h; DESIGN
+ * 4.31).  Not reference operators.  Four entries added to ABI version 8 WITHOUT a version change: additive - asr_beam_t, the
+ * select, reorder and backtrack entries above and the kernels they launch are unchanged.
+ * The search is the one of asr_beam_select_f32 / _lm_f32 / _ctc_f32 with one more term.  Every beam row carries, beside its
+ * running score, the position of its token sequence in the LM - held in the caller's extra workspace, like the parts of the
+ * finished entries:
+ *     p->scores   base: the score the search carries without this LM (attention, CTC prefix and judge terms)
+ *     n-gram      the automaton state (lm_start for the empty sequence), lm - the fp32 sum of lm_logp[state][c] over the tokens
+ *                 in order, every addition rounded on its own - and len, the tokens that are not <EOS>
+ *     word LM     the trie node of the pending word, the word state, lm over the COMPLETED words and their number nw, moving
+ *                 as asr_word_lm_score_f32's walk does (a <space> behind a pending word closes it)
+ * A candidate (k, v): base' is the candidate expression of the variant (plain, LM, CTC) operation for operation; lm', len' /
+ * nw' are those of the extended sequence, <EOS> taking the end term (n-gram: lm + lm_logp[state][eos]; word LM: the pending
+ * word closes, then the lookup of the LM's `eos` word).  It ranks by
+ *     (base' + weight lm') + bonus len'      (word LM: bonus nw')       fp32, each of the four operations rounded on its own
+ * and with lexicon_only (word LM) a token that leaves the trie, and a <space> or <EOS> whose pending node ends no word, rank
+ * -inf.  The first 2K by rank (ties: the lower flat index), the <EOS> rule, the finishing at t = L-1 and the done flags are
+ * asr_beam_select_f32's on the rank; live beams that finish as they stand at t = L-1 take the end term, but no <EOS> token (and
+ * with lexicon_only are dropped where the pending node ends no word).  fin_score holds the rank of a finished entry.
+ * weight = bonus = 0 (lexicon_only off): rank = base', and every output word of the search equals the one without this LM.
+ * lm_score of a hypothesis is asr_ngram_score_f32 (eos = p->eos) / asr_word_lm_score_f32 (eos_term 1) of its tokens, bit for
+ * bit, n_words the latter's count.
+ *   asr_beam_tlm_t           the LM of the call: kind, its tables (n-gram: lm_logp / lm_next [lm_states][V] as
+ *                            asr_ctc_beam_lm_f32 takes them; word LM: an asr_word_lm_t with V = p->V), weight, bonus (finite:
+ *                            ASR_E_ARG), lexicon_only, and the extra workspace ws (4-byte aligned, at least
+ *                            asr_beam_tlm_ws_bytes; else ASR_E_ARG).  lm_states V > INT_MAX, lm_start outside the states, or a
+ *                            word LM over another vocabulary: ASR_E_SHAPE.  All checks come before any launch.
+ *   asr_beam_tlm_ws_bytes    plain integers, no GPU: 4 (4 round64(B K) + 3 round64(B ASR_BEAM_FCAP)) - independent of L.
+ *   asr_beam_tlm_init_f32    the position of the empty sequence in every beam row.  One launch, before step 0.
+ *   asr_beam_select_tlm_f32  the select of step t: lm_logits NULL: no judge LM; ctc_weight 0: no CTC term (psi is not read),
+ *                            as asr_beam_select_ctc_f32.  One thread per live entry looks up its close pair and end term up
+ *                            front (LDS); the candidate loop reads LDS and the entry's table row / trie_next row; the thread
+ *                            that walks the ranked candidates writes the new positions in place from the staged copies, so
+ *                            asr_beam_reorder_f32 / _lm_f32 and asr_ctc_prefix_advance_f32 are used as they are.  One launch.
+ *   asr_beam_backtrack_tlm   asr_beam_backtrack, and in the same order att_score fp32 [B][K] (base), lm_score fp32 [B][K] and
+ *                            n int32 [B][K] (len / n_words); -inf, -inf, -1 for a rank without a hypothesis.
+ * No floating-point atomics, no host synchronisation, no allocation: the same bits in every run.
+ * ------------------------------------------------------------------------------------- */
+#define ASR_BEAM_TLM_NGRAM 1
+#define ASR_BEAM_TLM_WORD 2
+typedef struct {
+  int kind;                       /* ASR_BEAM_TLM_NGRAM or ASR_BEAM_TLM_WORD */
+  int lm_states, lm_start;        /* n-gram */
+  const float* lm_logp;
+  const int32_t* lm_next;
+  const asr_word_lm_t* word_lm;   /* word LM */
+  float weight, bonus;
+  int lexicon_only;
+  void* ws;
+  int64_t ws_bytes;
+} asr_beam_tlm_t;
+int asr_beam_tlm_ws_bytes(int B, int K, int64_t* ws_bytes);
+int asr_beam_tlm_init_f32(const asr_beam_t* p, const asr_beam_tlm_t* lm, asr_stream_t stream);
+int asr_beam_select_tlm_f32(const asr_beam_t* p, const asr_beam_tlm_t* lm, const float* lm_logits, float lm_weight,
+                            const float* psi, const float* psi_prev, float ctc_weight, int t, asr_stream_t stream);
+int asr_beam_backtrack_tlm(const asr_beam_t* p, const asr_beam_tlm_t* lm, float length_penalty, int32_t* tokens, float* scores,
+                           int32_t* lengths, float* att_score, float* lm_score, int32_t* n, asr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

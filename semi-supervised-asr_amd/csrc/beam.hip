@@ -11,10 +11,16 @@
 // to every candidate, and beam_reorder_lm gathers the LM's h / c of every layer (and the decoder's state) in one launch.
 // With the CTC prefix score (joint CTC-attention decoding; csrc/ctc_prefix.hip computes psi) the select kernel's
 // CTC variants rank score + (1 - w) logp + w (psi - psi_prev) (+ lm_weight * logp_lm).
+// With an n-gram automaton or a lexicon and word-level LM inside the search beam_select_tlm, a sibling of the
+// select kernel on the same list helpers, ranks (base' + weight lm') + bonus len' (word LM: nw') where base' is the variant's
+// candidate above: scores keeps base, the LM position of every beam row and the parts of the finished entries live in the
+// caller's extra workspace, one thread per live entry does the word LM's lookups up front, and the walker thread writes the
+// new positions in place - the reorder kernels are used as they are.  The plain select's instantiations are untouched.
 // And once at the end
 //   beam_backtrack  one workgroup per utterance: rank the finished hypotheses, follow the backpointers into token rows.
 #include <float.h>
 #include "seq_common.h"
+#include "word_lm.h"
 
 namespace {
 
@@ -153,6 +159,304 @@ __global__ __launch_bounds__(BEAM_NT) void beam_select_kernel(asr_beam_t p, int 
   }
 }
 
+// ---- an n-gram or a word-level LM inside the search ----------------------------------------------------------
+// The caller's extra workspace beside asr_beam_t: the LM position of every beam row and the parts of the finished entries.
+//   a / b     n-gram: the automaton state / unused;  word LM: the trie node of the pending word / the word state
+//   lm, n     the LM's fp32 sum;  n-gram: the non-<EOS> tokens (len);  word LM: the completed words (nw)
+constexpr int TLM_NGRAM = 1, TLM_WORD = 2;
+struct BeamTlm {
+  const float* logp;       // n-gram: [S][V]
+  const int32_t* next;
+  int start;
+  wlm::WordLm w;           // word LM
+  float weight, bonus;
+  bool lexicon_only;
+  int32_t *a, *b, *n;      // [B*K] positions
+  float* lm;
+  float *fin_base, *fin_lm;   // [B][BEAM_FCAP] parts of the finished entries (p.fin_score holds their rank)
+  int32_t* fin_n;
+};
+
+inline int64_t tlm_round64(int64_t n) { return (n + 63) & ~(int64_t)63; }
+inline int64_t tlm_ws_bytes(int B, int K) { return 4 * (4 * tlm_round64((int64_t)B * K) + 3 * tlm_round64((int64_t)B * BEAM_FCAP)); }
+
+// Today's candidate expression of the active variant, with the bits of the existing instantiations.  The rounded intrinsics
+// are plain operators to this compiler, and beam_select_kernel's loop compiles to: the judge's product fused into its sum
+// where the judge is the only extra term; no fusion with the CTC terms alone; with both, only (1 - w) logp fused into score.
+// The same is spelled out here with contraction off, so that the candidate loop and the second pass over the winners agree
+// and zero weights reproduce the search without this LM (tests/test_beam_ngram_gpu.py holds both).
+template <bool LM, bool CTC>
+__device__ __forceinline__ float beam_base(float sc, float x, float m, float ls, float lx, float lmm, float lml, float lmw,
+                                           float px, float pprev, float omw, float cw) {
+#pragma clang fp contract(off)
+  const float lp = (x - m) - ls;
+  float c;
+  if (CTC) {
+    const float a = omw * lp;
+    const float d = px - pprev;
+    const float e = cw * d;
+    c = LM ? __builtin_fmaf(omw, lp, sc) : sc + a;
+    c = c + e;
+  } else {
+    c = sc + lp;
+  }
+  if (LM) {
+    const float llp = (lx - lmm) - lml;
+    const float f = lmw * llp;
+    c = CTC ? c + f : __builtin_fmaf(lmw, llp, c);
+  }
+  return c;
+}
+
+// lm_rank's expression, (base + weight lm) + bonus n, with every one of the four operations rounded on its own: the rounded
+// intrinsics are plain operators to this compiler, so the contraction into a fused multiply-add is switched off here
+__device__ __forceinline__ float tlm_rank(float base, float lm, int n, float weight, float bonus) {
+#pragma clang fp contract(off)
+  const float wl = weight * lm;
+  const float s = base + wl;
+  const float bn = bonus * (float)n;
+  return s + bn;
+}
+
+// the staged position of a live entry (LDS), with what one thread looked up for it up front
+struct TlmStage {
+  int a, b, n;             // the old position
+  float lm;
+  float clp;               // word LM: the close pair of the pending word ...
+  int cnext;
+  float e_lm;              // ... and the entry as a complete hypothesis: lm, words, and whether it is one (lexicon_only)
+  int e_n, e_ok;
+};
+
+// lm', n' and validity of candidate v from the staged entry.  n-gram: one read of the entry's table row; word LM: LDS only,
+// and with lexicon_only one read of the entry's trie_next row.
+template <int KIND>
+__device__ __forceinline__ bool tlm_candidate(const BeamTlm& g, const TlmStage& s, int v, int V, int eos, float& lm, int& n) {
+  if constexpr (KIND == TLM_NGRAM) {
+    lm = __fadd_rn(s.lm, g.logp[(int64_t)s.a * V + v]);
+    n = s.n + (v != eos ? 1 : 0);
+    return true;
+  } else {
+    if (v == eos) {
+      lm = s.e_lm, n = s.e_n;
+      return s.e_ok != 0;
+    }
+    lm = s.lm, n = s.n;
+    if (v == g.w.space) {
+      if (s.a != 0) {
+        if (s.cnext < 0) return false;                      // lexicon_only: the pending node ends no word
+        lm = __fadd_rn(s.lm, s.clp), n = s.n + 1;
+      }
+      return true;
+    }
+    if (g.lexicon_only) return wlm::trie_step(g.w, s.a, v) >= 0;
+    return true;
+  }
+}
+
+template <int M, bool LM, bool CTC, int KIND>
+__global__ __launch_bounds__(BEAM_NT) void beam_select_tlm_kernel(asr_beam_t p, int t, const float* __restrict__ lm_logits,
+                                                                  float lmw, beam_ctc_args<CTC> ca, BeamTlm g) {
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int K = p.K, V = p.V, B = p.B;
+  if (p.done[b]) return;                                   // finished utterances are left untouched
+  __shared__ float s_score[BEAM_KMAX], s_max[BEAM_KMAX], s_lsum[BEAM_KMAX];
+  __shared__ float s_lmmax[LM ? BEAM_KMAX : 1], s_lmlsum[LM ? BEAM_KMAX : 1];
+  __shared__ TlmStage s_pos[BEAM_KMAX];
+  __shared__ float red_v[2][BEAM_WAVES];
+  __shared__ int red_i[2][BEAM_WAVES];
+  __shared__ float top_v[2 * BEAM_KMAX];
+  __shared__ int top_i[2 * BEAM_KMAX];
+  // the parts and the new position of every ranked candidate, and the same as a hypothesis finished as it stands (t = L-1)
+  __shared__ float top_base[2 * BEAM_KMAX], top_lm[2 * BEAM_KMAX], top_erank[2 * BEAM_KMAX], top_elm[2 * BEAM_KMAX];
+  __shared__ int top_n[2 * BEAM_KMAX], top_a[2 * BEAM_KMAX], top_b[2 * BEAM_KMAX], top_en[2 * BEAM_KMAX], top_eok[2 * BEAM_KMAX];
+  __shared__ int s_ntop, live_r[BEAM_KMAX];
+  if (tid < K) {
+    const float sc = p.scores[(int64_t)b * K + tid];
+    s_score[tid] = sc;
+    if (sc != -INFINITY) {                                  // one thread per live entry: its position, its lookups
+      const int64_t r = (int64_t)b * K + tid;
+      TlmStage s;
+      s.a = g.a[r], s.b = 0, s.n = g.n[r], s.lm = g.lm[r];
+      s.clp = 0.f, s.cnext = 0, s.e_lm = 0.f, s.e_n = 0, s.e_ok = 1;
+      if constexpr (KIND == TLM_WORD) {
+        s.b = g.b[r];
+        wlm::close_pair(g.w, s.a, s.b, g.lexicon_only, s.clp, s.cnext);
+        wlm::WordPos q{s.a, s.b, s.lm, s.n};
+        s.e_ok = wlm::finish(g.w, q, s.clp, s.cnext, true) ? 1 : 0;
+        s.e_lm = q.lm, s.e_n = q.nw;
+      }
+      s_pos[tid] = s;
+    }
+  }
+  __syncthreads();
+
+  // log-softmax statistics of every live beam's row: max and log(sum exp(x - max)), one wave per row
+  const float* lg = p.logits + (int64_t)b * K * V;
+  for (int k = wave; k < K; k += BEAM_WAVES) {
+    if (s_score[k] == -INFINITY) continue;                 // wave-uniform
+    float m, s;
+    wave_row_max_sumexp(lg + (int64_t)k * V, V, lane, m, s);
+    if (lane == 0) { s_max[k] = m; s_lsum[k] = logf(s); }
+    if (LM) {
+      wave_row_max_sumexp(lm_logits + ((int64_t)b * K + k) * V, V, lane, m, s);
+      if (lane == 0) { s_lmmax[k] = m; s_lmlsum[k] = logf(s); }
+    }
+  }
+  __syncthreads();
+
+  // every thread keeps its best M candidates by RANK (desc, flat index k*V+v asc on ties), visiting flat indices in
+  // increasing order
+  float lv[M];
+  int li[M];
+  top_clear(lv, li);
+  for (int k = 0; k < K; ++k) {
+    const float sc = s_score[k];
+    if (sc == -INFINITY) continue;
+    const float m = s_max[k], ls = s_lsum[k];
+    const float* row = lg + (int64_t)k * V;
+    const float* lrow = LM ? lm_logits + ((int64_t)b * K + k) * V : nullptr;
+    const float lmm = LM ? s_lmmax[k] : 0.f, lml = LM ? s_lmlsum[k] : 0.f;
+    const float* prow = nullptr;
+    float pprev = 0.f, omw = 0.f, cw = 0.f;
+    if constexpr (CTC) {
+      prow = ca.psi + ((int64_t)b * K + k) * V;
+      pprev = ca.psi_prev[b * K + k], cw = ca.w, omw = __fsub_rn(1.f, cw);
+    }
+    const TlmStage& st = s_pos[k];
+    for (int v = tid; v < V; v += BEAM_NT) {
+      const float base = beam_base<LM, CTC>(sc, row[v], m, ls, LM ? lrow[v] : 0.f, lmm, lml, lmw, CTC ? prow[v] : 0.f, pprev,
+                                            omw, cw);
+      float lm;
+      int n;
+      const bool ok = tlm_candidate<KIND>(g, st, v, V, p.eos, lm, n);
+      top_insert(lv, li, ok ? tlm_rank(base, lm, n, g.weight, g.bonus) : -INFINITY, k * V + v);
+    }
+  }
+
+  // merge: 2K rounds of a workgroup arg-best over the list heads; the owner of the winner pops its head
+  const int want = 2 * K;
+  int ntop = 0;
+  for (int r = 0; r < want; ++r) {
+    float v;
+    int i;
+    top_round(lv[0], li[0], red_v[r & 1], red_i[r & 1], BEAM_WAVES, v, i);
+    if (v == -INFINITY) break;                              // fewer than 2K finite candidates (uniform)
+    top_pop_if_head(lv, li, i);
+    if (tid == 0) { top_v[r] = v; top_i[r] = i; }
+    ntop = r + 1;
+  }
+  if (tid == 0) s_ntop = ntop;
+  __syncthreads();
+
+  // one thread per ranked candidate forms its parts again (the same operations on the same operands: the same bits) and the
+  // position behind it; at t = L-1 also what it is as a hypothesis that finishes as it stands
+  if (tid < ntop) {
+    const int idx = top_i[tid];
+    const int k = idx / V, v = idx - k * V;
+    const TlmStage st = s_pos[k];
+    const int64_t rk = (int64_t)b * K + k;
+    float pprev = 0.f, omw = 0.f, cw = 0.f, px = 0.f, lx = 0.f;
+    if constexpr (CTC) px = ca.psi[rk * V + v], pprev = ca.psi_prev[rk], cw = ca.w, omw = __fsub_rn(1.f, cw);
+    if (LM) lx = lm_logits[rk * V + v];
+    const float base = beam_base<LM, CTC>(s_score[k], lg[(int64_t)k * V + v], s_max[k], s_lsum[k], lx, LM ? s_lmmax[k] : 0.f,
+                                          LM ? s_lmlsum[k] : 0.f, lmw, px, pprev, omw, cw);
+    float lm;
+    int n;
+    tlm_candidate<KIND>(g, st, v, V, p.eos, lm, n);
+    top_base[tid] = base, top_lm[tid] = lm, top_n[tid] = n;
+    int na = 0, nb = 0, eok = 1, en = n;
+    float elm = lm;
+    if (v != p.eos) {
+      if constexpr (KIND == TLM_NGRAM) {
+        na = g.next[(int64_t)st.a * V + v];
+        if (t == p.L - 1) elm = __fadd_rn(lm, g.logp[(int64_t)na * V + p.eos]);
+      } else {
+        const wlm::WordPos q = wlm::after_token(g.w, wlm::WordPos{st.a, st.b, st.lm, st.n}, v, st.clp, st.cnext);
+        na = q.node, nb = q.state;
+        if (t == p.L - 1) {
+          float lp;
+          int nx;
+          wlm::close_pair(g.w, q.node, q.state, g.lexicon_only, lp, nx);
+          wlm::WordPos e = q;
+          eok = wlm::finish(g.w, e, lp, nx, true) ? 1 : 0;
+          elm = e.lm, en = e.nw;
+        }
+      }
+    }
+    top_a[tid] = na, top_b[tid] = nb;
+    top_elm[tid] = elm, top_en[tid] = en, top_eok[tid] = eok;
+    top_erank[tid] = tlm_rank(base, elm, en, g.weight, g.bonus);
+  }
+  __syncthreads();
+  if (tid != 0) return;
+
+  // the fairseq walk over the ranked candidates (a handful of entries: one thread); scores keeps base, the finished list
+  // the rank and the parts
+  ntop = s_ntop;
+  const int64_t hb = ((int64_t)t * B + b) * K;
+  int nf = p.nfin[b], nlive = 0;
+  for (int r = 0; r < ntop; ++r) {
+    const int idx = top_i[r];
+    const int k = idx / V, v = idx - k * V;
+    if (v == p.eos) {
+      if (r < K) {
+        const int64_t fo = (int64_t)b * BEAM_FCAP + nf;
+        int4* f = reinterpret_cast<int4*>(p.fin) + fo;
+        *f = make_int4(t, k, t + 1, 1);
+        p.fin_score[fo] = top_v[r];
+        g.fin_base[fo] = top_base[r], g.fin_lm[fo] = top_lm[r], g.fin_n[fo] = top_n[r];
+        ++nf;
+      }
+    } else if (nlive < K) {
+      const int64_t o = (int64_t)b * K + nlive;
+      p.tok_hist[hb + nlive] = v;
+      p.bp_hist[hb + nlive] = k;
+      p.scores[o] = top_base[r];
+      g.a[o] = top_a[r], g.lm[o] = top_lm[r], g.n[o] = top_n[r];
+      if constexpr (KIND == TLM_WORD) g.b[o] = top_b[r];
+      live_r[nlive] = r;
+      ++nlive;
+    }
+  }
+  for (int j = nlive; j < K; ++j) {                         // dead slots: a valid token and predecessor, score -inf
+    p.tok_hist[hb + j] = p.eos;
+    p.bp_hist[hb + j] = 0;
+    p.scores[(int64_t)b * K + j] = -INFINITY;
+  }
+  if (t == p.L - 1 && nf < K) {                             // max_dec_timesteps: the live beams finish as they stand,
+    for (int j = 0; j < nlive; ++j) {                       // with the end term an <EOS> would give and no <EOS> token
+      const int r = live_r[j];
+      if (!top_eok[r]) continue;                            // lexicon_only: the pending node ends no word
+      const int64_t fo = (int64_t)b * BEAM_FCAP + nf;
+      int4* f = reinterpret_cast<int4*>(p.fin) + fo;
+      *f = make_int4(t, j, t + 1, 0);
+      p.fin_score[fo] = top_erank[r];
+      g.fin_base[fo] = top_base[r], g.fin_lm[fo] = top_elm[r], g.fin_n[fo] = top_en[r];
+      ++nf;
+    }
+  }
+  p.nfin[b] = nf;
+  if (nf >= K || t == p.L - 1 || nlive == 0) {
+    p.done[b] = 1;
+    atomicAdd(p.ndone, 1);
+  }
+}
+
+// the position of the empty sequence in every beam row
+template <int KIND>
+__global__ __launch_bounds__(BEAM_NT) void beam_tlm_init_kernel(int R, BeamTlm g) {
+  const int r = blockIdx.x * BEAM_NT + threadIdx.x;
+  if (r >= R) return;
+  g.lm[r] = 0.f, g.n[r] = 0;
+  if constexpr (KIND == TLM_NGRAM) {
+    g.a[r] = g.start, g.b[r] = 0;
+  } else {
+    const wlm::WordPos q = wlm::start_pos(g.w);
+    g.a[r] = q.node, g.b[r] = q.state;
+  }
+}
+
 // the decoder state of beam row `row` (not done): gathered from row `src`, with the embedding of token `tok`
 __device__ __forceinline__ void beam_reorder_row(const asr_beam_state_t& s, int row, int src, int tok) {
   const int DO = s.D + s.O;
@@ -199,8 +503,21 @@ __global__ __launch_bounds__(BEAM_NT) void beam_reorder_lm_kernel(asr_beam_t p, 
   }
 }
 
+// PARTS: the parts of the finished entries (a search with an n-gram or word LM inside) follow the hypotheses
+// into the final order; without them the structure is empty and the kernel is the plain backtrack
+template <bool PARTS>
+struct beam_parts_args {
+  const float *fin_base, *fin_lm;   // [B][BEAM_FCAP]
+  const int32_t* fin_n;
+  float *out_base, *out_lm;         // [B][K]
+  int32_t* out_n;
+};
+template <>
+struct beam_parts_args<false> {};
+
+template <bool PARTS>
 __global__ __launch_bounds__(BEAM_NT) void beam_backtrack_kernel(asr_beam_t p, float alpha, int32_t* out_tok,
-                                                                 float* out_score, int32_t* out_len) {
+                                                                 float* out_score, int32_t* out_len, beam_parts_args<PARTS> pa) {
   const int b = blockIdx.x, tid = threadIdx.x, K = p.K, L = p.L;
   __shared__ int order[BEAM_FCAP];
   __shared__ float key[BEAM_FCAP];
@@ -228,9 +545,20 @@ __global__ __launch_bounds__(BEAM_NT) void beam_backtrack_kernel(asr_beam_t p, f
     if (r >= nf) {
       out_score[(int64_t)b * K + r] = -INFINITY;
       out_len[(int64_t)b * K + r] = 0;
+      if constexpr (PARTS) {
+        pa.out_base[(int64_t)b * K + r] = -INFINITY;
+        pa.out_lm[(int64_t)b * K + r] = -INFINITY;
+        pa.out_n[(int64_t)b * K + r] = -1;
+      }
       continue;
     }
     const int4 f = fin[order[r]];                          // (step, slot, length, ends with <EOS>)
+    if constexpr (PARTS) {
+      const int64_t fo = (int64_t)b * BEAM_FCAP + order[r];
+      pa.out_base[(int64_t)b * K + r] = pa.fin_base[fo];
+      pa.out_lm[(int64_t)b * K + r] = pa.fin_lm[fo];
+      pa.out_n[(int64_t)b * K + r] = pa.fin_n[fo];
+    }
     int s = f.x, j = f.y;
     if (f.w) {
       --s;                                                  // row[f.x] is the <EOS>; slot j is the beam at step f.x - 1
@@ -282,6 +610,57 @@ int check_beam_state(const asr_beam_t* p, int t, const asr_beam_state_t* s) {
   if (t < 0 || t >= p->L || s->D <= 0 || s->O < 0 || s->E <= 0 || s->Tp <= 0 || s->ldx < s->D + s->O + s->E)
     return ASR_E_ARG;
   if (s->x_src == s->x_dst || s->c_src == s->c_dst || s->w_src == s->w_dst) return ASR_E_ARG;   // a gather: out of place
+  return 0;
+}
+
+// the checks of an asr_beam_*_tlm call (before any launch), and the device's view of its LM and extra workspace
+int tlm_args(const asr_beam_t* p, const asr_beam_tlm_t* lm, bool need_logits, BeamTlm* g) {
+  int rc = check_beam(p, need_logits);
+  if (rc) return rc;
+  if (!lm || !lm->ws || !(fabsf(lm->weight) <= FLT_MAX) || !(fabsf(lm->bonus) <= FLT_MAX)) return ASR_E_ARG;
+  if (lm->ws_bytes < tlm_ws_bytes(p->B, p->K) || (((uintptr_t)lm->ws) & 3u)) return ASR_E_ARG;
+  *g = BeamTlm{};
+  if (lm->kind == ASR_BEAM_TLM_NGRAM) {
+    if (!lm->lm_logp || !lm->lm_next || lm->lm_states <= 0) return ASR_E_ARG;
+    if ((int64_t)lm->lm_states * p->V > INT_MAX || lm->lm_start < 0 || lm->lm_start >= lm->lm_states) return ASR_E_SHAPE;
+    g->logp = lm->lm_logp, g->next = lm->lm_next, g->start = lm->lm_start;
+  } else if (lm->kind == ASR_BEAM_TLM_WORD) {
+    rc = wlm::check_abi(lm->word_lm);
+    if (rc) return rc;
+    if (lm->word_lm->V != p->V) return ASR_E_SHAPE;
+    g->w = wlm::from_abi(*lm->word_lm);
+  } else {
+    return ASR_E_ARG;
+  }
+  g->weight = lm->weight, g->bonus = lm->bonus;
+  g->lexicon_only = lm->kind == ASR_BEAM_TLM_WORD && lm->lexicon_only != 0;
+  const int64_t n_bk = tlm_round64((int64_t)p->B * p->K), n_f = tlm_round64((int64_t)p->B * BEAM_FCAP);
+  g->a = (int32_t*)lm->ws;
+  g->b = g->a + n_bk;
+  g->n = g->b + n_bk;
+  g->lm = (float*)(g->n + n_bk);
+  g->fin_base = g->lm + n_bk;
+  g->fin_lm = g->fin_base + n_f;
+  g->fin_n = (int32_t*)(g->fin_lm + n_f);
+  return 0;
+}
+
+template <bool LM, bool CTC, int KIND>
+int beam_select_tlm_launch(const asr_beam_t* p, const float* lm_logits, float lmw, int t, hipStream_t stream, const BeamTlm& g,
+                           const float* psi, const float* psi_prev, float cw) {
+  const dim3 grid(p->B), block(BEAM_NT);
+  const int m = 2 * p->K;
+  beam_ctc_args<CTC> ca;
+  if constexpr (CTC) ca.psi = psi, ca.psi_prev = psi_prev, ca.w = cw;
+#define BEAM_SELECT(M_) \
+  hipLaunchKernelGGL((beam_select_tlm_kernel<M_, LM, CTC, KIND>), grid, block, 0, stream, *p, t, lm_logits, lmw, ca, g)
+  if (m <= 2) BEAM_SELECT(2);
+  else if (m <= 4) BEAM_SELECT(4);
+  else if (m <= 8) BEAM_SELECT(8);
+  else if (m <= 16) BEAM_SELECT(16);
+  else BEAM_SELECT(32);
+#undef BEAM_SELECT
+  ASR_CHECK_LAUNCH();
   return 0;
 }
 
@@ -343,8 +722,63 @@ extern "C" int asr_beam_backtrack(const asr_beam_t* p, float length_penalty, int
   int rc = check_beam(p, false);
   if (rc) return rc;
   if (!tokens || !scores || !lengths) return ASR_E_ARG;
-  hipLaunchKernelGGL(beam_backtrack_kernel, dim3(p->B), dim3(BEAM_NT), 0, (hipStream_t)stream_, *p, length_penalty,
-                     tokens, scores, lengths);
+  hipLaunchKernelGGL(beam_backtrack_kernel<false>, dim3(p->B), dim3(BEAM_NT), 0, (hipStream_t)stream_, *p, length_penalty,
+                     tokens, scores, lengths, beam_parts_args<false>());
+  ASR_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int asr_beam_tlm_ws_bytes(int B, int K, int64_t* ws_bytes) {
+  if (!ws_bytes || B <= 0) return ASR_E_ARG;
+  if (K < 1 || K > BEAM_KMAX) return ASR_E_SHAPE;
+  *ws_bytes = tlm_ws_bytes(B, K);
+  return 0;
+}
+
+extern "C" int asr_beam_tlm_init_f32(const asr_beam_t* p, const asr_beam_tlm_t* lm, asr_stream_t stream_) {
+  BeamTlm g;
+  const int rc = tlm_args(p, lm, false, &g);
+  if (rc) return rc;
+  const int R = p->B * p->K;
+  const dim3 grid((R + BEAM_NT - 1) / BEAM_NT), block(BEAM_NT);
+  if (lm->kind == ASR_BEAM_TLM_NGRAM) hipLaunchKernelGGL(beam_tlm_init_kernel<TLM_NGRAM>, grid, block, 0, (hipStream_t)stream_, R, g);
+  else hipLaunchKernelGGL(beam_tlm_init_kernel<TLM_WORD>, grid, block, 0, (hipStream_t)stream_, R, g);
+  ASR_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int asr_beam_select_tlm_f32(const asr_beam_t* p, const asr_beam_tlm_t* lm, const float* lm_logits, float lm_weight,
+                                       const float* psi, const float* psi_prev, float ctc_weight, int t, asr_stream_t stream_) {
+  BeamTlm g;
+  int rc = tlm_args(p, lm, true, &g);
+  if (rc) return rc;
+  if (t < 0 || t >= p->L || !(ctc_weight >= 0.f && ctc_weight <= 1.f)) return ASR_E_ARG;
+  const bool ctc = ctc_weight != 0.f;                      // at 0 psi is not read: the variant without it, as asr_beam_select_ctc_f32
+  if (ctc && (!psi || !psi_prev)) return ASR_E_ARG;
+  if (ctc && p->V < 3) return ASR_E_SHAPE;
+  hipStream_t stream = (hipStream_t)stream_;
+  const bool word = lm->kind == ASR_BEAM_TLM_WORD;
+#define TLM_SELECT(LM_, CTC_)                                                                                          \
+  (word ? beam_select_tlm_launch<LM_, CTC_, TLM_WORD>(p, lm_logits, lm_weight, t, stream, g, psi, psi_prev, ctc_weight) \
+        : beam_select_tlm_launch<LM_, CTC_, TLM_NGRAM>(p, lm_logits, lm_weight, t, stream, g, psi, psi_prev, ctc_weight))
+  if (ctc) rc = lm_logits ? TLM_SELECT(true, true) : TLM_SELECT(false, true);
+  else rc = lm_logits ? TLM_SELECT(true, false) : TLM_SELECT(false, false);
+#undef TLM_SELECT
+  return rc;
+}
+
+extern "C" int asr_beam_backtrack_tlm(const asr_beam_t* p, const asr_beam_tlm_t* lm, float length_penalty, int32_t* tokens,
+                                      float* scores, int32_t* lengths, float* att_score, float* lm_score, int32_t* n_out,
+                                      asr_stream_t stream_) {
+  BeamTlm g;
+  const int rc = tlm_args(p, lm, false, &g);
+  if (rc) return rc;
+  if (!tokens || !scores || !lengths || !att_score || !lm_score || !n_out) return ASR_E_ARG;
+  beam_parts_args<true> pa;
+  pa.fin_base = g.fin_base, pa.fin_lm = g.fin_lm, pa.fin_n = g.fin_n;
+  pa.out_base = att_score, pa.out_lm = lm_score, pa.out_n = n_out;
+  hipLaunchKernelGGL(beam_backtrack_kernel<true>, dim3(p->B), dim3(BEAM_NT), 0, (hipStream_t)stream_, *p, length_penalty,
+                     tokens, scores, lengths, pa);
   ASR_CHECK_LAUNCH();
   return 0;
 }

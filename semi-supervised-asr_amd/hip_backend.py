@@ -44,6 +44,7 @@ EXPORTS = (
     "asr_transducer_beam_backtrace_f32",
     "asr_transducer_wbeam_ws_bytes", "asr_transducer_wbeam_init_f32", "asr_transducer_wbeam_step_f32",
     "asr_transducer_wbeam_backtrace_f32",
+    "asr_beam_tlm_ws_bytes", "asr_beam_tlm_init_f32", "asr_beam_select_tlm_f32", "asr_beam_backtrack_tlm",
 )
 
 _lib = None
@@ -101,6 +102,13 @@ class Beam(ctypes.Structure):
     """asr_beam_t"""
     _fields_ = [(n, c_i) for n in ("B", "K", "V", "L", "eos")] + \
                [(n, c_p) for n in ("logits", "scores", "tok_hist", "bp_hist", "fin", "fin_score", "nfin", "done", "ndone")]
+
+
+class BeamTlm(ctypes.Structure):
+    """asr_beam_tlm_t"""
+    _fields_ = [("kind", c_i), ("lm_states", c_i), ("lm_start", c_i), ("lm_logp", c_p), ("lm_next", c_p),
+                ("word_lm", ctypes.POINTER(WordLmTable)), ("weight", c_f), ("bonus", c_f), ("lexicon_only", c_i), ("ws", c_p),
+                ("ws_bytes", c_i64)]
 
 
 class BeamState(ctypes.Structure):
@@ -338,6 +346,10 @@ def load():
     lib.asr_transducer_wbeam_init_f32.argtypes = wbeam + [c_i, c_p]
     lib.asr_transducer_wbeam_step_f32.argtypes = wbeam + [c_i, c_p]
     lib.asr_transducer_wbeam_backtrace_f32.argtypes = wbeam + [c_p] * 7
+    lib.asr_beam_tlm_ws_bytes.argtypes = [c_i, c_i, ctypes.POINTER(c_i64)]
+    lib.asr_beam_tlm_init_f32.argtypes = [ctypes.POINTER(Beam), ctypes.POINTER(BeamTlm), c_p]
+    lib.asr_beam_select_tlm_f32.argtypes = [ctypes.POINTER(Beam), ctypes.POINTER(BeamTlm), c_p, c_f, c_p, c_p, c_f, c_i, c_p]
+    lib.asr_beam_backtrack_tlm.argtypes = [ctypes.POINTER(Beam), ctypes.POINTER(BeamTlm), c_f] + [c_p] * 7
     lib.asr_mwer_fwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
     lib.asr_mwer_bwd_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_f, c_p, c_i64, c_p]
     lib.asr_dec_feedback_fwd.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_p, c_i64,
@@ -745,6 +757,88 @@ class BeamSearch:
         check(load().asr_beam_backtrack(ctypes.byref(self.struct), float(length_penalty), ptr(tokens), ptr(scores),
                                         ptr(lengths), stream()), "asr_beam_backtrack")
         return tokens, scores, lengths
+
+
+BEAM_TLM_NGRAM, BEAM_TLM_WORD = 1, 2     # ASR_BEAM_TLM_NGRAM, ASR_BEAM_TLM_WORD
+
+
+def beam_tlm_ws_bytes(B, K):
+    """asr_beam_tlm_ws_bytes on plain integers (no tensors, no GPU) -> the EXTRA workspace bytes of an attention beam search with
+    an n-gram or word LM inside: 4 (4 round64(B K) + 3 round64(B BEAM_FCAP)); UnsupportedShape for a beam outside
+    1 .. BEAM_KMAX."""
+    need = c_i64(0)
+    rc = load().asr_beam_tlm_ws_bytes(int(B), int(K), ctypes.byref(need))
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("beam_tlm: B %d, beam %d (beam 1 .. %d)" % (B, K, BEAM_KMAX))
+    check(rc, "asr_beam_tlm_ws_bytes")
+    return need.value
+
+
+class BeamTableLm:
+    """The n-gram automaton (ngram: the table on the device) or the lexicon and word LM (word_lm: word_lm.WordTable after
+    .to(device)) inside a BeamSearch (asr_beam_tlm_t, the asr_beam_*_tlm entries of csrc/beam.hip): candidates rank
+    by (base + weight lm) + bonus len (word LM: n_words), search.scores keeps base.  ws: the extra workspace (float32 or
+    int32, at least beam_tlm_ws_bytes bytes), the caller's; it holds the LM position of every beam row and the parts of the
+    finished entries.  init() before step 0, select() in place of the search's select / select_lm / select_ctc, backtrack()
+    in place of its backtrack: one launch each."""
+
+    def __init__(self, search, ws, ngram=None, word_lm=None, weight=0.0, bonus=0.0, lexicon_only=False):
+        if (ngram is None) == (word_lm is None):
+            raise ValueError("beam_tlm: one of ngram and word_lm")
+        self.search = search
+        t = BeamTlm()
+        if ngram is not None:
+            logp, nxt, S = _ngram_table(ngram, search.V, "beam_tlm")
+            t.kind, t.lm_states, t.lm_start, t.lm_logp, t.lm_next = BEAM_TLM_NGRAM, S, int(ngram.start), ptr(logp), ptr(nxt)
+            self._keep = (ngram, logp, nxt, ws)
+        else:
+            if word_lm.V != search.V:
+                raise UnsupportedShape("beam_tlm: the word LM spells in %d tokens, the search is over %d" % (word_lm.V, search.V))
+            self._word = _word_lm_table(word_lm, "beam_tlm")
+            t.kind, t.word_lm = BEAM_TLM_WORD, ctypes.pointer(self._word)
+            self._keep = (word_lm, ws)
+        need = beam_tlm_ws_bytes(search.B, search.K)
+        if not (ws.is_cuda and ws.is_contiguous() and ws.element_size() == 4 and ws.numel() * 4 >= need):
+            raise RuntimeError("beam_tlm: an extra workspace of %d bytes on the GPU" % need)
+        t.weight, t.bonus, t.lexicon_only = float(weight), float(bonus), 1 if lexicon_only else 0
+        t.ws, t.ws_bytes = ptr(ws), ws.numel() * 4
+        self.struct = t
+
+    def _run(self, rc, what):
+        if rc == ASR_E_SHAPE:
+            raise UnsupportedShape("%s: refused the sizes or the LM's tables" % what)
+        check(rc, what)
+
+    def init(self):
+        self._run(load().asr_beam_tlm_init_f32(ctypes.byref(self.search.struct), ctypes.byref(self.struct), stream()),
+                  "asr_beam_tlm_init_f32")
+
+    def select(self, logits, t, lm_logits=None, lm_weight=0.0, ctc=None, ctc_weight=0.0):
+        """The select of step t with the LM's term: lm_logits [B*K, V] (the judge, shallow fusion) and ctc (CtcPrefixState
+        after its score()) with ctc_weight as BeamSearch.select_lm / select_ctc take them."""
+        s = self.search
+        assert logits.is_contiguous() and tuple(logits.shape) == (s.B * s.K, s.V)
+        assert lm_logits is None or (lm_logits.is_contiguous() and lm_logits.shape == logits.shape)
+        assert ctc is None or tuple(ctc.psi.shape) == (s.B * s.K, s.V)
+        s.struct.logits = ptr(logits)
+        self._run(load().asr_beam_select_tlm_f32(ctypes.byref(s.struct), ctypes.byref(self.struct), ptr(lm_logits),
+                                                 float(lm_weight), ptr(ctc.psi) if ctc is not None else None,
+                                                 ptr(ctc.psi_prev) if ctc is not None else None,
+                                                 float(ctc_weight) if ctc is not None else 0.0, int(t), stream()),
+                  "asr_beam_select_tlm_f32")
+
+    def backtrack(self, length_penalty=0.0):
+        """-> BeamSearch.backtrack's tokens, scores (the rank / len**length_penalty), lengths, and in the same order att_score
+        fp32 [B, K] (base), lm_score fp32 [B, K], n int32 [B, K] (len, or n_words with a word LM; -1 without a hypothesis)."""
+        s = self.search
+        dev = s.scores.device
+        tokens = torch.empty(s.B, s.K, s.L, dtype=torch.int32, device=dev)
+        scores, att, lm = (torch.empty(s.B, s.K, dtype=torch.float32, device=dev) for _ in range(3))
+        lengths, n = (torch.empty(s.B, s.K, dtype=torch.int32, device=dev) for _ in range(2))
+        self._run(load().asr_beam_backtrack_tlm(ctypes.byref(s.struct), ctypes.byref(self.struct), float(length_penalty),
+                                                ptr(tokens), ptr(scores), ptr(lengths), ptr(att), ptr(lm), ptr(n), stream()),
+                  "asr_beam_backtrack_tlm")
+        return tokens, scores, lengths, att, lm, n
 
 
 class CtcPrefixState:

@@ -400,7 +400,8 @@ class Decoder(torch.nn.Module):
         return logits.transpose(0, 1), ys_log_probs, prediction, ws
 
     def recognize_beams(self, enc_pad, enc_len, max_dec_timesteps, topk, length_penalty=0.0, nbest=False, *, lm=None,
-                        lm_weight=0.0, ctc_logits=None, ctc_lens=None, ctc_decode_weight=0.0):
+                        lm_weight=0.0, ctc_logits=None, ctc_lens=None, ctc_decode_weight=0.0, ngram=None, ngram_weight=0.0,
+                        ngram_bonus=0.0, word_lm=None, word_lm_weight=0.0, word_bonus=0.0, lexicon_only=False):
         """Beam search with beam width topk (1..16) - model.py:369-406, which the reference left unfinished; the semantics
         are DESIGN 4.8's.  Eval arithmetic (no dropout, attention temperature 2.0), per utterance; hypotheses are ranked by
         score / len**length_penalty (score: the sum of the tokens' log-probabilities, <EOS> included).
@@ -410,6 +411,12 @@ class Decoder(torch.nn.Module):
         the valid frames) with ctc_decode_weight in (0, 1]: joint CTC-attention decoding - a token scores
         (1 - w) log p_asr + w (psi(g c) - psi(g)) with psi the CTC prefix score, computed on the device per step; it combines
         with the LM's term.  At 0 (or without the logits) the search is the one without it.
+        ngram (an ngram.NgramLM) or word_lm (a word_lm.WordLM), one of them: the n-gram automaton, or the lexicon
+        and the word-level LM, inside the search - a candidate ranks by (base + ngram_weight lm) + ngram_bonus len, with a word
+        LM (base + word_lm_weight lm) + word_bonus n_words, base being its score without this LM; lexicon_only keeps only
+        sequences of lexicon words (an utterance may then end without a hypothesis: a row of <EOS> at -inf).  Both combine with
+        lm and with ctc_decode_weight.  self.last_beams then keeps the device record of the call: dict(tokens int32 [B, topk, L],
+        lengths, scores, parts: dict(att, lm), n_words - with ngram the tokens without <EOS>); without them it is None.
         -> (prediction [B, L] int64, scores [B]): the best hypothesis, <EOS>-padded to L = max_dec_timesteps; with
         nbest=True all topk hypotheses, ranked: ([B, topk, L], [B, topk]).  topk = 1 is greedy decoding."""
         ctc_decode_weight = float(ctc_decode_weight)
@@ -423,6 +430,8 @@ class Decoder(torch.nn.Module):
                 raise ValueError("the CTC prefix score takes <PAD> = 0 as its blank; pad is %d" % self.pad)
             host = [int(n) for n in enc_len] if isinstance(enc_len, (list, tuple)) else None
             ctc_t = dict(logits=ctc_logits, frame_lens=ctc_lens, lens_host=host)
+        self.check_ngram(ngram)
+        self.check_word_lm(word_lm, ngram)
         lm_t = None
         if lm is not None:
             V = self.output_layer.weight.shape[0]
@@ -440,12 +449,19 @@ class Decoder(torch.nn.Module):
             Q = ops.linear(enc_pad, att.mlp_o.weight, None)
             w0 = AttLoc.initial_weights(enc_len, enc_pad.shape[1], enc_pad.device)
             cell = self.LSTMCell
-            tokens, scores, _ = ops.beam_search(
+            out = ops.beam_search(
                 P, Q, self.embedding.weight, cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh,
                 att.mlp_dec.weight, att.loc_conv.weight, att.mlp_att.weight, att.gvec.weight, att.mlp_o.bias,
                 self.output_layer.weight, self.output_layer.bias, w0, int(topk), int(max_dec_timesteps), self.bos,
                 self.eos, length_penalty=float(length_penalty), lm=lm_t, lm_weight=float(lm_weight), ctc=ctc_t,
-                ctc_weight=ctc_decode_weight)
+                ctc_weight=ctc_decode_weight, ngram=ngram, ngram_weight=float(ngram_weight), ngram_bonus=float(ngram_bonus),
+                word_lm=word_lm, word_lm_weight=float(word_lm_weight), word_bonus=float(word_bonus),
+                lexicon_only=bool(lexicon_only))
+            tokens, scores = out[0], out[1]
+            self.last_beams = None
+            if len(out) > 3:
+                self.last_beams = dict(tokens=tokens, lengths=out[2], scores=scores, parts=dict(att=out[3], lm=out[4]),
+                                       n_words=out[5])
             tokens = tokens.long()
         if nbest:
             return tokens, scores
@@ -879,8 +895,11 @@ class E2E(torch.nn.Module):
         return ops.ctc_loss(logits, self.encoder.enc2.last_lens_dev, labels, [int(y.size(0)) for y in ys], True)
 
     def recognize_beams(self, data, ilens, max_dec_timesteps, topk, length_penalty=0.0, nbest=False, *, lm=None,
-                        lm_weight=0.0, ctc_decode_weight=0.0):
-        """Encoder, then Decoder.recognize_beams (not a reference method).  ctc_decode_weight in (0, 1]: joint CTC-attention
+                        lm_weight=0.0, ctc_decode_weight=0.0, ngram=None, ngram_weight=0.0, ngram_bonus=0.0, word_lm=None,
+                        word_lm_weight=0.0, word_bonus=0.0, lexicon_only=False):
+        """Encoder, then Decoder.recognize_beams (not a reference method).  ngram / word_lm: the n-gram or the
+        lexicon and word-level LM inside the search, as the decoder's method takes them; self.last_beams keeps the device record
+        of such a call - dict(tokens, lengths, scores, parts: dict(att, lm), n_words) - in the style of last_rnnt_beams.  ctc_decode_weight in (0, 1]: joint CTC-attention
         decoding with the model's CTC head - it needs a model built with ctc_weight > 0; the weight of the
         training loss (self.ctc_weight) and this one are separate."""
         ctc_decode_weight = float(ctc_decode_weight)
@@ -888,6 +907,12 @@ class E2E(torch.nn.Module):
             raise ValueError("ctc_decode_weight must lie in [0, 1], got %r" % (ctc_decode_weight,))
         if ctc_decode_weight > 0 and not hasattr(self, "ctc_lo"):
             raise ValueError("ctc_decode_weight %g needs the CTC head: build the model with ctc_weight > 0" % ctc_decode_weight)
+        self.decoder.check_ngram(ngram)
+        self.decoder.check_word_lm(word_lm, ngram)
+        table_lm = {}
+        if ngram is not None or word_lm is not None:
+            table_lm = dict(ngram=ngram, ngram_weight=ngram_weight, ngram_bonus=ngram_bonus, word_lm=word_lm,
+                            word_lm_weight=word_lm_weight, word_bonus=word_bonus, lexicon_only=lexicon_only)
         if data.is_cuda:
             hb.upload_side_stream_for(data.shape[0] * data.shape[1])
         with torch.no_grad():
@@ -897,9 +922,11 @@ class E2E(torch.nn.Module):
                 bsz, frames, hid = enc_h.shape
                 ctc_logits = ops.linear(enc_h.reshape(bsz * frames, hid), self.ctc_lo.weight, self.ctc_lo.bias).view(bsz, frames, -1)
                 ctc_lens = self.encoder.enc2.last_lens_dev
-            return self.decoder.recognize_beams(enc_h, enc_lens, max_dec_timesteps, topk, length_penalty=length_penalty,
-                                                nbest=nbest, lm=lm, lm_weight=lm_weight, ctc_logits=ctc_logits,
-                                                ctc_lens=ctc_lens, ctc_decode_weight=ctc_decode_weight)
+            out = self.decoder.recognize_beams(enc_h, enc_lens, max_dec_timesteps, topk, length_penalty=length_penalty,
+                                               nbest=nbest, lm=lm, lm_weight=lm_weight, ctc_logits=ctc_logits,
+                                               ctc_lens=ctc_lens, ctc_decode_weight=ctc_decode_weight, **table_lm)
+            self.last_beams = self.decoder.last_beams
+            return out
 
     @property
     def time_reduction(self):

@@ -1442,7 +1442,8 @@ BEAM_POLL_STEPS = 8          # the host reads the all-done word of a beam search
 
 
 def beam_search(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo, w_out, b_out, w0, beam, L, bos, eos,
-                length_penalty=0.0, scaling=2.0, lm=None, lm_weight=0.0, ctc=None, ctc_weight=0.0):
+                length_penalty=0.0, scaling=2.0, lm=None, lm_weight=0.0, ctc=None, ctc_weight=0.0, ngram=None, ngram_weight=0.0,
+                ngram_bonus=0.0, word_lm=None, word_lm_weight=0.0, word_bonus=0.0, lexicon_only=False):
     """Beam search over the decoder (Decoder.recognize_beams, model.py:369-406; semantics in DESIGN 4.8), eval arithmetic.
 
     Inputs as decoder_sequence's for B utterances; the search runs B*beam rows (row b*beam + k).  Every step is
@@ -1461,7 +1462,17 @@ def beam_search(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo
     score + (1 - ctc_weight) logp + ctc_weight (psi - psi_prev) (+ lm_weight logp_lm), and the advance kernel beside the
     reorder: 2 launches on top of the plain (9) or the LM search (10 + n_layers), no host synchronisation added.  Without it
     (or with ctc_weight == 0) the search is the plain / LM one, launch for launch and bit for bit.
-    Returns tokens [B, beam, L] int32 (ranked, <EOS>-padded), scores [B, beam], lengths [B, beam]."""
+    ngram (an ngram.NgramLM or its table) or word_lm (a word_lm.WordLM or its table), one of them: the n-gram
+    automaton, or the lexicon and the word-level LM, inside the search.  Every beam row carries its LM position beside its score;
+    a candidate ranks by (base + ngram_weight lm) + ngram_bonus len - with a word LM (base + word_lm_weight lm) + word_bonus
+    n_words - where base is the candidate score of the search without it (the judge's and the CTC term included), lm the LM's
+    fp32 sum over the extended sequence (<EOS>: with the end-of-sentence term) and len its tokens without <EOS>; lexicon_only
+    keeps only sequences of lexicon words.  One init launch before the loop; the steps are the same launches as without it.
+    Returns tokens [B, beam, L] int32 (ranked, <EOS>-padded), scores [B, beam], lengths [B, beam] - and with ngram / word_lm
+    behind them att_score [B, beam] (base), lm_score [B, beam] (ops.ngram_score / ops.word_lm_score of the hypothesis, with the
+    end term, bit for bit) and n [B, beam] int32 (len, or n_words)."""
+    if ngram is not None and word_lm is not None:
+        raise ValueError("ngram and word_lm are two LMs for one search: pass one of them")
     dev = P.device
     B, Tp, A = P.shape
     O = Q.shape[2]
@@ -1484,6 +1495,15 @@ def beam_search(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo
                          % (lm["w_out"].shape[0], lm["emb"].shape[0], V))
     with torch.no_grad():
         search = hb.BeamSearch(B, beam, V, L, eos, dev)
+        table_lm = None
+        if ngram is not None or word_lm is not None:
+            tws = torch.empty(hb.beam_tlm_ws_bytes(B, beam) // 4, device=dev, dtype=torch.int32)
+            if ngram is not None:
+                table_lm = hb.BeamTableLm(search, tws, ngram=_ngram_table(ngram, dev), weight=ngram_weight, bonus=ngram_bonus)
+            else:
+                table_lm = hb.BeamTableLm(search, tws, word_lm=word_lm.to(dev), weight=word_lm_weight, bonus=word_bonus,
+                                          lexicon_only=lexicon_only)
+            table_lm.init()
         if joint:
             prefix = hb.CtcPrefixState(search, ctc["logits"].detach(), ctc["frame_lens"], 0, ctc.get("lens_host"))
         if fused:
@@ -1513,8 +1533,11 @@ def beam_search(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo
                 launches += lms.n + 1                      # the LM's layers and its output GEMM
             if joint:
                 prefix.score()
-                search.select_ctc(logits, prefix, ctc_weight, t, lm_logits if fused else None, lm_weight)
                 launches += 1                              # the prefix score
+            if table_lm is not None:
+                table_lm.select(logits, t, lm_logits if fused else None, lm_weight, prefix if joint else None, ctc_weight)
+            elif joint:
+                search.select_ctc(logits, prefix, ctc_weight, t, lm_logits if fused else None, lm_weight)
             elif fused:
                 search.select_lm(logits, lm_logits, lm_weight, t)
             else:
@@ -1543,5 +1566,5 @@ def beam_search(P, Q, emb_w, w_ih, w_hh, b_ih, b_hh, wdec, convw, watt, gvec, bo
         kind = "beam_ctc" if joint else ("beam_lm" if fused else "beam")      # (a joint search with an LM counts as beam_ctc)
         hb.LAUNCHES[kind + "_step"] += steps
         hb.LAUNCHES[kind + "_launch"] += launches
-        out = search.backtrack(length_penalty)
+        out = search.backtrack(length_penalty) if table_lm is None else table_lm.backtrack(length_penalty)
     return out

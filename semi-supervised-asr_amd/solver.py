@@ -323,9 +323,41 @@ class Solver(object):
             out = run()
         return out
 
-    def _beam(self, xs, ilens, beam_size, lm_weight=0.0, nbest=False, ctc_decode_weight=0.0):
+    ATT_NGRAM_LM_KEYS = ("arpa", "weight", "bonus")
+    ATT_WORD_LM_KEYS = ("arpa", "lexicon", "weight", "bonus", "lexicon_only")
+
+    @staticmethod
+    def att_lm_config(config):
+        """`att_ngram_lm` and `att_word_lm` (not reference keys; absent by default): the n-gram LM, or the lexicon
+        and the word-level LM, INSIDE the attention beam search (E2E.recognize_beams) - sub-dictionaries in the style of
+        `rnnt_word_lm`: `att_ngram_lm: {arpa, weight, bonus}` (an ARPA file over the vocabulary's symbols; bonus per token) and
+        `att_word_lm: {arpa, lexicon, weight, bonus, lexicon_only}` (an ARPA file over words spelled in the vocabulary's
+        characters, an optional lexicon file; bonus per completed word).  They combine with `lm_weight` and
+        `ctc_decode_weight`.  -> (kind, the sub-dictionary) with kind "ngram" / "word", or (None, None); ValueError with both,
+        without `beam_size` > 1, beside another decoder's key, without `arpa`, or with a sub-key that is none of these."""
+        ng, wd = config.get("att_ngram_lm"), config.get("att_word_lm")
+        if ng is None and wd is None:
+            return None, None
+        if ng is not None and wd is not None:
+            raise ValueError("att_ngram_lm and att_word_lm are two LMs for one search: set one of them")
+        name, sub, keys = ("att_ngram_lm", ng, Solver.ATT_NGRAM_LM_KEYS) if ng is not None else \
+            ("att_word_lm", wd, Solver.ATT_WORD_LM_KEYS)
+        others = [k for k in ("rnnt_beam_decode", "rnnt_greedy_decode", "two_pass_decode", "ctc_beam_decode", "ctc_greedy_decode")
+                  if config.get(k)]
+        if others:
+            raise ValueError("%s is the LM of the attention beam search: it does not combine with %s" % (name, ", ".join(others)))
+        if int(config.get("beam_size", 1) or 1) <= 1:
+            raise ValueError("%s is the LM of the attention beam search: set beam_size > 1" % name)
+        unknown = sorted(set(sub) - set(keys)) if isinstance(sub, dict) else None
+        if unknown is None or unknown or not sub.get("arpa"):
+            raise ValueError("%s is a dictionary with `arpa` and optionally %s%s"
+                             % (name, ", ".join(keys[1:]), "; got %s" % ", ".join(unknown) if unknown else ""))
+        return ("ngram" if ng is not None else "word"), sub
+
+    def _beam(self, xs, ilens, beam_size, lm_weight=0.0, nbest=False, ctc_decode_weight=0.0, table_lm=None):
         """Best beam-search hypothesis ids for one batch (E2E.recognize_beams; lm_weight > 0: rescored by the judge, shallow
-        fusion) - with nbest all beam_size of them per utterance, ranked ([B][K][L]).  The encoder still runs on the
+        fusion; table_lm: the keyword arguments of an n-gram or word LM inside the search) - with nbest all
+        beam_size of them per utterance, ranked ([B][K][L]).  The encoder still runs on the
         persistent LSTM kernels: the abort word is checked after the decode and the batch repeated on the per-step kernels,
         as in _greedy."""
         def run():
@@ -333,7 +365,7 @@ class Solver(object):
                 xs, ilens, self.config["max_dec_timesteps"], beam_size,
                 length_penalty=float(self.config.get("beam_length_penalty", 0.0)), nbest=nbest,
                 lm=self.judge if lm_weight > 0 else None, lm_weight=lm_weight,
-                **(dict(ctc_decode_weight=ctc_decode_weight) if ctc_decode_weight > 0 else {}))
+                **(dict(ctc_decode_weight=ctc_decode_weight) if ctc_decode_weight > 0 else {}), **(table_lm or {}))
             return prediction.cpu().numpy().tolist()
         out = run()
         if self._abort_seen(xs.device):
@@ -737,6 +769,19 @@ class Solver(object):
             rw = self.config["rnnt_word_lm"]
             ngram = dict(word_lm=self.load_word_lm(rw["arpa"], rw.get("lexicon")), word_lm_weight=float(rw.get("weight", 0.0) or 0.0),
                          word_bonus=float(rw.get("bonus", 0.0) or 0.0), lexicon_only=bool(rw.get("lexicon_only", False)))
+        # `att_ngram_lm` / `att_word_lm` (not reference keys): the n-gram or the lexicon and word LM inside the
+        # attention beam search; absent, nothing below differs
+        att_kind, att_sub = self.att_lm_config(self.config)
+        att_lm = None
+        if att_kind == "ngram":
+            from ngram import NgramLM
+            att_lm = dict(ngram=NgramLM.from_arpa(att_sub["arpa"], {s: i for s, i in self.vocab.items() if s not in ("<s>", "</s>")},
+                                                  self.vocab["<BOS>"], self.vocab["<EOS>"], V=len(self.vocab)),
+                          ngram_weight=float(att_sub.get("weight", 0.0) or 0.0), ngram_bonus=float(att_sub.get("bonus", 0.0) or 0.0))
+        elif att_kind == "word":
+            att_lm = dict(word_lm=self.load_word_lm(att_sub["arpa"], att_sub.get("lexicon")),
+                          word_lm_weight=float(att_sub.get("weight", 0.0) or 0.0), word_bonus=float(att_sub.get("bonus", 0.0) or 0.0),
+                          lexicon_only=bool(att_sub.get("lexicon_only", False)))
         if state_dict:
             self.model.load_state_dict(state_dict)
         else:
@@ -791,11 +836,11 @@ class Solver(object):
             elif two_pass:
                 preds += self._two_pass(xs, ilens, beam_size, ctc_w, lm_weight, ngram=ngram)
             elif nbest:
-                ranked = self._beam(xs, ilens, beam_size, lm_weight, nbest=True, ctc_decode_weight=ctc_w)
+                ranked = self._beam(xs, ilens, beam_size, lm_weight, nbest=True, ctc_decode_weight=ctc_w, table_lm=att_lm)
                 preds += [hyps[0] for hyps in ranked]
                 beams += ranked
-            elif lm_weight > 0 or ctc_w > 0:
-                preds += self._beam(xs, ilens, beam_size, lm_weight, ctc_decode_weight=ctc_w)
+            elif lm_weight > 0 or ctc_w > 0 or att_lm is not None:
+                preds += self._beam(xs, ilens, beam_size, lm_weight, ctc_decode_weight=ctc_w, table_lm=att_lm)
             else:
                 preds += self._beam(xs, ilens, beam_size) if beam_size > 1 else self._greedy(xs, ilens)
             refs += batch.ys_host

@@ -10,7 +10,12 @@ process: "beam" (the plain search), "beam_lm" (the fused search) and "lm_forward
 step on the same B*K rows, the only way to compute the LM's part without the fused kernels (its state is not permuted and
 nothing is selected: a lower bound of that composition).  `lm_us_per_step` of the fused line is (fused - plain) / L.
 With --profile the one case is the fused search.  --lm-micro times asr_lm_step_f32 alone (R = 4 and 128, one layer at
-H = In = 640: 13.1 MB of weights per call) for its achieved weight bandwidth."""
+H = In = 640: 13.1 MB of weights per call) for its achieved weight bandwidth.
+
+--ngram / --word-lm: a 3-gram automaton over the V tokens, or a lexicon of a few thousand words with a bigram word
+LM, inside the search.  Per (B, K), B in {1, 32} and K in {4, 8}, two lines from the same process, the plain search ("beam")
+and the fused one ("beam_ngram" / "beam_word_lm"), their calls alternating; `select_us_per_step` of the fused line is
+(fused - plain) / L, the cost of the fused select over the plain select.  With --profile the one case is the fused search."""
 import argparse
 import json
 import os
@@ -30,6 +35,9 @@ def main():
     ap.add_argument("--lm", action="store_true", help="shallow fusion with the cfg-4 judge: plain, fused, LM.forward_step")
     ap.add_argument("--lm-weight", type=float, default=0.3)
     ap.add_argument("--lm-micro", action="store_true", help="asr_lm_step_f32 alone: time and weight bandwidth")
+    ap.add_argument("--ngram", action="store_true", help="a 3-gram LM inside the search: plain and fused, alternating")
+    ap.add_argument("--word-lm", action="store_true", help="a lexicon and word LM inside the search: plain and fused, alternating")
+    ap.add_argument("--table-lm-weight", type=float, default=0.5)
     args = ap.parse_args()
     import __graft_entry__ as entry
     entry.build()
@@ -54,6 +62,8 @@ def main():
         return lm_micro(hb, lm)
     if args.lm:
         return lm_cases(args, hb, net, lm, V, L, Tp)
+    if args.ngram or args.word_lm:
+        return table_lm_cases(args, hb, net, V, L, Tp)
     cases = [(32, 4)] if args.profile else [(B, K) for B in (1, 32) for K in ("greedy", 1, 4, 8)]
     for B, K in cases:
         rs = np.random.RandomState(B)
@@ -137,6 +147,57 @@ def lm_cases(args, hb, net, lm, V, L, Tp):
                 rec["lm_us_per_step"] = round(1e3 * (med["beam_lm"] - med["beam"]) / L, 2)
             if method == "lm_forward_step":
                 rec["lm_us_per_step"] = round(1e3 * med[method] / L, 2)
+            print(json.dumps(rec), flush=True)
+
+
+def table_lm_cases(args, hb, net, V, L, Tp):
+    from ngram import NgramLM
+    from word_lm import WordLM
+    rs = np.random.RandomState(3)
+    space = V - 1
+    if args.ngram:
+        text = [[int(c) for c in rs.randint(3, V, size=rs.randint(5, 40))] for _ in range(400)]
+        kw = dict(ngram=NgramLM.estimate(text, 3, V, 1, 2), ngram_weight=args.table_lm_weight, ngram_bonus=0.2)
+        method = "beam_ngram"
+    else:
+        words = [[int(c) for c in rs.randint(3, space, size=rs.randint(1, 7))] for _ in range(3000)]
+        text = []
+        for _ in range(1500):
+            row = []
+            for i in rs.randint(len(words), size=rs.randint(2, 9)):
+                row += words[i] + [space]
+            text.append(row[:-1])
+        kw = dict(word_lm=WordLM.estimate(text, space, 2, V=V, bos=1, eos=2), word_lm_weight=args.table_lm_weight, word_bonus=0.2)
+        method = "beam_word_lm"
+    cases = [(32, 4)] if args.profile else [(B, K) for B in (1, 32) for K in (4, 8)]
+    reps = 1 if args.profile else args.reps
+    for B, K in cases:
+        ers = np.random.RandomState(B)
+        enc = torch.from_numpy(ers.randn(B, Tp, 512).astype(np.float32)).cuda()
+        lens = [Tp - (b * 37) % 40 for b in range(B)]
+        fns = dict(beam=lambda: net.decoder.recognize_beams(enc, lens, L, K)[0],
+                   fused=lambda: net.decoder.recognize_beams(enc, lens, L, K, **kw)[0])
+        for fn in fns.values():
+            fn()
+        torch.cuda.synchronize()
+        times = dict(beam=[], fused=[])
+        steps = {}
+        for _ in range(reps):                                    # alternating: both see the same clocks
+            for name in (("fused",) if args.profile else ("beam", "fused")):
+                hb.LAUNCHES.clear()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fns[name]()
+                b.record()
+                b.synchronize()
+                times[name].append(a.elapsed_time(b))
+                steps[name] = (hb.LAUNCHES["beam_step"], round(hb.LAUNCHES["beam_launch"] / max(1, hb.LAUNCHES["beam_step"]), 3))
+        med = {k: float(np.median(v)) for k, v in times.items() if v}
+        for name in med:
+            rec = dict(method="beam" if name == "beam" else method, K=K, B=B, L=L, Tp=Tp, V=V, ms_per_batch=round(med[name], 3),
+                       ms_all=[round(t, 3) for t in times[name]], steps=steps[name][0], launches_per_step=steps[name][1])
+            if name == "fused" and "beam" in med:
+                rec["select_us_per_step"] = round(1e3 * (med["fused"] - med["beam"]) / L, 2)
             print(json.dumps(rec), flush=True)
 
 
