@@ -1159,6 +1159,61 @@ int asr_ctc_beam_wlm_f32(int B, int T, int V, int K, const float* logits, int64_
                          asr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Contextual biasing: per-utterance phrase lists inside the CTC prefix beam search (csrc/context.h, csrc/context.hip,
+ * csrc/ctc_beam.hip).  Not reference operators.  Two entries added to ABI version 8 WITHOUT a version change:
+ * additive.
+ * The graphs arrive compiled (context.py, ContextGraph / ContextBatch .compile, which validates every index: the kernels trust
+ * the tables).  One table holds G graphs over N states in one numbering; all arrays are device memory:
+ *     arc_off  int32 [N+1]    the arcs of state s are arc_off[s] .. arc_off[s+1]-1: its transitions that differ from its
+ *                             default row
+ *     arc_tok  int32 [A]      ascending inside a state;   arc_next int32 [A] the state after the token
+ *     drow     int32 [N]      the default row of the state, in 0 .. R-1
+ *     dflt     int32 [R][V]   next(s, c) = dflt[drow[s]][c] where no arc of s lists c
+ *     credit   fp32  [N], pending fp32 [N]      root int32 [G]  the root of graph g
+ * graph_of int32 [rows] (device) names the graph of every row; a value outside 0 .. G-1 (-1 by convention) means no biasing
+ * for that row: bias 0, no state.  (The host layer refuses an index outside -1 .. G-1 before any launch; the kernels only
+ * guard their reads.)
+ * The bias of a token row: state = root; per token c in order  n = next(state, c), delta = credit[n] - pending[state] (one
+ * fp32 subtraction), bias = bias + delta (one fp32 addition), state = n;  behind the last token bias = bias - pending[state].
+ *   asr_context_score_f32   N padded TOKEN id rows ids int32 [N][ld >= L] with lens int32 [N] (clamped to L; < 0: an unused
+ *       slot, score -inf) -> score fp32 [N], the bias of the row under graph graph_of[n];  tok_score fp32 [N][L] or NULL: the
+ *       delta of every token, 0 behind the row.  An id outside 1 .. V-1 inside the length makes the row's score (and its
+ *       tok_score from there to the length) NaN; nothing is indexed with it.  One thread per row, one launch, no atomics.
+ *   asr_ctc_beam_ctx_f32    asr_ctc_beam_f32 (S = 0: lm_logp, lm_next and lm_score NULL) or asr_ctc_beam_lm_f32 (S > 0) with
+ *       the context inside the search.  An entry additionally carries its context state and bias - functions of the token
+ *       sequence, so prefix identity and the merge are unchanged, and pb, pnb, tot (and lm) are the search's without a
+ *       context, operation for operation.  A candidate ranks by
+ *           rank = r + ctx_weight bias'        r = tot' (S = 0) or (tot' + alpha lm') + beta len' (S > 0)
+ *       fp32, the product and the sum rounded on their own, as the last operations: ctx_weight = 0, or graph_of = -1, gives the
+ *       bits of the search without a context.  After the last frame bias = bias - pending[state] (and, S > 0 with lm_eos >= 0,
+ *       the end term joins lm), the rank is formed again and the entries are ranked once more, ties to the search's order.
+ *       Outputs: hyp, hyp_len as asr_ctc_beam_f32; score fp32 [B][K] the rank; ctc_score fp32 [B][K] tot; lm_score fp32 [B][K]
+ *       (S > 0) lm; ctx_score fp32 [B][K] bias - asr_context_score_f32 of the hypothesis bit for bit; -inf in unused slots.
+ *       An utterance of no frames gets the empty hypothesis in slot 0 with ctx_score 0.  c->V must be V, S V <= INT_MAX,
+ *       lm_start in 0 .. S-1 (ASR_E_SHAPE); ctx_weight, alpha, beta finite (ASR_E_ARG).  Workspace, launches (two) and limits
+ *       are asr_ctc_beam_f32's.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  int32_t V, N, G, R;     /* tokens, states, graphs, default rows */
+  int64_t A;              /* arcs */
+  const int32_t* arc_off;
+  const int32_t* arc_tok;
+  const int32_t* arc_next;
+  const int32_t* drow;
+  const int32_t* dflt;
+  const float* credit;
+  const float* pending;
+  const int32_t* root;
+} asr_context_t;
+int asr_context_score_f32(int N, int L, const asr_context_t* c, const int32_t* graph_of, const int32_t* ids, int64_t ld,
+                          const int32_t* lens, float* score, float* tok_score, asr_stream_t stream);
+int asr_ctc_beam_ctx_f32(int B, int T, int V, int K, const float* logits, int64_t ld, const int32_t* frame_lens,
+                         const asr_context_t* c, const int32_t* graph_of, float ctx_weight, int S, const float* lm_logp,
+                         const int32_t* lm_next, int lm_start, int lm_eos, float alpha, float beta, int32_t* hyp,
+                         int32_t* hyp_len, float* score, float* ctc_score, float* lm_score, float* ctx_score, void* ws,
+                         asr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * The front end (csrc/frontend.hip): packed waveforms -> the [B][T][D] features the encoder reads.  Not
  * reference operators - the reference reads features that Kaldi computed.  Five entries added to ABI version 8 WITHOUT a
  * version change: additive.

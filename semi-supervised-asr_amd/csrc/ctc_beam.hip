@@ -35,9 +35,18 @@
 //                         an utterance without frames use its finish).  Ranks are lm_rank's with nw for len.
 //                         With lexicon_only the walk also reads the entry's trie row (one coalesced read per (entry, token),
 //                         as the n-gram variant reads its LM row) and drops what leaves the lexicon.
+//   ctc_beam_kernel<M, kCtx>, <M, kNgramCtx>   the search with a context graph per utterance inside, alone or beside the
+//                         n-gram LM (the tables and the transition are context.h's): an entry also carries its
+//                         context state and bias, the fp32 sum of its deltas in token order - functions of the token
+//                         sequence again.  The candidate walk takes the step per (entry, token) where the n-gram mode reads
+//                         its LM row; a candidate ranks by what the search without a context would rank it by, plus
+//                         ctx_weight bias as the last operation; update forms the winner's state again.  After the last
+//                         frame final of the state joins bias and the entries rank once more (the n-gram mode's tail).  An
+//                         utterance whose graph index is -1 never moves: its bias stays 0 and its ranks are the plain ones.
 #include <float.h>
 #include <type_traits>
 #include "seq_common.h"
+#include "context.h"
 #include "word_lm.h"
 
 namespace {
@@ -50,10 +59,12 @@ constexpr int kHistLds = ASR_CTC_BEAM_LDS_ENTRIES;         // (frame, slot) hist
 static_assert(kKmax <= 32, "the merge map of an entry is one 32-bit mask");
 // (2048: the beam's two slots, the candidates' and the reduction's arrays - at most, with the word LM inside: 17 words per
 // entry, the state, lm and stay mass of a search with an LM 5, and node, nw and the close pair in two slots each 8; the
-// n-gram mode's rank and position are 2 in their place)
+// n-gram mode's rank and position are 2 in their place, and a context's state and bias in two slots 4 more)
 static_assert(kHistLds * 8 + kStage * kMaxThreads * 4 + 2048 <= 64 * 1024, "the static LDS of a workgroup");
 static_assert((17 + 5 + 4 * 2) * 4 * kKmax + 2 * 2 * (kMaxThreads / 64) * 4 <= 2048,
               "the beam's arrays of the word-LM variant inside the 2048 bytes above");
+static_assert((17 + 5 + 2 + 2 * 2) * 4 * kKmax + 2 * 2 * (kMaxThreads / 64) * 4 <= 2048,
+              "the beam's arrays of the n-gram + context variant inside the 2048 bytes above");
 
 struct BeamWs {
   int2* hist;      // [B][T][K] (parent slot, token; token 0: the entry stayed); absent when T K entries fit LDS
@@ -90,14 +101,31 @@ struct BeamWlm {
   int eos_term, lexicon_only;
 };
 
-constexpr int kPlain = 0, kNgram = 1, kWordLm = 2;           // what sits inside the search
+// the context of a fused search beside its LM (MODE = kCtx: no LM, its part all zero but ctc_score; kNgramCtx)
+struct BeamCtx : BeamLm {
+  ctx::Context c;
+  const int32_t* graph_of; // [B]
+  float* ctx_score;        // [B][K]
+  float weight;
+};
+
+constexpr int kPlain = 0, kNgram = 1, kWordLm = 2, kCtx = 3, kNgramCtx = 4;      // what sits inside the search
+
+template <int MODE>
+using BeamArg = std::conditional_t<MODE == kWordLm, BeamWlm, std::conditional_t<MODE == kCtx || MODE == kNgramCtx, BeamCtx, BeamLm>>;
+
+// the rank of a search with a context inside: the rank without one, plus weight bias as the last operation
+__device__ __forceinline__ float ctx_rank(float rank, float weight, float bias) { return __fadd_rn(rank, __fmul_rn(weight, bias)); }
 
 template <int M, int MODE>
 __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int K, const float* __restrict__ z, int64_t ld,
                                                                const int32_t* __restrict__ lens, int32_t* __restrict__ hyp,
                                                                int32_t* __restrict__ hyp_len, float* __restrict__ score,
-                                                               BeamWs w, std::conditional_t<MODE == kWordLm, BeamWlm, BeamLm> g) {
-  constexpr bool LM = MODE == kNgram, WLM = MODE == kWordLm, RK = MODE != kPlain;      // RK: the list holds ranks
+                                                               BeamWs w, BeamArg<MODE> g) {
+  constexpr bool LM = MODE == kNgram || MODE == kNgramCtx, WLM = MODE == kWordLm, CX = MODE == kCtx || MODE == kNgramCtx;
+  constexpr bool RK = MODE != kPlain;                        // RK: the list holds ranks
+  __shared__ int s_cst[2][kKmax];                            // (context only: the state and the bias of an entry)
+  __shared__ float s_bias[2][kKmax];
   __shared__ int s_state[2][kKmax], s_pos[kKmax];            // (LM only, like the next line: unused arrays take no LDS)
   __shared__ float s_lm[2][kKmax], s_stot[kKmax], s_rank[kKmax];
   __shared__ int s_node[2][kKmax], s_nw[2][kKmax], s_cnx[2][kKmax];      // (word LM only: trie node, words, close pair)
@@ -126,6 +154,16 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
         g.ctc_score[(int64_t)b * K + tid] = tid == 0 ? 0.f : -INFINITY;
         g.lm_score[(int64_t)b * K + tid] = tid == 0 ? lm0 : -INFINITY;
         g.n_words[(int64_t)b * K + tid] = tid == 0 ? 0 : -1;
+      } else if constexpr (CX) {                               // (final(root) = 0: the bias of the empty hypothesis)
+        float rank0 = 0.f;
+        if constexpr (LM) {
+          const float lm0 = g.eos >= 0 ? g.logp[(int64_t)g.start * V + g.eos] : 0.f;
+          rank0 = lm_rank(0.f, lm0, 0, g.alpha, g.beta);
+          g.lm_score[(int64_t)b * K + tid] = tid == 0 ? lm0 : -INFINITY;
+        }
+        score[(int64_t)b * K + tid] = tid == 0 ? ctx_rank(rank0, g.weight, 0.f) : -INFINITY;
+        g.ctc_score[(int64_t)b * K + tid] = tid == 0 ? 0.f : -INFINITY;
+        g.ctx_score[(int64_t)b * K + tid] = tid == 0 ? 0.f : -INFINITY;
       } else if constexpr (LM) {
         const float lm0 = g.eos >= 0 ? g.logp[(int64_t)g.start * V + g.eos] : 0.f;
         score[(int64_t)b * K + tid] = tid == 0 ? lm_rank(0.f, lm0, 0, g.alpha, g.beta) : -INFINITY;
@@ -141,6 +179,8 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
   const float* zb = z + (int64_t)b * T * ld;
   const float* lse = w.lse + (int64_t)b * T;
   int2* hist = (int64_t)len * K <= kHistLds ? s_hist : w.hist + (int64_t)b * T * K;
+  int croot = -1;                                            // (context) the root of this utterance's graph; < 0: no biasing
+  if constexpr (CX) croot = ctx::graph_root(g.c, g.graph_of, b);
   const int nstage = kStage * nt;
   if (tid < K) {                                             // the empty prefix at (0, -inf)
     s_pb[0][tid] = tid == 0 ? 0.f : -INFINITY;
@@ -152,6 +192,10 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
     if constexpr (LM) {
       s_state[0][tid] = g.start;
       s_lm[0][tid] = 0.f;
+    }
+    if constexpr (CX) {
+      s_cst[0][tid] = croot;
+      s_bias[0][tid] = 0.f;
     }
     if constexpr (WLM) {
       s_state[0][tid] = g.w.start;
@@ -214,7 +258,13 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
           npnb = logaddexp(npnb, (s_last[p][i] == cj ? s_pb[p][i] : s_tot[p][i]) + xj);
       s_spb[tid] = npb;
       s_spnb[tid] = npnb;
-      if constexpr (LM) {
+      if constexpr (CX) {
+        const float st = logaddexp(npb, npnb);
+        s_stot[tid] = st;
+        float rk = st;
+        if constexpr (LM) rk = lm_rank(st, s_lm[p][tid], lj, g.alpha, g.beta);
+        top_insert(lv, li, ctx_rank(rk, g.weight, s_bias[p][tid]), tid);
+      } else if constexpr (LM) {
         const float st = logaddexp(npb, npnb);
         s_stot[tid] = st;
         top_insert(lv, li, lm_rank(st, s_lm[p][tid], lj, g.alpha, g.beta), tid);
@@ -256,6 +306,13 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
           trow = g.w.trie_next + (int64_t)nodek * V;
         }
       }
+      // (context) what the transitions of the entry's state share, and its bias
+      ctx::Node cnode{};
+      float biask = 0.f;
+      if constexpr (CX) {
+        if (croot >= 0) cnode = ctx::node(g.c, s_cst[p][k]);
+        biask = s_bias[p][k];
+      }
       for (int c = tid; c < V; c += nt) {
         if (c == 0) continue;
         const float xc = c < nstage ? xs[c] : zr[c] - lcur;
@@ -267,6 +324,15 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
           const bool sp = c == g.w.space;
           if (g.lexicon_only && (sp ? no_sp : trow[c] < 0)) val = -INFINITY;
           val = lm_rank(val, sp ? lm_sp : lmk, sp ? nw_sp : nwk, g.alpha, g.beta);
+        }
+        if constexpr (CX) {                                      // (-inf stays -inf: weight and bias are finite)
+          float nb = biask;
+          if (croot >= 0) {
+            float d;
+            ctx::arc(g.c, cnode, c, &d);
+            nb = __fadd_rn(biask, d);
+          }
+          val = ctx_rank(val, g.weight, nb);
         }
         top_insert(lv, li, val, base + c);
       }
@@ -332,10 +398,14 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
           s_last[q][tid] = s_last[p][k];
           s_len[q][tid] = s_len[p][k];
           s_hash[q][tid] = s_hash[p][k];
-          if constexpr (RK) {
-            s_tot[q][tid] = s_stot[k];
+          if constexpr (RK) s_tot[q][tid] = s_stot[k];
+          if constexpr (LM || WLM) {
             s_lm[q][tid] = s_lm[p][k];
             s_state[q][tid] = s_state[p][k];
+          }
+          if constexpr (CX) {
+            s_cst[q][tid] = s_cst[p][k];
+            s_bias[q][tid] = s_bias[p][k];
           }
           if constexpr (WLM) {
             s_node[q][tid] = s_node[p][k];
@@ -347,6 +417,23 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
           const int e = my_i - K;
           k = e / (V - 1), tok = e - k * (V - 1) + 1;
           s_pb[q][tid] = -INFINITY;
+          if constexpr (CX) {                                    // the winner's state and bias once more: the walk's step
+            int cs = s_cst[p][k];
+            float nb = s_bias[p][k];
+            if (croot >= 0) {
+              float d;
+              cs = ctx::step(g.c, cs, tok, &d);
+              nb = __fadd_rn(nb, d);
+            }
+            s_cst[q][tid] = cs;
+            s_bias[q][tid] = nb;
+            if constexpr (!LM) {                                 // my_v is a rank: the candidate's mass once more
+              const float xc = tok < nstage ? xs[tok] : zr[tok] - lcur;
+              const float mass = (tok == s_last[p][k] ? s_pb[p][k] : s_tot[p][k]) + xc;
+              s_pnb[q][tid] = mass;
+              s_tot[q][tid] = mass;
+            }
+          }
           if constexpr (LM) {                                    // my_v is a rank: the candidate's mass once more
             const float xc = tok < nstage ? xs[tok] : zr[tok] - lcur;
             const float mass = (tok == s_last[p][k] ? s_pb[p][k] : s_tot[p][k]) + xc;
@@ -371,7 +458,7 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
             s_nw[q][tid] = e.nw;
             s_clp[q][tid] = cl;
             s_cnx[q][tid] = cn;
-          } else {
+          } else if constexpr (!CX) {
             s_pnb[q][tid] = my_v;
           }
           s_last[q][tid] = tok;
@@ -395,14 +482,25 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
   }
   // The n-gram mode keeps a tail of its own, with its ranks and positions in s_rank / s_pos: folded into the tail below it
   // measured about 1 % slower at K = 4 (0.6948 -> 0.7011 ms at B = 32, T' = 100, V = 50), and the fold gave way.
-  if constexpr (LM) {
+  if constexpr (LM || CX) {
+    // (context: final of the state joins bias, and weight bias the rank, in the same way)
     // the end-of-sentence term joins lm; the entries rank by lm_rank once more, ties to the search's order (without the term
     // every rank is the select's and the order stays); thread r walks the history of entry r back into the row of its rank
     if (tid < nlive) {
-      float lm = s_lm[p][tid];
-      if (g.eos >= 0) lm += g.logp[(int64_t)s_state[p][tid] * V + g.eos];
-      s_lm[p][tid] = lm;
-      s_rank[tid] = lm_rank(s_tot[p][tid], lm, s_len[p][tid], g.alpha, g.beta);
+      float rk = s_tot[p][tid];
+      if constexpr (LM) {
+        float lm = s_lm[p][tid];
+        if (g.eos >= 0) lm += g.logp[(int64_t)s_state[p][tid] * V + g.eos];
+        s_lm[p][tid] = lm;
+        rk = lm_rank(s_tot[p][tid], lm, s_len[p][tid], g.alpha, g.beta);
+      }
+      if constexpr (CX) {
+        float bias = s_bias[p][tid];
+        if (croot >= 0) bias = ctx::finish(g.c, s_cst[p][tid], bias);
+        s_bias[p][tid] = bias;
+        rk = ctx_rank(rk, g.weight, bias);
+      }
+      s_rank[tid] = rk;
     }
     __syncthreads();
     if (tid < K) {
@@ -421,12 +519,14 @@ __global__ __launch_bounds__(kMaxThreads) void ctc_beam_kernel(int T, int V, int
         }
         score[(int64_t)b * K + at] = rv;
         g.ctc_score[(int64_t)b * K + at] = s_tot[p][tid];
-        g.lm_score[(int64_t)b * K + at] = s_lm[p][tid];
+        if constexpr (LM) g.lm_score[(int64_t)b * K + at] = s_lm[p][tid];
+        if constexpr (CX) g.ctx_score[(int64_t)b * K + at] = s_bias[p][tid];
         hyp_len[(int64_t)b * K + at] = n;
       } else {
         score[(int64_t)b * K + tid] = -INFINITY;
         g.ctc_score[(int64_t)b * K + tid] = -INFINITY;
-        g.lm_score[(int64_t)b * K + tid] = -INFINITY;
+        if constexpr (LM) g.lm_score[(int64_t)b * K + tid] = -INFINITY;
+        if constexpr (CX) g.ctx_score[(int64_t)b * K + tid] = -INFINITY;
         hyp_len[(int64_t)b * K + tid] = -1;
       }
       s_pos[tid] = at;
@@ -507,7 +607,7 @@ int beam_check(int B, int T, int V, int K) {
   return 0;
 }
 
-// what the three entries check first, and what they do once their own checks have passed
+// what the four entries check first, and what they do once their own checks have passed
 bool common_args_ok(const float* logits, int64_t ld, int V, const int32_t* frame_lens, const int32_t* hyp, const int32_t* hyp_len,
                     const float* score, const void* ws) {
   return logits && frame_lens && hyp && hyp_len && score && ws && ld >= V;
@@ -565,6 +665,30 @@ extern "C" int asr_ctc_beam_lm_f32(int B, int T, int V, int K, const float* logi
   g.logp = lm_logp, g.next = lm_next, g.ctc_score = ctc_score, g.lm_score = lm_score;
   g.start = lm_start, g.eos = lm_eos < 0 ? -1 : lm_eos, g.alpha = alpha, g.beta = beta;
   return launch<kNgram>(B, T, V, K, logits, ld, frame_lens, hyp, hyp_len, score, ws, g, (hipStream_t)stream);
+}
+
+extern "C" int asr_ctc_beam_ctx_f32(int B, int T, int V, int K, const float* logits, int64_t ld, const int32_t* frame_lens,
+                                    const asr_context_t* c, const int32_t* graph_of, float ctx_weight, int S, const float* lm_logp,
+                                    const int32_t* lm_next, int lm_start, int lm_eos, float alpha, float beta, int32_t* hyp,
+                                    int32_t* hyp_len, float* score, float* ctc_score, float* lm_score, float* ctx_score, void* ws,
+                                    asr_stream_t stream) {
+  if (!common_args_ok(logits, ld, V, frame_lens, hyp, hyp_len, score, ws) || !graph_of || !ctc_score || !ctx_score || S < 0 ||
+      !(fabsf(ctx_weight) <= FLT_MAX))
+    return ASR_E_ARG;
+  if (S > 0 && (!lm_logp || !lm_next || !lm_score || !(fabsf(alpha) <= FLT_MAX) || !(fabsf(beta) <= FLT_MAX))) return ASR_E_ARG;
+  int rc = ctx::check_abi(c);
+  if (rc) return rc;
+  rc = beam_check(B, T, V, K);
+  if (rc) return rc;
+  if (c->V != V) return ASR_E_SHAPE;
+  if (S > 0 && ((int64_t)S * V > INT_MAX || lm_start < 0 || lm_start >= S || lm_eos >= V)) return ASR_E_SHAPE;
+  BeamCtx g{};
+  g.c = ctx::from_abi(*c), g.graph_of = graph_of, g.ctx_score = ctx_score, g.weight = ctx_weight;
+  g.ctc_score = ctc_score;
+  if (S == 0) return launch<kCtx>(B, T, V, K, logits, ld, frame_lens, hyp, hyp_len, score, ws, g, (hipStream_t)stream);
+  g.logp = lm_logp, g.next = lm_next, g.lm_score = lm_score;
+  g.start = lm_start, g.eos = lm_eos < 0 ? -1 : lm_eos, g.alpha = alpha, g.beta = beta;
+  return launch<kNgramCtx>(B, T, V, K, logits, ld, frame_lens, hyp, hyp_len, score, ws, g, (hipStream_t)stream);
 }
 
 extern "C" int asr_ctc_beam_wlm_f32(int B, int T, int V, int K, const float* logits, int64_t ld, const int32_t* frame_lens,

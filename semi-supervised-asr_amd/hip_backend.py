@@ -33,6 +33,7 @@ EXPORTS = (
     "asr_ctc_align_ws_bytes", "asr_ctc_align_f32", "asr_ctc_greedy_f32",
     "asr_ctc_beam_ws_bytes", "asr_ctc_beam_f32", "asr_ctc_beam_lm_f32", "asr_ngram_score_f32",
     "asr_word_lm_score_f32", "asr_ctc_beam_wlm_f32",
+    "asr_context_score_f32", "asr_ctc_beam_ctx_f32",
     "asr_fbank_num_frames", "asr_fbank_plan_bytes", "asr_fbank_f32", "asr_feat_cmvn_stats_f32", "asr_feat_finish_f32",
     "asr_mwer_fwd_f32", "asr_mwer_bwd_f32",
     "asr_resample_plan_bytes", "asr_resample_f32",
@@ -67,6 +68,13 @@ class WordLmTable(ctypes.Structure):
                 ("space", ctypes.c_int32), ("start", ctypes.c_int32), ("empty", ctypes.c_int32), ("eos", ctypes.c_int32),
                 ("unk", ctypes.c_int32), ("trie_next", c_p), ("trie_word", c_p), ("arc_off", c_p), ("arc_word", c_p),
                 ("arc_logp", c_p), ("arc_next", c_p), ("bo_logp", c_p), ("bo_state", c_p), ("uni_logp", c_p), ("uni_next", c_p)]
+
+
+class ContextTable(ctypes.Structure):
+    """asr_context_t"""
+    _fields_ = [("V", ctypes.c_int32), ("N", ctypes.c_int32), ("G", ctypes.c_int32), ("R", ctypes.c_int32), ("A", c_i64),
+                ("arc_off", c_p), ("arc_tok", c_p), ("arc_next", c_p), ("drow", c_p), ("dflt", c_p), ("credit", c_p),
+                ("pending", c_p), ("root", c_p)]
 
 
 class LstmUnpackJob(ctypes.Structure):
@@ -316,6 +324,9 @@ def load():
                                         c_p, c_p]
     lib.asr_ngram_score_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p]
     lib.asr_word_lm_score_f32.argtypes = [c_i, c_i, ctypes.POINTER(WordLmTable), c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]
+    lib.asr_context_score_f32.argtypes = [c_i, c_i, ctypes.POINTER(ContextTable), c_p, c_p, c_i64, c_p, c_p, c_p, c_p]
+    lib.asr_ctc_beam_ctx_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, ctypes.POINTER(ContextTable), c_p, c_f, c_i, c_p, c_p,
+                                         c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]
     lib.asr_ctc_beam_wlm_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, ctypes.POINTER(WordLmTable), c_f, c_f, c_i, c_i, c_p, c_p,
                                          c_p, c_p, c_p, c_p, c_p, c_p]
     lib.asr_fbank_num_frames.argtypes = [c_i64, c_i, c_i, ctypes.POINTER(c_i64)]
@@ -1655,6 +1666,90 @@ def ctc_beam_wlm(logits, frame_lens, K, table, alpha, beta, eos_term, lexicon_on
     check(rc, "asr_ctc_beam_wlm_f32")
     LAUNCHES["ctc_beam_wlm"] += 1
     LAUNCHES["ctc_beam_wlm_launch"] += 2
+
+
+_CONTEXT_DTYPES = dict(arc_off=torch.int32, arc_tok=torch.int32, arc_next=torch.int32, drow=torch.int32, dflt=torch.int32,
+                       credit=torch.float32, pending=torch.float32, root=torch.int32)
+
+
+def _context_table(table, rows, what, graph_of=None):
+    """The device form of a context (context.ContextTable after .to(device)) -> (asr_context_t, graph_of int32 [rows] on the
+    device: the caller's, or the table's own); the tensors stay the table's."""
+    t = ContextTable()
+    for name, dtype in _CONTEXT_DTYPES.items():
+        a = getattr(table, name)
+        if not (isinstance(a, torch.Tensor) and a.is_cuda):
+            raise RuntimeError("%s: the context's tables are not on the device (ContextGraph.to(device))" % what)
+        if a.dtype != dtype or not a.is_contiguous() or a.numel() == 0:
+            raise RuntimeError("%s: the context's %s must be a contiguous, non-empty %s tensor" % (what, name, dtype))
+        setattr(t, name, ptr(a))
+    shapes = dict(arc_off=table.N + 1, arc_tok=max(table.A, 1), arc_next=max(table.A, 1), drow=table.N, dflt=table.R * table.V,
+                  credit=table.N, pending=table.N, root=table.G)
+    for name, n in shapes.items():
+        if getattr(table, name).numel() != n:
+            raise RuntimeError("%s: the context's %s holds %d elements, its sizes say %d" % (what, name, getattr(table, name).numel(), n))
+    t.V, t.N, t.G, t.R, t.A = table.V, table.N, table.G, table.R, table.A
+    if graph_of is None:
+        graph_of = table.rows(rows)
+    if not (graph_of.is_cuda and graph_of.dtype == torch.int32 and graph_of.is_contiguous() and graph_of.numel() == rows):
+        raise RuntimeError("%s: graph_of must be a contiguous int32 tensor of %d rows on the device" % (what, rows))
+    return t, graph_of
+
+
+def context_score(table, ids, lens, score, tok_score=None, graph_of=None):
+    """asr_context_score_f32 (csrc/context.hip): the bias of N padded TOKEN id rows under their context graphs.
+    table: the context on the device; ids int32 [N, L] (a view with row stride >= L is taken as it is), lens int32 [N] (-1: an
+    unused slot, -inf); graph_of int32 [N] on the device (None: the table's own, one per row); score fp32 [N] and tok_score
+    (fp32 [N, L] or None) are the caller's.  One launch."""
+    if ids.dim() != 2 or ids.dtype != torch.int32 or ids.stride(1) != 1 or lens.dtype != torch.int32:
+        raise RuntimeError("context_score: ids must be int32 [N, L] with unit column stride, lens int32")
+    N, L = ids.shape
+    t, graph_of = _context_table(table, N, "context_score", graph_of)
+    if lens.numel() != N or score.numel() != N or not (lens.is_contiguous() and score.is_contiguous()) or \
+            score.dtype != torch.float32:
+        raise RuntimeError("context_score: lens and score must be contiguous with %d elements" % N)
+    if tok_score is not None and (tuple(tok_score.shape) != (N, L) or not tok_score.is_contiguous() or
+                                  tok_score.dtype != torch.float32):
+        raise RuntimeError("context_score: tok_score must be contiguous fp32 [%d, %d]" % (N, L))
+    rc = load().asr_context_score_f32(N, L, ctypes.byref(t), ptr(graph_of), ptr(ids), int(ids.stride(0)), ptr(lens), ptr(score),
+                                      ptr(tok_score) if tok_score is not None else None, stream())
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("context_score: a context of %d states, %d graphs, %d rows x %d tokens" % (t.N, t.G, t.R, t.V))
+    check(rc, "asr_context_score_f32")
+    LAUNCHES["context_score"] += 1
+
+
+def ctc_beam_ctx(logits, frame_lens, K, context, ctx_weight, table, alpha, beta, eos_term, hyp, hyp_len, score, ctc_score,
+                 lm_score, ctx_score, ws):
+    """asr_ctc_beam_ctx_f32 (csrc/ctc_beam.hip): ctc_beam (table None; lm_score None) or ctc_beam_lm (table: the
+    n-gram LM on the device) with the context `context` (context.ContextTable on the device, one graph per utterance) inside
+    the search - a candidate ranks by its rank without a context plus ctx_weight bias.  The arguments and outputs of
+    ctc_beam_lm, and ctx_score fp32 [B, K]: the bias of every hypothesis.  Two launches."""
+    logits, ld = _ctc_view(logits, "ctc logits")
+    B, T, V = logits.shape
+    if context.V != V:
+        raise UnsupportedShape("ctc_beam_ctx: the context is over %d tokens, the logits are over %d" % (context.V, V))
+    t, graph_of = _context_table(context, B, "ctc_beam_ctx")
+    logp = nxt = None
+    S = 0
+    if table is not None:
+        logp, nxt, S = _ngram_table(table, V, "ctc_beam_ctx")
+    need = ctc_beam_ws_bytes(B, T, V, K)
+    outs = (hyp_len, score, ctc_score, ctx_score) + ((lm_score,) if table is not None else ())
+    if ws.numel() * 4 < need or tuple(hyp.shape) != (B, K, T) or any(o.numel() != B * K for o in outs):
+        raise RuntimeError("ctc_beam_ctx: the workspace or an output is smaller than B %d, T %d, beam %d need" % (B, T, K))
+    if not (hyp.is_contiguous() and all(o.is_contiguous() for o in outs)):
+        raise RuntimeError("ctc_beam_ctx: the outputs must be contiguous")
+    rc = load().asr_ctc_beam_ctx_f32(B, T, V, int(K), ptr(logits), int(ld), ptr(frame_lens), ctypes.byref(t), ptr(graph_of),
+                                     float(ctx_weight), S, ptr(logp) if S else None, ptr(nxt) if S else None,
+                                     int(table.start) if S else 0, int(table.eos) if S and eos_term else -1, float(alpha),
+                                     float(beta), ptr(hyp), ptr(hyp_len), ptr(score), ptr(ctc_score),
+                                     ptr(lm_score) if S else None, ptr(ctx_score), ptr(ws), stream())
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("ctc_beam_ctx: B %d, T %d, V %d, beam %d, a context over %d tokens, %d LM states" % (B, T, V, K, context.V, S))
+    check(rc, "asr_ctc_beam_ctx_f32")
+    LAUNCHES["ctc_beam_ctx"] += 1
+    LAUNCHES["ctc_beam_ctx_launch"] += 2
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -590,9 +590,22 @@ class Decoder(torch.nn.Module):
         if self.pad != 0:
             raise ValueError("the word LM keeps id 0 for the CTC blank; pad is %d" % self.pad)
 
+    def check_context(self, context, word_lm=None):
+        """ValueError unless context (a context.ContextGraph or ContextBatch, or None) is over the decoder's vocabulary, <PAD>
+        = 0 is free to be the CTC blank, and no word LM is given beside it."""
+        if context is None:
+            return
+        if word_lm is not None:
+            raise ValueError("a context beside the word LM is not built: pass context with ngram, or alone")
+        V = self.output_layer.weight.shape[0]
+        if context.V != V:
+            raise ValueError("the context is over %d tokens, the decoder predicts %d" % (context.V, V))
+        if self.pad != 0:
+            raise ValueError("the context keeps id 0 for the CTC blank; pad is %d" % self.pad)
+
     def rescore_ctc_beams(self, enc_pad, enc_len, ctc_logits, ctc_lens, topk, ctc_weight=0.5, length_penalty=0.0, *, lm=None,
                           lm_weight=0.0, ngram=None, ngram_weight=0.0, ngram_bonus=0.0, word_lm=None, word_lm_weight=0.0,
-                          word_bonus=0.0, lexicon_only=False, eos_term=True):
+                          word_bonus=0.0, lexicon_only=False, eos_term=True, context=None, ctx_weight=1.0):
         """Two-pass decoding behind the encoder (E2E.recognize_two_pass): ops.ctc_beam over ctc_logits [B, T', V]
         (raw logits of a CTC head on enc_pad, blank = <PAD> = 0; ctc_lens int32 [B] on the device), score_hypotheses over
         the B topk rows, with lm and lm_weight != 0 LM.forward over the same rows, then the combination
@@ -608,17 +621,26 @@ class Decoder(torch.nn.Module):
         (lexicon_only and eos_term are the search's), and the combination is
         ((((1 - w) att + w ctc) + lm_weight lm) + word_lm_weight lm_word) + word_bonus n_words, then / (len + 1)**length_penalty:
         fp32, the two products and the two sums of the word term each rounded on their own, where the n-gram term stands;
-        the parts then also hold word_lm (lm_word), n_words and rank."""
+        the parts then also hold word_lm (lm_word), n_words and rank.
+        With context (a context.ContextGraph or ContextBatch) the first pass searches with the phrase lists
+        inside, alone or beside ngram, and the combination gains + ctx_weight ctx_score (the search's bias of the hypothesis)
+        behind the n-gram term, one product and one sum; the parts then also hold context (ctx_score) and rank."""
         K, w = int(topk), float(ctc_weight)
         if self.pad != 0:
             raise ValueError("the CTC search takes <PAD> = 0 as its blank; pad is %d" % self.pad)
         self.check_lm(lm)
         self.check_ngram(ngram)
+        self.check_context(context, word_lm)
         self.check_word_lm(word_lm, ngram)
         use_lm = lm is not None and float(lm_weight) != 0.0
         with torch.no_grad():
-            ng = rank = n_words = None
-            if word_lm is not None:
+            ng = rank = n_words = cx = None
+            if context is not None:
+                beams = ops.ctc_beam(ctc_logits, ctc_lens, K, ngram=ngram, ngram_weight=ngram_weight, ngram_bonus=ngram_bonus,
+                                     eos_term=True, context=context, ctx_weight=ctx_weight)
+                hyp, hyp_len, rank, ctc = beams[:4]
+                ng, cx = (beams[4] if ngram is not None else None), beams[-1]
+            elif word_lm is not None:
                 hyp, hyp_len, rank, ctc, ng, n_words = ops.ctc_beam(ctc_logits, ctc_lens, K, word_lm=word_lm,
                                                                     word_lm_weight=word_lm_weight, word_bonus=word_bonus,
                                                                     lexicon_only=lexicon_only, eos_term=eos_term)
@@ -649,6 +671,8 @@ class Decoder(torch.nn.Module):
             if word_lm is not None:
                 total = total + ng * float(torch.tensor(float(word_lm_weight), dtype=torch.float32))
                 total = total + n_words.clamp(min=0).to(torch.float32) * float(torch.tensor(float(word_bonus), dtype=torch.float32))
+            if context is not None:
+                total = total + cx * float(torch.tensor(float(ctx_weight), dtype=torch.float32))
             if float(length_penalty) != 0.0:
                 total = total / (hyp_len.clamp(min=0) + 1).to(torch.float32).pow(float(length_penalty))
             total = torch.where(hyp_len >= 0, total, torch.full_like(total, float("-inf")))
@@ -660,6 +684,8 @@ class Decoder(torch.nn.Module):
             parts.update(ngram=ng, rank=rank)
         if word_lm is not None:
             parts.update(word_lm=ng, n_words=n_words, rank=rank)
+        if context is not None:
+            parts.update(context=cx, rank=rank)
         return tokens, scores, parts
 
 
@@ -1029,7 +1055,7 @@ class E2E(torch.nn.Module):
         return K
 
     def recognize_ctc_beams(self, xs, ilens, topk, nbest=False, *, ngram=None, ngram_weight=0.0, ngram_bonus=0.0, word_lm=None,
-                            word_lm_weight=0.0, word_bonus=0.0, lexicon_only=False, eos_term=True):
+                            word_lm_weight=0.0, word_bonus=0.0, lexicon_only=False, eos_term=True, context=None, ctx_weight=1.0):
         """CTC prefix beam search with the CTC head alone (not a reference method): encoder, the head,
         ops.ctc_beam with beam width topk (1..16) -> (ids, scores): per utterance the best label sequence (an id list) and
         its log-mass; with nbest=True per utterance the ranked list of all hypotheses the search kept (at most topk) and
@@ -1040,13 +1066,21 @@ class E2E(torch.nn.Module):
         With word_lm (a word_lm.WordLM spelled in the decoder's vocabulary) the lexicon and the word LM sit
         inside the search: hypotheses rank by (log-mass + word_lm_weight lm) + word_bonus n_words, lexicon_only keeps only
         sequences of lexicon words (an utterance may then keep no hypothesis: an empty list; without nbest the empty id
-        list at -inf); self.last_ctc_beams then holds ctc_score, lm_score and n_words too."""
+        list at -inf); self.last_ctc_beams then holds ctc_score, lm_score and n_words too.
+        With context (a context.ContextGraph for every utterance, or a context.ContextBatch naming a graph per utterance;
+        DESIGN 4.32) the phrase lists sit inside the search, alone or beside ngram: a hypothesis ranks by its rank without a
+        context plus ctx_weight bias; self.last_ctc_beams then ends with ctx_score, the bias of every hypothesis."""
         K = self._beam_width(topk)
         self.decoder.check_ngram(ngram)
+        self.decoder.check_context(context, word_lm)
         self.decoder.check_word_lm(word_lm, ngram)
         with torch.no_grad():
             logits, lens_dev, _ = self._ctc_logits(xs, ilens, "recognize_ctc_beams")
-            if word_lm is not None:
+            if context is not None:
+                beams = ops.ctc_beam(logits, lens_dev, K, ngram=ngram, ngram_weight=ngram_weight, ngram_bonus=ngram_bonus,
+                                     eos_term=True, context=context, ctx_weight=ctx_weight)
+                hyp, hyp_len, score = beams[:3]
+            elif word_lm is not None:
                 beams = ops.ctc_beam(logits, lens_dev, K, word_lm=word_lm, word_lm_weight=word_lm_weight, word_bonus=word_bonus,
                                      lexicon_only=lexicon_only, eos_term=eos_term)
                 hyp, hyp_len, score = beams[:3]
@@ -1086,6 +1120,27 @@ class E2E(torch.nn.Module):
         score, n_words = ops.word_lm_score(word_lm, flat, first, eos_term=eos_term)
         return score.view(ids.shape[:-1]), n_words.view(ids.shape[:-1])
 
+    def context_score(self, context, ids, graph_of=None):
+        """The bias (ops.context_score) of hypotheses this model produced under a context.ContextGraph or
+        ContextBatch: ids as E2E.ngram_score takes them (a device tensor [..., L], <EOS>-padded, a row counting up to its
+        first <EOS> - or a list of id lists); graph_of: the graph of every row (a list or an int32 tensor; None: the
+        context's own list, or its one graph).  -> fp32 [...] on the device."""
+        self.decoder.check_context(context)
+        dev = next(self.parameters()).device
+        if graph_of is not None and not isinstance(graph_of, torch.Tensor):
+            graph_of = hb.to_device_i32([int(g) for g in graph_of], dev)
+        if not isinstance(ids, torch.Tensor):
+            rows = [[int(c) for c in row] for row in ids]
+            L = max([len(r) for r in rows] + [1])
+            flat = torch.tensor([r + [self.decoder.eos] * (L - len(r)) for r in rows], dtype=torch.int32).to(dev)
+            lens = hb.to_device_i32([len(r) for r in rows], dev)
+            return ops.context_score(context, flat, lens, graph_of=graph_of)
+        L = ids.shape[-1]
+        flat = ids.reshape(-1, L)
+        is_eos = flat == self.decoder.eos
+        first = torch.where(is_eos.any(dim=1), is_eos.to(torch.int32).argmax(dim=1), torch.full_like(flat[:, 0], L)).to(torch.int32)
+        return ops.context_score(context, flat, first, graph_of=graph_of).view(ids.shape[:-1])
+
     def ngram_score(self, ngram, ids, eos_term=True):
         """The n-gram LM's log-probability (ops.ngram_score) of hypotheses this model produced, to rescore any
         list with: ids a device tensor [..., L] of label ids, <EOS>-padded as recognize_beams(nbest=True) and
@@ -1107,7 +1162,7 @@ class E2E(torch.nn.Module):
 
     def recognize_two_pass(self, xs, ilens, topk, ctc_weight=0.5, length_penalty=0.0, nbest=False, *, lm=None, lm_weight=0.0,
                            ngram=None, ngram_weight=0.0, ngram_bonus=0.0, word_lm=None, word_lm_weight=0.0, word_bonus=0.0,
-                           lexicon_only=False, eos_term=True):
+                           lexicon_only=False, eos_term=True, context=None, ctx_weight=1.0):
         """Two-pass decoding (not a reference method): the CTC prefix beam search of the head proposes topk
         (1..16) hypotheses per utterance, ONE teacher-forced pass of the attention decoder over the B topk rows scores them
         (Decoder.score_hypotheses), and with lm (an LM module) and lm_weight != 0 one teacher-forced pass of the LM too.
@@ -1123,7 +1178,10 @@ class E2E(torch.nn.Module):
         order, with ctc the search's ctc_score and lm_ngram its lm_score (parts: also ngram and rank).
         With word_lm (a word_lm.WordLM) the first pass is the search with the lexicon and the word LM inside, and
         the score gains + word_lm_weight lm_word + word_bonus n_words where the n-gram term stands, before the length
-        penalty (parts: also word_lm, n_words and rank)."""
+        penalty (parts: also word_lm, n_words and rank).
+        With context (a context.ContextGraph or ContextBatch) the first pass searches with the phrase lists
+        inside, alone or beside ngram, and the score gains + ctx_weight ctx_score behind the n-gram term (parts: also
+        context and rank)."""
         K = self._beam_width(topk)
         w = float(ctc_weight)
         if not 0.0 <= w <= 1.0:
@@ -1131,11 +1189,14 @@ class E2E(torch.nn.Module):
         dec = self.decoder
         dec.check_lm(lm)
         dec.check_ngram(ngram)
+        dec.check_context(context, word_lm)
         dec.check_word_lm(word_lm, ngram)
         extra = {} if ngram is None else dict(ngram=ngram, ngram_weight=ngram_weight, ngram_bonus=ngram_bonus)
         if word_lm is not None:
             extra = dict(word_lm=word_lm, word_lm_weight=word_lm_weight, word_bonus=word_bonus, lexicon_only=lexicon_only,
                          eos_term=eos_term)
+        if context is not None:
+            extra.update(context=context, ctx_weight=ctx_weight)
         with torch.no_grad():
             logits, lens_dev, enc_lens, enc_h = self._encode_ctc(xs, ilens, "recognize_two_pass")
             tokens, scores, parts = dec.rescore_ctc_beams(enc_h, enc_lens, logits, lens_dev, K, ctc_weight=w,

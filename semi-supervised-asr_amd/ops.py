@@ -1054,7 +1054,7 @@ class _RnntJoint(torch.autograd.Function):
 
 
 def rnnt_joint(pe, pp, frame_lens_dev, label_lens):
-    """-> Z [B, T, U + 1, J] = tanh(pe[b, t] + pp[b, u]) for t < T_b, u <= U_b, exact zeros elsewhere (DESIGN 4.27).  pe
+    """-> Z [B, T, U + 1, J] = tanh(pe[b, t] + pp[b, u]) for t < T_b, u <= U_b, exact zeros elsewhere (DESIGN 4.32).  pe
     [B, T, J] and pp [B, U + 1, J] fp32 (the two projections, from ops.linear), frame_lens_dev int32 [B] on the device
     (Encoder.last_lens_dev), label_lens the label counts per utterance (host integers; U = their maximum).  J a multiple of
     4: hb.UnsupportedShape otherwise."""
@@ -1108,7 +1108,7 @@ class _RnntLoss(torch.autograd.Function):
 
 
 def rnnt_loss(logits, frame_lens_dev, labels_packed, label_lens):
-    """-> nll [B], the transducer negative log-likelihood of each utterance (DESIGN 4.27).  logits [B, T, U + 1, V] fp32 raw
+    """-> nll [B], the transducer negative log-likelihood of each utterance (DESIGN 4.32).  logits [B, T, U + 1, V] fp32 raw
     (not log-softmaxed; a view with row stride >= V is taken as it is), frame_lens_dev int32 [B] on the device
     (Encoder.last_lens_dev; an encoder gives every T_b >= 1), labels_packed the batch's labels as ONE int64 device tensor,
     label_lens their counts per utterance (host integers; U = their maximum).  Blank = 0.  Every utterance with a frame has
@@ -1255,7 +1255,7 @@ def ctc_greedy(logits, frame_lens_dev):
 
 
 def ctc_beam(logits, frame_lens_dev, beam, ngram=None, ngram_weight=0.0, ngram_bonus=0.0, eos_term=True, *, word_lm=None,
-             word_lm_weight=0.0, word_bonus=0.0, lexicon_only=False):
+             word_lm_weight=0.0, word_bonus=0.0, lexicon_only=False, context=None, ctx_weight=1.0):
     """-> (hyp int32 [B, beam, T'] padded with -1, hyp_len int32 [B, beam] with -1 in unused slots, score fp32 [B, beam]
     descending with -inf in unused slots): the CTC prefix beam search of raw logits [B, T', V] (blank = 0), asr_ctc_beam_f32
     (csrc/ctc_beam.hip), two launches.  Forward only, no host synchronisation.
@@ -1266,9 +1266,15 @@ def ctc_beam(logits, frame_lens_dev, beam, ngram=None, ngram_weight=0.0, ngram_b
     With word_lm (a word_lm.WordLM, or its table on the device) the lexicon and the word-level LM sit inside the search
     (asr_ctc_beam_wlm_f32, DESIGN 4.25, two launches): candidates rank by (tot + word_lm_weight lm) + word_bonus n_words with
     lm the sum over the completed words; lexicon_only keeps only sequences of lexicon words -> (hyp, hyp_len, score,
-    ctc_score, lm_score, n_words int32 [B, beam] with -1 in unused slots).  ngram and word_lm together: ValueError."""
+    ctc_score, lm_score, n_words int32 [B, beam] with -1 in unused slots).  ngram and word_lm together: ValueError.
+    With context (a context.ContextGraph for all rows, or a context.ContextBatch with one graph index per row) the phrase
+    lists sit inside the search, alone or beside ngram (asr_ctc_beam_ctx_f32, DESIGN 4.32, two launches): a candidate ranks
+    by its rank without a context plus ctx_weight bias -> (hyp, hyp_len, score: the rank, ctc_score[, lm_score], ctx_score
+    fp32 [B, beam]: the bias, ops.context_score of the hypothesis bit for bit).  context with word_lm: ValueError."""
     if ngram is not None and word_lm is not None:
         raise ValueError("ctc_beam: ngram and word_lm are two LMs for one search: pass one of them")
+    if context is not None and word_lm is not None:
+        raise ValueError("ctc_beam: a context beside the word LM is not built: pass context with ngram, or alone")
     logits = logits.detach()
     B, T, V = logits.shape
     K, dev = int(beam), logits.device
@@ -1276,6 +1282,13 @@ def ctc_beam(logits, frame_lens_dev, beam, ngram=None, ngram_weight=0.0, ngram_b
     hyp = torch.empty(B, K, T, device=dev, dtype=torch.int32)
     hyp_len = torch.empty(B, K, device=dev, dtype=torch.int32)
     score = torch.empty(B, K, device=dev, dtype=torch.float32)
+    if context is not None:
+        ctc_score, ctx_score = torch.empty_like(score), torch.empty_like(score)
+        lm_score = torch.empty_like(score) if ngram is not None else None
+        hb.ctc_beam_ctx(logits, frame_lens_dev, K, _context_table(context, dev, B), float(ctx_weight),
+                        _ngram_table(ngram, dev) if ngram is not None else None, float(ngram_weight), float(ngram_bonus),
+                        bool(eos_term), hyp, hyp_len, score, ctc_score, lm_score, ctx_score, ws)
+        return (hyp, hyp_len, score, ctc_score) + ((lm_score,) if ngram is not None else ()) + (ctx_score,)
     if ngram is None and word_lm is None:
         hb.ctc_beam(logits, frame_lens_dev, K, hyp, hyp_len, score, ws)
         return hyp, hyp_len, score
@@ -1368,6 +1381,39 @@ def rnnt_beam(pe, frame_lens_dev, w_gate, b_gate, w_pred, w_out, b_out, emb, bos
 def _ngram_table(ngram, dev):
     """An ngram.NgramLM (compiled and uploaded once per device) or an ngram.NgramTable -> the table on dev."""
     return ngram.to(dev)
+
+
+def _context_table(context, dev, rows):
+    """A context.ContextGraph / ContextBatch (compiled and uploaded once per device) or a context.ContextTable -> the table on
+    dev; ValueError when a batch lists its graphs for another number of rows."""
+    table = context.to(dev)
+    table.rows(rows)
+    return table
+
+
+def context_score(context, ids, lens, graph_of=None, per_token=False):
+    """-> score fp32 [N] (and with per_token the deltas fp32 [N, L]): the bias of the padded TOKEN id rows ids [N, L] (int32
+    or int64, on the device) with lens int32 [N] (-1: an unused slot, -inf) under their context graphs:
+    asr_context_score_f32 (csrc/context.hip), one launch.  graph_of: an int32 tensor [N] on the device naming
+    the graph of every row (-1: none, bias 0); None: the context's own list (a ContextBatch over N rows), or its one graph
+    for every row (a ContextGraph).  An id outside 1 .. V-1 inside the length gives NaN for that row.  No host
+    synchronisation."""
+    ids = ids.detach()
+    if ids.dtype != torch.int32:
+        ids = ids.to(torch.int32)
+    if ids.dim() != 2:
+        raise ValueError("context_score: ids must be [N, L], got %r" % (tuple(ids.shape),))
+    if ids.stride(1) != 1:
+        ids = ids.contiguous()
+    N, L = ids.shape
+    dev = ids.device
+    table = context.to(dev)
+    if graph_of is not None:
+        graph_of = graph_of.to(device=dev, dtype=torch.int32).contiguous()
+    score = torch.empty(N, device=dev, dtype=torch.float32)
+    tok = torch.empty(N, L, device=dev, dtype=torch.float32) if per_token else None
+    hb.context_score(table, ids, lens.to(torch.int32).contiguous(), score, tok, graph_of=graph_of)
+    return (score, tok) if per_token else score
 
 
 def ngram_score(ngram, ids, lens, eos_term=True, per_token=False):

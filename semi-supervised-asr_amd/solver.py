@@ -558,6 +558,43 @@ class Solver(object):
         return path, config.get("lexicon"), float(config.get("word_lm_weight", 0.0) or 0.0), \
             float(config.get("word_bonus", 0.0) or 0.0), bool(config.get("lexicon_only", False))
 
+    CONTEXT_BIAS_KEYS = ("phrases", "boost", "weight", "word_start_only")
+
+    @staticmethod
+    def context_config(config, two_pass, ctc_beam):
+        """`context_bias` (not a reference key; absent by default): `{phrases, boost, weight, word_start_only}` -
+        `phrases` the path of a file with one phrase per line in the vocabulary's symbols and an optional trailing boost,
+        `boost` the per-token boost of a line without one (default 1), `weight` what the bias is weighed by in the rank
+        (default 1), `word_start_only` (default false) lets a phrase begin only at the start or behind <space>.  The list
+        sits inside the CTC prefix beam search (`ctc_beam_decode`) or the first pass and the combination of
+        `two_pass_decode`, alone or beside `ngram_lm`.  -> the sub-dictionary or None.  ValueError: with any other decoder,
+        beside `word_lm`, without `phrases` or with a key that is none of these."""
+        sub = config.get("context_bias")
+        if sub is None:
+            return None
+        if not isinstance(sub, dict) or not sub.get("phrases"):
+            raise ValueError("context_bias is a dictionary {phrases: <file>, boost, weight, word_start_only} with phrases set")
+        unknown = [k for k in sub if k not in Solver.CONTEXT_BIAS_KEYS]
+        if unknown:
+            raise ValueError("context_bias: unknown key(s) %s (known: %s)" % (", ".join(unknown), ", ".join(Solver.CONTEXT_BIAS_KEYS)))
+        if not (ctc_beam or two_pass):
+            raise ValueError("context_bias is used by the CTC prefix beam search: set ctc_beam_decode or two_pass_decode - the "
+                             "other decoders have no place for it")
+        if config.get("word_lm") is not None:
+            raise ValueError("context_bias beside word_lm is not built: use it alone or with ngram_lm")
+        return sub
+
+    def load_context(self, sub):
+        """The ContextGraph of a `context_bias` dictionary over this vocabulary's symbols."""
+        from context import ContextGraph
+        space = None
+        if sub.get("word_start_only"):
+            if "<space>" not in self.vocab:
+                raise ValueError("context_bias: word_start_only needs <space> in the vocabulary")
+            space = self.vocab["<space>"]
+        return ContextGraph.from_text(sub["phrases"], self.vocab, boost=float(sub.get("boost", 1.0) or 1.0), V=len(self.vocab),
+                                      word_start_only=space)
+
     def load_word_lm(self, path, lexicon_path=None):
         """The WordLM of an ARPA file over words spelled in this vocabulary's one-character symbols, split at <space>."""
         from word_lm import WordLM
@@ -764,6 +801,12 @@ class Solver(object):
         if wlm_path is not None:
             ngram = dict(word_lm=self.load_word_lm(wlm_path, lexicon_path), word_lm_weight=wlm_w, word_bonus=word_bonus,
                          lexicon_only=lexicon_only)
+        # `context_bias` (not a reference key): a phrase list inside the CTC prefix beam search; absent, nothing
+        # below differs
+        ctx_sub = self.context_config(self.config, two_pass, ctc_beam and not rnnt_beam)
+        if ctx_sub is not None:
+            weight = ctx_sub.get("weight", 1.0)
+            ngram = dict(self._lm_kwargs(ngram), context=self.load_context(ctx_sub), ctx_weight=float(1.0 if weight is None else weight))
         if rnnt_beam and self.config.get("rnnt_word_lm") is not None:
             # `rnnt_word_lm` (not a reference key): the lexicon and the word LM inside the transducer search
             rw = self.config["rnnt_word_lm"]
