@@ -7,15 +7,15 @@
 //   beam_reorder  one workgroup per beam row: the next step's input slot gathers its predecessor's z, ctx, cell state
 //                 and attention weights (out of place: source and destination are different step slots) and the
 //                 embedding of its new token;
-// With a language model (shallow fusion) the select kernel's LM variant adds lm_weight * log_softmax(lm_logits)
-// to every candidate, and beam_reorder_lm gathers the LM's h / c of every layer (and the decoder's state) in one launch.
-// With the CTC prefix score (joint CTC-attention decoding; csrc/ctc_prefix.hip computes psi) the select kernel's
-// CTC variants rank score + (1 - w) logp + w (psi - psi_prev) (+ lm_weight * logp_lm).
-// With an n-gram automaton or a lexicon and word-level LM inside the search beam_select_tlm, a sibling of the
-// select kernel on the same list helpers, ranks (base' + weight lm') + bonus len' (word LM: nw') where base' is the variant's
-// candidate above: scores keeps base, the LM position of every beam row and the parts of the finished entries live in the
-// caller's extra workspace, one thread per live entry does the word LM's lookups up front, and the walker thread writes the
-// new positions in place - the reorder kernels are used as they are.  The plain select's instantiations are untouched.
+// One select kernel serves every mode.  Each candidate's value is beam_base: score + logp, with a language model (shallow
+// fusion) + lm_weight * log_softmax(lm_logits), with the CTC prefix score (joint CTC-attention decoding, DESIGN
+// 4.15; csrc/ctc_prefix.hip computes psi) score + (1 - w) logp + w (psi - psi_prev) (+ the LM's term).  beam_reorder_lm gathers
+// the LM's h / c of every layer (and the decoder's state) in one launch.
+// With an n-gram automaton or a lexicon and word-level LM inside the search (KIND) the kernel ranks
+// (base' + weight lm') + bonus len' (word LM: nw') where base' is beam_base: scores keeps base, the LM position of every beam
+// row and the parts of the finished entries live in the caller's extra workspace, one thread per live entry does the word LM's
+// lookups up front, one thread per winner forms its parts again, and the walker thread writes the new positions in place - the
+// reorder kernels are used as they are.  Without such an LM none of that state exists (if constexpr, arrays of the mode's size).
 // And once at the end
 //   beam_backtrack  one workgroup per utterance: rank the finished hypotheses, follow the backpointers into token rows.
 #include <float.h>
@@ -29,11 +29,7 @@ constexpr int BEAM_WAVES = BEAM_NT / 64;
 constexpr int BEAM_KMAX = ASR_BEAM_KMAX;
 constexpr int BEAM_FCAP = ASR_BEAM_FCAP;   // finished entries per utterance (< 2K can be held: include/asr_hip.h)
 
-// M: the per-thread candidate list length, a power of two >= 2K.  LM: candidates are score + logp + lmw * logp_lm (each
-// operation rounded on its own, in this order); without it lm_logits / lmw are not read and the code is the plain select's.
-// CTC: the candidate starts as score + (1 - w) * logp, then + w * (psi - psi_prev), then the LM's term - every operation
-// rounded on its own again; without it the kernel has no CTC argument at all (an empty structure) and its code is the
-// plain / LM select's.
+// CTC: the candidate carries the prefix score's term; without it the kernel has no CTC argument at all (an empty structure)
 template <bool CTC>
 struct beam_ctc_args {
   const float* psi;        // [B*K][V]
@@ -43,127 +39,13 @@ struct beam_ctc_args {
 template <>
 struct beam_ctc_args<false> {};
 
-template <int M, bool LM, bool CTC>
-__global__ __launch_bounds__(BEAM_NT) void beam_select_kernel(asr_beam_t p, int t, const float* __restrict__ lm_logits,
-                                                              float lmw, beam_ctc_args<CTC> ca) {
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int K = p.K, V = p.V, B = p.B;
-  if (p.done[b]) return;                                   // finished utterances are left untouched
-  __shared__ float s_score[BEAM_KMAX], s_max[BEAM_KMAX], s_lsum[BEAM_KMAX];
-  __shared__ float s_lmmax[LM ? BEAM_KMAX : 1], s_lmlsum[LM ? BEAM_KMAX : 1];
-  __shared__ float red_v[2][BEAM_WAVES];
-  __shared__ int red_i[2][BEAM_WAVES];
-  __shared__ float top_v[2 * BEAM_KMAX];
-  __shared__ int top_i[2 * BEAM_KMAX];
-  __shared__ int s_ntop;
-  if (tid < K) s_score[tid] = p.scores[(int64_t)b * K + tid];
-  __syncthreads();
-
-  // log-softmax statistics of every live beam's row: max and log(sum exp(x - max)), one wave per row
-  const float* lg = p.logits + (int64_t)b * K * V;
-  for (int k = wave; k < K; k += BEAM_WAVES) {
-    if (s_score[k] == -INFINITY) continue;                 // wave-uniform
-    float m, s;
-    wave_row_max_sumexp(lg + (int64_t)k * V, V, lane, m, s);
-    if (lane == 0) { s_max[k] = m; s_lsum[k] = logf(s); }
-    if (LM) {
-      wave_row_max_sumexp(lm_logits + ((int64_t)b * K + k) * V, V, lane, m, s);
-      if (lane == 0) { s_lmmax[k] = m; s_lmlsum[k] = logf(s); }
-    }
-  }
-  __syncthreads();
-
-  // every thread keeps its best M candidates (score desc, flat index k*V+v asc on ties), visiting flat indices in
-  // increasing order
-  float lv[M];
-  int li[M];
-  top_clear(lv, li);
-  for (int k = 0; k < K; ++k) {
-    const float sc = s_score[k];
-    if (sc == -INFINITY) continue;
-    const float m = s_max[k], ls = s_lsum[k];
-    const float* row = lg + (int64_t)k * V;
-    const float* lrow = LM ? lm_logits + ((int64_t)b * K + k) * V : nullptr;
-    const float lmm = LM ? s_lmmax[k] : 0.f, lml = LM ? s_lmlsum[k] : 0.f;
-    const float* prow = nullptr;
-    float pprev = 0.f, omw = 0.f, cw = 0.f;
-    if constexpr (CTC) {
-      prow = ca.psi + ((int64_t)b * K + k) * V;
-      pprev = ca.psi_prev[b * K + k], cw = ca.w, omw = __fsub_rn(1.f, cw);
-    }
-    for (int v = tid; v < V; v += BEAM_NT) {
-      float c = sc + ((row[v] - m) - ls);
-      if (CTC) {
-        c = __fadd_rn(sc, __fmul_rn(omw, (row[v] - m) - ls));
-        c = __fadd_rn(c, __fmul_rn(cw, __fsub_rn(prow[v], pprev)));
-      }
-      if (LM) c = __fadd_rn(c, __fmul_rn(lmw, (lrow[v] - lmm) - lml));   // no fused multiply-add: the order is the contract
-      top_insert(lv, li, c, k * V + v);
-    }
-  }
-
-  // merge: 2K rounds of a workgroup arg-best over the list heads; the owner of the winner pops its head
-  const int want = 2 * K;
-  int ntop = 0;
-  for (int r = 0; r < want; ++r) {
-    float v;
-    int i;
-    top_round(lv[0], li[0], red_v[r & 1], red_i[r & 1], BEAM_WAVES, v, i);
-    if (v == -INFINITY) break;                              // fewer than 2K finite candidates (uniform)
-    top_pop_if_head(lv, li, i);
-    if (tid == 0) { top_v[r] = v; top_i[r] = i; }
-    ntop = r + 1;
-  }
-  if (tid == 0) s_ntop = ntop;
-  __syncthreads();
-  if (tid != 0) return;
-
-  // the fairseq walk over the ranked candidates (a handful of entries: one thread)
-  ntop = s_ntop;
-  const int64_t hb = ((int64_t)t * B + b) * K;
-  int nf = p.nfin[b], nlive = 0;
-  for (int r = 0; r < ntop; ++r) {
-    const int idx = top_i[r];
-    const int k = idx / V, v = idx - k * V;
-    if (v == p.eos) {
-      if (r < K) {
-        int4* f = reinterpret_cast<int4*>(p.fin) + (int64_t)b * BEAM_FCAP + nf;
-        *f = make_int4(t, k, t + 1, 1);
-        p.fin_score[(int64_t)b * BEAM_FCAP + nf] = top_v[r];
-        ++nf;
-      }
-    } else if (nlive < K) {
-      p.tok_hist[hb + nlive] = v;
-      p.bp_hist[hb + nlive] = k;
-      p.scores[(int64_t)b * K + nlive] = top_v[r];
-      ++nlive;
-    }
-  }
-  for (int j = nlive; j < K; ++j) {                         // dead slots: a valid token and predecessor, score -inf
-    p.tok_hist[hb + j] = p.eos;
-    p.bp_hist[hb + j] = 0;
-    p.scores[(int64_t)b * K + j] = -INFINITY;
-  }
-  if (t == p.L - 1 && nf < K) {                             // max_dec_timesteps: the live beams finish as they stand
-    for (int j = 0; j < nlive; ++j) {
-      int4* f = reinterpret_cast<int4*>(p.fin) + (int64_t)b * BEAM_FCAP + nf;
-      *f = make_int4(t, j, t + 1, 0);
-      p.fin_score[(int64_t)b * BEAM_FCAP + nf] = p.scores[(int64_t)b * K + j];
-      ++nf;
-    }
-  }
-  p.nfin[b] = nf;
-  if (nf >= K || t == p.L - 1 || nlive == 0) {
-    p.done[b] = 1;
-    atomicAdd(p.ndone, 1);
-  }
-}
-
 // ---- an n-gram or a word-level LM inside the search ----------------------------------------------------------
 // The caller's extra workspace beside asr_beam_t: the LM position of every beam row and the parts of the finished entries.
 //   a / b     n-gram: the automaton state / unused;  word LM: the trie node of the pending word / the word state
 //   lm, n     the LM's fp32 sum;  n-gram: the non-<EOS> tokens (len);  word LM: the completed words (nw)
-constexpr int TLM_NGRAM = 1, TLM_WORD = 2;
+// Without such an LM (TLM_NONE) the select kernel's argument is the empty structure.
+constexpr int TLM_NONE = 0, TLM_NGRAM = 1, TLM_WORD = 2;
+template <bool ON>
 struct BeamTlm {
   const float* logp;       // n-gram: [S][V]
   const int32_t* next;
@@ -176,15 +58,17 @@ struct BeamTlm {
   float *fin_base, *fin_lm;   // [B][BEAM_FCAP] parts of the finished entries (p.fin_score holds their rank)
   int32_t* fin_n;
 };
+template <>
+struct BeamTlm<false> {};
 
-inline int64_t tlm_round64(int64_t n) { return (n + 63) & ~(int64_t)63; }
-inline int64_t tlm_ws_bytes(int B, int K) { return 4 * (4 * tlm_round64((int64_t)B * K) + 3 * tlm_round64((int64_t)B * BEAM_FCAP)); }
+inline int64_t tlm_ws_bytes(int B, int K) { return 4 * (4 * round64((int64_t)B * K) + 3 * round64((int64_t)B * BEAM_FCAP)); }
 
-// Today's candidate expression of the active variant, with the bits of the existing instantiations.  The rounded intrinsics
-// are plain operators to this compiler, and beam_select_kernel's loop compiles to: the judge's product fused into its sum
-// where the judge is the only extra term; no fusion with the CTC terms alone; with both, only (1 - w) logp fused into score.
-// The same is spelled out here with contraction off, so that the candidate loop and the second pass over the winners agree
-// and zero weights reproduce the search without this LM (tests/test_beam_ngram_gpu.py holds both).
+// THE candidate value of every mode: score + logp, with the judge + lmw * logp_lm, with the CTC prefix score
+// score + (1 - w) logp + w (psi - psi_prev) (+ lmw * logp_lm).  The rounded intrinsics are plain operators to this compiler, so
+// the contraction is switched off and the two fused multiply-adds this search has always had are written out: the judge's
+// product into its sum where the judge is the only extra term; with both terms, (1 - w) logp into score; none with the CTC term
+// alone.  The candidate loop and the second pass over the winners both call this, so they agree, and zero weights of an LM
+// inside the search reproduce the search without it (tests/test_beam_ngram_gpu.py holds both).
 template <bool LM, bool CTC>
 __device__ __forceinline__ float beam_base(float sc, float x, float m, float ls, float lx, float lmm, float lml, float lmw,
                                            float px, float pprev, float omw, float cw) {
@@ -231,7 +115,7 @@ struct TlmStage {
 // lm', n' and validity of candidate v from the staged entry.  n-gram: one read of the entry's table row; word LM: LDS only,
 // and with lexicon_only one read of the entry's trie_next row.
 template <int KIND>
-__device__ __forceinline__ bool tlm_candidate(const BeamTlm& g, const TlmStage& s, int v, int V, int eos, float& lm, int& n) {
+__device__ __forceinline__ bool tlm_candidate(const BeamTlm<true>& g, const TlmStage& s, int v, int V, int eos, float& lm, int& n) {
   if constexpr (KIND == TLM_NGRAM) {
     lm = __fadd_rn(s.lm, g.logp[(int64_t)s.a * V + v]);
     n = s.n + (v != eos ? 1 : 0);
@@ -254,39 +138,46 @@ __device__ __forceinline__ bool tlm_candidate(const BeamTlm& g, const TlmStage& 
   }
 }
 
+// M: the per-thread candidate list length, a power of two >= 2K.  LM, CTC: beam_base's terms; without LM lm_logits / lmw are
+// not read.  KIND: the LM inside the search; the arrays that only it needs have one element without it and, never named, take
+// no LDS.
 template <int M, bool LM, bool CTC, int KIND>
-__global__ __launch_bounds__(BEAM_NT) void beam_select_tlm_kernel(asr_beam_t p, int t, const float* __restrict__ lm_logits,
-                                                                  float lmw, beam_ctc_args<CTC> ca, BeamTlm g) {
+__global__ __launch_bounds__(BEAM_NT) void beam_select_kernel(asr_beam_t p, int t, const float* __restrict__ lm_logits,
+                                                              float lmw, beam_ctc_args<CTC> ca, BeamTlm<KIND != TLM_NONE> g) {
+  constexpr bool TLM = KIND != TLM_NONE;
+  constexpr int NK = TLM ? BEAM_KMAX : 1, NTOP = TLM ? 2 * BEAM_KMAX : 1;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = p.K, V = p.V, B = p.B;
   if (p.done[b]) return;                                   // finished utterances are left untouched
   __shared__ float s_score[BEAM_KMAX], s_max[BEAM_KMAX], s_lsum[BEAM_KMAX];
   __shared__ float s_lmmax[LM ? BEAM_KMAX : 1], s_lmlsum[LM ? BEAM_KMAX : 1];
-  __shared__ TlmStage s_pos[BEAM_KMAX];
+  __shared__ TlmStage s_pos[NK];
   __shared__ float red_v[2][BEAM_WAVES];
   __shared__ int red_i[2][BEAM_WAVES];
   __shared__ float top_v[2 * BEAM_KMAX];
   __shared__ int top_i[2 * BEAM_KMAX];
   // the parts and the new position of every ranked candidate, and the same as a hypothesis finished as it stands (t = L-1)
-  __shared__ float top_base[2 * BEAM_KMAX], top_lm[2 * BEAM_KMAX], top_erank[2 * BEAM_KMAX], top_elm[2 * BEAM_KMAX];
-  __shared__ int top_n[2 * BEAM_KMAX], top_a[2 * BEAM_KMAX], top_b[2 * BEAM_KMAX], top_en[2 * BEAM_KMAX], top_eok[2 * BEAM_KMAX];
-  __shared__ int s_ntop, live_r[BEAM_KMAX];
+  __shared__ float top_base[NTOP], top_lm[NTOP], top_erank[NTOP], top_elm[NTOP];
+  __shared__ int top_n[NTOP], top_a[NTOP], top_b[NTOP], top_en[NTOP], top_eok[NTOP];
+  __shared__ int s_ntop, live_r[NK];
   if (tid < K) {
     const float sc = p.scores[(int64_t)b * K + tid];
     s_score[tid] = sc;
-    if (sc != -INFINITY) {                                  // one thread per live entry: its position, its lookups
-      const int64_t r = (int64_t)b * K + tid;
-      TlmStage s;
-      s.a = g.a[r], s.b = 0, s.n = g.n[r], s.lm = g.lm[r];
-      s.clp = 0.f, s.cnext = 0, s.e_lm = 0.f, s.e_n = 0, s.e_ok = 1;
-      if constexpr (KIND == TLM_WORD) {
-        s.b = g.b[r];
-        wlm::close_pair(g.w, s.a, s.b, g.lexicon_only, s.clp, s.cnext);
-        wlm::WordPos q{s.a, s.b, s.lm, s.n};
-        s.e_ok = wlm::finish(g.w, q, s.clp, s.cnext, true) ? 1 : 0;
-        s.e_lm = q.lm, s.e_n = q.nw;
+    if constexpr (TLM) {
+      if (sc != -INFINITY) {                                // one thread per live entry: its position, its lookups
+        const int64_t r = (int64_t)b * K + tid;
+        TlmStage s;
+        s.a = g.a[r], s.b = 0, s.n = g.n[r], s.lm = g.lm[r];
+        s.clp = 0.f, s.cnext = 0, s.e_lm = 0.f, s.e_n = 0, s.e_ok = 1;
+        if constexpr (KIND == TLM_WORD) {
+          s.b = g.b[r];
+          wlm::close_pair(g.w, s.a, s.b, g.lexicon_only, s.clp, s.cnext);
+          wlm::WordPos q{s.a, s.b, s.lm, s.n};
+          s.e_ok = wlm::finish(g.w, q, s.clp, s.cnext, true) ? 1 : 0;
+          s.e_lm = q.lm, s.e_n = q.nw;
+        }
+        s_pos[tid] = s;
       }
-      s_pos[tid] = s;
     }
   }
   __syncthreads();
@@ -305,8 +196,8 @@ __global__ __launch_bounds__(BEAM_NT) void beam_select_tlm_kernel(asr_beam_t p, 
   }
   __syncthreads();
 
-  // every thread keeps its best M candidates by RANK (desc, flat index k*V+v asc on ties), visiting flat indices in
-  // increasing order
+  // every thread keeps its best M candidates (value - with an LM inside, rank - desc, flat index k*V+v asc on ties), visiting
+  // flat indices in increasing order
   float lv[M];
   int li[M];
   top_clear(lv, li);
@@ -323,14 +214,15 @@ __global__ __launch_bounds__(BEAM_NT) void beam_select_tlm_kernel(asr_beam_t p, 
       prow = ca.psi + ((int64_t)b * K + k) * V;
       pprev = ca.psi_prev[b * K + k], cw = ca.w, omw = __fsub_rn(1.f, cw);
     }
-    const TlmStage& st = s_pos[k];
     for (int v = tid; v < V; v += BEAM_NT) {
-      const float base = beam_base<LM, CTC>(sc, row[v], m, ls, LM ? lrow[v] : 0.f, lmm, lml, lmw, CTC ? prow[v] : 0.f, pprev,
-                                            omw, cw);
-      float lm;
-      int n;
-      const bool ok = tlm_candidate<KIND>(g, st, v, V, p.eos, lm, n);
-      top_insert(lv, li, ok ? tlm_rank(base, lm, n, g.weight, g.bonus) : -INFINITY, k * V + v);
+      float c = beam_base<LM, CTC>(sc, row[v], m, ls, LM ? lrow[v] : 0.f, lmm, lml, lmw, CTC ? prow[v] : 0.f, pprev, omw, cw);
+      if constexpr (TLM) {
+        float lm;
+        int n;
+        const bool ok = tlm_candidate<KIND>(g, s_pos[k], v, V, p.eos, lm, n);
+        c = ok ? tlm_rank(c, lm, n, g.weight, g.bonus) : -INFINITY;
+      }
+      top_insert(lv, li, c, k * V + v);
     }
   }
 
@@ -349,50 +241,52 @@ __global__ __launch_bounds__(BEAM_NT) void beam_select_tlm_kernel(asr_beam_t p, 
   if (tid == 0) s_ntop = ntop;
   __syncthreads();
 
-  // one thread per ranked candidate forms its parts again (the same operations on the same operands: the same bits) and the
-  // position behind it; at t = L-1 also what it is as a hypothesis that finishes as it stands
-  if (tid < ntop) {
-    const int idx = top_i[tid];
-    const int k = idx / V, v = idx - k * V;
-    const TlmStage st = s_pos[k];
-    const int64_t rk = (int64_t)b * K + k;
-    float pprev = 0.f, omw = 0.f, cw = 0.f, px = 0.f, lx = 0.f;
-    if constexpr (CTC) px = ca.psi[rk * V + v], pprev = ca.psi_prev[rk], cw = ca.w, omw = __fsub_rn(1.f, cw);
-    if (LM) lx = lm_logits[rk * V + v];
-    const float base = beam_base<LM, CTC>(s_score[k], lg[(int64_t)k * V + v], s_max[k], s_lsum[k], lx, LM ? s_lmmax[k] : 0.f,
-                                          LM ? s_lmlsum[k] : 0.f, lmw, px, pprev, omw, cw);
-    float lm;
-    int n;
-    tlm_candidate<KIND>(g, st, v, V, p.eos, lm, n);
-    top_base[tid] = base, top_lm[tid] = lm, top_n[tid] = n;
-    int na = 0, nb = 0, eok = 1, en = n;
-    float elm = lm;
-    if (v != p.eos) {
-      if constexpr (KIND == TLM_NGRAM) {
-        na = g.next[(int64_t)st.a * V + v];
-        if (t == p.L - 1) elm = __fadd_rn(lm, g.logp[(int64_t)na * V + p.eos]);
-      } else {
-        const wlm::WordPos q = wlm::after_token(g.w, wlm::WordPos{st.a, st.b, st.lm, st.n}, v, st.clp, st.cnext);
-        na = q.node, nb = q.state;
-        if (t == p.L - 1) {
-          float lp;
-          int nx;
-          wlm::close_pair(g.w, q.node, q.state, g.lexicon_only, lp, nx);
-          wlm::WordPos e = q;
-          eok = wlm::finish(g.w, e, lp, nx, true) ? 1 : 0;
-          elm = e.lm, en = e.nw;
+  // an LM inside: one thread per ranked candidate forms its parts again (the same operations on the same operands: the same
+  // bits) and the position behind it; at t = L-1 also what it is as a hypothesis that finishes as it stands
+  if constexpr (TLM) {
+    if (tid < ntop) {
+      const int idx = top_i[tid];
+      const int k = idx / V, v = idx - k * V;
+      const TlmStage st = s_pos[k];
+      const int64_t rk = (int64_t)b * K + k;
+      float pprev = 0.f, omw = 0.f, cw = 0.f, px = 0.f, lx = 0.f;
+      if constexpr (CTC) px = ca.psi[rk * V + v], pprev = ca.psi_prev[rk], cw = ca.w, omw = __fsub_rn(1.f, cw);
+      if (LM) lx = lm_logits[rk * V + v];
+      const float base = beam_base<LM, CTC>(s_score[k], lg[(int64_t)k * V + v], s_max[k], s_lsum[k], lx, LM ? s_lmmax[k] : 0.f,
+                                            LM ? s_lmlsum[k] : 0.f, lmw, px, pprev, omw, cw);
+      float lm;
+      int n;
+      tlm_candidate<KIND>(g, st, v, V, p.eos, lm, n);
+      top_base[tid] = base, top_lm[tid] = lm, top_n[tid] = n;
+      int na = 0, nb = 0, eok = 1, en = n;
+      float elm = lm;
+      if (v != p.eos) {
+        if constexpr (KIND == TLM_NGRAM) {
+          na = g.next[(int64_t)st.a * V + v];
+          if (t == p.L - 1) elm = __fadd_rn(lm, g.logp[(int64_t)na * V + p.eos]);
+        } else {
+          const wlm::WordPos q = wlm::after_token(g.w, wlm::WordPos{st.a, st.b, st.lm, st.n}, v, st.clp, st.cnext);
+          na = q.node, nb = q.state;
+          if (t == p.L - 1) {
+            float lp;
+            int nx;
+            wlm::close_pair(g.w, q.node, q.state, g.lexicon_only, lp, nx);
+            wlm::WordPos e = q;
+            eok = wlm::finish(g.w, e, lp, nx, true) ? 1 : 0;
+            elm = e.lm, en = e.nw;
+          }
         }
       }
+      top_a[tid] = na, top_b[tid] = nb;
+      top_elm[tid] = elm, top_en[tid] = en, top_eok[tid] = eok;
+      top_erank[tid] = tlm_rank(base, elm, en, g.weight, g.bonus);
     }
-    top_a[tid] = na, top_b[tid] = nb;
-    top_elm[tid] = elm, top_en[tid] = en, top_eok[tid] = eok;
-    top_erank[tid] = tlm_rank(base, elm, en, g.weight, g.bonus);
+    __syncthreads();
   }
-  __syncthreads();
   if (tid != 0) return;
 
-  // the fairseq walk over the ranked candidates (a handful of entries: one thread); scores keeps base, the finished list
-  // the rank and the parts
+  // the fairseq walk over the ranked candidates (a handful of entries: one thread).  An LM inside: scores keeps base, the
+  // finished list the rank and the parts, the positions move in place
   ntop = s_ntop;
   const int64_t hb = ((int64_t)t * B + b) * K;
   int nf = p.nfin[b], nlive = 0;
@@ -405,17 +299,21 @@ __global__ __launch_bounds__(BEAM_NT) void beam_select_tlm_kernel(asr_beam_t p, 
         int4* f = reinterpret_cast<int4*>(p.fin) + fo;
         *f = make_int4(t, k, t + 1, 1);
         p.fin_score[fo] = top_v[r];
-        g.fin_base[fo] = top_base[r], g.fin_lm[fo] = top_lm[r], g.fin_n[fo] = top_n[r];
+        if constexpr (TLM) g.fin_base[fo] = top_base[r], g.fin_lm[fo] = top_lm[r], g.fin_n[fo] = top_n[r];
         ++nf;
       }
     } else if (nlive < K) {
       const int64_t o = (int64_t)b * K + nlive;
       p.tok_hist[hb + nlive] = v;
       p.bp_hist[hb + nlive] = k;
-      p.scores[o] = top_base[r];
-      g.a[o] = top_a[r], g.lm[o] = top_lm[r], g.n[o] = top_n[r];
-      if constexpr (KIND == TLM_WORD) g.b[o] = top_b[r];
-      live_r[nlive] = r;
+      if constexpr (TLM) {
+        p.scores[o] = top_base[r];
+        g.a[o] = top_a[r], g.lm[o] = top_lm[r], g.n[o] = top_n[r];
+        if constexpr (KIND == TLM_WORD) g.b[o] = top_b[r];
+        live_r[nlive] = r;
+      } else {
+        p.scores[o] = top_v[r];
+      }
       ++nlive;
     }
   }
@@ -424,15 +322,21 @@ __global__ __launch_bounds__(BEAM_NT) void beam_select_tlm_kernel(asr_beam_t p, 
     p.bp_hist[hb + j] = 0;
     p.scores[(int64_t)b * K + j] = -INFINITY;
   }
-  if (t == p.L - 1 && nf < K) {                             // max_dec_timesteps: the live beams finish as they stand,
-    for (int j = 0; j < nlive; ++j) {                       // with the end term an <EOS> would give and no <EOS> token
-      const int r = live_r[j];
-      if (!top_eok[r]) continue;                            // lexicon_only: the pending node ends no word
+  if (t == p.L - 1 && nf < K) {                             // max_dec_timesteps: the live beams finish as they stand; an LM
+    for (int j = 0; j < nlive; ++j) {                       // inside adds the end term an <EOS> would give and no <EOS> token
+      if constexpr (TLM) {
+        if (!top_eok[live_r[j]]) continue;                  // lexicon_only: the pending node ends no word
+      }
       const int64_t fo = (int64_t)b * BEAM_FCAP + nf;
       int4* f = reinterpret_cast<int4*>(p.fin) + fo;
       *f = make_int4(t, j, t + 1, 0);
-      p.fin_score[fo] = top_erank[r];
-      g.fin_base[fo] = top_base[r], g.fin_lm[fo] = top_elm[r], g.fin_n[fo] = top_en[r];
+      if constexpr (TLM) {
+        const int r = live_r[j];
+        p.fin_score[fo] = top_erank[r];
+        g.fin_base[fo] = top_base[r], g.fin_lm[fo] = top_elm[r], g.fin_n[fo] = top_en[r];
+      } else {
+        p.fin_score[fo] = p.scores[(int64_t)b * K + j];
+      }
       ++nf;
     }
   }
@@ -445,7 +349,7 @@ __global__ __launch_bounds__(BEAM_NT) void beam_select_tlm_kernel(asr_beam_t p, 
 
 // the position of the empty sequence in every beam row
 template <int KIND>
-__global__ __launch_bounds__(BEAM_NT) void beam_tlm_init_kernel(int R, BeamTlm g) {
+__global__ __launch_bounds__(BEAM_NT) void beam_tlm_init_kernel(int R, BeamTlm<true> g) {
   const int r = blockIdx.x * BEAM_NT + threadIdx.x;
   if (r >= R) return;
   g.lm[r] = 0.f, g.n[r] = 0;
@@ -583,18 +487,32 @@ int check_beam(const asr_beam_t* p, bool need_logits) {
   return 0;
 }
 
-template <bool LM, bool CTC = false>
-int beam_select_launch(const asr_beam_t* p, const float* lm_logits, float lmw, int t, hipStream_t stream,
-                       const float* psi = nullptr, const float* psi_prev = nullptr, float cw = 0.f) {
-  int rc = check_beam(p, true);
+// the checks every select entry shares, each written once; an entry calls them in its own order of precedence
+int check_step(const asr_beam_t* p, int t) {
+  const int rc = check_beam(p, true);
   if (rc) return rc;
-  if (t < 0 || t >= p->L) return ASR_E_ARG;
+  return t < 0 || t >= p->L ? ASR_E_ARG : 0;
+}
+
+int check_ctc(const asr_beam_t* p, const float* psi, const float* psi_prev, float cw) {
+  if (!(cw >= 0.f && cw <= 1.f)) return ASR_E_ARG;
+  if (cw == 0.f) return 0;                                  // psi is not read: the variant without it
+  if (!psi || !psi_prev) return ASR_E_ARG;
+  return p && p->V < 3 ? ASR_E_SHAPE : 0;
+}
+
+// the one launch of a checked select: the judge if lm_logits, the CTC term if cw != 0, the LM inside the search if g
+template <bool LM, bool CTC, int KIND>
+int beam_select_launch(const asr_beam_t* p, int t, const float* lm_logits, float lmw, const float* psi, const float* psi_prev,
+                       float cw, const BeamTlm<true>* g, hipStream_t stream) {
   const dim3 grid(p->B), block(BEAM_NT);
   const int m = 2 * p->K;
   beam_ctc_args<CTC> ca;
   if constexpr (CTC) ca.psi = psi, ca.psi_prev = psi_prev, ca.w = cw;
+  BeamTlm<KIND != TLM_NONE> ga;
+  if constexpr (KIND != TLM_NONE) ga = *g;
 #define BEAM_SELECT(M_) \
-  hipLaunchKernelGGL((beam_select_kernel<M_, LM, CTC>), grid, block, 0, stream, *p, t, lm_logits, lmw, ca)
+  hipLaunchKernelGGL((beam_select_kernel<M_, LM, CTC, KIND>), grid, block, 0, stream, *p, t, lm_logits, lmw, ca, ga)
   if (m <= 2) BEAM_SELECT(2);
   else if (m <= 4) BEAM_SELECT(4);
   else if (m <= 8) BEAM_SELECT(8);
@@ -603,6 +521,17 @@ int beam_select_launch(const asr_beam_t* p, const float* lm_logits, float lmw, i
 #undef BEAM_SELECT
   ASR_CHECK_LAUNCH();
   return 0;
+}
+
+int beam_select(const asr_beam_t* p, int t, const float* lm_logits, float lmw, const float* psi, const float* psi_prev, float cw,
+                int kind, const BeamTlm<true>* g, hipStream_t stream) {
+#define BEAM_MODE(LM_, CTC_)                                                                                            \
+  (kind == TLM_WORD    ? beam_select_launch<LM_, CTC_, TLM_WORD>(p, t, lm_logits, lmw, psi, psi_prev, cw, g, stream)    \
+   : kind == TLM_NGRAM ? beam_select_launch<LM_, CTC_, TLM_NGRAM>(p, t, lm_logits, lmw, psi, psi_prev, cw, g, stream)   \
+                       : beam_select_launch<LM_, CTC_, TLM_NONE>(p, t, lm_logits, lmw, psi, psi_prev, cw, g, stream))
+  if (cw != 0.f) return lm_logits ? BEAM_MODE(true, true) : BEAM_MODE(false, true);
+  return lm_logits ? BEAM_MODE(true, false) : BEAM_MODE(false, false);
+#undef BEAM_MODE
 }
 
 int check_beam_state(const asr_beam_t* p, int t, const asr_beam_state_t* s) {
@@ -614,12 +543,12 @@ int check_beam_state(const asr_beam_t* p, int t, const asr_beam_state_t* s) {
 }
 
 // the checks of an asr_beam_*_tlm call (before any launch), and the device's view of its LM and extra workspace
-int tlm_args(const asr_beam_t* p, const asr_beam_tlm_t* lm, bool need_logits, BeamTlm* g) {
+int tlm_args(const asr_beam_t* p, const asr_beam_tlm_t* lm, bool need_logits, BeamTlm<true>* g) {
   int rc = check_beam(p, need_logits);
   if (rc) return rc;
   if (!lm || !lm->ws || !(fabsf(lm->weight) <= FLT_MAX) || !(fabsf(lm->bonus) <= FLT_MAX)) return ASR_E_ARG;
   if (lm->ws_bytes < tlm_ws_bytes(p->B, p->K) || (((uintptr_t)lm->ws) & 3u)) return ASR_E_ARG;
-  *g = BeamTlm{};
+  *g = BeamTlm<true>{};
   if (lm->kind == ASR_BEAM_TLM_NGRAM) {
     if (!lm->lm_logp || !lm->lm_next || lm->lm_states <= 0) return ASR_E_ARG;
     if ((int64_t)lm->lm_states * p->V > INT_MAX || lm->lm_start < 0 || lm->lm_start >= lm->lm_states) return ASR_E_SHAPE;
@@ -634,7 +563,7 @@ int tlm_args(const asr_beam_t* p, const asr_beam_tlm_t* lm, bool need_logits, Be
   }
   g->weight = lm->weight, g->bonus = lm->bonus;
   g->lexicon_only = lm->kind == ASR_BEAM_TLM_WORD && lm->lexicon_only != 0;
-  const int64_t n_bk = tlm_round64((int64_t)p->B * p->K), n_f = tlm_round64((int64_t)p->B * BEAM_FCAP);
+  const int64_t n_bk = round64((int64_t)p->B * p->K), n_f = round64((int64_t)p->B * BEAM_FCAP);
   g->a = (int32_t*)lm->ws;
   g->b = g->a + n_bk;
   g->n = g->b + n_bk;
@@ -645,48 +574,25 @@ int tlm_args(const asr_beam_t* p, const asr_beam_tlm_t* lm, bool need_logits, Be
   return 0;
 }
 
-template <bool LM, bool CTC, int KIND>
-int beam_select_tlm_launch(const asr_beam_t* p, const float* lm_logits, float lmw, int t, hipStream_t stream, const BeamTlm& g,
-                           const float* psi, const float* psi_prev, float cw) {
-  const dim3 grid(p->B), block(BEAM_NT);
-  const int m = 2 * p->K;
-  beam_ctc_args<CTC> ca;
-  if constexpr (CTC) ca.psi = psi, ca.psi_prev = psi_prev, ca.w = cw;
-#define BEAM_SELECT(M_) \
-  hipLaunchKernelGGL((beam_select_tlm_kernel<M_, LM, CTC, KIND>), grid, block, 0, stream, *p, t, lm_logits, lmw, ca, g)
-  if (m <= 2) BEAM_SELECT(2);
-  else if (m <= 4) BEAM_SELECT(4);
-  else if (m <= 8) BEAM_SELECT(8);
-  else if (m <= 16) BEAM_SELECT(16);
-  else BEAM_SELECT(32);
-#undef BEAM_SELECT
-  ASR_CHECK_LAUNCH();
-  return 0;
-}
-
 }  // namespace
 
 extern "C" int asr_beam_select_f32(const asr_beam_t* p, int t, asr_stream_t stream_) {
-  return beam_select_launch<false>(p, nullptr, 0.f, t, (hipStream_t)stream_);
+  const int rc = check_step(p, t);
+  return rc ? rc : beam_select(p, t, nullptr, 0.f, nullptr, nullptr, 0.f, TLM_NONE, nullptr, (hipStream_t)stream_);
 }
 
 extern "C" int asr_beam_select_lm_f32(const asr_beam_t* p, const float* lm_logits, float lm_weight, int t,
                                       asr_stream_t stream_) {
   if (!lm_logits) return ASR_E_ARG;
-  return beam_select_launch<true>(p, lm_logits, lm_weight, t, (hipStream_t)stream_);
+  const int rc = check_step(p, t);
+  return rc ? rc : beam_select(p, t, lm_logits, lm_weight, nullptr, nullptr, 0.f, TLM_NONE, nullptr, (hipStream_t)stream_);
 }
 
 extern "C" int asr_beam_select_ctc_f32(const asr_beam_t* p, const float* lm_logits, float lm_weight, const float* psi,
                                        const float* psi_prev, float ctc_weight, int t, asr_stream_t stream_) {
-  if (!(ctc_weight >= 0.f && ctc_weight <= 1.f)) return ASR_E_ARG;
-  hipStream_t stream = (hipStream_t)stream_;
-  if (ctc_weight == 0.f)                                    // psi is not read: the plain / LM select, the same kernel
-    return lm_logits ? beam_select_launch<true>(p, lm_logits, lm_weight, t, stream)
-                     : beam_select_launch<false>(p, nullptr, 0.f, t, stream);
-  if (!psi || !psi_prev) return ASR_E_ARG;
-  if (p && p->V < 3) return ASR_E_SHAPE;
-  return lm_logits ? beam_select_launch<true, true>(p, lm_logits, lm_weight, t, stream, psi, psi_prev, ctc_weight)
-                   : beam_select_launch<false, true>(p, nullptr, 0.f, t, stream, psi, psi_prev, ctc_weight);
+  int rc = check_ctc(p, psi, psi_prev, ctc_weight);
+  if (!rc) rc = check_step(p, t);
+  return rc ? rc : beam_select(p, t, lm_logits, lm_weight, psi, psi_prev, ctc_weight, TLM_NONE, nullptr, (hipStream_t)stream_);
 }
 
 extern "C" int asr_beam_reorder_f32(const asr_beam_t* p, int t, const asr_beam_state_t* s, asr_stream_t stream_) {
@@ -736,7 +642,7 @@ extern "C" int asr_beam_tlm_ws_bytes(int B, int K, int64_t* ws_bytes) {
 }
 
 extern "C" int asr_beam_tlm_init_f32(const asr_beam_t* p, const asr_beam_tlm_t* lm, asr_stream_t stream_) {
-  BeamTlm g;
+  BeamTlm<true> g;
   const int rc = tlm_args(p, lm, false, &g);
   if (rc) return rc;
   const int R = p->B * p->K;
@@ -749,28 +655,19 @@ extern "C" int asr_beam_tlm_init_f32(const asr_beam_t* p, const asr_beam_tlm_t* 
 
 extern "C" int asr_beam_select_tlm_f32(const asr_beam_t* p, const asr_beam_tlm_t* lm, const float* lm_logits, float lm_weight,
                                        const float* psi, const float* psi_prev, float ctc_weight, int t, asr_stream_t stream_) {
-  BeamTlm g;
+  BeamTlm<true> g;
   int rc = tlm_args(p, lm, true, &g);
+  if (!rc) rc = check_step(p, t);
+  if (!rc) rc = check_ctc(p, psi, psi_prev, ctc_weight);
   if (rc) return rc;
-  if (t < 0 || t >= p->L || !(ctc_weight >= 0.f && ctc_weight <= 1.f)) return ASR_E_ARG;
-  const bool ctc = ctc_weight != 0.f;                      // at 0 psi is not read: the variant without it, as asr_beam_select_ctc_f32
-  if (ctc && (!psi || !psi_prev)) return ASR_E_ARG;
-  if (ctc && p->V < 3) return ASR_E_SHAPE;
-  hipStream_t stream = (hipStream_t)stream_;
-  const bool word = lm->kind == ASR_BEAM_TLM_WORD;
-#define TLM_SELECT(LM_, CTC_)                                                                                          \
-  (word ? beam_select_tlm_launch<LM_, CTC_, TLM_WORD>(p, lm_logits, lm_weight, t, stream, g, psi, psi_prev, ctc_weight) \
-        : beam_select_tlm_launch<LM_, CTC_, TLM_NGRAM>(p, lm_logits, lm_weight, t, stream, g, psi, psi_prev, ctc_weight))
-  if (ctc) rc = lm_logits ? TLM_SELECT(true, true) : TLM_SELECT(false, true);
-  else rc = lm_logits ? TLM_SELECT(true, false) : TLM_SELECT(false, false);
-#undef TLM_SELECT
-  return rc;
+  return beam_select(p, t, lm_logits, lm_weight, psi, psi_prev, ctc_weight, lm->kind == ASR_BEAM_TLM_WORD ? TLM_WORD : TLM_NGRAM,
+                     &g, (hipStream_t)stream_);
 }
 
 extern "C" int asr_beam_backtrack_tlm(const asr_beam_t* p, const asr_beam_tlm_t* lm, float length_penalty, int32_t* tokens,
                                       float* scores, int32_t* lengths, float* att_score, float* lm_score, int32_t* n_out,
                                       asr_stream_t stream_) {
-  BeamTlm g;
+  BeamTlm<true> g;
   const int rc = tlm_args(p, lm, false, &g);
   if (rc) return rc;
   if (!tokens || !scores || !lengths || !att_score || !lm_score || !n_out) return ASR_E_ARG;

@@ -711,30 +711,30 @@ class BeamSearch:
                            tok_hist=ptr(self.tok_hist), bp_hist=ptr(self.bp_hist), fin=ptr(self.fin),
                            fin_score=ptr(self.fin_score), nfin=ptr(self.nfin), done=ptr(self.done), ndone=ptr(self.ndone))
 
+    def _step(self, logits, lm_logits=None, ctc=None):
+        """What every select shares: logits [B*K, V] contiguous, lm_logits like them, ctc.psi of their shape -> the struct with
+        the step's logits."""
+        assert logits.is_contiguous() and tuple(logits.shape) == (self.B * self.K, self.V)
+        assert lm_logits is None or (lm_logits.is_contiguous() and lm_logits.shape == logits.shape)
+        assert ctc is None or tuple(ctc.psi.shape) == (self.B * self.K, self.V)
+        self.struct.logits = ptr(logits)
+        return ctypes.byref(self.struct)
+
     def select(self, logits, t):
         """logits [B*K, V] (contiguous) of step t -> tokens, backpointers, scores, finished list, done flags."""
-        assert logits.is_contiguous() and tuple(logits.shape) == (self.B * self.K, self.V)
-        self.struct.logits = ptr(logits)
-        check(load().asr_beam_select_f32(ctypes.byref(self.struct), int(t), stream()), "asr_beam_select_f32")
+        check(load().asr_beam_select_f32(self._step(logits), int(t), stream()), "asr_beam_select_f32")
 
     def select_lm(self, logits, lm_logits, lm_weight, t):
         """select() on score + log_softmax(logits) + lm_weight * log_softmax(lm_logits) (shallow fusion, DESIGN 4.9);
         lm_logits [B*K, V] like logits."""
-        assert logits.is_contiguous() and tuple(logits.shape) == (self.B * self.K, self.V)
-        assert lm_logits.is_contiguous() and lm_logits.shape == logits.shape
-        self.struct.logits = ptr(logits)
-        check(load().asr_beam_select_lm_f32(ctypes.byref(self.struct), ptr(lm_logits), float(lm_weight), int(t), stream()),
+        check(load().asr_beam_select_lm_f32(self._step(logits, lm_logits), ptr(lm_logits), float(lm_weight), int(t), stream()),
               "asr_beam_select_lm_f32")
 
     def select_ctc(self, logits, ctc, ctc_weight, t, lm_logits=None, lm_weight=0.0):
         """select() / select_lm() (lm_logits given) with the CTC prefix score of `ctc` (CtcPrefixState, after its score()):
         score + (1 - ctc_weight) * logp + ctc_weight * (psi - psi_prev) (+ lm_weight * logp_lm) - DESIGN 4.15.
         ctc_weight = 0 launches the plain / LM select."""
-        assert logits.is_contiguous() and tuple(logits.shape) == (self.B * self.K, self.V)
-        assert lm_logits is None or (lm_logits.is_contiguous() and lm_logits.shape == logits.shape)
-        assert tuple(ctc.psi.shape) == (self.B * self.K, self.V)
-        self.struct.logits = ptr(logits)
-        check(load().asr_beam_select_ctc_f32(ctypes.byref(self.struct), ptr(lm_logits), float(lm_weight), ptr(ctc.psi),
+        check(load().asr_beam_select_ctc_f32(self._step(logits, lm_logits, ctc), ptr(lm_logits), float(lm_weight), ptr(ctc.psi),
                                              ptr(ctc.psi_prev), float(ctc_weight), int(t), stream()), "asr_beam_select_ctc_f32")
 
     @staticmethod
@@ -759,12 +759,16 @@ class BeamSearch:
         check(load().asr_beam_reorder_lm_f32(ctypes.byref(self.struct), int(t), ctypes.byref(st) if st is not None else None,
                                              ctypes.byref(lm_state.reorder_struct()), stream()), "asr_beam_reorder_lm_f32")
 
+    def _hyps(self):
+        """A backtrack's outputs: tokens [B, K, L] int32, scores [B, K] fp32, lengths [B, K] int32."""
+        dev = self.scores.device
+        return (torch.empty(self.B, self.K, self.L, dtype=torch.int32, device=dev),
+                torch.empty(self.B, self.K, dtype=torch.float32, device=dev),
+                torch.empty(self.B, self.K, dtype=torch.int32, device=dev))
+
     def backtrack(self, length_penalty=0.0):
         """-> tokens [B, K, L] int32 (ranked, <EOS>-padded), scores [B, K] (score / len**length_penalty), lengths [B, K]."""
-        dev = self.scores.device
-        tokens = torch.empty(self.B, self.K, self.L, dtype=torch.int32, device=dev)
-        scores = torch.empty(self.B, self.K, dtype=torch.float32, device=dev)
-        lengths = torch.empty(self.B, self.K, dtype=torch.int32, device=dev)
+        tokens, scores, lengths = self._hyps()
         check(load().asr_beam_backtrack(ctypes.byref(self.struct), float(length_penalty), ptr(tokens), ptr(scores),
                                         ptr(lengths), stream()), "asr_beam_backtrack")
         return tokens, scores, lengths
@@ -827,13 +831,8 @@ class BeamTableLm:
     def select(self, logits, t, lm_logits=None, lm_weight=0.0, ctc=None, ctc_weight=0.0):
         """The select of step t with the LM's term: lm_logits [B*K, V] (the judge, shallow fusion) and ctc (CtcPrefixState
         after its score()) with ctc_weight as BeamSearch.select_lm / select_ctc take them."""
-        s = self.search
-        assert logits.is_contiguous() and tuple(logits.shape) == (s.B * s.K, s.V)
-        assert lm_logits is None or (lm_logits.is_contiguous() and lm_logits.shape == logits.shape)
-        assert ctc is None or tuple(ctc.psi.shape) == (s.B * s.K, s.V)
-        s.struct.logits = ptr(logits)
-        self._run(load().asr_beam_select_tlm_f32(ctypes.byref(s.struct), ctypes.byref(self.struct), ptr(lm_logits),
-                                                 float(lm_weight), ptr(ctc.psi) if ctc is not None else None,
+        self._run(load().asr_beam_select_tlm_f32(self.search._step(logits, lm_logits, ctc), ctypes.byref(self.struct),
+                                                 ptr(lm_logits), float(lm_weight), ptr(ctc.psi) if ctc is not None else None,
                                                  ptr(ctc.psi_prev) if ctc is not None else None,
                                                  float(ctc_weight) if ctc is not None else 0.0, int(t), stream()),
                   "asr_beam_select_tlm_f32")
@@ -842,10 +841,8 @@ class BeamTableLm:
         """-> BeamSearch.backtrack's tokens, scores (the rank / len**length_penalty), lengths, and in the same order att_score
         fp32 [B, K] (base), lm_score fp32 [B, K], n int32 [B, K] (len, or n_words with a word LM; -1 without a hypothesis)."""
         s = self.search
-        dev = s.scores.device
-        tokens = torch.empty(s.B, s.K, s.L, dtype=torch.int32, device=dev)
-        scores, att, lm = (torch.empty(s.B, s.K, dtype=torch.float32, device=dev) for _ in range(3))
-        lengths, n = (torch.empty(s.B, s.K, dtype=torch.int32, device=dev) for _ in range(2))
+        tokens, scores, lengths = s._hyps()
+        att, lm, n = torch.empty_like(scores), torch.empty_like(scores), torch.empty_like(lengths)
         self._run(load().asr_beam_backtrack_tlm(ctypes.byref(s.struct), ctypes.byref(self.struct), float(length_penalty),
                                                 ptr(tokens), ptr(scores), ptr(lengths), ptr(att), ptr(lm), ptr(n), stream()),
                   "asr_beam_backtrack_tlm")

@@ -1,4 +1,4 @@
-"""The attention beam search with an n-gram or word-level LM inside, on the GPU (csrc/beam.hip's beam_select_tlm kernels and
+"""The attention beam search with an n-gram or word-level LM inside, on the GPU (csrc/beam.hip's select kernel with its KIND and
 the asr_beam_*_tlm entries): the select alone against a stable sort in float32, bit for bit; the search against
 the float64 restatement (tests/beam_ngram_ref.py); zero weights against the search without the LM; the parts against the
 scorers; lexicon_only; launches and memory; the untouched plain entries; poisoned buffers; refusals, the model and the solver.
@@ -431,6 +431,25 @@ def test_plain_entries_are_untouched(hb, golden_dir):
         assert np.array_equal(g[name + "_out_tok"], toks.cpu().numpy()) and _bits(g[name + "_out_score"]) == _bits(sc.cpu().numpy())
         assert np.array_equal(g[name + "_out_len"], lens.cpu().numpy())
     print("beam-ngram-parity plain entries: select and backtrack outputs equal the parent build's record, 0 ulp; left out 0")
+
+
+def test_select_variants_keep_their_bits(hb, golden_dir):
+    """The candidate expressions that beam_plain_select.npz does not cover - the judge, the CTC prefix score, both, and the
+    plain select at the longest list (K = 4 and 16: M = 8 and 32), at t = 3 and t = L - 1 - against the outputs recorded from
+    the build before the select kernels were folded into one (tests/golden/make_beam_select_golden.py), 0 ulp.  The inputs'
+    checksums are part of the record: a generator that drifts fails here and not as a difference of the outputs."""
+    import make_beam_select_golden as G
+    g = np.load(os.path.join(golden_dir, "beam_select_variants.npz"))
+    rec = G.record(hb)
+    assert sorted(rec) == sorted(g.files)
+    inputs = [k for k in rec if k.startswith("in_")]
+    assert len(inputs) == 10 and all(int(rec[k]) == int(g[k]) for k in inputs), "the inputs are not the recorded ones"
+    bad = [k for k in rec if k not in inputs and not (rec[k].dtype == g[k].dtype and rec[k].shape == g[k].shape
+                                                       and np.array_equal(G.bits(rec[k]), G.bits(g[k])))]
+    assert not bad, bad
+    assert len(rec) - len(inputs) == 9 * 2 * len(G.CASES) and all(int(g[k].max()) > 0 for k in g.files if k.endswith("_nfin"))
+    print("beam-ngram-parity select variants: %d cases x 2 steps, %d arrays equal the record of the build before the fold, 0 ulp; "
+          "left out 0" % (len(G.CASES), len(rec) - len(inputs)))
 
 
 @pytest.mark.parametrize("pattern", P.PATTERNS)
