@@ -967,7 +967,8 @@ class _CtcLoss(torch.autograd.Function):
         else:
             ctx.lease, ws = None, torch.empty(words, device=dev, dtype=torch.float32)
         offs_dev = hb.to_device_i32(offsets, dev)
-        labels = labels.contiguous()
+        # (a batch of empty transcripts has no label to point at: the library wants a pointer all the same)
+        labels = labels.contiguous() if labels.numel() else torch.zeros(1, device=dev, dtype=torch.long)
         nll = torch.empty(B, device=dev, dtype=torch.float32)
         hb.ctc_loss_fwd(logits, ld, frame_lens, labels, offs_dev, lmax, zero_infinity, nll, ws)
         ctx.save_for_backward(logits, frame_lens, labels, offs_dev)
