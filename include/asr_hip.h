@@ -1021,6 +1021,57 @@ int asr_ctc_greedy_f32(int B, int T, int V, const float* logits, int64_t ld, con
                        int32_t* n, int32_t* frame_tok, asr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * CTC segmentation (csrc/ctc_segment.hip; Kuerzinger et al. 2020): asr_ctc_align_f32 for a long recording and a
+ * transcript of several utterances.  Not a reference operator.  Two entries added to ABI version 8 WITHOUT a version change,
+ * like the other CTC entries: additive.
+ * logits, ld, frame_lens, labels, label_offsets, max_label_len are asr_ctc_align_f32's, with its conventions.  One batch row
+ * is a recording; its labels are the concatenation of its utterances:
+ *   utt_offsets int32 [N + 1]  ascending label indices into the packed labels, over all recordings
+ *   rec_utts    int32 [B + 1]  recording b owns the utterances rec_utts[b] .. rec_utts[b + 1] - 1, whose label ranges tile
+ *                              [label_offsets[b], label_offsets[b + 1]) exactly (the caller's duty; not checked on the device)
+ *   asr_ctc_segment_f32  asr_ctc_align_f32's recurrence, predecessors, skip rule and TIE RULE.  With free_ends != 0 the
+ *                       emission of state 0 and of state S - 1 is 0 instead of x[t][0], at every frame: audio before the first
+ *                       and after the last label costs nothing, score[b] is the log-probability of the text over the stretch
+ *                       of frames it picks for itself, and the frames whose state is 0 or S - 1 get path = -2 (outside the
+ *                       text); t >= T_b gets -1 as before.  L = 0 with free ends: score 0, every valid frame -2.
+ *                       With free_ends = 0: path, score, first, last and token_logp are asr_ctc_align_f32's, bit for bit
+ *                       (lse from the same kernel, one fp32 subtraction per emission, one fp32 add per cell, token_logp
+ *                       summed by one lane in ascending frame order), here up to ASR_CTC_SEG_MAX_LABELS labels.
+ *                       Per utterance u, packed [N]:
+ *                         utt_begin int32   first of the utterance's first label
+ *                         utt_end   int32   last of its last label
+ *                         utt_logp  fp32    sum_{t = begin .. end} x[t][path[t]], by ONE lane in ascending frame order
+ *                         utt_conf  fp32    the minimum, over the consecutive blocks of `window` frames from begin (the last
+ *                                           may be shorter), of the block's mean of x[t][path[t]]: each block summed in
+ *                                           ascending order, then divided once by its count in fp32
+ *                       An utterance without labels: -1 / -1 / 0 / 0.  INFEASIBLE recordings (asr_ctc_align_f32's kinds) get
+ *                       that entry's -inf / -1 pattern, and all their utterances -1 / -1 / -inf / -inf.
+ *                       Two launches: the frame log-sum-exps; then one workgroup per recording.  Thread i owns K CONTIGUOUS
+ *                       states (K = 4 up to 2 max_label_len + 1 = 1 024 states, on 64 .. 256 threads; K = 16 beyond, on 128 ..
+ *                       1 024 threads) and keeps them in registers; K is even, so the one value a thread needs from its
+ *                       neighbour - that thread's top state of the frame before - goes through LDS, one barrier per frame.
+ *                       Static LDS only (41 KB: the labels and the exchange line); no dynamic LDS is asked for.  Each
+ *                       state's choice is two bits, formed in the owning thread's registers (contiguous states leave no
+ *                       ballot to take) and stored to the workspace: a frame's back-pointers are a bit row with state s at
+ *                       bits 2 s, 2 s + 1.  The backtrace is one wave that fetches the candidate words of 32 frames at once
+ *                       (the state falls by at most 2 per frame) and walks them in registers; the output passes are
+ *                       parallel over frames, labels and utterances.
+ *   asr_ctc_segment_ws_bytes   the bytes of the workspace (8-byte aligned: ASR_E_ALIGN; too small: ASR_E_ARG): with R = B T
+ *                       rounded up to 64, W = ceil((2 max_label_len + 1) / 32):
+ *                       8 B T W  (the back-pointers) + 12 R  (log-sum-exps, the state and x[t][path[t]] of every frame).
+ * V < 2 or max_label_len > ASR_CTC_SEG_MAX_LABELS: ASR_E_SHAPE.  window < 1: ASR_E_ARG.  No floating-point atomics, no host
+ * synchronisation, no allocation; a function of its inputs and shapes only - the same bits in every run, in and outside
+ * deterministic mode, and a recording's results do not depend on the rest of the batch.
+ * ------------------------------------------------------------------------------------- */
+#define ASR_CTC_SEG_MAX_LABELS 8191
+int asr_ctc_segment_ws_bytes(int B, int T, int V, int max_label_len, int64_t* ws_bytes);
+int asr_ctc_segment_f32(int B, int T, int V, const float* logits, int64_t ld, const int32_t* frame_lens, const int64_t* labels,
+                        const int32_t* label_offsets, int max_label_len, int free_ends, int N, const int32_t* utt_offsets,
+                        const int32_t* rec_utts, int window, int32_t* path, float* score, int32_t* first, int32_t* last,
+                        float* token_logp, int32_t* utt_begin, int32_t* utt_end, float* utt_logp, float* utt_conf, void* ws,
+                        int64_t ws_bytes, asr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * CTC prefix beam search (csrc/ctc_beam.hip): the K best label sequences of the CTC head, the first pass of
  * two-pass decoding.  Not a reference operator.  Two entries added to ABI version 8 WITHOUT a version change, like the other
  * CTC entries: additive.

@@ -31,6 +31,7 @@ EXPORTS = (
     "asr_ctc_ws_bytes", "asr_ctc_loss_fwd", "asr_ctc_loss_bwd",
     "asr_ctc_prefix_init_f32", "asr_ctc_prefix_score_f32", "asr_beam_select_ctc_f32", "asr_ctc_prefix_advance_f32",
     "asr_ctc_align_ws_bytes", "asr_ctc_align_f32", "asr_ctc_greedy_f32",
+    "asr_ctc_segment_ws_bytes", "asr_ctc_segment_f32",
     "asr_ctc_beam_ws_bytes", "asr_ctc_beam_f32", "asr_ctc_beam_lm_f32", "asr_ngram_score_f32",
     "asr_word_lm_score_f32", "asr_ctc_beam_wlm_f32",
     "asr_context_score_f32", "asr_ctc_beam_ctx_f32",
@@ -318,6 +319,9 @@ def load():
     lib.asr_ctc_align_ws_bytes.argtypes = [c_i, c_i, c_i, c_i, ctypes.POINTER(c_i64)]
     lib.asr_ctc_align_f32.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
     lib.asr_ctc_greedy_f32.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]
+    lib.asr_ctc_segment_ws_bytes.argtypes = [c_i, c_i, c_i, c_i, ctypes.POINTER(c_i64)]
+    lib.asr_ctc_segment_f32.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i,
+                                        c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]
     lib.asr_ctc_beam_ws_bytes.argtypes = [c_i, c_i, c_i, c_i, ctypes.POINTER(c_i64)]
     lib.asr_ctc_beam_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p]
     lib.asr_ctc_beam_lm_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_i, c_p, c_p, c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_p, c_p,
@@ -1495,6 +1499,44 @@ def ctc_greedy(logits, frame_lens, ids, n, frame_tok):
         raise UnsupportedShape("ctc_greedy: V %d (V >= 2)" % V)
     check(rc, "asr_ctc_greedy_f32")
     LAUNCHES["ctc_greedy"] += 1
+
+
+CTC_SEG_MAX_LABELS = 8191       # ASR_CTC_SEG_MAX_LABELS: the labels of one recording's transcript
+
+
+def ctc_segment_ws_bytes(B, T, V, max_label_len):
+    """asr_ctc_segment_ws_bytes on plain integers (no tensors, no GPU) -> the workspace bytes of a ctc_segment call;
+    UnsupportedShape for sizes the kernel refuses (more than CTC_SEG_MAX_LABELS labels, V < 2)."""
+    need = c_i64(0)
+    rc = load().asr_ctc_segment_ws_bytes(int(B), int(T), int(V), int(max_label_len), ctypes.byref(need))
+    if rc == -2:
+        raise UnsupportedShape("ctc_segment: B %d, T %d, V %d, %d labels (at most %d labels, V >= 2)"
+                               % (B, T, V, max_label_len, CTC_SEG_MAX_LABELS))
+    check(rc, "asr_ctc_segment_ws_bytes")
+    return need.value
+
+
+def ctc_segment(logits, frame_lens, labels, label_offsets, max_label_len, free_ends, utt_offsets, rec_utts, window, path, score,
+                first, last, token_logp, utt_begin, utt_end, utt_logp, utt_conf, ws):
+    """asr_ctc_segment_f32 (csrc/ctc_segment.hip): the best CTC alignment of every recording's transcript, with
+    free ends when free_ends is set, and the begin / end / log-probability / confidence of its utterances.  logits, frame_lens,
+    labels, label_offsets, max_label_len and the outputs path .. token_logp are ctc_align's; utt_offsets int32 [N + 1] and
+    rec_utts int32 [B + 1] on the device (the utterances' label ranges tile their recording's: the caller's duty); utt_begin /
+    utt_end int32 [N], utt_logp / utt_conf fp32 [N] and the workspace ws (a float32 tensor of at least ctc_segment_ws_bytes
+    bytes) are the caller's.  Two launches."""
+    logits, ld = _ctc_view(logits, "ctc logits")
+    B, T, V = logits.shape
+    if labels.dtype != torch.long or not labels.is_cuda:
+        raise RuntimeError("ctc_segment: labels must be one packed int64 tensor on the GPU")
+    rc = load().asr_ctc_segment_f32(B, T, V, ptr(logits), int(ld), ptr(frame_lens), c_p(labels.data_ptr()), ptr(label_offsets),
+                                    int(max_label_len), int(bool(free_ends)), int(utt_begin.numel()), ptr(utt_offsets),
+                                    ptr(rec_utts), int(window), ptr(path), ptr(score), ptr(first), ptr(last), ptr(token_logp),
+                                    ptr(utt_begin), ptr(utt_end), ptr(utt_logp), ptr(utt_conf), ptr(ws), ws.numel() * 4, stream())
+    if rc == ASR_E_SHAPE:
+        raise UnsupportedShape("ctc_segment: B %d, T %d, V %d, %d labels (at most %d labels, V >= 2)"
+                               % (B, T, V, max_label_len, CTC_SEG_MAX_LABELS))
+    check(rc, "asr_ctc_segment_f32")
+    LAUNCHES["ctc_segment"] += 1
 
 
 CTC_BEAM_ONE_WAVE_KV = 1024      # ASR_CTC_BEAM_ONE_WAVE_KV: K V up to this runs one wave per utterance

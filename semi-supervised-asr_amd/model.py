@@ -1005,6 +1005,39 @@ class E2E(torch.nn.Module):
         self.last_alignment = res                                # (the device tensors of the call, path included)
         return out
 
+    def segment(self, xs, ilens, texts, window=30):
+        """CTC segmentation of recordings against their transcripts (not a reference method): encoder, the CTC
+        head, ops.ctc_segment with free ends.  `texts` is a list, per recording, of label tensors, one per utterance.  -> one
+        dict per recording: score (the log-probability of the text over the frames it picks; -inf: it does not fit), frames
+        (the recording's encoder frames) and utterances, a list of dicts: tokens (the label ids), begin / end (inclusive
+        ENCODER frames; times time_reduction for input frames; -1 without labels or when the text does not fit), logp (the
+        path's log-probability over begin .. end) and confidence (the lowest mean of the path's frame log-probabilities over
+        the consecutive blocks of `window` frames: one bad stretch sinks it).  The recording goes through the encoder in one
+        pass.  self.last_segmentation keeps the device result (ops.CtcSegmentation).  One host read."""
+        with torch.no_grad():
+            logits, lens_dev, enc_lens = self._ctc_logits(xs, ilens, "segment")
+            flat = [y.reshape(-1) for rec in texts for y in rec]
+            labels = (torch.cat(flat) if flat else torch.zeros(0)).to(device=logits.device, dtype=torch.long)
+            counts = [[int(y.numel()) for y in rec] for rec in texts]
+            res = ops.ctc_segment(logits, lens_dev, labels, counts, free_ends=True, window=window)
+            # one read: [begin, end, logp, confidence] per utterance, then the labels and the scores
+            packed = torch.cat([res.utt_begin.double(), res.utt_end.double(), res.utt_logp.double(), res.utt_conf.double(),
+                                labels.double(), res.score.double()]).cpu()
+        n = sum(len(rec) for rec in counts)
+        begin, end = packed[:n].long().tolist(), packed[n:2 * n].long().tolist()
+        logp, conf = packed[2 * n:3 * n].tolist(), packed[3 * n:4 * n].tolist()
+        toks, score = packed[4 * n:4 * n + labels.numel()].long().tolist(), packed[4 * n + labels.numel():].tolist()
+        out, u, o = [], 0, 0
+        for b, rec in enumerate(counts):
+            utts = []
+            for c in rec:
+                utts.append(dict(tokens=toks[o:o + c], begin=begin[u], end=end[u], logp=logp[u], confidence=conf[u]))
+                u += 1
+                o += c
+            out.append(dict(score=score[b], frames=int(enc_lens[b]), utterances=utts))
+        self.last_segmentation = res
+        return out
+
     def align_rnnt(self, xs, ilens, ys):
         """Forced alignment of the transcripts `ys` (a list of label tensors, as forward takes them) to the utterances with
         the transducer head (not a reference method): encoder, TransducerHead.logits, ops.rnnt_align.  -> one

@@ -1199,6 +1199,65 @@ def ctc_align(logits, frame_lens_dev, labels_packed, label_lens):
     return out
 
 
+class CtcSegmentation(object):
+    """What ops.ctc_segment returns, every field a device tensor: path int32 [B, T'] (the token of each encoder frame, 0 =
+    blank, -2 outside the text with free ends, -1 behind the recording and in every frame of an infeasible one), score fp32
+    [B], first / last int32 and token_logp fp32 packed like the labels, offsets int32 [B + 1] (CtcAlignment's fields, per
+    recording); and per utterance, packed [N] in the order of the recordings: utt_begin / utt_end int32 (inclusive encoder
+    frames; -1: no labels, or infeasible), utt_logp fp32 (the path's log-probability over begin .. end), utt_conf fp32 (the
+    lowest window mean of the path's frame log-probabilities; both 0 without labels, -inf when infeasible); utt_offsets int32
+    [N + 1] (utterance u owns [utt_offsets[u], utt_offsets[u + 1]) of the packed label fields) and rec_utts int32 [B + 1]
+    (recording b owns the utterances rec_utts[b] .. rec_utts[b + 1] - 1); utt_lens: the host's counts."""
+
+    __slots__ = ("path", "score", "first", "last", "token_logp", "offsets", "utt_begin", "utt_end", "utt_logp", "utt_conf",
+                 "utt_offsets", "rec_utts", "utt_lens")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def ctc_segment(logits, frame_lens_dev, labels_packed, utt_lens, *, free_ends=True, window=30):
+    """-> CtcSegmentation: CTC segmentation (Kuerzinger et al. 2020) of each recording against its transcript,
+    asr_ctc_segment_f32 (csrc/ctc_segment.hip), two launches.  logits [B, T', V] fp32 raw, frame_lens_dev int32
+    [B] on the device, labels_packed ONE int64 device tensor (every recording's utterances one after the other), utt_lens a
+    list per recording of the label counts of its utterances; blank = 0.  free_ends: the audio before the first and after the
+    last label costs nothing (False: ops.ctc_align's alignment, bit for bit, up to hb.CTC_SEG_MAX_LABELS labels); window: the
+    frames per block of the confidence.  Forward only: logits that require grad are accepted and nothing is recorded.  No host
+    synchronisation."""
+    logits = logits.detach()
+    B, T, V = logits.shape
+    counts = [[int(n) for n in rec] for rec in utt_lens]
+    if len(counts) != B:
+        raise ValueError("ctc_segment: utterance counts for %d recordings, the logits hold %d" % (len(counts), B))
+    if int(window) < 1:
+        raise ValueError("ctc_segment: window %d (at least 1 frame)" % int(window))
+    offsets, utt_offsets, rec_utts = [0], [0], [0]
+    for rec in counts:
+        for n in rec:
+            if n < 0:
+                raise ValueError("ctc_segment: an utterance of %d labels" % n)
+            utt_offsets.append(utt_offsets[-1] + n)
+        offsets.append(utt_offsets[-1])
+        rec_utts.append(len(utt_offsets) - 1)
+    if offsets[-1] != labels_packed.numel():
+        raise ValueError("ctc_segment: the utterance lengths sum to %d, the packed labels hold %d"
+                         % (offsets[-1], labels_packed.numel()))
+    lmax = max(offsets[b + 1] - offsets[b] for b in range(B))
+    total, N, dev = offsets[-1], len(utt_offsets) - 1, logits.device
+    ws = torch.empty((hb.ctc_segment_ws_bytes(B, T, V, lmax) + 3) // 4, device=dev, dtype=torch.float32)
+    i32, f32 = dict(device=dev, dtype=torch.int32), dict(device=dev, dtype=torch.float32)
+    out = CtcSegmentation(path=torch.empty(B, T, **i32), score=torch.empty(B, **f32), first=torch.empty(total, **i32),
+                          last=torch.empty(total, **i32), token_logp=torch.empty(total, **f32),
+                          offsets=hb.to_device_i32(offsets, dev), utt_begin=torch.empty(N, **i32), utt_end=torch.empty(N, **i32),
+                          utt_logp=torch.empty(N, **f32), utt_conf=torch.empty(N, **f32),
+                          utt_offsets=hb.to_device_i32(utt_offsets, dev), rec_utts=hb.to_device_i32(rec_utts, dev), utt_lens=counts)
+    hb.ctc_segment(logits, frame_lens_dev, labels_packed.contiguous(), out.offsets, lmax, free_ends, out.utt_offsets,
+                   out.rec_utts, int(window), out.path, out.score, out.first, out.last, out.token_logp, out.utt_begin,
+                   out.utt_end, out.utt_logp, out.utt_conf, ws)
+    return out
+
+
 class RnntAlignment(object):
     """What ops.rnnt_align returns, every field a device tensor: score fp32 [B] (the best alignment's log-probability, -inf:
     the row cannot be aligned), packed like the labels emit_frame int32 (the encoder frame on which label i is emitted, -1:

@@ -684,6 +684,33 @@ class Solver(object):
             self.model.train(was_training)
         return records
 
+    def segment(self, loader_or_batches, min_confidence=None, window=30):
+        """CTC segmentation of recordings against their transcripts with the model's CTC head (E2E.segment; the
+        model needs `ctc_weight` > 0).  `loader_or_batches` yields (xs, ilens, texts) with `texts` a list, per recording, of
+        label tensors, one per utterance.  -> one record per recording, in order: score, frames and utterances, each with
+        tokens (the vocabulary's symbols), begin / end (inclusive encoder frames; times model.time_reduction for input
+        frames), logp, confidence and keep (confidence >= min_confidence; True when no threshold is given).  The device
+        results are read once per batch."""
+        self.flush()
+        symbols = {i: s for s, i in self.vocab.items()}
+        was_training = self.model.training
+        self.model.eval()
+        records = []
+        try:
+            for xs, ilens, texts in loader_or_batches:
+                out = self.model.segment(xs, ilens, texts, window=window)
+                if self._abort_seen(xs.device):                 # see _greedy
+                    hb.disable_persistent(xs.device)
+                    out = self.model.segment(xs, ilens, texts, window=window)
+                for rec in out:
+                    for utt in rec["utterances"]:
+                        utt["tokens"] = [symbols[i] for i in utt["tokens"]]
+                        utt["keep"] = bool(min_confidence is None or utt["confidence"] >= min_confidence)
+                records += out
+        finally:
+            self.model.train(was_training)
+        return records
+
     def align_rnnt(self, loader=None):
         """Forced alignment of every utterance of `loader` (default: the dev loader) to its transcript with the model's
         transducer head (E2E.align_rnnt; the model needs `rnnt_weight` > 0) -> one record per utterance, in
