@@ -2276,27 +2276,90 @@ def upload_side_stream_for(n_frames):
         UPLOAD_SIDE_STREAM[0] = int(n_frames) >= UPLOAD_SIDE_MIN_FRAMES
 
 
+RING_SLOTS = 8
+
+
+def _ring_event():
+    """The event behind a lap's copies (no timing: the cheap kind)."""
+    return torch.cuda.Event()
+
+
+def _ring_buffer(size, torch_dtype):
+    return torch.empty(size, dtype=torch_dtype).pin_memory()
+
+
+def _ring_new(size, torch_dtype):
+    return dict(bufs=[_ring_buffer(size, torch_dtype) for _ in range(RING_SLOTS)], i=0, stream=None, open=False, lap=[],
+                pending=[], retired=[])
+
+
+def _ring_stage(ring, flat):
+    """Next slot of `ring`, filled with the host tensor `flat` -> slot index.  The slot's buffer was the source of an
+    asynchronous copy RING_SLOTS uploads ago, and a copy reads its pinned source when it RUNS: the buffer is rewritten only
+    once that copy is known to have run.  One event per lap of the ring says so (_ring_sent records it behind the lap's last
+    copy): at the start of a lap the events of the lap before are looked at once, and in the steady state they have fired
+    long ago - the other seven uploads of the lap cost nothing.  With a GPU that lags further behind (a pipelined step, a
+    long kernel in front) the host does NOT wait: while an event is outstanding, every slot it comes to retires its buffer
+    (kept alive until those events have fired) and takes a fresh one."""
+    k = ring["i"] % RING_SLOTS
+    ring["i"] += 1
+    if k == 0 and ring["lap"]:
+        ring["pending"], ring["lap"] = ring["pending"] + ring["lap"], []
+    if ring["pending"]:
+        ring["pending"] = [e for e in ring["pending"] if not e.query()]
+        if ring["pending"]:
+            ring["retired"] = [(b, evs) for b, evs in ring["retired"] if not all(e.query() for e in evs)]
+            ring["retired"].append((ring["bufs"][k], list(ring["pending"])))
+            ring["bufs"][k] = _ring_buffer(flat.numel(), flat.dtype)
+        else:
+            ring["retired"] = []            # (every event a retired buffer waited for was in `pending`)
+    ring["bufs"][k].copy_(flat)
+    return k
+
+
+def _ring_sent(ring, k, stream):
+    """The copy out of slot k has just been enqueued on `stream`.  The lap's event goes behind its last copy; a lap whose
+    copies went to more than one stream (the upload stream switched on or off, another current stream) gets one per stream."""
+    if ring["open"] and ring["stream"] != stream:
+        ev = _ring_event()
+        ev.record(ring["stream"])
+        ring["lap"].append(ev)
+    ring["stream"], ring["open"] = stream, True
+    if k == RING_SLOTS - 1:
+        ev = _ring_event()
+        ev.record(stream)
+        ring["lap"].append(ev)
+        ring["open"] = False
+
+
 def _to_device(arr, torch_dtype, device):
     """Host array -> device tensor without blocking the host and without a place in the compute stream: staged through a
     small ring of pinned buffers and copied on a side stream (the compute stream only waits for the copy's event - the
     host runs ahead of the GPU, so the copy has long finished when the stream gets there; as an in-stream copy each of
-    these small uploads cost ~10 us of the step)."""
+    these small uploads cost ~10 us of the step).  The tensor returned keeps its values whatever the host does next: every
+    lap of the ring leaves an event behind its copies, on the stream that runs them, and a buffer is rewritten only after
+    the events of the lap before have fired (_ring_stage); on the CPU the result owns its memory."""
+    dev = torch.device(device)
+    flat = torch.from_numpy(arr.reshape(-1))
+    if dev.type != "cuda":      # (no copy engine, no ring: .to("cpu") of a host buffer is the buffer itself)
+        return flat.to(torch_dtype, copy=True).view(arr.shape)
     key = (str(device), str(torch_dtype), arr.size)
     ring = _pinned_ring.get(key)
     if ring is None:            # (not setdefault(key, dict(...)): its default is built - eight pinned allocations - on EVERY call)
-        ring = _pinned_ring[key] = dict(bufs=[torch.empty(arr.size, dtype=torch_dtype).pin_memory() for _ in range(8)], i=0)
-    buf = ring["bufs"][ring["i"] % 8]
-    ring["i"] += 1
-    buf.copy_(torch.from_numpy(arr.reshape(-1)))
-    dev = torch.device(device)
-    if dev.type != "cuda" or not UPLOAD_SIDE_STREAM[0]:
-        return buf.to(device, non_blocking=True).view(arr.shape)
+        ring = _pinned_ring[key] = _ring_new(arr.size, torch_dtype)
+    k = _ring_stage(ring, flat)
+    buf = ring["bufs"][k]
+    main = torch.cuda.current_stream(dev)
+    if not UPLOAD_SIDE_STREAM[0]:
+        out = buf.to(dev, non_blocking=True)
+        _ring_sent(ring, k, main)
+        return out.view(arr.shape)
     side = _upload_streams.get(str(dev))
     if side is None:
         side = _upload_streams.setdefault(str(dev), torch.cuda.Stream(device=dev))
-    main = torch.cuda.current_stream(dev)
     with torch.cuda.stream(side):
         out = buf.to(dev, non_blocking=True)
+    _ring_sent(ring, k, side)
     main.wait_stream(side)
     out.record_stream(main)
     return out.view(arr.shape)

@@ -588,7 +588,9 @@ class _Pyramid(torch.autograd.Function):
         if ctx.rep is not None:                    # the replica's gradient belongs to the frame it copies; the padding row
             dout = dout.clone()                    # whose place it took gets none
             dout[ctx.rep, 0, :C] += dout[ctx.rep, 0, C:]
-            dout[ctx.rep, 0, C:] = 0.0
+            # (not `dout[ctx.rep, 0, C:] = 0.0`: the scalar goes to the device by a blocking copy, and the host, which
+            # is to stay a step ahead of the GPU, waits in every backward pass for all that is queued)
+            dout[:, 0, C:].index_fill_(0, ctx.rep, 0.0)
         hb.pyramid_bwd(dout, ctx.mask, din)
         return din, None, None
 
