@@ -917,6 +917,51 @@ int asr_ctc_loss_bwd(int B, int T, int V, const float* logits, int64_t ld, const
                      int64_t ws_bytes, float* dlogits, int64_t lddz, asr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Star CTC: the CTC loss for transcripts with missing words (csrc/ctc_star.hip; after Star Temporal
+ * Classification, Pratap et al. 2022, and its relatives W-CTC and OTC).  Three entries added to ABI version 8 WITHOUT a
+ * version change, like the CTC loss entries: additive - no existing entry, constant or kernel changes.
+ * The arguments and conventions are asr_ctc_loss_fwd's (raw logits [B][T][V] with row stride ld, blank = 0, frame_lens int32
+ * [B] on the device, one packed int64 label tensor with int32 offsets, x[t][v] = z[t][v] - logsumexp_v z[t]), plus
+ *   penalty       fp32 [B] on the device: the price of one frame in a star state, <= 0 or -inf (the caller's to check).
+ * Per frame nb[t] = logsumexp_{v >= 1} z[t][v] - lse[t], a direct log-sum-exp over the non-blank entries (never
+ * log(1 - p_0)).  For labels l_1 .. l_L the lattice has S = 3 L + 2 states: b_0, s_0, then (l_g, b_g, s_g) for g = 1 .. L.
+ *   emission      b_g: x[t][0]    l_g: x[t][l_g]    s_g: nb[t] + penalty[b]   ("any token", at a price)
+ *   b_g comes from b_g, s_g, and l_g if g >= 1;   s_g comes from s_g, b_g, and l_g if g >= 1;
+ *   l_g comes from l_g, b_{g-1}, s_{g-1}, and l_{g-1} if g >= 2 and l_g != l_{g-1};  every transition takes one frame.
+ *   Frame 0 sits in b_0, s_0 or l_1; the path ends in l_L, b_L or s_L (L = 0: b_0 or s_0).
+ *   nll[b] = -logsumexp over all state paths of the summed emissions: the path sum of this automaton, NOT a normalised
+ *   probability (a star frame and a label frame may both count the same token) - it may be negative when the penalty is near
+ *   0, and nll_star <= nll_ctc always.  penalty = -inf leaves the star states unreachable: the plain CTC lattice.
+ * A row is infeasible when frames < labels + adjacent equal labels, when a label lies outside [1, V) or there are more than
+ * max_label_len of them, or when it has no frame (T_b = 0, whatever L): nll = +inf, or 0 with zero_infinity.
+ *   max_label_len at most ASR_CTC_STAR_MAX_LABELS (3 L + 2 states fit the LDS rows of the CTC chains); V >= 2: ASR_E_SHAPE
+ *                 otherwise.  It picks the kernel by 3 max_label_len + 2 states: one wave per utterance up to 64 states
+ *                 (max_label_len <= 20), one 256-thread workgroup with a state per thread up to 256 (<= 84), states strided
+ *                 over the threads beyond (>= 85).
+ *   asr_ctc_star_ws_bytes   4 ( B T (3 max_label_len + 4) + B (max_label_len + V + 1) ), each of the six parts rounded up to
+ *                 64 words: lse, nb, the raw nll, alpha, the label-sorted position list, its heads.  The workspace is 4-byte
+ *                 aligned (ASR_E_ARG otherwise, and when it is too small); the forward fills it, the backward overwrites
+ *                 alpha with the log occupancy of every (t, s): one backward per forward, same arguments.
+ *   asr_ctc_star_loss_fwd   three launches (lse and nb per frame; alpha).
+ *   asr_ctc_star_loss_bwd   dlogits[b][t][k] = grad_nll[b] (softmax_k - occ_k), with gamma_t(s) the state occupancy,
+ *                 occ_k = sum_{s : label k} gamma_t(s) + [k >= 1] (sum_g gamma_t(s_g)) exp(x[t][k] - nb[t]);
+ *                 row stride lddz >= V; exact zeros for t >= frame_lens[b] and, with zero_infinity, for an infeasible
+ *                 utterance (without it: grad_nll[b] softmax_k).  No gradient flows to penalty.  Two launches.
+ * No floating-point atomics: the blank's and the star's sums are taken by the wave (lane-strided ascending, then the xor
+ * butterfly), each label's by ONE lane along the sorted position list - the same bits in every run, in and outside
+ * deterministic mode, whatever the rest of the batch.  No host synchronisation, no allocation.
+ * ------------------------------------------------------------------------------------- */
+#define ASR_CTC_STAR_MAX_LABELS 681
+int asr_ctc_star_ws_bytes(int B, int T, int V, int max_label_len, int64_t* ws_bytes);
+int asr_ctc_star_loss_fwd(int B, int T, int V, const float* logits, int64_t ld, const int32_t* frame_lens,
+                          const int64_t* labels, const int32_t* label_offsets, int max_label_len, const float* penalty,
+                          int zero_infinity, float* nll, void* ws, int64_t ws_bytes, asr_stream_t stream);
+int asr_ctc_star_loss_bwd(int B, int T, int V, const float* logits, int64_t ld, const int32_t* frame_lens,
+                          const int64_t* labels, const int32_t* label_offsets, int max_label_len, const float* penalty,
+                          int zero_infinity, const float* grad_nll, void* ws, int64_t ws_bytes, float* dlogits, int64_t lddz,
+                          asr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Joint CTC-attention decoding: the CTC prefix score inside the beam search (csrc/ctc_prefix.hip, the CTC variants of the
  * select kernel in csrc/beam.hip).  Four entries added to ABI version 8 WITHOUT a version change, like the CTC
  * loss entries: additive - no existing entry, structure or constant changes, and asr_beam_select_f32 /

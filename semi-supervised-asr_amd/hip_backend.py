@@ -29,6 +29,7 @@ EXPORTS = (
     "asr_colsum_det_f32", "asr_gemm_det_f32", "asr_gemm_det_ws_bytes", "asr_embedding_grad_det_f32", "asr_rows_fill_grad_det_f32",
     "asr_sumsq_det_f32", "asr_gather_sumsq_det_f32", "asr_sum_det_f32", "asr_dec_step_bwd_det", "asr_dec_seq_bwd_det",
     "asr_ctc_ws_bytes", "asr_ctc_loss_fwd", "asr_ctc_loss_bwd",
+    "asr_ctc_star_ws_bytes", "asr_ctc_star_loss_fwd", "asr_ctc_star_loss_bwd",
     "asr_ctc_prefix_init_f32", "asr_ctc_prefix_score_f32", "asr_beam_select_ctc_f32", "asr_ctc_prefix_advance_f32",
     "asr_ctc_align_ws_bytes", "asr_ctc_align_f32", "asr_ctc_greedy_f32",
     "asr_ctc_segment_ws_bytes", "asr_ctc_segment_f32",
@@ -312,6 +313,9 @@ def load():
     lib.asr_ctc_ws_bytes.argtypes = [c_i, c_i, c_i, c_i, ctypes.POINTER(c_i64)]
     lib.asr_ctc_loss_fwd.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i64, c_p]
     lib.asr_ctc_loss_bwd.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i64, c_p, c_i64, c_p]
+    lib.asr_ctc_star_ws_bytes.argtypes = [c_i, c_i, c_i, c_i, ctypes.POINTER(c_i64)]
+    lib.asr_ctc_star_loss_fwd.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_i64, c_p]
+    lib.asr_ctc_star_loss_bwd.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_i64, c_p, c_i64, c_p]
     lib.asr_ctc_prefix_init_f32.argtypes = [ctypes.POINTER(CtcPrefix), ctypes.POINTER(ctypes.c_int32), c_p]
     lib.asr_ctc_prefix_score_f32.argtypes = [ctypes.POINTER(CtcPrefix), ctypes.POINTER(Beam), c_i, c_p]
     lib.asr_beam_select_ctc_f32.argtypes = [ctypes.POINTER(Beam), c_p, c_f, c_p, c_p, c_f, c_i, c_p]
@@ -1132,6 +1136,60 @@ def ctc_loss_bwd(logits, ld, frame_lens, labels, label_offsets, max_label_len, z
     check(load().asr_ctc_loss_bwd(*args, ptr(grad_nll), ptr(ws), ws.numel() * 4, ptr(dlogits), int(lddz), stream()),
           "asr_ctc_loss_bwd")
     LAUNCHES["ctc_loss_bwd"] += 1
+    return dlogits
+
+
+CTC_STAR_MAX_LABELS = 681     # ASR_CTC_STAR_MAX_LABELS: 3 L + 2 states within the CTC chains' 2 * 1023 + 1
+
+
+def ctc_star_ws_bytes(B, T, V, max_label_len):
+    """asr_ctc_star_ws_bytes on plain integers (no tensors, no GPU) -> the workspace bytes of a star CTC call; UnsupportedShape
+    for sizes the kernels refuse (more than CTC_STAR_MAX_LABELS labels, V < 2)."""
+    need = c_i64(0)
+    rc = load().asr_ctc_star_ws_bytes(int(B), int(T), int(V), int(max_label_len), ctypes.byref(need))
+    if rc == -2:
+        raise UnsupportedShape("ctc_star_loss: B %d, T %d, V %d, %d labels (at most %d labels, V >= 2)"
+                               % (B, T, V, max_label_len, CTC_STAR_MAX_LABELS))
+    check(rc, "asr_ctc_star_ws_bytes")
+    return need.value
+
+
+def _ctc_star_args(logits, ld, frame_lens, labels, label_offsets, max_label_len, penalty, zero_infinity):
+    B, T, V = logits.shape
+    if labels.dtype != torch.long or not labels.is_cuda:
+        raise RuntimeError("ctc_star_loss: labels must be one packed int64 tensor on the GPU")
+    if penalty.dtype != torch.float32 or not penalty.is_cuda or penalty.shape != (B,) or not penalty.is_contiguous():
+        raise RuntimeError("ctc_star_loss: penalty must be a contiguous fp32 [B] tensor on the GPU")
+    return (B, T, V, ptr(logits), int(ld), ptr(frame_lens), c_p(labels.data_ptr()), ptr(label_offsets), int(max_label_len),
+            ptr(penalty), int(bool(zero_infinity)))
+
+
+def _star_ws(ws, ws_bytes):
+    """(pointer, bytes) of a workspace tensor of any dtype on the GPU - the library checks alignment and size itself"""
+    if not ws.is_cuda:
+        raise RuntimeError("ctc_star_loss: the workspace must live on the GPU")
+    return c_p(ws.data_ptr()), ws.numel() * ws.element_size() if ws_bytes is None else int(ws_bytes)
+
+
+def ctc_star_loss_fwd(logits, ld, frame_lens, labels, label_offsets, max_label_len, penalty, zero_infinity, nll, ws,
+                      ws_bytes=None):
+    """asr_ctc_star_loss_fwd: ctc_loss_fwd's arguments plus penalty, fp32 [B] on the device (<= 0 or -inf: the caller's to
+    check).  nll [B] and the workspace ws (at least ctc_star_ws_bytes bytes, 4-byte aligned; ws_bytes: what the library is
+    told it holds, the tensor's size by default) are the caller's.  The workspace goes to ctc_star_loss_bwd unchanged."""
+    args = _ctc_star_args(logits, ld, frame_lens, labels, label_offsets, max_label_len, penalty, zero_infinity)
+    check(load().asr_ctc_star_loss_fwd(*args, ptr(nll), *_star_ws(ws, ws_bytes), stream()), "asr_ctc_star_loss_fwd")
+    LAUNCHES["ctc_star_loss"] += 1
+    return nll
+
+
+def ctc_star_loss_bwd(logits, ld, frame_lens, labels, label_offsets, max_label_len, penalty, zero_infinity, grad_nll, ws,
+                      dlogits, lddz, ws_bytes=None):
+    """asr_ctc_star_loss_bwd behind a ctc_star_loss_fwd with the same arguments and workspace: dlogits [B, T, >= V] with row
+    stride lddz gets grad_nll[b] d nll_b / d logits, exact zeros behind each utterance."""
+    args = _ctc_star_args(logits, ld, frame_lens, labels, label_offsets, max_label_len, penalty, zero_infinity)
+    check(load().asr_ctc_star_loss_bwd(*args, ptr(grad_nll), *_star_ws(ws, ws_bytes), ptr(dlogits), int(lddz), stream()),
+          "asr_ctc_star_loss_bwd")
+    LAUNCHES["ctc_star_loss_bwd"] += 1
     return dlogits
 
 

@@ -795,7 +795,8 @@ class E2E(torch.nn.Module):
 
     def __init__(self, input_dim, enc_hidden_dim, enc_n_layers, subsample, dropout_rate, dec_hidden_dim, att_dim,
                  conv_channels, conv_kernel_size, att_odim, embedding_dim, output_dim, ls_weight, labeldist,
-                 pad=0, bos=1, eos=2, ctc_weight=0.0, rnnt_weight=0.0, rnnt_joint_dim=256, rnnt_pred_dim=None):
+                 pad=0, bos=1, eos=2, ctc_weight=0.0, rnnt_weight=0.0, rnnt_joint_dim=256, rnnt_pred_dim=None,
+                 ctc_star_penalty=None):
         super(E2E, self).__init__()
         self.encoder = Encoder(input_dim=input_dim, hidden_dim=enc_hidden_dim, n_layers=enc_n_layers,
                                subsample=subsample, dropout_rate=dropout_rate)
@@ -815,6 +816,16 @@ class E2E(torch.nn.Module):
             if pad != 0:
                 raise ValueError("the CTC branch takes <PAD> = 0 as its blank; pad is %d" % pad)
             self.ctc_lo = torch.nn.Linear(enc_hidden_dim, output_dim)
+        # `ctc_star_penalty` (not in the reference): a float <= 0 makes the CTC term of a TRAINING step the star
+        # CTC loss (ops.ctc_star_loss) - transcripts with missing words; None: the plain loss, launch for launch.  A plain
+        # attribute, no parameter and no state_dict key: it may be reassigned between steps (a penalty schedule is the
+        # caller's host arithmetic).  In eval mode the plain CTC loss runs, so a dev loss stays comparable.
+        self.ctc_star_penalty = None if ctc_star_penalty is None else float(ctc_star_penalty)
+        if self.ctc_star_penalty is not None:
+            if self.ctc_weight <= 0:
+                raise ValueError("ctc_star_penalty needs the CTC branch: ctc_weight is 0")
+            if not self.ctc_star_penalty <= 0:
+                raise ValueError("ctc_star_penalty must be <= 0, got %r" % (ctc_star_penalty,))
         # `rnnt_weight` (not in the reference): w > 0 adds the transducer head and trains on
         # (1 - w_ctc - w_rnnt) L_att + w_ctc L_ctc + w_rnnt L_rnnt.  Like the CTC branch the head exists only
         # then: at 0 its parameters, its state_dict keys and every launch are absent.
@@ -914,11 +925,15 @@ class E2E(torch.nn.Module):
         """Per-utterance CTC negative log-likelihood [B] of the labels `ys` given the encoder output enc_h [B, T', H] of the
         forward that has just run (the frame lengths are the encoder's device copy): ctc_lo over the B T' rows on the GEMM,
         then ops.ctc_loss on the raw logits.  An utterance with fewer frames than its labels need counts as 0
-        (zero_infinity), like torch.nn.functional.ctc_loss(zero_infinity=True)."""
+        (zero_infinity), like torch.nn.functional.ctc_loss(zero_infinity=True).  In training mode with
+        self.ctc_star_penalty set: ops.ctc_star_loss with that penalty for every row instead."""
         bsz, frames, hid = enc_h.shape
         logits = ops.linear(enc_h.reshape(bsz * frames, hid), self.ctc_lo.weight, self.ctc_lo.bias).view(bsz, frames, -1)
         labels = torch.cat([y.reshape(-1) for y in ys]).to(device=enc_h.device, dtype=torch.long)
-        return ops.ctc_loss(logits, self.encoder.enc2.last_lens_dev, labels, [int(y.size(0)) for y in ys], True)
+        ylens = [int(y.size(0)) for y in ys]
+        if self.training and self.ctc_star_penalty is not None:
+            return ops.ctc_star_loss(logits, self.encoder.enc2.last_lens_dev, labels, ylens, self.ctc_star_penalty, True)
+        return ops.ctc_loss(logits, self.encoder.enc2.last_lens_dev, labels, ylens, True)
 
     def recognize_beams(self, data, ilens, max_dec_timesteps, topk, length_penalty=0.0, nbest=False, *, lm=None,
                         lm_weight=0.0, ctc_decode_weight=0.0, ngram=None, ngram_weight=0.0, ngram_bonus=0.0, word_lm=None,

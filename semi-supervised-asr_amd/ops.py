@@ -998,6 +998,80 @@ def ctc_loss(logits, frame_lens_dev, labels_packed, label_lens, zero_infinity=Tr
     return _CtcLoss.apply(logits, frame_lens_dev, labels_packed, label_lens, zero_infinity)
 
 
+class _CtcStarLoss(torch.autograd.Function):
+    """Star CTC negative log path sum per utterance of RAW logits [B, T', V] -> nll [B]: asr_ctc_star_loss_fwd / _bwd
+    (csrc/ctc_star.hip), three launches forward and two backward.  _CtcLoss with one more input, the per-row
+    penalty (fp32 [B] on the device; no gradient flows to it): the same pooled workspace lease from the forward to the end of
+    the backward, ordered sums only, no host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, logits, frame_lens, labels, label_lens, penalty, zero_infinity):
+        B, T, V = logits.shape
+        if not (logits.stride(2) == 1 and logits.stride(1) >= V and logits.stride(0) == T * logits.stride(1)):
+            logits = logits.contiguous()
+        ld = logits.stride(1)
+        lens, offsets, lmax = _label_offsets("ctc_star_loss", label_lens, B, labels.numel())
+        dev = logits.device
+        words = (hb.ctc_star_ws_bytes(B, T, V, lmax) + 3) // 4
+        if ctx.needs_input_grad[0]:
+            cap = _row_capacity(words)
+            ctx.lease = _POOL.acquire(("ctc_star", str(dev), cap), lambda: torch.empty(cap, device=dev, dtype=torch.float32))
+            ws = ctx.lease.ws
+        else:
+            ctx.lease, ws = None, torch.empty(words, device=dev, dtype=torch.float32)
+        offs_dev = hb.to_device_i32(offsets, dev)
+        labels = labels.contiguous() if labels.numel() else torch.zeros(1, device=dev, dtype=torch.long)
+        nll = torch.empty(B, device=dev, dtype=torch.float32)
+        hb.ctc_star_loss_fwd(logits, ld, frame_lens, labels, offs_dev, lmax, penalty, zero_infinity, nll, ws)
+        ctx.save_for_backward(logits, frame_lens, labels, offs_dev, penalty)
+        ctx.ld, ctx.lmax, ctx.zero_infinity = ld, lmax, bool(zero_infinity)
+        return nll
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, frame_lens, labels, offs_dev, penalty = ctx.saved_tensors
+        if ctx.lease is None or ctx.lease.ws is None:
+            raise RuntimeError("ctc_star_loss: the backward runs once, behind a forward that ran with autograd enabled")
+        B, T, V = logits.shape
+        dz = torch.empty(B, T, V, device=logits.device, dtype=torch.float32)
+        hb.ctc_star_loss_bwd(logits, ctx.ld, frame_lens, labels, offs_dev, ctx.lmax, penalty, ctx.zero_infinity,
+                             g.contiguous(), ctx.lease.ws, dz, V)
+        ctx.lease.release()
+        return dz, None, None, None, None, None
+
+
+def ctc_star_loss(logits, frame_lens_dev, labels_packed, label_lens, penalty, zero_infinity=True):
+    """-> nll [B]: the star CTC loss of each utterance, for transcripts with missing words (after Star Temporal
+    Classification, Pratap et al. 2022).  The arguments are ctc_loss's plus `penalty`: between any two labels, before the
+    first and behind the last the lattice may spend frames in a star state that emits "any non-blank token" at
+    log p(non-blank) + penalty per frame.  penalty is a Python float for every row or an fp32 [B] tensor, each value <= 0 or
+    -inf; ValueError for a positive or NaN value (a tensor on the GPU is read back once for that check: pass a float or a host
+    tensor where that matters).  -inf closes the star states of a row - the plain CTC lattice; a float -inf or None calls
+    ctc_loss itself.
+    The value is the negative log PATH SUM of the star lattice, not a normalised probability: a frame's token may count both
+    as a label and as a star, so nll may be negative when the penalty is near 0, and nll <= the CTC nll always.  Infeasible
+    rows and zero_infinity as in ctc_loss (a row without frames is infeasible whatever its labels).  No gradient flows to
+    penalty."""
+    if penalty is None:
+        return ctc_loss(logits, frame_lens_dev, labels_packed, label_lens, zero_infinity)
+    B = logits.shape[0]
+    if torch.is_tensor(penalty):
+        host = penalty.detach().to(device="cpu", dtype=torch.float32).reshape(-1)
+        if host.numel() != B:
+            raise ValueError("ctc_star_loss: %d penalties for %d utterances" % (host.numel(), B))
+        if bool((torch.isnan(host) | (host > 0)).any()):
+            raise ValueError("ctc_star_loss: every penalty must be <= 0 (or -inf), got %r" % (host.tolist(),))
+        pen = penalty.detach().to(device=logits.device, dtype=torch.float32).reshape(B).contiguous()
+    else:
+        p = float(penalty)
+        if p != p or p > 0:
+            raise ValueError("ctc_star_loss: the penalty must be <= 0 (or -inf), got %r" % (penalty,))
+        if p == float("-inf"):
+            return ctc_loss(logits, frame_lens_dev, labels_packed, label_lens, zero_infinity)
+        pen = torch.full((B,), p, device=logits.device, dtype=torch.float32)
+    return _CtcStarLoss.apply(logits, frame_lens_dev, labels_packed, label_lens, pen, zero_infinity)
+
+
 def _label_offsets(what, label_lens, B, n_labels=None):
     """Host label counts -> (counts, offsets [B + 1], the largest count); ValueError where they do not fit the batch."""
     lens = [int(n) for n in label_lens]

@@ -232,6 +232,9 @@ class Solver(object):
             # `ctc_weight` (not a reference key; default 0): w > 0 adds the CTC branch on the encoder and every labeled
             # step trains on (1 - w) L_att + w L_ctc; at 0 the model is the reference's
             ctc_weight=float(cfg.get("ctc_weight", 0.0)),
+            # `ctc_star_penalty` (not a reference key; absent or null = off): a float <= 0 makes the CTC term of every
+            # training step the star CTC loss, for transcripts with missing words; it needs ctc_weight > 0
+            ctc_star_penalty=cfg.get("ctc_star_penalty", None),
             # `rnnt_weight`, `rnnt_joint_dim`, `rnnt_pred_dim` (not reference keys; absent by default): w > 0 adds the
             # transducer head and the term w L_rnnt; the keys reach the model only then
             **self.rnnt_model_args(cfg)))
