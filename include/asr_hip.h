@@ -962,6 +962,76 @@ int asr_ctc_star_loss_bwd(int B, int T, int V, const float* logits, int64_t ld, 
                           asr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Graph CTC (GTC; Moritz et al. 2021): a CTC loss over a label graph, for n-best pseudo-labels, confusion networks and any
+ * other supervision that is a weighted set of label sequences (csrc/gtc.hip; the graphs are built and
+ * validated on the host, gtc.py).  Three entries added to ABI version 8 WITHOUT a version change: additive - no existing
+ * entry, constant or kernel changes.  The arguments and conventions are asr_ctc_loss_fwd's (raw logits [B][T][V] with row
+ * stride ld, blank = 0, frame_lens int32 [B] on the device, x[t][v] = z[t][v] - logsumexp_v z[t]), with a graph table and
+ * graph_of int32 [B] on the device (the graph of every row, in 0 .. G-1; rows may share a graph) in place of the labels.
+ * Definition.  Per utterance there is a graph with N nodes.  Node n has a token lab[n] in [0, V) (0 = blank), a start
+ * weight start[n] and a final weight fin[n], fp32, finite or -inf.  Arcs (m -> n, w) carry an fp32 weight w, finite.
+ * Self-loops are ordinary arcs and are never implied; there are no parallel arcs.  With T the row's frame count a path is
+ * n_0 .. n_{T-1} along arcs, its score
+ *   start[n_0] + sum_t x[t][lab[n_t]] + sum_{t >= 1} w(n_{t-1}, n_t) + fin[n_{T-1}]
+ * and nll = -logsumexp over all paths: a PATH SUM, not a normalised probability (the weights are any log numbers; two paths
+ * may spell the same tokens).  dlogits[b][t][k] = grad_nll[b] (softmax_k - occ_k), occ_k = sum_{n : lab[n] = k} gamma_t(n),
+ * gamma the node occupancy, normalised over the frame's nodes.  A row with no path of finite score, or with T = 0, is
+ * infeasible: nll = +inf, or 0 with zero_infinity, and a zero gradient either way.  No gradient flows to arc, start or
+ * final weights.
+ * The table (asr_gtc_graphs_t; every pointer on the device, no array empty; its contents are trusted on the device and
+ * validated on the host, like the context and n-gram tables).  G graphs concatenated, NN nodes and A arcs in all:
+ *   node_off int32 [G + 1]     the nodes of graph g are node_off[g] .. node_off[g + 1] - 1; arcs name nodes by their index
+ *                              inside the graph
+ *   lab int32 [NN], start, fin fp32 [NN]
+ *   in_ptr int32 [NN + 1], in_src int32 [A], in_w fp32 [A]       arcs by destination (CSR over all nodes), sources ascending
+ *   out_ptr int32 [NN + 1], out_dst int32 [A], out_w fp32 [A]    arcs by source, destinations ascending
+ *   order int32 [NN]           per graph its nodes sorted by (token, node)
+ *   head int32 [G][V]          (first index in the graph's order << 12) | run length of the token's nodes; 0: no node
+ *   V, G; max_nodes, max_arcs  the largest graph's, at most ASR_GTC_MAX_NODES (the CTC chains' 2 * 1023 + 1 states, so their
+ *                              LDS rows serve) and ASR_GTC_MAX_ARCS (65 536: both arc lists of a graph, 1 MiB, stay in a
+ *                              quarter of one XCD's L2 while a chain re-reads them every frame); V >= 2: ASR_E_SHAPE otherwise.
+ *                              max_nodes picks the kernel: one wave per utterance up to 64 nodes, a node per thread up to
+ *                              256, nodes strided over 256 threads beyond.
+ *   asr_gtc_ws_bytes   plain integers: 4 (B T (max_nodes + 1) + B), each of the three parts rounded up to 64 words: lse, the
+ *                      raw nll, alpha.  The workspace is 4-byte aligned (ASR_E_ARG otherwise, and when it is too small); the
+ *                      forward fills it, the backward overwrites alpha with the occupancy of every (t, n): one backward
+ *                      per forward, same arguments.
+ *   asr_gtc_loss_fwd   two launches (lse per frame; alpha).     asr_gtc_loss_bwd   two launches (the backward chain - the
+ *                      occupancies gamma_t(m) = sum over arcs (m -> n, w) of gamma_{t+1}(n) exp(alpha_t(m) + w - in_{t+1}(n)),
+ *                      in the log-sum-exp over n's incoming arcs, in linear space from the forward's own shares -; the gradient); row
+ *                      stride lddz >= V, exact zeros for t >= frame_lens[b] and for an infeasible row.
+ * A thread sums the arcs of its node with an online log-sum-exp in the table's order (-inf (+) x = x exactly; unreachable
+ * nodes stay -inf); the first four arcs of a node ride in registers, the rest are read from global memory every frame.  No
+ * floating-point atomics, every sum in an order fixed by the graph and the shapes: the same bits in every run, in and
+ * outside deterministic mode, whatever the rest of the batch.  No host synchronisation, no allocation.
+ * ------------------------------------------------------------------------------------- */
+#define ASR_GTC_MAX_NODES 2047
+#define ASR_GTC_MAX_ARCS 65536
+typedef struct {
+  int32_t V, G;                   /* tokens, graphs */
+  int32_t max_nodes, max_arcs;    /* of the largest graph */
+  const int32_t* node_off;
+  const int32_t* lab;
+  const float* start;
+  const float* fin;
+  const int32_t* in_ptr;
+  const int32_t* in_src;
+  const float* in_w;
+  const int32_t* out_ptr;
+  const int32_t* out_dst;
+  const float* out_w;
+  const int32_t* order;
+  const int32_t* head;
+} asr_gtc_graphs_t;
+int asr_gtc_ws_bytes(int B, int T, int V, int max_nodes, int64_t* ws_bytes);
+int asr_gtc_loss_fwd(int B, int T, int V, const float* logits, int64_t ld, const int32_t* frame_lens,
+                     const asr_gtc_graphs_t* graphs, const int32_t* graph_of, int zero_infinity, float* nll, void* ws,
+                     int64_t ws_bytes, asr_stream_t stream);
+int asr_gtc_loss_bwd(int B, int T, int V, const float* logits, int64_t ld, const int32_t* frame_lens,
+                     const asr_gtc_graphs_t* graphs, const int32_t* graph_of, int zero_infinity, const float* grad_nll,
+                     void* ws, int64_t ws_bytes, float* dlogits, int64_t lddz, asr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Joint CTC-attention decoding: the CTC prefix score inside the beam search (csrc/ctc_prefix.hip, the CTC variants of the
  * select kernel in csrc/beam.hip).  Four entries added to ABI version 8 WITHOUT a version change, like the CTC
  * loss entries: additive - no existing entry, structure or constant changes, and asr_beam_select_f32 /

@@ -30,6 +30,7 @@ EXPORTS = (
     "asr_sumsq_det_f32", "asr_gather_sumsq_det_f32", "asr_sum_det_f32", "asr_dec_step_bwd_det", "asr_dec_seq_bwd_det",
     "asr_ctc_ws_bytes", "asr_ctc_loss_fwd", "asr_ctc_loss_bwd",
     "asr_ctc_star_ws_bytes", "asr_ctc_star_loss_fwd", "asr_ctc_star_loss_bwd",
+    "asr_gtc_ws_bytes", "asr_gtc_loss_fwd", "asr_gtc_loss_bwd",
     "asr_ctc_prefix_init_f32", "asr_ctc_prefix_score_f32", "asr_beam_select_ctc_f32", "asr_ctc_prefix_advance_f32",
     "asr_ctc_align_ws_bytes", "asr_ctc_align_f32", "asr_ctc_greedy_f32",
     "asr_ctc_segment_ws_bytes", "asr_ctc_segment_f32",
@@ -77,6 +78,13 @@ class ContextTable(ctypes.Structure):
     _fields_ = [("V", ctypes.c_int32), ("N", ctypes.c_int32), ("G", ctypes.c_int32), ("R", ctypes.c_int32), ("A", c_i64),
                 ("arc_off", c_p), ("arc_tok", c_p), ("arc_next", c_p), ("drow", c_p), ("dflt", c_p), ("credit", c_p),
                 ("pending", c_p), ("root", c_p)]
+
+
+class GtcGraphs(ctypes.Structure):
+    """asr_gtc_graphs_t"""
+    _fields_ = [("V", ctypes.c_int32), ("G", ctypes.c_int32), ("max_nodes", ctypes.c_int32), ("max_arcs", ctypes.c_int32),
+                ("node_off", c_p), ("lab", c_p), ("start", c_p), ("fin", c_p), ("in_ptr", c_p), ("in_src", c_p), ("in_w", c_p),
+                ("out_ptr", c_p), ("out_dst", c_p), ("out_w", c_p), ("order", c_p), ("head", c_p)]
 
 
 class LstmUnpackJob(ctypes.Structure):
@@ -316,6 +324,10 @@ def load():
     lib.asr_ctc_star_ws_bytes.argtypes = [c_i, c_i, c_i, c_i, ctypes.POINTER(c_i64)]
     lib.asr_ctc_star_loss_fwd.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_i64, c_p]
     lib.asr_ctc_star_loss_bwd.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_i64, c_p, c_i64, c_p]
+    lib.asr_gtc_ws_bytes.argtypes = [c_i, c_i, c_i, c_i, ctypes.POINTER(c_i64)]
+    lib.asr_gtc_loss_fwd.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, ctypes.POINTER(GtcGraphs), c_p, c_i, c_p, c_p, c_i64, c_p]
+    lib.asr_gtc_loss_bwd.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, ctypes.POINTER(GtcGraphs), c_p, c_i, c_p, c_p, c_i64, c_p,
+                                     c_i64, c_p]
     lib.asr_ctc_prefix_init_f32.argtypes = [ctypes.POINTER(CtcPrefix), ctypes.POINTER(ctypes.c_int32), c_p]
     lib.asr_ctc_prefix_score_f32.argtypes = [ctypes.POINTER(CtcPrefix), ctypes.POINTER(Beam), c_i, c_p]
     lib.asr_beam_select_ctc_f32.argtypes = [ctypes.POINTER(Beam), c_p, c_f, c_p, c_p, c_f, c_i, c_p]
@@ -1190,6 +1202,78 @@ def ctc_star_loss_bwd(logits, ld, frame_lens, labels, label_offsets, max_label_l
     check(load().asr_ctc_star_loss_bwd(*args, ptr(grad_nll), *_star_ws(ws, ws_bytes), ptr(dlogits), int(lddz), stream()),
           "asr_ctc_star_loss_bwd")
     LAUNCHES["ctc_star_loss_bwd"] += 1
+    return dlogits
+
+
+GTC_MAX_NODES = 2047          # ASR_GTC_MAX_NODES: the CTC chains' 2 * 1023 + 1 states
+GTC_MAX_ARCS = 65536          # ASR_GTC_MAX_ARCS, per graph
+
+_GTC_DTYPES = dict(node_off=torch.int32, lab=torch.int32, start=torch.float32, fin=torch.float32, in_ptr=torch.int32,
+                   in_src=torch.int32, in_w=torch.float32, out_ptr=torch.int32, out_dst=torch.int32, out_w=torch.float32,
+                   order=torch.int32, head=torch.int32)
+
+
+def gtc_ws_bytes(B, T, V, max_nodes):
+    """asr_gtc_ws_bytes on plain integers (no tensors, no GPU) -> the workspace bytes of a graph CTC call; UnsupportedShape
+    for sizes the kernels refuse (more than GTC_MAX_NODES nodes, V < 2)."""
+    need = c_i64(0)
+    rc = load().asr_gtc_ws_bytes(int(B), int(T), int(V), int(max_nodes), ctypes.byref(need))
+    if rc == -2:
+        raise UnsupportedShape("gtc_loss: B %d, T %d, V %d, %d nodes (at most %d nodes, V >= 2)"
+                               % (B, T, V, max_nodes, GTC_MAX_NODES))
+    check(rc, "asr_gtc_ws_bytes")
+    return need.value
+
+
+def _gtc_table(table, rows, graph_of=None):
+    """The device form of a graph table (gtc.GraphTable after .to(device)) -> (asr_gtc_graphs_t, graph_of int32 [rows] on
+    the device: the caller's, or the table's own); the tensors stay the table's."""
+    t = GtcGraphs()
+    shapes = dict(node_off=table.G + 1, lab=table.NN, start=table.NN, fin=table.NN, in_ptr=table.NN + 1,
+                  in_src=max(table.A, 1), in_w=max(table.A, 1), out_ptr=table.NN + 1, out_dst=max(table.A, 1),
+                  out_w=max(table.A, 1), order=table.NN, head=table.G * table.V)
+    for name, dtype in _GTC_DTYPES.items():
+        a = getattr(table, name)
+        if not (isinstance(a, torch.Tensor) and a.is_cuda):
+            raise RuntimeError("gtc_loss: the graph tables are not on the device (Graph.to(device))")
+        if a.dtype != dtype or not a.is_contiguous() or a.numel() != shapes[name]:
+            raise RuntimeError("gtc_loss: the table's %s must be a contiguous %s tensor of %d elements" % (name, dtype, shapes[name]))
+        setattr(t, name, ptr(a))
+    t.V, t.G, t.max_nodes, t.max_arcs = table.V, table.G, table.max_nodes, table.max_arcs
+    if graph_of is None:
+        graph_of = table.rows(rows)
+    if not (graph_of.is_cuda and graph_of.dtype == torch.int32 and graph_of.is_contiguous() and graph_of.numel() == rows):
+        raise RuntimeError("gtc_loss: graph_of must be a contiguous int32 tensor of %d rows on the device" % rows)
+    return t, graph_of
+
+
+def gtc_loss_fwd(logits, ld, frame_lens, table, zero_infinity, nll, ws, ws_bytes=None, graph_of=None):
+    """asr_gtc_loss_fwd (csrc/gtc.hip): ctc_loss_fwd's arguments with a graph table on the device
+    (gtc.GraphTable after .to(device); its own graph_of, or the caller's int32 [B]) in place of the labels.  nll [B] and the
+    workspace ws (at least gtc_ws_bytes bytes, 4-byte aligned; ws_bytes: what the library is told it holds, the tensor's
+    size by default) are the caller's.  The workspace goes to gtc_loss_bwd unchanged.  UnsupportedShape for a graph above
+    GTC_MAX_NODES nodes or GTC_MAX_ARCS arcs."""
+    B, T, V = logits.shape
+    t, graph_of = _gtc_table(table, B, graph_of)
+    rc = load().asr_gtc_loss_fwd(B, T, V, ptr(logits), int(ld), ptr(frame_lens), ctypes.byref(t), ptr(graph_of),
+                                 int(bool(zero_infinity)), ptr(nll), *_star_ws(ws, ws_bytes), stream())
+    if rc == -2:
+        raise UnsupportedShape("gtc_loss: B %d, T %d, V %d, graphs of up to %d nodes and %d arcs (at most %d and %d, V >= 2)"
+                               % (B, T, V, table.max_nodes, table.max_arcs, GTC_MAX_NODES, GTC_MAX_ARCS))
+    check(rc, "asr_gtc_loss_fwd")
+    LAUNCHES["gtc_loss"] += 1
+    return nll
+
+
+def gtc_loss_bwd(logits, ld, frame_lens, table, zero_infinity, grad_nll, ws, dlogits, lddz, ws_bytes=None, graph_of=None):
+    """asr_gtc_loss_bwd behind a gtc_loss_fwd with the same arguments and workspace: dlogits [B, T, >= V] with row stride
+    lddz gets grad_nll[b] d nll_b / d logits, exact zeros behind each utterance and for a row without a path."""
+    B, T, V = logits.shape
+    t, graph_of = _gtc_table(table, B, graph_of)
+    check(load().asr_gtc_loss_bwd(B, T, V, ptr(logits), int(ld), ptr(frame_lens), ctypes.byref(t), ptr(graph_of),
+                                  int(bool(zero_infinity)), ptr(grad_nll), *_star_ws(ws, ws_bytes), ptr(dlogits), int(lddz),
+                                  stream()), "asr_gtc_loss_bwd")
+    LAUNCHES["gtc_loss_bwd"] += 1
     return dlogits
 
 

@@ -1,5 +1,6 @@
 """Same CLI as the reference main.py:6-41 (flags -config/-c, --sup_pretrain, --judge_pretrain, --ssl_train,
---load_model, --load_judge, --test, and --mwer_train: minimum error rate fine-tuning, not a reference flag); yaml.safe_load because bare yaml.load() raises on PyYAML 6.
+--load_model, --load_judge, --test, and - not reference flags - --mwer_train: minimum error rate fine-tuning, --pseudo_train:
+n-best pseudo-label training on the unlabeled speech with the graph CTC loss); yaml.safe_load because bare yaml.load() raises on PyYAML 6.
 Launch under torch.distributed.run for data parallelism (one process per GPU)."""
 from argparse import ArgumentParser
 
@@ -11,7 +12,7 @@ if __name__ == "__main__":
     parser = ArgumentParser()
     parser.add_argument("-config", "-c", default="config.yaml")
     for flag in ("--sup_pretrain", "--judge_pretrain", "--ssl_train", "--load_model", "--load_judge", "--test",
-                 "--mwer_train"):
+                 "--mwer_train", "--pseudo_train"):
         parser.add_argument(flag, action="store_true")
     args = parser.parse_args()
     with open(args.config, "r") as f:
@@ -27,5 +28,7 @@ if __name__ == "__main__":
         solver.ssl_train()
     if args.mwer_train:
         solver.mwer_train()
+    if args.pseudo_train:
+        solver.pseudo_train()
     if args.test:
         solver.test()

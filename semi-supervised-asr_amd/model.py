@@ -935,6 +935,18 @@ class E2E(torch.nn.Module):
             return ops.ctc_star_loss(logits, self.encoder.enc2.last_lens_dev, labels, ylens, self.ctc_star_penalty, True)
         return ops.ctc_loss(logits, self.encoder.enc2.last_lens_dev, labels, ylens, True)
 
+    def gtc_nll(self, enc_h, graphs):
+        """Per-utterance graph CTC negative log path sum [B] (not a reference method) of the label graphs
+        `graphs` - one gtc.Graph for every row or a gtc.GraphBatch naming a graph per row - given the encoder output enc_h
+        [B, T', H] of the forward that has just run: ctc_lo over the B T' rows on the GEMM, then ops.gtc_loss on the raw
+        logits.  A row whose graph has no path of its frame count counts as 0 (zero_infinity), like ctc_nll.  The value is a
+        path sum, not a normalised probability; no gradient flows to the graph's weights."""
+        if not hasattr(self, "ctc_lo"):
+            raise ValueError("gtc_nll needs the CTC head: build the model with ctc_weight > 0")
+        bsz, frames, hid = enc_h.shape
+        logits = ops.linear(enc_h.reshape(bsz * frames, hid), self.ctc_lo.weight, self.ctc_lo.bias).view(bsz, frames, -1)
+        return ops.gtc_loss(logits, self.encoder.enc2.last_lens_dev, graphs, True)
+
     def recognize_beams(self, data, ilens, max_dec_timesteps, topk, length_penalty=0.0, nbest=False, *, lm=None,
                         lm_weight=0.0, ctc_decode_weight=0.0, ngram=None, ngram_weight=0.0, ngram_bonus=0.0, word_lm=None,
                         word_lm_weight=0.0, word_bonus=0.0, lexicon_only=False):

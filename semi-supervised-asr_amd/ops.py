@@ -1072,6 +1072,67 @@ def ctc_star_loss(logits, frame_lens_dev, labels_packed, label_lens, penalty, ze
     return _CtcStarLoss.apply(logits, frame_lens_dev, labels_packed, label_lens, pen, zero_infinity)
 
 
+class _GtcLoss(torch.autograd.Function):
+    """Graph CTC negative log path sum per utterance of RAW logits [B, T', V] -> nll [B]: asr_gtc_loss_fwd / _bwd
+    (csrc/gtc.hip), two launches forward and two backward.  _CtcStarLoss with a graph table in place of the
+    labels: the same pooled workspace lease from the forward to the end of the backward, ordered sums only, no host
+    synchronisation."""
+
+    @staticmethod
+    def forward(ctx, logits, frame_lens, table, zero_infinity):
+        B, T, V = logits.shape
+        if not (logits.stride(2) == 1 and logits.stride(1) >= V and logits.stride(0) == T * logits.stride(1)):
+            logits = logits.contiguous()
+        ld = logits.stride(1)
+        dev = logits.device
+        words = (hb.gtc_ws_bytes(B, T, V, table.max_nodes) + 3) // 4
+        if ctx.needs_input_grad[0]:
+            cap = _row_capacity(words)
+            ctx.lease = _POOL.acquire(("gtc", str(dev), cap), lambda: torch.empty(cap, device=dev, dtype=torch.float32))
+            ws = ctx.lease.ws
+        else:
+            ctx.lease, ws = None, torch.empty(words, device=dev, dtype=torch.float32)
+        nll = torch.empty(B, device=dev, dtype=torch.float32)
+        hb.gtc_loss_fwd(logits, ld, frame_lens, table, zero_infinity, nll, ws)
+        ctx.save_for_backward(logits, frame_lens)
+        ctx.table, ctx.ld, ctx.zero_infinity = table, ld, bool(zero_infinity)
+        return nll
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, frame_lens = ctx.saved_tensors
+        if ctx.lease is None or ctx.lease.ws is None:
+            raise RuntimeError("gtc_loss: the backward runs once, behind a forward that ran with autograd enabled")
+        B, T, V = logits.shape
+        dz = torch.empty(B, T, V, device=logits.device, dtype=torch.float32)
+        hb.gtc_loss_bwd(logits, ctx.ld, frame_lens, ctx.table, ctx.zero_infinity, g.contiguous(), ctx.lease.ws, dz, V)
+        ctx.lease.release()
+        return dz, None, None, None
+
+
+def gtc_loss(logits, frame_lens_dev, graphs, zero_infinity=True):
+    """-> nll [B]: the graph CTC loss of each utterance (GTC, Moritz et al. 2021) - the supervision of a row is
+    a label graph (gtc.py): the plain CTC lattice (gtc.Graph.ctc), an n-best list with a weight per hypothesis
+    (Graph.from_nbest), a confusion network (Graph.from_confusion) or any Graph.  `graphs` is one gtc.Graph for every row or a
+    gtc.GraphBatch that names a graph per row; it is compiled and uploaded once per object and device.  The other arguments
+    are ctc_loss's: raw logits [B, T', V] (a strided view with a row stride >= V is taken as it is), the frame lengths on the
+    device.
+    The value is the negative log PATH SUM of the graph, start + emissions + arc weights + final weight summed over all node
+    paths of the row's frame count - not a normalised probability: the weights are any log numbers, and two paths may spell
+    the same tokens.  A row with no path of finite score, or without frames, counts as 0 with zero_infinity and as +inf
+    without; its gradient is zero either way.  No gradient flows to the arc, start or final weights.  UnsupportedShape for a
+    graph above hb.GTC_MAX_NODES nodes, ValueError where the graphs do not fit the batch."""
+    import gtc
+    if not isinstance(graphs, (gtc.Graph, gtc.GraphBatch)):
+        raise ValueError("gtc_loss: graphs must be a gtc.Graph or a gtc.GraphBatch, got %r" % type(graphs).__name__)
+    B, _, V = logits.shape
+    if graphs.V != V:
+        raise ValueError("gtc_loss: the graphs are over %d tokens, the logits over %d" % (graphs.V, V))
+    if isinstance(graphs, gtc.GraphBatch) and graphs.graph_of.size != B:
+        raise ValueError("gtc_loss: the batch lists a graph for %d utterances, the call has %d" % (graphs.graph_of.size, B))
+    return _GtcLoss.apply(logits, frame_lens_dev, graphs.to(logits.device), zero_infinity)
+
+
 def _label_offsets(what, label_lens, B, n_labels=None):
     """Host label counts -> (counts, offsets [B + 1], the largest count); ValueError where they do not fit the batch."""
     lens = [int(n) for n in label_lens]

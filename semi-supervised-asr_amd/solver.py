@@ -102,7 +102,9 @@ class Solver(object):
         self.proportion = self.calculate_length_proportion()
         self.build_model(load_model=load_model)
         self.model.space_id = self.mwer_space      # E2E.mwer_forward(unit="word") splits the hypotheses at this id
-        self.settle_host_memory()          # the corpora stay for good: keep the garbage collector from walking them mid-epoch
+        # the pseudo-labelling keys are refused here where they cannot hold; absent, nothing differs
+        self.pseudo_config(config, self.world, hasattr(self.model, "ctc_lo"))
+        self.settle_host_memory()         # the corpora stay for good: keep the garbage collector from walking them mid-epoch
 
     # ------------------------------------------------------------------ checkpoints (.ckpt/.opt/.judge.*)
     def save_model(self, model_path):
@@ -1367,6 +1369,158 @@ class Solver(object):
                 best_model = self.model.state_dict()
                 print(f"Save #{epoch} model, val_loss={val_loss:.3f}, CER={cer:.3f}")
             self.save_model(f"{path}-mwer-{epoch:03d}")
+        return best_model, best_cer
+
+    # ------------------------------------------------------------------ n-best pseudo-labelling with the graph CTC loss
+    PSEUDO_KEYS = ("pseudo_beam", "pseudo_temperature", "pseudo_weight", "pseudo_epochs")
+
+    @staticmethod
+    def pseudo_config(config, world=1, has_ctc_head=True):
+        """The pseudo-labelling keys (not reference keys; all absent by default = off) -> None when `pseudo_beam`
+        is absent, else (K, temperature, weight, epochs, ngram): `pseudo_beam` K in 2..16 hypotheses of the CTC prefix beam
+        search per unlabeled utterance, weighed by the softmax of `pseudo_temperature` (default 1) times their scores;
+        `pseudo_weight` (default 1) times the mean graph CTC loss is the step's loss; `pseudo_epochs` (default 1) passes of
+        Solver.pseudo_train over the unlabeled speech.  `ngram_lm` (with `ngram_weight`, `ngram_bonus`) sits inside the search
+        when it is configured: ngram is (path, weight, bonus) or None.  ValueError: a beam outside 2..16, a temperature or
+        weight that is negative or not finite, no epochs, another pseudo key or an n-gram weight without what it belongs to,
+        `word_lm` (the search of the pseudo-labels has no place for it), a model without the CTC head, more than one
+        process."""
+        if config.get("pseudo_beam") is None:
+            for key in Solver.PSEUDO_KEYS[1:]:
+                if config.get(key) is not None:
+                    raise ValueError("%s is set without pseudo_beam, the width of the n-best search it belongs to" % key)
+            return None
+        K = int(config["pseudo_beam"])
+        if not 2 <= K <= hb.BEAM_KMAX:
+            raise ValueError("pseudo_beam %d outside 2..%d" % (K, hb.BEAM_KMAX))
+        temp = config.get("pseudo_temperature")
+        weight = config.get("pseudo_weight")
+        epochs = config.get("pseudo_epochs")
+        temp, weight, epochs = (1.0 if temp is None else float(temp), 1.0 if weight is None else float(weight),
+                                1 if epochs is None else int(epochs))
+        if not (0 <= temp < float("inf")) or not (0 <= weight < float("inf")) or epochs < 1:
+            raise ValueError("pseudo_temperature %g and pseudo_weight %g must be finite and >= 0, pseudo_epochs %d >= 1"
+                             % (temp, weight, epochs))
+        ngram = None
+        if config.get("ngram_lm") is None:
+            for key in ("ngram_weight", "ngram_bonus"):
+                if key in config:
+                    raise ValueError("%s is set without ngram_lm, the ARPA file it weighs" % key)
+        else:
+            ngram = (config["ngram_lm"], float(config.get("ngram_weight", 0.0) or 0.0), float(config.get("ngram_bonus", 0.0) or 0.0))
+        if config.get("word_lm") is not None:
+            raise ValueError("pseudo_beam searches with the CTC head and, at most, ngram_lm: word_lm has no place in it")
+        if not has_ctc_head:
+            raise ValueError("pseudo_beam needs the CTC head: build the model with ctc_weight > 0")
+        if int(world) > 1:
+            raise ValueError("pseudo-label training runs in one process: data-parallel pseudo-labelling (world size %d) is "
+                             "not supported" % world)
+        return K, temp, weight, epochs, ngram
+
+    def _pseudo_ngram(self, spec):
+        """The NgramLM of the pseudo-label search as _ctc_beams takes it, loaded once."""
+        if spec is None:
+            return None
+        if getattr(self, "_pseudo_lm", None) is None or self._pseudo_lm[0] != spec[0]:
+            from ngram import NgramLM
+            lm = NgramLM.from_arpa(spec[0], {s: i for s, i in self.vocab.items() if s not in ("<s>", "</s>")},
+                                   self.vocab["<BOS>"], self.vocab["<EOS>"], V=len(self.vocab))
+            self._pseudo_lm = (spec[0], lm)
+        return self._pseudo_lm[1], spec[1], spec[2]
+
+    def pseudo_graphs(self, xs, ilens, K, temperature, ngram=None):
+        """The n-best pseudo-labels of one unlabeled batch as label graphs: under no_grad and in eval mode the CTC prefix beam
+        search (E2E.recognize_ctc_beams, nbest) with beam width K - its ONE device-to-host read of (hyp, hyp_len, score) is the
+        only one of the step -, gtc.nbest_weights over every row's list, gtc.Graph.from_nbest per row.  -> (gtc.GraphBatch,
+        the id lists, the log weights) ; the model is left in the mode it came in."""
+        import gtc
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                ids, scores = self.model.recognize_ctc_beams(xs, ilens, K, nbest=True, **self._lm_kwargs(ngram))
+        finally:
+            self.model.train(was_training)
+        B = len(ids)
+        score = np.full((B, K), -np.inf)
+        hyp_len = np.full((B, K), -1, dtype=np.int64)
+        for b in range(B):
+            n = len(ids[b])
+            score[b, :n] = scores[b]
+            hyp_len[b, :n] = [len(h) for h in ids[b]]
+        logw = gtc.nbest_weights(score, hyp_len, temperature)
+        V = self.model.ctc_lo.out_features
+        graphs = []
+        for b in range(B):
+            live = [k for k in range(len(ids[b])) if logw[b, k] > -np.inf]
+            if live:
+                graphs.append(gtc.Graph.from_nbest([ids[b][k] for k in live], [logw[b, k] for k in live], V))
+            else:                                       # (a search that kept nothing: the empty hypothesis)
+                graphs.append(gtc.Graph.from_nbest([[]], [0.0], V))
+        return gtc.GraphBatch(graphs, range(B)), ids, logw
+
+    def pseudo_train_one_iteration(self, unlab_xs, unlab_ilens, lab=None, tf_rate=1.0):
+        """One pseudo-label step on an unlabeled batch already on the device: the n-best search and its graphs
+        (pseudo_graphs), then the encoder in training mode, loss = pseudo_weight * mean E2E.gtc_nll - plus, with lab =
+        (xs, ilens, ys), the supervised loss of that labeled batch - through the step every other loop takes (_step).
+        -> (loss, mean graph CTC loss) as StepScalars; self.last_pseudo keeps the graphs, id lists and log weights of the
+        call.  The host read of the n-best list is deliberate: the graph is compiled on the host."""
+        ps = self.pseudo_config(self.config, self.world, hasattr(self.model, "ctc_lo"))
+        if ps is None:
+            raise ValueError("pseudo_train_one_iteration needs `pseudo_beam` in the configuration")
+        K, temperature, weight, _, ngram_spec = ps
+        xs, ilens, _, _ = parallel.shard_batch(unlab_xs, unlab_ilens, None, 0, 1)    # (a one-process LocalShard passes through)
+        batch, ids, logw = self.pseudo_graphs(xs, ilens, K, temperature, self._pseudo_ngram(ngram_spec))
+        self.last_pseudo = dict(graphs=batch, ids=ids, log_weights=logw)
+
+        def make_local():
+            enc_h, _ = self.model.encoder(xs, ilens)
+            gtc_mean = self.model.gtc_nll(enc_h, batch).sum() * (1.0 / len(ilens))
+            loss = weight * gtc_mean
+            if lab is not None:
+                loss = loss + self._sharded_forward(lab[0], lab[1], lab[2], tf_rate)
+            return loss, [loss, gtc_mean]
+        loss, gtc_mean = self._step(make_local, self.gen_opt, 2)
+        return loss, gtc_mean
+
+    def pseudo_train(self):
+        """`pseudo_epochs` passes of pseudo-label steps over the unlabeled speech (main.py --pseudo_train), the dev CER after
+        each as sup_pretrain reports it; checkpoints by sup_pretrain's rule (the best CER under model_name, every epoch under
+        model_name-pseudo-NNN)."""
+        cfg = self.config
+        ps = self.pseudo_config(cfg, self.world, hasattr(self.model, "ctc_lo"))
+        if ps is None:
+            raise ValueError("pseudo_train needs `pseudo_beam` in the configuration")
+        K, temperature, weight, epochs, _ = ps
+        self.model.train()
+        best_cer, best_model = 200, None
+        path = os.path.join(cfg["model_dir"], cfg["model_name"])
+        steps_per_epoch = len(self.train_unlab_x_loader)
+        print("------pseudo-label training (%d-best, temperature %g, weight %g)-------" % (K, temperature, weight))
+        for epoch in range(epochs):
+            running = [0.0]
+
+            def log(item):
+                it, (loss, gtc_mean) = item
+                running[0] += float(loss)
+                if self.rank == 0:
+                    print(f"epoch: {epoch}, [{it + 1}/{steps_per_epoch}], loss: {loss:.3f}, gtc: {gtc_mean:.3f}", end="\r")
+                self.logger.scalar_summary(tag=f"{cfg['tag']}/pseudo/train_loss", value=float(loss),
+                                           step=epoch * steps_per_epoch + it + 1)
+            push, done = self._lagged(log)
+            for it, (xs, ilens) in enumerate(self._feed(self.train_unlab_x_loader, kind="speech", train=True)):
+                push((it, self.pseudo_train_one_iteration(xs, ilens)))
+            done()
+            val_loss, cer, hyps, refs = self.validation()
+            print(f"Epoch: {epoch}, train_loss={running[0] / steps_per_epoch:.4f}, valid_loss={val_loss:.4f}, CER={cer:.4f}")
+            self.logger.scalar_summary(f"{cfg['tag']}/pseudo/cer", cer, epoch)
+            self.logger.scalar_summary(f"{cfg['tag']}/pseudo/val_loss", val_loss, epoch)
+            if cer < best_cer:
+                best_cer = cer
+                self.save_model(path)
+                best_model = self.model.state_dict()
+                print(f"Save #{epoch} model, val_loss={val_loss:.3f}, CER={cer:.3f}")
+            self.save_model(f"{path}-pseudo-{epoch:03d}")
         return best_model, best_cer
 
     # ------------------------------------------------------------------ semi-supervised training
