@@ -1032,6 +1032,50 @@ int asr_gtc_loss_bwd(int B, int T, int V, const float* logits, int64_t ld, const
                      void* ws, int64_t ws_bytes, float* dlogits, int64_t lddz, asr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Graph CTC, the n-best graph builder: the list asr_ctc_beam_f32 leaves on the device compiled into an asr_gtc_graphs_t
+ * table on the device, one prefix-tree graph per row (csrc/gtc_nbest.hip).  Two entries added to ABI version 8
+ * WITHOUT a version change: additive - no existing entry, constant or kernel changes.
+ * Inputs: hyp int32 [B][K][L] (padded with -1), hyp_len int32 [B][K] (-1: a dead slot), score fp32 [B][K] (-inf: a dead
+ * slot), temperature (finite, >= 0), V.  1 <= K <= ASR_BEAM_KMAX, L >= 1, 2 <= V <= 2^20; otherwise ASR_E_SHAPE, as when
+ * B times a capacity would pass INT_MAX / 2.  Trust: the tokens of live hypotheses lie in 1 .. V-1 (they come from the
+ * search); like the contents of the other tables they are not checked on the device.  A token outside is copied into lab
+ * as it stands; no index of the builder itself is formed from a token.
+ * Output: the complete table, G = B graphs, graph_of[b] = b.  For every row it is, element for element, what
+ * gtc.Graph.from_nbest and gtc._concat (gtc.py) make of the same list:
+ *   weights     a slot is live iff hyp_len >= 0 and score > -inf.  log w_k = the log-softmax of temperature * score over the
+ *               row's admitted live slots (below), in float64; log_weights fp64 [B][K] holds it, -inf in every other slot.
+ *   duplicates  equal hypotheses join their weights by logaddexp in float64, in ascending slot order.
+ *   no slot     a row without an admitted slot gets the graph of the empty hypothesis at weight 0.
+ *   numbering   node 0 is the root's blank; trie node u (breadth first, children in token order, u = 1, 2, ..) gives the
+ *               token node 2u - 1 and the blank node 2u.
+ *   arcs        l_u -> l_u, l_u -> b_u, b_u -> b_u, b_u -> l_c for each child c of u, and l_u -> l_c where the tokens differ,
+ *               all at weight 0; out lists by (source, destination), in lists by (destination, source).  Start weight 0 on
+ *               the root's blank and the root's children, -inf elsewhere; final weight = the joined weight of the
+ *               hypotheses that end in u on l_u and b_u, -inf elsewhere (rounded to fp32 once).
+ *   order, head as in the table's definition above.   node_off, in_ptr, out_ptr: running offsets over the rows.
+ * The node limit.  Hypotheses are admitted in slot order while the tree stays within (ASR_GTC_MAX_NODES - 1) / 2 = 1023 trie
+ * nodes beyond the root: hypothesis k adds len_k - max over the admitted j < k of lcp(j, k) nodes.  The first live
+ * hypothesis that does not fit and every live slot behind it are dropped; the weights are the log-softmax over the admitted
+ * slots only; dropped int32 [B] counts the live slots a row lost.
+ * Capacity.  Nothing is read back, so the caller sizes the arrays by bounds (asr_nbest_gtc_bytes): cap_nodes =
+ * min(2 K L + 1, ASR_GTC_MAX_NODES) per row, cap_arcs = 3 cap_nodes; lab, start, fin, order [B cap_nodes]; in_ptr, out_ptr
+ * [B cap_nodes + 1]; the arc arrays [B cap_arcs]; node_off [B + 1]; head [B][V].  The table's max_nodes and max_arcs are these
+ * bounds (ASR_E_ARG otherwise): the loss kernels dispatch by them and guard every row's own N, which moves thread ownership
+ * only, never the order of a sum.  Everything behind the counts actually written is undefined.
+ *   asr_nbest_gtc_bytes  plain integers, no GPU: the two capacities and the workspace (8 B bytes: a node and an arc count
+ *                        per row), 4-byte aligned.
+ *   asr_nbest_gtc_f32    two launches, one workgroup per row each: the counts; then every array of the row, the workgroup
+ *                        summing the counts of the rows in front itself.  The pointers of `table` name the caller's arrays,
+ *                        which the call WRITES.  Integer work and float64 weights: bit-reproducible, a row's graph (its
+ *                        nodes and arcs numbered inside the graph, lab, start, fin, order, its head row) a function of that
+ *                        row alone.  No host synchronisation, no allocation.
+ * ------------------------------------------------------------------------------------- */
+int asr_nbest_gtc_bytes(int B, int K, int L, int V, int32_t* cap_nodes, int32_t* cap_arcs, int64_t* ws_bytes);
+int asr_nbest_gtc_f32(int B, int K, int L, int V, const int32_t* hyp, const int32_t* hyp_len, const float* score,
+                      double temperature, const asr_gtc_graphs_t* table, int32_t* graph_of, double* log_weights,
+                      int32_t* dropped, void* ws, int64_t ws_bytes, asr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Joint CTC-attention decoding: the CTC prefix score inside the beam search (csrc/ctc_prefix.hip, the CTC variants of the
  * select kernel in csrc/beam.hip).  Four entries added to ABI version 8 WITHOUT a version change, like the CTC
  * loss entries: additive - no existing entry, structure or constant changes, and asr_beam_select_f32 /

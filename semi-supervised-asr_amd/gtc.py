@@ -9,6 +9,8 @@ called).
   g.compile() -> GraphTable                    the device form; g.to(device) uploads it once per device
   GraphBatch(graphs, graph_of)                 several graphs in one table, graph_of[b] in 0 .. G-1 per utterance
   nbest_weights(score, hyp_len, temperature)   the log weights of a ranked list from the scores of the search
+  DeviceGraphTable                             the table ops.gtc_nbest_graphs builds on the device: sized by
+                                               bounds, never read back
 
 The definition (include/asr_hip.h, "Graph CTC").  Node n carries a token lab[n] in [0, V) (0 = blank), a start weight and a
 final weight (finite or -inf); an arc (m -> n, w) a finite weight.  Self-loops are ordinary arcs and are never implied; there
@@ -82,6 +84,38 @@ class GraphTable(object):
         if B not in self._rows:
             self._rows[B] = torch.zeros(int(B), dtype=torch.int32, device=self.lab.device)
         return self._rows[B]
+
+
+class DeviceGraphTable(GraphTable):
+    """A table the device built (ops.gtc_nbest_graphs, csrc/gtc_nbest.hip): one graph per row, graph_of the
+    identity.  The tensors are sized by bounds - cap_nodes nodes and cap_arcs arcs per row - and only the device knows how
+    much of them is written: NN and A here are those CAPACITIES (B cap_nodes, B cap_arcs), max_nodes and max_arcs the per-row
+    bounds the loss kernels dispatch by, and nothing in this class or behind it reads a device value.  Everything behind
+    node_off[B] nodes and in_ptr[node_off[B]] arcs is undefined.  dropped int32 [B] (live slots lost to the node limit) and
+    log_weights float64 [B, K] (-inf in dead and dropped slots) stay on the device."""
+
+    def __init__(self, V, B, cap_nodes, cap_arcs, device):
+        import torch
+        self.V, self.G, self.max_nodes, self.max_arcs = int(V), int(B), int(cap_nodes), int(cap_arcs)
+        self.cap_nodes, self.cap_arcs = self.max_nodes, self.max_arcs
+        self.NN, self.A = self.G * self.cap_nodes, self.G * self.cap_arcs
+        i32, f32 = torch.int32, torch.float32
+        sizes = dict(node_off=(self.G + 1, i32), lab=(self.NN, i32), start=(self.NN, f32), fin=(self.NN, f32),
+                     in_ptr=(self.NN + 1, i32), in_src=(self.A, i32), in_w=(self.A, f32), out_ptr=(self.NN + 1, i32),
+                     out_dst=(self.A, i32), out_w=(self.A, f32), order=(self.NN, i32), head=(self.G * self.V, i32))
+        for name in self.FIELDS:
+            setattr(self, name, torch.empty(sizes[name][0], device=device, dtype=sizes[name][1]))
+        self.head = self.head.view(self.G, self.V)
+        self.graph_of = torch.empty(self.G, device=device, dtype=i32)
+        self.dropped = self.log_weights = None
+        self._rows = {}
+
+    def to(self, device):
+        import torch
+        want = torch.device(device)
+        if want.type != self.lab.device.type or (want.index is not None and want.index != self.lab.device.index):
+            raise ValueError("gtc: a table built on %s cannot serve %s" % (self.lab.device, device))
+        return self
 
 
 class Graph(object):

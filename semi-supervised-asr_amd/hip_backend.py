@@ -31,6 +31,7 @@ EXPORTS = (
     "asr_ctc_ws_bytes", "asr_ctc_loss_fwd", "asr_ctc_loss_bwd",
     "asr_ctc_star_ws_bytes", "asr_ctc_star_loss_fwd", "asr_ctc_star_loss_bwd",
     "asr_gtc_ws_bytes", "asr_gtc_loss_fwd", "asr_gtc_loss_bwd",
+    "asr_nbest_gtc_bytes", "asr_nbest_gtc_f32",
     "asr_ctc_prefix_init_f32", "asr_ctc_prefix_score_f32", "asr_beam_select_ctc_f32", "asr_ctc_prefix_advance_f32",
     "asr_ctc_align_ws_bytes", "asr_ctc_align_f32", "asr_ctc_greedy_f32",
     "asr_ctc_segment_ws_bytes", "asr_ctc_segment_f32",
@@ -328,6 +329,10 @@ def load():
     lib.asr_gtc_loss_fwd.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, ctypes.POINTER(GtcGraphs), c_p, c_i, c_p, c_p, c_i64, c_p]
     lib.asr_gtc_loss_bwd.argtypes = [c_i, c_i, c_i, c_p, c_i64, c_p, ctypes.POINTER(GtcGraphs), c_p, c_i, c_p, c_p, c_i64, c_p,
                                      c_i64, c_p]
+    lib.asr_nbest_gtc_bytes.argtypes = [c_i, c_i, c_i, c_i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                        ctypes.POINTER(c_i64)]
+    lib.asr_nbest_gtc_f32.argtypes = [c_i, c_i, c_i, c_i, c_p, c_p, c_p, ctypes.c_double, ctypes.POINTER(GtcGraphs), c_p, c_p,
+                                      c_p, c_p, c_i64, c_p]
     lib.asr_ctc_prefix_init_f32.argtypes = [ctypes.POINTER(CtcPrefix), ctypes.POINTER(ctypes.c_int32), c_p]
     lib.asr_ctc_prefix_score_f32.argtypes = [ctypes.POINTER(CtcPrefix), ctypes.POINTER(Beam), c_i, c_p]
     lib.asr_beam_select_ctc_f32.argtypes = [ctypes.POINTER(Beam), c_p, c_f, c_p, c_p, c_f, c_i, c_p]
@@ -1227,7 +1232,9 @@ def gtc_ws_bytes(B, T, V, max_nodes):
 
 def _gtc_table(table, rows, graph_of=None):
     """The device form of a graph table (gtc.GraphTable after .to(device)) -> (asr_gtc_graphs_t, graph_of int32 [rows] on
-    the device: the caller's, or the table's own); the tensors stay the table's."""
+    the device: the caller's, or the table's own); the tensors stay the table's.  A table built on the device
+    (gtc.DeviceGraphTable) passes the same checks from host-known numbers alone: its NN and A are the capacities its arrays
+    were sized by, not counts read back."""
     t = GtcGraphs()
     shapes = dict(node_off=table.G + 1, lab=table.NN, start=table.NN, fin=table.NN, in_ptr=table.NN + 1,
                   in_src=max(table.A, 1), in_w=max(table.A, 1), out_ptr=table.NN + 1, out_dst=max(table.A, 1),
@@ -1275,6 +1282,39 @@ def gtc_loss_bwd(logits, ld, frame_lens, table, zero_infinity, grad_nll, ws, dlo
                                   stream()), "asr_gtc_loss_bwd")
     LAUNCHES["gtc_loss_bwd"] += 1
     return dlogits
+
+
+def gtc_nbest_bytes(B, K, L, V):
+    """asr_nbest_gtc_bytes on plain integers (no tensors, no GPU) -> (cap_nodes, cap_arcs, workspace bytes) of an n-best graph
+    build: the per-row capacities its table is sized by; UnsupportedShape for K outside 1 .. BEAM_KMAX, V outside 2 .. 2**20
+    or a batch whose arrays would pass the int32 offsets."""
+    cn, ca, need = ctypes.c_int32(0), ctypes.c_int32(0), c_i64(0)
+    rc = load().asr_nbest_gtc_bytes(int(B), int(K), int(L), int(V), ctypes.byref(cn), ctypes.byref(ca), ctypes.byref(need))
+    if rc == -2:
+        raise UnsupportedShape("gtc_nbest_graphs: B %d, K %d, L %d, V %d (K in 1..%d, V in 2..2**20)" % (B, K, L, V, BEAM_KMAX))
+    check(rc, "asr_nbest_gtc_bytes")
+    return cn.value, ca.value, need.value
+
+
+def gtc_nbest(hyp, hyp_len, score, temperature, table, log_weights, dropped, ws):
+    """asr_nbest_gtc_f32 (csrc/gtc_nbest.hip): the n-best list of ctc_beam - hyp int32 [B, K, L], hyp_len int32
+    [B, K], score fp32 [B, K] on the device - compiled into `table`, a gtc.DeviceGraphTable whose capacity-sized arrays (and
+    graph_of) the call writes; log_weights fp64 [B, K], dropped int32 [B] and the workspace (gtc_nbest_bytes) are the
+    caller's.  Two launches, no host synchronisation."""
+    B, K, L = hyp.shape
+    for name, a, dtype, n in (("hyp", hyp, torch.int32, B * K * L), ("hyp_len", hyp_len, torch.int32, B * K),
+                              ("score", score, torch.float32, B * K), ("log_weights", log_weights, torch.float64, B * K),
+                              ("dropped", dropped, torch.int32, B)):
+        if not (a.is_cuda and a.dtype == dtype and a.is_contiguous() and a.numel() == n):
+            raise RuntimeError("gtc_nbest_graphs: %s must be a contiguous %s tensor of %d elements on the device" % (name, dtype, n))
+    t, graph_of = _gtc_table(table, B)
+    rc = load().asr_nbest_gtc_f32(B, K, L, table.V, ptr(hyp), ptr(hyp_len), ptr(score), float(temperature), ctypes.byref(t),
+                                  ptr(graph_of), c_p(log_weights.data_ptr()), ptr(dropped), *_star_ws(ws, None), stream())
+    if rc == -2:
+        raise UnsupportedShape("gtc_nbest_graphs: B %d, K %d, L %d, V %d (K in 1..%d, V in 2..2**20)" % (B, K, L, table.V, BEAM_KMAX))
+    check(rc, "asr_nbest_gtc_f32")
+    LAUNCHES["gtc_nbest"] += 1
+    return table
 
 
 RNNT_MAX_LABELS = 1023       # ASR_RNNT_MAX_LABELS

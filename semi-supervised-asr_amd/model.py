@@ -940,7 +940,8 @@ class E2E(torch.nn.Module):
         `graphs` - one gtc.Graph for every row or a gtc.GraphBatch naming a graph per row - given the encoder output enc_h
         [B, T', H] of the forward that has just run: ctc_lo over the B T' rows on the GEMM, then ops.gtc_loss on the raw
         logits.  A row whose graph has no path of its frame count counts as 0 (zero_infinity), like ctc_nll.  The value is a
-        path sum, not a normalised probability; no gradient flows to the graph's weights."""
+        path sum, not a normalised probability; no gradient flows to the graph's weights.  `graphs` may also be the
+        gtc.DeviceGraphTable of ops.gtc_nbest_graphs."""
         if not hasattr(self, "ctc_lo"):
             raise ValueError("gtc_nll needs the CTC head: build the model with ctc_weight > 0")
         bsz, frames, hid = enc_h.shape
@@ -1160,6 +1161,22 @@ class E2E(torch.nn.Module):
         if word_lm is not None:                                  # (lexicon_only may leave an utterance without a hypothesis)
             return [u[0] if u else [] for u in ids], [u[0] if u else float("-inf") for u in scores]
         return [u[0] for u in ids], [u[0] for u in scores]
+
+    def ctc_beams_on_device(self, xs, ilens, topk, *, ngram=None, ngram_weight=0.0, ngram_bonus=0.0):
+        """recognize_ctc_beams without its host read (not a reference method): encoder, the head, ops.ctc_beam
+        with beam width topk (with ngram inside, as there) -> (hyp int32 [B, topk, T'], hyp_len int32 [B, topk], score fp32
+        [B, topk]) on the device, for ops.gtc_nbest_graphs.  Nothing is read back."""
+        K = self._beam_width(topk)
+        self.decoder.check_ngram(ngram)
+        with torch.no_grad():
+            logits, lens_dev, _ = self._ctc_logits(xs, ilens, "ctc_beams_on_device")
+            if ngram is None:
+                beams = ops.ctc_beam(logits, lens_dev, K)
+            else:
+                beams = ops.ctc_beam(logits, lens_dev, K, ngram=ngram, ngram_weight=ngram_weight, ngram_bonus=ngram_bonus,
+                                     eos_term=True)
+        self.last_ctc_beams = tuple(beams)
+        return beams[0], beams[1], beams[2]
 
     def word_lm_score(self, word_lm, ids, eos_term=True):
         """The word LM's log-probability (ops.word_lm_score) of hypotheses this model produced, to rescore any

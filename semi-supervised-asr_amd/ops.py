@@ -1121,16 +1121,51 @@ def gtc_loss(logits, frame_lens_dev, graphs, zero_infinity=True):
     paths of the row's frame count - not a normalised probability: the weights are any log numbers, and two paths may spell
     the same tokens.  A row with no path of finite score, or without frames, counts as 0 with zero_infinity and as +inf
     without; its gradient is zero either way.  No gradient flows to the arc, start or final weights.  UnsupportedShape for a
-    graph above hb.GTC_MAX_NODES nodes, ValueError where the graphs do not fit the batch."""
+    graph above hb.GTC_MAX_NODES nodes, ValueError where the graphs do not fit the batch.
+    `graphs` may also be the gtc.DeviceGraphTable of gtc_nbest_graphs, one graph per row: whether it fits
+    the call is decided from its host-known V and row count, nothing of it is read back."""
     import gtc
-    if not isinstance(graphs, (gtc.Graph, gtc.GraphBatch)):
-        raise ValueError("gtc_loss: graphs must be a gtc.Graph or a gtc.GraphBatch, got %r" % type(graphs).__name__)
+    if not isinstance(graphs, (gtc.Graph, gtc.GraphBatch, gtc.DeviceGraphTable)):
+        raise ValueError("gtc_loss: graphs must be a gtc.Graph, a gtc.GraphBatch or a gtc.DeviceGraphTable, got %r"
+                         % type(graphs).__name__)
     B, _, V = logits.shape
     if graphs.V != V:
         raise ValueError("gtc_loss: the graphs are over %d tokens, the logits over %d" % (graphs.V, V))
     if isinstance(graphs, gtc.GraphBatch) and graphs.graph_of.size != B:
         raise ValueError("gtc_loss: the batch lists a graph for %d utterances, the call has %d" % (graphs.graph_of.size, B))
+    if isinstance(graphs, gtc.DeviceGraphTable) and graphs.G != B:
+        raise ValueError("gtc_loss: the table holds a graph for %d utterances, the call has %d" % (graphs.G, B))
     return _GtcLoss.apply(logits, frame_lens_dev, graphs.to(logits.device), zero_infinity)
+
+
+def gtc_nbest_graphs(hyp, hyp_len, score, V, temperature=1.0):
+    """-> gtc.DeviceGraphTable: the n-best list of ctc_beam - hyp int32 [B, K, L] padded with -1, hyp_len int32 [B, K] with -1
+    in dead slots, score fp32 [B, K] with -inf in dead slots, all on the device - compiled into one prefix-tree graph per row
+    on the device (asr_nbest_gtc_f32, csrc/gtc_nbest.hip; two launches, no host synchronisation).  For every row
+    the table holds what gtc.Graph.from_nbest and the host compiler make of the same list, element for element, with the
+    log-softmax of temperature * score over the row's live slots as weights (gtc.nbest_weights, float64 on the device); a row
+    without a live slot gets the empty hypothesis at weight 0.  A tree above 1023 trie nodes cannot raise on the device:
+    hypotheses are admitted in rank order while the tree fits, the first that does not and every slot behind it are dropped
+    and the weights renormalised over the admitted ones.  The table carries .dropped int32 [B] (live slots lost) and
+    .log_weights float64 [B, K] (-inf in dead and dropped slots) as device tensors and goes to gtc_loss / E2E.gtc_nll as it
+    is.  The tokens of live hypotheses are trusted to lie in 1 .. V-1, as ctc_beam writes them.  ValueError for a
+    temperature that is negative or not finite; UnsupportedShape for K above hb.BEAM_KMAX."""
+    import gtc
+    t = float(temperature)
+    if not (0.0 <= t < float("inf")):
+        raise ValueError("gtc_nbest_graphs: the temperature must be finite and >= 0, got %r" % (temperature,))
+    if hyp.dim() != 3 or tuple(hyp_len.shape) != tuple(hyp.shape[:2]) or tuple(score.shape) != tuple(hyp.shape[:2]):
+        raise ValueError("gtc_nbest_graphs: hyp [B, K, L] with hyp_len and score [B, K], got %s, %s, %s"
+                         % (tuple(hyp.shape), tuple(hyp_len.shape), tuple(score.shape)))
+    B, K, L = hyp.shape
+    dev = hyp.device
+    cap_nodes, cap_arcs, ws_bytes = hb.gtc_nbest_bytes(B, K, L, int(V))
+    table = gtc.DeviceGraphTable(int(V), B, cap_nodes, cap_arcs, dev)
+    table.log_weights = torch.empty(B, K, device=dev, dtype=torch.float64)
+    table.dropped = torch.empty(B, device=dev, dtype=torch.int32)
+    ws = torch.empty((ws_bytes + 3) // 4, device=dev, dtype=torch.int32)
+    hb.gtc_nbest(hyp.contiguous(), hyp_len.contiguous(), score.contiguous(), t, table, table.log_weights, table.dropped, ws)
+    return table
 
 
 def _label_offsets(what, label_lens, B, n_labels=None):

@@ -1384,9 +1384,10 @@ class Solver(object):
         when it is configured: ngram is (path, weight, bonus) or None.  ValueError: a beam outside 2..16, a temperature or
         weight that is negative or not finite, no epochs, another pseudo key or an n-gram weight without what it belongs to,
         `word_lm` (the search of the pseudo-labels has no place for it), a model without the CTC head, more than one
-        process."""
+        process.  `pseudo_graphs_on_gpu` is read by its own accessor (pseudo_graphs_on_gpu); without pseudo_beam it raises
+        here like the other pseudo keys."""
         if config.get("pseudo_beam") is None:
-            for key in Solver.PSEUDO_KEYS[1:]:
+            for key in Solver.PSEUDO_KEYS[1:] + ("pseudo_graphs_on_gpu",):
                 if config.get(key) is not None:
                     raise ValueError("%s is set without pseudo_beam, the width of the n-best search it belongs to" % key)
             return None
@@ -1416,6 +1417,16 @@ class Solver(object):
             raise ValueError("pseudo-label training runs in one process: data-parallel pseudo-labelling (world size %d) is "
                              "not supported" % world)
         return K, temp, weight, epochs, ngram
+
+    @staticmethod
+    def pseudo_graphs_on_gpu(config):
+        """The key `pseudo_graphs_on_gpu` (not a reference key; absent or false = off) -> bool: with it the
+        pseudo-label step builds its graphs on the device (ops.gtc_nbest_graphs) and reads nothing back.  It belongs to
+        `pseudo_beam`: ValueError without it, as for the other pseudo keys (pseudo_config raises the same)."""
+        on = config.get("pseudo_graphs_on_gpu")
+        if on is not None and config.get("pseudo_beam") is None:
+            raise ValueError("pseudo_graphs_on_gpu is set without pseudo_beam, the width of the n-best search it belongs to")
+        return bool(on)
 
     def _pseudo_ngram(self, spec):
         """The NgramLM of the pseudo-label search as _ctc_beams takes it, loaded once."""
@@ -1464,14 +1475,30 @@ class Solver(object):
         (pseudo_graphs), then the encoder in training mode, loss = pseudo_weight * mean E2E.gtc_nll - plus, with lab =
         (xs, ilens, ys), the supervised loss of that labeled batch - through the step every other loop takes (_step).
         -> (loss, mean graph CTC loss) as StepScalars; self.last_pseudo keeps the graphs, id lists and log weights of the
-        call.  The host read of the n-best list is deliberate: the graph is compiled on the host."""
+        call.  That path reads the n-best list to the host and compiles the graphs there.  With `pseudo_graphs_on_gpu` (DESIGN
+        4.37) the list stays on the device: E2E.ctc_beams_on_device, ops.gtc_nbest_graphs, then the same step on that table -
+        no host read between entry and _step; self.last_pseudo then keeps device tensors: hyp, hyp_len, score, log_weights,
+        dropped, and the table under graphs."""
         ps = self.pseudo_config(self.config, self.world, hasattr(self.model, "ctc_lo"))
         if ps is None:
             raise ValueError("pseudo_train_one_iteration needs `pseudo_beam` in the configuration")
         K, temperature, weight, _, ngram_spec = ps
         xs, ilens, _, _ = parallel.shard_batch(unlab_xs, unlab_ilens, None, 0, 1)    # (a one-process LocalShard passes through)
-        batch, ids, logw = self.pseudo_graphs(xs, ilens, K, temperature, self._pseudo_ngram(ngram_spec))
-        self.last_pseudo = dict(graphs=batch, ids=ids, log_weights=logw)
+        if self.pseudo_graphs_on_gpu(self.config):
+            was_training = self.model.training
+            self.model.eval()
+            try:
+                with torch.no_grad():
+                    hyp, hyp_len, score = self.model.ctc_beams_on_device(xs, ilens, K,
+                                                                         **self._lm_kwargs(self._pseudo_ngram(ngram_spec)))
+                    batch = ops.gtc_nbest_graphs(hyp, hyp_len, score, self.model.ctc_lo.out_features, temperature)
+            finally:
+                self.model.train(was_training)
+            self.last_pseudo = dict(graphs=batch, hyp=hyp, hyp_len=hyp_len, score=score, log_weights=batch.log_weights,
+                                    dropped=batch.dropped)
+        else:
+            batch, ids, logw = self.pseudo_graphs(xs, ilens, K, temperature, self._pseudo_ngram(ngram_spec))
+            self.last_pseudo = dict(graphs=batch, ids=ids, log_weights=logw)
 
         def make_local():
             enc_h, _ = self.model.encoder(xs, ilens)
